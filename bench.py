@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the FTE hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (W steps), times exactly K steps, writes the last step's outputs with --dump-outputs and prints
+the result line (value, ms_per_step).  --full adds what the headline does not need: the same K steps launched eagerly
+with per-kernel events (roofline, kernel_ms_per_step), the secondary configurations and the CPU baseline.
 
 N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run (RANK / WORLD_SIZE in the environment) the ranks
 are taken as given; started as a plain `python bench.py --gpus N` the script launches its own N ranks (self_launch()) and
@@ -47,6 +51,7 @@ ALG_BYTES_STEP = 3600.0             # compulsory bytes / frame / iteration (dete
 FP64_PEAK_TFLOPS = 78.6             # MI355X FP64 vector = matrix peak (AMD datasheet)
 HBM_PEAK_GBS = 8000.0
 PROFILE_DIR = "round6"        # profiles/<dir>/pmc_*.json: quoted only when their build_id matches the loaded library
+OUTPUT_BUDGET_BYTES = 60 * 10**6    # --dump-outputs: array bytes in all (the files, headers included, stay under 64 MB)
 
 
 def _log(msg):
@@ -508,6 +513,20 @@ def _emit(obj):
     out.flush()
 
 
+def dump_outputs(path, ctx, st):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of the context receives it
+    (FTEContext.result() and the LM cost), float64, one <path>/<name>.npy each.  At most OUTPUT_BUDGET_BYTES in all: a longer
+    sequence is sampled at a fixed, seeded set of frames, whose indices frames.npy holds."""
+    os.makedirs(path, exist_ok=True)
+    x, pos, dx, ddx = (a.cpu().numpy() for a in ctx.result())
+    n = x.shape[0]
+    keep = OUTPUT_BUDGET_BYTES // (x[0].nbytes + pos[0].nbytes + dx[0].nbytes + ddx[0].nbytes + 8)
+    frames = np.arange(n) if n <= keep else np.sort(np.random.default_rng(20210313).choice(n, keep, replace=False))
+    arrays = dict(x=x[frames], positions=pos[frames], dx=dx[frames], ddx=ddx[frames], cost=np.array([st["cost"]]), frames=frames)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -597,9 +616,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=N_FRAMES)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the headline is their median")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config-2 / solve-to-tolerance extras")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed blocks of --steps steps; the headline is their median (default 1: exactly --steps timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the eagerly launched profiled steps (roofline, per-kernel times, collectives), "
+                         "the secondary configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (x, positions, dx, ddx, cost) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the config-2 / solve-to-tolerance extras")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly in the timed region")
     ap.add_argument("--dry-run", action="store_true", help="launch, rendezvous, one collective and the JSON line only (no GPU work)")
     ap.add_argument("--shard", choices=("both", "windows", "separators", "replicas"), default="both",
@@ -615,6 +640,8 @@ def main():
     ap.add_argument("--refine-sweeps", type=int, default=None, help="block-Jacobi sweeps over the dropped couplings")
     ap.add_argument("--chunk-nodes", type=int, default=0, help="nodes per run of the chunked solver (0 auto, -1 whole-chain BCR)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs writes the single-GPU solve's outputs: use it with --gpus 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -743,7 +770,7 @@ def main():
                 _log(f"driver {kind}")
             pre[kind] = time_other_driver(kind)
         windows = pre["windows"]["value"] > pre["separators"]["value"]
-    if world > 1 and args.shard in ("both", "replicas"):
+    if world > 1 and (args.shard == "replicas" or (args.shard == "both" and args.full)):
         if rank == 0:
             _log("replicas")
         replicas = time_replicas()
@@ -805,7 +832,7 @@ def main():
         if rank == 0:
             _log("timed region")
         # ---- timed region: blocks of exactly K steps, each bracketed by barrier + synchronise; the headline is the MEDIAN
-        #      block (a block is 11 ms at K = 20: a single one wanders by +-2 % from box to box and run to run) -----------
+        #      block (--repeats; one block by default, so that K is the number of timed steps) -----------
         block_dt = []
         for _rep in range(args.repeats):
             t0 = time.perf_counter()
@@ -813,90 +840,45 @@ def main():
                 solver.step()
             sync()
             block_dt.append(time.perf_counter() - t0)
-        # ---- the same K steps again, launched eagerly with HIP events around every kernel (events cannot be
-        #      recorded inside a captured graph); kernel durations do not depend on how they were launched ----
-        solver.set_x(x0_local)            # same start, same LM trajectory as the timed region
-        for _ in range(args.warmup):
-            solver.step()
-        sync()
-        if windows:
-            solver.enable_graph(False)    # (events cannot be recorded inside the driver's captured phases either)
-        ctx.profile_begin()
-        solver.collect_timing(True)       # N > 1: HIP events around the collectives of every step
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            solver.step()
-        sync()
-        dt_eager = time.perf_counter() - t1
-        prof = ctx.profile_end()
-        coll = solver.timing_summary()
-        solver.collect_timing(False)
+        st = ctx.state()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, ctx, st)
+        if args.full:
+            # ---- the same K steps again, launched eagerly with HIP events around every kernel (events cannot be
+            #      recorded inside a captured graph); kernel durations do not depend on how they were launched ----
+            solver.set_x(x0_local)            # same start, same LM trajectory as the timed region
+            for _ in range(args.warmup):
+                solver.step()
+            sync()
+            if windows:
+                solver.enable_graph(False)    # (events cannot be recorded inside the driver's captured phases either)
+            ctx.profile_begin()
+            solver.collect_timing(True)       # N > 1: HIP events around the collectives of every step
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                solver.step()
+            sync()
+            dt_eager = time.perf_counter() - t1
+            prof = ctx.profile_end()
+            coll = solver.timing_summary()
+            solver.collect_timing(False)
     tmax = torch.tensor(block_dt, dtype=torch.float64, device="cuda" if backend == "nccl" or world == 1 else "cpu")
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)          # every block: the slowest rank's time
     block_dt = [float(v) for v in tmax.tolist()]
     dt = float(np.median(block_dt))
-    st = ctx.state()
     assert st["status"] != 7, "the timed steps were refused by the truncation check: not a valid measurement"
 
     if rank == 0:
         n_loc = n1 - n0
         ms_step = 1e3 * dt / args.steps
         value = args.frames * args.steps / dt
-        dom = max(PHASE_OF, key=lambda k: prof[k]["ms"])            # the kernel with the largest summed launch time
-        launches = max(prof[dom]["launches"], 1)
-        avg_ms = prof[dom]["ms"] / launches
-        phase = PHASE_OF[dom]
-        total_units = (n_loc if phase == "assemble" else (n_loc + 2) // 3) * args.steps
-        share = prof[dom]["units"] / max(total_units, 1)             # of the chain's nodes (frames for assemble)
-        flops_per_launch = ALG_FLOPS[phase] * n_loc * args.steps * share / launches
-        achieved = flops_per_launch / (max(avg_ms, 1e-9) * 1e-3) / 1e12
-        gpu_ms_step = sum(v["ms"] for v in prof.values()) / args.steps
-        kname = fte.FTEContext.PROF_KERNELS[dom]
-        # HBM bytes / launch and matrix-core counters of the dominant kernel: from the committed PMC passes under
-        # profiles/ (counters need their own rocprofv3 runs) - quoted ONLY when that summary was measured on this very
-        # binary (build_id = hash over all HIP sources, embedded in the .so); otherwise null, never a stale number
-        traffic, mfma, pmc_note = None, None, None
-        per_kernel = None
-        try:
-            from acinoset_amd import _lib
-            pdir = os.path.join(ROOT, "profiles", PROFILE_DIR)
-            tj = json.load(open(os.path.join(pdir, "pmc_traffic.json")))
-            mj = json.load(open(os.path.join(pdir, "pmc_mfma_lds.json")))
-            bid = _lib.built_id()
-            if tj.get("build_id") != bid or mj.get("build_id") != bid:
-                pmc_note = (f"profiles/{PROFILE_DIR} was measured on build {tj.get('build_id')}, this library is {bid}: "
-                            "traffic / pmc not quoted")
-            elif args.frames == N_FRAMES and world == 1:
-                traffic = tj["kernels"]["acino::" + kname]["bytes_per_launch"]
-                mk = mj["kernels"]["acino::" + kname]
-                mfma = dict(mfma_f64_flops_executed_per_launch=mk["mfma_f64_flops_per_launch"],
-                            mfma_util_percent=mk["mfma_util_percent"], lds_bank_conflict_rate=mk["lds_bank_conflict_rate"])
-                # per kernel: executed / algorithmic flops and measured / algorithmic bytes (regressions show up here)
-                per_kernel = {}
-                for cls, kn in fte.FTEContext.PROF_KERNELS.items():
-                    full = "acino::" + kn
-                    if full not in tj["kernels"] or prof[cls]["launches"] == 0:
-                        continue
-                    lps = prof[cls]["launches"] / args.steps
-                    ent = dict(launches_per_step=lps, hbm_bytes_per_step=tj["kernels"][full]["bytes_per_launch"] * lps)
-                    if full in mj["kernels"]:
-                        ent["mfma_flops_executed_per_step"] = mj["kernels"][full]["mfma_f64_flops_per_launch"] * lps
-                        ent["mfma_util_percent"] = mj["kernels"][full]["mfma_util_percent"]
-                    per_kernel[cls] = ent
-                hbm_step = sum(v["hbm_bytes_per_step"] for v in per_kernel.values())
-                exe_step = sum(v.get("mfma_flops_executed_per_step", 0.0) for v in per_kernel.values())
-                per_kernel["_step"] = dict(hbm_bytes=hbm_step, hbm_over_algorithmic=hbm_step / (ALG_BYTES_STEP * args.frames),
-                                           mfma_flops_executed=exe_step,
-                                           mfma_executed_over_algorithmic_solve=exe_step / ((ALG_FLOPS["elim"] + ALG_FLOPS["update"] +
-                                                                                             ALG_FLOPS["backsub"]) * args.frames))
-        except Exception as exc:
-            pmc_note = f"no PMC summary quoted ({exc!r})"
         out = {
             "metric": "FTE frames/sec (residual+Jac+LM step), 6-cam x 20-joint",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "timing": {"what": f"median of {len(block_dt)} blocks of {args.steps} steps, each bracketed by barrier + synchronise",
+            "timing": {"what": (f"one block of {args.steps} steps" if len(block_dt) == 1 else
+                                f"median of {len(block_dt)} blocks of {args.steps} steps") + ", each bracketed by barrier + synchronise",
                        "ms_per_step_blocks": [1e3 * v / args.steps for v in block_dt],
                        "ms_per_step_min": 1e3 * min(block_dt) / args.steps, "ms_per_step_max": 1e3 * max(block_dt) / args.steps},
             "dtype": "f64", "data": "synthetic",
@@ -913,21 +895,6 @@ def main():
                        "parallelism": (f"frames sharded x{world}, " + (f"overlapping windows (halo {args.halo} frames), 2 all-gathers / step"
                                                                         if windows else "separator system, 1 all-reduce + 2 all-gathers / step"))
                        if world > 1 else "single GPU"},
-            "roofline": {"bound": "mfma", "kernel": kname,
-                         "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic,
-                         "launches_per_step": launches / args.steps, "avg_launch_ms": avg_ms,
-                         "algorithmic_flops_per_launch": flops_per_launch,
-                         "share_of_phase": {"phase": phase, "nodes_or_frames": share},
-                         "pmc": mfma, "pmc_note": pmc_note, "per_kernel": per_kernel,
-                         "step": {"achieved_tflops": ALG_FLOPS_STEP * n_loc / (ms_step * 1e-3) / 1e12,
-                                  "frac_fp64": ALG_FLOPS_STEP * n_loc / (ms_step * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
-                                  "achieved_hbm_gbs": ALG_BYTES_STEP * n_loc / (ms_step * 1e-3) / 1e9,
-                                  "frac_hbm": ALG_BYTES_STEP * n_loc / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                  "gpu_kernel_ms_per_step": gpu_ms_step,
-                                  "launch": "eager" if args.no_graph else ("hipGraph replay" if world == 1 else ("2 graph phases + 2 all-gathers" if windows else "4 hipGraph phases + 3 collectives")),
-                                  "ms_per_step_eager_with_events": 1e3 * dt_eager / args.steps},
-                         "kernel_ms_per_step": {k: v["ms"] / args.steps for k, v in prof.items()}},
             "lm_state": {k: st[k] for k in ("cost", "iter", "accepted", "lam", "status_name", "trunc_eps")},
         }
         if world > 1:
@@ -937,27 +904,93 @@ def main():
                               "chosen": "the faster of the two sharded drivers in their own timed runs" if pre else f"--shard {args.shard}",
                               "separators": pre.get("separators"), "windows": pre.get("windows"),
                               "replicas": replicas, "modelled_on_one_gpu": _shard_model_figures(world, args.halo, args.frames)}
-            out["collectives"] = {"backend": "RCCL (torch.distributed nccl)" if backend == "nccl" else backend,
-                                  "per_step": coll,
-                                  "payload_bytes": ({"all_gather_edge_slabs": world * 2 * (args.halo + 3) * 25 * 8, "all_gather_scalars": world * 8 * 8}
-                                                    if windows else
-                                                    {"all_reduce_separators": (world - 1) * (2 * 80 * 80 + 80) * 8,
-                                                     "all_gather_edges": world * 6 * 25 * 8, "all_gather_scalars": world * 8 * 8}),
-                                  "note": "rank 0's HIP-event time around each collective on the launch stream (includes "
-                                          "waiting for the slowest rank); kernel_ms_per_step above is rank 0's shard"}
-        if world == 1 and not args.no_secondary:
-            out["secondary"] = secondary_metrics(det, rig, seq["Ts"])
-            # time to solution, first class beside the per-iteration headline (what an inexact step must answer to)
-            out["end_to_end"] = {k: out["secondary"][k] for k in ("solve_10k_frames", "config3_solve_1k_frames",
-                                                                   "skeleton_fte_human_real_detections") if k in out["secondary"]}
-        if not args.no_cpu_baseline and world == 1:
-            _log("cpu baseline (oracle on the host cores)")
-            out["cpu_baseline"] = cpu_baseline(det, rig, seq["Ts"], x0_full)
-            _log("done")
-        elif world > 1:
-            out["cpu_baseline"] = None
-        if world == 1:
+        else:
             out["world"], out["backend"], out["devices_seen"] = 1, None, devices_seen
+        if args.full:
+            dom = max(PHASE_OF, key=lambda k: prof[k]["ms"])            # the kernel with the largest summed launch time
+            launches = max(prof[dom]["launches"], 1)
+            avg_ms = prof[dom]["ms"] / launches
+            phase = PHASE_OF[dom]
+            total_units = (n_loc if phase == "assemble" else (n_loc + 2) // 3) * args.steps
+            share = prof[dom]["units"] / max(total_units, 1)             # of the chain's nodes (frames for assemble)
+            flops_per_launch = ALG_FLOPS[phase] * n_loc * args.steps * share / launches
+            achieved = flops_per_launch / (max(avg_ms, 1e-9) * 1e-3) / 1e12
+            gpu_ms_step = sum(v["ms"] for v in prof.values()) / args.steps
+            kname = fte.FTEContext.PROF_KERNELS[dom]
+            # HBM bytes / launch and matrix-core counters of the dominant kernel: from the committed PMC passes under
+            # profiles/ (counters need their own rocprofv3 runs) - quoted ONLY when that summary was measured on this very
+            # binary (build_id = hash over all HIP sources, embedded in the .so); otherwise null, never a stale number
+            traffic, mfma, pmc_note = None, None, None
+            per_kernel = None
+            try:
+                from acinoset_amd import _lib
+                pdir = os.path.join(ROOT, "profiles", PROFILE_DIR)
+                tj = json.load(open(os.path.join(pdir, "pmc_traffic.json")))
+                mj = json.load(open(os.path.join(pdir, "pmc_mfma_lds.json")))
+                bid = _lib.built_id()
+                if tj.get("build_id") != bid or mj.get("build_id") != bid:
+                    pmc_note = (f"profiles/{PROFILE_DIR} was measured on build {tj.get('build_id')}, this library is {bid}: "
+                                "traffic / pmc not quoted")
+                elif args.frames == N_FRAMES and world == 1:
+                    traffic = tj["kernels"]["acino::" + kname]["bytes_per_launch"]
+                    mk = mj["kernels"]["acino::" + kname]
+                    mfma = dict(mfma_f64_flops_executed_per_launch=mk["mfma_f64_flops_per_launch"],
+                                mfma_util_percent=mk["mfma_util_percent"], lds_bank_conflict_rate=mk["lds_bank_conflict_rate"])
+                    # per kernel: executed / algorithmic flops and measured / algorithmic bytes (regressions show up here)
+                    per_kernel = {}
+                    for cls, kn in fte.FTEContext.PROF_KERNELS.items():
+                        full = "acino::" + kn
+                        if full not in tj["kernels"] or prof[cls]["launches"] == 0:
+                            continue
+                        lps = prof[cls]["launches"] / args.steps
+                        ent = dict(launches_per_step=lps, hbm_bytes_per_step=tj["kernels"][full]["bytes_per_launch"] * lps)
+                        if full in mj["kernels"]:
+                            ent["mfma_flops_executed_per_step"] = mj["kernels"][full]["mfma_f64_flops_per_launch"] * lps
+                            ent["mfma_util_percent"] = mj["kernels"][full]["mfma_util_percent"]
+                        per_kernel[cls] = ent
+                    hbm_step = sum(v["hbm_bytes_per_step"] for v in per_kernel.values())
+                    exe_step = sum(v.get("mfma_flops_executed_per_step", 0.0) for v in per_kernel.values())
+                    per_kernel["_step"] = dict(hbm_bytes=hbm_step, hbm_over_algorithmic=hbm_step / (ALG_BYTES_STEP * args.frames),
+                                               mfma_flops_executed=exe_step,
+                                               mfma_executed_over_algorithmic_solve=exe_step / ((ALG_FLOPS["elim"] + ALG_FLOPS["update"] +
+                                                                                                 ALG_FLOPS["backsub"]) * args.frames))
+            except Exception as exc:
+                pmc_note = f"no PMC summary quoted ({exc!r})"
+            out["roofline"] = {"bound": "mfma", "kernel": kname,
+                               "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic,
+                               "launches_per_step": launches / args.steps, "avg_launch_ms": avg_ms,
+                               "algorithmic_flops_per_launch": flops_per_launch,
+                               "share_of_phase": {"phase": phase, "nodes_or_frames": share},
+                               "pmc": mfma, "pmc_note": pmc_note, "per_kernel": per_kernel,
+                               "step": {"achieved_tflops": ALG_FLOPS_STEP * n_loc / (ms_step * 1e-3) / 1e12,
+                                        "frac_fp64": ALG_FLOPS_STEP * n_loc / (ms_step * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
+                                        "achieved_hbm_gbs": ALG_BYTES_STEP * n_loc / (ms_step * 1e-3) / 1e9,
+                                        "frac_hbm": ALG_BYTES_STEP * n_loc / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                        "gpu_kernel_ms_per_step": gpu_ms_step,
+                                        "launch": "eager" if args.no_graph else ("hipGraph replay" if world == 1 else ("2 graph phases + 2 all-gathers" if windows else "4 hipGraph phases + 3 collectives")),
+                                        "ms_per_step_eager_with_events": 1e3 * dt_eager / args.steps},
+                               "kernel_ms_per_step": {k: v["ms"] / args.steps for k, v in prof.items()}}
+            if world > 1:
+                out["collectives"] = {"backend": "RCCL (torch.distributed nccl)" if backend == "nccl" else backend,
+                                      "per_step": coll,
+                                      "payload_bytes": ({"all_gather_edge_slabs": world * 2 * (args.halo + 3) * 25 * 8, "all_gather_scalars": world * 8 * 8}
+                                                        if windows else
+                                                        {"all_reduce_separators": (world - 1) * (2 * 80 * 80 + 80) * 8,
+                                                         "all_gather_edges": world * 6 * 25 * 8, "all_gather_scalars": world * 8 * 8}),
+                                      "note": "rank 0's HIP-event time around each collective on the launch stream (includes "
+                                              "waiting for the slowest rank); kernel_ms_per_step above is rank 0's shard"}
+            if world == 1 and not args.no_secondary:
+                out["secondary"] = secondary_metrics(det, rig, seq["Ts"])
+                # time to solution, first class beside the per-iteration headline (what an inexact step must answer to)
+                out["end_to_end"] = {k: out["secondary"][k] for k in ("solve_10k_frames", "config3_solve_1k_frames",
+                                                                       "skeleton_fte_human_real_detections") if k in out["secondary"]}
+            if not args.no_cpu_baseline and world == 1:
+                _log("cpu baseline (oracle on the host cores)")
+                out["cpu_baseline"] = cpu_baseline(det, rig, seq["Ts"], x0_full)
+                _log("done")
+            elif world > 1:
+                out["cpu_baseline"] = None
         _emit(out)
     if world > 1:
         dist.barrier()

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/waits; rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp; cd /tmp
-B="python $R/bench.py --no-cpu-baseline --no-secondary --steps 3 --warmup 1"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary --steps 3 --warmup 1"
 timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM --output-format csv -d $OUT/p1 -o p1 -- $B > /dev/null 2> $OUT/p1.err
 timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS SQ_INSTS_MFMA --output-format csv -d $OUT/p2 -o p2 -- $B > /dev/null 2> $OUT/p2.err
 cd $R

@@ -44,7 +44,7 @@ for cn, ks in sorted(acc.items()):
 csv.writer(open(os.path.join(dst, "rocprofv3_pmc_by_kernel.csv"), "w")).writerows(rows)
 
 traffic = {"source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, bench.py --steps 3 --warmup 1 "
-                     "--no-secondary at 10 000 frames; FETCH_SIZE doubled (gfx950: 128-B requests tallied at 64 B)",
+                     "--full --no-secondary at 10 000 frames; FETCH_SIZE doubled (gfx950: 128-B requests tallied at 64 B)",
            "build_id": BUILD_ID, "kernels": {}}
 for k in acc.get("FETCH_SIZE", {}):
     if not k.startswith("acino::"):

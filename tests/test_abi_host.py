@@ -232,6 +232,37 @@ def test_bench_json_line_filter():
     assert bench._json_line_of("nothing here")[0] is None
 
 
+def test_bench_dump_outputs_float64_within_budget_and_seeded(tmp_path):
+    """bench.py --dump-outputs (host side): one float64 .npy per output of FTEContext.result() plus the cost; a sequence too
+    long for the budget is sampled at the same frames every run, and the files stay under 64 MB."""
+    import glob
+    import bench
+
+    class Ctx:
+        def __init__(self, n):
+            self.n = n
+
+        def result(self):
+            a = torch.arange(self.n, dtype=torch.float64)[:, None]
+            return a + torch.zeros(self.n, 25, dtype=torch.float64), a[..., None] + torch.zeros(self.n, 20, 3, dtype=torch.float64), \
+                -a + torch.zeros(self.n, 25, dtype=torch.float64), 2 * a + torch.zeros(self.n, 25, dtype=torch.float64)
+
+    small = tmp_path / "small"
+    bench.dump_outputs(str(small), Ctx(30), {"cost": 1.25})
+    names = sorted(os.path.basename(f) for f in glob.glob(str(small / "*.npy")))
+    assert names == ["cost.npy", "ddx.npy", "dx.npy", "frames.npy", "positions.npy", "x.npy"]
+    assert all(np.load(str(small / n)).dtype == np.float64 for n in names)
+    assert np.load(str(small / "positions.npy")).shape == (30, 20, 3) and np.load(str(small / "cost.npy")).tolist() == [1.25]
+    n = bench.OUTPUT_BUDGET_BYTES // (8 * (3 * 25 + 60)) + 1000
+    runs = []
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), Ctx(n), {"cost": 0.0})
+        assert sum(os.path.getsize(f) for f in glob.glob(str(tmp_path / tag / "*.npy"))) < 64e6
+        runs.append(np.load(str(tmp_path / tag / "frames.npy")))
+    assert len(runs[0]) < n and np.array_equal(runs[0], runs[1]) and np.all(np.diff(runs[0]) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "x.npy"))[:, 0], runs[0])
+
+
 def test_level_split_tables_cover_every_tile_once():
     """Fused narrow levels of the separator reduction (csrc/seplevel.hip): for every T the T workgroups of a node together
     compute each of the 55 output tiles (15 lower tiles of P_l, 15 of P_r, 25 of X) exactly once, every workgroup computes the
