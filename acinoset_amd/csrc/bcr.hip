@@ -1715,6 +1715,54 @@ void BcrSchedule::build(int n, bool pin_left, bool pin_right, int max_levels, in
     tail.clear();
     tail_levels = 0;
   }
+  backsub_tail = tail_levels > 0;
+  if (levels.empty()) consumers_add_al = false;
+  else if (fused) {     // every node is consumed by a kernel that forms D + AL + SL + SR itself - unless a wide level runs first
+    consumers_add_al = true;
+    for (const BcrLevel& lv : levels)
+      if (!lv.fused && !lv.isolated) consumers_add_al = false;
+  } else {              // every node of the chain must pass through exactly one of the two narrow-level kernels at level 0
+    consumers_add_al = !levels[0].isolated && levels[0].n_elim <= 128 && levels[0].n_remain <= 128;
+  }
+  // k_sep_tail: at most 12 levels above the isolated one (SepTailArgs), <= 128 isolated nodes, and the tags of one launch
+  // number 64 versions (sweep s: 1 + s, a node's solution: 63)
+  const int top = (int)levels.size() - 1;
+  sep_tail = refine > 0 && refine <= 60 && top <= 12 && levels[top].n_elim <= 128;
+}
+
+int BcrSchedule::sep_tail_blocks() const {
+  int n = 0;
+  for (const BcrLevel& lv : levels) n += lv.n_elim;
+  return n;
+}
+
+std::vector<int> BcrSchedule::pack() const {
+  std::vector<int> v(elim);
+  v.insert(v.end(), remain.begin(), remain.end());
+  if (backsub_tail) {
+    v.insert(v.end(), tail.begin(), tail.end());
+    v.insert(v.end(), 4, 0);
+  }
+  for (const std::vector<int>* a : {&pairs, &elim6, &iso_loc, &fold}) v.insert(v.end(), a->begin(), a->end());
+  return v;
+}
+
+void BcrSchedule::bind(int* d, BcrChain& ch) const {
+  ch.d_elim = d;
+  d += elim.size();
+  ch.d_remain = d;
+  d += remain.size();
+  ch.d_tail = backsub_tail ? d : nullptr;
+  ch.d_done = backsub_tail ? d + tail.size() : nullptr;
+  if (backsub_tail) d += tail.size() + 4;
+  ch.d_pairs = pairs.empty() ? nullptr : d;
+  ch.n_pairs = (int)(pairs.size() / 2);
+  d += pairs.size();
+  ch.d_elim6 = fused_levels ? d : nullptr;
+  d += elim6.size();
+  ch.d_iso_loc = fused_levels ? d : nullptr;
+  d += iso_loc.size();
+  ch.d_fold = fused_levels ? d : nullptr;
 }
 
 static constexpr size_t kElimLds = (MAT + BS + 8 + 18 * NP + 3 * BS) * sizeof(double);
@@ -1753,17 +1801,9 @@ int bcr_set_func_attributes() {
 }
 
 // k_sep_tail's isolated workgroups spin-wait on each other's flags, the levels above them on lower block indices: the launch
-// is only safe when ALL of its workgroups are resident at once.  blocks = workgroups the schedule would launch (0: the
-// kernel does not apply), capacity = what the current device holds of them (occupancy query x compute units - a CU-masked
-// or partitioned device, CPX mode, answers with what it really has).
-int bcr_sep_tail_fit(const BcrSchedule& sch, int* blocks, int* capacity) {
-  *blocks = 0;
-  *capacity = 0;
-  const int top = (int)sch.levels.size() - 1;
-  if (!(sch.refine > 0 && top >= 0 && sch.levels[top].isolated && top <= 12 && sch.levels[top].n_elim <= 128)) return ACINO_OK;
-  int n = 0;
-  for (int k = top; k >= 0; --k) n += sch.levels[k].n_elim;
-  *blocks = n;
+// is only safe when ALL of its workgroups are resident at once.  capacity = what the current device holds of them (occupancy
+// query x compute units - a CU-masked or partitioned device, CPX mode, answers with what it really has).
+int bcr_sep_tail_capacity(int* capacity) {
   int dev = 0, cus = 0, per_cu = 0;
   ACINO_HIP_CHECK(hipGetDevice(&dev));
   ACINO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -1802,35 +1842,16 @@ static bool dbg_check(const char* what, int level, const BcrChain& ch, const int
   return e != 0 || nan_d || nan_b;
 }
 
-bool bcr_level0_adds_al(const BcrSchedule& sch) {
-  if (sch.levels.empty() || getenv("ACINO_SEP_COMBINE")) return false;
-  if (sch.fused_levels) {      // every node is consumed by a kernel that forms D + AL + SL + SR itself
-    for (const BcrLevel& lv : sch.levels)
-      if (!lv.fused && !lv.isolated) return false;
-    return true;
-  }
-  const BcrLevel& lv = sch.levels[0];
-  // (every node of the chain must pass through exactly one of the two narrow-level kernels at level 0)
-  return !lv.isolated && lv.n_elim <= 128 && lv.n_remain <= 128;
-}
-
-// true when k_sep_tail runs the back-substitution of this chain (truncated solve, sweeps and every level above in one launch)
-static bool sep_tail_applies(const BcrChain& ch, const BcrSchedule& sch) {
-  const int top = (int)sch.levels.size() - 1;
-  return sch.refine > 0 && sch.refine <= 60 && top >= 0 && sch.levels[top].isolated && ch.refine_buf && ch.st_flags && ch.st_ll && top <= 12 &&
-         sch.levels[top].n_elim <= 128;
-}
-
-int bcr_reduce(const BcrChain& ch_in, const BcrSchedule& sch, const FteConst* d_c, int* d_numeric_err,
+int bcr_reduce(const BcrChain& ch, const BcrSchedule& sch, const FteConst* d_c, int* d_numeric_err,
                const int* d_status, hipStream_t s, Profiler* prof) {
   static const bool dbg = getenv("ACINO_DEBUG_SYNC") != nullptr;
   bool dbg_hit = false;
   int level = 0;
-  const bool fz = sch.fused_levels && ch_in.SL != nullptr;      // chain with fused narrow levels
-  BcrChain ch = ch_in;
-  const bool add_al = !fz && ch.AL0 != nullptr && bcr_level0_adds_al(sch);
+  const bool fz = sch.fused_levels;      // chain with fused narrow levels
+  // the level-0 narrow kernels add the runs' contributions (fused levels: k_sep_level and k_sep_fold read ch.AL0 themselves)
+  const double* al0 = fz ? nullptr : ch.AL0;
   for (const BcrLevel& lv : sch.levels) {
-    if (fz && lv.fused) {
+    if (lv.fused) {
       {
         ProfSpan sp(prof, PC_ELIM_DEEP, s, lv.n_elim);
         if (int rc = slv_launch_level(ch, lv, d_numeric_err, d_status, s)) return rc;
@@ -1840,13 +1861,10 @@ int bcr_reduce(const BcrChain& ch_in, const BcrSchedule& sch, const FteConst* d_
       continue;
     }
     if (fz && lv.isolated) {
-      if (sep_tail_applies(ch, sch)) break;              // k_sep_tail factors the isolated nodes itself
+      if (sch.sep_tail) break;              // k_sep_tail factors the isolated nodes itself
       // per-level kernels: materialise D + AL + SL + SR (and the couplings' home slots) for them
-      {
-        ProfSpan sp(prof, PC_SEP_COMBINE, s, lv.n_elim);
-        if (int rc = slv_launch_fold(ch, ch.d_fold + 3 * (size_t)sch.n_fold_pins, lv.n_elim, d_status, s)) return rc;
-      }
-      ch.AL0 = nullptr;
+      ProfSpan sp(prof, PC_SEP_COMBINE, s, lv.n_elim);
+      if (int rc = slv_launch_fold(ch, ch.d_fold + 3 * (size_t)sch.n_fold_pins, lv.n_elim, d_status, s)) return rc;
     }
     {
       const bool fused0 = level == 0 && ch.st != nullptr;
@@ -1873,7 +1891,7 @@ int bcr_reduce(const BcrChain& ch_in, const BcrSchedule& sch, const FteConst* d_
         const int total = lv.n_elim * (T + extra), nx = std::min(8, (total + 31) / 32), per = (total + nx - 1) / nx;
         hipLaunchKernelGGL(k_bcr_elim_deep, dim3(8 * per), dim3(256), kElimDeepLds, s, ch,
                            ch.d_elim + 3 * lv.elim_off, d_numeric_err, d_status, T, extra, nx, per, total,
-                           (level == 0 && add_al) ? ch.AL0 : (const double*)nullptr);
+                           level == 0 ? al0 : nullptr);
       } else
         hipLaunchKernelGGL(k_bcr_elim, dim3(lv.n_elim), dim3(256), kElimLds, s, ch, ch.d_elim + 3 * lv.elim_off,
                            d_c, d_numeric_err, d_status, level);
@@ -1892,7 +1910,7 @@ int bcr_reduce(const BcrChain& ch_in, const BcrSchedule& sch, const FteConst* d_
           const int total = (2 * S + 1) * lv.n_remain, nx = std::min(8, (total + 31) / 32), per = (total + nx - 1) / nx;
           hipLaunchKernelGGL(k_bcr_update_deep, dim3(8 * per), dim3(256), kUpdateDeepLds, s, ch,
                              ch.d_remain + 4 * lv.remain_off, d_status, S, nx, per, total,
-                             (level == 0 && add_al) ? ch.AL0 : (const double*)nullptr);
+                             level == 0 ? al0 : nullptr);
         } else
           hipLaunchKernelGGL(k_bcr_update, dim3(3 * lv.n_remain), dim3(256), kUpdateLds, s, ch,
                              ch.d_remain + 4 * lv.remain_off, d_c, d_status, level);
@@ -1904,7 +1922,7 @@ int bcr_reduce(const BcrChain& ch_in, const BcrSchedule& sch, const FteConst* d_
   }
   if (fz && sch.n_fold_pins > 0) {       // the pins' Schur complements, for the export
     ProfSpan sp(prof, PC_SEP_COMBINE, s, sch.n_fold_pins);
-    if (int rc = slv_launch_fold(ch_in, ch_in.d_fold, sch.n_fold_pins, d_status, s)) return rc;
+    if (int rc = slv_launch_fold(ch, ch.d_fold, sch.n_fold_pins, d_status, s)) return rc;
   }
   if (!sch.pairs.empty() && ch.d_pairs && ch.trunc_eps2 && sch.refine == 0) {
     ProfSpan sp(prof, PC_TRUNC_CHECK, s, (long long)sch.pairs.size() / 2);
@@ -1918,7 +1936,7 @@ int bcr_reduce(const BcrChain& ch_in, const BcrSchedule& sch, const FteConst* d_
 int bcr_backsub(const BcrChain& ch, const BcrSchedule& sch, const FteConst* d_c, const int* d_status, hipStream_t s,
                 Profiler* prof, int* d_numeric_err) {
   int top = (int)sch.levels.size() - 1;
-  if (sep_tail_applies(ch, sch)) {
+  if (sch.sep_tail) {
     // one launch for the truncated solve, the sweeps and every level above them (k_sep_tail)
     const BcrLevel& iso = sch.levels[top];
     SepTailArgs a;
@@ -1936,7 +1954,7 @@ int bcr_backsub(const BcrChain& ch, const BcrSchedule& sch, const FteConst* d_c,
     a.epoch = ch.st_flags + ch.n_st_flags;
     a.ll = ch.st_ll;
     a.norms = ch.trunc_eps2;
-    a.fused = (sch.fused_levels && ch.SL != nullptr) ? 1 : 0;
+    a.fused = sch.fused_levels ? 1 : 0;
     a.iso_loc = ch.d_iso_loc;
     {
       ProfSpan sp(prof, PC_REFINE, s, blocks);
@@ -1945,7 +1963,7 @@ int bcr_backsub(const BcrChain& ch, const BcrSchedule& sch, const FteConst* d_c,
     ACINO_LAUNCH_CHECK();
     return ACINO_OK;
   }
-  if (sch.refine > 0 && top >= 0 && sch.levels[top].isolated && ch.refine_buf) {
+  if (sch.refine > 0) {
     // truncated solve of the isolated nodes, then the block-Jacobi sweeps over their dropped couplings
     const BcrLevel& lv = sch.levels[top];
     const int* iso = ch.d_elim + 3 * lv.elim_off;
@@ -1979,7 +1997,7 @@ int bcr_backsub(const BcrChain& ch, const BcrSchedule& sch, const FteConst* d_c,
     }
     --top;
   }
-  if (ch.d_tail && sch.tail_levels > 0) {
+  if (sch.backsub_tail) {
     const int n_tail = (int)sch.tail.size() / 4;
     ACINO_HIP_CHECK(hipMemsetAsync(ch.d_done, 0, sizeof(int), s));
     {

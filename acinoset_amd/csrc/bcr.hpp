@@ -6,6 +6,8 @@
 
 namespace acino {
 
+struct BcrChain;
+
 struct BcrLevel {
   int n_elim, n_remain;
   int elim_off, remain_off;  // offsets (in entries) into the device schedule arrays
@@ -30,7 +32,6 @@ struct BcrSchedule {
   // DROPPED and every remaining node is factorised on its own.  pairs = (left node, right node) of every dropped
   // coupling block (stored at Cpl[left]); their normalised size is measured on the device (k_bcr_trunc_check).
   std::vector<int> pairs;
-  size_t ints() const { return elim.size() + remain.size() + tail.size() + pairs.size() + 4 + fused_ints(); }   // (+ the tail's progress counter)
   // refine > 0 (incomplete reductions only): block-Jacobi sweeps over the isolated nodes that re-introduce the dropped
   // couplings after the truncated solve (k_bcr_refine); the isolated level then stays out of the fused tail.
   int refine = 0;
@@ -47,8 +48,21 @@ struct BcrSchedule {
   // when k_sep_tail does not apply): 3 ints per entry - node, flags, location of its right coupling (copied to slot `node`; -1: none)
   std::vector<int> fold;
   int n_fold_pins = 0;        // the first n_fold_pins entries of fold are the pins, the rest the isolated level
-  size_t fused_ints() const { return elim6.size() + iso_loc.size() + fold.size(); }
+  // ---- the solve path: decided once, here and by the context (shared_gpu, the device's capacity for k_sep_tail) ----
+  // consumers_add_al: the chunk sweep's left-run contributions (BcrChain::AL0) are added by the kernels that consume each node -
+  //   with fused levels every consumer at any level, otherwise the level-0 narrow kernels; false: k_sep_combine folds them into
+  //   D / b first.  The chain value the context keeps has AL0 set exactly when this holds.
+  bool consumers_add_al = false;
+  // sep_tail: k_sep_tail runs the back-substitution (truncated solve, sweeps and every level above them in one launch)
+  bool sep_tail = false;
+  // backsub_tail: k_bcr_backsub_tail runs the deepest tail_levels levels of the back-substitution in one launch
+  bool backsub_tail = false;
   void build(int n, bool pin_left, bool pin_right, int max_levels = 0, int refine_sweeps = 0, bool fused = false);
+  int sep_tail_blocks() const;   // workgroups of k_sep_tail: every node the schedule eliminates
+  // the device format: elim, remain, (backsub_tail: tail + its progress counter), pairs, elim6, iso_loc, fold - and the chain's
+  // pointers into a copy of it at d
+  std::vector<int> pack() const;
+  void bind(int* d, BcrChain& ch) const;
 };
 
 // Device views of one chain.
@@ -61,18 +75,19 @@ struct BcrChain {
   double* Wl;    // [n][80][80] W_l of eliminated nodes
   double* Wr;    // [n][80][80] W_r of eliminated nodes
   double* b;     // [n][80] rhs -> y -> solution
-  const int* d_elim;
-  const int* d_remain;
-  const int* d_tail;         // device copy of BcrSchedule::tail (null: no fused tail)
-  int* d_done;               // progress counter of the tail kernel
+  const int* d_elim = nullptr;    // the schedule's device copy (BcrSchedule::bind)
+  const int* d_remain = nullptr;
+  const int* d_tail = nullptr;    // BcrSchedule::tail (null: backsub_tail is off)
+  int* d_done = nullptr;          // progress counter of the tail kernel
   const int* d_pairs = nullptr;   // dropped couplings of an incomplete reduction (2 ints each) ...
   int n_pairs = 0;
   double* trunc_eps2 = nullptr;   // ... and [n_pairs] squared Frobenius norms of L_b^-1 C L_a^-T, written every reduction
   double* refine_buf = nullptr;   // [3][n_isolated][80] x0 and the two iterates of the refinement sweeps
   const double* AL0 = nullptr;    // separator chain of the chunked solver: [n][80][80] left-run contributions (lower tiles; row 79:
-                                  // the update of b), added to D / b by the LEVEL-0 kernels of the reduction when set
+                                  // the update of b), added by the kernels that consume each node when set
+                                  // (BcrSchedule::consumers_add_al)
   int* st_flags = nullptr;        // k_sep_tail: [n_st_flags] flags (zeroed by the consumer of the solution), then the epoch of its
-  int n_st_flags = 0;             //             hand-off tags (null: per-level kernels)
+  int n_st_flags = 0;             //             hand-off tags
   unsigned long long* st_ll = nullptr;   // k_sep_tail: tagged word pairs, [2][n_isolated][80][2] iterates + [n][80][2] solutions
   // fused narrow levels (seplevel.hip; all null: the per-phase kernels of bcr.hip only).  With them Cpl holds 2 n blocks:
   // slot n + i = the coupling created by the elimination of node i.
@@ -80,7 +95,7 @@ struct BcrChain {
   double* SR = nullptr;           //             tiles; row 79: the update of b) / from its RIGHT side
   double* Y = nullptr;            // [n][80] y = U^T b of eliminated nodes (b itself stays intact until the back-substitution:
                                   //         the sibling workgroups of a node all read it)
-  const int* d_elim6 = nullptr;
+  const int* d_elim6 = nullptr;   // (BcrSchedule::bind)
   const int* d_iso_loc = nullptr;
   const int* d_fold = nullptr;
   int implicit_couplings;    // 1: level-0 couplings are the analytic smoothness blocks (never stored)
@@ -98,11 +113,7 @@ int bcr_reduce(const BcrChain& ch, const BcrSchedule& sch, const FteConst* d_c, 
 int bcr_backsub(const BcrChain& ch, const BcrSchedule& sch, const FteConst* d_c, const int* d_status, hipStream_t s,
                 Profiler* prof = nullptr, int* d_numeric_err = nullptr);
 int bcr_set_func_attributes();
-// the single-launch back-substitution of an incomplete reduction with refinement (k_sep_tail) needs every one of its
-// workgroups resident: blocks it would launch (0 = not applicable) and the device's capacity for them
-int bcr_sep_tail_fit(const BcrSchedule& sch, int* blocks, int* capacity);
-// true when level 0 of the schedule runs the narrow-level kernels, which can add the chunk sweep's left-run contributions
-// (BcrChain::AL0) themselves - no k_sep_combine launch
-bool bcr_level0_adds_al(const BcrSchedule& sch);
+// k_sep_tail's workgroups spin-wait on each other: the current device's capacity for them (all must be resident at once)
+int bcr_sep_tail_capacity(int* capacity);
 
 }  // namespace acino

@@ -1109,16 +1109,14 @@ int chunk_reduce(const BcrChain& ch, const ChunkPlan& pl, const SepView& sp, con
   }
   ACINO_LAUNCH_CHECK();
   if (pl.n_sep == 0) return ACINO_OK;
-  BcrChain sc = sepch;
-  sc.AL0 = nullptr;
-  if (bcr_level0_adds_al(sepsch)) {
-    sc.AL0 = sp.AL;                  // level 0 of the reduction adds the runs' contributions itself
-  } else {
-    ProfSpan span(prof, PC_SEP_COMBINE, s, pl.n_sep);
-    hipLaunchKernelGGL(k_sep_combine, dim3(pl.n_sep), dim3(256), 0, s, sp, d_status);
+  if (!sepsch.consumers_add_al) {    // (otherwise the kernels that consume each separator add its AL: sepch.AL0)
+    {
+      ProfSpan span(prof, PC_SEP_COMBINE, s, pl.n_sep);
+      hipLaunchKernelGGL(k_sep_combine, dim3(pl.n_sep), dim3(256), 0, s, sp, d_status);
+    }
+    ACINO_LAUNCH_CHECK();
   }
-  ACINO_LAUNCH_CHECK();
-  return bcr_reduce(sc, sepsch, d_c, d_numeric_err, d_status, s, prof);
+  return bcr_reduce(sepch, sepsch, d_c, d_numeric_err, d_status, s, prof);
 }
 
 int chunk_backsub(const BcrChain& ch, const ChunkPlan& pl, const SepView& sp, const BcrChain& sepch,

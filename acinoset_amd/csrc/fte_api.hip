@@ -24,13 +24,14 @@ struct Buffers {
   double* totals;     // [8]
   int* nbehind;
   int* numeric_err;
-  int* sched;         // elim (3/entry), remain (4/entry), tail (4/entry), dropped-coupling pairs (2/entry), tail counter
+  int* sched;         // BcrSchedule::pack()
   double* trunc_eps2; // [n_pairs + 1]
   double* refine_buf; // [3][n_isolated][80] (incomplete reduction with refinement sweeps)
   int* st_flags;      // [n_isolated + n_sep] flags of k_sep_tail (chunked solver with refinement), then the epoch counter
   int n_st_flags;
   unsigned long long* st_ll;   // k_sep_tail's hand-off slots (BcrChain::st_ll)
   size_t n_st_ll;
+  double* sep_al;     // chunked solver: [n_sep][80][80] the runs' contributions AL (SepView::AL; BcrChain::AL0 when consumers add it)
 };
 
 }  // namespace acino
@@ -93,13 +94,18 @@ struct Layout {
     if (plan.active()) sched.build(plan.n_sep, p->pin_left != 0, p->pin_right != 0, p->bcr_levels, p->refine_sweeps,
                                    fused_levels_enabled());
     else sched.build(chain_nodes(p), p->pin_left != 0, p->pin_right != 0, p->bcr_levels, p->refine_sweeps);
+    // the one-launch back-substitutions wait for each other's workgroups: kept off GPUs that other spin-waiting kernels may
+    // share (shared_gpu: batched clips, several ranks on one device).  k_sep_tail is the separator chain's; whether the device
+    // holds all of its workgroups is decided by acino_fte_create.
+    sched.backsub_tail = sched.backsub_tail && !p->shared_gpu;
+    sched.sep_tail = sched.sep_tail && plan.active() && !p->shared_gpu;
   }
 };
 
 static size_t carve(const acino_fte_params* p, char* base, Buffers* out, BcrChain* ch, const Layout& lay, BcrChain* sepch = nullptr) {
   Carver c{base, 0};
   const size_t N = p->n_frames, T = chain_nodes(p);
-  const size_t sched_ints = lay.sched.ints(), n_pairs = lay.sched.pairs.size() / 2;
+  const size_t sched_ints = lay.sched.pack().size(), n_pairs = lay.sched.pairs.size() / 2;
   const bool chunked = lay.plan.active();
   Buffers b;
   b.cst = c.take<FteConst>(1);
@@ -124,7 +130,7 @@ static size_t carve(const acino_fte_params* p, char* base, Buffers* out, BcrChai
   b.n_st_flags = 0;
   b.st_ll = nullptr;
   b.n_st_ll = 0;
-  if (lay.sched.refine > 0 && chunked) {
+  if (lay.sched.sep_tail) {
     b.n_st_flags = lay.sched.levels.back().n_elim + lay.plan.n_sep;
     b.st_flags = c.take<int>((size_t)b.n_st_flags + 2);
     b.n_st_ll = (2 * (size_t)lay.sched.levels.back().n_elim + (size_t)lay.plan.n_sep) * BS * 2;
@@ -138,12 +144,6 @@ static size_t carve(const acino_fte_params* p, char* base, Buffers* out, BcrChai
   chn.Wl = c.take<double>(chunked ? T * BS : T * BS * BS);   // chunked: f_k = F_k x_L of the interior nodes, [80] each
   chn.Wr = chunked ? nullptr : c.take<double>(T * BS * BS);
   chn.b = c.take<double>(T * BS);
-  chn.d_elim = nullptr;
-  chn.d_remain = nullptr;
-  chn.d_tail = nullptr;
-  chn.d_done = nullptr;
-  chn.d_pairs = nullptr;
-  chn.n_pairs = 0;
   chn.trunc_eps2 = b.trunc_eps2;
   chn.implicit_couplings = 1;
   chn.dbg = nullptr;
@@ -153,6 +153,7 @@ static size_t carve(const acino_fte_params* p, char* base, Buffers* out, BcrChai
   chn.H0 = b.H[0]; chn.H1 = b.H[1];
   chn.gn_part = b.gn_part;
   BcrChain sc = chn;
+  b.sep_al = nullptr;
   if (chunked) {
     const size_t S = lay.plan.n_sep > 0 ? lay.plan.n_sep : 1;
     sc.n_nodes = lay.plan.n_sep;
@@ -168,7 +169,8 @@ static size_t carve(const acino_fte_params* p, char* base, Buffers* out, BcrChai
       sc.SR = c.take<double>(S * BS * BS);
       sc.Y = c.take<double>(S * BS);
     }
-    sc.AL0 = c.take<double>(S * BS * BS);   // (the sweep's left-run contributions; handed to the reduction by chunk_reduce)
+    b.sep_al = c.take<double>(S * BS * BS);
+    sc.AL0 = lay.sched.consumers_add_al ? b.sep_al : nullptr;   // (otherwise k_sep_combine folds AL into D / b: chunk_reduce)
     sc.implicit_couplings = 0;      // dense couplings, plain (non-fused) kernels
     sc.st = nullptr;
     sc.x0 = sc.x1 = sc.g0 = sc.g1 = sc.H0 = sc.H1 = nullptr;
@@ -742,37 +744,16 @@ int acino_fte_create(acino_fte_ctx** out, const acino_fte_params* p, const doubl
   if (e == hipSuccess) e = hipMemsetAsync(ctx->b.nbehind, 0, 4 * sizeof(int), s);
   if (e == hipSuccess) e = hipMemsetAsync(ctx->b.x[0], 0, sizeof(double) * (p->n_frames + 2 * HALO) * NP, s);
   if (e == hipSuccess) e = hipMemsetAsync(ctx->b.x[1], 0, sizeof(double) * (p->n_frames + 2 * HALO) * NP, s);
-  if (e == hipSuccess && !ctx->sched.elim.empty())
-    e = hipMemcpyAsync(ctx->b.sched, ctx->sched.elim.data(), sizeof(int) * ctx->sched.elim.size(),
-                       hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && !ctx->sched.remain.empty())
-    e = hipMemcpyAsync(ctx->b.sched + ctx->sched.elim.size(), ctx->sched.remain.data(),
-                       sizeof(int) * ctx->sched.remain.size(), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && !ctx->sched.tail.empty())
-    e = hipMemcpyAsync(ctx->b.sched + ctx->sched.elim.size() + ctx->sched.remain.size(), ctx->sched.tail.data(),
-                       sizeof(int) * ctx->sched.tail.size(), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && !ctx->sched.pairs.empty())
-    e = hipMemcpyAsync(ctx->b.sched + ctx->sched.elim.size() + ctx->sched.remain.size() + ctx->sched.tail.size(),
-                       ctx->sched.pairs.data(), sizeof(int) * ctx->sched.pairs.size(), hipMemcpyHostToDevice, s);
-  // (fused narrow levels: their entry tables follow the tail's progress counter)
-  const size_t fused_off = ctx->sched.elim.size() + ctx->sched.remain.size() + ctx->sched.tail.size() + ctx->sched.pairs.size() + 4;
-  {
-    std::vector<int> fz;
-    fz.insert(fz.end(), ctx->sched.elim6.begin(), ctx->sched.elim6.end());
-    fz.insert(fz.end(), ctx->sched.iso_loc.begin(), ctx->sched.iso_loc.end());
-    fz.insert(fz.end(), ctx->sched.fold.begin(), ctx->sched.fold.end());
-    if (e == hipSuccess && !fz.empty()) {
-      e = hipMemcpyAsync(ctx->b.sched + fused_off, fz.data(), sizeof(int) * fz.size(), hipMemcpyHostToDevice, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);       // (fz is a local)
-    }
-  }
+  const std::vector<int> sched_ints = ctx->sched.pack();
+  if (e == hipSuccess && !sched_ints.empty())
+    e = hipMemcpyAsync(ctx->b.sched, sched_ints.data(), sizeof(int) * sched_ints.size(), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemsetAsync(ctx->b.trunc_eps2, 0, sizeof(double) * (7 * (ctx->sched.pairs.size() / 2 + 1) + 1), s);
   if (e == hipSuccess && ctx->b.st_flags) e = hipMemsetAsync(ctx->b.st_flags, 0, sizeof(int) * ((size_t)ctx->b.n_st_flags + 2), s);
   if (e == hipSuccess && ctx->b.st_ll) e = hipMemsetAsync(ctx->b.st_ll, 0, sizeof(unsigned long long) * ctx->b.n_st_ll, s);
   // (the runs write the contribution AL of every separator that has a run on its right: a right pin has none - zero once)
   if (e == hipSuccess && ctx->plan.active() && ctx->plan.n_sep > 0)
-    e = hipMemsetAsync(const_cast<double*>(ctx->sepchain.AL0), 0, sizeof(double) * (size_t)ctx->plan.n_sep * BS * BS, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+    e = hipMemsetAsync(ctx->b.sep_al, 0, sizeof(double) * (size_t)ctx->plan.n_sep * BS * BS, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);       // (sched_ints is a local)
   if (e != hipSuccess) {
     set_error("context upload failed: %s", hipGetErrorString(e));
     delete ctx;
@@ -780,49 +761,31 @@ int acino_fte_create(acino_fte_ctx** out, const acino_fte_params* p, const doubl
   }
   {
     BcrChain& red = ctx->plan.active() ? ctx->sepchain : ctx->chain;   // the chain the schedule reduces
-    red.d_elim = ctx->b.sched;
-    red.d_remain = ctx->b.sched + ctx->sched.elim.size();
-    if (!ctx->sched.tail.empty() && !p->shared_gpu) {
-      red.d_tail = red.d_remain + ctx->sched.remain.size();
-      red.d_done = ctx->b.sched + ctx->sched.elim.size() + ctx->sched.remain.size() + ctx->sched.tail.size() +
-                  ctx->sched.pairs.size();
-    }
-    if (!ctx->sched.pairs.empty()) {
-      red.d_pairs = ctx->b.sched + ctx->sched.elim.size() + ctx->sched.remain.size() + ctx->sched.tail.size();
-      red.n_pairs = (int)(ctx->sched.pairs.size() / 2);
-    }
+    ctx->sched.bind(ctx->b.sched, red);
     ctx->n_trunc = red.n_pairs;
     red.refine_buf = ctx->b.refine_buf;
-    if (ctx->sched.fused_levels) {
-      red.d_elim6 = ctx->b.sched + fused_off;
-      red.d_iso_loc = red.d_elim6 + ctx->sched.elim6.size();
-      red.d_fold = red.d_iso_loc + ctx->sched.iso_loc.size();
+    red.st_flags = ctx->b.st_flags;
+    red.n_st_flags = ctx->b.n_st_flags;
+    red.st_ll = ctx->b.st_ll;
+  }
+  if (ctx->sched.sep_tail) {
+    // k_sep_tail only on devices that hold all of its workgroups at once (occupancy x compute units of THIS device: a CU mask,
+    // a partitioned GPU); the others take the per-level kernels
+    int capacity = 0;
+    rc = bcr_set_func_attributes();                // (the occupancy query needs the kernel's LDS attribute in place)
+    if (!rc) rc = bcr_sep_tail_capacity(&capacity);
+    if (rc) {
+      delete ctx;
+      return rc;
     }
-    // one persistent launch for the separator chain's back-substitution: its isolated workgroups wait for each other, so it
-    // is kept off GPUs that other spin-waiting kernels may share (shared_gpu: batched clips, several ranks on one device)
-    // - and off devices that cannot hold all of its workgroups at once (occupancy x compute units of THIS device: a CU mask, a
-    // partitioned GPU): those take the per-level kernels
-    red.st_flags = nullptr;
-    if (ctx->plan.active() && !p->shared_gpu && !getenv("ACINO_NO_SEP_TAIL") && ctx->b.st_flags) {
-      int blocks = 0, capacity = 0;
-      int rc = bcr_set_func_attributes();                // (the occupancy query needs the kernel's LDS attribute in place)
-      if (!rc) rc = bcr_sep_tail_fit(ctx->sched, &blocks, &capacity);
-      if (rc) {
-        delete ctx;
-        return rc;
-      }
-      if (const char* e = getenv("ACINO_SEP_TAIL_CAPACITY")) capacity = atoi(e);   // (tests: pretend a smaller device)
-      if (blocks > 0 && blocks <= capacity) {
-        red.st_flags = ctx->b.st_flags;
-        red.n_st_flags = ctx->b.n_st_flags;
-        red.st_ll = ctx->b.st_ll;
-      }
-    }
+    // (tests: pretend a smaller device - never a larger one, whose launch would wait for workgroups that are not resident)
+    if (const char* v = getenv("ACINO_SEP_TAIL_CAPACITY")) capacity = std::min(capacity, atoi(v));
+    ctx->sched.sep_tail = ctx->sched.sep_tail_blocks() <= capacity;
   }
   if (ctx->plan.active()) {
-    ctx->sep = SepView{ctx->sepchain.D, ctx->sepchain.Cpl, const_cast<double*>(ctx->sepchain.AL0), ctx->sepchain.b};
-    ctx->sep.flags = ctx->sepchain.st_flags;
-    ctx->sep.n_flags = ctx->sepchain.st_flags ? ctx->b.n_st_flags : 0;
+    ctx->sep = SepView{ctx->sepchain.D, ctx->sepchain.Cpl, ctx->b.sep_al, ctx->sepchain.b};
+    ctx->sep.flags = ctx->sched.sep_tail ? ctx->b.st_flags : nullptr;
+    ctx->sep.n_flags = ctx->sched.sep_tail ? ctx->b.n_st_flags : 0;
   }
   ctx->n_blk_asm = n_assemble_blocks(p->n_frames);
   ctx->n_blk_trial = (int)(((size_t)p->n_frames * NP + 255) / 256);
@@ -1002,52 +965,40 @@ int acino_fte_export_separators(acino_fte_ctx* ctx, double* d_sep, int rank, int
   return ACINO_OK;
 }
 
-size_t acino_sep_scratch_bytes(int n_sep) {
-  if (n_sep < 1) return 0;
-  BcrSchedule sch;
-  // (GENERAL 80 x 80 blocks: the fused narrow levels of seplevel.hip need the identity padding of FTE nodes - their right-hand
-  //  side rides in the padding column - so this entry point keeps the per-phase kernels)
-  sch.build(n_sep, false, false);
-  size_t ints = sch.elim.size() + sch.remain.size() + sch.fused_ints() + 8;
-  return 6 * align_up((size_t)n_sep * BS * BS * sizeof(double)) + align_up(ints * sizeof(int)) + 1024;   // D U Cpl Wl Wr, b
-}
-
 namespace acino {
 static const BcrSchedule& sep_schedule(int n_sep) {
   static thread_local std::map<int, BcrSchedule> cache;   // schedules are immutable once built
   auto it = cache.find(n_sep);
   if (it == cache.end()) {
     BcrSchedule sch;
+    // (GENERAL 80 x 80 blocks: the fused narrow levels of seplevel.hip need the identity padding of FTE nodes - their right-hand
+    //  side rides in the padding column - so this chain keeps the per-phase kernels, and the per-level back-substitution)
     sch.build(n_sep, false, false);
+    sch.backsub_tail = false;
     it = cache.emplace(n_sep, std::move(sch)).first;
   }
   return it->second;
 }
+}  // namespace acino
+
+size_t acino_sep_scratch_bytes(int n_sep) {
+  if (n_sep < 1) return 0;
+  const size_t ints = sep_schedule(n_sep).pack().size();
+  return 6 * align_up((size_t)n_sep * BS * BS * sizeof(double)) + align_up(ints * sizeof(int)) + 1024;   // D U Cpl Wl Wr, b
+}
+
+namespace acino {
 static BcrChain sep_chain(void* d_scratch, int n_sep, const BcrSchedule& sch) {
   Carver c{(char*)d_scratch, 0};
   BcrChain ch;
   ch.n_nodes = n_sep;
   ch.D = c.take<double>((size_t)n_sep * BS * BS);
   ch.U = c.take<double>((size_t)n_sep * BS * BS);
-  ch.Cpl = c.take<double>((sch.fused_levels ? 2 : 1) * (size_t)n_sep * BS * BS);
+  ch.Cpl = c.take<double>((size_t)n_sep * BS * BS);
   ch.Wl = c.take<double>((size_t)n_sep * BS * BS);
   ch.Wr = c.take<double>((size_t)n_sep * BS * BS);
   ch.b = c.take<double>((size_t)n_sep * BS);
-  if (sch.fused_levels) {
-    ch.SL = c.take<double>((size_t)n_sep * BS * BS);
-    ch.SR = c.take<double>((size_t)n_sep * BS * BS);
-    ch.Y = c.take<double>((size_t)n_sep * BS);
-  }
-  int* d_sched = c.take<int>(sch.elim.size() + sch.remain.size() + sch.fused_ints() + 8);
-  ch.d_elim = d_sched;
-  ch.d_remain = d_sched + sch.elim.size();
-  if (sch.fused_levels) {
-    ch.d_elim6 = ch.d_remain + sch.remain.size();
-    ch.d_iso_loc = ch.d_elim6 + sch.elim6.size();
-    ch.d_fold = ch.d_iso_loc + sch.iso_loc.size();
-  }
-  ch.d_tail = nullptr;            // (the separator chain keeps the per-level kernels)
-  ch.d_done = nullptr;
+  sch.bind(c.take<int>(sch.pack().size()), ch);
   ch.implicit_couplings = 0;
   ch.dbg = nullptr;
   ch.st = nullptr;
@@ -1059,25 +1010,18 @@ static BcrChain sep_chain(void* d_scratch, int n_sep, const BcrSchedule& sch) {
 // host-to-device copy, so the write is stream-ordered, capturable and never synchronises (chains of <= 128 separators;
 // longer ones fall back to a copy and are not graph-captured).
 struct SchedArg {
+  static constexpr size_t cap = 960;
   int n;
-  int v[960];
+  int v[cap];
 };
 __global__ void k_write_schedule(SchedArg a, int* __restrict__ dst) {
   for (int i = threadIdx.x; i < a.n; i += blockDim.x) dst[i] = a.v[i];
 }
-static bool sep_schedule_fits_arg(const BcrSchedule& sch) { return sch.elim.size() + sch.remain.size() + sch.fused_ints() <= 960; }
-static std::vector<int> sep_schedule_ints(const BcrSchedule& sch) {      // in the order sep_chain lays them out
-  std::vector<int> v(sch.elim);
-  v.insert(v.end(), sch.remain.begin(), sch.remain.end());
-  v.insert(v.end(), sch.elim6.begin(), sch.elim6.end());
-  v.insert(v.end(), sch.iso_loc.begin(), sch.iso_loc.end());
-  v.insert(v.end(), sch.fold.begin(), sch.fold.end());
-  return v;
-}
+static bool sep_schedule_fits_arg(const BcrSchedule& sch) { return sch.pack().size() <= SchedArg::cap; }
 static int sep_upload_schedule(const BcrChain& ch, const BcrSchedule& sch, hipStream_t s) {
   int* d_sched = const_cast<int*>(ch.d_elim);
-  const std::vector<int> v = sep_schedule_ints(sch);
-  if (sep_schedule_fits_arg(sch)) {
+  const std::vector<int> v = sch.pack();
+  if (v.size() <= SchedArg::cap) {
     SchedArg a;
     a.n = (int)v.size();
     std::copy(v.begin(), v.end(), a.v);
@@ -1324,7 +1268,7 @@ int acino_fte_solve(acino_fte_ctx* ctx, int max_iter, acino_fte_state* out, void
   // (a context continues where its last solve stopped: the device's iteration counter is cumulative.  What the fall-back below
   //  has left of THIS call's budget is counted from the value at entry - only read where the fall-back can happen.)
   int iter_at_entry = 0;
-  if (ctx->sepchain.st_flags && max_iter > 0) {
+  if (ctx->sched.sep_tail && max_iter > 0) {
     if (int rc = acino_fte_get_state(ctx, &st, stream)) return rc;
     iter_at_entry = st.iter;
   }
@@ -1346,12 +1290,12 @@ int acino_fte_solve(acino_fte_ctx* ctx, int max_iter, acino_fte_state* out, void
     ACINO_HIP_CHECK(hipMemcpyAsync(&ne, ctx->b.numeric_err, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
     ACINO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   }
-  if (st.status == 6 && (ne & 8) && ctx->sepchain.st_flags && max_iter > 0) {
+  if (st.status == 6 && (ne & 8) && ctx->sched.sep_tail && max_iter > 0) {
     // the single-launch back-substitution of the separator chain (k_sep_tail: numeric_err bit 3) waited in vain for another
     // workgroup (something else holds the compute units it counted on): the refused step changed nothing but the counters -
     // fall back to the per-level kernels for the rest of this context's life and go on from the same iterate.  (The other
     // bounded wait - the d_done tail of bcr.hip - has no such alternative: status 6 is returned.)
-    ctx->sepchain.st_flags = nullptr;
+    ctx->sched.sep_tail = false;
     ctx->sep.flags = nullptr;
     ctx->sep.n_flags = 0;
     if (ctx->gexec) {
@@ -1456,7 +1400,7 @@ int acino_fte_debug_read(acino_fte_ctx* ctx, int what, double* d_out, int64_t n,
     case 1: src = ctx->sepchain.D; cnt = S * MB; break;
     case 2: src = ctx->sepchain.b; cnt = S * BS; break;
     case 3: src = ctx->sepchain.Cpl; cnt = S * MB; break;
-    case 4: src = ctx->sepchain.AL0; cnt = S * MB; break;
+    case 4: src = ctx->b.sep_al; cnt = S * MB; break;
     case 6: src = ctx->chain.D; cnt = T * MB; break;
     case 7: src = ctx->chain.Wl; cnt = ctx->plan.active() ? T * BS : T * MB; break;
     default: ACINO_REQUIRE(false, "what");

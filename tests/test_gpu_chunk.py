@@ -236,14 +236,17 @@ def test_separator_tail_falls_back_to_the_per_level_kernels_on_a_device_that_can
 
 
 @pytest.mark.parametrize("n,kw", [(999, {}), (999, dict(bcr_levels=0)), (3331, {}), (400, dict(shared_gpu=True)), (190, {}),
-                                   (2500, dict(chunk_nodes=4))])
+                                   (2500, dict(chunk_nodes=4)), (10000, dict(chunk_nodes=4)),
+                                   (10000, dict(chunk_nodes=4, bcr_levels=0))])
 def test_fused_narrow_levels_equal_the_per_phase_kernels(mods, monkeypatch, n, kw):
     """Round 6: a narrow level of the separator reduction is ONE launch (csrc/seplevel.hip: elimination and Schur products, the
     products kept as per-side running sums, the isolated level factored inside k_sep_tail).  ACINO_NO_FUSED_LEVELS=1 selects the
     per-phase kernels of csrc/bcr.hip for the same chain: both are exact eliminations of the same system, so the LM walk - trial
     cost, accept / reject, predicted reduction, trial iterate - must agree to rounding.  Cases: truncated + refined (tail kernel),
     complete reduction, a shared GPU (per-level back-substitution: the sums are folded for it), a chain too short to truncate,
-    many short runs (wide first level on the old kernels, narrow ones fused)."""
+    many short runs (2500 frames: 208 separators, every level fused; 10000 frames: 833 separators, truncated + refined and
+    complete - two wide levels on the per-phase kernels after k_sep_combine has folded the runs' contributions, then fused
+    levels, then, on a device that cannot hold 833 workgroups of k_sep_tail, the fold of the isolated level)."""
     calib, fte, synth = mods
     seq = synth.make_sequence(n, "loop")
     rig = (seq["K"], seq["D"], seq["R"], seq["t"])
