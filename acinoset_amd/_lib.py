@@ -13,7 +13,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libacinoset_hip.so")
 BUILD_ID_SOURCE = "camera_kernels.hip"      # defines acino_build_id()
 SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_api.hip", "sba.hip", "ekf.hip", "skel_fte.hip"]
-HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp", os.path.join("..", "..", "include", "acinoset_hip.h")]
+HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
+           "pinhole.hpp", "fte_assemble_body.inc", os.path.join("..", "..", "include", "acinoset_hip.h")]
 
 ABI_VERSION = 3          # ACINO_ABI_VERSION of include/acinoset_hip.h
 N_ACTIVE = 25
@@ -130,6 +131,7 @@ SIGNATURES = {
     "acino_sizeof_fte_state": (_Z, []),
     "acino_fte_workspace_bytes": (_Z, [C.POINTER(FteParams)]),
     "acino_fte_create": (_I, [C.POINTER(_P), C.POINTER(FteParams), _P, _P, _P, _Z, _P]),
+    "acino_fte_create_pinhole": (_I, [C.POINTER(_P), C.POINTER(FteParams), _P, _P, _P, _Z, _P]),
     "acino_fte_destroy": (_I, [_P]),
     "acino_fte_plan": (_I, [C.POINTER(FteParams), C.POINTER(C.c_int32)]),
     "acino_fte_set_x": (_I, [_P, _P, _P]),

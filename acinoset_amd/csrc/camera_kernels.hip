@@ -3,6 +3,7 @@
 #include <stdarg.h>
 
 #include "common.hpp"
+#include "pinhole.hpp"
 
 namespace acino {
 
@@ -15,16 +16,7 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
-// ---- pinhole (rational) model ----------------------------------------------------------------
-struct Pin {
-  double fx, fy, cx, cy;
-  double d[14];
-  double R[9];
-  double t[3];
-  double pad0, pad1;
-};
-static_assert(sizeof(Pin) == ACINO_PINHOLE_STRIDE * sizeof(double), "pinhole record layout");
-
+// ---- pinhole (rational) model (record: pinhole.hpp) ---------------------------------------------
 __device__ __forceinline__ void undistort_pinhole_pt(const Pin& c, double u, double v, double& x, double& y) {
   const double* k = c.d;
   double x0 = (u - c.cx) / c.fx, y0 = (v - c.cy) / c.fy;

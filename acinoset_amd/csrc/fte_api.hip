@@ -605,7 +605,7 @@ __global__ void k_copy_vec(const double* __restrict__ src, double* __restrict__ 
   if (i < n) dst[i] = src[i];
 }
 
-static int fill_const(const acino_fte_params* p, const double* h_cams, FteConst* c) {
+static int fill_const(const acino_fte_params* p, const double* h_cams, int camera_model, FteConst* c) {
   memset(c, 0, sizeof(*c));
   c->n_frames = p->n_frames;
   c->n_cams = p->n_cams;
@@ -633,7 +633,11 @@ static int fill_const(const acino_fte_params* p, const double* h_cams, FteConst*
   c->refine_sweeps = p->refine_sweeps;
   c->own_lo = p->own_count > 0 ? p->own_first : 0;
   c->own_hi = p->own_count > 0 ? p->own_first + p->own_count : p->n_frames;
-  memcpy(c->cams, h_cams, sizeof(double) * ACINO_CAM_STRIDE * p->n_cams);
+  c->camera_model = camera_model;
+  if (camera_model == CAMERA_PINHOLE)
+    memcpy(c->pcams, h_cams, sizeof(double) * ACINO_PINHOLE_STRIDE * p->n_cams);
+  else
+    memcpy(c->cams, h_cams, sizeof(double) * ACINO_CAM_STRIDE * p->n_cams);
   return ACINO_OK;
 }
 
@@ -698,13 +702,18 @@ size_t acino_fte_workspace_bytes(const acino_fte_params* p) {
   return carve(p, nullptr, nullptr, nullptr, lay) + 256;
 }
 
-int acino_fte_create(acino_fte_ctx** out, const acino_fte_params* p, const double* d_det, const double* d_cams24,
-                     void* d_workspace, size_t workspace_bytes, void* stream) {
+}  // extern "C"
+
+// acino_fte_create / acino_fte_create_pinhole: d_cams holds n_cams records of the model's stride (24 | 32 doubles)
+static int fte_create(acino_fte_ctx** out, const acino_fte_params* p, const double* d_det, const double* d_cams,
+                      int camera_model, void* d_workspace, size_t workspace_bytes, void* stream) {
   ACINO_REQUIRE(out != nullptr, "out");
   *out = nullptr;
   int rc = validate(p);
   if (rc) return rc;
-  ACINO_REQUIRE(d_det && d_cams24 && d_workspace, "null buffer");
+  ACINO_REQUIRE(d_det && d_cams && d_workspace, "null buffer");
+  if (camera_model == CAMERA_PINHOLE)
+    ACINO_REQUIRE(p->precision == ACINO_PREC_F64, "the pinhole camera model is assembled in fp64 only (precision ACINO_PREC_F64)");
   ACINO_REQUIRE(((uintptr_t)d_workspace & 255) == 0, "workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   acino_fte_ctx* ctx = new (std::nothrow) acino_fte_ctx();
@@ -725,16 +734,16 @@ int acino_fte_create(acino_fte_ctx** out, const acino_fte_params* p, const doubl
   }
   ctx->ws_bytes = need;
   ctx->d_det = d_det;
-  double h_cams[ACINO_MAX_CAMS * ACINO_CAM_STRIDE];
-  hipError_t e = hipMemcpyAsync(h_cams, d_cams24, sizeof(double) * ACINO_CAM_STRIDE * p->n_cams,
-                                hipMemcpyDeviceToHost, s);
+  const int stride = camera_model == CAMERA_PINHOLE ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE;
+  double h_cams[ACINO_MAX_CAMS * ACINO_PINHOLE_STRIDE];
+  hipError_t e = hipMemcpyAsync(h_cams, d_cams, sizeof(double) * stride * p->n_cams, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
     set_error("reading camera records failed: %s", hipGetErrorString(e));
     delete ctx;
     return ACINO_ERR_HIP;
   }
-  fill_const(p, h_cams, &ctx->h);
+  fill_const(p, h_cams, camera_model, &ctx->h);
   acino_fte_state st;
   memset(&st, 0, sizeof(st));
   st.lam = p->lam0;
@@ -798,6 +807,18 @@ int acino_fte_create(acino_fte_ctx** out, const acino_fte_params* p, const doubl
   }
   *out = ctx;
   return ACINO_OK;
+}
+
+extern "C" {
+
+int acino_fte_create(acino_fte_ctx** out, const acino_fte_params* p, const double* d_det, const double* d_cams24,
+                     void* d_workspace, size_t workspace_bytes, void* stream) {
+  return fte_create(out, p, d_det, d_cams24, CAMERA_FISHEYE, d_workspace, workspace_bytes, stream);
+}
+
+int acino_fte_create_pinhole(acino_fte_ctx** out, const acino_fte_params* p, const double* d_det, const double* d_cams32,
+                             void* d_workspace, size_t workspace_bytes, void* stream) {
+  return fte_create(out, p, d_det, d_cams32, CAMERA_PINHOLE, d_workspace, workspace_bytes, stream);
 }
 
 // The linear solver's layout for these parameters: out[0] = nodes per run (0: block cyclic reduction over the whole chain),
@@ -877,6 +898,8 @@ __global__ void k_restart_status(acino_fte_state* st, double lam0) {
 int acino_fte_set_precision(acino_fte_ctx* ctx, int precision) {
   ACINO_REQUIRE(ctx, "null");
   ACINO_REQUIRE(precision >= ACINO_PREC_F64 && precision <= ACINO_PREC_BF16_RES, "precision");
+  ACINO_REQUIRE(ctx->h.camera_model != CAMERA_PINHOLE || precision == ACINO_PREC_F64,
+                "the pinhole camera model is assembled in fp64 only (precision ACINO_PREC_F64)");
   ctx->h.precision = precision;            // the assembly kernel is chosen on the host; the device block does not need it
   if (ctx->gexec) {
     (void)hipGraphExecDestroy(ctx->gexec);

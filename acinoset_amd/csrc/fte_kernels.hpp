@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "pinhole.hpp"
 
 namespace acino {
 
@@ -43,7 +44,12 @@ struct FteConst {
   int32_t refine_sweeps;   // block-Jacobi sweeps after the truncated solve: the admissible quantity becomes (2 eps)^(r+1)
   int32_t pad2;
   Cam cams[ACINO_MAX_CAMS];
+  // (appended after the fisheye records: no offset the fisheye kernels read moves)
+  Pin pcams[ACINO_MAX_CAMS];      // camera_model == CAMERA_PINHOLE: the 32-double records (cams unused)
+  int32_t camera_model;           // CAMERA_FISHEYE | CAMERA_PINHOLE
+  int32_t pad3;
 };
+enum { CAMERA_FISHEYE = 0, CAMERA_PINHOLE = 1 };
 
 // (D3^T D3)[n, n+k] for global frame n, 0 <= k <= 3, sequence length ng (stencil -1, 3, -3, 1).
 __host__ __device__ inline double band_coef(int64_t n, int k, int64_t ng) {

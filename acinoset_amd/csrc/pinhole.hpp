@@ -1,0 +1,52 @@
+// The OpenCV "standard" pinhole camera (cv2.projectPoints: rational + tangential + thin-prism distortion), shared by the
+// point-wise camera kernels and the FTE assembly.
+#pragma once
+#include "common.hpp"
+
+namespace acino {
+
+// ---- pinhole camera record (32 doubles, see acinoset_hip.h) --------------------------------
+struct Pin {
+  double fx, fy, cx, cy;
+  double d[14];           // k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 tx ty (the tilt tx, ty is refused by calib.pinhole_record)
+  double R[9];
+  double t[3];
+  double pad0, pad1;
+};
+static_assert(sizeof(Pin) == ACINO_PINHOLE_STRIDE * sizeof(double), "pinhole record layout");
+
+// cv2.projectPoints of a camera-frame point and d(uv)/d(Xc); the skew entry of K is ignored, as OpenCV does.  The algebra
+// of pinhole_cam<JAC> (sba.hip), with the two reciprocals 1 / z and 1 / (1 + k4 r^2 + k5 r^4 + k6 r^6) by rcp64 as in the
+// rest of the per-point camera arithmetic.
+template <bool JAC>
+__device__ __forceinline__ void pinhole_project(const Pin& c, double xc, double yc, double zc, double uv[2], double J[2][3]) {
+  const double* k = c.d;
+  const double iz = rcp64(zc);
+  const double a = xc * iz, b = yc * iz;
+  const double r2 = a * a + b * b, r4 = r2 * r2, r6 = r4 * r2;
+  const double num = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
+  const double iden = rcp64(1 + k[5] * r2 + k[6] * r4 + k[7] * r6);
+  const double rad = num * iden;
+  const double xd = a * rad + 2 * k[2] * a * b + k[3] * (r2 + 2 * a * a) + k[8] * r2 + k[9] * r4;
+  const double yd = b * rad + k[2] * (r2 + 2 * b * b) + 2 * k[3] * a * b + k[10] * r2 + k[11] * r4;
+  uv[0] = c.fx * xd + c.cx;
+  uv[1] = c.fy * yd + c.cy;
+  if (JAC) {
+    const double dnum = k[0] + 2 * k[1] * r2 + 3 * k[4] * r4, dden = k[5] + 2 * k[6] * r2 + 3 * k[7] * r4;
+    const double drad = (dnum - rad * dden) * iden;                  // d rad / d r2
+    const double sx = k[8] + 2 * k[9] * r2, sy = k[10] + 2 * k[11] * r2;
+    const double dx_da = rad + 2 * a * a * drad + 2 * k[2] * b + 6 * k[3] * a + 2 * a * sx;
+    const double dx_db = 2 * a * b * drad + 2 * k[2] * a + 2 * k[3] * b + 2 * b * sx;
+    const double dy_da = 2 * a * b * drad + 2 * k[2] * a + 2 * k[3] * b + 2 * a * sy;
+    const double dy_db = rad + 2 * b * b * drad + 6 * k[2] * b + 2 * k[3] * a + 2 * b * sy;
+    const double du_da = c.fx * dx_da, du_db = c.fx * dx_db, dv_da = c.fy * dy_da, dv_db = c.fy * dy_db;
+    J[0][0] = du_da * iz;
+    J[0][1] = du_db * iz;
+    J[0][2] = -(du_da * a + du_db * b) * iz;
+    J[1][0] = dv_da * iz;
+    J[1][1] = dv_db * iz;
+    J[1][2] = -(dv_da * a + dv_db * b) * iz;
+  }
+}
+
+}  // namespace acino

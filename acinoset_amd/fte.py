@@ -33,6 +33,35 @@ R_MEAS = 5.0                          # measurement std-dev, px (:243)
 # acino_fte_params::precision: "f64" everywhere, or BASELINE config 5's "bf16 residuals with fp32 accumulate"
 PRECISIONS = {"f64": 0, "bf16": 1, "bf16_residuals": 2}
 REDESC = (3.0, 10.0, 20.0)            # redescending a, b, c (:25-27)
+CAMERA_MODELS = ("fisheye", "pinhole")
+
+
+def camera_model_of(camera_model=None, project_func=None, precision="f64"):
+    """The camera model of an FTE problem: ``camera_model`` "fisheye" (the default: the reference's pt3d_to_2d) or "pinhole"
+    (cv2.projectPoints, the rational / tangential / thin-prism model), or the reference's injection seam ``project_func``:
+    ``calib.project_points_fisheye`` (or None) selects fisheye, ``calib.project_points`` pinhole.  The pinhole model is
+    assembled in fp64 only.  Raises before any device work."""
+    if project_func is None or project_func is calib.project_points_fisheye:
+        seam = None if project_func is None else "fisheye"
+    elif project_func is calib.project_points:
+        seam = "pinhole"
+    else:
+        raise NotImplementedError("project_func must be acinoset_amd.calib.project_points_fisheye or "
+                                  "acinoset_amd.calib.project_points (the FTE assembly is a HIP kernel per camera model)")
+    if camera_model is not None and camera_model not in CAMERA_MODELS:
+        raise ValueError(f"camera_model must be one of {CAMERA_MODELS}")
+    if camera_model is not None and seam is not None and camera_model != seam:
+        raise ValueError(f"camera_model={camera_model!r} contradicts project_func (the {seam} model)")
+    model = camera_model or seam or "fisheye"
+    if model == "pinhole" and precision != "f64":
+        raise ValueError(f"the pinhole camera model is assembled in fp64 only (precision 'f64', got {precision!r})")
+    return model
+
+
+def camera_records(model, k_arr, d_arr, r_arr, t_arr):
+    """The rig as the library's camera records of ``model``: [C, 24] fisheye or [C, 32] pinhole (include/acinoset_hip.h)."""
+    recs = calib.pinhole_records if model == "pinhole" else calib.fisheye_records
+    return np.ascontiguousarray(recs(k_arr, d_arr, r_arr, t_arr))
 
 
 def bounds45():
@@ -109,7 +138,8 @@ def auto_bcr_levels(params, min_distance_frames=384):
 class FTEContext:
     """Owns the device buffers of one FTE problem (one shard of a sequence on one GPU)."""
 
-    def __init__(self, det, k_arr, d_arr, r_arr, t_arr, Ts, **kw):
+    def __init__(self, det, k_arr, d_arr, r_arr, t_arr, Ts, camera_model=None, project_func=None, **kw):
+        self.camera_model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
         _lib.require_gpu()
         dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
@@ -118,7 +148,7 @@ class FTEContext:
             raise ValueError("det must be [N, C, 20, 3] = (x, y, likelihood)")
         self.N, self.C = int(self.det.shape[0]), int(self.det.shape[1])
         self.Ts = float(Ts)
-        self.cams = torch.as_tensor(calib.fisheye_records(k_arr, d_arr, r_arr, t_arr), device=dev)
+        self.cams = torch.as_tensor(camera_records(self.camera_model, k_arr, d_arr, r_arr, t_arr), device=dev)
         if self.cams.shape[0] != self.C:
             raise ValueError("camera count mismatch between det and the rig")
         self._kw = self._resolve_defaults(dict(kw))
@@ -170,8 +200,9 @@ class FTEContext:
         base = self.workspace.data_ptr()
         self._ws_ptr = (base + 255) // 256 * 256
         self._h = C.c_void_p()
-        check(lib().acino_fte_create(C.byref(self._h), C.byref(self.params), ptr(self.det), ptr(self.cams),
-                                     C.c_void_p(self._ws_ptr), nbytes, stream_ptr()))
+        create = lib().acino_fte_create_pinhole if self.camera_model == "pinhole" else lib().acino_fte_create
+        check(create(C.byref(self._h), C.byref(self.params), ptr(self.det), ptr(self.cams), C.c_void_p(self._ws_ptr), nbytes,
+                     stream_ptr()))
         if self._graph:
             check(lib().acino_fte_enable_graph(self._h, 1))
 
@@ -241,7 +272,8 @@ class FTEContext:
     def set_precision(self, precision):
         """Switch the assembly arithmetic (PRECISIONS) and re-evaluate the current iterate in it; the controller keeps
         its damping (after a lambda overflow: lam0) and goes back to "running" - used to polish a mixed-precision solve
-        with fp64 iterations."""
+        with fp64 iterations.  (The pinhole model is fp64 only.)"""
+        camera_model_of(self.camera_model, None, precision)
         check(lib().acino_fte_set_precision(self._h, PRECISIONS[precision]))
         self._kw["precision"] = precision            # (a later rebuild - escalation - keeps the switched arithmetic)
         check(lib().acino_fte_reevaluate(self._h, stream_ptr()))
@@ -331,7 +363,8 @@ def cheetah_fk(q):
     return calib._ret(pos, q)
 
 
-def nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, n_frames=None, start_frame=0, det_first_frame=None):
+def nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, n_frames=None, start_frame=0, det_first_frame=None,
+                   camera_model="fisheye"):
     """Initial guess of :262-277,333-337: adjacent-pair triangulation of the detections above the
     likelihood threshold, least-squares line (linregress) through the nose (marker 2) over frames,
     psi_0 = atan2(y_slope, x_slope), every other state 0.  Returns x0[N,45] (numpy) for the frames
@@ -340,8 +373,9 @@ def nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, n_frames=None, s
     The reference regresses over ALL triangulated frames of the video (:268-271) and evaluates the line on the window
     (:272-276, :334-337): pass the whole video's detections with ``det_first_frame=0`` and the window through
     ``start_frame`` / ``n_frames`` for exactly that.  By default (``det_first_frame=None``) ``det`` IS the window -
-    its first row is frame ``start_frame`` - and the line is fitted to the window's own frames."""
-    tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False)
+    its first row is frame ``start_frame`` - and the line is fitted to the window's own frames.
+    ``camera_model``: "fisheye" or "pinhole", the model of the rig (calib.triangulate_pairs_dense)."""
+    tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False, model=camera_model)
     nose = tri[:, 2] if isinstance(tri, np.ndarray) else tri[:, 2].cpu().numpy()
     first = start_frame if det_first_frame is None else det_first_frame
     N = (nose.shape[0] if det_first_frame is None else nose.shape[0] - (start_frame - first)) if n_frames is None else n_frames
@@ -363,11 +397,12 @@ def nose_line_from_points(frames, nose_xyz, n_frames, start_frame=0):
     return x0
 
 
-def triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh):
+def triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, camera_model="fisheye"):
     """Per-frame initial guess for LONG sequences (an extension: the reference's straight nose line
     cannot follow a trajectory that turns): head position from the triangulated head markers, heading
-    from the neck_base->nose direction, gaps filled by linear interpolation; other states 0."""
-    tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False)
+    from the neck_base->nose direction, gaps filled by linear interpolation; other states 0.
+    ``camera_model`` as in nose_line_init."""
+    tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False, model=camera_model)
     tri = tri if isinstance(tri, np.ndarray) else tri.cpu().numpy()
     N = tri.shape[0]
     seen = np.isfinite(tri[:, 0:3]).all(-1)              # eyes + nose: mean of the ones that were triangulated
@@ -401,19 +436,19 @@ def clear_context_cache():
     _CTX_CACHE.clear()
 
 
-def _context_for(det, k_arr, d_arr, r_arr, t_arr, Ts, reuse, kw):
+def _context_for(det, k_arr, d_arr, r_arr, t_arr, Ts, reuse, kw, camera_model="fisheye"):
     if not reuse:
-        return FTEContext(det, k_arr, d_arr, r_arr, t_arr, Ts, **kw), False
+        return FTEContext(det, k_arr, d_arr, r_arr, t_arr, Ts, camera_model=camera_model, **kw), False
     import hashlib
-    cams = np.ascontiguousarray(calib.fisheye_records(k_arr, d_arr, r_arr, t_arr))
-    key = (tuple(det.shape), str(det.device), float(Ts), hashlib.sha256(cams.tobytes()).hexdigest(),
+    cams = camera_records(camera_model, k_arr, d_arr, r_arr, t_arr)
+    key = (tuple(det.shape), str(det.device), float(Ts), camera_model, hashlib.sha256(cams.tobytes()).hexdigest(),
            tuple(sorted((k, repr(v)) for k, v in kw.items())))
     ctx = _CTX_CACHE.get(key)
     if ctx is None or not ctx._h.value:
         for old in list(_CTX_CACHE.values()):            # (one workspace at a time: a 10 000-frame context holds ~1 GB)
             old.close()
         _CTX_CACHE.clear()
-        ctx = FTEContext(det.clone(), k_arr, d_arr, r_arr, t_arr, Ts, **kw)
+        ctx = FTEContext(det.clone(), k_arr, d_arr, r_arr, t_arr, Ts, camera_model=camera_model, **kw)
         ctx.enable_graph(True)
         _CTX_CACHE[key] = ctx
     else:
@@ -422,14 +457,15 @@ def _context_for(det, k_arr, d_arr, r_arr, t_arr, Ts, reuse, kw):
     return ctx, True
 
 
-def triangulation_init_active(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, raise_now=True):
+def triangulation_init_active(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, raise_now=True, camera_model="fisheye"):
     """``triangulation_init`` for a detections tensor that lives on the GPU: the same initial guess, formed on the device and
     returned as the 25 active states [N, 25].  Two launches (pairwise triangulation, ``acino_fte_triangulation_init``: head
     mean, unwrapped heading, interpolation over the frames that lack them) and no host round trip - the numpy form copied
     the 4.8 MB triangulation of a 10 000-frame sequence to the host (3 ms of a 15 ms solve), a torch form of the same
     arithmetic took ~60 small launches and three synchronisations (2 ms).  ``raise_now=False`` returns ``(xa, flag)`` with the
-    "no head marker in the whole sequence" flag left on the device for the caller to test later."""
-    tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False)
+    "no head marker in the whole sequence" flag left on the device for the caller to test later.  ``camera_model`` as in
+    nose_line_init."""
+    tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False, model=camera_model)
     n = int(tri.shape[0])
     xa = torch.empty((n, N_ACTIVE), dtype=torch.float64, device=tri.device)
     nbytes = int(lib().acino_fte_triangulation_init_scratch_bytes(n))
@@ -446,7 +482,8 @@ def triangulation_init_active(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, raise
 
 
 def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thresh=0.5, start_frame=0,
-              max_iter=100, init="nose_line", return_numpy=True, reuse_context=False, **kw):
+              max_iter=100, init="nose_line", return_numpy=True, reuse_context=False, camera_model=None, project_func=None,
+              **kw):
     """The FTE solve call.
 
     meas[N,C,20,2] pixel detections, likelihood[N,C,20], cameras as in the scene file (k_arr[C,3,3],
@@ -454,7 +491,10 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     (default: the reference's nose-line initialisation).  Returns (results, info) where results has the
     reference's fte.pickle layout and info the solver status (iterations, final cost, |g|_inf, ...).
     ``reuse_context``: keep the context (workspace, constants, captured graph) for the next call with the same shapes, rig
-    and options (see _CTX_CACHE above)."""
+    and options (see _CTX_CACHE above).  ``camera_model`` "fisheye" (default) or "pinhole" - then d_arr[C] holds OpenCV
+    distortion vectors of 4, 5, 8 or 12 entries -, or the reference's ``project_func`` seam (camera_model_of); the initial
+    guess and the solve both use that model."""
+    model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     meas_t = meas if isinstance(meas, torch.Tensor) else torch.as_tensor(np.asarray(meas, dtype=np.float64))
     lik_t = likelihood if isinstance(likelihood, torch.Tensor) else torch.as_tensor(np.asarray(likelihood, dtype=np.float64))
     det = torch.cat([meas_t.to(torch.float64), lik_t.to(torch.float64).unsqueeze(-1).to(meas_t.device)], dim=-1)
@@ -463,9 +503,10 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     xa0 = init_flag = None
     if x0 is None:
         if init == "nose_line":
-            x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frame)
+            x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frame, camera_model=model)
         elif init == "triangulation":
-            xa0, init_flag = triangulation_init_active(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, raise_now=False)   # (stays on the device)
+            xa0, init_flag = triangulation_init_active(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, raise_now=False,
+                                                       camera_model=model)   # (stays on the device)
         else:
             raise ValueError("init must be 'nose_line' or 'triangulation'")
     if xa0 is None:
@@ -476,7 +517,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         if np.any(x0[:, inactive] != 0):
             raise ValueError("states with Q == 0 must start (and stay) at 0 (all_optimizations.py:543)")
         xa0 = x0[:, ACTIVE]
-    ctx, cached = _context_for(det, k_arr, d_arr, r_arr, t_arr, Ts, reuse_context, dict(kw, dlc_thresh=dlc_thresh))
+    ctx, cached = _context_for(det, k_arr, d_arr, r_arr, t_arr, Ts, reuse_context, dict(kw, dlc_thresh=dlc_thresh), model)
     kw.pop("trunc_distance", None)
     try:
         ctx.set_x(xa0)
@@ -507,13 +548,15 @@ def _derivatives(x_clip, Ts):
 
 
 def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
-                    init="nose_line", return_numpy=True, **kw):
+                    init="nose_line", return_numpy=True, camera_model=None, project_func=None, **kw):
     """Equal-length clips of one rig solved as ONE problem (BASELINE config 5's batched FTE at full width): the clips
     are laid end to end on the frame axis, the smoothness prior is cut at the clip boundaries (``clip_len``), and the
     block-cyclic reduction runs over the whole chain - every launch is as wide as all clips together, so the narrow
     levels that dominate a single short clip almost vanish.  One Levenberg-Marquardt controller acts on the SUM of the
     clips' costs (the problem is block diagonal: each clip converges to its own optimum, but damping and accept/reject
-    are shared, so iterates differ from per-clip solves until convergence).  Returns a list of (results, info)."""
+    are shared, so iterates differ from per-clip solves until convergence).  Returns a list of (results, info).
+    ``camera_model`` / ``project_func`` as in fte_solve."""
+    model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     B = len(dets)
     if B == 0:
         return []
@@ -528,9 +571,9 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
         if x0s is not None and x0s[b] is not None:
             x0 = x0s[b]
         elif init == "nose_line":
-            x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frames[b])
+            x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frames[b], camera_model=model)
         elif init == "triangulation":
-            x0 = triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh)
+            x0 = triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, camera_model=model)
         else:
             raise ValueError("init must be 'nose_line' or 'triangulation'")
         x0 = np.asarray(x0.cpu().numpy() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
@@ -542,7 +585,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     dev = torch.device("cuda", torch.cuda.current_device())
     det_all = torch.cat([d.to(device=dev, dtype=torch.float64) for d in dets_t], dim=0)
     polish = kw.pop("polish_f64", False)
-    ctx = FTEContext(det_all, k_arr, d_arr, r_arr, t_arr, Ts, dlc_thresh=dlc_thresh, clip_len=S, **kw)
+    ctx = FTEContext(det_all, k_arr, d_arr, r_arr, t_arr, Ts, dlc_thresh=dlc_thresh, clip_len=S, camera_model=model, **kw)
     try:
         ctx.set_x(x0_all[:, ACTIVE])
         info = ctx.solve(max_iter)
@@ -570,7 +613,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
 
 
 def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
-                    init="nose_line", n_streams=8, peek_every=8, return_numpy=True, **kw):
+                    init="nose_line", n_streams=8, peek_every=8, return_numpy=True, camera_model=None, project_func=None, **kw):
     """Several independent sequences (BASELINE config 5's "batched FTE": one rig, many clips) solved concurrently
     on ONE GPU.  Every sequence gets its own context and runs on one of ``n_streams`` HIP streams; a Levenberg-
     Marquardt step never synchronises with the host (the accept/reject controller is a device kernel and the step is
@@ -578,7 +621,9 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     overlap with the wide levels of another's (HIP multiplexes the streams onto 4 hardware queues by default; 8 streams
     keep all of them busy whatever the stream-to-queue assignment).  ``dets``: list of det[N_b, C, 20, 3] (lengths may differ).
     Returns a list of (results, info) exactly as ``fte_solve`` would for each sequence alone.  The reference solves
-    clips one after another (src/all_optimizations.py:22, one ``fte()`` call per data directory)."""
+    clips one after another (src/all_optimizations.py:22, one ``fte()`` call per data directory).  ``camera_model`` /
+    ``project_func`` as in fte_solve."""
+    model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     _lib.require_gpu()
     B = len(dets)
     if B == 0:
@@ -593,9 +638,10 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
             if x0s is not None and x0s[b] is not None:
                 x0 = x0s[b]
             elif init == "nose_line":
-                x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frames[b])
+                x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frames[b],
+                                    camera_model=model)
             elif init == "triangulation":
-                x0 = triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh)
+                x0 = triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, camera_model=model)
             else:
                 raise ValueError("init must be 'nose_line' or 'triangulation'")
             x0 = np.asarray(x0.cpu().numpy() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
@@ -606,7 +652,8 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
             s = streams[b % len(streams)]
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                ctx = FTEContext(det, k_arr, d_arr, r_arr, t_arr, Ts, dlc_thresh=dlc_thresh, shared_gpu=True, **kw)
+                ctx = FTEContext(det, k_arr, d_arr, r_arr, t_arr, Ts, dlc_thresh=dlc_thresh, shared_gpu=True, camera_model=model,
+                                 **kw)
                 ctxs.append(ctx)
                 ctx.enable_graph(True)
                 ctx.set_x(x0[:, ACTIVE])

@@ -227,6 +227,12 @@ size_t acino_fte_workspace_bytes(const acino_fte_params* p);
  * d_workspace >= acino_fte_workspace_bytes(p), 256-byte aligned.  Synchronises the stream once. */
 int acino_fte_create(acino_fte_ctx** out, const acino_fte_params* p, const double* d_det,
                      const double* d_cams24, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The same problem on the OpenCV pinhole camera (cv2.projectPoints: k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4, skew ignored,
+ * the tilted model tau_x = tau_y = 0): d_cams32[C][32] pinhole records, everything else as acino_fte_create - the
+ * workspace size, every call on the handle, clips, graphs, profiling.  fp64 only: p->precision other than
+ * ACINO_PREC_F64, or a later acino_fte_set_precision to a bf16 mode, is ACINO_ERR_INVALID_ARG. */
+int acino_fte_create_pinhole(acino_fte_ctx** out, const acino_fte_params* p, const double* d_det,
+                             const double* d_cams32, void* d_workspace, size_t workspace_bytes, void* stream);
 int acino_fte_destroy(acino_fte_ctx* ctx);
 /* Layout the linear solver chooses for these parameters: out[0] = nodes per run of the chunked solver (0: block cyclic
  * reduction over the whole chain), out[1] = runs, out[2] = separators, out[3] = reduction levels of the reduced chain
