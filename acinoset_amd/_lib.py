@@ -14,7 +14,8 @@ SO_PATH = os.path.join(_HERE, "libacinoset_hip.so")
 BUILD_ID_SOURCE = "camera_kernels.hip"      # defines acino_build_id()
 SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_api.hip", "sba.hip", "ekf.hip", "skel_fte.hip"]
 HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
-           "pinhole.hpp", "fte_assemble_body.inc", os.path.join("..", "..", "include", "acinoset_hip.h")]
+           "pinhole.hpp", "fte_assemble_body.inc", "ekf_forward_body.inc", "skel_assemble_body.inc",
+           os.path.join("..", "..", "include", "acinoset_hip.h")]
 
 ABI_VERSION = 3          # ACINO_ABI_VERSION of include/acinoset_hip.h
 N_ACTIVE = 25
@@ -176,6 +177,7 @@ SIGNATURES = {
     "acino_sizeof_ekf_params": (_Z, []),
     "acino_ekf_workspace_bytes": (_Z, [_L, _I]),
     "acino_ekf_run": (_I, [C.POINTER(EkfParams), _P, _P, _P, _P, _Z, _P, _P, _P, _P]),
+    "acino_ekf_run_pinhole": (_I, [C.POINTER(EkfParams), _P, _P, _P, _P, _Z, _P, _P, _P, _P]),
     "acino_skeleton_fk": (_I, [_P, _L, _I, _I, C.POINTER(SkelOp), _I, _P, _P]),
     "acino_sizeof_skel_fte_params": (_Z, []),
     "acino_sizeof_skel_fte_info": (_Z, []),
@@ -185,6 +187,10 @@ SIGNATURES = {
                                   _P, _Z, C.POINTER(SkelFteInfo), _P]),
     "acino_skel_fte_solve_batch": (_I, [C.POINTER(SkelFteParams), _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P, _P,
                                         _P, _P, _P, _Z, C.POINTER(SkelFteInfo), _P]),
+    "acino_skel_fte_solve_pinhole": (_I, [C.POINTER(SkelFteParams), C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P,
+                                          _P, _P, _Z, C.POINTER(SkelFteInfo), _P]),
+    "acino_skel_fte_solve_batch_pinhole": (_I, [C.POINTER(SkelFteParams), _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P,
+                                                _P, _P, _P, _P, _P, _Z, C.POINTER(SkelFteInfo), _P]),
     "acino_selftest_mfma": (_I, [_P, _P, _I, _P, _P]),
     "acino_debug_poison_lds": (_I, [_I, _I, _P]),
     "acino_debug_level_split": (_I, [_I, _P]),

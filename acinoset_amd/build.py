@@ -6,7 +6,9 @@ project_dir, poses)`` (:306-335: IPOPT, then ``save_data`` -> ``data/results/tra
 (:343-365), ``save_data`` (:367-378).  Same names, same argument meaning, same files read and written; the model object is
 a plain container of arrays instead of a Pyomo model, and the solve is the projected Levenberg-Marquardt of
 ``csrc/skel_fte.hip`` on the GPU (``exe_path`` - the IPOPT binary - is accepted and ignored).  What is solved, with the
-reference's own index quirks, is written down in oracle/skel_fte.py and DESIGN.md section 8.
+reference's own index quirks, is written down in oracle/skel_fte.py and DESIGN.md section 8.  The cameras are the reference's
+fisheye model by default; ``camera_model="pinhole"`` (or ``project_func=calib.project_points``) on ``build_model`` /
+``solve_video`` selects cv2.projectPoints (rational / tangential / thin-prism distortion), kept on the model for the solve.
 """
 import ctypes as C
 import glob
@@ -16,7 +18,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, calib, io, skeleton
+from . import _lib, calib, fte, io, skeleton
 from ._lib import SkelFteInfo, SkelFteParams, SkelOp, check, lib, ptr, stream_ptr
 
 MODEL_WEIGHT = 0.002        # build.py:186-191
@@ -101,7 +103,7 @@ def _rows_by_frame_value(idx, want):
     return order[pos]
 
 
-def _forehead_union(tabs, lik_thresh, k_arr, d_arr, r_arr, t_arr):
+def _forehead_union(tabs, lik_thresh, k_arr, d_arr, r_arr, t_arr, camera_model="fisheye"):
     """The triangulated forehead over every frame that AT LEAST TWO cameras hold (the reference's pairwise triangulation uses
     every frame a camera pair shares, calib.py:394-423) - frames, points [F, 3] (NaN where no pair sees it).  A camera without
     the frame contributes a row of likelihood 0."""
@@ -113,21 +115,37 @@ def _forehead_union(tabs, lik_thresh, k_arr, d_arr, r_arr, t_arr):
         col = np.zeros((frames.size, 1, 3))
         col[held[:, c], 0] = vals[_rows_by_frame_value(idx, frames[held[:, c]]), parts.index("forehead")]
         cols.append(col)
-    tri = calib.triangulate_pairs_dense(np.stack(cols, axis=1), lik_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False)
+    tri = calib.triangulate_pairs_dense(np.stack(cols, axis=1), lik_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False,
+                                        model=camera_model)
     return frames, np.asarray(tri.cpu().numpy() if isinstance(tri, torch.Tensor) else tri)[:, 0]
 
 
+def _scene_distortion(camera_model, k_arr, d_arr, r_arr, t_arr):
+    """The rig's distortion vectors as the model reads them: fisheye k1..k4 (the reference's ``reshape((-1, 4))``, :100), or
+    the whole OpenCV pinhole vector of every camera (4, 5, 8, 12 or 14 entries; calib.pinhole_record refuses the others and
+    the tilted model)."""
+    if camera_model == "fisheye":
+        return d_arr.reshape((-1, 4))
+    d_arr = d_arr.reshape((len(k_arr), -1))
+    calib.pinhole_records(k_arr, d_arr, r_arr, t_arr)
+    return d_arr
+
+
 def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_frames=N_FRAMES, start_frame=START_FRAME,
-                h=H_STEP, pairing="reference", lik_thresh=LIK_THRESH, r_meas=R_MEAS, model_weight=MODEL_WEIGHT, initial_line=True):
+                h=H_STEP, pairing="reference", lik_thresh=LIK_THRESH, r_meas=R_MEAS, model_weight=MODEL_WEIGHT, initial_line=True,
+                camera_model=None, project_func=None):
     """build.py:28-304.  ``project_dir`` is the reference's: ``data/4_cam_scene_static_sba.json`` and ``data/*.h5`` are read
     from it (:97-109); alternatively pass ``scene = (k_arr, d_arr, r_arr, t_arr)`` and ``dlc_tables`` = one
-    ``(bodyparts, values[frames, K, 3])`` per camera.  Returns ``(model, pose_to_3d)`` as the reference does."""
+    ``(bodyparts, values[frames, K, 3])`` per camera.  ``camera_model`` "fisheye" (the default) or "pinhole", or
+    ``project_func`` = calib.project_points_fisheye / calib.project_points, as fte.camera_model_of; the model keeps it as
+    ``camera_model`` and every triangulation here uses it.  Returns ``(model, pose_to_3d)`` as the reference does."""
+    cam_model = fte.camera_model_of(camera_model, project_func)
     prog = skeleton.compile_skeleton(skel_dict)
     names = prog["names"]
     if scene is None:
         scene = io.load_scene(os.path.join(project_dir, "data", "4_cam_scene_static_sba.json"))[:4]
     k_arr, d_arr, r_arr, t_arr = (np.asarray(a, dtype=np.float64) for a in scene)
-    d_arr = d_arr.reshape((-1, 4))                                           # :100
+    d_arr = _scene_distortion(cam_model, k_arr, d_arr, r_arr, t_arr)
     if dlc_tables is None:
         paths = sorted(glob.glob(os.path.join(project_dir, "data", "*.h5")))  # :106
         dlc_tables = [io.read_dlc_table(p) for p in paths]
@@ -162,7 +180,7 @@ def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_f
     #      regression against the frame VALUE, evaluated at 0 .. N-1 (:157)
     init_x = np.zeros((n_frames, 3 + 3 * prog["n_angles"]))
     if initial_line and all("forehead" in parts for parts, _v, _i in tabs) and C_ >= 2:   # (initial_line=False: the caller brings x0)
-        common, tri = _forehead_union(tabs, lik_thresh, k_arr, d_arr, r_arr, t_arr)
+        common, tri = _forehead_union(tabs, lik_thresh, k_arr, d_arr, r_arr, t_arr, cam_model)
         ok = np.isfinite(tri).all(1)
         if ok.sum() >= 2:
             f = common.astype(np.float64)[ok]
@@ -172,7 +190,8 @@ def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_f
     lo, hi = bounds_table(skel_dict, n_frames)
     model = SkeletonModel(skel=skel_dict, prog=prog, names=names, active=active_states(skel_dict), meas=meas, weights=w,
                           K=k_arr, D=d_arr, R=r_arr, t=t_arr, h=float(h), lo=lo, hi=hi, init_x=init_x,
-                          start_frame=int(start_frame), model_weight=float(model_weight), pairing=pair, x=None, info=None)
+                          start_frame=int(start_frame), model_weight=float(model_weight), pairing=pair, camera_model=cam_model,
+                          x=None, info=None)
 
     def pose_to_3d(*states):
         return np.asarray(skeleton.skeleton_fk(prog, np.asarray(states, dtype=np.float64)[None, :]))[0]
@@ -206,7 +225,14 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
     In a batch a clip that fails numerically does not fail the call: its ``info["status_name"]`` is "numeric" (its results are
-    the last accepted iterate) and the other clips' results stand."""
+    the last accepted iterate) and the other clips' results stand.  The models' ``camera_model`` (fisheye or pinhole) selects
+    the assembly kernel; a batch that mixes the two is refused."""
+    cam_models = {getattr(m, "camera_model", "fisheye") for m in models}
+    if len(cam_models) > 1:
+        raise ValueError("the models of one batch share the camera model (got " + " and ".join(sorted(cam_models)) + ")")
+    cam_model = cam_models.pop()
+    if cam_model not in fte.CAMERA_MODELS:
+        raise ValueError(f"camera_model must be one of {fte.CAMERA_MODELS}")
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     m0 = models[0]
@@ -240,14 +266,15 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)   # noqa: E731
     meas = t(np.stack([np.nan_to_num(m.meas, nan=0.0) for m in models]))
     w = t(np.stack([np.where(np.isfinite(m.meas).all(-1), m.weights, 0.0) for m in models]))
-    cams = torch.as_tensor(calib.fisheye_records(m0.K, m0.D, m0.R, m0.t), device=dev)
+    cams = torch.as_tensor(fte.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
     lo, hi = t(np.stack([m.lo[:, act] for m in models])), t(np.stack([m.hi[:, act] for m in models]))
     x = t(np.stack([xf[:, act] for xf in xs]))
     pos = torch.empty((B, N, len(m0.names), 3), dtype=torch.float64, device=dev)
     infos = (SkelFteInfo * B)()
     act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
-    check(lib().acino_skel_fte_solve_batch(C.byref(p), B, _ops_array(prog), act_c, ptr(meas), ptr(w), ptr(cams), ptr(lo), ptr(hi),
-                                           ptr(x), ptr(pos), C.c_void_p(ws_ptr), nbytes, infos, stream_ptr()))
+    solve = lib().acino_skel_fte_solve_batch_pinhole if cam_model == "pinhole" else lib().acino_skel_fte_solve_batch
+    check(solve(C.byref(p), B, _ops_array(prog), act_c, ptr(meas), ptr(w), ptr(cams), ptr(lo), ptr(hi), ptr(x), ptr(pos),
+                C.c_void_p(ws_ptr), nbytes, infos, stream_ptr()))
     xh, ph = x.cpu().numpy(), pos.cpu().numpy()
     out = []
     for i, (m, xf) in enumerate(zip(models, xs)):
@@ -366,11 +393,14 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
 
     ``dx`` / ``ddx`` are taken per window and selected with the same depth rule as ``x``: at a seam between two windows the
     stitched ``x`` jumps between two independently converged solutions, and differences ACROSS a seam would read as spikes of
-    jump / h and jump / h^2.  ``kw``: build_model's (``pairing``, ``h``, ...) and solve_models' (``max_iter``, ...) keywords.
+    jump / h and jump / h^2.  ``kw``: build_model's (``pairing``, ``h``, ``camera_model``, ``project_func``, ...) and
+    solve_models' (``max_iter``, ...) keywords.
     Returns ``(results, infos, starts)``: ``results`` as convert_to_dict over frames first_frame .. last_frame (plus
     ``start_frame`` and ``seams``: the first frame, relative to first_frame, of every stretch taken from a new window), one
     info per window (with ``mean_abs_residual_px`` and ``warm_started_from``)."""
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
+    cam_model = fte.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
+    build_kw["camera_model"] = cam_model
     if dlc_tables is None:
         paths = sorted(glob.glob(os.path.join(project_dir, "data", "*.h5")))
         dlc_tables = [io.read_dlc_table(p) for p in paths]
@@ -392,7 +422,8 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
         k_arr, d_arr, r_arr, t_arr = (np.asarray(a, dtype=np.float64) for a in scene)
         cols = [vals[rw, parts.index("forehead")][:, None, :] for (parts, vals, _ix), rw in zip(tabs3, rows3)]
         tri = calib.triangulate_pairs_dense(np.stack(cols, axis=1), build_kw.get("lik_thresh", LIK_THRESH), k_arr,
-                                            d_arr.reshape((-1, 4)), r_arr, t_arr, return_masks=False)
+                                            _scene_distortion(cam_model, k_arr, d_arr, r_arr, t_arr), r_arr, t_arr,
+                                            return_masks=False, model=cam_model)
         tri = np.asarray(tri.cpu().numpy() if isinstance(tri, torch.Tensor) else tri)[:, 0]
         ok = np.isfinite(tri).all(1)
         if ok.sum() >= 2:

@@ -8,6 +8,8 @@ arrays and returns that dictionary (25 columns, pose parameters in the order of 
 plus the gated-outlier count and the marker positions of both state sequences.  All model constants are the
 reference's literals; the arithmetic runs in csrc/ekf.hip (one workgroup per sequence, covariance resident in LDS).
 Several clips are filtered by one launch with ``ekf_batch`` (the filter is sequential in frames, parallel in clips).
+The camera model is the reference's fisheye by default; ``camera_model="pinhole"`` (or ``project_func=calib.project_points``)
+projects with cv2.projectPoints (rational / tangential / thin-prism distortion) instead, in fp64 as the fisheye path.
 """
 import ctypes as C
 
@@ -39,9 +41,11 @@ def get_3d_marker_coords(x):
     return fte.cheetah_fk(q.reshape(-1, fte.N_STATES)).reshape(x.shape[:-1] + (20, 3))
 
 
-def initial_state(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, start_frame=0):
-    """:700-711 - nose position and heading from two regressions of the triangulated nose on the frame number."""
-    tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False)
+def initial_state(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, start_frame=0, camera_model=None, project_func=None):
+    """:700-711 - nose position and heading from two regressions of the triangulated nose on the frame number.  The nose is
+    triangulated with the camera model of ``camera_model`` / ``project_func`` (fte.camera_model_of)."""
+    model = fte.camera_model_of(camera_model, project_func)
+    tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False, model=model)
     nose = tri[:, 2] if isinstance(tri, np.ndarray) else tri[:, 2].cpu().numpy()
     ok = np.isfinite(nose).all(1)
     if ok.sum() < 2:
@@ -57,9 +61,12 @@ def initial_state(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, start_frame=
 
 
 def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, start_frames=None, states0=None,
-              with_positions=True, smoother_pivoting=False):
+              with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None):
     """Filter + smooth several clips of the same rig.  ``dets``: list of det[N_b, C, 20, 3] (x, y, likelihood);
-    clips of equal length share one launch.  Returns one result dictionary per clip."""
+    clips of equal length share one launch.  Returns one result dictionary per clip.  ``camera_model`` "fisheye" (the
+    default) or "pinhole", or ``project_func`` = calib.project_points_fisheye / calib.project_points (fte.camera_model_of:
+    a contradiction is a ValueError, any other function NotImplementedError, both before any device work)."""
+    model = fte.camera_model_of(camera_model, project_func)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     B = len(dets)
@@ -68,7 +75,7 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
     for d in dets_d:
         if d.dim() != 4 or d.shape[2] != 20 or d.shape[3] != 3:
             raise ValueError("det must be [N, C, 20, 3] = (x, y, likelihood)")
-    cams = torch.as_tensor(calib.fisheye_records(k_arr, d_arr, r_arr, t_arr), device=dev)
+    cams = torch.as_tensor(fte.camera_records(model, k_arr, d_arr, r_arr, t_arr), device=dev)
     n_cams = int(cams.shape[0])
     if any(int(d.shape[1]) != n_cams for d in dets_d):
         raise ValueError("camera count mismatch between det and the rig")
@@ -81,7 +88,7 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
             if s.size != N_EKF_STATES:
                 raise ValueError("states0 must have 75 entries (pose, velocity, acceleration)")
         else:
-            s = initial_state(dets_d[b], k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, start_frames[b])
+            s = initial_state(dets_d[b], k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, start_frames[b], camera_model=model)
         s0.append(s)
     out = [None] * B
     groups = {}
@@ -100,8 +107,9 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
         est = torch.empty((len(members), n_frames, N_EKF_STATES), dtype=torch.float64, device=dev)
         smo = torch.empty_like(est)
         outl = torch.zeros(len(members), dtype=torch.int32, device=dev)
-        check(lib().acino_ekf_run(C.byref(prm), ptr(det), ptr(cams), ptr(st0), C.c_void_p(ws_ptr), nbytes, ptr(est),
-                                  ptr(smo), C.c_void_p(outl.data_ptr()), stream_ptr()))
+        run = lib().acino_ekf_run_pinhole if model == "pinhole" else lib().acino_ekf_run
+        check(run(C.byref(prm), ptr(det), ptr(cams), ptr(st0), C.c_void_p(ws_ptr), nbytes, ptr(est), ptr(smo),
+                  C.c_void_p(outl.data_ptr()), stream_ptr()))
         est_h, smo_h, outl_h = est.cpu().numpy(), smo.cpu().numpy(), outl.cpu().numpy()
         for j, b in enumerate(members):
             r = dict(x=est_h[j, :, :N_POSE], dx=est_h[j, :, N_POSE:2 * N_POSE], ddx=est_h[j, :, 2 * N_POSE:],
@@ -115,7 +123,8 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
 
 
 def ekf(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, start_frame=0, states0=None,
-        with_positions=True, smoother_pivoting=False):
-    """One clip: det[N, C, 20, 3] for the frames start_frame .. start_frame + N - 1."""
+        with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None):
+    """One clip: det[N, C, 20, 3] for the frames start_frame .. start_frame + N - 1 (camera model as ``ekf_batch``)."""
     return ekf_batch([det], k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, [start_frame],
-                     None if states0 is None else [states0], with_positions, smoother_pivoting)[0]
+                     None if states0 is None else [states0], with_positions, smoother_pivoting, camera_model=camera_model,
+                     project_func=project_func)[0]

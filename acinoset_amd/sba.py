@@ -296,16 +296,28 @@ def dense_observations(det, dlc_thresh, min_views=2):
     return keep, uv, cam_idx, pt_start, pt_obs
 
 
+def _dense_camera_model(camera_model, precision):
+    """0 (fisheye) or 1 (pinhole) for the dense entries; the pinhole model is fp64 only - refused before any device work."""
+    from . import fte
+    if camera_model is not None and camera_model not in fte.CAMERA_MODELS:
+        raise ValueError(f"camera_model must be one of {fte.CAMERA_MODELS}")
+    if camera_model == "pinhole" and precision != "f64":
+        raise ValueError(f"the pinhole camera model is solved in fp64 only (precision 'f64', got {precision!r})")
+    return 1 if camera_model == "pinhole" else 0
+
+
 def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_arr, t_arr, dlc_thresh=0.5, precision="f64",
                                               max_iter=100, ftol=1e-10, gtol=1e-10, f_scale=1.0, lam0=1e-3, min_views=2,
-                                              group=None):
+                                              group=None, camera_model=None):
     """calib.py:369-390 on DENSE data, everything resident on the device: det[N, C, 20, 3] detections and
-    points_3d[N, 20, 3] initial points (e.g. ``positions`` of an FTE solve, clips concatenated along N); fisheye model.
-    Returns (points[N, 20, 3] - refined where a point had >= min_views views, input value elsewhere -, r_arr[C, 3, 3],
+    points_3d[N, 20, 3] initial points (e.g. ``positions`` of an FTE solve, clips concatenated along N).  ``camera_model``:
+    "fisheye" (the default) or "pinhole" (cv2.projectPoints, distortion vectors of 4, 5, 8 or 12 entries; fp64 only:
+    ``precision="bf16"`` with pinhole is a ValueError before any device work).  Returns (points[N, 20, 3] - refined where a point had >= min_views views, input value elsewhere -, r_arr[C, 3, 3],
     t_arr[C, 3, 1], info) with info = the solver summary plus ``n_points``, ``n_obs`` and the rms residuals (px)
     before / after.  ``group``: a torch.distributed group whose ranks each hold their own sequences (points sharded,
     cameras replicated: the reduced camera system - (6C)^2 + 6C doubles - is all-reduced every iteration)."""
     global last_info
+    model = _dense_camera_model(camera_model, precision)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     det = calib._to_dev(det, dev)
@@ -322,7 +334,13 @@ def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_ar
     for c in range(n_cams):
         k = np.asarray(k_arr[c], dtype=np.float64)
         intr[c, :4] = [k[0, 0], k[1, 1], k[0, 2], k[1, 2]]
-        intr[c, 4:8] = np.asarray(d_arr[c], dtype=np.float64).reshape(-1)[:4]
+        if model == 0:
+            intr[c, 4:8] = np.asarray(d_arr[c], dtype=np.float64).reshape(-1)[:4]
+        else:                                     # (as _solve for the pinhole model)
+            dist = np.asarray(d_arr[c], dtype=np.float64).reshape(-1)
+            if dist.size not in (4, 5, 8, 12):
+                raise ValueError("pinhole distortion vector must have 4, 5, 8 or 12 entries (cv2.projectPoints)")
+            intr[c, 4:4 + dist.size] = dist
         r = np.asarray(r_arr[c], dtype=np.float64)
         u, _s, vt = np.linalg.svd(calib._rodrigues(r) if r.size == 3 else r)     # (as _solve: cv2.Rodrigues' SO(3) projection)
         Rt[c, :9] = (u @ vt).reshape(-1)
@@ -330,7 +348,7 @@ def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_ar
     d_intr, d_Rt = torch.as_tensor(intr, device=dev), torch.as_tensor(Rt, device=dev)
     d_pts = pts_all[keep].contiguous()
     prm = SbaParams(n_cams=n_cams, optimize_cameras=1, n_points=n_points, n_obs=n_obs, f_scale=float(f_scale),
-                    lam0=float(lam0), ftol=float(ftol), gtol=float(gtol), max_iter=int(max_iter), camera_model=0,
+                    lam0=float(lam0), ftol=float(ftol), gtol=float(gtol), max_iter=int(max_iter), camera_model=model,
                     precision=PRECISIONS[precision])
     nbytes = lib().acino_sba_workspace_bytes(n_cams, n_points, n_obs)
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
@@ -356,18 +374,22 @@ def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_ar
 
 
 def refine_extrinsics_from_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, dlc_thresh=0.5, precision="bf16", fte_iter=60,
-                                 sba_iter=60, fte_kw=None, sba_kw=None):
+                                 sba_iter=60, fte_kw=None, sba_kw=None, camera_model=None):
     """BASELINE config 5 end to end on one GPU: the clips' trajectories are estimated with the current rig (fte_solve_clips:
     all clips as one chain, ``precision`` = "bf16": bf16 residual / Jacobian rows, fp32 accumulation), then the marker
     positions of ALL clips and their above-threshold detections go through one bundle adjustment of points + the shared
-    extrinsics in the same precision mode.  Returns (r_arr, t_arr, info) with info = dict(fte=..., sba=...)."""
+    extrinsics in the same precision mode.  ``camera_model="pinhole"`` runs both stages on the OpenCV pinhole camera; that
+    model is fp64 only, so it needs ``precision="f64"`` (bf16 with pinhole is a ValueError before any device work).
+    Returns (r_arr, t_arr, info) with info = dict(fte=..., sba=...)."""
     from . import fte
+    _dense_camera_model(camera_model, precision)
+    cam_kw = {} if camera_model is None else dict(camera_model=camera_model)
     outs = fte.fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, dlc_thresh=dlc_thresh, max_iter=fte_iter,
-                               return_numpy=False, precision=precision, **(fte_kw or {}))
+                               return_numpy=False, precision=precision, **cam_kw, **(fte_kw or {}))
     dev = torch.device("cuda", torch.cuda.current_device())
     pos = torch.cat([o[0]["positions"] for o in outs], 0)
     det_all = torch.cat([calib._to_dev(d, dev) for d in dets], 0)
     _pts, r_new, t_new, info = bundle_adjust_dense_points_and_extrinsics(det_all, pos, k_arr, d_arr, r_arr, t_arr, dlc_thresh,
                                                                          precision=precision, max_iter=sba_iter,
-                                                                         **(sba_kw or {}))
+                                                                         **cam_kw, **(sba_kw or {}))
     return r_new, t_new, dict(fte=outs[0][1], sba=info)

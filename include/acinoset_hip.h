@@ -452,6 +452,17 @@ int acino_skel_fte_solve_batch(const acino_skel_fte_params* p, int n_clips, cons
                                const double* d_meas, const double* d_w, const double* d_cams24, const double* d_lo,
                                const double* d_hi, double* d_x, double* d_pos, void* d_workspace, size_t workspace_bytes,
                                acino_skel_fte_info* infos, void* stream);
+/* The same two entries on the OpenCV pinhole camera (cv2.projectPoints: k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4, skew ignored,
+ * the tilted model tau_x = tau_y = 0): d_cams32[C][32] pinhole records in place of d_cams24, every other argument, the
+ * workspace size and the solver as above.  fp64. */
+int acino_skel_fte_solve_pinhole(const acino_skel_fte_params* p, const acino_skel_op* h_ops, const int32_t* h_active,
+                                 const double* d_meas, const double* d_w, const double* d_cams32, const double* d_lo,
+                                 const double* d_hi, double* d_x, double* d_pos, void* d_workspace, size_t workspace_bytes,
+                                 acino_skel_fte_info* info, void* stream);
+int acino_skel_fte_solve_batch_pinhole(const acino_skel_fte_params* p, int n_clips, const acino_skel_op* h_ops,
+                                       const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams32,
+                                       const double* d_lo, const double* d_hi, double* d_x, double* d_pos, void* d_workspace,
+                                       size_t workspace_bytes, acino_skel_fte_info* infos, void* stream);
 
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
@@ -477,6 +488,10 @@ size_t acino_sizeof_ekf_params(void);
 size_t acino_ekf_workspace_bytes(int64_t n_frames, int n_seq);
 int acino_ekf_run(const acino_ekf_params* prm, const double* d_det, const double* d_cams24, const double* d_states0,
                   void* d_ws, size_t ws_bytes, double* d_est, double* d_smooth, int32_t* d_outliers, void* stream);
+/* The same filter on the OpenCV pinhole camera: d_cams32[n_cams][32] pinhole records in place of d_cams24; the same
+ * parameters, workspace size and smoother.  fp64. */
+int acino_ekf_run_pinhole(const acino_ekf_params* prm, const double* d_det, const double* d_cams32, const double* d_states0,
+                          void* d_ws, size_t ws_bytes, double* d_est, double* d_smooth, int32_t* d_outliers, void* stream);
 
 /* The same sharded iteration as FOUR fused phases with the three collectives between them; each phase is a fixed
  * launch sequence on caller-owned buffers and is captured into a hipGraph (acino_fte_enable_graph) per buffer set:

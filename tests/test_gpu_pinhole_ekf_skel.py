@@ -1,0 +1,297 @@
+"""GPU (-m gpu): the EKF + RTS smoother, the skeleton FTE and the dense bundle adjustment on the OpenCV pinhole camera.
+
+The EKF (k_ekf_forward_pinhole) against oracle.ekf with the pinhole measurement function (tests/pinhole_ekf_ref.py), the
+skeleton solve (k_skel_assemble_pinhole) against oracle.skel_fte's Levenberg-Marquardt with the pinhole camera
+(tests/pinhole_skel_ref.py), both at the tolerances of their fisheye tests; recovery of synthetic motion; the dense SBA and
+the config 5 chain on a pinhole rig against the scipy oracle; and the default (no keyword) calls equal the fisheye ones bit for
+bit.  The pinhole model is pinned to oracle/camera.py's restatement of cv2.projectPoints, not to OpenCV itself."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import pinhole_ekf_ref as pekf
+import pinhole_fte_ref as pref
+import pinhole_skel_ref as pskel
+from oracle import camera as ocam
+from oracle import sba as osba
+from oracle import skel_fte as osf
+
+pytestmark = pytest.mark.gpu
+
+EKF_TOL = (("x", 5e-6), ("dx", 5e-5), ("ddx", 1e-3), ("smoothed_x", 5e-6), ("smoothed_dx", 5e-5), ("smoothed_ddx", 1e-3))
+
+
+# ---- EKF ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("d", ["D12", "D5"])
+def test_ekf_pinhole_matches_the_reference(gpu_lib, d):
+    from acinoset_amd import calib, ekf
+    dist = getattr(pref, d)
+    cases = ((30, "sprint", 1, slice(None)), (16, "sprint", 3, [0, 2, 5]), (12, "sprint", 4, [1])) if d == "D12" else \
+        ((20, "loop", 2, slice(None)), (16, "sprint", 5, [1, 3, 4]), (12, "loop", 6, [2]))
+    for n, kind, seed, cams in cases:                                               # 6, 3 and 1 cameras
+        seq = pref.pinhole_sequence(n, kind, dist, seed=20210313 + seed)
+        det = seq["det"][:, cams]
+        rig = (seq["K"][cams], seq["D"][cams], seq["R"][cams], seq["t"][cams])
+        s0 = ekf.initial_state(seq["det"], seq["K"], seq["D"], seq["R"], seq["t"], 120.0, 0.5, camera_model="pinhole")
+        want = pekf.ekf(det, *rig, 120.0, 0.5, 2704, s0)
+        got = ekf.ekf(det, *rig, 120.0, 0.5, (2704, 1520), states0=s0, camera_model="pinhole")
+        assert got["outliers_ignored"] == want["outliers_ignored"]
+        for k, tol in EKF_TOL:
+            scale = max(1.0, np.abs(want[k]).max())
+            assert np.abs(got[k] - want[k]).max() < tol * scale, (d, n, kind, k, np.abs(got[k] - want[k]).max())
+        assert np.abs(got["smoothed_positions"] - ekf.get_3d_marker_coords(want["smoothed_x"])).max() < 1e-5
+        seam = ekf.ekf(det, *rig, 120.0, 0.5, (2704, 1520), states0=s0, project_func=calib.project_points)
+        for k in ("x", "dx", "ddx", "smoothed_x", "smoothed_dx", "smoothed_ddx"):
+            assert np.array_equal(seam[k], got[k])
+        assert seam["outliers_ignored"] == got["outliers_ignored"]
+
+
+def test_ekf_pinhole_batch_of_mixed_lengths_equals_the_clips_one_by_one(gpu_lib):
+    from acinoset_amd import ekf
+    seqs = [pref.pinhole_sequence(n, "sprint", pref.D5, seed=7 + i) for i, n in enumerate((12, 12, 9, 2, 1))]
+    rig = (seqs[0]["K"], seqs[0]["D"], seqs[0]["R"], seqs[0]["t"])
+    s0 = [ekf.initial_state(seqs[0]["det"], *rig, 120.0, 0.5, camera_model="pinhole")] * 5
+    batch = ekf.ekf_batch([s["det"] for s in seqs], *rig, 120.0, 0.5, (2704, 1520), states0=s0, camera_model="pinhole")
+    for s, r in zip(seqs, batch):
+        one = ekf.ekf(s["det"], *rig, 120.0, 0.5, (2704, 1520), states0=s0[0], camera_model="pinhole")
+        assert r["outliers_ignored"] == one["outliers_ignored"]
+        for k in ("x", "dx", "ddx", "smoothed_x", "smoothed_dx", "smoothed_ddx"):
+            assert np.array_equal(r[k], one[k])
+
+
+def test_ekf_default_is_the_fisheye_filter_bit_for_bit(gpu_lib):
+    from acinoset_amd import calib, ekf, synth
+    seq = synth.make_sequence(20, "loop", seed=20210315)
+    rig = (seq["K"], seq["D"], seq["R"], seq["t"])
+    base = ekf.ekf(seq["det"], *rig, 120.0, 0.5, (2704, 1520))
+    for kw in (dict(camera_model="fisheye"), dict(project_func=calib.project_points_fisheye)):
+        other = ekf.ekf(seq["det"], *rig, 120.0, 0.5, (2704, 1520), **kw)
+        assert other["outliers_ignored"] == base["outliers_ignored"]
+        for k in ("x", "dx", "ddx", "smoothed_x", "smoothed_dx", "smoothed_ddx"):
+            assert np.array_equal(other[k], base[k])
+
+
+# ---- skeleton FTE -------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fx(golden_dir):
+    g = np.load(os.path.join(golden_dir, "skel_fte_model.npz"))
+    return g, json.loads(str(g["skeleton_json"]))
+
+
+def _tables(det, parts):
+    return [(list(parts), det[:, c]) for c in range(det.shape[1])]
+
+
+def _pin_scene(g, d):
+    return g["K"], np.tile(getattr(pref, d), (len(g["K"]), 1)), g["R"], g["t"]
+
+
+@pytest.mark.parametrize("d", ["D5", "D12"])
+@pytest.mark.parametrize("pairing", ["reference", "name"])
+def test_skel_pinhole_solve_walks_the_reference_lm_path(gpu_lib, fx, golden_dir, pairing, d):
+    """As test_skel_fte.py::test_gpu_solve_walks_the_oracle_lm_path, on the fixture's rig with a pinhole distortion vector:
+    after 0, 1, 2, 5 and 12 iterations the same accepted steps, iterates and costs as the pinhole reference's lm_solve."""
+    from acinoset_amd import build
+    g, sk = fx
+    if pairing == "reference":
+        det, n, sf = g["det"], int(g["n_frames"]), int(g["start_frame"])
+    else:
+        det, n, sf = np.load(os.path.join(golden_dir, "human_dlc_slice.npz"))["det"].astype(np.float64), 40, 60
+    scene = _pin_scene(g, d)
+    model, _ = build.build_model(sk, scene=scene, dlc_tables=_tables(det, g["parts"]), n_frames=n, start_frame=sf,
+                                 pairing=pairing, camera_model="pinhole")
+    assert model.camera_model == "pinhole"
+    prob = pskel.PinholeSkelFTEProblem(sk, model.meas, model.weights, *scene, model.h)
+    act = prob.ACT
+    x0 = model.init_x
+    F0 = prob.evaluate(x0[:, act], need_jac=False)[0]
+    for k in (0, 1, 2, 5, 12):
+        res, info = build.solve_model(model, x0=x0, max_iter=k, ftol=0.0, xtol=0.0, gtol=0.0)
+        xo, oinfo = osf.lm_solve(prob, x0[:, act], max_iter=k, ftol=0.0, xtol=0.0, gtol=0.0) if k else (x0[:, act], dict(cost=F0, accepted=0))
+        assert abs(info["cost_initial"] - F0) < 1e-12 * abs(F0)
+        assert info["accepted"] == oinfo["accepted"], (k, info, oinfo)
+        ctol, xtol_ = (1e-10, 1e-8) if k <= 5 else (1e-8, 1e-6)
+        assert abs(info["cost_final"] - oinfo["cost"]) < ctol * abs(oinfo["cost"]), (k, info["cost_final"], oinfo["cost"])
+        assert np.abs(res["x"][:, act] - xo).max() < xtol_, (k, float(np.abs(res["x"][:, act] - xo).max()))
+        inact = np.setdiff1d(np.arange(48), act)
+        assert np.all(res["x"][:, inact] == 0)
+        out = prob.outputs(xo)
+        assert np.abs(res["positions"] - out["positions"]).max() < xtol_
+
+
+def test_skel_pinhole_batch_equals_the_clips_one_by_one(gpu_lib, fx, golden_dir):
+    from acinoset_amd import build
+    g, sk = fx
+    det = np.load(os.path.join(golden_dir, "human_dlc_slice.npz"))["det"].astype(np.float64)
+    scene = _pin_scene(g, "D5")
+    models = [build.build_model(sk, scene=scene, dlc_tables=_tables(det, g["parts"]), n_frames=40, start_frame=sf,
+                                pairing="name", camera_model="pinhole")[0] for sf in (60, 150, 300)]
+    kw = dict(max_iter=400, ftol=1e-6)
+    one = [build.solve_model(m, **kw) for m in models]
+    many = build.solve_models(models, **kw)
+    for (r1, i1), (rb, ib) in zip(one, many):
+        assert i1 == ib, (i1, ib)
+        assert np.array_equal(r1["x"], rb["x"]) and np.array_equal(r1["positions"], rb["positions"])
+
+
+def test_skel_default_is_the_fisheye_solve_bit_for_bit(gpu_lib, fx):
+    from acinoset_amd import build, calib
+    g, sk = fx
+    kw = dict(scene=(g["K"], g["D"], g["R"], g["t"]), dlc_tables=_tables(g["det"], g["parts"]), n_frames=int(g["n_frames"]),
+              start_frame=int(g["start_frame"]))
+    base, _ = build.build_model(sk, **kw)
+    r0, i0 = build.solve_model(base, max_iter=20)
+    for ckw in (dict(camera_model="fisheye"), dict(project_func=calib.project_points_fisheye)):
+        m, _ = build.build_model(sk, **kw, **ckw)
+        assert np.array_equal(m.init_x, base.init_x) and np.array_equal(m.D, base.D)
+        r1, i1 = build.solve_model(m, max_iter=20)
+        assert i1 == i0 and np.array_equal(r1["x"], r0["x"]) and np.array_equal(r1["positions"], r0["positions"])
+
+
+def _synthetic_motion(g, sk, n_frames, seed=1):
+    """A smooth motion of the fixture's skeleton in front of its two cameras: root drifting at 1.1 m/s, every active angle a
+    sine of 0.05 .. 0.3 rad at 1.5 Hz (inside the model's limits)."""
+    act = osf.active_states(sk)
+    rng = np.random.default_rng(seed)
+    tt = np.arange(n_frames) / 120.0
+    q = np.zeros((n_frames, 48))
+    q[:, :3] = g["init_x"][0, :3] + np.outer(tt, [1.0, 0.5, 0.0])
+    ang = act[act >= 3]
+    q[:, ang] = rng.uniform(0.05, 0.3, ang.size) * np.sin(2 * np.pi * 1.5 * tt[:, None] + rng.uniform(0, 6, ang.size))
+    return q, osf.skeleton_fk_jac(sk, q)[0]
+
+
+def _synthetic_tables(pos, names, scene, project):
+    """One detection table per camera over the pose names (likelihood 0.9, noiseless), projected by ``project``."""
+    K, D, R, t = scene
+    tabs = []
+    for c in range(len(K)):
+        vals = np.zeros(pos.shape[:2] + (3,))
+        vals[..., :2] = project(pos.reshape(-1, 3), K[c], D[c], R[c], t[c]).reshape(pos.shape[:2] + (2,))
+        vals[..., 2] = 0.9
+        tabs.append((list(names), vals))
+    return tabs
+
+
+def test_skel_pinhole_recovers_synthetic_motion_like_the_fisheye_solve(gpu_lib, fx):
+    from acinoset_amd import build, skeleton
+    g, sk = fx
+    N = 40
+    q, pos = _synthetic_motion(g, sk, N)
+    names = skeleton.compile_skeleton(sk)["names"]
+    act = osf.active_states(sk)
+    rng = np.random.default_rng(2)
+    x0 = q.copy()
+    x0[:, :3] += rng.normal(0, 0.02, (1, 3))
+    x0[:, act[act >= 3]] += rng.normal(0, 0.05, (1, int((act >= 3).sum())))
+    err = {}
+    for model_name, scene, project in (("pinhole", _pin_scene(g, "D12"), ocam.project_points),
+                                       ("fisheye", (g["K"], g["D"], g["R"], g["t"]), ocam.project_points_fisheye)):
+        tabs = _synthetic_tables(pos, names, scene, project)
+        m, _ = build.build_model(sk, scene=scene, dlc_tables=tabs, n_frames=N, start_frame=0, pairing="name",
+                                 initial_line=False, camera_model=model_name)
+        res, info = build.solve_model(m, x0=x0, max_iter=300)
+        assert info["status_name"] != "numeric" and info["cost_final"] < 0.1 * info["cost_initial"]
+        err[model_name] = float(np.abs(res["positions"] - pos).max())
+    print(f"synthetic skeleton recovery: max pose error pinhole {err['pinhole'] * 1e3:.3f} mm, fisheye {err['fisheye'] * 1e3:.3f} mm")
+    assert err["fisheye"] < 0.01
+    assert err["pinhole"] <= max(2 * err["fisheye"], 1e-3), err
+
+
+def test_solve_video_on_a_short_pinhole_video(gpu_lib, fx):
+    from acinoset_amd import build, calib, skeleton
+    g, sk = fx
+    N = 160
+    _q, pos = _synthetic_motion(g, sk, N, seed=3)
+    names = skeleton.compile_skeleton(sk)["names"]
+    scene = _pin_scene(g, "D5")
+    tabs = _synthetic_tables(pos, names, scene, ocam.project_points)
+    res, infos, starts = build.solve_video(sk, scene=scene, dlc_tables=tabs, window=60, overlap=20, pairing="name",
+                                           camera_model="pinhole", max_iter=200)
+    assert len(starts) == len(infos) >= 3 and res["positions"].shape == (N, len(names), 3)
+    assert np.isfinite(res["x"]).all() and all(i["status_name"] != "numeric" for i in infos)
+    px = [i["mean_abs_residual_px"] for i in infos]
+    print(f"pinhole video: {len(starts)} windows, mean abs residual px {np.round(px, 3)}")
+    assert np.median(px) < 5.0
+    with pytest.raises(ValueError, match="contradicts"):
+        build.solve_video(sk, scene=scene, dlc_tables=tabs, window=60, overlap=20, camera_model="fisheye",
+                          project_func=calib.project_points)
+
+
+# ---- dense SBA and the config 5 chain -----------------------------------------------------------------------------------
+def _pin_clips(n_clips, n_frames, d=pref.D12, kind="trot"):
+    seqs = [pref.pinhole_sequence(n_frames, kind, d, seed=20210313 + i) for i in range(n_clips)]
+    return seqs, (seqs[0]["K"], seqs[0]["D"], seqs[0]["R"], seqs[0]["t"])
+
+
+def _perturb(R, t, rng, deg=0.5, cm=1.0):
+    Rp = np.array([ocam.rodrigues(rng.normal(0, 1, 3) / np.sqrt(3) * np.radians(deg)) @ R[c] for c in range(len(R))])
+    tp = np.asarray(t, dtype=np.float64).reshape(-1, 3, 1) + rng.normal(0, 1, (len(R), 3, 1)) / np.sqrt(3) * cm * 1e-2
+    return Rp, tp
+
+
+def _pair_distances(r1, t1, r2, t2):
+    rot, dire, lens1, lens2 = [], [], [], []
+    for a in range(len(r1) - 1):
+        Ra, ba = osba.relative_pose(r1, t1, a, a + 1)
+        Rb, bb = osba.relative_pose(r2, t2, a, a + 1)
+        rot.append(np.degrees(np.arccos(np.clip((np.trace(Ra @ Rb.T) - 1) / 2, -1, 1))))
+        dire.append(np.degrees(np.arccos(np.clip(ba @ bb / (np.linalg.norm(ba) * np.linalg.norm(bb)), -1, 1))))
+        lens1.append(np.linalg.norm(ba))
+        lens2.append(np.linalg.norm(bb))
+    lens1, lens2 = np.array(lens1), np.array(lens2)
+    return max(rot), max(dire), float(np.abs(lens1 / lens1.sum() - lens2 / lens2.sum()).max())
+
+
+def test_dense_pinhole_extrinsic_refinement_against_the_scipy_oracle(gpu_lib):
+    from acinoset_amd import fte, sba
+    seqs, (K, D, R, t) = _pin_clips(2, 40)
+    det = np.concatenate([s["det"] for s in seqs], 0)
+    rng = np.random.default_rng(3)
+    pos_true = np.concatenate([np.asarray(fte.cheetah_fk(s["q_true"])) for s in seqs], 0)
+    X0 = pos_true + rng.normal(0, 0.01, pos_true.shape)
+    Rp, tp = _perturb(R, t, rng)
+    seen = det[..., 2].transpose(0, 2, 1) > 0.5
+    kp = seen.sum(-1) >= 2
+    pi, ci, p2 = [], [], []
+    for pid, (n, l) in enumerate(zip(*np.nonzero(kp))):
+        for c in np.nonzero(seen[n, l])[0]:
+            pi.append(pid); ci.append(c); p2.append(det[n, c, l, :2])
+    pi, ci, p2 = np.array(pi), np.array(ci), np.array(p2)
+    pts, rm, tt, info = sba.bundle_adjust_dense_points_and_extrinsics(det, X0, K, D, Rp, tp, 0.5, max_iter=100,
+                                                                      camera_model="pinhole")
+    assert info["n_points"] == int(kp.sum()) and info["n_obs"] == len(pi)
+    end = osba.residuals(pts.cpu().numpy()[kp], rm, tt, K, D, pi, ci, p2, ocam.project_points)
+    assert abs(osba.cauchy_cost(end) - info["cost_final"]) < 1e-9 * info["cost_final"]
+    assert info["status_name"] in ("ftol", "gtol", "max_iter")
+    _p, _r, _t, _res, oopt = osba.bundle_adjust_points_and_extrinsics(p2, X0[kp], pi, ci, K, D, Rp, tp, max_nfev=60,
+                                                                      consistent_mask=True, project_func=ocam.project_points)
+    assert info["cost_final"] <= oopt.cost * (1 + 1e-6), (info["cost_final"], oopt.cost)
+    # the default is the fisheye solve, bit for bit
+    from acinoset_amd import synth
+    fseqs = [synth.make_sequence(30, "trot", seed=20210313 + i) for i in range(2)]
+    fdet = np.concatenate([s["det"] for s in fseqs], 0)
+    fX0 = np.concatenate([np.asarray(fte.cheetah_fk(s["q_true"])) for s in fseqs], 0)
+    fr = (fseqs[0]["K"], fseqs[0]["D"], fseqs[0]["R"], fseqs[0]["t"])
+    a = sba.bundle_adjust_dense_points_and_extrinsics(fdet, fX0, *fr, 0.5, max_iter=30)
+    b = sba.bundle_adjust_dense_points_and_extrinsics(fdet, fX0, *fr, 0.5, max_iter=30, camera_model="fisheye")
+    assert np.array_equal(a[0].cpu().numpy(), b[0].cpu().numpy()) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    assert a[3]["cost_final"] == b[3]["cost_final"]
+
+
+def test_config5_chain_recovers_a_perturbed_pinhole_rig(gpu_lib):
+    from acinoset_amd import sba
+    seqs, (K, D, R, t) = _pin_clips(8, 120)
+    rng = np.random.default_rng(11)
+    Rp, tp = _perturb(R, t, rng)
+    r_new, t_new, info = sba.refine_extrinsics_from_clips([s["det"] for s in seqs], K, D, Rp, tp, seqs[0]["Ts"], precision="f64",
+                                                          fte_iter=40, sba_iter=60, camera_model="pinhole")
+    before = _pair_distances(R, t, Rp, tp)
+    after = _pair_distances(R, t, r_new, t_new)
+    print(f"pinhole config 5 chain: SBA {info['sba']['iterations']} it, rms {info['sba']['rms_before']:.2f} -> "
+          f"{info['sba']['rms_after']:.2f} px; rig error {before} -> {after}")
+    assert info["sba"]["status_name"] in ("ftol", "gtol", "max_iter")
+    assert after[0] < 0.5 * before[0] and after[1] < 0.5 * before[1] and after[2] < 0.5 * before[2], (before, after)
+    assert info["sba"]["rms_after"] < 1.2 * info["sba"]["rms_before"] and info["sba"]["rms_after"] < 6.0
