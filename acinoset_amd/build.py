@@ -18,7 +18,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, calib, fte, io, skeleton
+from . import _lib, calib, io, skeleton
 from ._lib import SkelFteInfo, SkelFteParams, SkelOp, check, lib, ptr, stream_ptr
 
 MODEL_WEIGHT = 0.002        # build.py:186-191
@@ -137,9 +137,9 @@ def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_f
     """build.py:28-304.  ``project_dir`` is the reference's: ``data/4_cam_scene_static_sba.json`` and ``data/*.h5`` are read
     from it (:97-109); alternatively pass ``scene = (k_arr, d_arr, r_arr, t_arr)`` and ``dlc_tables`` = one
     ``(bodyparts, values[frames, K, 3])`` per camera.  ``camera_model`` "fisheye" (the default) or "pinhole", or
-    ``project_func`` = calib.project_points_fisheye / calib.project_points, as fte.camera_model_of; the model keeps it as
+    ``project_func`` = calib.project_points_fisheye / calib.project_points, as calib.camera_model_of; the model keeps it as
     ``camera_model`` and every triangulation here uses it.  Returns ``(model, pose_to_3d)`` as the reference does."""
-    cam_model = fte.camera_model_of(camera_model, project_func)
+    cam_model = calib.camera_model_of(camera_model, project_func)
     prog = skeleton.compile_skeleton(skel_dict)
     names = prog["names"]
     if scene is None:
@@ -231,8 +231,8 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     if len(cam_models) > 1:
         raise ValueError("the models of one batch share the camera model (got " + " and ".join(sorted(cam_models)) + ")")
     cam_model = cam_models.pop()
-    if cam_model not in fte.CAMERA_MODELS:
-        raise ValueError(f"camera_model must be one of {fte.CAMERA_MODELS}")
+    if cam_model not in calib.CAMERAS:
+        raise ValueError(f"camera_model must be one of {calib.CAMERA_MODELS}")
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     m0 = models[0]
@@ -266,13 +266,13 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)   # noqa: E731
     meas = t(np.stack([np.nan_to_num(m.meas, nan=0.0) for m in models]))
     w = t(np.stack([np.where(np.isfinite(m.meas).all(-1), m.weights, 0.0) for m in models]))
-    cams = torch.as_tensor(fte.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
+    cams = torch.as_tensor(calib.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
     lo, hi = t(np.stack([m.lo[:, act] for m in models])), t(np.stack([m.hi[:, act] for m in models]))
     x = t(np.stack([xf[:, act] for xf in xs]))
     pos = torch.empty((B, N, len(m0.names), 3), dtype=torch.float64, device=dev)
     infos = (SkelFteInfo * B)()
     act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
-    solve = lib().acino_skel_fte_solve_batch_pinhole if cam_model == "pinhole" else lib().acino_skel_fte_solve_batch
+    solve = getattr(lib(), calib.CAMERAS[cam_model].skel_fte_solve_batch)
     check(solve(C.byref(p), B, _ops_array(prog), act_c, ptr(meas), ptr(w), ptr(cams), ptr(lo), ptr(hi), ptr(x), ptr(pos),
                 C.c_void_p(ws_ptr), nbytes, infos, stream_ptr()))
     xh, ph = x.cpu().numpy(), pos.cpu().numpy()
@@ -399,7 +399,7 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     ``start_frame`` and ``seams``: the first frame, relative to first_frame, of every stretch taken from a new window), one
     info per window (with ``mean_abs_residual_px`` and ``warm_started_from``)."""
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
-    cam_model = fte.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
+    cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
     build_kw["camera_model"] = cam_model
     if dlc_tables is None:
         paths = sorted(glob.glob(os.path.join(project_dir, "data", "*.h5")))

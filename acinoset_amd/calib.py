@@ -12,6 +12,8 @@ Inputs may be numpy arrays (returned as numpy, like cv2 does) or torch CUDA tens
 tensors, no host round trip).  All arithmetic runs in hand-written HIP kernels through the C ABI of
 libacinoset_hip.so; there is no CPU path - a missing library or GPU raises RuntimeError.
 """
+from typing import Callable, NamedTuple
+
 import numpy as np
 import torch
 
@@ -92,6 +94,13 @@ def pinhole_record(k, d, r, t):
     return rec
 
 
+def pinhole_records(k_arr, d_arr, r_arr, t_arr):
+    k_arr, r_arr = _host(k_arr), _host(r_arr)
+    d_arr = _host(d_arr).reshape(len(k_arr), -1)
+    t_arr = _host(t_arr).reshape(len(k_arr), -1)
+    return np.stack([pinhole_record(k_arr[i], d_arr[i], r_arr[i], t_arr[i]) for i in range(len(k_arr))])
+
+
 def _triangulate(fn_name, rec_fn, img_pts_1, img_pts_2, cam_a, cam_b):
     dev = _dev()
     p1 = _to_dev(img_pts_1, dev).reshape(-1, 2)
@@ -147,14 +156,64 @@ def undistort_points_fisheye(pts, k, d, max_iter=10, eps=1e-8):
     return _ret(out, pts)
 
 
+# --------------------------------------------------------------------------- camera models
+class CameraModel(NamedTuple):
+    """One camera model as the library knows it (include/acinoset_hip.h): code in FteConst and acino_sba_params, record
+    stride and builder, whether its kernels are fp64 only, and the names of the C entry points that exist once per model."""
+    code: int
+    stride: int
+    records: Callable
+    fp64_only: bool
+    fte_create: str
+    ekf_run: str
+    skel_fte_solve_batch: str
+    triangulate_pairs: str
+
+
+CAMERAS = {
+    "fisheye": CameraModel(0, CAM_STRIDE, fisheye_records, False, "acino_fte_create", "acino_ekf_run",
+                           "acino_skel_fte_solve_batch", "acino_triangulate_pairs"),
+    "pinhole": CameraModel(1, PINHOLE_STRIDE, pinhole_records, True, "acino_fte_create_pinhole", "acino_ekf_run_pinhole",
+                           "acino_skel_fte_solve_batch_pinhole", "acino_triangulate_pairs_pinhole"),
+}
+CAMERA_MODELS = tuple(CAMERAS)
+
+
+def camera_model_of(camera_model=None, project_func=None, precision="f64", by_name=False,
+                    seams=(project_points_fisheye, project_points)):
+    """The camera model of a problem, a name in CAMERAS: ``camera_model``, or the one the reference's injection seam
+    ``project_func`` selects, or "fisheye" (the reference's default).  Raises before any device work."""
+    # The entries keep different rules.  FTE, EKF, skeleton: project_func by identity with ``seams``, any other callable is
+    # NotImplementedError.  get_pairwise_3d_points_from_df: its triangulate_func the same way, with the triangulations as
+    # ``seams``.  Sparse SBA (by_name): project_func by __name__ - None or a name containing "fisheye" is fisheye,
+    # "project_points" pinhole -, so the reference package's own functions select a model too.  Dense SBA: camera_model
+    # alone.  Only the FTE and dense SBA entries pass a precision: only they refuse bf16 with the fp64-only pinhole model.
+    if project_func is None:
+        seam = None
+    elif by_name:
+        name = getattr(project_func, "__name__", "")
+        seam = "fisheye" if "fisheye" in name else "pinhole" if name == "project_points" else None
+    else:
+        seam = "fisheye" if project_func is seams[0] else "pinhole" if project_func is seams[1] else None
+    if project_func is not None and seam is None:
+        raise NotImplementedError(f"no HIP kernel for {getattr(project_func, '__name__', project_func)!r}: pass "
+                                  f"acinoset_amd.calib.{seams[0].__name__} or .{seams[1].__name__}")
+    if camera_model is not None and camera_model not in CAMERAS:
+        raise ValueError(f"camera_model must be one of {CAMERA_MODELS}")
+    if camera_model is not None and seam is not None and camera_model != seam:
+        raise ValueError(f"camera_model={camera_model!r} contradicts project_func (the {seam} model)")
+    model = camera_model or seam or "fisheye"
+    if CAMERAS[model].fp64_only and precision != "f64":
+        raise ValueError(f"the {model} camera model is fp64 only (precision 'f64', got {precision!r})")
+    return model
+
+
+def camera_records(model, k_arr, d_arr, r_arr, t_arr):
+    """The rig as the library's camera records of ``model``: [C, 24] fisheye or [C, 32] pinhole (include/acinoset_hip.h)."""
+    return CAMERAS[model].records(k_arr, d_arr, r_arr, t_arr)
+
+
 # --------------------------------------------------------------------------- dense index path
-def pinhole_records(k_arr, d_arr, r_arr, t_arr):
-    k_arr, r_arr = _host(k_arr), _host(r_arr)
-    d_arr = _host(d_arr).reshape(len(k_arr), -1)
-    t_arr = _host(t_arr).reshape(len(k_arr), -1)
-    return np.stack([pinhole_record(k_arr[i], d_arr[i], r_arr[i], t_arr[i]) for i in range(len(k_arr))])
-
-
 def triangulate_pairs_dense(det, thresh, k_arr, d_arr, r_arr, t_arr, return_masks=True, model="fisheye"):
     """det[N,C,L,3] (x, y, likelihood) -> tri[N,L,3] (NaN where no adjacent pair), npairs[N,L] u8,
     pairmask[N,L] u8.  The dense form of get_pairwise_3d_points_from_df (adjacent pairs, mean).
@@ -164,17 +223,16 @@ def triangulate_pairs_dense(det, thresh, k_arr, d_arr, r_arr, t_arr, return_mask
     d = _to_dev(det, dev)
     if d.dim() != 4 or d.shape[-1] != 3:
         raise ValueError("det must be [N, C, L, 3]")
-    if model not in ("fisheye", "pinhole"):
+    if model not in CAMERAS:
         raise ValueError("model must be 'fisheye' or 'pinhole'")
     N, Cn, L, _ = d.shape
-    recs = fisheye_records if model == "fisheye" else pinhole_records
-    cams = torch.as_tensor(recs(k_arr, d_arr, r_arr, t_arr), device=dev)
+    cams = torch.as_tensor(camera_records(model, k_arr, d_arr, r_arr, t_arr), device=dev)
     if cams.shape[0] != Cn:
         raise ValueError("camera count mismatch")
     tri = torch.empty((N, L, 3), dtype=torch.float64, device=dev)
     npairs = torch.empty((N, L), dtype=torch.uint8, device=dev)
     mask = torch.empty((N, L), dtype=torch.uint8, device=dev)
-    fn = lib().acino_triangulate_pairs if model == "fisheye" else lib().acino_triangulate_pairs_pinhole
+    fn = getattr(lib(), CAMERAS[model].triangulate_pairs)
     check(fn(ptr(d), N, Cn, L, float(thresh), ptr(cams), ptr(tri), ptr(npairs), ptr(mask), stream_ptr()))
     if not return_masks:
         return _ret(tri, det)
@@ -248,13 +306,7 @@ def get_pairwise_3d_points_from_df(points_2d_df, k_arr, d_arr, r_arr, t_arr, tri
     Like the reference, raises KeyError when no adjacent pair exists at all.
     """
     import pandas as pd
-    if triangulate_func is None or triangulate_func is triangulate_points_fisheye:
-        model = "fisheye"
-    elif triangulate_func is triangulate_points:
-        model = "pinhole"
-    else:
-        raise NotImplementedError("triangulate_func must be acinoset_amd.calib.triangulate_points_fisheye or "
-                                  "acinoset_amd.calib.triangulate_points (the dense HIP index path has no CPU fallback)")
+    model = camera_model_of(project_func=triangulate_func, seams=(triangulate_points_fisheye, triangulate_points))
     n_cam = len(k_arr)
     det, frames, markers = dataframe_to_dense(points_2d_df, n_cam)
     det[..., 2] = np.where(np.isfinite(det[..., 2]), np.inf, -np.inf)   # presence == valid

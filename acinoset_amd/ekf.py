@@ -43,8 +43,8 @@ def get_3d_marker_coords(x):
 
 def initial_state(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, start_frame=0, camera_model=None, project_func=None):
     """:700-711 - nose position and heading from two regressions of the triangulated nose on the frame number.  The nose is
-    triangulated with the camera model of ``camera_model`` / ``project_func`` (fte.camera_model_of)."""
-    model = fte.camera_model_of(camera_model, project_func)
+    triangulated with the camera model of ``camera_model`` / ``project_func`` (calib.camera_model_of)."""
+    model = calib.camera_model_of(camera_model, project_func)
     tri = calib.triangulate_pairs_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, return_masks=False, model=model)
     nose = tri[:, 2] if isinstance(tri, np.ndarray) else tri[:, 2].cpu().numpy()
     ok = np.isfinite(nose).all(1)
@@ -64,9 +64,9 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
               with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None):
     """Filter + smooth several clips of the same rig.  ``dets``: list of det[N_b, C, 20, 3] (x, y, likelihood);
     clips of equal length share one launch.  Returns one result dictionary per clip.  ``camera_model`` "fisheye" (the
-    default) or "pinhole", or ``project_func`` = calib.project_points_fisheye / calib.project_points (fte.camera_model_of:
+    default) or "pinhole", or ``project_func`` = calib.project_points_fisheye / calib.project_points (calib.camera_model_of:
     a contradiction is a ValueError, any other function NotImplementedError, both before any device work)."""
-    model = fte.camera_model_of(camera_model, project_func)
+    model = calib.camera_model_of(camera_model, project_func)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     B = len(dets)
@@ -75,7 +75,7 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
     for d in dets_d:
         if d.dim() != 4 or d.shape[2] != 20 or d.shape[3] != 3:
             raise ValueError("det must be [N, C, 20, 3] = (x, y, likelihood)")
-    cams = torch.as_tensor(fte.camera_records(model, k_arr, d_arr, r_arr, t_arr), device=dev)
+    cams = torch.as_tensor(calib.camera_records(model, k_arr, d_arr, r_arr, t_arr), device=dev)
     n_cams = int(cams.shape[0])
     if any(int(d.shape[1]) != n_cams for d in dets_d):
         raise ValueError("camera count mismatch between det and the rig")
@@ -107,7 +107,7 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
         est = torch.empty((len(members), n_frames, N_EKF_STATES), dtype=torch.float64, device=dev)
         smo = torch.empty_like(est)
         outl = torch.zeros(len(members), dtype=torch.int32, device=dev)
-        run = lib().acino_ekf_run_pinhole if model == "pinhole" else lib().acino_ekf_run
+        run = getattr(lib(), calib.CAMERAS[model].ekf_run)
         check(run(C.byref(prm), ptr(det), ptr(cams), ptr(st0), C.c_void_p(ws_ptr), nbytes, ptr(est), ptr(smo),
                   C.c_void_p(outl.data_ptr()), stream_ptr()))
         est_h, smo_h, outl_h = est.cpu().numpy(), smo.cpu().numpy(), outl.cpu().numpy()

@@ -33,35 +33,10 @@ R_MEAS = 5.0                          # measurement std-dev, px (:243)
 # acino_fte_params::precision: "f64" everywhere, or BASELINE config 5's "bf16 residuals with fp32 accumulate"
 PRECISIONS = {"f64": 0, "bf16": 1, "bf16_residuals": 2}
 REDESC = (3.0, 10.0, 20.0)            # redescending a, b, c (:25-27)
-CAMERA_MODELS = ("fisheye", "pinhole")
-
-
-def camera_model_of(camera_model=None, project_func=None, precision="f64"):
-    """The camera model of an FTE problem: ``camera_model`` "fisheye" (the default: the reference's pt3d_to_2d) or "pinhole"
-    (cv2.projectPoints, the rational / tangential / thin-prism model), or the reference's injection seam ``project_func``:
-    ``calib.project_points_fisheye`` (or None) selects fisheye, ``calib.project_points`` pinhole.  The pinhole model is
-    assembled in fp64 only.  Raises before any device work."""
-    if project_func is None or project_func is calib.project_points_fisheye:
-        seam = None if project_func is None else "fisheye"
-    elif project_func is calib.project_points:
-        seam = "pinhole"
-    else:
-        raise NotImplementedError("project_func must be acinoset_amd.calib.project_points_fisheye or "
-                                  "acinoset_amd.calib.project_points (the FTE assembly is a HIP kernel per camera model)")
-    if camera_model is not None and camera_model not in CAMERA_MODELS:
-        raise ValueError(f"camera_model must be one of {CAMERA_MODELS}")
-    if camera_model is not None and seam is not None and camera_model != seam:
-        raise ValueError(f"camera_model={camera_model!r} contradicts project_func (the {seam} model)")
-    model = camera_model or seam or "fisheye"
-    if model == "pinhole" and precision != "f64":
-        raise ValueError(f"the pinhole camera model is assembled in fp64 only (precision 'f64', got {precision!r})")
-    return model
-
-
-def camera_records(model, k_arr, d_arr, r_arr, t_arr):
-    """The rig as the library's camera records of ``model``: [C, 24] fisheye or [C, 32] pinhole (include/acinoset_hip.h)."""
-    recs = calib.pinhole_records if model == "pinhole" else calib.fisheye_records
-    return np.ascontiguousarray(recs(k_arr, d_arr, r_arr, t_arr))
+# the camera models live in calib (CAMERAS); these names stay for the callers that import them from here
+CAMERA_MODELS = calib.CAMERA_MODELS
+camera_model_of = calib.camera_model_of
+camera_records = calib.camera_records
 
 
 def bounds45():
@@ -200,7 +175,7 @@ class FTEContext:
         base = self.workspace.data_ptr()
         self._ws_ptr = (base + 255) // 256 * 256
         self._h = C.c_void_p()
-        create = lib().acino_fte_create_pinhole if self.camera_model == "pinhole" else lib().acino_fte_create
+        create = getattr(lib(), calib.CAMERAS[self.camera_model].fte_create)
         check(create(C.byref(self._h), C.byref(self.params), ptr(self.det), ptr(self.cams), C.c_void_p(self._ws_ptr), nbytes,
                      stream_ptr()))
         if self._graph:
@@ -481,6 +456,24 @@ def triangulation_init_active(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, raise
     return xa
 
 
+def _initial_x0(det, x0, init, rig, dlc_thresh, start_frame, camera_model, shape_error):
+    """The initial state [N, 45] of one sequence (numpy): ``x0`` as given, or else the ``init`` guess from ``det`` with the
+    rig's camera model; checked for its shape (``shape_error``) and for zeros in the states with Q == 0."""
+    if x0 is None:
+        if init == "nose_line":
+            x0 = nose_line_init(det, *rig, dlc_thresh, start_frame=start_frame, camera_model=camera_model)
+        elif init == "triangulation":
+            x0 = triangulation_init(det, *rig, dlc_thresh, camera_model=camera_model)
+        else:
+            raise ValueError("init must be 'nose_line' or 'triangulation'")
+    x0 = np.asarray(x0.cpu().numpy() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
+    if x0.shape != (det.shape[0], N_STATES):
+        raise ValueError(shape_error)
+    if np.any(x0[:, np.setdiff1d(np.arange(N_STATES), ACTIVE)] != 0):
+        raise ValueError("states with Q == 0 must start (and stay) at 0 (all_optimizations.py:543)")
+    return x0
+
+
 def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thresh=0.5, start_frame=0,
               max_iter=100, init="nose_line", return_numpy=True, reuse_context=False, camera_model=None, project_func=None,
               **kw):
@@ -500,23 +493,13 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     det = torch.cat([meas_t.to(torch.float64), lik_t.to(torch.float64).unsqueeze(-1).to(meas_t.device)], dim=-1)
     _lib.require_gpu()
     det = det.to(torch.device("cuda", torch.cuda.current_device()))
-    xa0 = init_flag = None
-    if x0 is None:
-        if init == "nose_line":
-            x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frame, camera_model=model)
-        elif init == "triangulation":
-            xa0, init_flag = triangulation_init_active(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, raise_now=False,
-                                                       camera_model=model)   # (stays on the device)
-        else:
-            raise ValueError("init must be 'nose_line' or 'triangulation'")
-    if xa0 is None:
-        x0 = np.asarray(x0.cpu().numpy() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
-        if x0.shape != (det.shape[0], N_STATES):
-            raise ValueError("x0 must be [N, 45]")
-        inactive = np.setdiff1d(np.arange(N_STATES), ACTIVE)
-        if np.any(x0[:, inactive] != 0):
-            raise ValueError("states with Q == 0 must start (and stay) at 0 (all_optimizations.py:543)")
-        xa0 = x0[:, ACTIVE]
+    init_flag = None
+    if x0 is None and init == "triangulation":
+        xa0, init_flag = triangulation_init_active(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, raise_now=False,
+                                                   camera_model=model)   # (stays on the device)
+    else:
+        xa0 = _initial_x0(det, x0, init, (k_arr, d_arr, r_arr, t_arr), dlc_thresh, start_frame, model,
+                          "x0 must be [N, 45]")[:, ACTIVE]
     ctx, cached = _context_for(det, k_arr, d_arr, r_arr, t_arr, Ts, reuse_context, dict(kw, dlc_thresh=dlc_thresh), model)
     kw.pop("trunc_distance", None)
     try:
@@ -565,23 +548,10 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     if any(int(d.shape[0]) != S for d in dets_t):
         raise ValueError("fte_solve_clips needs clips of equal length (use fte_solve_batch otherwise)")
     start_frames = list(start_frames) if start_frames is not None else [0] * B
-    inactive = np.setdiff1d(np.arange(N_STATES), ACTIVE)
     x0_all = np.zeros((B * S, N_STATES))
     for b, det in enumerate(dets_t):
-        if x0s is not None and x0s[b] is not None:
-            x0 = x0s[b]
-        elif init == "nose_line":
-            x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frames[b], camera_model=model)
-        elif init == "triangulation":
-            x0 = triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, camera_model=model)
-        else:
-            raise ValueError("init must be 'nose_line' or 'triangulation'")
-        x0 = np.asarray(x0.cpu().numpy() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
-        if x0.shape != (S, N_STATES):
-            raise ValueError(f"x0 of clip {b} must be [{S}, 45]")
-        if np.any(x0[:, inactive] != 0):
-            raise ValueError("states with Q == 0 must start (and stay) at 0 (all_optimizations.py:543)")
-        x0_all[b * S:(b + 1) * S] = x0
+        x0_all[b * S:(b + 1) * S] = _initial_x0(det, None if x0s is None else x0s[b], init, (k_arr, d_arr, r_arr, t_arr),
+                                                dlc_thresh, start_frames[b], model, f"x0 of clip {b} must be [{S}, 45]")
     dev = torch.device("cuda", torch.cuda.current_device())
     det_all = torch.cat([d.to(device=dev, dtype=torch.float64) for d in dets_t], dim=0)
     polish = kw.pop("polish_f64", False)
@@ -630,25 +600,12 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
         return []
     start_frames = list(start_frames) if start_frames is not None else [0] * B
     streams = [torch.cuda.Stream() for _ in range(max(1, min(int(n_streams), B)))]
-    inactive = np.setdiff1d(np.arange(N_STATES), ACTIVE)
     ctxs = []
     try:
         for b, det in enumerate(dets):
             det = det if isinstance(det, torch.Tensor) else torch.as_tensor(np.asarray(det, dtype=np.float64))
-            if x0s is not None and x0s[b] is not None:
-                x0 = x0s[b]
-            elif init == "nose_line":
-                x0 = nose_line_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, start_frame=start_frames[b],
-                                    camera_model=model)
-            elif init == "triangulation":
-                x0 = triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, camera_model=model)
-            else:
-                raise ValueError("init must be 'nose_line' or 'triangulation'")
-            x0 = np.asarray(x0.cpu().numpy() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
-            if x0.shape != (det.shape[0], N_STATES):
-                raise ValueError(f"x0 of sequence {b} must be [N, 45]")
-            if np.any(x0[:, inactive] != 0):
-                raise ValueError("states with Q == 0 must start (and stay) at 0 (all_optimizations.py:543)")
+            x0 = _initial_x0(det, None if x0s is None else x0s[b], init, (k_arr, d_arr, r_arr, t_arr), dlc_thresh,
+                             start_frames[b], model, f"x0 of sequence {b} must be [N, 45]")
             s = streams[b % len(streams)]
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):

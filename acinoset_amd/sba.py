@@ -27,17 +27,6 @@ last_info = None
 PRECISIONS = {"f64": 0, "bf16": 1}
 
 
-def _camera_model(project_func):
-    """0 = cv2.fisheye model (the reference's sba_board_points_fisheye, app.py:220-223), 1 = cv2.projectPoints pinhole
-    model (sba_board_points, app.py:215-218); decided by the injected projection function's name."""
-    name = getattr(project_func, "__name__", "")
-    if project_func is None or "fisheye" in name:
-        return 0
-    if name == "project_points":
-        return 1
-    raise NotImplementedError(f"GPU bundle adjustment knows the reference's two camera models (got project_func={name})")
-
-
 def _csr_by_point(point_3d_indices, n_points):
     idx = np.asarray(point_3d_indices, dtype=np.int64)
     if idx.size and (idx.min() < 0 or idx.max() >= n_points):
@@ -86,7 +75,7 @@ class ReduceHook:
 
 
 def _solve(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr, optimize_cameras,
-           f_scale, max_iter, ftol, gtol, lam0=1e-3, model=0, group=None, sharded=False, precision="f64", host_checks=True):
+           f_scale, max_iter, ftol, gtol, lam0=1e-3, model="fisheye", group=None, sharded=False, precision="f64", host_checks=True):
     global last_info
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -111,7 +100,7 @@ def _solve(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr,
     for c in range(n_cams):
         k = np.asarray(k_arr[c], dtype=np.float64)
         dist = np.asarray(d_arr[c], dtype=np.float64).reshape(-1)
-        if model == 0:
+        if model == "fisheye":
             if abs(k[0, 1]) > 1e-12 * abs(k[0, 0]):
                 raise NotImplementedError("skewed fisheye intrinsics are not supported by the GPU bundle adjustment "
                                           "(calib.py:78 calibrates with CALIB_FIX_SKEW)")
@@ -132,7 +121,7 @@ def _solve(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr,
 
     prm = SbaParams(n_cams=n_cams, optimize_cameras=int(bool(optimize_cameras)), n_points=n_points, n_obs=n_obs,
                     f_scale=float(f_scale), lam0=float(lam0), ftol=float(ftol), gtol=float(gtol), max_iter=int(max_iter),
-                    camera_model=int(model), precision=PRECISIONS[precision])
+                    camera_model=calib.CAMERAS[model].code, precision=PRECISIONS[precision])
     nbytes = lib().acino_sba_workspace_bytes(n_cams, n_points, n_obs)
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
     ws_ptr = (ws.data_ptr() + 255) // 256 * 256
@@ -165,7 +154,8 @@ def bundle_adjust_points_only(points_2d, points_3d, point_3d_indices, camera_ind
                               project_func=None, f_scale=50, max_iter=200, ftol=1e-15, gtol=1e-10):
     """calib.py:327-341: refine the 3-D points, cameras fixed; Cauchy loss with scale ``f_scale`` px."""
     pts, _r, _t, residuals = _solve(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr,
-                                    False, f_scale, max_iter, ftol, gtol, model=_camera_model(project_func))
+                                    False, f_scale, max_iter, ftol, gtol,
+                                    model=calib.camera_model_of(None, project_func, by_name=True))
     return pts, residuals
 
 
@@ -174,7 +164,7 @@ def bundle_adjust_points_and_extrinsics(points_2d, points_3d, point_3d_indices, 
     """calib.py:369-390: refine the 3-D points and every camera's rotation + translation (Cauchy loss, scale 1).
     ``precision="bf16"``: BASELINE config 5's mixed mode (residual / Jacobian rows in bf16, blocks accumulated in fp32)."""
     return _solve(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr, True, 1.0,
-                  max_iter, ftol, gtol, model=_camera_model(project_func), precision=precision)
+                  max_iter, ftol, gtol, model=calib.camera_model_of(None, project_func, by_name=True), precision=precision)
 
 
 def bundle_adjust_points_and_extrinsics_sharded(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr,
@@ -186,7 +176,8 @@ def bundle_adjust_points_and_extrinsics_sharded(points_2d, points_3d, point_3d_i
     vector - BASELINE config 5's extrinsic refinement over all sequences).  Returns this rank's refined points, the
     common poses and this rank's residuals; ``last_info`` carries the GLOBAL costs."""
     return _solve(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr, True, 1.0,
-                  max_iter, ftol, gtol, model=_camera_model(project_func), group=group, sharded=True, precision=precision)
+                  max_iter, ftol, gtol, model=calib.camera_model_of(None, project_func, by_name=True), group=group,
+                  sharded=True, precision=precision)
 
 
 def prepare_calib_board_data_for_bundle_adjustment(img_pts_arr, fnames_arr, board_shape, k_arr, d_arr, r_arr, t_arr,
@@ -296,16 +287,6 @@ def dense_observations(det, dlc_thresh, min_views=2):
     return keep, uv, cam_idx, pt_start, pt_obs
 
 
-def _dense_camera_model(camera_model, precision):
-    """0 (fisheye) or 1 (pinhole) for the dense entries; the pinhole model is fp64 only - refused before any device work."""
-    from . import fte
-    if camera_model is not None and camera_model not in fte.CAMERA_MODELS:
-        raise ValueError(f"camera_model must be one of {fte.CAMERA_MODELS}")
-    if camera_model == "pinhole" and precision != "f64":
-        raise ValueError(f"the pinhole camera model is solved in fp64 only (precision 'f64', got {precision!r})")
-    return 1 if camera_model == "pinhole" else 0
-
-
 def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_arr, t_arr, dlc_thresh=0.5, precision="f64",
                                               max_iter=100, ftol=1e-10, gtol=1e-10, f_scale=1.0, lam0=1e-3, min_views=2,
                                               group=None, camera_model=None):
@@ -317,7 +298,7 @@ def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_ar
     before / after.  ``group``: a torch.distributed group whose ranks each hold their own sequences (points sharded,
     cameras replicated: the reduced camera system - (6C)^2 + 6C doubles - is all-reduced every iteration)."""
     global last_info
-    model = _dense_camera_model(camera_model, precision)
+    model = calib.camera_model_of(camera_model, precision=precision)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     det = calib._to_dev(det, dev)
@@ -334,7 +315,7 @@ def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_ar
     for c in range(n_cams):
         k = np.asarray(k_arr[c], dtype=np.float64)
         intr[c, :4] = [k[0, 0], k[1, 1], k[0, 2], k[1, 2]]
-        if model == 0:
+        if model == "fisheye":
             intr[c, 4:8] = np.asarray(d_arr[c], dtype=np.float64).reshape(-1)[:4]
         else:                                     # (as _solve for the pinhole model)
             dist = np.asarray(d_arr[c], dtype=np.float64).reshape(-1)
@@ -348,8 +329,8 @@ def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_ar
     d_intr, d_Rt = torch.as_tensor(intr, device=dev), torch.as_tensor(Rt, device=dev)
     d_pts = pts_all[keep].contiguous()
     prm = SbaParams(n_cams=n_cams, optimize_cameras=1, n_points=n_points, n_obs=n_obs, f_scale=float(f_scale),
-                    lam0=float(lam0), ftol=float(ftol), gtol=float(gtol), max_iter=int(max_iter), camera_model=model,
-                    precision=PRECISIONS[precision])
+                    lam0=float(lam0), ftol=float(ftol), gtol=float(gtol), max_iter=int(max_iter),
+                    camera_model=calib.CAMERAS[model].code, precision=PRECISIONS[precision])
     nbytes = lib().acino_sba_workspace_bytes(n_cams, n_points, n_obs)
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
     ws_ptr = (ws.data_ptr() + 255) // 256 * 256
@@ -382,7 +363,7 @@ def refine_extrinsics_from_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, dlc_thres
     model is fp64 only, so it needs ``precision="f64"`` (bf16 with pinhole is a ValueError before any device work).
     Returns (r_arr, t_arr, info) with info = dict(fte=..., sba=...)."""
     from . import fte
-    _dense_camera_model(camera_model, precision)
+    calib.camera_model_of(camera_model, precision=precision)
     cam_kw = {} if camera_model is None else dict(camera_model=camera_model)
     outs = fte.fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, dlc_thresh=dlc_thresh, max_iter=fte_iter,
                                return_numpy=False, precision=precision, **cam_kw, **(fte_kw or {}))
