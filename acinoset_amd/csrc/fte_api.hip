@@ -6,6 +6,7 @@
 
 #include "bcr.hpp"
 #include "chunk.hpp"
+#include "fte_cov.hpp"
 #include "seplevel.hpp"
 
 namespace acino {
@@ -1370,6 +1371,49 @@ int acino_fte_get_grad_hess(acino_fte_ctx* ctx, double* d_g, double* d_h, void* 
   hipLaunchKernelGGL(k_export_HG, dim3(std::max(1, ctx->n_blk_trial)), dim3(256), 0, (hipStream_t)stream, b.state,
                      b.g[0], b.g[1], b.H[0], b.H[1], (int64_t)ctx->h.n_frames, d_g, d_h);
   ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
+
+// ---- posterior covariance (csrc/fte_cov.hip) ----
+static int cov_supported(const FteConst& h) {
+  const char* why = nullptr;
+  if (h.pin_left || h.pin_right || h.n_global != h.n_frames || h.n_offset != 0) why = "a sharded context (one rank's part of a sequence)";
+  else if (h.own_lo != 0 || h.own_hi != h.n_frames) why = "a windowed context (own range)";
+  else if (h.precision != ACINO_PREC_F64) why = "a context in a bf16 precision (switch to ACINO_PREC_F64 and re-evaluate first)";
+  if (why) {
+    set_error("acino_fte_covariance: not supported for %s; it needs the whole sequence in one fp64 context", why);
+    return ACINO_ERR_UNSUPPORTED;
+  }
+  return ACINO_OK;
+}
+
+size_t acino_fte_covariance_workspace_bytes(const acino_fte_params* p) {
+  if (!p || p->n_frames < 1 || p->clip_len < 0 || (p->clip_len > 0 && p->n_frames % p->clip_len != 0)) return 0;
+  return cov_workspace_bytes(p->n_frames, p->clip_len);
+}
+
+int acino_fte_covariance(acino_fte_ctx* ctx, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
+                         double* d_std_pos, void* stream) {
+  ACINO_REQUIRE(ctx && d_ws, "null");
+  ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos, "no output asked for");
+  int rc = cov_supported(ctx->h);
+  if (rc) return rc;
+  const size_t need = cov_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len);
+  if (ws_bytes < need || ((uintptr_t)d_ws & 255) != 0) {
+    set_error("covariance workspace too small or misaligned: need %zu bytes at a 256-byte boundary, got %zu", need, ws_bytes);
+    return ACINO_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const Buffers& b = ctx->b;
+  rc = launch_fte_cov(b.cst, ctx->h, b.state, b.x, b.H, b.g, d_ws, d_cov_x, d_cov_pos, d_std_pos, s);
+  if (rc) return rc;
+  int flag = 0;
+  ACINO_HIP_CHECK(hipMemcpyAsync(&flag, d_ws, sizeof(int), hipMemcpyDeviceToHost, s));
+  ACINO_HIP_CHECK(hipStreamSynchronize(s));
+  if (flag) {
+    set_error("acino_fte_covariance: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive definite)");
+    return ACINO_ERR_NUMERIC;
+  }
   return ACINO_OK;
 }
 

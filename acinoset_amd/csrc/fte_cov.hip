@@ -1,0 +1,406 @@
+// Posterior (Laplace) covariance of an FTE trajectory (gfx950, fp64 matrix cores).
+//
+//   A = blockdiag(H_n) + 2 q (x) D3^T D3      at the context's CURRENT iterate, no Marquardt term; bound-active variables
+//                                             pinned (row and column zeroed, diagonal 1) - oracle.fte.solve_banded, lam = 0
+//
+// is the Gauss-Newton Hessian of the objective F the solve minimises, with its IRLS weights.  The loss is rho(e) = e^2 / 2
+// near 0 (common.hpp: redescending) on residuals scaled by 1 / R_meas, the prior q d^2 with q = 1 / (Q_sigma^2 Ts^4): F is a
+// negative log-posterior AS IT STANDS, and A^-1 is its Laplace covariance with NO further factor - rad^2 for the angles, m^2
+// for the head position and for the marker positions.
+//
+// A is block tridiagonal in nodes of 3 frames (75 unknowns, identity padding to 80; a ragged last node is padded the same
+// way), every clip on a node grid of its own.  With D_k the diagonal blocks and E_k = A[node k, node k + 1] (the constant
+// third-difference stencil: <= 3 terms per entry, diagonal in the state index)
+//
+//   forward   F_0 = D_0,   F_k+1 = D_k+1 - E_k^T F_k^-1 E_k           k_fte_cov_sweep, workgroup (clip, 0)
+//   backward  B_M-1 = D_M-1, B_k-1 = D_k-1 - E_k-1 B_k^-1 E_k-1^T     k_fte_cov_sweep, workgroup (clip, 1), concurrently
+//   combine   Sigma_k = (A^-1)_kk = (F_k + B_k - D_k)^-1              k_fte_cov_combine, one workgroup per node
+//
+// exactly (no truncation, no halo).  The sweeps store, per node, the correction they SUBTRACTED (CF_k = E^T F_k-1^-1 E,
+// CB_k = E B_k+1^-1 E^T; lower tiles), and the combine forms D_k - CF_k - CB_k from them - F_k + B_k - D_k without ever
+// adding and subtracting D_k.  Per node of a sweep: the node in LDS, chol80 (U = L^-T), W = U^T E (a column of W is a
+// combination of <= 3 rows of U), then the correction W^T W on the matrix cores.  NOT E^T (U U^T) E: the explicit inverse
+// carries an error of cond(F) eps, and D - E^T G E cancels - a last node of ONE frame lost 5 digits that way (7e-6 at 7
+// frames, 5e-8 at 121; the numpy restatement shows the same), W^T W is as good as a banded Cholesky solve (3e-10, the
+// references' own spread).  The combine inverts explicitly (G = U U^T is its OUTPUT) and writes the node's three 25 x 25
+// diagonal blocks and J_l Sigma J_l^T for the 20 markers of each of its frames, J_l = d FK_l / d x from the rotation axes
+// the FK chain leaves behind (cheetah_fk.hpp): column a = omega_a x (p_l - pivot_a) for the angles marker l hangs on, e_a
+// for the head position.
+//
+// No workgroup waits for another inside a kernel; a non-positive pivot sets the error word (chol80) and NaNs run through
+// the remaining nodes - no trap, no abort.  A translation unit of its own: nothing here is shared with the LM step's kernels
+// beyond the device functions of dense80.hpp / bcr_dev.hpp, which stay as they are.
+#include "bcr_dev.hpp"
+#include "cheetah_fk.hpp"
+#include "fte_cov.hpp"
+
+namespace acino {
+
+CovGrid cov_grid(int64_t n_frames, int64_t clip_len) {
+  CovGrid g;
+  g.clip = clip_len > 0 ? clip_len : n_frames;
+  g.n_clips = (int)(n_frames / g.clip);
+  g.nodes_per_clip = (int)((g.clip + 2) / 3);
+  return g;
+}
+
+size_t cov_workspace_bytes(int64_t n_frames, int64_t clip_len) {
+  const CovGrid g = cov_grid(n_frames, clip_len);
+  return COV_HEAD_BYTES + 2 * (size_t)g.n_nodes() * COV_TERM_DOUBLES * sizeof(double);
+}
+
+namespace {
+
+struct CovArgs {
+  const FteConst* cst;
+  const acino_fte_state* st;
+  const double *x0, *x1, *g0, *g1, *H0, *H1;
+  double* terms;           // [2][n_nodes][COV_TERM_DOUBLES]: CF, then CB
+  int* err;
+  int n_clips, nodes_per_clip;
+  long long clip;
+  double *cov_x, *cov_pos, *std_pos;
+};
+
+struct CovIn {
+  const double *x, *g, *H;
+};
+__device__ __forceinline__ CovIn cov_inputs(const CovArgs& A) {
+  const int cur = A.st->cur;
+  return CovIn{cur ? A.x1 : A.x0, cur ? A.g1 : A.g0, cur ? A.H1 : A.H0};
+}
+
+constexpr int COV_TAB = 232;                                        // 9 * NP doubles, padded
+constexpr size_t COV_LDS = (2 * MAT + COV_TAB) * sizeof(double) + 2 * BS * sizeof(int);
+
+// code[row] of a node whose first frame is global frame f0 and which holds nlive frames of its clip:
+// 0 free, 1 bound-active (the solve's rule: build_finish, oracle active_set), 2 padding / no such frame
+__device__ __forceinline__ void cov_codes(int* code, const CovIn& in, const FteConst& K, int64_t f0, int nlive, int tid) {
+  if (tid < BS) {
+    int c = 2;
+    const int fr = tid / NP, p = tid % NP;
+    if (tid < 3 * NP && fr < nlive) {
+      const int64_t n = f0 + fr;
+      const double d = in.H[n * HPAIRS + hpair(p, p)];              // (measurement part + smoothness diagonal)
+      const double xv = in.x[(n + HALO) * NP + p], gv = in.g[n * NP + p];
+      const double gtol = GRAD_ZERO_REL * d;
+      c = ((xv <= K.lo[p] && gv > gtol) || (xv >= K.hi[p] && gv < -gtol)) ? 1 : 0;
+    }
+    code[tid] = c;
+  }
+}
+
+// D_k into Lm (ACC: on top of what is there), both triangles.  r0: the node's first frame counted inside its clip.
+template <bool ACC>
+__device__ __forceinline__ void cov_fill(double* Lm, const int* code, const CovIn& in, const FteConst& K, int64_t f0,
+                                         int64_t r0, int64_t clip, int tid) {
+  for (int e = tid; e < BS * BS; e += 256) {
+    const int r = e / BS, c = e % BS;
+    double v = 0.0;
+    if (code[r] | code[c]) {
+      v = r == c ? 1.0 : 0.0;
+    } else {
+      const int fr = r / NP, p = r % NP, fc = c / NP, q = c % NP;
+      if (fr == fc) v = in.H[(f0 + fr) * HPAIRS + hpair(p, q)];
+      else if (p == q) v = 2.0 * K.q_w[p] * band_coef(r0 + (fr < fc ? fr : fc), fr < fc ? fc - fr : fr - fc, clip);
+    }
+    Lm[r * LD + c] = ACC ? Lm[r * LD + c] + v : v;
+  }
+}
+
+// G = U U^T from the factor chol80 left in Lm (U in the diagonal and strictly-upper tiles), all 80 x 80 entries of Gm
+__device__ __forceinline__ void cov_gram(double* Gm, const double* Lm, int wave, int lane) {
+  const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int t = wave + 4 * q;
+    if (t < 15) {
+      const int ib = tri_i(t), jb = tri_j(t);
+      const double* pa = Lm + (ib * 16 + li) * LD + ib * 16 + lk;   // U(ib, k >= ib)[i][kk]
+      const double* pb = Lm + (jb * 16 + li) * LD + ib * 16 + lk;   // U(jb, k >= ib)[j][kk]
+      d4 acc = {0, 0, 0, 0};
+      switch (ib) {
+        case 0: acc = mma_seq<20, false>(acc, pa, 4, pb, 4); break;
+        case 1: acc = mma_seq<16, false>(acc, pa, 4, pb, 4); break;
+        case 2: acc = mma_seq<12, false>(acc, pa, 4, pb, 4); break;
+        case 3: acc = mma_seq<8, false>(acc, pa, 4, pb, 4); break;
+        default: acc = mma_seq<4, false>(acc, pa, 4, pb, 4); break;
+      }
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        Gm[(ib * 16 + lk + 4 * rr) * LD + jb * 16 + li] = acc[rr];
+        if (ib != jb) Gm[(jb * 16 + li) * LD + ib * 16 + lk + 4 * rr] = acc[rr];
+      }
+    }
+  }
+}
+
+}  // namespace
+
+// grid = 2 * n_clips: workgroup (clip, direction).  Walks the clip's nodes; stores the correction of every node it enters.
+__global__ void __launch_bounds__(256) k_fte_cov_sweep(CovArgs A) {
+  extern __shared__ __attribute__((aligned(16))) double cov_smem[];
+  double* Lm = cov_smem;
+  double* Gm = Lm + MAT;
+  double* wtab = Gm + MAT;                          // [(s * 3 + t) * NP + p]: coupling of source frame s with target frame t
+  int* code = reinterpret_cast<int*>(wtab + COV_TAB);
+  int* coden = code + BS;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int clip_i = (int)blockIdx.x >> 1, back = (int)blockIdx.x & 1;
+  if (clip_i >= A.n_clips) return;
+  const FteConst& K = *A.cst;
+  const CovIn in = cov_inputs(A);
+  const int M = A.nodes_per_clip;
+  const int64_t clip = A.clip, fclip = (int64_t)clip_i * clip;
+  const size_t n_nodes = (size_t)A.n_clips * M;
+  int k = back ? M - 1 : 0;
+  {
+    const int64_t r0 = 3 * (int64_t)k;
+    cov_codes(code, in, K, fclip + r0, (int)min((int64_t)3, clip - r0), tid);
+    __syncthreads();
+    cov_fill<false>(Lm, code, in, K, fclip + r0, r0, clip, tid);
+  }
+  for (int step = 0; step + 1 < M; ++step) {
+    const int kn = back ? k - 1 : k + 1;
+    const int64_t rs = 3 * (int64_t)k, rn = 3 * (int64_t)kn;
+    cov_codes(coden, in, K, fclip + rn, (int)min((int64_t)3, clip - rn), tid);
+    __syncthreads();
+    // the stencil between node k (source, frames rs + s) and node kn (target, frames rn + t), pinned variables uncoupled
+    for (int e = tid; e < 9 * NP; e += 256) {
+      const int s = e / (3 * NP), t = (e / NP) % 3, p = e % NP;
+      const int dist = back ? 3 + s - t : 3 + t - s;               // frames between the two, > 3: not coupled
+      double v = 0.0;
+      if (dist <= 3 && code[s * NP + p] == 0 && coden[t * NP + p] == 0)
+        v = 2.0 * K.q_w[p] * band_coef(back ? rn + t : rs + s, dist, clip);
+      wtab[e] = v;
+    }
+    chol80(Lm, tid, A.err);
+    // W = U^T E, stored transposed: row (t, p) of Wt is a combination of <= 3 ROWS of U (upper triangular: the lower tiles
+    // of Lm hold L and are masked out).  Rows 75 .. 79 are zero.
+    for (int e = tid; e < BS * BS; e += 256) {
+      const int c = e / BS, r = e % BS;
+      double v = 0.0;
+      if (c < 3 * NP) {
+        const int t = c / NP, p = c % NP;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+          const int i = s * NP + p;
+          v += r >= i ? wtab[(s * 3 + t) * NP + p] * Lm[i * LD + r] : 0.0;
+        }
+      }
+      Gm[c * LD + r] = v;
+    }
+    __syncthreads();
+    // Lm <- -(W^T W) = -(E^T F^-1 E): the 15 lower tiles on the matrix cores, mirrored
+    {
+      const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int t = wave + 4 * q;
+        if (t < 15) {
+          const int ib = tri_i(t), jb = tri_j(t);
+          d4 acc = {0, 0, 0, 0};
+          acc = mma_seq<20, false>(acc, Gm + (ib * 16 + li) * LD + lk, 4, Gm + (jb * 16 + li) * LD + lk, 4);
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            Lm[(ib * 16 + lk + 4 * rr) * LD + jb * 16 + li] = -acc[rr];
+            if (ib != jb) Lm[(jb * 16 + li) * LD + ib * 16 + lk + 4 * rr] = -acc[rr];
+          }
+        }
+      }
+    }
+    __syncthreads();
+    double2* dst = reinterpret_cast<double2*>(A.terms + ((size_t)back * n_nodes + (size_t)clip_i * M + kn) * COV_TERM_DOUBLES);
+    for (int idx = tid; idx < LOWER_ITEMS; idx += 256) {
+      int row, col;
+      lower_item(idx, row, col);
+      dst[idx] = make_double2(-Lm[row * LD + col], -Lm[row * LD + col + 1]);
+    }
+    __syncthreads();
+    cov_fill<true>(Lm, coden, in, K, fclip + rn, rn, clip, tid);
+    int* sw = code;
+    code = coden;
+    coden = sw;
+    k = kn;
+  }
+}
+
+namespace {
+struct CovFrame {
+  static constexpr bool kHasOm = true;
+  double sc[22][2];
+  double pos[21][3];
+  double om[22][3];
+};
+// the rotation group whose frame carries marker l (cheetah_fk.hpp: fk_columns)
+__device__ __forceinline__ int cov_marker_grp(int l) {
+  // {0, 0, 0, 1, 2, 3, 4, 5, 2, 6, 7, 2, 8, 9, 3, 10 | 11, 3, 12, 13}, one nibble per marker (arithmetic, not a table)
+  const unsigned long long lo = 0xA398276254321000ull, hi = 0xDC3Bull;
+  return (int)(((l < 16 ? lo : hi) >> (4 * (l & 15))) & 15);
+}
+}  // namespace
+
+// grid = n_nodes: Sigma_k = (D_k - CF_k - CB_k)^-1, its three diagonal blocks, the markers' covariances.
+__global__ void __launch_bounds__(256) k_fte_cov_combine(CovArgs A) {
+  extern __shared__ __attribute__((aligned(16))) double cov_smem[];
+  double* Lm = cov_smem;
+  double* Gm = Lm + MAT;
+  double* tr = Gm + MAT;                             // [60][3] diagonal of the markers' covariances
+  int* code = reinterpret_cast<int*>(tr + COV_TAB);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const FteConst& K = *A.cst;
+  const CovIn in = cov_inputs(A);
+  const int M = A.nodes_per_clip;
+  const int node = (int)blockIdx.x, clip_i = node / M, k = node % M;
+  const int64_t clip = A.clip, r0 = 3 * (int64_t)k, f0 = (int64_t)clip_i * clip + r0;
+  const int nlive = (int)min((int64_t)3, clip - r0);
+  const size_t n_nodes = (size_t)A.n_clips * M;
+  cov_codes(code, in, K, f0, nlive, tid);
+  __syncthreads();
+  cov_fill<false>(Lm, code, in, K, f0, r0, clip, tid);
+  __syncthreads();
+  {
+    const bool hf = k > 0, hb = k + 1 < M;
+    const double2* cf = reinterpret_cast<const double2*>(A.terms + (size_t)node * COV_TERM_DOUBLES);
+    const double2* cb = reinterpret_cast<const double2*>(A.terms + (n_nodes + node) * COV_TERM_DOUBLES);
+    for (int idx = tid; idx < LOWER_ITEMS; idx += 256) {
+      int row, col;
+      lower_item(idx, row, col);
+      double2 v = make_double2(0.0, 0.0);
+      if (hf) v = cf[idx];
+      if (hb) {
+        const double2 w = cb[idx];
+        v.x += w.x;
+        v.y += w.y;
+      }
+      Lm[row * LD + col] -= v.x;
+      Lm[row * LD + col + 1] -= v.y;
+      if ((row >> 4) != (col >> 4)) {                // (a diagonal tile holds both of its triangles)
+        Lm[col * LD + row] -= v.x;
+        Lm[(col + 1) * LD + row] -= v.y;
+      }
+    }
+  }
+  __syncthreads();
+  chol80(Lm, tid, A.err);
+  cov_gram(Gm, Lm, wave, lane);
+  __syncthreads();
+  // a variable held at its bound has no spread; padding is not an unknown
+  for (int e = tid; e < BS * BS; e += 256) {
+    const int r = e / BS, c = e % BS;
+    if (code[r] | code[c]) Gm[r * LD + c] = 0.0;
+  }
+  __syncthreads();
+  if (A.cov_x) {
+    for (int e = tid; e < nlive * NP * NP; e += 256) {
+      const int fr = e / (NP * NP), p = (e / NP) % NP, q = e % NP;
+      A.cov_x[(f0 + fr) * (NP * NP) + p * NP + q] = Gm[(fr * NP + p) * LD + fr * NP + q];
+    }
+  }
+  if (!A.cov_pos && !A.std_pos) return;
+  // ---- markers: FK of the node's frames (Lm is free: the factor is spent), J[fr][l][i][p], J Sigma J^T
+  CovFrame* F = reinterpret_cast<CovFrame*>(Lm);
+  double* J = Lm + 3 * ((sizeof(CovFrame) + 7) / 8);
+  for (int task = tid; task < nlive * NP; task += 256) {
+    const int fr = task / NP, a = task % NP;
+    const double xv = in.x[(f0 + fr + HALO) * NP + a];
+    if (a < 3) {
+      F[fr].pos[20][a] = xv;
+    } else {
+      double s, c;
+      sincos(xv, &s, &c);
+      F[fr].sc[a - 3][0] = s;
+      F[fr].sc[a - 3][1] = c;
+    }
+  }
+  __syncthreads();
+  for (int task = tid; task < nlive * 3; task += 256) fk_columns(F[task / 3], task % 3);
+  __syncthreads();
+  for (int task = tid; task < nlive * NL * NP; task += 256) {
+    const int fr = task / (NL * NP), l = (task / NP) % NL, p = task % NP;
+    double j0 = 0.0, j1 = 0.0, j2 = 0.0;
+    if (p < 3) {
+      j0 = p == 0 ? 1.0 : 0.0;
+      j1 = p == 1 ? 1.0 : 0.0;
+      j2 = p == 2 ? 1.0 : 0.0;
+    } else {
+      const int ga = c_state_grp[p], gm = cov_marker_grp(l);
+      if ((c_ancmask[gm] >> ga) & 1) {
+        const double* w = F[fr].om[p - 3];
+        const double* c = F[fr].pos[c_grp_pivot[ga]];
+        const double* m = F[fr].pos[l];
+        const double d0 = m[0] - c[0], d1 = m[1] - c[1], d2 = m[2] - c[2];
+        j0 = w[1] * d2 - w[2] * d1;
+        j1 = w[2] * d0 - w[0] * d2;
+        j2 = w[0] * d1 - w[1] * d0;
+      }
+    }
+    double* Jl = J + (size_t)(fr * NL + l) * 3 * NP;
+    Jl[p] = j0;
+    Jl[NP + p] = j1;
+    Jl[2 * NP + p] = j2;
+  }
+  __syncthreads();
+  if (tid < nlive * NL * 3) {
+    const int fr = tid / (NL * 3), l = (tid / 3) % NL, i = tid % 3;
+    const double* Jl = J + (size_t)(fr * NL + l) * 3 * NP;
+    const double* S = Gm + (fr * NP) * LD + fr * NP;
+    double o0 = 0.0, o1 = 0.0, o2 = 0.0;
+    for (int q = 0; q < NP; ++q) {
+      double t = 0.0;
+      for (int p = 0; p < NP; ++p) t += Jl[i * NP + p] * S[p * LD + q];
+      o0 += t * Jl[q];
+      o1 += t * Jl[NP + q];
+      o2 += t * Jl[2 * NP + q];
+    }
+    if (A.cov_pos) {
+      double* out = A.cov_pos + ((f0 + fr) * NL + l) * 9 + 3 * i;
+      out[0] = o0;
+      out[1] = o1;
+      out[2] = o2;
+    }
+    tr[tid] = i == 0 ? o0 : (i == 1 ? o1 : o2);
+  }
+  __syncthreads();
+  if (A.std_pos && tid < nlive * NL) {
+    const int fr = tid / NL, l = tid % NL;
+    A.std_pos[(f0 + fr) * NL + l] = sqrt(fmax(tr[3 * tid] + tr[3 * tid + 1] + tr[3 * tid + 2], 0.0));
+  }
+}
+
+int launch_fte_cov(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
+                   double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
+                   double* d_std_pos, hipStream_t s) {
+  const CovGrid gr = cov_grid(h_c.n_frames, h_c.clip_len);
+  CovArgs A;
+  A.cst = d_c;
+  A.st = d_st;
+  A.x0 = x[0];
+  A.x1 = x[1];
+  A.g0 = g[0];
+  A.g1 = g[1];
+  A.H0 = H[0];
+  A.H1 = H[1];
+  A.err = reinterpret_cast<int*>(d_ws);
+  A.terms = reinterpret_cast<double*>(reinterpret_cast<char*>(d_ws) + COV_HEAD_BYTES);
+  A.n_clips = gr.n_clips;
+  A.nodes_per_clip = gr.nodes_per_clip;
+  A.clip = gr.clip;
+  A.cov_x = d_cov_x;
+  A.cov_pos = d_cov_pos;
+  A.std_pos = d_std_pos;
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)COV_LDS));
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_combine),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
+  ACINO_HIP_CHECK(hipMemsetAsync(d_ws, 0, COV_HEAD_BYTES, s));
+  if (gr.nodes_per_clip > 1) {
+    hipLaunchKernelGGL(k_fte_cov_sweep, dim3(2 * gr.n_clips), dim3(256), COV_LDS, s, A);
+    ACINO_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_fte_cov_combine, dim3((unsigned)gr.n_nodes()), dim3(256), COV_LDS, s, A);
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
+
+}  // namespace acino

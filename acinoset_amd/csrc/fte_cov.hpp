@@ -1,0 +1,27 @@
+// Posterior (Laplace) covariance of an FTE trajectory: launcher of the kernels in fte_cov.hip.
+#pragma once
+#include "fte_kernels.hpp"
+
+namespace acino {
+
+// Node grid of the covariance pass: every clip (clip_len > 0; otherwise the whole sequence is one clip) is cut into nodes
+// of 3 frames of its own, a ragged last node padded with identity rows.
+struct CovGrid {
+  int n_clips, nodes_per_clip;
+  int64_t clip;                                            // frames per clip
+  int64_t n_nodes() const { return (int64_t)n_clips * nodes_per_clip; }
+};
+CovGrid cov_grid(int64_t n_frames, int64_t clip_len);
+
+// one correction term of one sweep: the 15 lower 16 x 16 tiles of an 80 x 80 block, packed (bcr_dev.hpp: lower_item)
+constexpr size_t COV_TERM_DOUBLES = 2 * 1920;
+constexpr size_t COV_HEAD_BYTES = 256;                     // the error word
+size_t cov_workspace_bytes(int64_t n_frames, int64_t clip_len);
+
+// Sweeps + combine on stream s at the CURRENT iterate (st->cur selects the buffers).  d_ws: cov_workspace_bytes, 256-byte
+// aligned; its first int is the error word (non-zero afterwards: a non-positive pivot).  Any output may be null.
+int launch_fte_cov(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
+                   double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
+                   double* d_std_pos, hipStream_t s);
+
+}  // namespace acino

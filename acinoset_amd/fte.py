@@ -327,6 +327,23 @@ class FTEContext:
         check(lib().acino_fte_get_grad_hess(self._h, ptr(g), ptr(h), stream_ptr()))
         return g, h
 
+    def covariance(self, std_only=False):
+        """Laplace covariance of the CURRENT iterate (acino_fte_covariance): the inverse of the Gauss-Newton matrix
+        blockdiag(H_n) + 2 q (x) D3^T D3 with the bound-active variables pinned, no Marquardt term.  Returns
+        ``(cov_x [N,25,25], cov_pos [N,20,3,3], std_pos [N,20])`` as tensors on the context's device - rad^2 / m^2 and, for
+        ``std_pos`` = sqrt(trace(cov_pos)), metres; ``std_only``: ``(None, None, std_pos)``.  The solver state is not
+        touched.  Whole-sequence fp64 contexts only (RuntimeError otherwise)."""
+        dev = self.device
+        nbytes = lib().acino_fte_covariance_workspace_bytes(C.byref(self.params))
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        cov_x = None if std_only else torch.empty((self.N, N_ACTIVE, N_ACTIVE), dtype=torch.float64, device=dev)
+        cov_pos = None if std_only else torch.empty((self.N, N_MARKERS, 3, 3), dtype=torch.float64, device=dev)
+        std_pos = torch.empty((self.N, N_MARKERS), dtype=torch.float64, device=dev)
+        check(lib().acino_fte_covariance(self._h, C.c_void_p(ws_ptr), nbytes, ptr(cov_x), ptr(cov_pos), ptr(std_pos),
+                                         stream_ptr()))
+        return cov_x, cov_pos, std_pos
+
 
 def cheetah_fk(q):
     """pose_to_3d of :170-186: q[N,45] full state -> positions[N,20,3]."""
@@ -476,7 +493,7 @@ def _initial_x0(det, x0, init, rig, dlc_thresh, start_frame, camera_model, shape
 
 def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thresh=0.5, start_frame=0,
               max_iter=100, init="nose_line", return_numpy=True, reuse_context=False, camera_model=None, project_func=None,
-              **kw):
+              return_cov=False, **kw):
     """The FTE solve call.
 
     meas[N,C,20,2] pixel detections, likelihood[N,C,20], cameras as in the scene file (k_arr[C,3,3],
@@ -486,7 +503,8 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     ``reuse_context``: keep the context (workspace, constants, captured graph) for the next call with the same shapes, rig
     and options (see _CTX_CACHE above).  ``camera_model`` "fisheye" (default) or "pinhole" - then d_arr[C] holds OpenCV
     distortion vectors of 4, 5, 8 or 12 entries -, or the reference's ``project_func`` seam (camera_model_of); the initial
-    guess and the solve both use that model."""
+    guess and the solve both use that model.  ``return_cov``: results gain ``cov_x`` [N,25,25], ``cov_positions`` [N,20,3,3]
+    and ``std_positions`` [N,20] (FTEContext.covariance at the returned x, from the context that produced it)."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     meas_t = meas if isinstance(meas, torch.Tensor) else torch.as_tensor(np.asarray(meas, dtype=np.float64))
     lik_t = likelihood if isinstance(likelihood, torch.Tensor) else torch.as_tensor(np.asarray(likelihood, dtype=np.float64))
@@ -506,6 +524,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         ctx.set_x(xa0)
         info = ctx.solve(max_iter)
         x, pos, dx, ddx = ctx.result()
+        cov = ctx.covariance() if return_cov and info["status"] != 5 else None
     except Exception:
         # (the initial guess's flag is read after the solve - no synchronisation in front of it -, but whatever a solve from an
         #  all-zero start ran into must not hide the real cause)
@@ -521,6 +540,8 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         raise RuntimeError("FTE: block factorisation hit a non-positive pivot")
     conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
     results = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frame)
+    if return_cov:
+        results.update(cov_x=conv(cov[0]), cov_positions=conv(cov[1]), std_positions=conv(cov[2]))
     return results, info
 
 
@@ -531,14 +552,15 @@ def _derivatives(x_clip, Ts):
 
 
 def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
-                    init="nose_line", return_numpy=True, camera_model=None, project_func=None, **kw):
+                    init="nose_line", return_numpy=True, camera_model=None, project_func=None, return_cov=False, **kw):
     """Equal-length clips of one rig solved as ONE problem (BASELINE config 5's batched FTE at full width): the clips
     are laid end to end on the frame axis, the smoothness prior is cut at the clip boundaries (``clip_len``), and the
     block-cyclic reduction runs over the whole chain - every launch is as wide as all clips together, so the narrow
     levels that dominate a single short clip almost vanish.  One Levenberg-Marquardt controller acts on the SUM of the
     clips' costs (the problem is block diagonal: each clip converges to its own optimum, but damping and accept/reject
     are shared, so iterates differ from per-clip solves until convergence).  Returns a list of (results, info).
-    ``camera_model`` / ``project_func`` as in fte_solve."""
+    ``camera_model`` / ``project_func`` / ``return_cov`` as in fte_solve (the covariance per clip: the clips are
+    independent, so it is the one a solve of the clip alone would give at the same x)."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     B = len(dets)
     if B == 0:
@@ -570,20 +592,26 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
         x, pos, _dx, _ddx = ctx.result()
         if info["status"] == 5:
             raise RuntimeError("FTE: block factorisation hit a non-positive pivot")
+        cov = ctx.covariance() if return_cov else None
         conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
         out = []
         for b in range(B):
             xb = x[b * S:(b + 1) * S].contiguous()
             dxb, ddxb = _derivatives(xb, Ts)                     # per clip: no differences across a clip boundary
-            out.append((dict(positions=conv(pos[b * S:(b + 1) * S]), x=conv(xb), dx=conv(dxb), ddx=conv(ddxb),
-                             start_frame=start_frames[b]), dict(info, clips=B, cost_is_sum_over_clips=True)))
+            res = dict(positions=conv(pos[b * S:(b + 1) * S]), x=conv(xb), dx=conv(dxb), ddx=conv(ddxb),
+                       start_frame=start_frames[b])
+            if return_cov:
+                res.update(cov_x=conv(cov[0][b * S:(b + 1) * S]), cov_positions=conv(cov[1][b * S:(b + 1) * S]),
+                           std_positions=conv(cov[2][b * S:(b + 1) * S]))
+            out.append((res, dict(info, clips=B, cost_is_sum_over_clips=True)))
         return out
     finally:
         ctx.close()
 
 
 def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
-                    init="nose_line", n_streams=8, peek_every=8, return_numpy=True, camera_model=None, project_func=None, **kw):
+                    init="nose_line", n_streams=8, peek_every=8, return_numpy=True, camera_model=None, project_func=None,
+                    return_cov=False, **kw):
     """Several independent sequences (BASELINE config 5's "batched FTE": one rig, many clips) solved concurrently
     on ONE GPU.  Every sequence gets its own context and runs on one of ``n_streams`` HIP streams; a Levenberg-
     Marquardt step never synchronises with the host (the accept/reject controller is a device kernel and the step is
@@ -592,7 +620,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     keep all of them busy whatever the stream-to-queue assignment).  ``dets``: list of det[N_b, C, 20, 3] (lengths may differ).
     Returns a list of (results, info) exactly as ``fte_solve`` would for each sequence alone.  The reference solves
     clips one after another (src/all_optimizations.py:22, one ``fte()`` call per data directory).  ``camera_model`` /
-    ``project_func`` as in fte_solve."""
+    ``project_func`` / ``return_cov`` as in fte_solve."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     _lib.require_gpu()
     B = len(dets)
@@ -640,8 +668,11 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
                 if infos[b]["status"] == 5:
                     raise RuntimeError(f"FTE: block factorisation hit a non-positive pivot (sequence {b})")
                 x, pos, dx, ddx = ctxs[b].result()
-                out.append((dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frames[b]),
-                            infos[b]))
+                res = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frames[b])
+                if return_cov:
+                    cov = ctxs[b].covariance()
+                    res.update(cov_x=conv(cov[0]), cov_positions=conv(cov[1]), std_positions=conv(cov[2]))
+                out.append((res, infos[b]))
         for s in streams:
             torch.cuda.current_stream().wait_stream(s)
         return out

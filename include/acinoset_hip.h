@@ -273,6 +273,26 @@ int acino_fte_cost(acino_fte_ctx* ctx, const double* d_x, double* d_cost, void* 
 /* Gradient d_g[N][25] and Gauss-Newton blocks d_h[N][25][25] (measurement part + smoothness diagonal) of the
  * CURRENT iterate, for parity checks.  Either may be NULL. */
 int acino_fte_get_grad_hess(acino_fte_ctx* ctx, double* d_g, double* d_h, void* stream);
+/* Posterior covariance of the trajectory at the context's CURRENT iterate (csrc/fte_cov.hip).  With
+ *   A = blockdiag(H_n) + 2 q (x) D3^T D3   (no Marquardt term; H_n and the active set as the context holds them, the
+ *                                           bound-active variables pinned: row and column zeroed, diagonal 1)
+ * the Gauss-Newton Hessian of the solve's objective F, the outputs are blocks of A^-1, all fp64:
+ *   d_cov_x[N][25][25]     the diagonal 25 x 25 blocks of A^-1, one per frame; rows / columns of variables held at a bound
+ *                          are exactly 0
+ *   d_cov_pos[N][20][3][3] J_l cov_x[n] J_l^T, J_l the 3 x 25 Jacobian of marker l's position (the FK of acino_fk_active)
+ *   d_std_pos[N][20]       sqrt(trace(cov_pos)): one error bar per marker and frame, in metres
+ * Any of the three may be NULL (not all).  UNITS: F counts a scaled residual e as rho(e) = e^2 / 2 near 0 and the prior as
+ * q d^2, i.e. F is a negative log-posterior as it stands and A^-1 its Laplace covariance with no further factor: rad^2 for
+ * angles, m^2 for the head position and the markers.
+ * The call is exact (two pivot sweeps per clip over nodes of 3 frames + one inversion per node), reads the context's current
+ * H / gradient / iterate - after acino_fte_load_x run acino_fte_reevaluate first - and leaves the context's solver state,
+ * buffers and captured graphs untouched.  d_ws: caller-owned, acino_fte_covariance_workspace_bytes(params) bytes, 256-byte
+ * aligned (ACINO_ERR_WORKSPACE otherwise).  It synchronises the stream once, to read the error word: a non-positive pivot
+ * is ACINO_ERR_NUMERIC.  ACINO_ERR_UNSUPPORTED (no launch) for sharded, pinned or windowed contexts (n_global != n_frames,
+ * pin_left / pin_right, own_count > 0) and for contexts in a bf16 precision. */
+size_t acino_fte_covariance_workspace_bytes(const acino_fte_params* p);
+int acino_fte_covariance(acino_fte_ctx* ctx, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
+                         double* d_std_pos, void* stream);
 /* Live per-kernel timing for bench.py: HIP events recorded on the launch stream around every kernel between
  * begin and end.  end synchronises and returns, per class {elim, elim_deep, update0, update, update_deep, backsub0,
  * backsub, trial, assemble, totals, control, backsub_tail, trunc_check, chunk_sweep, sep_combine, chunk_backsub, refine} (one class per kernel), the summed event time in ms, the launch
