@@ -1392,10 +1392,10 @@ size_t acino_fte_covariance_workspace_bytes(const acino_fte_params* p) {
   return cov_workspace_bytes(p->n_frames, p->clip_len);
 }
 
-int acino_fte_covariance(acino_fte_ctx* ctx, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
-                         double* d_std_pos, void* stream) {
-  ACINO_REQUIRE(ctx && d_ws, "null");
-  ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos, "no output asked for");
+// Both covariance entries: checks, one run of the sweeps, the error word.
+static int cov_run(const char* who, acino_fte_ctx* ctx, double ts, void* d_ws, size_t ws_bytes, double* d_cov_x,
+                   double* d_cov_pos, double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel,
+                   double* d_std_vel, void* stream) {
   int rc = cov_supported(ctx->h);
   if (rc) return rc;
   const size_t need = cov_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len);
@@ -1405,16 +1405,39 @@ int acino_fte_covariance(acino_fte_ctx* ctx, void* d_ws, size_t ws_bytes, double
   }
   hipStream_t s = (hipStream_t)stream;
   const Buffers& b = ctx->b;
-  rc = launch_fte_cov(b.cst, ctx->h, b.state, b.x, b.H, b.g, d_ws, d_cov_x, d_cov_pos, d_std_pos, s);
+  rc = launch_fte_cov_rates(b.cst, ctx->h, b.state, b.x, b.H, b.g, d_ws, d_cov_x, d_cov_pos, d_std_pos, d_cov_dx, d_cov_ddx,
+                            d_cov_vel, d_std_vel, ts, s);
   if (rc) return rc;
   int flag = 0;
   ACINO_HIP_CHECK(hipMemcpyAsync(&flag, d_ws, sizeof(int), hipMemcpyDeviceToHost, s));
   ACINO_HIP_CHECK(hipStreamSynchronize(s));
   if (flag) {
-    set_error("acino_fte_covariance: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive definite)");
+    set_error("%s: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive definite)", who);
     return ACINO_ERR_NUMERIC;
   }
   return ACINO_OK;
+}
+
+int acino_fte_covariance(acino_fte_ctx* ctx, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
+                         double* d_std_pos, void* stream) {
+  ACINO_REQUIRE(ctx && d_ws, "null");
+  ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos, "no output asked for");
+  return cov_run("acino_fte_covariance", ctx, 1.0, d_ws, ws_bytes, d_cov_x, d_cov_pos, d_std_pos, nullptr, nullptr, nullptr,
+                 nullptr, stream);
+}
+
+size_t acino_fte_covariance_rates_workspace_bytes(const acino_fte_params* p) {
+  return acino_fte_covariance_workspace_bytes(p);        // (the rates read the sweeps' corrections: nothing more to keep)
+}
+
+int acino_fte_covariance_rates(acino_fte_ctx* ctx, double ts, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
+                               double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel, double* d_std_vel,
+                               void* stream) {
+  ACINO_REQUIRE(ctx && d_ws, "null");
+  ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos || d_cov_dx || d_cov_ddx || d_cov_vel || d_std_vel, "no output asked for");
+  ACINO_REQUIRE(ts > 0, "ts");
+  return cov_run("acino_fte_covariance_rates", ctx, ts, d_ws, ws_bytes, d_cov_x, d_cov_pos, d_std_pos, d_cov_dx, d_cov_ddx,
+                 d_cov_vel, d_std_vel, stream);
 }
 
 int acino_fte_get_result(acino_fte_ctx* ctx, double ts, double* d_x, double* d_pos, double* d_dx, double* d_ddx,

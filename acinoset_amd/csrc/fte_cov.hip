@@ -27,6 +27,8 @@
 // the FK chain leaves behind (cheetah_fk.hpp): column a = omega_a x (p_l - pivot_a) for the angles marker l hangs on, e_a
 // for the head position.
 //
+// k_fte_cov_rates (below the combine) reads the same corrections for the covariance of dx, ddx and the marker velocities.
+//
 // No workgroup waits for another inside a kernel; a non-positive pivot sets the error word (chol80) and NaNs run through
 // the remaining nodes - no trap, no abort.  A translation unit of its own: nothing here is shared with the LM step's kernels
 // beyond the device functions of dense80.hpp / bcr_dev.hpp, which stay as they are.
@@ -60,6 +62,8 @@ struct CovArgs {
   int n_clips, nodes_per_clip;
   long long clip;
   double *cov_x, *cov_pos, *std_pos;
+  double *cov_dx, *cov_ddx, *cov_vel, *std_vel;   // k_fte_cov_rates
+  double inv_ts;
 };
 
 struct CovIn {
@@ -368,9 +372,300 @@ __global__ void __launch_bounds__(256) k_fte_cov_combine(CovArgs A) {
   }
 }
 
+// ---- covariance of dx, ddx and of the marker velocities ----------------------------------------------------------------
+// Every output is c Sigma c^T for coefficient rows c over a window of <= 3 consecutive frames, which lies in node k or
+// across nodes k - 1 and k.  The two nodes, everything before them eliminated into F_k-1 = D_k-1 - CF_k-1 and everything
+// behind them into D_k - CB_k, have the joint precision [[F_k-1, E], [E^T, D_k - CB_k]] whose Schur complement is the
+// S_k = D_k - CF_k - CB_k of the combine.  With F_k-1 = L1 L1^T, S_k = L2 L2^T, U = L^-T and c = [c_a | c_b]:
+//   Y1 = U1^T c_a^T,   Y2 = U2^T (c_b^T - E^T U1 Y1),   c Sigma c^T = Y1^T Y1 + Y2^T Y2
+// - sums of squares from the factors.  NOT differences of blocks of A^-1: neighbouring frames are correlated to 1 - 1e-6
+// and the blocks, good to 4e-10 themselves, leave cov_ddx 1.8e-8 off when differenced (numpy, sprint, 120 frames).
+// The rows go through in batches of 32 (25 states of one frame; 10 markers x 3), stored as rows (Y^T): every product is
+// A B^T on the matrix cores and the batch's Gram matrix stays in the accumulators of the four waves across both terms.
+namespace {
+constexpr int RB = 32;
+constexpr size_t COV_RATES_LDS = (3 * MAT + COV_TAB) * sizeof(double) + 2 * BS * sizeof(int);
+
+// <= 3 window frames with their coefficients; loc = frame counted from the first frame of node k - 1 (0..2: node k - 1,
+// 3..5: node k), -1: no such member
+struct RateBatch {
+  int kind, l0;                                          // 0 dx, 1 ddx, 2 marker velocity; first marker of the batch
+  double c0, c1, c2;
+  int loc0, loc1, loc2;
+};
+
+__device__ __forceinline__ double rate_jac(const CovFrame& F, int l, int i, int p) {
+  if (p < 3) return p == i ? 1.0 : 0.0;
+  const int ga = c_state_grp[p], gm = cov_marker_grp(l);
+  if (!((c_ancmask[gm] >> ga) & 1)) return 0.0;
+  const double* w = F.om[p - 3];
+  const double* c = F.pos[c_grp_pivot[ga]];
+  const double* m = F.pos[l];
+  const double d0 = m[0] - c[0], d1 = m[1] - c[1], d2 = m[2] - c[2];
+  return i == 0 ? w[1] * d2 - w[2] * d1 : (i == 1 ? w[2] * d0 - w[0] * d2 : w[0] * d1 - w[1] * d0);
+}
+
+// entry (row c of the batch, column col of node k - 1 (part 0) / node k (part 1)) of the coefficient matrix.
+// F[0]: last frame of node k - 1, F[1 + t]: frame t of node k
+__device__ __forceinline__ double rate_coef(const RateBatch& B, const CovFrame* F, int c, int part, int col) {
+  if (col >= 3 * NP) return 0.0;
+  const int loc = part * 3 + col / NP, p = col % NP;
+  const double cm = loc == B.loc0 ? B.c0 : (loc == B.loc1 ? B.c1 : (loc == B.loc2 ? B.c2 : 0.0));
+  if (cm == 0.0) return 0.0;
+  if (B.kind < 2) return c == p ? cm : 0.0;
+  if (c >= 30) return 0.0;
+  return cm * rate_jac(F[loc - 2], B.l0 + c / 3, c % 3, p);
+}
+
+// out[32][80] = in[32][80] U (UT = false) or in U^T (UT = true); U upper triangular with zeros below
+template <bool UT>
+__device__ __forceinline__ void rates_mul(double* out, const double* in, const double* U, int wave, int lane) {
+  const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const int t = wave + 4 * q;
+    if (t < 10) {
+      const int ib = t / 5, jb = t % 5;
+      const double* pa = in + (ib * 16 + li) * LD + lk;
+      d4 acc = {0, 0, 0, 0};
+      if (UT) acc = mma_seq<20, false>(acc, pa, 4, U + (jb * 16 + li) * LD + lk, 4);
+      else acc = mma_seq<20, false>(acc, pa, 4, U + lk * LD + jb * 16 + li, 4 * LD);
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) out[(ib * 16 + lk + 4 * rr) * LD + jb * 16 + li] = acc[rr];
+    }
+  }
+}
+
+// tile (wave >> 1, wave & 1) of Y Y^T, Y[32][80]
+__device__ __forceinline__ d4 rates_gram(d4 acc, const double* Y, int wave, int lane) {
+  const int li = lane & 15, lk = lane >> 4;
+  return mma_seq<20, false>(acc, Y + ((wave >> 1) * 16 + li) * LD + lk, 4, Y + ((wave & 1) * 16 + li) * LD + lk, 4);
+}
+
+// Lm -= cf + cb (packed lower tiles; either may be null), both triangles
+__device__ __forceinline__ void cov_sub_terms(double* Lm, const double2* cf, const double2* cb, int tid) {
+  for (int idx = tid; idx < LOWER_ITEMS; idx += 256) {
+    int row, col;
+    lower_item(idx, row, col);
+    double2 v = make_double2(0.0, 0.0);
+    if (cf) v = cf[idx];
+    if (cb) {
+      const double2 w = cb[idx];
+      v.x += w.x;
+      v.y += w.y;
+    }
+    Lm[row * LD + col] -= v.x;
+    Lm[row * LD + col + 1] -= v.y;
+    if ((row >> 4) != (col >> 4)) {
+      Lm[col * LD + row] -= v.x;
+      Lm[(col + 1) * LD + row] -= v.y;
+    }
+  }
+}
+}  // namespace
+
+// grid = n_nodes: cov_dx, cov_ddx, cov_vel, std_vel of the node's frames.  Reads the corrections the sweeps left.
+__global__ void __launch_bounds__(256) k_fte_cov_rates(CovArgs A) {
+  extern __shared__ __attribute__((aligned(16))) double cov_smem[];
+  double* U1 = cov_smem;                             // factor of F_k-1
+  double* U2 = U1 + MAT;                             // factor of S_k
+  double* X = U2 + MAT;                              // two batch buffers [32][LD] and the FK of four frames
+  double* Z = X + RB * LD;
+  CovFrame* F = reinterpret_cast<CovFrame*>(Z + RB * LD);
+  static_assert(2 * RB * LD * sizeof(double) + 4 * sizeof(CovFrame) <= MAT * sizeof(double), "batch buffers + FK frames");
+  double* wtab = X + MAT;
+  int* codep = reinterpret_cast<int*>(wtab + COV_TAB);
+  int* code = codep + BS;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const FteConst& K = *A.cst;
+  const CovIn in = cov_inputs(A);
+  const int M = A.nodes_per_clip;
+  const int node = (int)blockIdx.x, clip_i = node / M, k = node % M;
+  const int64_t clip = A.clip, r0 = 3 * (int64_t)k, f0 = (int64_t)clip_i * clip + r0;
+  const int nlive = (int)min((int64_t)3, clip - r0);
+  const size_t n_nodes = (size_t)A.n_clips * M;
+  const bool prev = k > 0;
+  cov_codes(code, in, K, f0, nlive, tid);
+  if (prev) cov_codes(codep, in, K, f0 - 3, 3, tid);
+  __syncthreads();
+  cov_fill<false>(U2, code, in, K, f0, r0, clip, tid);
+  if (prev) {
+    cov_fill<false>(U1, codep, in, K, f0 - 3, r0 - 3, clip, tid);
+    // E = A[node k - 1, node k] (the sweep's table): source frame s of node k - 1, target frame t of node k
+    for (int e = tid; e < 9 * NP; e += 256) {
+      const int s = e / (3 * NP), t = (e / NP) % 3, p = e % NP;
+      const int dist = 3 + t - s;
+      double v = 0.0;
+      if (dist <= 3 && codep[s * NP + p] == 0 && code[t * NP + p] == 0) v = 2.0 * K.q_w[p] * band_coef(r0 - 3 + s, dist, clip);
+      wtab[e] = v;
+    }
+  }
+  __syncthreads();
+  {
+    const double2* terms = reinterpret_cast<const double2*>(A.terms);
+    const size_t T2 = COV_TERM_DOUBLES / 2;
+    cov_sub_terms(U2, prev ? terms + (size_t)node * T2 : nullptr, k + 1 < M ? terms + (n_nodes + node) * T2 : nullptr, tid);
+    if (k > 1) cov_sub_terms(U1, terms + (size_t)(node - 1) * T2, nullptr, tid);
+  }
+  __syncthreads();
+  chol80(U2, tid, A.err);
+  if (prev) chol80(U1, tid, A.err);
+  // keep U alone: the lower tiles hold L, the diagonal tiles leftovers below their diagonal
+  for (int e = tid; e < BS * BS; e += 256) {
+    const int r = e / BS, c = e % BS;
+    if (r > c) {
+      U2[r * LD + c] = 0.0;
+      if (prev) U1[r * LD + c] = 0.0;
+    }
+  }
+  // FK of the last frame of node k - 1 (slot 0) and of the node's own frames (slots 1 ..)
+  const bool vel = A.cov_vel || A.std_vel;
+  if (vel) {
+    for (int task = tid; task < 4 * NP; task += 256) {
+      const int slot = task / NP, a = task % NP;
+      if (slot == 0 ? prev : slot - 1 < nlive) {
+        const double xv = in.x[(f0 + slot - 1 + HALO) * NP + a];
+        if (a < 3) {
+          F[slot].pos[20][a] = xv;
+        } else {
+          double s, c;
+          sincos(xv, &s, &c);
+          F[slot].sc[a - 3][0] = s;
+          F[slot].sc[a - 3][1] = c;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < 12) {
+      const int slot = tid / 3;
+      if (slot == 0 ? prev : slot - 1 < nlive) fk_columns(F[slot], tid % 3);
+    }
+  }
+  __syncthreads();
+  const double it = A.inv_ts;
+  for (int b = 0; b < 12; ++b) {
+    RateBatch B;
+    const int j = b < 6 ? b >> 1 : (b - 6) >> 1;
+    B.kind = b < 6 ? b & 1 : 2;
+    B.l0 = b < 6 ? 0 : ((b - 6) & 1) * 10;
+    if (j >= nlive) continue;
+    if (B.kind == 0 ? !A.cov_dx : (B.kind == 1 ? !A.cov_ddx : !vel)) continue;
+    // the window (first frame w0 inside the clip) and its coefficients: k_derivatives with its start-up rules
+    const int64_t n = r0 + j;
+    int64_t w0 = 0;
+    B.c0 = B.c1 = B.c2 = 0.0;
+    if (B.kind < 2) {
+      if (clip >= 3) {
+        w0 = n >= 2 ? n - 2 : 0;
+        if (B.kind == 1) {
+          B.c0 = it * it;
+          B.c1 = -2.0 * it * it;
+          B.c2 = it * it;
+        } else if (n >= 2) {
+          B.c1 = -it;
+          B.c2 = it;
+        } else if (n == 1) {
+          B.c0 = -it;
+          B.c1 = it;
+        } else {                                       // dx_0 = dx_1 - Ts ddx_2
+          B.c0 = -2.0 * it;
+          B.c1 = 3.0 * it;
+          B.c2 = -it;
+        }
+      } else if (clip == 2 && B.kind == 0) {           // dx_0 = dx_1, ddx = 0
+        B.c0 = -it;
+        B.c1 = it;
+      }
+    } else if (clip >= 2) {                            // v_n from frames n - 1, n; frame 0 repeats frame 1
+      w0 = (n >= 1 ? n : 1) - 1;
+      B.c0 = -it;
+      B.c1 = it;
+    }
+    const int base = (int)(w0 - (r0 - 3));
+    B.loc0 = B.c0 != 0.0 ? base : -1;
+    B.loc1 = B.c1 != 0.0 ? base + 1 : -1;
+    B.loc2 = B.c2 != 0.0 ? base + 2 : -1;
+    const bool need_a = prev && ((B.loc0 >= 0 && B.loc0 < 3) || (B.loc1 >= 0 && B.loc1 < 3) || (B.loc2 >= 0 && B.loc2 < 3));
+    d4 gacc = {0, 0, 0, 0};
+    if (need_a) {
+      if (B.kind < 2) {
+        // Y1^T = c_a U1 directly: a row combines <= 3 rows of U1 (the pattern of W = U^T E in the sweep)
+        for (int e = tid; e < RB * BS; e += 256) {
+          const int c = e / BS, r = e % BS;
+          double v = 0.0;
+          if (c < NP) {
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+              const double cm = s == B.loc0 ? B.c0 : (s == B.loc1 ? B.c1 : (s == B.loc2 ? B.c2 : 0.0));
+              const int i = s * NP + c;
+              if (cm != 0.0 && codep[i] == 0) v += cm * U1[i * LD + r];
+            }
+          }
+          Z[c * LD + r] = v;
+        }
+      } else {
+        for (int e = tid; e < RB * BS; e += 256) {
+          const int c = e / BS, col = e % BS;
+          X[c * LD + col] = codep[col] == 0 ? rate_coef(B, F, c, 0, col) : 0.0;
+        }
+        __syncthreads();
+        rates_mul<false>(Z, X, U1, wave, lane);
+      }
+      __syncthreads();
+      gacc = rates_gram(gacc, Z, wave, lane);
+      rates_mul<true>(X, Z, U1, wave, lane);           // (U1 Y1)^T
+      __syncthreads();
+    }
+    // (c_b^T - E^T U1 Y1)^T
+    for (int e = tid; e < RB * BS; e += 256) {
+      const int c = e / BS, col = e % BS;
+      double v = code[col] == 0 ? rate_coef(B, F, c, 1, col) : 0.0;
+      if (need_a && col < 3 * NP) {
+        const int t = col / NP, p = col % NP;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) v -= X[c * LD + s * NP + p] * wtab[(s * 3 + t) * NP + p];
+      }
+      Z[c * LD + col] = v;
+    }
+    __syncthreads();
+    rates_mul<false>(X, Z, U2, wave, lane);            // Y2^T
+    __syncthreads();
+    gacc = rates_gram(gacc, X, wave, lane);
+    {
+      const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) Z[((wave >> 1) * 16 + lk + 4 * rr) * LD + (wave & 1) * 16 + li] = gacc[rr];
+    }
+    __syncthreads();
+    if (B.kind < 2) {
+      double* out = (B.kind ? A.cov_ddx : A.cov_dx) + (f0 + j) * (NP * NP);
+      for (int e = tid; e < NP * NP; e += 256) out[e] = Z[(e / NP) * LD + e % NP];
+    } else {
+      if (A.cov_vel && tid < 90) {
+        const int ll = tid / 9, i = (tid / 3) % 3, i2 = tid % 3;
+        A.cov_vel[((f0 + j) * NL + B.l0 + ll) * 9 + 3 * i + i2] = Z[(3 * ll + i) * LD + 3 * ll + i2];
+      }
+      if (A.std_vel && tid < 10) {
+        const int d = 3 * tid;
+        A.std_vel[(f0 + j) * NL + B.l0 + tid] =
+            sqrt(fmax(Z[d * LD + d] + Z[(d + 1) * LD + d + 1] + Z[(d + 2) * LD + d + 2], 0.0));
+      }
+    }
+    __syncthreads();
+  }
+}
+
 int launch_fte_cov(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
                    double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
                    double* d_std_pos, hipStream_t s) {
+  return launch_fte_cov_rates(d_c, h_c, d_st, x, H, g, d_ws, d_cov_x, d_cov_pos, d_std_pos, nullptr, nullptr, nullptr,
+                              nullptr, 1.0, s);
+}
+
+int launch_fte_cov_rates(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
+                         double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
+                         double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel, double* d_std_vel,
+                         double ts, hipStream_t s) {
   const CovGrid gr = cov_grid(h_c.n_frames, h_c.clip_len);
   CovArgs A;
   A.cst = d_c;
@@ -389,6 +684,12 @@ int launch_fte_cov(const FteConst* d_c, const FteConst& h_c, const acino_fte_sta
   A.cov_x = d_cov_x;
   A.cov_pos = d_cov_pos;
   A.std_pos = d_std_pos;
+  A.cov_dx = d_cov_dx;
+  A.cov_ddx = d_cov_ddx;
+  A.cov_vel = d_cov_vel;
+  A.std_vel = d_std_vel;
+  A.inv_ts = 1.0 / ts;
+  const bool blocks = d_cov_x || d_cov_pos || d_std_pos, rates = d_cov_dx || d_cov_ddx || d_cov_vel || d_std_vel;
   ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)COV_LDS));
   ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_combine),
@@ -398,8 +699,16 @@ int launch_fte_cov(const FteConst* d_c, const FteConst& h_c, const acino_fte_sta
     hipLaunchKernelGGL(k_fte_cov_sweep, dim3(2 * gr.n_clips), dim3(256), COV_LDS, s, A);
     ACINO_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_fte_cov_combine, dim3((unsigned)gr.n_nodes()), dim3(256), COV_LDS, s, A);
-  ACINO_LAUNCH_CHECK();
+  if (blocks) {
+    hipLaunchKernelGGL(k_fte_cov_combine, dim3((unsigned)gr.n_nodes()), dim3(256), COV_LDS, s, A);
+    ACINO_LAUNCH_CHECK();
+  }
+  if (rates) {
+    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_rates),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_RATES_LDS));
+    hipLaunchKernelGGL(k_fte_cov_rates, dim3((unsigned)gr.n_nodes()), dim3(256), COV_RATES_LDS, s, A);
+    ACINO_LAUNCH_CHECK();
+  }
   return ACINO_OK;
 }
 

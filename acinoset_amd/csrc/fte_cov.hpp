@@ -24,4 +24,11 @@ int launch_fte_cov(const FteConst* d_c, const FteConst& h_c, const acino_fte_sta
                    double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
                    double* d_std_pos, hipStream_t s);
 
+// The same with the covariances of dx / ddx [N][25][25] and of the marker velocities [N][20][3][3], [N][20] (k_fte_cov_rates:
+// one more workgroup per node after the SAME sweeps; same workspace).  ts: the frame period the rates are taken with.
+int launch_fte_cov_rates(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
+                         double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
+                         double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel, double* d_std_vel,
+                         double ts, hipStream_t s);
+
 }  // namespace acino

@@ -344,6 +344,50 @@ class FTEContext:
                                          stream_ptr()))
         return cov_x, cov_pos, std_pos
 
+    def covariance_rates(self, std_only=False, with_cov=False):
+        """Laplace covariance of what ``result()`` returns as dx / ddx, and of the marker velocities
+        (acino_fte_covariance_rates; same matrix, same sweeps as ``covariance``).  Returns ``(cov_dx [N,25,25],
+        cov_ddx [N,25,25], cov_vel [N,20,3,3], std_vel [N,20])`` on the context's device - (rad/s)^2, (m/s)^2, (rad/s^2)^2,
+        (m/s^2)^2; ``std_vel`` = sqrt(trace(cov_vel)) in m/s; ``std_only``: ``(None, None, None, std_vel)``.  dx_n, ddx_n
+        come from the frames (n-2, n-1, n) of the frame's own clip, frames 0 and 1 of a clip from its first three frames
+        by the start-up rules of ``result()``; the velocity of frame 0 repeats frame 1.  ``with_cov``: the three arrays
+        of ``covariance()`` from the SAME call (one run of the sweeps), returned as a second tuple."""
+        dev = self.device
+        nbytes = lib().acino_fte_covariance_rates_workspace_bytes(C.byref(self.params))
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+
+        def new(*shape, skip=False):
+            return None if skip else torch.empty((self.N,) + shape, dtype=torch.float64, device=dev)
+
+        cov_x = new(N_ACTIVE, N_ACTIVE, skip=std_only or not with_cov)
+        cov_pos = new(N_MARKERS, 3, 3, skip=std_only or not with_cov)
+        std_pos = new(N_MARKERS, skip=not with_cov)
+        cov_dx = new(N_ACTIVE, N_ACTIVE, skip=std_only)
+        cov_ddx = new(N_ACTIVE, N_ACTIVE, skip=std_only)
+        cov_vel = new(N_MARKERS, 3, 3, skip=std_only)
+        std_vel = new(N_MARKERS)
+        check(lib().acino_fte_covariance_rates(self._h, self.Ts, C.c_void_p(ws_ptr), nbytes, ptr(cov_x), ptr(cov_pos),
+                                               ptr(std_pos), ptr(cov_dx), ptr(cov_ddx), ptr(cov_vel), ptr(std_vel),
+                                               stream_ptr()))
+        rates = (cov_dx, cov_ddx, cov_vel, std_vel)
+        return (rates, (cov_x, cov_pos, std_pos)) if with_cov else rates
+
+    def _covariances(self, return_cov, return_rate_cov):
+        """(cov, rate_cov) as the solve entries return them: either may be None; both from one call when both are asked."""
+        if return_rate_cov:
+            out = self.covariance_rates(with_cov=bool(return_cov))
+            return (out[1], out[0]) if return_cov else (None, out)
+        return (self.covariance() if return_cov else None), None
+
+
+def _cov_results(res, cov, rate_cov, conv, sl=slice(None)):
+    if cov is not None:
+        res.update(cov_x=conv(cov[0][sl]), cov_positions=conv(cov[1][sl]), std_positions=conv(cov[2][sl]))
+    if rate_cov is not None:
+        res.update(cov_dx=conv(rate_cov[0][sl]), cov_ddx=conv(rate_cov[1][sl]), cov_velocities=conv(rate_cov[2][sl]),
+                   std_velocities=conv(rate_cov[3][sl]))
+
 
 def cheetah_fk(q):
     """pose_to_3d of :170-186: q[N,45] full state -> positions[N,20,3]."""
@@ -493,7 +537,7 @@ def _initial_x0(det, x0, init, rig, dlc_thresh, start_frame, camera_model, shape
 
 def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thresh=0.5, start_frame=0,
               max_iter=100, init="nose_line", return_numpy=True, reuse_context=False, camera_model=None, project_func=None,
-              return_cov=False, **kw):
+              return_cov=False, return_rate_cov=False, **kw):
     """The FTE solve call.
 
     meas[N,C,20,2] pixel detections, likelihood[N,C,20], cameras as in the scene file (k_arr[C,3,3],
@@ -504,7 +548,10 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     and options (see _CTX_CACHE above).  ``camera_model`` "fisheye" (default) or "pinhole" - then d_arr[C] holds OpenCV
     distortion vectors of 4, 5, 8 or 12 entries -, or the reference's ``project_func`` seam (camera_model_of); the initial
     guess and the solve both use that model.  ``return_cov``: results gain ``cov_x`` [N,25,25], ``cov_positions`` [N,20,3,3]
-    and ``std_positions`` [N,20] (FTEContext.covariance at the returned x, from the context that produced it)."""
+    and ``std_positions`` [N,20] (FTEContext.covariance at the returned x, from the context that produced it).
+    ``return_rate_cov``: results gain ``cov_dx`` / ``cov_ddx`` [N,25,25], ``cov_velocities`` [N,20,3,3] and
+    ``std_velocities`` [N,20] (FTEContext.covariance_rates: the error bars of dx, ddx and of the markers' velocities);
+    with ``return_cov`` as well both sets come from one call."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     meas_t = meas if isinstance(meas, torch.Tensor) else torch.as_tensor(np.asarray(meas, dtype=np.float64))
     lik_t = likelihood if isinstance(likelihood, torch.Tensor) else torch.as_tensor(np.asarray(likelihood, dtype=np.float64))
@@ -524,7 +571,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         ctx.set_x(xa0)
         info = ctx.solve(max_iter)
         x, pos, dx, ddx = ctx.result()
-        cov = ctx.covariance() if return_cov and info["status"] != 5 else None
+        cov, rate_cov = ctx._covariances(return_cov, return_rate_cov) if info["status"] != 5 else (None, None)
     except Exception:
         # (the initial guess's flag is read after the solve - no synchronisation in front of it -, but whatever a solve from an
         #  all-zero start ran into must not hide the real cause)
@@ -540,8 +587,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         raise RuntimeError("FTE: block factorisation hit a non-positive pivot")
     conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
     results = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frame)
-    if return_cov:
-        results.update(cov_x=conv(cov[0]), cov_positions=conv(cov[1]), std_positions=conv(cov[2]))
+    _cov_results(results, cov, rate_cov, conv)
     return results, info
 
 
@@ -552,15 +598,16 @@ def _derivatives(x_clip, Ts):
 
 
 def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
-                    init="nose_line", return_numpy=True, camera_model=None, project_func=None, return_cov=False, **kw):
+                    init="nose_line", return_numpy=True, camera_model=None, project_func=None, return_cov=False,
+                    return_rate_cov=False, **kw):
     """Equal-length clips of one rig solved as ONE problem (BASELINE config 5's batched FTE at full width): the clips
     are laid end to end on the frame axis, the smoothness prior is cut at the clip boundaries (``clip_len``), and the
     block-cyclic reduction runs over the whole chain - every launch is as wide as all clips together, so the narrow
     levels that dominate a single short clip almost vanish.  One Levenberg-Marquardt controller acts on the SUM of the
     clips' costs (the problem is block diagonal: each clip converges to its own optimum, but damping and accept/reject
     are shared, so iterates differ from per-clip solves until convergence).  Returns a list of (results, info).
-    ``camera_model`` / ``project_func`` / ``return_cov`` as in fte_solve (the covariance per clip: the clips are
-    independent, so it is the one a solve of the clip alone would give at the same x)."""
+    ``camera_model`` / ``project_func`` / ``return_cov`` / ``return_rate_cov`` as in fte_solve (the covariance per clip: the
+    clips are independent, so it is the one a solve of the clip alone would give at the same x)."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     B = len(dets)
     if B == 0:
@@ -592,7 +639,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
         x, pos, _dx, _ddx = ctx.result()
         if info["status"] == 5:
             raise RuntimeError("FTE: block factorisation hit a non-positive pivot")
-        cov = ctx.covariance() if return_cov else None
+        cov, rate_cov = ctx._covariances(return_cov, return_rate_cov)
         conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
         out = []
         for b in range(B):
@@ -600,9 +647,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
             dxb, ddxb = _derivatives(xb, Ts)                     # per clip: no differences across a clip boundary
             res = dict(positions=conv(pos[b * S:(b + 1) * S]), x=conv(xb), dx=conv(dxb), ddx=conv(ddxb),
                        start_frame=start_frames[b])
-            if return_cov:
-                res.update(cov_x=conv(cov[0][b * S:(b + 1) * S]), cov_positions=conv(cov[1][b * S:(b + 1) * S]),
-                           std_positions=conv(cov[2][b * S:(b + 1) * S]))
+            _cov_results(res, cov, rate_cov, conv, slice(b * S, (b + 1) * S))
             out.append((res, dict(info, clips=B, cost_is_sum_over_clips=True)))
         return out
     finally:
@@ -611,7 +656,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
 
 def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
                     init="nose_line", n_streams=8, peek_every=8, return_numpy=True, camera_model=None, project_func=None,
-                    return_cov=False, **kw):
+                    return_cov=False, return_rate_cov=False, **kw):
     """Several independent sequences (BASELINE config 5's "batched FTE": one rig, many clips) solved concurrently
     on ONE GPU.  Every sequence gets its own context and runs on one of ``n_streams`` HIP streams; a Levenberg-
     Marquardt step never synchronises with the host (the accept/reject controller is a device kernel and the step is
@@ -620,7 +665,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     keep all of them busy whatever the stream-to-queue assignment).  ``dets``: list of det[N_b, C, 20, 3] (lengths may differ).
     Returns a list of (results, info) exactly as ``fte_solve`` would for each sequence alone.  The reference solves
     clips one after another (src/all_optimizations.py:22, one ``fte()`` call per data directory).  ``camera_model`` /
-    ``project_func`` / ``return_cov`` as in fte_solve."""
+    ``project_func`` / ``return_cov`` / ``return_rate_cov`` as in fte_solve."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     _lib.require_gpu()
     B = len(dets)
@@ -669,9 +714,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
                     raise RuntimeError(f"FTE: block factorisation hit a non-positive pivot (sequence {b})")
                 x, pos, dx, ddx = ctxs[b].result()
                 res = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frames[b])
-                if return_cov:
-                    cov = ctxs[b].covariance()
-                    res.update(cov_x=conv(cov[0]), cov_positions=conv(cov[1]), std_positions=conv(cov[2]))
+                _cov_results(res, *ctxs[b]._covariances(return_cov, return_rate_cov), conv)
                 out.append((res, infos[b]))
         for s in streams:
             torch.cuda.current_stream().wait_stream(s)

@@ -293,6 +293,27 @@ int acino_fte_get_grad_hess(acino_fte_ctx* ctx, double* d_g, double* d_h, void* 
 size_t acino_fte_covariance_workspace_bytes(const acino_fte_params* p);
 int acino_fte_covariance(acino_fte_ctx* ctx, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
                          double* d_std_pos, void* stream);
+/* The same call with error bars for what a user takes from dx / ddx and from the speed of a marker (a superset: any of
+ * the seven outputs may be NULL, not all; ONE run of the sweeps serves them all; the first three are bit-identical to
+ * acino_fte_covariance).  ts > 0: the frame period, as in acino_fte_get_result.  With Sigma_win the 75 x 75 block of
+ * A^-1 over a window of three consecutive frames of the frame's own clip (rows / columns of pinned variables 0):
+ *   d_cov_dx[N][25][25]    C Sigma_win C^T, C = c (x) I_25 with the three scalars that make dx_n out of the window;
+ *                          (rad/s)^2, (m/s)^2
+ *   d_cov_ddx[N][25][25]   the same for ddx_n; (rad/s^2)^2, (m/s^2)^2
+ *   d_cov_vel[N][20][3][3] covariance of the marker velocity v_n,l = (p_l(x_n) - p_l(x_n-1)) / ts, linearised:
+ *                          (J_l(x_n) e_n - J_l(x_n-1) e_n-1) / ts for the estimation errors e; (m/s)^2
+ *   d_std_vel[N][20]       sqrt(trace(cov_vel)), m/s
+ * dx_n / ddx_n are those of acino_fte_get_result / acino_fte_derivatives taken per clip.  n >= 2: the window is
+ * (x_n-2, x_n-1, x_n), dx_n = (x_n - x_n-1) / ts, ddx_n = (x_n - 2 x_n-1 + x_n-2) / ts^2.  START-UP FRAMES n = 0, 1 of a
+ * clip: the window is frames 0..2 of the clip, ddx_0 = ddx_1 = ddx_2, dx_1 = (x_1 - x_0) / ts, dx_0 = dx_1 - ts ddx_2;
+ * cov_vel / std_vel of frame 0 repeat frame 1.  Clips of 2 frames: ddx = 0, dx_0 = dx_1; of 1 frame: everything 0.
+ * No further factor (see above).  The velocity of two neighbouring frames is NOT bounded by cov_x: the prior correlates
+ * them almost perfectly, and sqrt(2 diag cov_x) / ts overstates the spread of dx by orders of magnitude.
+ * Workspace (the same byte count), statuses, synchronisation and what the call leaves untouched: as acino_fte_covariance. */
+size_t acino_fte_covariance_rates_workspace_bytes(const acino_fte_params* p);
+int acino_fte_covariance_rates(acino_fte_ctx* ctx, double ts, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
+                               double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel, double* d_std_vel,
+                               void* stream);
 /* Live per-kernel timing for bench.py: HIP events recorded on the launch stream around every kernel between
  * begin and end.  end synchronises and returns, per class {elim, elim_deep, update0, update, update_deep, backsub0,
  * backsub, trial, assemble, totals, control, backsub_tail, trunc_check, chunk_sweep, sep_combine, chunk_backsub, refine} (one class per kernel), the summed event time in ms, the launch
