@@ -150,6 +150,8 @@ SIGNATURES = {
     "acino_fte_covariance": (_I, [_P, _P, _Z, _P, _P, _P, _P]),
     "acino_fte_covariance_rates_workspace_bytes": (_Z, [C.POINTER(FteParams)]),
     "acino_fte_covariance_rates": (_I, [_P, C.c_double, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "acino_fte_sample_workspace_bytes": (_Z, [C.POINTER(FteParams)]),
+    "acino_fte_sample": (_I, [_P, _L, _P, _P, _Z, _P, _P, _P]),
     "acino_fte_derivatives": (_I, [_P, _L, _D, _P, _P, _P]),
     "acino_fte_load_x": (_I, [_P, _P, _P]),
     "acino_fte_set_halo": (_I, [_P, _I, _P, _P, _P]),

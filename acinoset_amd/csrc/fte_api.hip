@@ -1375,13 +1375,13 @@ int acino_fte_get_grad_hess(acino_fte_ctx* ctx, double* d_g, double* d_h, void* 
 }
 
 // ---- posterior covariance (csrc/fte_cov.hip) ----
-static int cov_supported(const FteConst& h) {
+static int cov_supported(const FteConst& h, const char* who = "acino_fte_covariance") {
   const char* why = nullptr;
   if (h.pin_left || h.pin_right || h.n_global != h.n_frames || h.n_offset != 0) why = "a sharded context (one rank's part of a sequence)";
   else if (h.own_lo != 0 || h.own_hi != h.n_frames) why = "a windowed context (own range)";
   else if (h.precision != ACINO_PREC_F64) why = "a context in a bf16 precision (switch to ACINO_PREC_F64 and re-evaluate first)";
   if (why) {
-    set_error("acino_fte_covariance: not supported for %s; it needs the whole sequence in one fp64 context", why);
+    set_error("%s: not supported for %s; it needs the whole sequence in one fp64 context", who, why);
     return ACINO_ERR_UNSUPPORTED;
   }
   return ACINO_OK;
@@ -1438,6 +1438,42 @@ int acino_fte_covariance_rates(acino_fte_ctx* ctx, double ts, void* d_ws, size_t
   ACINO_REQUIRE(ts > 0, "ts");
   return cov_run("acino_fte_covariance_rates", ctx, ts, d_ws, ws_bytes, d_cov_x, d_cov_pos, d_std_pos, d_cov_dx, d_cov_ddx,
                  d_cov_vel, d_std_vel, stream);
+}
+
+size_t acino_fte_sample_workspace_bytes(const acino_fte_params* p) {
+  return acino_fte_covariance_workspace_bytes(p);        // (U_k^T takes the place of the backward sweep's corrections)
+}
+
+int acino_fte_sample(acino_fte_ctx* ctx, int64_t n_samples, const double* d_z, void* d_ws, size_t ws_bytes,
+                     double* d_x_samples, double* d_pos_samples, void* stream) {
+  ACINO_REQUIRE(ctx && d_ws, "null");
+  ACINO_REQUIRE(n_samples >= 1, "n_samples");
+  ACINO_REQUIRE(d_z && d_x_samples, "null buffer");
+  ACINO_REQUIRE((n_samples + 63) / 64 <= 65535, "n_samples (at most 65535 panels of 64)");
+  ACINO_REQUIRE(d_z != d_x_samples, "d_z must not alias d_x_samples");
+  int rc = cov_supported(ctx->h, "acino_fte_sample");
+  if (rc) return rc;
+  const size_t need = cov_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len);
+  if (ws_bytes < need || ((uintptr_t)d_ws & 255) != 0) {
+    set_error("sample workspace too small or misaligned: need %zu bytes at a 256-byte boundary, got %zu", need, ws_bytes);
+    return ACINO_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const Buffers& b = ctx->b;
+  rc = launch_fte_sample(b.cst, ctx->h, b.state, b.x, b.H, b.g, d_ws, n_samples, d_z, d_x_samples, s);
+  if (rc) return rc;
+  if (d_pos_samples) {
+    rc = launch_fk_active(d_x_samples - HALO * NP, n_samples * (int64_t)ctx->h.n_frames, d_pos_samples, s);
+    if (rc) return rc;
+  }
+  int flag = 0;
+  ACINO_HIP_CHECK(hipMemcpyAsync(&flag, d_ws, sizeof(int), hipMemcpyDeviceToHost, s));
+  ACINO_HIP_CHECK(hipStreamSynchronize(s));
+  if (flag) {
+    set_error("acino_fte_sample: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive definite)");
+    return ACINO_ERR_NUMERIC;
+  }
+  return ACINO_OK;
 }
 
 int acino_fte_get_result(acino_fte_ctx* ctx, double ts, double* d_x, double* d_pos, double* d_dx, double* d_ddx,

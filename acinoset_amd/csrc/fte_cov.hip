@@ -142,6 +142,8 @@ __device__ __forceinline__ void cov_gram(double* Gm, const double* Lm, int wave,
 }  // namespace
 
 // grid = 2 * n_clips: workgroup (clip, direction).  Walks the clip's nodes; stores the correction of every node it enters.
+// FWD_ONLY (the sampler, below): grid = n_clips, the forward direction alone - the same code, CF_k the same bits.
+template <bool FWD_ONLY>
 __global__ void __launch_bounds__(256) k_fte_cov_sweep(CovArgs A) {
   extern __shared__ __attribute__((aligned(16))) double cov_smem[];
   double* Lm = cov_smem;
@@ -150,7 +152,7 @@ __global__ void __launch_bounds__(256) k_fte_cov_sweep(CovArgs A) {
   int* code = reinterpret_cast<int*>(wtab + COV_TAB);
   int* coden = code + BS;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int clip_i = (int)blockIdx.x >> 1, back = (int)blockIdx.x & 1;
+  const int clip_i = FWD_ONLY ? (int)blockIdx.x : (int)blockIdx.x >> 1, back = FWD_ONLY ? 0 : (int)blockIdx.x & 1;
   if (clip_i >= A.n_clips) return;
   const FteConst& K = *A.cst;
   const CovIn in = cov_inputs(A);
@@ -655,6 +657,268 @@ __global__ void __launch_bounds__(256) k_fte_cov_rates(CovArgs A) {
   }
 }
 
+// ---- joint samples of the whole trajectory: delta = L^-T z, A = L L^T ---------------------------------------------------
+// The forward pivots F_k = D_k - CF_k = L_k L_k^T are the diagonal blocks of the Cholesky factor of A (frame-major order;
+// the identity padding decouples), W_k^T = E_k^T U_k its sub-diagonal blocks, U_k = L_k^-T.  Backward substitution:
+//   delta_last = U_last z_last,   delta_k = U_k (z_k - U_k^T (E_k delta_k+1))
+// - products of the triangular factors only (the rule of the sweeps: never G = U U^T on E delta).  Three launches:
+// k_fte_cov_sweep<true> (one workgroup per clip) leaves CF_k; k_fte_sample_factors, one workgroup per node, all in
+// parallel, stores U_k^T = L_k^-1 as its 15 lower tiles in the CB half of the workspace (which the forward-only sweep does
+// not write); k_fte_sample_backsub, grid (clips, panels of 64 samples), walks the nodes from last to first.
+namespace {
+struct SampleIo {
+  const double* z;                                       // [S][N][25]
+  double* xs;                                            // [S][N][25]
+  long long n_samples, n_frames;
+};
+constexpr int SPB = 64;                                  // samples per panel: one 16-sample row tile per wave
+constexpr size_t SAMPLE_FACT_LDS = MAT * sizeof(double) + BS * sizeof(int);
+constexpr size_t SAMPLE_LDS = (MAT + 2 * SPB * LD + COV_TAB) * sizeof(double) + 2 * BS * sizeof(int);
+
+// Samples are held as ROWS (16 per wave, leading dimension LD); Lt = U^T = L^-1, lower triangular, its upper tiles never
+// read.  Column tile JB of  in U:  k runs over the tile rows 0 .. JB of U alone (the zero half is skipped).
+template <int JB>
+__device__ __forceinline__ d4 sample_mul_u(const double* in, const double* Lt, int li, int lk) {
+  d4 acc = {0, 0, 0, 0};
+  return mma_seq<4 * (JB + 1), false>(acc, in + li * LD + lk, 4, Lt + (JB * 16 + li) * LD + lk, 4);
+}
+// Column tile IB of  in U^T:  k runs over the tile columns IB .. 4 of U.
+template <int IB>
+__device__ __forceinline__ d4 sample_mul_ut(const double* in, const double* Lt, int li, int lk) {
+  d4 acc = {0, 0, 0, 0};
+  return mma_seq<4 * (NT - IB), false>(acc, in + li * LD + IB * 16 + lk, 4, Lt + (IB * 16 + lk) * LD + IB * 16 + li, 4 * LD);
+}
+
+struct SampleNode {
+  const double* xhat;                                    // the iterate, halo rows included
+  const int* code;
+  double* xs;
+  long long n_samples, n_frames, s_first, f0;            // s_first: the wave's first sample; f0: the node's first frame
+  int nlive;
+};
+
+// W = z - V U (V = E delta_k+1 as rows; FIRST: the clip's last node, W = z), tile JB of the wave's 16 rows
+template <int JB, bool FIRST>
+__device__ __forceinline__ void sample_w_tile(double* W, const double* V, const double* Lt, const double (&zv)[4],
+                                              const int* code, int li, int lk) {
+  d4 acc = {0, 0, 0, 0};
+  if (!FIRST) acc = sample_mul_u<JB>(V, Lt, li, lk);
+  const int c = JB * 16 + li;
+  const bool free_var = code[c] == 0;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) W[(lk + 4 * rr) * LD + c] = (free_var ? zv[rr] : 0.0) - acc[rr];
+}
+
+// delta = W U^T, tile IB: kept as rows for the next node and written out as x_hat + delta for the node's live frames
+template <int IB>
+__device__ __forceinline__ void sample_d_tile(double* D, const double* W, const double* Lt, const SampleNode& nd, int li,
+                                              int lk) {
+  const d4 acc = sample_mul_ut<IB>(W, Lt, li, lk);
+  const int c = IB * 16 + li;
+  const bool out = c < 3 * NP && c / NP < nd.nlive;
+  const bool free_var = nd.code[c] == 0;
+  const double xh = out ? nd.xhat[(nd.f0 + c / NP + HALO) * NP + c % NP] : 0.0;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    D[(lk + 4 * rr) * LD + c] = acc[rr];
+    const long long s = nd.s_first + lk + 4 * rr;
+    if (out && s < nd.n_samples) nd.xs[(s * nd.n_frames + nd.f0) * NP + c] = free_var ? xh + acc[rr] : xh;
+  }
+}
+}  // namespace
+
+// grid = n_nodes: F_k = D_k - CF_k, chol80, U_k^T -> the CB slot of the node (packed lower tiles, zeros above the diagonal)
+__global__ void __launch_bounds__(256) k_fte_sample_factors(CovArgs A) {
+  extern __shared__ __attribute__((aligned(16))) double cov_smem[];
+  double* Lm = cov_smem;
+  int* code = reinterpret_cast<int*>(Lm + MAT);
+  const int tid = threadIdx.x;
+  const FteConst& K = *A.cst;
+  const CovIn in = cov_inputs(A);
+  const int M = A.nodes_per_clip;
+  const int node = (int)blockIdx.x, clip_i = node / M, k = node % M;
+  if (clip_i >= A.n_clips) return;
+  const int64_t clip = A.clip, r0 = 3 * (int64_t)k, f0 = (int64_t)clip_i * clip + r0;
+  const size_t n_nodes = (size_t)A.n_clips * M;
+  cov_codes(code, in, K, f0, (int)min((int64_t)3, clip - r0), tid);
+  __syncthreads();
+  cov_fill<false>(Lm, code, in, K, f0, r0, clip, tid);
+  __syncthreads();
+  if (k > 0) {
+    cov_sub_terms(Lm, reinterpret_cast<const double2*>(A.terms + (size_t)node * COV_TERM_DOUBLES), nullptr, tid);
+    __syncthreads();
+  }
+  chol80(Lm, tid, A.err);
+  double2* dst = reinterpret_cast<double2*>(A.terms + (n_nodes + node) * COV_TERM_DOUBLES);
+  for (int idx = tid; idx < LOWER_ITEMS; idx += 256) {
+    int row, col;
+    lower_item(idx, row, col);                           // U^T[row][col] = U[col][row]; a diagonal tile holds leftovers below U
+    dst[idx] = make_double2(col <= row ? Lm[col * LD + row] : 0.0, col + 1 <= row ? Lm[(col + 1) * LD + row] : 0.0);
+  }
+}
+
+// grid = (n_clips, panels): the backward substitution of one clip for 64 samples, wave w the samples 16 w .. 16 w + 15 of
+// the panel.  A wave reads and writes its own rows of the two panel buffers only; the barriers order the shared factor,
+// stencil table and codes.  U_k-1's tiles are requested into registers while node k computes.
+__global__ void __launch_bounds__(256) k_fte_sample_backsub(CovArgs A, SampleIo io) {
+  extern __shared__ __attribute__((aligned(16))) double cov_smem[];
+  double* Lt = cov_smem;
+  double* P0 = Lt + MAT;
+  double* P1 = P0 + SPB * LD;
+  double* wtab = P1 + SPB * LD;                          // [(s * 3 + t) * NP + p]: frame s of node k with frame t of node k + 1
+  int* code = reinterpret_cast<int*>(wtab + COV_TAB);
+  int* coden = code + BS;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int clip_i = (int)blockIdx.x;
+  if (clip_i >= A.n_clips) return;
+  const FteConst& K = *A.cst;
+  const CovIn in = cov_inputs(A);
+  const int M = A.nodes_per_clip;
+  const int64_t clip = A.clip, fclip = (int64_t)clip_i * clip;
+  const size_t n_nodes = (size_t)A.n_clips * M;
+  const long long S = io.n_samples, N = io.n_frames;
+  const long long s_first = (long long)blockIdx.y * SPB + 16 * wave;
+  const bool live = s_first < S;                         // (wave-uniform; a dead wave only keeps the barriers)
+  double* Wb = P0 + 16 * wave * LD;                      // W, then the next node's delta source ...
+  double* Db = P1 + 16 * wave * LD;                      // ... and back: the two trade places every node
+  const double2* ut = reinterpret_cast<const double2*>(A.terms + (n_nodes + (size_t)clip_i * M) * COV_TERM_DOUBLES);
+  constexpr int NQ = (LOWER_ITEMS + 255) / 256;
+  constexpr size_t T2 = COV_TERM_DOUBLES / 2;
+  double2 uf[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int idx = tid + 256 * q;
+    if (idx < LOWER_ITEMS) uf[q] = ut[(size_t)(M - 1) * T2 + idx];
+  }
+  for (int k = M - 1; k >= 0; --k) {
+    const int64_t r0 = 3 * (int64_t)k, f0 = fclip + r0;
+    const int nlive = (int)min((int64_t)3, clip - r0);
+    const bool first = k + 1 == M;
+    cov_codes(code, in, K, f0, nlive, tid);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int idx = tid + 256 * q;
+      if (idx < LOWER_ITEMS) {
+        int row, col;
+        lower_item(idx, row, col);
+        Lt[row * LD + col] = uf[q].x;
+        Lt[row * LD + col + 1] = uf[q].y;
+      }
+    }
+    if (k > 0) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int idx = tid + 256 * q;
+        if (idx < LOWER_ITEMS) uf[q] = ut[(size_t)(k - 1) * T2 + idx];
+      }
+    }
+    double zv[NT][4];
+#pragma unroll
+    for (int jb = 0; jb < NT; ++jb) {
+      const int c = jb * 16 + li;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const long long s = s_first + lk + 4 * rr;
+        zv[jb][rr] = (s < S && c < 3 * NP && c / NP < nlive) ? io.z[(s * N + f0) * NP + c] : 0.0;
+      }
+    }
+    __syncthreads();
+    if (!first) {
+      for (int e = tid; e < 9 * NP; e += 256) {
+        const int s = e / (3 * NP), t = (e / NP) % 3, p = e % NP;
+        const int dist = 3 + t - s;
+        double v = 0.0;
+        if (dist <= 3 && code[s * NP + p] == 0 && coden[t * NP + p] == 0) v = 2.0 * K.q_w[p] * band_coef(r0 + s, dist, clip);
+        wtab[e] = v;
+      }
+      __syncthreads();
+      if (live) {                                        // V = E_k delta_k+1, <= 3 stencil terms per entry
+        for (int e = lane; e < 16 * BS; e += 64) {
+          const int sl = e / BS, r = e % BS;
+          double v = 0.0;
+          if (r < 3 * NP) {
+            const int fr = r / NP, p = r % NP;
+#pragma unroll
+            for (int t = 0; t < 3; ++t) v += wtab[(fr * 3 + t) * NP + p] * Wb[sl * LD + t * NP + p];
+          }
+          Db[sl * LD + r] = v;
+        }
+      }
+      __syncthreads();
+    }
+    if (live) {
+      if (first) {
+        sample_w_tile<0, true>(Wb, Db, Lt, zv[0], code, li, lk);
+        sample_w_tile<1, true>(Wb, Db, Lt, zv[1], code, li, lk);
+        sample_w_tile<2, true>(Wb, Db, Lt, zv[2], code, li, lk);
+        sample_w_tile<3, true>(Wb, Db, Lt, zv[3], code, li, lk);
+        sample_w_tile<4, true>(Wb, Db, Lt, zv[4], code, li, lk);
+      } else {
+        sample_w_tile<0, false>(Wb, Db, Lt, zv[0], code, li, lk);
+        sample_w_tile<1, false>(Wb, Db, Lt, zv[1], code, li, lk);
+        sample_w_tile<2, false>(Wb, Db, Lt, zv[2], code, li, lk);
+        sample_w_tile<3, false>(Wb, Db, Lt, zv[3], code, li, lk);
+        sample_w_tile<4, false>(Wb, Db, Lt, zv[4], code, li, lk);
+      }
+    }
+    __syncthreads();
+    if (live) {
+      const SampleNode nd{in.x, code, io.xs, S, N, s_first, f0, nlive};
+      sample_d_tile<0>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<1>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<2>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<3>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<4>(Db, Wb, Lt, nd, li, lk);
+    }
+    {                                                    // delta_k is the next node's source; this node's codes its neighbour's
+      double* sw = Wb;
+      Wb = Db;
+      Db = sw;
+      int* sc = code;
+      code = coden;
+      coden = sc;
+    }
+    __syncthreads();
+  }
+}
+
+int launch_fte_sample(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
+                      double* const H[2], double* const g[2], void* d_ws, int64_t n_samples, const double* d_z,
+                      double* d_x_samples, hipStream_t s) {
+  const CovGrid gr = cov_grid(h_c.n_frames, h_c.clip_len);
+  CovArgs A = {};
+  A.cst = d_c;
+  A.st = d_st;
+  A.x0 = x[0];
+  A.x1 = x[1];
+  A.g0 = g[0];
+  A.g1 = g[1];
+  A.H0 = H[0];
+  A.H1 = H[1];
+  A.err = reinterpret_cast<int*>(d_ws);
+  A.terms = reinterpret_cast<double*>(reinterpret_cast<char*>(d_ws) + COV_HEAD_BYTES);
+  A.n_clips = gr.n_clips;
+  A.nodes_per_clip = gr.nodes_per_clip;
+  A.clip = gr.clip;
+  A.inv_ts = 1.0;
+  const SampleIo io{d_z, d_x_samples, (long long)n_samples, (long long)h_c.n_frames};
+  const int64_t panels = (n_samples + SPB - 1) / SPB;
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_sample_backsub),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS));
+  ACINO_HIP_CHECK(hipMemsetAsync(d_ws, 0, COV_HEAD_BYTES, s));
+  if (gr.nodes_per_clip > 1) {
+    hipLaunchKernelGGL(k_fte_cov_sweep<true>, dim3(gr.n_clips), dim3(256), COV_LDS, s, A);
+    ACINO_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_fte_sample_factors, dim3((unsigned)gr.n_nodes()), dim3(256), SAMPLE_FACT_LDS, s, A);
+  ACINO_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_fte_sample_backsub, dim3((unsigned)gr.n_clips, (unsigned)panels), dim3(256), SAMPLE_LDS, s, A, io);
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
+
 int launch_fte_cov(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
                    double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
                    double* d_std_pos, hipStream_t s) {
@@ -690,13 +954,13 @@ int launch_fte_cov_rates(const FteConst* d_c, const FteConst& h_c, const acino_f
   A.std_vel = d_std_vel;
   A.inv_ts = 1.0 / ts;
   const bool blocks = d_cov_x || d_cov_pos || d_std_pos, rates = d_cov_dx || d_cov_ddx || d_cov_vel || d_std_vel;
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)COV_LDS));
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
   ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_combine),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
   ACINO_HIP_CHECK(hipMemsetAsync(d_ws, 0, COV_HEAD_BYTES, s));
   if (gr.nodes_per_clip > 1) {
-    hipLaunchKernelGGL(k_fte_cov_sweep, dim3(2 * gr.n_clips), dim3(256), COV_LDS, s, A);
+    hipLaunchKernelGGL(k_fte_cov_sweep<false>, dim3(2 * gr.n_clips), dim3(256), COV_LDS, s, A);
     ACINO_LAUNCH_CHECK();
   }
   if (blocks) {

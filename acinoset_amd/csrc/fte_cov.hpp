@@ -31,4 +31,11 @@ int launch_fte_cov_rates(const FteConst* d_c, const FteConst& h_c, const acino_f
                          double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel, double* d_std_vel,
                          double ts, hipStream_t s);
 
+// Joint samples of the trajectory: d_x_samples[S][N][25] = x_hat + L^-T z for d_z[S][N][25], A = L L^T the matrix the
+// covariances invert (frame-major order; z of pinned variables counts as 0).  Forward sweep alone, the factors of all nodes
+// in parallel, one backward substitution per clip and panel of 64 samples.  Workspace and error word as launch_fte_cov.
+int launch_fte_sample(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
+                      double* const H[2], double* const g[2], void* d_ws, int64_t n_samples, const double* d_z,
+                      double* d_x_samples, hipStream_t s);
+
 }  // namespace acino

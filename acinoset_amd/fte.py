@@ -373,6 +373,63 @@ class FTEContext:
         rates = (cov_dx, cov_ddx, cov_vel, std_vel)
         return (rates, (cov_x, cov_pos, std_pos)) if with_cov else rates
 
+    def sample(self, n_samples, seed=0, z=None, positions=True, rates=False, clip=False):
+        """Joint draws of the whole trajectory from the Laplace posterior of the CURRENT iterate (acino_fte_sample):
+        ``x[s] = x_hat + L^-T z[s]`` with ``A = L L^T`` the matrix ``covariance()`` inverts (unknowns frame-major, z of
+        bound-active variables counted as 0), so ``Cov(x[s]) = A^-1`` - between frames as well, which is what a stride
+        length, a mean speed or a phase between two feet needs.  Returns a dict of tensors on the context's device: ``x``
+        [S,N,25]; with ``positions`` the FK of every sample, ``positions`` [S,N,20,3]; with ``rates`` also ``dx``, ``ddx``
+        [S,N,25] (acino_fte_derivatives per sample and clip: the start-up rules of ``result()``).  ``z=None``:
+        ``torch.randn`` from a ``torch.Generator`` on the context's device seeded with ``seed`` (same seed, same device:
+        same samples); a given ``z`` [S,N,25] is used as is (the map is deterministic).  ``clip=True`` clamps ``x`` to the
+        box of the solve before FK and rates; default off, the Laplace posterior as documented.  The solver state is not
+        touched.  Whole-sequence fp64 contexts only (RuntimeError otherwise)."""
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError("n_samples must be >= 1")
+        dev = self.device
+        if z is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+            z = torch.randn((S, self.N, N_ACTIVE), dtype=torch.float64, device=dev, generator=gen)
+        else:
+            z = calib._to_dev(z, dev)
+            if tuple(z.shape) != (S, self.N, N_ACTIVE) or z.dtype != torch.float64:
+                raise ValueError(f"z must be float64 [{S}, {self.N}, 25]")
+            z = z.contiguous()
+        nbytes = lib().acino_fte_sample_workspace_bytes(C.byref(self.params))
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        x = torch.empty((S, self.N, N_ACTIVE), dtype=torch.float64, device=dev)
+        fk_now = bool(positions) and not clip
+        pos = torch.empty((S, self.N, N_MARKERS, 3), dtype=torch.float64, device=dev) if positions else None
+        check(lib().acino_fte_sample(self._h, S, ptr(z), C.c_void_p(ws_ptr), nbytes, ptr(x), ptr(pos if fk_now else None),
+                                     stream_ptr()))
+        if clip:
+            lo = torch.tensor(list(self.params.lo), dtype=torch.float64, device=dev)
+            hi = torch.tensor(list(self.params.hi), dtype=torch.float64, device=dev)
+            x = torch.minimum(torch.maximum(x, lo), hi).contiguous()
+            if positions:
+                check(lib().acino_fk_active(ptr(x), S * self.N, ptr(pos), stream_ptr()))
+        out = dict(x=x)
+        if positions:
+            out["positions"] = pos
+        if rates:
+            L = int(self.params.clip_len) or self.N
+            dx, ddx = torch.empty_like(x), torch.empty_like(x)
+            xc, dxc, ddxc = (t.view(S * (self.N // L), L, N_ACTIVE) for t in (x, dx, ddx))
+            for i in range(xc.shape[0]):
+                check(lib().acino_fte_derivatives(ptr(xc[i]), L, self.Ts, ptr(dxc[i]), ptr(ddxc[i]), stream_ptr()))
+            out.update(dx=dx, ddx=ddx)
+        return out
+
+    def _samples(self, n_samples, sample_seed):
+        """(x_samples, positions_samples) as the solve entries return them, or None."""
+        if not n_samples:
+            return None
+        out = self.sample(n_samples, seed=sample_seed)
+        return out["x"], out["positions"]
+
     def _covariances(self, return_cov, return_rate_cov):
         """(cov, rate_cov) as the solve entries return them: either may be None; both from one call when both are asked."""
         if return_rate_cov:
@@ -387,6 +444,11 @@ def _cov_results(res, cov, rate_cov, conv, sl=slice(None)):
     if rate_cov is not None:
         res.update(cov_dx=conv(rate_cov[0][sl]), cov_ddx=conv(rate_cov[1][sl]), cov_velocities=conv(rate_cov[2][sl]),
                    std_velocities=conv(rate_cov[3][sl]))
+
+
+def _sample_results(res, samples, conv, sl=slice(None)):
+    if samples is not None:
+        res.update(x_samples=conv(samples[0][:, sl]), positions_samples=conv(samples[1][:, sl]))
 
 
 def cheetah_fk(q):
@@ -537,7 +599,7 @@ def _initial_x0(det, x0, init, rig, dlc_thresh, start_frame, camera_model, shape
 
 def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thresh=0.5, start_frame=0,
               max_iter=100, init="nose_line", return_numpy=True, reuse_context=False, camera_model=None, project_func=None,
-              return_cov=False, return_rate_cov=False, **kw):
+              return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, **kw):
     """The FTE solve call.
 
     meas[N,C,20,2] pixel detections, likelihood[N,C,20], cameras as in the scene file (k_arr[C,3,3],
@@ -551,7 +613,9 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     and ``std_positions`` [N,20] (FTEContext.covariance at the returned x, from the context that produced it).
     ``return_rate_cov``: results gain ``cov_dx`` / ``cov_ddx`` [N,25,25], ``cov_velocities`` [N,20,3,3] and
     ``std_velocities`` [N,20] (FTEContext.covariance_rates: the error bars of dx, ddx and of the markers' velocities);
-    with ``return_cov`` as well both sets come from one call."""
+    with ``return_cov`` as well both sets come from one call.  ``n_samples`` > 0: results gain ``x_samples`` [S,N,25] and
+    ``positions_samples`` [S,N,20,3], joint draws of the whole trajectory from the same posterior (FTEContext.sample with
+    ``seed=sample_seed``; sample axis first)."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     meas_t = meas if isinstance(meas, torch.Tensor) else torch.as_tensor(np.asarray(meas, dtype=np.float64))
     lik_t = likelihood if isinstance(likelihood, torch.Tensor) else torch.as_tensor(np.asarray(likelihood, dtype=np.float64))
@@ -572,6 +636,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         info = ctx.solve(max_iter)
         x, pos, dx, ddx = ctx.result()
         cov, rate_cov = ctx._covariances(return_cov, return_rate_cov) if info["status"] != 5 else (None, None)
+        samples = ctx._samples(n_samples, sample_seed) if info["status"] != 5 else None
     except Exception:
         # (the initial guess's flag is read after the solve - no synchronisation in front of it -, but whatever a solve from an
         #  all-zero start ran into must not hide the real cause)
@@ -588,6 +653,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
     results = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frame)
     _cov_results(results, cov, rate_cov, conv)
+    _sample_results(results, samples, conv)
     return results, info
 
 
@@ -599,7 +665,7 @@ def _derivatives(x_clip, Ts):
 
 def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
                     init="nose_line", return_numpy=True, camera_model=None, project_func=None, return_cov=False,
-                    return_rate_cov=False, **kw):
+                    return_rate_cov=False, n_samples=0, sample_seed=0, **kw):
     """Equal-length clips of one rig solved as ONE problem (BASELINE config 5's batched FTE at full width): the clips
     are laid end to end on the frame axis, the smoothness prior is cut at the clip boundaries (``clip_len``), and the
     block-cyclic reduction runs over the whole chain - every launch is as wide as all clips together, so the narrow
@@ -607,7 +673,8 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     clips' costs (the problem is block diagonal: each clip converges to its own optimum, but damping and accept/reject
     are shared, so iterates differ from per-clip solves until convergence).  Returns a list of (results, info).
     ``camera_model`` / ``project_func`` / ``return_cov`` / ``return_rate_cov`` as in fte_solve (the covariance per clip: the
-    clips are independent, so it is the one a solve of the clip alone would give at the same x)."""
+    clips are independent, so it is the one a solve of the clip alone would give at the same x).  ``n_samples`` / ``sample_seed``
+    as in fte_solve: every clip gets its slice of the frame axis of one call's samples."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     B = len(dets)
     if B == 0:
@@ -640,6 +707,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
         if info["status"] == 5:
             raise RuntimeError("FTE: block factorisation hit a non-positive pivot")
         cov, rate_cov = ctx._covariances(return_cov, return_rate_cov)
+        samples = ctx._samples(n_samples, sample_seed)
         conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
         out = []
         for b in range(B):
@@ -648,6 +716,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
             res = dict(positions=conv(pos[b * S:(b + 1) * S]), x=conv(xb), dx=conv(dxb), ddx=conv(ddxb),
                        start_frame=start_frames[b])
             _cov_results(res, cov, rate_cov, conv, slice(b * S, (b + 1) * S))
+            _sample_results(res, samples, conv, slice(b * S, (b + 1) * S))
             out.append((res, dict(info, clips=B, cost_is_sum_over_clips=True)))
         return out
     finally:
@@ -656,7 +725,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
 
 def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
                     init="nose_line", n_streams=8, peek_every=8, return_numpy=True, camera_model=None, project_func=None,
-                    return_cov=False, return_rate_cov=False, **kw):
+                    return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, **kw):
     """Several independent sequences (BASELINE config 5's "batched FTE": one rig, many clips) solved concurrently
     on ONE GPU.  Every sequence gets its own context and runs on one of ``n_streams`` HIP streams; a Levenberg-
     Marquardt step never synchronises with the host (the accept/reject controller is a device kernel and the step is
@@ -665,7 +734,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     keep all of them busy whatever the stream-to-queue assignment).  ``dets``: list of det[N_b, C, 20, 3] (lengths may differ).
     Returns a list of (results, info) exactly as ``fte_solve`` would for each sequence alone.  The reference solves
     clips one after another (src/all_optimizations.py:22, one ``fte()`` call per data directory).  ``camera_model`` /
-    ``project_func`` / ``return_cov`` / ``return_rate_cov`` as in fte_solve."""
+    ``project_func`` / ``return_cov`` / ``return_rate_cov`` / ``n_samples`` / ``sample_seed`` as in fte_solve."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     _lib.require_gpu()
     B = len(dets)
@@ -715,6 +784,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
                 x, pos, dx, ddx = ctxs[b].result()
                 res = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frames[b])
                 _cov_results(res, *ctxs[b]._covariances(return_cov, return_rate_cov), conv)
+                _sample_results(res, ctxs[b]._samples(n_samples, sample_seed), conv)
                 out.append((res, infos[b]))
         for s in streams:
             torch.cuda.current_stream().wait_stream(s)

@@ -314,6 +314,23 @@ size_t acino_fte_covariance_rates_workspace_bytes(const acino_fte_params* p);
 int acino_fte_covariance_rates(acino_fte_ctx* ctx, double ts, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
                                double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel, double* d_std_vel,
                                void* stream);
+/* Joint draws of the WHOLE trajectory from the same Laplace posterior: what the two entries above give as diagonal blocks,
+ * this one gives as samples, so that any statistic of any functional across frames (stride length, mean speed over a
+ * stride, the phase between two feet) is a line of numpy on them.  A = the matrix of acino_fte_covariance at the CURRENT
+ * iterate, unknowns ordered frame-major (n, p), A = L L^T its Cholesky factor.  For the caller's d_z[S][N][25]
+ *   d_x_samples[s] = x_hat + delta(s),   delta(s) = L^-T z(s),   z of a pinned variable counted as 0 (delta exactly 0 there)
+ * so Cov(delta) = A^-1 for standard-normal z (E[delta_n delta_n^T] = cov_x[n], E[delta_n delta_m^T] the block (n, m) of
+ * A^-1).  The map z -> delta is deterministic: the library owns no random generator, and the result for one clip does not
+ * depend on the other clips of the context.  d_pos_samples[S][N][20][3] (may be NULL): acino_fk_active of every sample -
+ * the real FK, not its linearisation.  dx / ddx of a sample: acino_fte_derivatives on d_x_samples[s] (per clip).
+ * Three launches: the forward pivot sweep of the covariance (one workgroup per clip), the factors U_k = L_k^-T of all nodes
+ * in parallel, one backward substitution per clip and panel of 64 samples, delta_k = U_k (z_k - U_k^T (E_k delta_k+1)).
+ * n_samples >= 1; d_z must not alias the outputs (ACINO_ERR_INVALID_ARG, before any device call, as for a NULL d_z /
+ * d_x_samples).  Workspace (the same byte count), ACINO_ERR_WORKSPACE / _UNSUPPORTED / _NUMERIC, the one synchronisation
+ * and what the call leaves untouched: as acino_fte_covariance. */
+size_t acino_fte_sample_workspace_bytes(const acino_fte_params* p);
+int acino_fte_sample(acino_fte_ctx* ctx, int64_t n_samples, const double* d_z, void* d_ws, size_t ws_bytes,
+                     double* d_x_samples, double* d_pos_samples, void* stream);
 /* Live per-kernel timing for bench.py: HIP events recorded on the launch stream around every kernel between
  * begin and end.  end synchronises and returns, per class {elim, elim_deep, update0, update, update_deep, backsub0,
  * backsub, trial, assemble, totals, control, backsub_tail, trunc_check, chunk_sweep, sep_combine, chunk_backsub, refine} (one class per kernel), the summed event time in ms, the launch
