@@ -114,6 +114,40 @@ __device__ __forceinline__ void project_fisheye_pt(const Cam& c, double X, doubl
   v = yd * c.fy + c.cy;
 }
 
+// The reference's closed-form projection inside the NLP (pt3d_to_2d, all_optimizations.py:193-209: r = sqrt(a^2 + b^2 +
+// 1e-12), no r -> 0 branch, no skew) of a camera-frame point, and d(uv)/d(Xc): the fp64 arithmetic of the FTE assembly,
+// statement for statement, which the assembly and the reprojection report (fte_reproj.hip) both call.  Two calls - the
+// pixel, then the Jacobian from what the pixel left in FisheyeNlp - because the assembly evaluates the loss in between, and
+// keeps the order of its statements (and with it its code).
+struct FisheyeNlp {
+  double iz, a, b, r2, ir, r, th2, thD, m;
+};
+__device__ __forceinline__ void fisheye_nlp_uv(const Cam& cam, double xc, double yc, double zc, FisheyeNlp& p, double& u,
+                                               double& v) {
+  p.iz = rcp64(zc);
+  p.a = xc * p.iz, p.b = yc * p.iz;
+  p.r2 = p.a * p.a + p.b * p.b + 1e-12;
+  p.ir = rsqrt(p.r2);                 // every later "/ r" is a multiplication
+  p.r = p.r2 * p.ir;
+  double th = atan(p.r);
+  p.th2 = th * th;
+  double poly = 1 + p.th2 * (cam.k1 + p.th2 * (cam.k2 + p.th2 * (cam.k3 + p.th2 * cam.k4)));
+  p.thD = th * poly;
+  p.m = p.thD * p.ir;
+  u = cam.fx * p.a * p.m + cam.cx;
+  v = cam.fy * p.b * p.m + cam.cy;
+}
+__device__ __forceinline__ void fisheye_nlp_jac(const Cam& cam, const FisheyeNlp& p, double ju[3], double jv[3]) {
+  const double a = p.a, b = p.b, ir = p.ir, m = p.m, iz = p.iz, th2 = p.th2;
+  double dthD = 1 + th2 * (3 * cam.k1 + th2 * (5 * cam.k2 + th2 * (7 * cam.k3 + th2 * 9 * cam.k4)));
+  double dm_dr = (dthD * rcp64(1 + p.r2) * p.r - p.thD) * (ir * ir);
+  double dm_da = dm_dr * a * ir, dm_db = dm_dr * b * ir;
+  double du_da = cam.fx * (m + a * dm_da), du_db = cam.fx * a * dm_db;
+  double dv_da = cam.fy * b * dm_da, dv_db = cam.fy * (m + b * dm_db);
+  ju[0] = du_da * iz, ju[1] = du_db * iz, ju[2] = -(du_da * a + du_db * b) * iz;
+  jv[0] = dv_da * iz, jv[1] = dv_db * iz, jv[2] = -(dv_da * a + dv_db * b) * iz;
+}
+
 // bf16 storage rounding (round-to-nearest-even on the upper 16 bits of the float)
 __device__ __forceinline__ float bf16_round(float x) {
   unsigned u = __float_as_uint(x);

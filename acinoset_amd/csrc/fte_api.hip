@@ -7,6 +7,7 @@
 #include "bcr.hpp"
 #include "chunk.hpp"
 #include "fte_cov.hpp"
+#include "fte_reproj.hpp"
 #include "seplevel.hpp"
 
 namespace acino {
@@ -1474,6 +1475,17 @@ int acino_fte_sample(acino_fte_ctx* ctx, int64_t n_samples, const double* d_z, v
     return ACINO_ERR_NUMERIC;
   }
   return ACINO_OK;
+}
+
+// ---- the iterate in image space (csrc/fte_reproj.hip): one launch, no synchronisation, no workspace ----
+int acino_fte_reprojection(acino_fte_ctx* ctx, const double* d_cov_pos, double* d_uv, double* d_cov_uv, double* d_res,
+                           double* d_weight, double* d_mahal2, uint8_t* d_flags, void* stream) {
+  ACINO_REQUIRE(ctx, "null context");
+  ACINO_REQUIRE(d_uv || d_cov_uv || d_res || d_weight || d_mahal2 || d_flags, "no output asked for");
+  ACINO_REQUIRE(!d_cov_uv || d_cov_pos, "d_cov_uv needs d_cov_pos");
+  const Buffers& b = ctx->b;
+  return launch_fte_reproj(b.cst, ctx->h, b.state, ctx->d_det, b.x, d_cov_pos, d_uv, d_cov_uv, d_res, d_weight, d_mahal2,
+                           d_flags, (hipStream_t)stream);
 }
 
 int acino_fte_get_result(acino_fte_ctx* ctx, double ts, double* d_x, double* d_pos, double* d_dx, double* d_ddx,

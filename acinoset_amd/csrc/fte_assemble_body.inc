@@ -210,35 +210,23 @@
           vf[2] += gu * ju[2] + gv * jv[2];
         }
       } else {
-        double iz = rcp64(zc);
-        double a = xc * iz, b = yc * iz;
-        const double r2 = a * a + b * b + 1e-12;
-        const double ir = rsqrt(r2);                 // every later "/ r" is a multiplication
-        double r = r2 * ir;
-        double th = atan(r);
-        double th2 = th * th;
-        double poly = 1 + th2 * (cam.k1 + th2 * (cam.k2 + th2 * (cam.k3 + th2 * cam.k4)));
-        double thD = th * poly;
-        double m = thD * ir;
-        double su = w * (cam.fx * a * m + cam.cx - um);
-        double sv = w * (cam.fy * b * m + cam.cy - vm);
+        FisheyeNlp fp;
+        double pu, pv;
+        fisheye_nlp_uv(cam, xc, yc, zc, fp, pu, pv);            // (common.hpp: the reference's pt3d_to_2d)
+        double su = w * (pu - um);
+        double sv = w * (pv - vm);
         double rho_u, drho_u = 0, h_u = 0, rho_v, drho_v = 0, h_v = 0;
         redescending<JAC>(K.loss, su, rho_u, drho_u, h_u);
         redescending<JAC>(K.loss, sv, rho_v, drho_v, h_v);
         cost_c += rho_u + rho_v;
         if (JAC) {
-          double dthD = 1 + th2 * (3 * cam.k1 + th2 * (5 * cam.k2 + th2 * (7 * cam.k3 + th2 * 9 * cam.k4)));
-          double dm_dr = (dthD * rcp64(1 + r2) * r - thD) * (ir * ir);
-          double dm_da = dm_dr * a * ir, dm_db = dm_dr * b * ir;
-          double du_da = cam.fx * (m + a * dm_da), du_db = cam.fx * a * dm_db;
-          double dv_da = cam.fy * b * dm_da, dv_db = cam.fy * (m + b * dm_db);
-          double uc0 = du_da * iz, uc1 = du_db * iz, uc2 = -(du_da * a + du_db * b) * iz;
-          double vc0 = dv_da * iz, vc1 = dv_db * iz, vc2 = -(dv_da * a + dv_db * b) * iz;
+          double uc[3], vc[3];
+          fisheye_nlp_jac(cam, fp, uc, vc);
           double ju[3], jv[3];
   #pragma unroll
           for (int j = 0; j < 3; ++j) {
-            ju[j] = uc0 * cam.R[j] + uc1 * cam.R[3 + j] + uc2 * cam.R[6 + j];
-            jv[j] = vc0 * cam.R[j] + vc1 * cam.R[3 + j] + vc2 * cam.R[6 + j];
+            ju[j] = uc[0] * cam.R[j] + uc[1] * cam.R[3 + j] + uc[2] * cam.R[6 + j];
+            jv[j] = vc[0] * cam.R[j] + vc[1] * cam.R[3 + j] + vc[2] * cam.R[6 + j];
           }
           double gu = w * drho_u * (su > 0 ? 1.0 : (su < 0 ? -1.0 : 0.0));
           double gv = w * drho_v * (sv > 0 ? 1.0 : (sv < 0 ? -1.0 : 0.0));

@@ -423,6 +423,43 @@ class FTEContext:
             out.update(dx=dx, ddx=ddx)
         return out
 
+    def reprojection(self, cov=True, cov_pos=None):
+        """The CURRENT iterate in image space (acino_fte_reprojection), per (frame, camera, marker): a dict of tensors on
+        the context's device - ``uv`` [N,C,20,2] the predicted pixel (NaN on a camera's singular plane), ``cov_uv``
+        [N,C,20,2,2] its Laplace covariance J_pi cov_pos J_pi^T in px^2, ``std_uv`` [N,C,20] = sqrt(trace(cov_uv)) in px,
+        ``res`` [N,C,20,2] = uv - detection (NaN where the detection is not finite), ``weight`` [N,C,20,2] the curvature
+        weight in [0, 1] the solve gave each component (0: not weighted at all), ``mahal2`` [N,C,20] the squared gating
+        distance res^T (cov_uv + R^2 I)^-1 res, ``flags`` [N,C,20] uint8 (bit 0 weighted by the solve, bit 1 behind the
+        camera, bit 2 singular plane).  ``cov=True`` without ``cov_pos`` [N,20,3,3] runs ``covariance()`` first (and raises
+        what that raises: whole-sequence fp64 contexts only); ``cov=False``: ``cov_uv`` and ``std_uv`` are None and
+        ``mahal2`` is res^T res / R^2 - valid for every context.  One launch, nothing of the solver state is touched."""
+        dev = self.device
+        if cov and cov_pos is None:
+            cov_pos = self.covariance()[1]
+        if cov:
+            cov_pos = calib._to_dev(cov_pos, dev)
+            if tuple(cov_pos.shape) != (self.N, N_MARKERS, 3, 3) or cov_pos.dtype != torch.float64:
+                raise ValueError(f"cov_pos must be float64 [{self.N}, 20, 3, 3]")
+            cov_pos = cov_pos.contiguous()
+        else:
+            cov_pos = None
+        shape = (self.N, self.C, N_MARKERS)
+        uv = torch.empty(shape + (2,), dtype=torch.float64, device=dev)
+        cov_uv = torch.empty(shape + (2, 2), dtype=torch.float64, device=dev) if cov else None
+        res, weight = torch.empty_like(uv), torch.empty_like(uv)
+        mahal2 = torch.empty(shape, dtype=torch.float64, device=dev)
+        flags = torch.empty(shape, dtype=torch.uint8, device=dev)
+        check(lib().acino_fte_reprojection(self._h, ptr(cov_pos), ptr(uv), ptr(cov_uv), ptr(res), ptr(weight), ptr(mahal2),
+                                           ptr(flags), stream_ptr()))
+        std_uv = torch.sqrt(cov_uv[..., 0, 0] + cov_uv[..., 1, 1]) if cov else None
+        return dict(uv=uv, cov_uv=cov_uv, std_uv=std_uv, res=res, weight=weight, mahal2=mahal2, flags=flags)
+
+    def _reprojection(self, return_reprojection, cov):
+        """The report as the solve entries return it, or None; ``cov``: what _covariances gave (its sweeps are not run twice)."""
+        if not return_reprojection:
+            return None
+        return self.reprojection(cov_pos=None if cov is None else cov[1])
+
     def _samples(self, n_samples, sample_seed):
         """(x_samples, positions_samples) as the solve entries return them, or None."""
         if not n_samples:
@@ -444,6 +481,46 @@ def _cov_results(res, cov, rate_cov, conv, sl=slice(None)):
     if rate_cov is not None:
         res.update(cov_dx=conv(rate_cov[0][sl]), cov_ddx=conv(rate_cov[1][sl]), cov_velocities=conv(rate_cov[2][sl]),
                    std_velocities=conv(rate_cov[3][sl]))
+
+
+_REPROJ_KEYS = dict(uv="uv", cov_uv="cov_uv", std_uv="std_uv", res="residuals", weight="weights", mahal2="mahal2", flags="flags")
+
+
+def _reproj_results(res, reproj, conv, sl=slice(None)):
+    if reproj is not None:
+        res.update({name: conv(reproj[k][sl]) for k, name in _REPROJ_KEYS.items()})
+
+
+def detection_report(reproj, gate=None):
+    """Summary of ``FTEContext.reprojection()`` (or of the ``uv`` ... ``flags`` entries of a solve's results) per (camera,
+    marker), as a dict of numpy arrays [C, 20]: ``n_weighted`` the detections the solve weighted (bit 0 of the flags),
+    ``n_inlier`` those of them whose smaller component weight is >= 0.5 ("used as inliers": the redescending loss kept at
+    least half of their curvature), ``rms_inlier`` the RMS residual of those in px (NaN where there is none).  With
+    ``gate`` - a chi-square quantile with 2 degrees of freedom the caller picks, e.g. 9.21 for 99 % - also the finite
+    detections inside / outside ``mahal2 <= gate``, split by bit 0: ``n_weighted_inside``, ``n_weighted_outside``,
+    ``n_unweighted_inside`` (low-likelihood detections that agree with the trajectory all the same) and
+    ``n_unweighted_outside``.  Host arithmetic on the arrays given; no kernel."""
+    def host(key):
+        a = reproj[key] if key in reproj else reproj[_REPROJ_KEYS[key]]      # (a solve's results say residuals / weights)
+        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+    res, weight, flags = host("res"), host("weight"), host("flags")
+    weighted = (flags & 1) != 0
+    inlier = weighted & (weight.min(axis=-1) >= 0.5)
+    n_in = inlier.sum(axis=0)
+    sq = np.where(inlier, (np.where(inlier[..., None], res, 0.0) ** 2).sum(axis=-1), 0.0).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rms = np.where(n_in > 0, np.sqrt(sq / np.maximum(n_in, 1)), np.nan)
+    out = dict(n_weighted=weighted.sum(axis=0), n_inlier=n_in, rms_inlier=rms)
+    if gate is not None:
+        m2 = host("mahal2")
+        finite = np.isfinite(m2)
+        inside = finite & (np.where(finite, m2, np.inf) <= float(gate))
+        outside = finite & ~inside
+        out.update(n_weighted_inside=(inside & weighted).sum(axis=0), n_weighted_outside=(outside & weighted).sum(axis=0),
+                   n_unweighted_inside=(inside & ~weighted).sum(axis=0),
+                   n_unweighted_outside=(outside & ~weighted).sum(axis=0))
+    return out
 
 
 def _sample_results(res, samples, conv, sl=slice(None)):
@@ -599,7 +676,7 @@ def _initial_x0(det, x0, init, rig, dlc_thresh, start_frame, camera_model, shape
 
 def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thresh=0.5, start_frame=0,
               max_iter=100, init="nose_line", return_numpy=True, reuse_context=False, camera_model=None, project_func=None,
-              return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, **kw):
+              return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, **kw):
     """The FTE solve call.
 
     meas[N,C,20,2] pixel detections, likelihood[N,C,20], cameras as in the scene file (k_arr[C,3,3],
@@ -615,7 +692,10 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     ``std_velocities`` [N,20] (FTEContext.covariance_rates: the error bars of dx, ddx and of the markers' velocities);
     with ``return_cov`` as well both sets come from one call.  ``n_samples`` > 0: results gain ``x_samples`` [S,N,25] and
     ``positions_samples`` [S,N,20,3], joint draws of the whole trajectory from the same posterior (FTEContext.sample with
-    ``seed=sample_seed``; sample axis first)."""
+    ``seed=sample_seed``; sample axis first).  ``return_reprojection``: results gain the solve in image space -
+    ``uv`` [N,C,20,2], ``cov_uv`` [N,C,20,2,2], ``std_uv`` [N,C,20], ``residuals`` and ``weights`` [N,C,20,2], ``mahal2``
+    and ``flags`` [N,C,20] (FTEContext.reprojection; ``detection_report`` summarises them); with ``return_cov`` as well the
+    covariance sweeps run once."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     meas_t = meas if isinstance(meas, torch.Tensor) else torch.as_tensor(np.asarray(meas, dtype=np.float64))
     lik_t = likelihood if isinstance(likelihood, torch.Tensor) else torch.as_tensor(np.asarray(likelihood, dtype=np.float64))
@@ -637,6 +717,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         x, pos, dx, ddx = ctx.result()
         cov, rate_cov = ctx._covariances(return_cov, return_rate_cov) if info["status"] != 5 else (None, None)
         samples = ctx._samples(n_samples, sample_seed) if info["status"] != 5 else None
+        reproj = ctx._reprojection(return_reprojection, cov) if info["status"] != 5 else None
     except Exception:
         # (the initial guess's flag is read after the solve - no synchronisation in front of it -, but whatever a solve from an
         #  all-zero start ran into must not hide the real cause)
@@ -654,6 +735,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     results = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frame)
     _cov_results(results, cov, rate_cov, conv)
     _sample_results(results, samples, conv)
+    _reproj_results(results, reproj, conv)
     return results, info
 
 
@@ -665,7 +747,7 @@ def _derivatives(x_clip, Ts):
 
 def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
                     init="nose_line", return_numpy=True, camera_model=None, project_func=None, return_cov=False,
-                    return_rate_cov=False, n_samples=0, sample_seed=0, **kw):
+                    return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, **kw):
     """Equal-length clips of one rig solved as ONE problem (BASELINE config 5's batched FTE at full width): the clips
     are laid end to end on the frame axis, the smoothness prior is cut at the clip boundaries (``clip_len``), and the
     block-cyclic reduction runs over the whole chain - every launch is as wide as all clips together, so the narrow
@@ -674,7 +756,8 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     are shared, so iterates differ from per-clip solves until convergence).  Returns a list of (results, info).
     ``camera_model`` / ``project_func`` / ``return_cov`` / ``return_rate_cov`` as in fte_solve (the covariance per clip: the
     clips are independent, so it is the one a solve of the clip alone would give at the same x).  ``n_samples`` / ``sample_seed``
-    as in fte_solve: every clip gets its slice of the frame axis of one call's samples."""
+    as in fte_solve: every clip gets its slice of the frame axis of one call's samples.  ``return_reprojection`` as in
+    fte_solve, sliced per clip in the same way."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     B = len(dets)
     if B == 0:
@@ -708,6 +791,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
             raise RuntimeError("FTE: block factorisation hit a non-positive pivot")
         cov, rate_cov = ctx._covariances(return_cov, return_rate_cov)
         samples = ctx._samples(n_samples, sample_seed)
+        reproj = ctx._reprojection(return_reprojection, cov)
         conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
         out = []
         for b in range(B):
@@ -717,6 +801,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
                        start_frame=start_frames[b])
             _cov_results(res, cov, rate_cov, conv, slice(b * S, (b + 1) * S))
             _sample_results(res, samples, conv, slice(b * S, (b + 1) * S))
+            _reproj_results(res, reproj, conv, slice(b * S, (b + 1) * S))
             out.append((res, dict(info, clips=B, cost_is_sum_over_clips=True)))
         return out
     finally:
@@ -725,7 +810,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
 
 def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
                     init="nose_line", n_streams=8, peek_every=8, return_numpy=True, camera_model=None, project_func=None,
-                    return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, **kw):
+                    return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, **kw):
     """Several independent sequences (BASELINE config 5's "batched FTE": one rig, many clips) solved concurrently
     on ONE GPU.  Every sequence gets its own context and runs on one of ``n_streams`` HIP streams; a Levenberg-
     Marquardt step never synchronises with the host (the accept/reject controller is a device kernel and the step is
@@ -734,7 +819,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     keep all of them busy whatever the stream-to-queue assignment).  ``dets``: list of det[N_b, C, 20, 3] (lengths may differ).
     Returns a list of (results, info) exactly as ``fte_solve`` would for each sequence alone.  The reference solves
     clips one after another (src/all_optimizations.py:22, one ``fte()`` call per data directory).  ``camera_model`` /
-    ``project_func`` / ``return_cov`` / ``return_rate_cov`` / ``n_samples`` / ``sample_seed`` as in fte_solve."""
+    ``project_func`` / ``return_cov`` / ``return_rate_cov`` / ``n_samples`` / ``sample_seed`` / ``return_reprojection`` as in fte_solve."""
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     _lib.require_gpu()
     B = len(dets)
@@ -783,8 +868,10 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
                     raise RuntimeError(f"FTE: block factorisation hit a non-positive pivot (sequence {b})")
                 x, pos, dx, ddx = ctxs[b].result()
                 res = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frames[b])
-                _cov_results(res, *ctxs[b]._covariances(return_cov, return_rate_cov), conv)
+                cov, rate_cov = ctxs[b]._covariances(return_cov, return_rate_cov)
+                _cov_results(res, cov, rate_cov, conv)
                 _sample_results(res, ctxs[b]._samples(n_samples, sample_seed), conv)
+                _reproj_results(res, ctxs[b]._reprojection(return_reprojection, cov), conv)
                 out.append((res, infos[b]))
         for s in streams:
             torch.cuda.current_stream().wait_stream(s)

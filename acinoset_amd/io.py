@@ -147,6 +147,29 @@ def dense_detections(points_2d_df, n_cameras, markers, start_frame=None, end_fra
     return det, lo
 
 
+def reprojection_to_points_2d_df(uv, flags, start_frame=0, markers=None, likelihood=None):
+    """Predicted pixels of an FTE solve (``uv`` [N,C,L,2] and ``flags`` [N,C,L] of FTEContext.reprojection / fte_solve(...,
+    return_reprojection=True)) as the long table [frame, camera, marker, x, y, likelihood] of dlc_wide_to_long /
+    create_dlc_points_2d_file, rows ordered by camera, frame, marker (in the order of ``markers``): predictions can be fed to everything that eats
+    detections (dense_detections reads the table back to the same array, likelihood 0 where a row was left out).  Rows
+    whose pixel is NaN (singular plane) or behind the camera (bit 1 of the flags) are left out.  ``markers``: the L names
+    (default: the cheetah's 20); ``likelihood``: a scalar or an array [N,C,L] (default 1.0)."""
+    import pandas as pd
+    uv = np.asarray(uv.detach().cpu().numpy() if hasattr(uv, "detach") else uv, dtype=np.float64)
+    flags = np.asarray(flags.detach().cpu().numpy() if hasattr(flags, "detach") else flags)
+    N, Cn, L, _ = uv.shape
+    if markers is None:
+        from .fte import MARKERS as markers
+    if len(markers) != L or flags.shape != (N, Cn, L):
+        raise ValueError("uv must be [N, C, L, 2], flags [N, C, L] and markers L names")
+    lik = np.broadcast_to(np.asarray(1.0 if likelihood is None else likelihood, dtype=np.float64), (N, Cn, L))
+    keep = np.isfinite(uv).all(-1) & ((flags & 2) == 0)
+    ci, fi, mi = np.nonzero(keep.transpose(1, 0, 2))                       # camera-major: camera, frame, marker
+    return pd.DataFrame({"frame": fi.astype(np.int64) + int(start_frame), "camera": ci.astype(object),
+                         "marker": np.array(markers, dtype=object)[mi], "x": uv[fi, ci, mi, 0], "y": uv[fi, ci, mi, 1],
+                         "likelihood": lik[fi, ci, mi]})[["frame", "camera", "marker", "x", "y", "likelihood"]]
+
+
 def positions_from_points_3d_df(points_3d_df, markers, start_frame, n_frames):
     """The scatter of all_optimizations.py:932-937: positions[N, len(markers), 3], NaN where not triangulated."""
     positions = np.full((n_frames, len(markers), 3), np.nan)

@@ -331,6 +331,32 @@ int acino_fte_covariance_rates(acino_fte_ctx* ctx, double ts, void* d_ws, size_t
 size_t acino_fte_sample_workspace_bytes(const acino_fte_params* p);
 int acino_fte_sample(acino_fte_ctx* ctx, int64_t n_samples, const double* d_z, void* d_ws, size_t ws_bytes,
                      double* d_x_samples, double* d_pos_samples, void* stream);
+/* The solve seen in IMAGE space, at the CURRENT iterate: for every (frame n, camera c, marker l), with p = FK_l(x_n) (the
+ * FK of acino_fk_active) and (uv, J_pi, z_cam) the projection of the context's own camera model - the device function the
+ * assembly calls: the reference's pt3d_to_2d for acino_fte_create, cv2.projectPoints for acino_fte_create_pinhole -,
+ * J_pi = d uv / d p (2 x 3, world frame), z = the detection:
+ *   d_uv[N][C][20][2]        predicted pixel.  NaN on the singular plane abs(z_cam) < 1e-9 (which the assembly drops); behind
+ *                            the camera it is the mirrored projection the solve itself penalises (bit 1 of the flags)
+ *   d_cov_uv[N][C][20][2][2] J_pi cov_pos[n][l] J_pi^T, px^2, both off-diagonal entries the same bits (cov_pos enters by its
+ *                            symmetric part).  Needs d_cov_pos [N][20][3][3], normally d_cov_pos of acino_fte_covariance at
+ *                            the same iterate: d_cov_uv without d_cov_pos is ACINO_ERR_INVALID_ARG.  NaN where uv is
+ *   d_res[N][C][20][2]       uv - z for every detection whose x and y are finite, whatever its likelihood; NaN otherwise and
+ *                            where uv is NaN
+ *   d_weight[N][C][20][2]    the Gauss-Newton curvature weight h in [0, 1] of the redescending loss at e = inv_r_meas *
+ *                            abs(res), per component: what the solve made of the detection (1: used as measured, towards 0:
+ *                            redescended).  Exactly 0 where the assembly gives the detection no weight (likelihood <=
+ *                            dlc_thresh, non-finite, singular plane)
+ *   d_mahal2[N][C][20]       res^T (cov_uv + R^2 I)^-1 res, R = 1 / inv_r_meas: the squared gating distance of the
+ *                            detection under the posterior predictive (chi-square, 2 degrees of freedom); with d_cov_pos ==
+ *                            NULL res^T res / R^2.  NaN where res is
+ *   d_flags[N][C][20] (u8)   bit 0: the assembly weights this detection; bit 1: z_cam < 1e-6 (what n_behind counts among
+ *                            the detections above the threshold); bit 2: singular plane
+ * Any output may be NULL (not all).  Argument checks come before any device call.  ONE launch of a streaming kernel:
+ * stream-ordered, no synchronisation, no allocation, no workspace; the context's solver state, buffers and captured graphs
+ * are untouched.  It reads the iterate alone, in fp64 whatever the context's precision, so it is valid for every context
+ * (clips; sharded / windowed contexts: their local frames). */
+int acino_fte_reprojection(acino_fte_ctx* ctx, const double* d_cov_pos, double* d_uv, double* d_cov_uv, double* d_res,
+                           double* d_weight, double* d_mahal2, uint8_t* d_flags, void* stream);
 /* Live per-kernel timing for bench.py: HIP events recorded on the launch stream around every kernel between
  * begin and end.  end synchronises and returns, per class {elim, elim_deep, update0, update, update_deep, backsub0,
  * backsub, trial, assemble, totals, control, backsub_tail, trunc_check, chunk_sweep, sep_combine, chunk_backsub, refine} (one class per kernel), the summed event time in ms, the launch
