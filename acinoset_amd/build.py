@@ -220,32 +220,131 @@ def _finite_diff_states(x_full, hh):
     return dx, ddx
 
 
-def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16):
-    """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
-    (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
-    on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
-    In a batch a clip that fails numerically does not fail the call: its ``info["status_name"]`` is "numeric" (its results are
-    the last accepted iterate) and the other clips' results stand.  The models' ``camera_model`` (fisheye or pinhole) selects
-    the assembly kernel; a batch that mixes the two is refused."""
+def _batch_camera_model(models):
     cam_models = {getattr(m, "camera_model", "fisheye") for m in models}
     if len(cam_models) > 1:
         raise ValueError("the models of one batch share the camera model (got " + " and ".join(sorted(cam_models)) + ")")
     cam_model = cam_models.pop()
     if cam_model not in calib.CAMERAS:
         raise ValueError(f"camera_model must be one of {calib.CAMERA_MODELS}")
+    return cam_model
+
+
+def _batch_check(models):
+    m0 = models[0]
+    for m in models:
+        if ((m.N, m.P) != (m0.N, m0.P) or repr(m.prog["ops"]) != repr(m0.prog["ops"]) or list(m.active) != list(m0.active)
+                or m.meas.shape != m0.meas.shape):
+            raise ValueError("the models of one batch share skeleton, active states, cameras and length")
+        if not all(np.array_equal(np.asarray(getattr(m, k)), np.asarray(getattr(m0, k))) for k in ("K", "D", "R", "t")):
+            raise ValueError("the models of one batch share the cameras")
+        if (m.h, m.model_weight) != (m0.h, m0.model_weight):
+            raise ValueError("the models of one batch share h and the model weight")
+
+
+def _skel_params(m0, n_act, max_iter=0, lam0=1e-3, ftol=0.0, xtol=0.0, gtol=0.0, l1_eps=1e-2, lam_max=1e16):
+    p = SkelFteParams()
+    p.n_frames, p.n_cams, p.n_pose, p.n_ops = m0.N, int(m0.meas.shape[1]), len(m0.names), len(m0.prog["ops"])
+    p.n_angles, p.n_active, p.max_iter = m0.prog["n_angles"], int(n_act), int(max_iter)
+    p.h, p.model_weight, p.l1_eps = float(m0.h), float(m0.model_weight), float(l1_eps)
+    p.lam0, p.ftol, p.xtol, p.gtol, p.lam_max = float(lam0), float(ftol), float(xtol), float(gtol), float(lam_max)
+    return p
+
+
+def _covariance(models, xs, l1_eps, want, raise_numeric=True):
+    """model_covariance with the outputs chosen by name (``want``: a subset of cov_x, cov_pos, std_pos).  ``raise_numeric=False``:
+    a singular single clip is reported in its ``status`` like a clip of a batch."""
+    if len(models) == 0:
+        raise ValueError("no models")
+    cam_model = _batch_camera_model(models)
+    _batch_check(models)
+    m0 = models[0]
+    B, N, P = len(models), m0.N, m0.P
+    act = np.asarray(m0.active, dtype=np.int32)
+    if len(xs) != B:
+        raise ValueError(f"{len(xs)} iterates for {B} models")
+    xs = [np.asarray(xf, dtype=np.float64) for xf in xs]
+    for xf in xs:
+        if xf.shape != (N, P):
+            raise ValueError(f"every x must be [{N}, {P}] (the full-state layout of results['x'])")
+        if not np.isfinite(xf[:, act]).all():
+            raise ValueError("x must be finite")
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    p = _skel_params(m0, len(act), l1_eps=l1_eps)
+    nbytes = lib().acino_skel_fte_covariance_workspace_bytes(C.byref(p), B)
+    if nbytes == 0:
+        raise ValueError("problem outside the kernel limits (n_active <= 64)")
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)   # noqa: E731
+    meas = t(np.stack([np.nan_to_num(m.meas, nan=0.0) for m in models]))
+    w = t(np.stack([np.where(np.isfinite(m.meas).all(-1), m.weights, 0.0) for m in models]))
+    cams = torch.as_tensor(calib.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
+    lo, hi = t(np.stack([m.lo[:, act] for m in models])), t(np.stack([m.hi[:, act] for m in models]))
+    x = t(np.stack([xf[:, act] for xf in xs]))
+    Pa, Lp = len(act), len(m0.names)
+    empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+    cov_x = empty(B, N, Pa, Pa) if "cov_x" in want else None
+    cov_pos = empty(B, N, Lp, 3, 3) if "cov_pos" in want else None
+    std_pos = empty(B, N, Lp) if "std_pos" in want else None
+    status = (C.c_int32 * B)()
+    act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
+    rc = lib().acino_skel_fte_covariance(C.byref(p), B, 1 if cam_model == "pinhole" else 0, _ops_array(m0.prog), act_c, ptr(meas),
+                                         ptr(w), ptr(cams), ptr(lo), ptr(hi), ptr(x), ptr(cov_x), ptr(cov_pos), ptr(std_pos),
+                                         status, C.c_void_p(ws_ptr), nbytes, stream_ptr())
+    if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
+        check(rc)
+    out = [dict(status=int(status[i])) for i in range(B)]
+    if cov_x is not None:
+        ch = cov_x.cpu().numpy()
+        for i in range(B):
+            full = np.zeros((N, P, P))
+            full[:, act[:, None], act[None, :]] = ch[i]
+            out[i]["cov_x"] = full
+    if cov_pos is not None:
+        for i, c in enumerate(cov_pos.cpu().numpy()):
+            out[i]["cov_pos"] = c
+    if std_pos is not None:
+        for i, c in enumerate(std_pos.cpu().numpy()):
+            out[i]["std_pos"] = c
+    return out
+
+
+def model_covariance(models, xs, std_only=False, l1_eps=1e-2):
+    """Error bars of the skeleton solve at the iterates ``xs`` (one [N, P] array per model, the layout of ``results["x"]``;
+    normally the solutions): acino_skel_fte_covariance, all models in one batched call (one workgroup per clip).  Returns one
+    dict per model: ``cov_x`` [N, P, P] - the frame's diagonal block of A^-1 in the full-state layout, zero rows and columns
+    for the states outside ``model.active`` -, ``cov_pos`` [N, n_pose, 3, 3], ``std_pos`` [N, n_pose] (metres) and ``status``
+    (0, or 5: the clip's matrix is singular - a state observed in no frame - and its arrays are NaN; for ONE model that is a
+    RuntimeError, as in the solve).  ``std_only`` leaves cov_x and cov_pos out.
+
+    A is the Fisher information of the stated model plus the smoothness prior: every weighted detection enters with w^2 (the
+    L1 objective is the likelihood of Laplace noise of scale 1 / w), whatever its residual - neither the solver's IRLS curvature
+    nor ``l1_eps`` enter the matrix, and outliers above the likelihood threshold are not discounted.  Variables the solver would
+    hold at a bound at ``x`` are pinned (zero rows and columns; ``l1_eps`` only enters this rule, through the solver's diagonal).
+    The same batch checks and camera-model selection as ``solve_models``."""
+    return _covariance(models, xs, l1_eps, ("std_pos",) if std_only else ("cov_x", "cov_pos", "std_pos"))
+
+
+def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
+                 return_cov=False):
+    """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
+    (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
+    on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
+    In a batch a clip that fails numerically does not fail the call: its ``info["status_name"]`` is "numeric" (its results are
+    the last accepted iterate) and the other clips' results stand.  The models' ``camera_model`` (fisheye or pinhole) selects
+    the assembly kernel; a batch that mixes the two is refused.  ``return_cov``: ``cov_x``, ``cov_pos`` and ``std_pos`` of
+    ``model_covariance`` at the returned ``x`` are added to every ``results`` (one more batched call; a clip whose covariance
+    is singular gets NaN arrays)."""
+    cam_model = _batch_camera_model(models)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     m0 = models[0]
     B, N, P = len(models), m0.N, m0.P
     act = np.asarray(m0.active, dtype=np.int32)
     prog = m0.prog
-    for m in models:
-        if (m.N, m.P) != (N, P) or repr(m.prog["ops"]) != repr(prog["ops"]) or list(m.active) != list(m0.active) or m.meas.shape != m0.meas.shape:
-            raise ValueError("the models of one batch share skeleton, active states, cameras and length")
-        if not all(np.array_equal(np.asarray(getattr(m, k)), np.asarray(getattr(m0, k))) for k in ("K", "D", "R", "t")):
-            raise ValueError("the models of one batch share the cameras")
-        if (m.h, m.model_weight) != (m0.h, m0.model_weight):
-            raise ValueError("the models of one batch share h and the model weight")
+    _batch_check(models)
     xs = [np.array(m.init_x if x0 is None or x0[i] is None else x0[i], dtype=np.float64, copy=True) for i, m in enumerate(models)]
     inactive = np.setdiff1d(np.arange(P), act)
     for xf in xs:
@@ -253,11 +352,7 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
             raise ValueError(f"x0 must be [{N}, {P}]")
         if np.any(xf[:, inactive] != 0):
             raise ValueError("states that move no pose must start (and stay) at 0")
-    p = SkelFteParams()
-    p.n_frames, p.n_cams, p.n_pose, p.n_ops = N, int(m0.meas.shape[1]), len(m0.names), len(prog["ops"])
-    p.n_angles, p.n_active, p.max_iter = prog["n_angles"], len(act), int(max_iter)
-    p.h, p.model_weight, p.l1_eps = float(m0.h), float(m0.model_weight), float(l1_eps)
-    p.lam0, p.ftol, p.xtol, p.gtol, p.lam_max = float(lam0), float(ftol), float(xtol), float(gtol), float(lam_max)
+    p = _skel_params(m0, len(act), max_iter, lam0, ftol, xtol, gtol, l1_eps, lam_max)
     nbytes = lib().acino_skel_fte_workspace_bytes_batch(C.byref(p), B)
     if nbytes == 0:
         raise ValueError("problem outside the kernel limits (n_active <= 64)")
@@ -281,16 +376,23 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
         xf[:, act] = xh[i]
         dx, ddx = _finite_diff_states(xf, float(m.h))
         out.append((dict(positions=ph[i], x=xf, dx=dx, ddx=ddx), infos[i].as_dict()))
+    if return_cov:
+        del ws
+        covs = _covariance(models, [r["x"] for r, _i in out], l1_eps, ("cov_x", "cov_pos", "std_pos"))
+        for (res, _info), cv in zip(out, covs):
+            res.update(cov_x=cv["cov_x"], cov_pos=cv["cov_pos"], std_pos=cv["std_pos"])
     return out
 
 
-def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16):
+def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
+                return_cov=False):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
-    failure is the call's)."""
+    failure is the call's).  ``return_cov``: ``cov_x`` / ``cov_pos`` / ``std_pos`` at the returned ``x`` (``model_covariance``)
+    join ``results``."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
-                        l1_eps=l1_eps, lam_max=lam_max)[0]
+                        l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -376,7 +478,7 @@ def window_residual_px(model, info):
 
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
-                overlap=20, warm_px=15.0, warm_passes=3, **kw):
+                overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -397,7 +499,15 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     solve_models' (``max_iter``, ...) keywords.
     Returns ``(results, infos, starts)``: ``results`` as convert_to_dict over frames first_frame .. last_frame (plus
     ``start_frame`` and ``seams``: the first frame, relative to first_frame, of every stretch taken from a new window), one
-    info per window (with ``mean_abs_residual_px`` and ``warm_started_from``)."""
+    info per window (with ``mean_abs_residual_px`` and ``warm_started_from``).
+
+    ``return_cov``: after the final stitching ONE batched ``model_covariance`` call over all windows at their final iterates;
+    ``results`` gains ``std_pos`` [frames, n_pose] and ``cov_pos`` [frames, n_pose, 3, 3], every frame from the same window that
+    supplied its ``positions``, and every info ``cov_status``.  A window's covariance ignores the frames outside it, so its bars
+    grow towards the window's ends - which is why the stitch takes each frame from the window in which it is most interior.  A
+    window whose covariance is singular (``cov_status`` 5: a state observed in none of its frames) gives NaN bars for its frames;
+    such windows are listed in ``results["cov_singular_windows"]`` and nothing is raised (``owner``: the window every frame was
+    taken from; ``window_std_pos``: every window's own bars)."""
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
     cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
     build_kw["camera_model"] = cam_model
@@ -490,7 +600,18 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
         info["mean_abs_residual_px"], info["warm_started_from"] = px[i], warm_from[i]
         infos.append(info)
     seams = [int(n) for n in np.nonzero(np.diff(owner) != 0)[0] + 1]
-    return dict(positions=pos, x=x, dx=dx, ddx=ddx, start_frame=f0, seams=seams), infos, starts
+    results = dict(positions=pos, x=x, dx=dx, ddx=ddx, start_frame=f0, seams=seams)
+    if return_cov:
+        covs = _covariance(models, [res["x"] for res, _info in solved], kw.get("l1_eps", 1e-2), ("cov_pos", "std_pos"),
+                           raise_numeric=False)
+        std_pos, cov_pos = np.full((total, Lp), np.nan), np.full((total, Lp, 3, 3), np.nan)
+        for w_i, (st, cv) in enumerate(zip(starts, covs)):
+            mine = np.nonzero(owner == w_i)[0]
+            std_pos[mine], cov_pos[mine] = cv["std_pos"][mine - (st - f0)], cv["cov_pos"][mine - (st - f0)]
+            infos[w_i]["cov_status"] = cv["status"]
+        results.update(std_pos=std_pos, cov_pos=cov_pos, owner=owner.copy(), window_std_pos=[cv["std_pos"] for cv in covs],
+                       cov_singular_windows=[i for i, cv in enumerate(covs) if cv["status"] == 5])
+    return results, infos, starts
 
 
 def convert_to_dict(m, poses=None):
@@ -512,7 +633,8 @@ def save_data(file_data, file_path, poses=None, dict=True):
 
 def solve_optimisation(model, exe_path=None, project_dir=None, poses=None, **solver_kw):
     """build.py:306-335: solve, then save ``data/results/traj_results.pickle`` under ``project_dir`` (when given).
-    ``exe_path`` named the IPOPT executable; there is none here."""
+    ``exe_path`` named the IPOPT executable; there is none here.  ``return_cov=True`` (a ``solve_model`` keyword) adds the
+    covariance arrays to the returned ``results``; the saved pickle keeps the reference's four entries."""
     results, info = solve_model(model, **solver_kw)
     model.x, model.info = results, info
     if project_dir is not None:

@@ -3,6 +3,9 @@
 // differ only in the camera record (SkelDev::cams or SkelDev::pins) and the projection with its 2x3 Jacobian; the product
 // with R, the L1 residual, the IRLS curvature and the singular-plane cut are the same statements.  An include rather than a
 // shared __device__ function keeps the fisheye kernels' code exactly as it was.
+// With ACINO_SKEL_FISHER 1 (k_skel_cov_assemble*, skel_cov.hip; the solve's kernels leave it undefined and compile to what they
+// were) the block that goes to H is the Fisher information J^T diag(w^2) J of the stated Laplace model instead of the IRLS
+// curvature - g, hd and the cost stay the solver's own, they feed its pin rule - and the link operators go to opv_out.
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const SkelDev& D = *dev;
   const int tid = threadIdx.x, n = blockIdx.x;
@@ -23,6 +26,9 @@
   double* hwr = gsr + SK_MAXROWS;                             // [R] IRLS curvature weight
   double* red = hwr + SK_MAXROWS;                             // [8]
   double* A = red + 8;                                        // [R][lda]
+#if defined(ACINO_SKEL_FISHER) && ACINO_SKEL_FISHER
+  double* fwr = A + (size_t)R * lda;                          // [R] Fisher weight w^2 of a kept row (0 for a dropped one)
+#endif
   if (tid < P) xs[tid] = x[(size_t)n * P + tid];
   __syncthreads();
   // ---- link operators: R_loc = Rz(psi) Rx(phi) Ry(theta) of the parent's own angles (reference sign convention)
@@ -67,6 +73,9 @@
     }
   }
   __syncthreads();
+#if defined(ACINO_SKEL_FISHER) && ACINO_SKEL_FISHER
+  for (int e = tid; e < NOPS * 12; e += 256) opv_out[(size_t)n * NOPS * 12 + e] = opv[e];
+#endif
   if (tid < 3) {                         // poses, coordinate by coordinate, in program order
     for (int s = 0; s < NPOSE; ++s) pos[s * 3 + tid] = xs[tid];
     for (int k = 0; k < NOPS; ++k) pos[D.op[k].child * 3 + tid] = pos[D.op[k].parent * 3 + tid] + opv[(k * 4) * 3 + tid];
@@ -152,6 +161,9 @@
       gsr[r0 + 1] = gv;
       hwr[r0] = hu;
       hwr[r0 + 1] = hv;
+#if defined(ACINO_SKEL_FISHER) && ACINO_SKEL_FISHER
+      fwr[r0] = fwr[r0 + 1] = w * w;
+#endif
     }
   }
   if (JAC) {
@@ -179,11 +191,21 @@
       const int p = e / P, pc = e % P;
       if (pc < p) continue;
       double s = 0.0;
+#if defined(ACINO_SKEL_FISHER) && ACINO_SKEL_FISHER
+      for (int r = 0; r < R; ++r) s += fwr[r] * A[r * lda + p] * A[r * lda + pc];
+      if (p == pc) {
+        double sd = 0.0;                                        // the solver's diagonal, in its own summation order
+        for (int r = 0; r < R; ++r) sd += hwr[r] * A[r * lda + p] * A[r * lda + pc];
+        hd[(size_t)n * P + p] = sd + 2.0 * D.q * b0;
+        s += 2.0 * D.q * b0;
+      }
+#else
       for (int r = 0; r < R; ++r) s += hwr[r] * A[r * lda + p] * A[r * lda + pc];
       if (p == pc) {
         s += 2.0 * D.q * b0;
         hd[(size_t)n * P + p] = s;
       }
+#endif
       H[((size_t)n * P + p) * P + pc] = s;
       H[((size_t)n * P + pc) * P + p] = s;
     }

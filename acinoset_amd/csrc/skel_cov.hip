@@ -1,0 +1,595 @@
+// Error bars for the generic-skeleton FTE (gfx950, fp64): per-frame covariance of the active states and of every pose slot,
+// evaluated at a given iterate x (normally the solution of skel_fte.hip).  With the unknowns frame-major,
+//     A = blockdiag_n( sum_{c,l,d} w_ncl^2 J_ncld^T J_ncld )  +  2 q D3^T D3 ,      q = model_weight / h^4
+// J_ncld = d(pi_c(pose_l(x_n))_d)/dx_n from the solve's own assembly statements (skel_assemble_body.inc: same link program,
+// same camera functions, same dropped rows: w = 0, non-finite measurements, |z_cam| < 1e-9), D3 the third-difference operator
+// of a clip with band_coef's coefficients.  This is the FISHER information of the model the objective states plus the prior:
+// sum |w r| is the negative log-likelihood of Laplace noise of scale 1 / w, whose information for location is w^2, and A^-1
+// is the asymptotic covariance of the L1 estimate.  The IRLS curvature w^2 / max(|e|, l1_eps) that the solver factors is
+// deliberately NOT used: it depends on l1_eps, inflates the information of a well-fitted detection by up to 1 / l1_eps, and
+// is a device of the optimiser, not a property of the model.  Every detection above the caller's likelihood threshold counts
+// fully - outliers are not discounted: the bars are those of the stated model.  No Marquardt term.
+// Bound-active variables are pinned exactly as the solver pins them - skel_fixed(x, g, hd, lo, hi) with the solver's own
+// gradient g (L1 + smoothness) and IRLS diagonal hd at x: row and column zeroed, diagonal 1 - and their rows and columns are
+// exactly 0 in every output.
+//   k_skel_cov_assemble[_pinhole]  one workgroup per frame: the assembly body with ACINO_SKEL_FISHER: H_F, g, hd, link operators
+//   k_skel_cov_build               k_skel_build at lam = 0 with H_F for H: band blocks, pin mask, the original diagonal
+//   k_skel_selinv<PT>              ONE workgroup per clip.  Forward: the banded block Cholesky of k_skel_solve (panel in LDS,
+//                                  diagonal tiles by the register pivot chain, window update in memory), factored panels to
+//                                  memory.  Backward, right to left, the Takahashi recursion: with W = L_nn^-1 and
+//                                  Z_j = L_n+j,n W (j = 1..3), and the known blocks S_n+i,n+j of the inverse,
+//                                      S_n+i,n = - sum_j S_n+i,n+j Z_j   (i = 1..3),     S_nn = W^T W - sum_j Z_j^T S_n+j,n
+//                                  and S_nn symmetrised at every frame (without that the recursion amplifies the rounding-level
+//                                  antisymmetric part of the diagonal blocks by an order of magnitude per frame).
+//                                  Every block needed lies inside the factor's band: the result is exact.  All products are
+//                                  fp64 MFMA 16 x 16 tile products.  W and Z_j replace the panel IN PLACE in LDS (133 KB at
+//                                  PT = 64, so nothing else fits at that size); the S blocks replace the factor's blocks in
+//                                  memory (band[n][j] = S_n+j,n) and the 3 x 3 window of a frame is read from there as MFMA
+//                                  operands - at every PT, one code path: the window is 6 blocks of at most 32 KB written
+//                                  by this workgroup one to three frames earlier (L2 hits).
+//   k_skel_cov_out, k_skel_cov_pose  one workgroup per frame, streaming: cov_x from S_nn; G_l (3 x P) from the link operators,
+//                                  G_l cov_x G_l^T and sqrt(trace)
+// A pivot p of the factorisation that is not above SK_PIV_REL * A_pp - non-positive, or positive only by the rounding of the
+// cancellation A_pp - sum L^2 - marks the clip singular (a state observed in no frame of the clip: the prior alone leaves its
+// quadratic drift free): status 5, outputs NaN.  One clip is latency-bound by construction, as the solve; the call is meant
+// for batches (a video is 78 windows).
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "skel_dev.hpp"
+
+namespace acino {
+
+constexpr double SK_PIV_REL = 1e-12;
+
+// ---- Fisher assembly: the solve's assembly body, current iterate only (the clip words are all zero: status 0, buffer 0)
+#define ACINO_SKEL_FISHER 1
+__global__ void __launch_bounds__(256)
+k_skel_cov_assemble(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which, const double* __restrict__ x0,
+                    const double* __restrict__ x1, const double* __restrict__ meas, const double* __restrict__ wgt,
+                    double* __restrict__ H0, double* __restrict__ H1, double* __restrict__ g0, double* __restrict__ g1,
+                    double* __restrict__ hd0, double* __restrict__ hd1, double* __restrict__ c0, double* __restrict__ c1,
+                    double* __restrict__ opv_out) {
+  constexpr bool JAC = true;
+#define ACINO_SKEL_PINHOLE 0
+#include "skel_assemble_body.inc"
+#undef ACINO_SKEL_PINHOLE
+}
+__global__ void __launch_bounds__(256)
+k_skel_cov_assemble_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
+                            const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
+                            const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1,
+                            double* __restrict__ g0, double* __restrict__ g1, double* __restrict__ hd0, double* __restrict__ hd1,
+                            double* __restrict__ c0, double* __restrict__ c1, double* __restrict__ opv_out) {
+  constexpr bool JAC = true;
+#define ACINO_SKEL_PINHOLE 1
+#include "skel_assemble_body.inc"
+#undef ACINO_SKEL_PINHOLE
+}
+#undef ACINO_SKEL_FISHER
+
+// ---- the banded system at lam = 0 (k_skel_build's statements): band[n][j] = block (n + j, n), [PT][PT] row-major;
+//      fxm[n][PT] the pin mask; diag0[n][PT] the diagonal of A as built (the pivot test's yardstick)
+__global__ void __launch_bounds__(256)
+k_skel_cov_build(const SkelDev* __restrict__ dev, const double* __restrict__ x, const double* __restrict__ g,
+                 const double* __restrict__ H, const double* __restrict__ hd, const double* __restrict__ lo,
+                 const double* __restrict__ hi, double* __restrict__ band, unsigned char* __restrict__ fxm,
+                 double* __restrict__ diag0) {
+  const SkelDev& D = *dev;
+  const int tid = threadIdx.x, n = blockIdx.x, P = D.n_act, PT = D.PT, N = D.n_frames, nl = n % N;
+  __shared__ unsigned char fx[4][SK_MAXP];
+  for (int e = tid; e < 4 * P; e += 256) {
+    const int j = e / P, p = e % P;
+    bool f = false;
+    if (nl + j < N) {
+      const size_t q = (size_t)(n + j) * P + p;
+      f = skel_fixed(x[q], g[q], hd[q], lo[q], hi[q]);
+    }
+    fx[j][p] = f ? 1 : 0;
+  }
+  __syncthreads();
+  double* B = band + (size_t)n * 4 * PT * PT;
+  for (int e = tid; e < PT * PT; e += 256) {
+    const int p = e / PT, pc = e % PT;
+    double v = 0.0;
+    if (p < P && pc < P) {
+      if (fx[0][p] || fx[0][pc]) v = p == pc ? 1.0 : 0.0;
+      else v = H[((size_t)n * P + p) * P + pc];
+    } else if (p == pc) v = 1.0;
+    B[e] = v;
+    if (p == pc) diag0[(size_t)n * PT + p] = v;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+      double c = 0.0;
+      if (p == pc && p < P && nl + j < N && !fx[0][p] && !fx[j][p]) c = 2.0 * D.q * band_coef(nl, j, N);
+      B[(size_t)j * PT * PT + e] = c;
+    }
+  }
+  if (tid < PT) fxm[(size_t)n * PT + tid] = tid < P ? fx[0][tid] : 0;
+}
+
+// ---- selected inverse, one workgroup per clip ------------------------------------------------------------------------
+// One 16 x 16 tile product on a wave: acc += sum_{k in [k0, k1)} a_at(k) b_at(k), where lane (li, lk) supplies
+// a_at(k) = opA[row li][k] and b_at(k) = opB[k][col li]; acc[rr] is C[lk + 4 rr][li] (the MFMA layout of the solve).
+template <class FA, class FB>
+__device__ __forceinline__ d4 sk_tile_mac(d4 acc, int k0, int k1, int lk, FA a_at, FB b_at) {
+  for (int k = k0; k < k1; k += 16) {
+    double av[4], bv[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      av[s] = a_at(k + 4 * s + lk);
+      bv[s] = b_at(k + 4 * s + lk);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = mfma(av[s], bv[s], acc);
+  }
+  return acc;
+}
+
+constexpr int SKC_T = 512, SKC_W = SKC_T / 64;
+template <int PT>
+__global__ void __launch_bounds__(SKC_T)
+k_skel_selinv(const SkelDev* __restrict__ dev, SkelClip* __restrict__ clip, double* __restrict__ band_all,
+              const double* __restrict__ diag0_all) {
+  constexpr int LDP = PT + 1, NTP = PT / 16, RT = 4 * NTP, NT2 = NTP * NTP, BB = PT * PT;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  SkelClip& cs = clip[blockIdx.x];
+  int* const numeric_err = &cs.pivot_err;
+  const int N = dev->n_frames;
+  const size_t fr0 = (size_t)blockIdx.x * N;                 // the clip's first frame
+  double* const band = band_all + fr0 * 4 * BB;
+  const double* const diag0 = diag0_all + fr0 * PT;
+  double* Pn = reinterpret_cast<double*>(smem_raw);          // [4 PT][LDP]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  auto load_panel = [&](int n) {
+    for (int e = tid; e < 4 * BB; e += SKC_T) {
+      const int j = e / BB, rem = e % BB;
+      Pn[(j * PT + rem / PT) * LDP + rem % PT] = (n + j < N) ? band[((size_t)n * 4 + j) * BB + rem] : 0.0;
+    }
+  };
+  // ---------------- forward: the factorisation of k_skel_solve (no right-hand side) ----------------
+  for (int n = 0; n < N; ++n) {
+    load_panel(n);
+    __syncthreads();
+#pragma unroll 1
+    for (int kb = 0; kb < NTP; ++kb) {
+      double* Tkk = Pn + (kb * 16) * LDP + kb * 16;
+      if (wave == 0) {
+        d4 acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = Tkk[(lk + 4 * r) * LDP + li];
+        chol16_inv_acc<LDP>(Tkk, acc, lane, numeric_err);
+      }
+      __syncthreads();
+      if (tid < 16) {                                          // pivot = 1 / U_pp^2 against the entry it was cancelled from
+        const double u = Tkk[tid * LDP + tid];
+        if (!(u * u * diag0[(size_t)n * PT + kb * 16 + tid] * SK_PIV_REL < 1.0)) atomicOr(numeric_err, 1);
+      }
+      for (int t = kb + 1 + wave; t < RT; t += SKC_W) {          // panel: tile(t, kb) <- tile(t, kb) U_kk
+        double* At = Pn + (t * 16) * LDP + kb * 16;
+        double av[4], bv[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          av[s] = At[li * LDP + 4 * s + lk];
+          bv[s] = Tkk[(4 * s + lk) * LDP + li];
+        }
+        d4 acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = mfma(av[s], bv[s], acc);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) At[(lk + 4 * rr) * LDP + li] = acc[rr];
+      }
+      __syncthreads();
+      int q = 0;                                             // trailing tiles inside the panel
+      for (int ct = kb + 1; ct < NTP; ++ct)
+        for (int rt = ct; rt < RT; ++rt, ++q) {
+          if (q % SKC_W != wave) continue;
+          double* Cc = Pn + (rt * 16) * LDP + ct * 16;
+          const double* Ar = Pn + (rt * 16) * LDP + kb * 16;
+          const double* Ac = Pn + (ct * 16) * LDP + kb * 16;
+          d4 a;
+          double av[4], bv[4];
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) a[rr] = Cc[(lk + 4 * rr) * LDP + li];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            av[s] = Ar[li * LDP + 4 * s + lk];
+            bv[s] = Ac[li * LDP + 4 * s + lk];
+          }
+#pragma unroll
+          for (int s = 0; s < 4; ++s) a = mfma(-av[s], bv[s], a);
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) Cc[(lk + 4 * rr) * LDP + li] = a[rr];
+        }
+      __syncthreads();
+    }
+    // ---- window update in memory: block (n + i, n + j) -= L_i L_j^T, stored at band[n + j][i - j]
+    for (int t = wave; t < 6 * NT2; t += SKC_W) {
+      const int blk = t / NT2, rem = t % NT2;
+      const int i = blk < 1 ? 1 : (blk < 3 ? 2 : 3), j = blk < 1 ? 1 : (blk < 3 ? blk : blk - 2);
+      const int rt = rem / NTP, ct = rem % NTP;
+      if (n + i >= N) continue;
+      double* Cg = band + ((size_t)(n + j) * 4 + (i - j)) * BB;
+      d4 a;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) a[rr] = Cg[(rt * 16 + lk + 4 * rr) * PT + ct * 16 + li];
+      const double* Ar = Pn + (i * PT + rt * 16 + li) * LDP;
+      const double* Ac = Pn + (j * PT + ct * 16 + li) * LDP;
+      a = sk_tile_mac(a, 0, PT, lk, [&](int k) { return -Ar[k]; }, [&](int k) { return Ac[k]; });
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) Cg[(rt * 16 + lk + 4 * rr) * PT + ct * 16 + li] = a[rr];
+    }
+    // ---- the factored panel replaces the frame's blocks (read again by the backward pass)
+    for (int e = tid; e < 4 * BB; e += SKC_T) {
+      const int j = e / BB, rem = e % BB;
+      if (n + j < N || j == 0) band[((size_t)n * 4 + j) * BB + rem] = Pn[(j * PT + rem / PT) * LDP + rem % PT];
+    }
+    __syncthreads();
+  }
+  {
+    __shared__ int failed;
+    if (tid == 0) {
+      failed = __hip_atomic_load(numeric_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+      if (failed) cs.status = 5;
+    }
+    __syncthreads();
+    if (failed) return;
+  }
+  // ---------------- backward: the Takahashi recursion ----------------
+  // block S_a,b of the inverse (a, b frames of the window, already computed): entry (r, k)
+  auto s_block = [&](int a, int b) -> const double* { return band + ((size_t)std::min(a, b) * 4 + (a > b ? a - b : b - a)) * BB; };
+  for (int n = N - 1; n >= 0; --n) {
+    load_panel(n);
+    __syncthreads();
+    // ---- W = L_nn^-1 in place of the frame's own block: diagonal tiles hold U_kk = L_kk^-T, transpose them; then row by row
+    //      W(r, c) = - W(r, r) sum_{c <= k < r} L(r, k) W(k, c): a row's tiles into registers, then over the row's L tiles
+    if (wave < NTP) {
+      double* T = Pn + (wave * 16) * LDP + wave * 16;
+      double v[4];
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) v[rr] = T[(lk + 4 * rr) * LDP + li];
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) T[li * LDP + lk + 4 * rr] = v[rr];
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int r = 1; r < NTP; ++r) {
+      d4 w = {0, 0, 0, 0};
+      const int c = wave;                                    // tile (r, c), c < r, on wave c
+      if (c < r) {
+        const double* Lr = Pn + (r * 16 + li) * LDP;
+        d4 t = {0, 0, 0, 0};
+        t = sk_tile_mac(t, c * 16, r * 16, lk, [&](int k) { return Lr[k]; }, [&](int k) { return Pn[k * LDP + c * 16 + li]; });
+        const double* Wrr = Pn + (r * 16 + li) * LDP + r * 16;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) w = mfma(-Wrr[4 * s + lk], t[s], w);      // (t's accumulator layout IS the B operand's)
+      }
+      __syncthreads();
+      if (c < r) {
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) Pn[(r * 16 + lk + 4 * rr) * LDP + c * 16 + li] = w[rr];
+      }
+      __syncthreads();
+    }
+    // ---- Z_j = L_n+j,n W in place of L_n+j,n: tile (rt, ct) = sum_{k >= ct} L(rt, k) W(k, ct); all tiles into registers first
+    {
+      constexpr int ZT = 3 * NT2, PER = (ZT + SKC_W - 1) / SKC_W;
+      d4 z[PER];
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        const int t = wave + SKC_W * q;
+        z[q] = d4{0, 0, 0, 0};
+        if (t < ZT) {
+          const int rt = t / NTP, ct = t % NTP;              // rt over the 3 NTP row tiles below the diagonal block
+          const double* Lr = Pn + (PT + rt * 16 + li) * LDP;
+          z[q] = sk_tile_mac(z[q], ct * 16, PT, lk, [&](int k) { return Lr[k]; }, [&](int k) { return Pn[k * LDP + ct * 16 + li]; });
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        const int t = wave + SKC_W * q;
+        if (t < ZT) {
+          const int rt = t / NTP, ct = t % NTP;
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) Pn[(PT + rt * 16 + lk + 4 * rr) * LDP + ct * 16 + li] = z[q][rr];
+        }
+      }
+      __syncthreads();
+    }
+    // ---- S_n+i,n = - sum_j S_n+i,n+j Z_j (i = 1..3) -> band[n][i]; S_n+i,n+j for j > i is the transpose of S_n+j,n+i
+    for (int t = wave; t < 3 * NT2; t += SKC_W) {
+      const int i = 1 + t / NT2, rt = (t % NT2) / NTP, ct = t % NTP;
+      if (n + i >= N) continue;
+      d4 a = {0, 0, 0, 0};
+      for (int j = 1; j < 4; ++j) {
+        if (n + j >= N) break;
+        const double* Sb = s_block(n + i, n + j);
+        const double* Zj = Pn + (size_t)(j * PT) * LDP + ct * 16 + li;
+        if (i >= j) {
+          const double* Sr = Sb + (size_t)(rt * 16 + li) * PT;
+          a = sk_tile_mac(a, 0, PT, lk, [&](int k) { return -Sr[k]; }, [&](int k) { return Zj[k * LDP]; });
+        } else {
+          const double* Sc = Sb + rt * 16 + li;
+          a = sk_tile_mac(a, 0, PT, lk, [&](int k) { return -Sc[(size_t)k * PT]; }, [&](int k) { return Zj[k * LDP]; });
+        }
+      }
+      double* Cg = band + ((size_t)n * 4 + i) * BB;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) Cg[(rt * 16 + lk + 4 * rr) * PT + ct * 16 + li] = a[rr];
+    }
+    __syncthreads();                                         // the new column is read back below (same workgroup)
+    // ---- S_nn = W^T W - sum_j Z_j^T S_n+j,n -> band[n][0]
+    for (int t = wave; t < NT2; t += SKC_W) {
+      const int rt = t / NTP, ct = t % NTP;
+      d4 a = {0, 0, 0, 0};
+      a = sk_tile_mac(a, std::max(rt, ct) * 16, PT, lk, [&](int k) { return Pn[k * LDP + rt * 16 + li]; },
+                      [&](int k) { return Pn[k * LDP + ct * 16 + li]; });
+      for (int j = 1; j < 4; ++j) {
+        if (n + j >= N) break;
+        const double* Zj = Pn + (size_t)(j * PT) * LDP + rt * 16 + li;
+        const double* Sj = band + ((size_t)n * 4 + j) * BB + ct * 16 + li;
+        a = sk_tile_mac(a, 0, PT, lk, [&](int k) { return -Zj[k * LDP]; }, [&](int k) { return Sj[(size_t)k * PT]; });
+      }
+      double* Cg = band + (size_t)n * 4 * BB;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) Cg[(rt * 16 + lk + 4 * rr) * PT + ct * 16 + li] = a[rr];
+    }
+    __syncthreads();
+    // ---- S_nn <- (S_nn + S_nn^T) / 2.  Not cosmetic: the rounding-level antisymmetric part of a diagonal block is the one error
+    //      mode the recursion amplifies (about 10 x per frame on the shipped detections, |Z_1|, |Z_2| ~ 3: the third-difference
+    //      prior extrapolates); projected out at every frame, the blocks stay at the accuracy of the factor.
+    {
+      double* Cg = band + (size_t)n * 4 * BB;
+      for (int e = tid; e < BB; e += SKC_T) {
+        const int p = e / PT, pc = e % PT;
+        if (p > pc) {
+          const double v = 0.5 * (Cg[p * PT + pc] + Cg[pc * PT + p]);
+          Cg[p * PT + pc] = v;
+          Cg[pc * PT + p] = v;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- outputs -------------------------------------------------------------------------------------------------------
+// cov_x[n][P][P] from S_nn (its lower triangle, mirrored); pinned rows / columns 0; NaN for a singular clip
+__global__ void __launch_bounds__(256)
+k_skel_cov_out(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, const double* __restrict__ band,
+               const unsigned char* __restrict__ fxm, double* __restrict__ cov_x) {
+  const SkelDev& D = *dev;
+  const int n = blockIdx.x, P = D.n_act, PT = D.PT;
+  const bool bad = clip[n / D.n_frames].status != 0;
+  const double* S = band + (size_t)n * 4 * PT * PT;
+  const unsigned char* fx = fxm + (size_t)n * PT;
+  for (int e = threadIdx.x; e < P * P; e += 256) {
+    const int p = e / P, pc = e % P;
+    double v = (fx[p] || fx[pc]) ? 0.0 : S[(size_t)max(p, pc) * PT + min(p, pc)];
+    if (bad) v = __builtin_nan("");
+    cov_x[(size_t)n * P * P + e] = v;
+  }
+}
+
+// cov_pos[n][l] = G_l cov_x G_l^T, std_pos[n][l] = sqrt(trace): G_l = [I | d(M off)/d(angle) of the ops on slot l's path]
+__global__ void __launch_bounds__(256)
+k_skel_cov_pose(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, const double* __restrict__ band,
+                const unsigned char* __restrict__ fxm, const double* __restrict__ opv_all, double* __restrict__ cov_pos,
+                double* __restrict__ std_pos) {
+  const SkelDev& D = *dev;
+  const int n = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int P = D.n_act, PT = D.PT, NPOSE = D.n_pose, NOPS = D.n_ops;
+  if (clip[n / D.n_frames].status != 0) {
+    const double nan = __builtin_nan("");
+    for (int e = tid; e < NPOSE * 9; e += 256)
+      if (cov_pos) cov_pos[(size_t)n * NPOSE * 9 + e] = nan;
+    for (int e = tid; e < NPOSE; e += 256)
+      if (std_pos) std_pos[(size_t)n * NPOSE + e] = nan;
+    return;
+  }
+  __shared__ double Cm[SK_MAXP][SK_MAXP + 1];
+  __shared__ double opv[ACINO_SKEL_MAX_OPS * 12];
+  __shared__ double G[4][3][SK_MAXP], T[4][3][SK_MAXP], out9[4][9];
+  const double* S = band + (size_t)n * 4 * PT * PT;
+  const unsigned char* fx = fxm + (size_t)n * PT;
+  for (int e = tid; e < P * P; e += 256) {
+    const int p = e / P, pc = e % P;
+    Cm[p][pc] = (fx[p] || fx[pc]) ? 0.0 : S[(size_t)max(p, pc) * PT + min(p, pc)];
+  }
+  for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
+  __syncthreads();
+  for (int l0 = 0; l0 < NPOSE; l0 += 4) {
+    const int l = l0 + wave;
+    const bool on = l < NPOSE;
+    if (on && lane < P) {
+      double gc[3] = {lane == 0 ? 1.0 : 0.0, lane == 1 ? 1.0 : 0.0, lane == 2 ? 1.0 : 0.0};
+      const unsigned long long path = D.pmask[l];
+      for (int k = 0; k < NOPS; ++k) {
+        if (!((path >> k) & 1ull)) continue;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax)
+          if (D.amap[k][ax] == lane) {
+            const double* dv = opv + (k * 4 + 1 + ax) * 3;
+            gc[0] += dv[0];
+            gc[1] += dv[1];
+            gc[2] += dv[2];
+          }
+      }
+      G[wave][0][lane] = gc[0];
+      G[wave][1][lane] = gc[1];
+      G[wave][2][lane] = gc[2];
+    }
+    __syncthreads();
+    if (on && lane < P) {
+      double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+      for (int q = 0; q < P; ++q) {
+        const double c = Cm[q][lane];
+        t0 += G[wave][0][q] * c;
+        t1 += G[wave][1][q] * c;
+        t2 += G[wave][2][q] * c;
+      }
+      T[wave][0][lane] = t0;
+      T[wave][1][lane] = t1;
+      T[wave][2][lane] = t2;
+    }
+    __syncthreads();
+    if (on && lane < 9) {
+      const int i = lane / 3, j = lane % 3;
+      double s = 0.0;
+      for (int q = 0; q < P; ++q) s += T[wave][i][q] * G[wave][j][q];
+      out9[wave][lane] = s;
+      if (cov_pos) cov_pos[((size_t)n * NPOSE + l) * 9 + lane] = s;
+    }
+    __syncthreads();
+    if (on && lane == 0 && std_pos) std_pos[(size_t)n * NPOSE + l] = sqrt(fmax(out9[wave][0] + out9[wave][4] + out9[wave][8], 0.0));
+    __syncthreads();
+  }
+}
+
+struct SkelCovLayout {
+  size_t dev, clip, H, g, hd, cost, opv, band, diag0, fxm, total;
+};
+static size_t skc_align(size_t v) { return (v + 255) / 256 * 256; }
+static SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops) {
+  SkelCovLayout L;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off = skc_align(off + bytes);
+    return o;
+  };
+  L.dev = take(sizeof(SkelDev));
+  L.clip = take(sizeof(SkelClip) * (size_t)n_clips);
+  L.H = take(sizeof(double) * NT * P * P);
+  L.g = take(sizeof(double) * NT * P);
+  L.hd = take(sizeof(double) * NT * P);
+  L.cost = take(sizeof(double) * NT);
+  L.opv = take(sizeof(double) * NT * (size_t)std::max(n_ops, 1) * 12);
+  L.band = take(sizeof(double) * NT * 4 * PT * PT);
+  L.diag0 = take(sizeof(double) * NT * PT);
+  L.fxm = take(NT * PT);
+  L.total = off;
+  return L;
+}
+
+}  // namespace acino
+
+using namespace acino;
+
+extern "C" {
+
+size_t acino_skel_fte_covariance_workspace_bytes(const acino_skel_fte_params* p, int n_clips) {
+  if (!p || p->n_frames < 1 || p->n_active < 3 || p->n_active > SK_MAXP || n_clips < 1 || p->n_ops < 0 ||
+      p->n_ops > ACINO_SKEL_MAX_OPS)
+    return 0;
+  const int PT = (p->n_active + 15) / 16 * 16;
+  return skel_cov_layout((size_t)p->n_frames * n_clips, n_clips, p->n_active, PT, p->n_ops).total;
+}
+
+int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                              const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                              const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x, double* d_cov_pos,
+                              double* d_std_pos, int32_t* h_status, void* d_ws, size_t ws_bytes, void* stream) {
+  int rc = skel_validate(p);
+  if (rc) return rc;
+  ACINO_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips in 1..65535");
+  ACINO_REQUIRE(camera_model == 0 || camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
+  ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws, "null buffer");
+  ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos, "at least one of d_cov_x, d_cov_pos, d_std_pos");
+  const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16;
+  const size_t NT = (size_t)N * B;                           // frames of all clips
+  ACINO_REQUIRE(NT < (size_t)1 << 31, "n_clips * n_frames < 2^31");
+  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops);
+  if (((uintptr_t)d_ws & 255) != 0) {
+    set_error("workspace must be 256-byte aligned");
+    return ACINO_ERR_WORKSPACE;
+  }
+  if (ws_bytes < lay.total) {
+    set_error("workspace too small (acino_skel_fte_covariance_workspace_bytes)");
+    return ACINO_ERR_WORKSPACE;
+  }
+  std::vector<SkelDev> hv(1);                                // (lives until the one synchronisation at the end)
+  SkelDev& h = hv[0];
+  if ((rc = skel_program(p, h_ops, h_active, h))) return rc;
+  const size_t lds_asm = skel_assemble_lds(h.n_rows, P) + sizeof(double) * h.n_rows;      // + the Fisher weights
+  ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
+  const size_t lds_inv = sizeof(double) * (size_t)4 * PT * (PT + 1);
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)d_ws;
+  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
+  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
+  unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
+  {
+    static PerDeviceOnce attr;
+    if (attr.first()) {
+      const int big = 160 * 1024, big_inv = 160 * 1024 - 1024;
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble_pinhole),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<16>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<32>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<48>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<64>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
+    }
+  }
+  ACINO_HIP_CHECK(hipMemcpyAsync(d_dev, &h, sizeof(SkelDev), hipMemcpyHostToDevice, s));
+  if (camera_model == 1)
+    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, pins), d_cams,
+                                   sizeof(double) * ACINO_PINHOLE_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
+  else
+    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, cams), d_cams,
+                                   sizeof(double) * ACINO_CAM_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
+  ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)B, s));
+  if (camera_model == 1)
+    hipLaunchKernelGGL(k_skel_cov_assemble_pinhole, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas,
+                       d_w, D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
+  else
+    hipLaunchKernelGGL(k_skel_cov_assemble, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas, d_w,
+                       D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
+  ACINO_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_skel_cov_build, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_x, D(lay.g), D(lay.H), D(lay.hd), d_lo, d_hi,
+                     D(lay.band), d_fxm, D(lay.diag0));
+  ACINO_LAUNCH_CHECK();
+  switch (PT) {
+    case 16: hipLaunchKernelGGL(k_skel_selinv<16>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
+    case 32: hipLaunchKernelGGL(k_skel_selinv<32>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
+    case 48: hipLaunchKernelGGL(k_skel_selinv<48>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
+    default: hipLaunchKernelGGL(k_skel_selinv<64>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
+  }
+  ACINO_LAUNCH_CHECK();
+  if (d_cov_x) {
+    hipLaunchKernelGGL(k_skel_cov_out, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_clip, D(lay.band), d_fxm, d_cov_x);
+    ACINO_LAUNCH_CHECK();
+  }
+  if (d_cov_pos || d_std_pos) {
+    hipLaunchKernelGGL(k_skel_cov_pose, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_clip, D(lay.band), d_fxm, D(lay.opv), d_cov_pos,
+                       d_std_pos);
+    ACINO_LAUNCH_CHECK();
+  }
+  std::vector<SkelClip> hc(B);
+  ACINO_HIP_CHECK(hipMemcpyAsync(hc.data(), d_clip, sizeof(SkelClip) * (size_t)B, hipMemcpyDeviceToHost, s));
+  ACINO_HIP_CHECK(hipStreamSynchronize(s));
+  bool numeric = false;
+  for (int b = 0; b < B; ++b) {
+    numeric = numeric || hc[b].status == 5;
+    if (h_status) h_status[b] = hc[b].status;
+  }
+  if (numeric && (B == 1 || !h_status)) {
+    set_error("pivot not above zero in the banded factorisation of the Fisher information (a state observed in no frame of the clip)");
+    return ACINO_ERR_NUMERIC;
+  }
+  return ACINO_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,101 @@
+// What the generic-skeleton kernels of skel_fte.hip (the solve) and skel_cov.hip (the covariance at an iterate) share: the
+// device-resident problem description, the controller state of a clip, the bound-active rule, the argument checks and the
+// host-side compilation of the link program into SkelDev.
+#pragma once
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "dense80.hpp"
+#include "pinhole.hpp"
+
+namespace acino {
+
+constexpr int SK_MAXP = 64;        // active states per frame
+constexpr int SK_MAXROWS = 256;    // residual rows per frame = 2 * poses * cameras
+
+struct SkelDev {                   // device-resident description of one problem
+  int32_t n_frames, n_cams, n_pose, n_ops, n_act, PT, n_rows, pad;
+  double q;                        // model weight / h^4
+  double l1_eps, lam_floor;
+  acino_skel_op op[ACINO_SKEL_MAX_OPS];
+  int8_t amap[ACINO_SKEL_MAX_OPS][4];              // per op: active index of the parent's phi, theta, psi (-1: none)
+  unsigned long long pmask[ACINO_SKEL_MAX_OPS + 1];  // per pose slot: the ops on its path from the root
+  Cam cams[ACINO_MAX_CAMS];
+  Pin pins[ACINO_MAX_CAMS];        // the pinhole model's records (k_skel_assemble_pinhole); appended: the offsets above stay
+};
+
+struct SkelClip {                  // controller state of one clip (device)
+  double F, lam, nu, gnorm, cost0, Ft, pred, step;
+  int32_t cur, status, it, accepted, pivot_err, pad;
+};
+
+// the solver's bound-active rule: at a bound with the gradient pushing outward (d0: the IRLS diagonal of that variable)
+__device__ __forceinline__ bool skel_fixed(double xv, double gv, double d0, double lo, double hi) {
+  const double gtol = GRAD_ZERO_REL * d0;
+  return (xv <= lo && gv > gtol) || (xv >= hi && gv < -gtol);
+}
+
+// dynamic LDS of the assembly kernels (skel_assemble_body.inc), without the Fisher weights of the covariance's assembly
+inline size_t skel_assemble_lds(int n_rows, int P) {
+  return sizeof(double) * (SK_MAXP + ACINO_SKEL_MAX_OPS * 12 + (ACINO_SKEL_MAX_OPS + 1) * 3 + SK_MAXROWS * 5 + 8 +
+                           (size_t)n_rows * (P | 1));
+}
+
+inline int skel_validate(const acino_skel_fte_params* p) {
+  ACINO_REQUIRE(p != nullptr, "params");
+  ACINO_REQUIRE(p->n_frames >= 1, "n_frames >= 1");
+  ACINO_REQUIRE(p->n_cams >= 1 && p->n_cams <= ACINO_MAX_CAMS, "n_cams in 1..16");
+  ACINO_REQUIRE(p->n_pose >= 1 && p->n_pose <= ACINO_SKEL_MAX_OPS + 1, "n_pose");
+  ACINO_REQUIRE(p->n_ops >= 0 && p->n_ops <= ACINO_SKEL_MAX_OPS, "n_ops <= ACINO_SKEL_MAX_OPS");
+  ACINO_REQUIRE(p->n_angles >= 1, "n_angles");
+  ACINO_REQUIRE(p->n_active >= 3 && p->n_active <= SK_MAXP, "n_active in 3..64 (x, y, z and the angles that move a pose)");
+  ACINO_REQUIRE(2 * p->n_pose * p->n_cams <= SK_MAXROWS, "2 * n_pose * n_cams <= 256 residual rows per frame");
+  ACINO_REQUIRE(p->n_pose * p->n_cams <= 256, "n_pose * n_cams <= 256");
+  ACINO_REQUIRE(p->h > 0 && p->model_weight >= 0 && p->l1_eps > 0, "h > 0, model_weight >= 0, l1_eps > 0");
+  ACINO_REQUIRE(p->lam0 > 0 && p->max_iter >= 0, "lam0 > 0, max_iter >= 0");
+  return ACINO_OK;
+}
+
+// The host half of SkelDev (everything but the camera records, which are copied on the device): sizes, constants, the link
+// program, the active index of every op's parent angles, the ops on every pose's path.  h_ops / h_active must not be NULL.
+inline int skel_program(const acino_skel_fte_params* p, const acino_skel_op* h_ops, const int32_t* h_active, SkelDev& h) {
+  const int N = p->n_frames, P = p->n_active, PT = (P + 15) / 16 * 16, L = p->n_angles;
+  memset(&h, 0, sizeof(h));
+  h.n_frames = N;
+  h.n_cams = p->n_cams;
+  h.n_pose = p->n_pose;
+  h.n_ops = p->n_ops;
+  h.n_act = P;
+  h.PT = PT;
+  h.n_rows = 2 * p->n_pose * p->n_cams;
+  h.q = p->model_weight / (p->h * p->h * p->h * p->h);
+  h.l1_eps = p->l1_eps;
+  h.lam_floor = DIAG_FLOOR;
+  ACINO_REQUIRE(h_active[0] == 0 && h_active[1] == 1 && h_active[2] == 2, "the first three active states are x, y, z");
+  std::vector<int> where(3 + 3 * L, -1);
+  for (int a = 0; a < P; ++a) {
+    ACINO_REQUIRE(h_active[a] >= 0 && h_active[a] < 3 + 3 * L && (a == 0 || h_active[a] > h_active[a - 1]),
+                  "active state indices must be increasing and inside [0, 3 + 3 L)");
+    where[h_active[a]] = a;
+  }
+  std::vector<unsigned long long> path(p->n_pose, 0ull);
+  for (int k = 0; k < p->n_ops; ++k) {
+    const acino_skel_op& o = h_ops[k];
+    ACINO_REQUIRE(o.child >= 0 && o.child < p->n_pose && o.parent >= 0 && o.parent < p->n_pose, "op slot out of range");
+    ACINO_REQUIRE(o.angle >= 0 && o.angle < L, "op angle index out of range");
+    h.op[k] = o;
+    for (int ax = 0; ax < 3; ++ax) {
+      const int st = 3 + ax * L + o.angle;
+      const int a = ((o.flags >> ax) & 1) ? where[st] : -1;
+      ACINO_REQUIRE(!((o.flags >> ax) & 1) || a >= 0, "an enabled angle of a parent part is missing from the active states");
+      h.amap[k][ax] = (int8_t)a;
+    }
+    h.amap[k][3] = -1;
+    path[o.child] = path[o.parent] | (1ull << k);          // (a slot defined twice keeps its last definition, as the poses)
+  }
+  for (int l = 0; l < p->n_pose; ++l) h.pmask[l] = path[l];
+  return ACINO_OK;
+}
+
+}  // namespace acino

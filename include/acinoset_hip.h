@@ -548,6 +548,32 @@ int acino_skel_fte_solve_batch_pinhole(const acino_skel_fte_params* p, int n_cli
                                        const double* d_lo, const double* d_hi, double* d_x, double* d_pos, void* d_workspace,
                                        size_t workspace_bytes, acino_skel_fte_info* infos, void* stream);
 
+/* ---- error bars of the generic-skeleton FTE: per-frame covariance of the states and of every pose slot --------------------
+ * Evaluated at the iterate d_x[n_clips][N][n_active] (normally the solution of acino_skel_fte_solve*), unknowns frame-major:
+ *   A = blockdiag_n( sum_{c,l,d} w_ncl^2 J_ncld^T J_ncld ) + 2 q D3^T D3,   q = model_weight / h^4
+ * with J the 1 x n_active rows of the solve's own assembly (rows it drops - w = 0, non-finite measurements, |z_cam| < 1e-9 -
+ * contribute nothing) and D3 the third-difference operator of a clip.  This is the Fisher information of the model the
+ * objective states (sum |w r| is the negative log-likelihood of Laplace noise of scale 1 / w: information w^2) plus the prior;
+ * A^-1 is the asymptotic covariance of the L1 estimate.  The IRLS curvature w^2 / max(|e|, l1_eps) of the solver is NOT used,
+ * every detection the caller gave a weight counts fully (outliers are not discounted), and there is no Marquardt term.
+ * Bound-active variables are pinned as the solver pins them (at a bound with its own gradient pushing outward): their rows
+ * and columns are exactly 0 in every output.  Outputs (fp64, any may be NULL but not all three):
+ *   d_cov_x  [n_clips][N][n_active][n_active]  diagonal blocks of A^-1
+ *   d_cov_pos[n_clips][N][n_pose][3][3]        G_l cov_x G_l^T, G_l the 3 x n_active Jacobian of pose slot l
+ *   d_std_pos[n_clips][N][n_pose]              sqrt(trace(cov_pos)), metres
+ * camera_model 0: d_cams = fisheye records [C][24]; 1: pinhole records [C][32].  h_ops / h_active / d_meas / d_w / d_lo / d_hi as
+ * the solve; limits as the solve (n_active <= 64, 2 n_pose C <= 256); arguments are validated before any device call.  The
+ * workspace is the caller's, 256-byte aligned (ACINO_ERR_WORKSPACE otherwise).  A pivot that is not above zero (a state observed
+ * in no frame of the clip) makes the clip singular: h_status[b] = 5 (else 0) and its outputs are NaN; with n_clips > 1 and
+ * h_status given the call returns ACINO_OK and the other clips stand, otherwise ACINO_ERR_NUMERIC.  One stream synchronisation,
+ * to read the status words.  One workgroup per clip walks the factorisation and the Takahashi recursion: meant for batches. */
+size_t acino_skel_fte_covariance_workspace_bytes(const acino_skel_fte_params* p, int n_clips);
+int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int camera_model /* 0 fisheye: d_cams24, 1 pinhole: d_cams32 */,
+                              const acino_skel_op* h_ops, const int32_t* h_active, const double* d_meas, const double* d_w,
+                              const double* d_cams, const double* d_lo, const double* d_hi, const double* d_x,
+                              double* d_cov_x, double* d_cov_pos, double* d_std_pos, int32_t* h_status /* [n_clips], may be NULL */,
+                              void* d_ws, size_t ws_bytes, void* stream);
+
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
  * 75 = 3 x 25 [pose | velocity | acceleration], pose parameters in the order of qb_list (:734-746).  d_det is
