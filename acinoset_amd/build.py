@@ -251,9 +251,9 @@ def _skel_params(m0, n_act, max_iter=0, lam0=1e-3, ftol=0.0, xtol=0.0, gtol=0.0,
     return p
 
 
-def _covariance(models, xs, l1_eps, want, raise_numeric=True):
-    """model_covariance with the outputs chosen by name (``want``: a subset of cov_x, cov_pos, std_pos).  ``raise_numeric=False``:
-    a singular single clip is reported in its ``status`` like a clip of a batch."""
+def _posterior_inputs(models, xs, l1_eps, workspace_bytes):
+    """What the two calls at an iterate share (model_covariance, model_samples): the batch checks, the device arrays of the
+    models and of ``xs``, the parameter block and a workspace of ``workspace_bytes(p, B)`` bytes."""
     if len(models) == 0:
         raise ValueError("no models")
     cam_model = _batch_camera_model(models)
@@ -272,7 +272,7 @@ def _covariance(models, xs, l1_eps, want, raise_numeric=True):
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     p = _skel_params(m0, len(act), l1_eps=l1_eps)
-    nbytes = lib().acino_skel_fte_covariance_workspace_bytes(C.byref(p), B)
+    nbytes = workspace_bytes(p, B)
     if nbytes == 0:
         raise ValueError("problem outside the kernel limits (n_active <= 64)")
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
@@ -283,16 +283,26 @@ def _covariance(models, xs, l1_eps, want, raise_numeric=True):
     cams = torch.as_tensor(calib.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
     lo, hi = t(np.stack([m.lo[:, act] for m in models])), t(np.stack([m.hi[:, act] for m in models]))
     x = t(np.stack([xf[:, act] for xf in xs]))
+    act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
+    head = (C.byref(p), B, 1 if cam_model == "pinhole" else 0, _ops_array(m0.prog), act_c, ptr(meas), ptr(w), ptr(cams), ptr(lo),
+            ptr(hi), ptr(x))
+    keep = (p, ws, meas, w, cams, lo, hi, x, act_c)
+    return dict(xs=xs, act=act, dev=dev, head=head, tail=(C.c_void_p(ws_ptr), nbytes, stream_ptr()), keep=keep)
+
+
+def _covariance(models, xs, l1_eps, want, raise_numeric=True):
+    """model_covariance with the outputs chosen by name (``want``: a subset of cov_x, cov_pos, std_pos).  ``raise_numeric=False``:
+    a singular single clip is reported in its ``status`` like a clip of a batch."""
+    io_ = _posterior_inputs(models, xs, l1_eps, lambda p, B: lib().acino_skel_fte_covariance_workspace_bytes(C.byref(p), B))
+    m0, act, dev = models[0], io_["act"], io_["dev"]
+    B, N, P = len(models), m0.N, m0.P
     Pa, Lp = len(act), len(m0.names)
     empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
     cov_x = empty(B, N, Pa, Pa) if "cov_x" in want else None
     cov_pos = empty(B, N, Lp, 3, 3) if "cov_pos" in want else None
     std_pos = empty(B, N, Lp) if "std_pos" in want else None
     status = (C.c_int32 * B)()
-    act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
-    rc = lib().acino_skel_fte_covariance(C.byref(p), B, 1 if cam_model == "pinhole" else 0, _ops_array(m0.prog), act_c, ptr(meas),
-                                         ptr(w), ptr(cams), ptr(lo), ptr(hi), ptr(x), ptr(cov_x), ptr(cov_pos), ptr(std_pos),
-                                         status, C.c_void_p(ws_ptr), nbytes, stream_ptr())
+    rc = lib().acino_skel_fte_covariance(*io_["head"], ptr(cov_x), ptr(cov_pos), ptr(std_pos), status, *io_["tail"])
     if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
         check(rc)
     out = [dict(status=int(status[i])) for i in range(B)]
@@ -327,8 +337,56 @@ def model_covariance(models, xs, std_only=False, l1_eps=1e-2):
     return _covariance(models, xs, l1_eps, ("std_pos",) if std_only else ("cov_x", "cov_pos", "std_pos"))
 
 
+def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1_eps=1e-2):
+    """Joint draws of the whole trajectory from the Laplace posterior of the skeleton solve at the iterates ``xs`` (one [N, P]
+    array per model, the layout of ``results["x"]``): acino_skel_fte_sample, all models in ONE batched call.  With A the matrix
+    of ``model_covariance`` (Fisher blocks, smoothness prior, bound-active variables pinned) and A = L L^T,
+    ``x_samples[s] = x + L^-T z[s]``: for standard-normal z the draws have covariance A^-1 with every cross-frame block - what
+    step length, mean speed over a stride or the range of a joint angle over the clip need, and what the per-frame blocks of
+    ``model_covariance`` cannot give.  ``z``: an optional [B][S][N][n_active] array (the map is deterministic; sample s depends
+    on z[:, s] alone); otherwise ``np.random.default_rng(seed).standard_normal`` of that shape with S = ``n_samples`` is drawn
+    on the host.  Returns one dict per model: ``x_samples`` [S, N, P] in the full-state layout (states outside ``model.active``
+    keep ``x``'s values; pinned variables equal ``x`` exactly), ``pos_samples`` [S, N, n_pose, 3] - the forward kinematics of
+    every sample, not a linearisation - unless ``positions=False``, and ``status`` (0, or 5: singular, NaN samples; for ONE
+    model that is a RuntimeError, as in ``model_covariance``).  Samples are NOT clipped to the limits: the Laplace posterior is
+    a Gaussian and only the pinned variables are held (``np.clip`` to ``model.lo`` / ``model.hi`` if the box matters)."""
+    B = len(models)
+    n_act = len(models[0].active) if B else 0
+    N = models[0].N if B else 0
+    if z is None:
+        if n_samples is None or int(n_samples) < 1:
+            raise ValueError("n_samples >= 1 (or pass z)")
+        z = np.random.default_rng(seed).standard_normal((B, int(n_samples), N, n_act))
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    if z.ndim != 4 or z.shape[0] != B or z.shape[1] < 1 or z.shape[2:] != (N, n_act):
+        raise ValueError(f"z must be [{B}][S][{N}][{n_act}] (models, samples, frames, active states), S >= 1")
+    if n_samples is not None and int(n_samples) != z.shape[1]:
+        raise ValueError(f"n_samples = {n_samples}, z holds {z.shape[1]} samples")
+    if not np.isfinite(z).all():
+        raise ValueError("z must be finite")
+    S = z.shape[1]
+    io_ = _posterior_inputs(models, xs, l1_eps, lambda p, nb: lib().acino_skel_fte_sample_workspace_bytes(C.byref(p), nb, S))
+    m0, act, dev = models[0], io_["act"], io_["dev"]
+    zd = torch.as_tensor(z, device=dev)
+    xs_d = torch.empty((B, S, N, n_act), dtype=torch.float64, device=dev)
+    pos_d = torch.empty((B, S, N, len(m0.names), 3), dtype=torch.float64, device=dev) if positions else None
+    status = (C.c_int32 * B)()
+    check(lib().acino_skel_fte_sample(*io_["head"], S, ptr(zd), ptr(xs_d), ptr(pos_d), status, *io_["tail"]))
+    xh = xs_d.cpu().numpy()
+    ph = pos_d.cpu().numpy() if positions else None
+    out = []
+    for i, xf in enumerate(io_["xs"]):
+        full = np.broadcast_to(xf, (S,) + xf.shape).copy()
+        full[:, :, act] = xh[i]
+        o = dict(x_samples=full, status=int(status[i]))
+        if positions:
+            o["pos_samples"] = ph[i]
+        out.append(o)
+    return out
+
+
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
-                 return_cov=False):
+                 return_cov=False, n_samples=0, sample_seed=0):
     """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
@@ -336,7 +394,8 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     the last accepted iterate) and the other clips' results stand.  The models' ``camera_model`` (fisheye or pinhole) selects
     the assembly kernel; a batch that mixes the two is refused.  ``return_cov``: ``cov_x``, ``cov_pos`` and ``std_pos`` of
     ``model_covariance`` at the returned ``x`` are added to every ``results`` (one more batched call; a clip whose covariance
-    is singular gets NaN arrays)."""
+    is singular gets NaN arrays).  ``n_samples`` > 0: ``x_samples`` [S, N, P] and ``pos_samples`` [S, N, n_pose, 3] of
+    ``model_samples(models, xs, n_samples, seed=sample_seed)`` at the returned ``x`` join every ``results`` the same way."""
     cam_model = _batch_camera_model(models)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -381,18 +440,23 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
         covs = _covariance(models, [r["x"] for r, _i in out], l1_eps, ("cov_x", "cov_pos", "std_pos"))
         for (res, _info), cv in zip(out, covs):
             res.update(cov_x=cv["cov_x"], cov_pos=cv["cov_pos"], std_pos=cv["std_pos"])
+    if n_samples:
+        ws = None
+        draws = model_samples(models, [r["x"] for r, _i in out], n_samples=n_samples, seed=sample_seed, l1_eps=l1_eps)
+        for (res, _info), dr in zip(out, draws):
+            res.update(x_samples=dr["x_samples"], pos_samples=dr["pos_samples"])
     return out
 
 
 def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
-                return_cov=False):
+                return_cov=False, n_samples=0, sample_seed=0):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
     failure is the call's).  ``return_cov``: ``cov_x`` / ``cov_pos`` / ``std_pos`` at the returned ``x`` (``model_covariance``)
-    join ``results``."""
+    join ``results``; ``n_samples`` > 0: ``x_samples`` / ``pos_samples`` (``model_samples`` with ``seed=sample_seed``) do."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
-                        l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov)[0]
+                        l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -507,7 +571,12 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     grow towards the window's ends - which is why the stitch takes each frame from the window in which it is most interior.  A
     window whose covariance is singular (``cov_status`` 5: a state observed in none of its frames) gives NaN bars for its frames;
     such windows are listed in ``results["cov_singular_windows"]`` and nothing is raised (``owner``: the window every frame was
-    taken from; ``window_std_pos``: every window's own bars)."""
+    taken from; ``window_std_pos``: every window's own bars).
+
+    There is no ``n_samples`` here: a stitched video is not one posterior (every window has its own, and draws of neighbouring
+    windows are independent); call ``model_samples`` on the windows' models."""
+    if "n_samples" in kw or "sample_seed" in kw:
+        raise TypeError("solve_video takes no n_samples: a stitched video is not one posterior (use model_samples per window)")
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
     cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
     build_kw["camera_model"] = cam_model
@@ -634,7 +703,8 @@ def save_data(file_data, file_path, poses=None, dict=True):
 def solve_optimisation(model, exe_path=None, project_dir=None, poses=None, **solver_kw):
     """build.py:306-335: solve, then save ``data/results/traj_results.pickle`` under ``project_dir`` (when given).
     ``exe_path`` named the IPOPT executable; there is none here.  ``return_cov=True`` (a ``solve_model`` keyword) adds the
-    covariance arrays to the returned ``results``; the saved pickle keeps the reference's four entries."""
+    covariance arrays to the returned ``results``, ``n_samples=S`` (with ``sample_seed``) the posterior samples; the saved pickle
+    keeps the reference's four entries."""
     results, info = solve_model(model, **solver_kw)
     model.x, model.info = results, info
     if project_dir is not None:

@@ -16,7 +16,7 @@
 //   k_skel_cov_build               k_skel_build at lam = 0 with H_F for H: band blocks, pin mask, the original diagonal
 //   k_skel_selinv<PT>              ONE workgroup per clip.  Forward: the banded block Cholesky of k_skel_solve (panel in LDS,
 //                                  diagonal tiles by the register pivot chain, window update in memory), factored panels to
-//                                  memory.  Backward, right to left, the Takahashi recursion: with W = L_nn^-1 and
+//                                  memory - skel_band_factor<PT> of skel_factor.hpp, shared with skel_sample.hip.  Backward, right to left, the Takahashi recursion: with W = L_nn^-1 and
 //                                  Z_j = L_n+j,n W (j = 1..3), and the known blocks S_n+i,n+j of the inverse,
 //                                      S_n+i,n = - sum_j S_n+i,n+j Z_j   (i = 1..3),     S_nn = W^T W - sum_j Z_j^T S_n+j,n
 //                                  and S_nn symmetrised at every frame (without that the recursion amplifies the rounding-level
@@ -40,11 +40,9 @@
 #include <limits>
 #include <vector>
 
-#include "skel_dev.hpp"
+#include "skel_factor.hpp"
 
 namespace acino {
-
-constexpr double SK_PIV_REL = 1e-12;
 
 // ---- Fisher assembly: the solve's assembly body, current iterate only (the clip words are all zero: status 0, buffer 0)
 #define ACINO_SKEL_FISHER 1
@@ -112,30 +110,12 @@ k_skel_cov_build(const SkelDev* __restrict__ dev, const double* __restrict__ x, 
   if (tid < PT) fxm[(size_t)n * PT + tid] = tid < P ? fx[0][tid] : 0;
 }
 
-// ---- selected inverse, one workgroup per clip ------------------------------------------------------------------------
-// One 16 x 16 tile product on a wave: acc += sum_{k in [k0, k1)} a_at(k) b_at(k), where lane (li, lk) supplies
-// a_at(k) = opA[row li][k] and b_at(k) = opB[k][col li]; acc[rr] is C[lk + 4 rr][li] (the MFMA layout of the solve).
-template <class FA, class FB>
-__device__ __forceinline__ d4 sk_tile_mac(d4 acc, int k0, int k1, int lk, FA a_at, FB b_at) {
-  for (int k = k0; k < k1; k += 16) {
-    double av[4], bv[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      av[s] = a_at(k + 4 * s + lk);
-      bv[s] = b_at(k + 4 * s + lk);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc = mfma(av[s], bv[s], acc);
-  }
-  return acc;
-}
-
-constexpr int SKC_T = 512, SKC_W = SKC_T / 64;
+// ---- selected inverse, one workgroup per clip (sk_tile_mac, SKC_T and the forward pass: skel_factor.hpp) -------------------
 template <int PT>
 __global__ void __launch_bounds__(SKC_T)
 k_skel_selinv(const SkelDev* __restrict__ dev, SkelClip* __restrict__ clip, double* __restrict__ band_all,
               const double* __restrict__ diag0_all) {
-  constexpr int LDP = PT + 1, NTP = PT / 16, RT = 4 * NTP, NT2 = NTP * NTP, BB = PT * PT;
+  constexpr int LDP = PT + 1, NTP = PT / 16, NT2 = NTP * NTP, BB = PT * PT;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   SkelClip& cs = clip[blockIdx.x];
   int* const numeric_err = &cs.pivot_err;
@@ -145,91 +125,9 @@ k_skel_selinv(const SkelDev* __restrict__ dev, SkelClip* __restrict__ clip, doub
   const double* const diag0 = diag0_all + fr0 * PT;
   double* Pn = reinterpret_cast<double*>(smem_raw);          // [4 PT][LDP]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  auto load_panel = [&](int n) {
-    for (int e = tid; e < 4 * BB; e += SKC_T) {
-      const int j = e / BB, rem = e % BB;
-      Pn[(j * PT + rem / PT) * LDP + rem % PT] = (n + j < N) ? band[((size_t)n * 4 + j) * BB + rem] : 0.0;
-    }
-  };
+  auto load_panel = [&](int n) { skel_load_panel<PT>(Pn, band, n, N); };
   // ---------------- forward: the factorisation of k_skel_solve (no right-hand side) ----------------
-  for (int n = 0; n < N; ++n) {
-    load_panel(n);
-    __syncthreads();
-#pragma unroll 1
-    for (int kb = 0; kb < NTP; ++kb) {
-      double* Tkk = Pn + (kb * 16) * LDP + kb * 16;
-      if (wave == 0) {
-        d4 acc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = Tkk[(lk + 4 * r) * LDP + li];
-        chol16_inv_acc<LDP>(Tkk, acc, lane, numeric_err);
-      }
-      __syncthreads();
-      if (tid < 16) {                                          // pivot = 1 / U_pp^2 against the entry it was cancelled from
-        const double u = Tkk[tid * LDP + tid];
-        if (!(u * u * diag0[(size_t)n * PT + kb * 16 + tid] * SK_PIV_REL < 1.0)) atomicOr(numeric_err, 1);
-      }
-      for (int t = kb + 1 + wave; t < RT; t += SKC_W) {          // panel: tile(t, kb) <- tile(t, kb) U_kk
-        double* At = Pn + (t * 16) * LDP + kb * 16;
-        double av[4], bv[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          av[s] = At[li * LDP + 4 * s + lk];
-          bv[s] = Tkk[(4 * s + lk) * LDP + li];
-        }
-        d4 acc = {0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = mfma(av[s], bv[s], acc);
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) At[(lk + 4 * rr) * LDP + li] = acc[rr];
-      }
-      __syncthreads();
-      int q = 0;                                             // trailing tiles inside the panel
-      for (int ct = kb + 1; ct < NTP; ++ct)
-        for (int rt = ct; rt < RT; ++rt, ++q) {
-          if (q % SKC_W != wave) continue;
-          double* Cc = Pn + (rt * 16) * LDP + ct * 16;
-          const double* Ar = Pn + (rt * 16) * LDP + kb * 16;
-          const double* Ac = Pn + (ct * 16) * LDP + kb * 16;
-          d4 a;
-          double av[4], bv[4];
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) a[rr] = Cc[(lk + 4 * rr) * LDP + li];
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            av[s] = Ar[li * LDP + 4 * s + lk];
-            bv[s] = Ac[li * LDP + 4 * s + lk];
-          }
-#pragma unroll
-          for (int s = 0; s < 4; ++s) a = mfma(-av[s], bv[s], a);
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) Cc[(lk + 4 * rr) * LDP + li] = a[rr];
-        }
-      __syncthreads();
-    }
-    // ---- window update in memory: block (n + i, n + j) -= L_i L_j^T, stored at band[n + j][i - j]
-    for (int t = wave; t < 6 * NT2; t += SKC_W) {
-      const int blk = t / NT2, rem = t % NT2;
-      const int i = blk < 1 ? 1 : (blk < 3 ? 2 : 3), j = blk < 1 ? 1 : (blk < 3 ? blk : blk - 2);
-      const int rt = rem / NTP, ct = rem % NTP;
-      if (n + i >= N) continue;
-      double* Cg = band + ((size_t)(n + j) * 4 + (i - j)) * BB;
-      d4 a;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) a[rr] = Cg[(rt * 16 + lk + 4 * rr) * PT + ct * 16 + li];
-      const double* Ar = Pn + (i * PT + rt * 16 + li) * LDP;
-      const double* Ac = Pn + (j * PT + ct * 16 + li) * LDP;
-      a = sk_tile_mac(a, 0, PT, lk, [&](int k) { return -Ar[k]; }, [&](int k) { return Ac[k]; });
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) Cg[(rt * 16 + lk + 4 * rr) * PT + ct * 16 + li] = a[rr];
-    }
-    // ---- the factored panel replaces the frame's blocks (read again by the backward pass)
-    for (int e = tid; e < 4 * BB; e += SKC_T) {
-      const int j = e / BB, rem = e % BB;
-      if (n + j < N || j == 0) band[((size_t)n * 4 + j) * BB + rem] = Pn[(j * PT + rem / PT) * LDP + rem % PT];
-    }
-    __syncthreads();
-  }
+  skel_band_factor<PT>(N, band, diag0, numeric_err, Pn);
   {
     __shared__ int failed;
     if (tid == 0) {
@@ -451,11 +349,8 @@ k_skel_cov_pose(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ cl
   }
 }
 
-struct SkelCovLayout {
-  size_t dev, clip, H, g, hd, cost, opv, band, diag0, fxm, total;
-};
 static size_t skc_align(size_t v) { return (v + 255) / 256 * 256; }
-static SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops) {
+SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops) {
   SkelCovLayout L;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -475,6 +370,52 @@ static SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int 
   L.fxm = take(NT * PT);
   L.total = off;
   return L;
+}
+
+int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                          const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                          const double* d_lo, const double* d_hi, const double* d_x, void* d_ws, const SkelCovLayout& lay,
+                          SkelDev& h, hipStream_t s) {
+  const int B = n_clips, P = p->n_active;
+  const size_t NT = (size_t)p->n_frames * B;
+  int rc;
+  if ((rc = skel_program(p, h_ops, h_active, h))) return rc;
+  const size_t lds_asm = skel_assemble_lds(h.n_rows, P) + sizeof(double) * h.n_rows;      // + the Fisher weights
+  ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
+  char* base = (char*)d_ws;
+  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
+  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
+  unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
+  {
+    static PerDeviceOnce attr;
+    if (attr.first()) {
+      const int big = 160 * 1024;
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble_pinhole),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    }
+  }
+  ACINO_HIP_CHECK(hipMemcpyAsync(d_dev, &h, sizeof(SkelDev), hipMemcpyHostToDevice, s));
+  if (camera_model == 1)
+    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, pins), d_cams,
+                                   sizeof(double) * ACINO_PINHOLE_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
+  else
+    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, cams), d_cams,
+                                   sizeof(double) * ACINO_CAM_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
+  ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)B, s));
+  if (camera_model == 1)
+    hipLaunchKernelGGL(k_skel_cov_assemble_pinhole, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas,
+                       d_w, D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
+  else
+    hipLaunchKernelGGL(k_skel_cov_assemble, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas, d_w,
+                       D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
+  ACINO_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_skel_cov_build, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_x, D(lay.g), D(lay.H), D(lay.hd), d_lo, d_hi,
+                     D(lay.band), d_fxm, D(lay.diag0));
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
 }
 
 }  // namespace acino
@@ -514,12 +455,10 @@ int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int c
     return ACINO_ERR_WORKSPACE;
   }
   std::vector<SkelDev> hv(1);                                // (lives until the one synchronisation at the end)
-  SkelDev& h = hv[0];
-  if ((rc = skel_program(p, h_ops, h_active, h))) return rc;
-  const size_t lds_asm = skel_assemble_lds(h.n_rows, P) + sizeof(double) * h.n_rows;      // + the Fisher weights
-  ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
-  const size_t lds_inv = sizeof(double) * (size_t)4 * PT * (PT + 1);
   hipStream_t s = (hipStream_t)stream;
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, hv[0], s)))
+    return rc;
+  const size_t lds_inv = skel_factor_lds(PT);
   char* base = (char*)d_ws;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
   SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
@@ -528,11 +467,7 @@ int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int c
   {
     static PerDeviceOnce attr;
     if (attr.first()) {
-      const int big = 160 * 1024, big_inv = 160 * 1024 - 1024;
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble_pinhole),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
+      const int big_inv = 160 * 1024 - 1024;
       ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<16>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
       ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<32>),
@@ -543,24 +478,6 @@ int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int c
                                           hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
     }
   }
-  ACINO_HIP_CHECK(hipMemcpyAsync(d_dev, &h, sizeof(SkelDev), hipMemcpyHostToDevice, s));
-  if (camera_model == 1)
-    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, pins), d_cams,
-                                   sizeof(double) * ACINO_PINHOLE_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
-  else
-    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, cams), d_cams,
-                                   sizeof(double) * ACINO_CAM_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
-  ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)B, s));
-  if (camera_model == 1)
-    hipLaunchKernelGGL(k_skel_cov_assemble_pinhole, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas,
-                       d_w, D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
-  else
-    hipLaunchKernelGGL(k_skel_cov_assemble, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas, d_w,
-                       D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
-  ACINO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_skel_cov_build, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_x, D(lay.g), D(lay.H), D(lay.hd), d_lo, d_hi,
-                     D(lay.band), d_fxm, D(lay.diag0));
-  ACINO_LAUNCH_CHECK();
   switch (PT) {
     case 16: hipLaunchKernelGGL(k_skel_selinv<16>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
     case 32: hipLaunchKernelGGL(k_skel_selinv<32>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;

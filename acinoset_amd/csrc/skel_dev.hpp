@@ -36,6 +36,45 @@ __device__ __forceinline__ bool skel_fixed(double xv, double gv, double d0, doub
   return (xv <= lo && gv > gtol) || (xv >= hi && gv < -gtol);
 }
 
+// poses of one frame from its active states: the link program, pose[child] = pose[parent] + M(parent's own angles) off
+// (states outside the active set are 0).  xs[n_act] -> out[n_pose][3]; out is read back (a slot's parent), by this thread only.
+__device__ __forceinline__ void skel_pose_row(const SkelDev& D, const double* __restrict__ xs, double* __restrict__ out) {
+  for (int s = 0; s < D.n_pose; ++s)
+    for (int j = 0; j < 3; ++j) out[s * 3 + j] = xs[j];
+  for (int k = 0; k < D.n_ops; ++k) {
+    const acino_skel_op& o = D.op[k];
+    double Rm[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    if (o.flags & 2) {
+      double s, c;
+      sincos(D.amap[k][1] >= 0 ? xs[D.amap[k][1]] : 0.0, &s, &c);
+      Rm[0][0] = c; Rm[0][2] = -s; Rm[2][0] = s; Rm[2][2] = c;
+    }
+    if (o.flags & 1) {
+      double s, c;
+      sincos(D.amap[k][0] >= 0 ? xs[D.amap[k][0]] : 0.0, &s, &c);
+      for (int j = 0; j < 3; ++j) {
+        const double r1 = Rm[1][j], r2 = Rm[2][j];
+        Rm[1][j] = c * r1 + s * r2;
+        Rm[2][j] = -s * r1 + c * r2;
+      }
+    }
+    if (o.flags & 4) {
+      double s, c;
+      sincos(D.amap[k][2] >= 0 ? xs[D.amap[k][2]] : 0.0, &s, &c);
+      for (int j = 0; j < 3; ++j) {
+        const double r0 = Rm[0][j], r1 = Rm[1][j];
+        Rm[0][j] = c * r0 + s * r1;
+        Rm[1][j] = -s * r0 + c * r1;
+      }
+    }
+    for (int i = 0; i < 3; ++i) {
+      const double d = (o.flags & 8) ? Rm[i][0] * o.off[0] + Rm[i][1] * o.off[1] + Rm[i][2] * o.off[2]
+                                     : Rm[0][i] * o.off[0] + Rm[1][i] * o.off[1] + Rm[2][i] * o.off[2];
+      out[o.child * 3 + i] = out[o.parent * 3 + i] + d;
+    }
+  }
+}
+
 // dynamic LDS of the assembly kernels (skel_assemble_body.inc), without the Fisher weights of the covariance's assembly
 inline size_t skel_assemble_lds(int n_rows, int P) {
   return sizeof(double) * (SK_MAXP + ACINO_SKEL_MAX_OPS * 12 + (ACINO_SKEL_MAX_OPS + 1) * 3 + SK_MAXROWS * 5 + 8 +

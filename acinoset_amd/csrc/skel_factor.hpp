@@ -1,0 +1,149 @@
+// What the two uses of the skeleton FTE's Fisher matrix share (skel_cov.hip: the selected inverse; skel_sample.hip: joint
+// posterior samples): the 16 x 16 tile product, the banded block Cholesky A = L L^T as a device function template, the
+// workspace layout and the launches that build the band at an iterate.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+
+#include "skel_dev.hpp"
+
+namespace acino {
+
+constexpr double SK_PIV_REL = 1e-12;
+
+// One 16 x 16 tile product on a wave: acc += sum_{k in [k0, k1)} a_at(k) b_at(k), where lane (li, lk) supplies
+// a_at(k) = opA[row li][k] and b_at(k) = opB[k][col li]; acc[rr] is C[lk + 4 rr][li] (the MFMA layout of the solve).
+template <class FA, class FB>
+__device__ __forceinline__ d4 sk_tile_mac(d4 acc, int k0, int k1, int lk, FA a_at, FB b_at) {
+  for (int k = k0; k < k1; k += 16) {
+    double av[4], bv[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      av[s] = a_at(k + 4 * s + lk);
+      bv[s] = b_at(k + 4 * s + lk);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = mfma(av[s], bv[s], acc);
+  }
+  return acc;
+}
+
+constexpr int SKC_T = 512, SKC_W = SKC_T / 64;    // threads / waves of the one workgroup that factors a clip
+
+// dynamic LDS of a kernel that calls skel_band_factor<PT>: the panel [4 PT][PT + 1]
+inline size_t skel_factor_lds(int PT) { return sizeof(double) * (size_t)4 * PT * (PT + 1); }
+
+// frame n's four blocks (n + j, n), j = 0..3, into the panel Pn[4 PT][PT + 1] (zeros past the clip's end); SKC_T threads
+template <int PT>
+__device__ __forceinline__ void skel_load_panel(double* __restrict__ Pn, const double* __restrict__ band, int n, int N) {
+  constexpr int LDP = PT + 1, BB = PT * PT;
+  for (int e = threadIdx.x; e < 4 * BB; e += SKC_T) {
+    const int j = e / BB, rem = e % BB;
+    Pn[(j * PT + rem / PT) * LDP + rem % PT] = (n + j < N) ? band[((size_t)n * 4 + j) * BB + rem] : 0.0;
+  }
+}
+
+// The banded block Cholesky of one clip, left to right, by ONE workgroup of SKC_T threads (the factorisation of k_skel_solve
+// without a right-hand side): panel in LDS, diagonal tiles by the register pivot chain, window update in memory, factored
+// panels written back.  band[n][j] = block (n + j, n) of A in, of L out - except that every diagonal 16 x 16 tile of
+// band[n][0] = L_nn is replaced by U_kk = L_kk^-T (upper triangular, exact zeros below).  diag0[n][PT]: the diagonal of A as
+// built; a pivot that is not above SK_PIV_REL * A_pp sets *numeric_err.  Ends with a workgroup barrier.
+template <int PT>
+__device__ __forceinline__ void skel_band_factor(int N, double* __restrict__ band, const double* __restrict__ diag0,
+                                                 int* numeric_err, double* __restrict__ Pn) {
+  constexpr int LDP = PT + 1, NTP = PT / 16, RT = 4 * NTP, NT2 = NTP * NTP, BB = PT * PT;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  for (int n = 0; n < N; ++n) {
+    skel_load_panel<PT>(Pn, band, n, N);
+    __syncthreads();
+#pragma unroll 1
+    for (int kb = 0; kb < NTP; ++kb) {
+      double* Tkk = Pn + (kb * 16) * LDP + kb * 16;
+      if (wave == 0) {
+        d4 acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = Tkk[(lk + 4 * r) * LDP + li];
+        chol16_inv_acc<LDP>(Tkk, acc, lane, numeric_err);
+      }
+      __syncthreads();
+      if (tid < 16) {                                          // pivot = 1 / U_pp^2 against the entry it was cancelled from
+        const double u = Tkk[tid * LDP + tid];
+        if (!(u * u * diag0[(size_t)n * PT + kb * 16 + tid] * SK_PIV_REL < 1.0)) atomicOr(numeric_err, 1);
+      }
+      for (int t = kb + 1 + wave; t < RT; t += SKC_W) {          // panel: tile(t, kb) <- tile(t, kb) U_kk
+        double* At = Pn + (t * 16) * LDP + kb * 16;
+        double av[4], bv[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          av[s] = At[li * LDP + 4 * s + lk];
+          bv[s] = Tkk[(4 * s + lk) * LDP + li];
+        }
+        d4 acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = mfma(av[s], bv[s], acc);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) At[(lk + 4 * rr) * LDP + li] = acc[rr];
+      }
+      __syncthreads();
+      int q = 0;                                             // trailing tiles inside the panel
+      for (int ct = kb + 1; ct < NTP; ++ct)
+        for (int rt = ct; rt < RT; ++rt, ++q) {
+          if (q % SKC_W != wave) continue;
+          double* Cc = Pn + (rt * 16) * LDP + ct * 16;
+          const double* Ar = Pn + (rt * 16) * LDP + kb * 16;
+          const double* Ac = Pn + (ct * 16) * LDP + kb * 16;
+          d4 a;
+          double av[4], bv[4];
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) a[rr] = Cc[(lk + 4 * rr) * LDP + li];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            av[s] = Ar[li * LDP + 4 * s + lk];
+            bv[s] = Ac[li * LDP + 4 * s + lk];
+          }
+#pragma unroll
+          for (int s = 0; s < 4; ++s) a = mfma(-av[s], bv[s], a);
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) Cc[(lk + 4 * rr) * LDP + li] = a[rr];
+        }
+      __syncthreads();
+    }
+    // ---- window update in memory: block (n + i, n + j) -= L_i L_j^T, stored at band[n + j][i - j]
+    for (int t = wave; t < 6 * NT2; t += SKC_W) {
+      const int blk = t / NT2, rem = t % NT2;
+      const int i = blk < 1 ? 1 : (blk < 3 ? 2 : 3), j = blk < 1 ? 1 : (blk < 3 ? blk : blk - 2);
+      const int rt = rem / NTP, ct = rem % NTP;
+      if (n + i >= N) continue;
+      double* Cg = band + ((size_t)(n + j) * 4 + (i - j)) * BB;
+      d4 a;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) a[rr] = Cg[(rt * 16 + lk + 4 * rr) * PT + ct * 16 + li];
+      const double* Ar = Pn + (i * PT + rt * 16 + li) * LDP;
+      const double* Ac = Pn + (j * PT + ct * 16 + li) * LDP;
+      a = sk_tile_mac(a, 0, PT, lk, [&](int k) { return -Ar[k]; }, [&](int k) { return Ac[k]; });
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) Cg[(rt * 16 + lk + 4 * rr) * PT + ct * 16 + li] = a[rr];
+    }
+    // ---- the factored panel replaces the frame's blocks (read again by whoever walks back)
+    for (int e = tid; e < 4 * BB; e += SKC_T) {
+      const int j = e / BB, rem = e % BB;
+      if (n + j < N || j == 0) band[((size_t)n * 4 + j) * BB + rem] = Pn[(j * PT + rem / PT) * LDP + rem % PT];
+    }
+    __syncthreads();
+  }
+}
+
+// ---- host: the workspace both entries use, and the launches up to the band --------------------------------------------
+struct SkelCovLayout {
+  size_t dev, clip, H, g, hd, cost, opv, band, diag0, fxm, total;
+};
+SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops);
+// Validates the link program into h (which must live until the caller's synchronisation), uploads it and the cameras, clears
+// the clips' status words and launches k_skel_cov_assemble[_pinhole] and k_skel_cov_build on stream s: on return the
+// workspace holds band, fxm, diag0 and the link operators opv of every frame at d_x.
+int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                          const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                          const double* d_lo, const double* d_hi, const double* d_x, void* d_ws, const SkelCovLayout& lay,
+                          SkelDev& h, hipStream_t s);
+
+}  // namespace acino

@@ -574,6 +574,33 @@ int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int c
                               double* d_cov_x, double* d_cov_pos, double* d_std_pos, int32_t* h_status /* [n_clips], may be NULL */,
                               void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- joint posterior samples of the generic-skeleton FTE trajectory ---------------------------------------------------------
+ * The other use of the same matrix: with A exactly the matrix of acino_skel_fte_covariance at d_x (Fisher blocks with w^2,
+ * 2 q D3^T D3, bound-active variables pinned, unknowns frame-major, no Marquardt term) and A = L L^T its banded Cholesky factor,
+ *   d_x_samples[b][s] = d_x[b] + delta,   delta = L_b^-T z[b][s],   z of a pinned variable counted as 0
+ * for the caller's d_z[n_clips][S][N][n_active] (S = n_samples).  For standard-normal z, Cov(delta) = A^-1 with every
+ * cross-frame block: the samples are joint draws of the whole trajectory from the Laplace posterior - what step length, mean
+ * speed over a stride or the range of a joint angle over a clip are computed from.  delta is exactly 0 at pinned variables
+ * whatever z holds there.  The map is deterministic - the library owns no random generator - and delta(s) depends on z(s)
+ * alone: the same bits whatever other samples or clips share the call.  Samples are NOT clipped to the box [d_lo, d_hi]: the
+ * Laplace posterior is a Gaussian, and only the pinned variables are held.  Outputs (fp64):
+ *   d_x_samples  [n_clips][S][N][n_active]
+ *   d_pos_samples[n_clips][S][N][n_pose][3]   may be NULL; the forward kinematics of every sample itself (the link program on
+ *                                             the sample's active states, every other state 0) - not the linearisation
+ * Argument conventions, limits (n_active <= 64, 2 n_pose C <= 256), workspace alignment, h_status, the return rules and the one
+ * stream synchronisation are those of acino_skel_fte_covariance: a singular clip (a pivot not above zero) gets h_status[b] = 5
+ * and NaN samples; with n_clips > 1 and h_status given the other clips stand and the call returns ACINO_OK, otherwise
+ * ACINO_ERR_NUMERIC.  n_samples < 1, a NULL d_z or d_x_samples, and d_z overlapping either output are ACINO_ERR_INVALID_ARG
+ * before any device call.  The factorisation is one workgroup per clip; the back-substitution runs on a grid of (panels of 64
+ * samples, clips). */
+size_t acino_skel_fte_sample_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int64_t n_samples);
+int acino_skel_fte_sample(const acino_skel_fte_params* p, int n_clips, int camera_model /* 0 fisheye: d_cams24, 1 pinhole: d_cams32 */,
+                          const acino_skel_op* h_ops, const int32_t* h_active, const double* d_meas, const double* d_w,
+                          const double* d_cams, const double* d_lo, const double* d_hi, const double* d_x, int64_t n_samples,
+                          const double* d_z /* [n_clips][S][N][n_active] */, double* d_x_samples /* [n_clips][S][N][n_active] */,
+                          double* d_pos_samples /* [n_clips][S][N][n_pose][3], may be NULL */,
+                          int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes, void* stream);
+
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
  * 75 = 3 x 25 [pose | velocity | acceleration], pose parameters in the order of qb_list (:734-746).  d_det is
