@@ -384,9 +384,127 @@ def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1
         out.append(o)
     return out
 
+REPROJ_KEYS = ("uv", "cov_uv", "std_uv", "res", "mahal2", "flags")
+
+
+def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1e-2):
+    """The skeleton solve seen in the images at the iterates ``xs`` (one [N, P] array per model, the layout of ``results["x"]``):
+    acino_skel_fte_reprojection, all models in ONE batched call of one streaming kernel.  Returns one dict per model, every
+    array indexed [N, C, n_pose] like ``model.meas`` / ``model.weights``:
+
+    ``uv`` [.., 2] the predicted pixel (NaN on a camera's singular plane); ``cov_uv`` [.., 2, 2] = J_pi cov_pos J_pi^T in px^2
+    and ``std_uv`` = sqrt(trace); ``res`` [.., 2] = uv - detection for every FINITE detection whatever its weight (NaN for a
+    missing one: the measurements go to the device raw); ``mahal2`` = res^T (cov_uv + (2 r^2) I)^-1 res with r = 1 / w for a
+    weighted detection and ``r_gate`` (px; default 1 / max(model.weights): the R of the weighted ones) for the others, so that
+    a low-likelihood detection can be asked whether it agrees with the trajectory all the same; ``flags`` (uint8) bit 0: the
+    solve weights this detection, bit 1: behind the camera, bit 2: singular plane.
+
+    The objective is plain L1 - every weighted detection pulls with the same force however wrong it is - so ``mahal2`` is the
+    one number that says which detections the trajectory contradicts.  2 r^2 is the variance of the stated Laplace noise:
+    a moment-matched gating distance, not an exact chi-square.
+
+    ``cov=True`` without ``cov_pos`` (one [N, n_pose, 3, 3] array per model, normally ``model_covariance``'s at the same x)
+    computes it first; a clip whose covariance is singular then gets NaN ``cov_uv`` / ``std_uv`` / ``mahal2`` and
+    ``cov_status`` 5 in its dict (else 0) - nothing is raised, ``uv`` / ``res`` / ``flags`` stand.  ``cov=False``: ``cov_uv`` and
+    ``std_uv`` are None and ``mahal2`` is res^T res / (2 r^2); no factorisation at all, so this also serves the shipped human
+    skeleton, whose covariance is singular by definition.  Batch checks and camera-model selection as ``model_covariance``."""
+    if len(models) == 0:
+        raise ValueError("no models")
+    cam_model = _batch_camera_model(models)
+    _batch_check(models)
+    m0 = models[0]
+    B, N, P = len(models), m0.N, m0.P
+    Cn, Lp = int(m0.meas.shape[1]), len(m0.names)
+    act = np.asarray(m0.active, dtype=np.int32)
+    if len(xs) != B:
+        raise ValueError(f"{len(xs)} iterates for {B} models")
+    xs = [np.asarray(xf, dtype=np.float64) for xf in xs]
+    for xf in xs:
+        if xf.shape != (N, P):
+            raise ValueError(f"every x must be [{N}, {P}] (the full-state layout of results['x'])")
+        if not np.isfinite(xf[:, act]).all():
+            raise ValueError("x must be finite")
+    if r_gate is None:
+        w_max = max(float(np.nanmax(np.asarray(m.weights), initial=0.0)) for m in models)
+        if not w_max > 0:
+            raise ValueError("no positive weight in the models: pass r_gate (px), the noise scale of an unweighted detection")
+        r_gate = 1.0 / w_max
+    r_gate = float(r_gate)
+    if not (r_gate > 0 and np.isfinite(r_gate)):
+        raise ValueError("r_gate must be positive and finite (px)")
+    if cov_pos is not None:
+        if not cov:
+            raise ValueError("cov_pos given with cov=False")
+        if len(cov_pos) != B:
+            raise ValueError(f"{len(cov_pos)} cov_pos arrays for {B} models")
+        cov_pos = [np.asarray(cp, dtype=np.float64) for cp in cov_pos]
+        for cp in cov_pos:
+            if cp.shape != (N, Lp, 3, 3):
+                raise ValueError(f"every cov_pos must be [{N}, {Lp}, 3, 3]")
+    cov_status = None
+    if cov and cov_pos is None:
+        covs = _covariance(models, xs, l1_eps, ("cov_pos",), raise_numeric=False)
+        cov_pos, cov_status = [cv["cov_pos"] for cv in covs], [cv["status"] for cv in covs]
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    p = _skel_params(m0, len(act), l1_eps=l1_eps)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)   # noqa: E731
+    meas = t(np.stack([m.meas for m in models]))                      # raw: a NaN detection gives a NaN residual
+    w = t(np.stack([m.weights for m in models]))
+    cams = torch.as_tensor(calib.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
+    x = t(np.stack([xf[:, act] for xf in xs]))
+    cp_d = t(np.stack(cov_pos)) if cov else None
+    empty = lambda *shape: torch.empty((B, N, Cn, Lp) + shape, dtype=torch.float64, device=dev)   # noqa: E731
+    uv, res, m2 = empty(2), empty(2), empty()
+    cuv = empty(2, 2) if cov else None
+    flags = torch.empty((B, N, Cn, Lp), dtype=torch.uint8, device=dev)
+    act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
+    check(lib().acino_skel_fte_reprojection(C.byref(p), B, 1 if cam_model == "pinhole" else 0, _ops_array(m0.prog), act_c, ptr(meas),
+                                            ptr(w), ptr(cams), ptr(x), ptr(cp_d), 1.0 / r_gate, ptr(uv), ptr(cuv), ptr(res), ptr(m2),
+                                            ptr(flags), stream_ptr()))
+    uv, res, m2, flags = uv.cpu().numpy(), res.cpu().numpy(), m2.cpu().numpy(), flags.cpu().numpy()
+    cuv = cuv.cpu().numpy() if cov else None
+    out = []
+    for i in range(B):
+        o = dict(uv=uv[i], cov_uv=None, std_uv=None, res=res[i], mahal2=m2[i], flags=flags[i])
+        if cov:
+            o["cov_uv"] = cuv[i]
+            o["std_uv"] = np.sqrt(np.maximum(cuv[i][..., 0, 0] + cuv[i][..., 1, 1], 0.0))
+        if cov_status is not None:
+            o["cov_status"] = cov_status[i]
+        out.append(o)
+    return out
+
+
+def detection_report(reproj, gate=None):
+    """Summary of one dict of ``model_reprojection`` (or of the ``uv`` ... ``flags`` entries of a solve's results) per (camera,
+    pose slot), as a dict of numpy arrays [C, n_pose]: ``n_weighted`` the detections the solve weighted (bit 0 of the flags),
+    ``mean_abs_res_px`` the mean of |res| over their components - the quantity the L1 objective sums, and what
+    ``window_residual_px`` averages per window - and ``max_abs_res_px`` (both NaN where nothing is weighted).  With ``gate`` - a
+    chi-square quantile with 2 degrees of freedom the caller picks, e.g. 9.21 - also the finite detections inside / outside
+    ``mahal2 <= gate``, split by bit 0: ``n_weighted_inside``, ``n_weighted_outside``, ``n_unweighted_inside`` (low-likelihood
+    detections that agree with the trajectory all the same) and ``n_unweighted_outside``, as ``fte.detection_report`` counts
+    them.  Host arithmetic on the arrays given; no kernel."""
+    res, flags = np.asarray(reproj["res"]), np.asarray(reproj["flags"])
+    weighted = (flags & 1) != 0
+    n_w = weighted.sum(axis=0)
+    ar = np.abs(np.where(weighted[..., None], res, 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(n_w > 0, ar.sum(axis=(0, -1)) / (2 * np.maximum(n_w, 1)), np.nan)
+    out = dict(n_weighted=n_w, mean_abs_res_px=mean, max_abs_res_px=np.where(n_w > 0, ar.max(axis=(0, -1), initial=0.0), np.nan))
+    if gate is not None:
+        m2 = np.asarray(reproj["mahal2"])
+        finite = np.isfinite(m2)
+        inside = finite & (np.where(finite, m2, np.inf) <= float(gate))
+        outside = finite & ~inside
+        out.update(n_weighted_inside=(inside & weighted).sum(axis=0), n_weighted_outside=(outside & weighted).sum(axis=0),
+                   n_unweighted_inside=(inside & ~weighted).sum(axis=0),
+                   n_unweighted_outside=(outside & ~weighted).sum(axis=0))
+    return out
+
 
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
-                 return_cov=False, n_samples=0, sample_seed=0):
+                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False):
     """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
@@ -395,7 +513,10 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     the assembly kernel; a batch that mixes the two is refused.  ``return_cov``: ``cov_x``, ``cov_pos`` and ``std_pos`` of
     ``model_covariance`` at the returned ``x`` are added to every ``results`` (one more batched call; a clip whose covariance
     is singular gets NaN arrays).  ``n_samples`` > 0: ``x_samples`` [S, N, P] and ``pos_samples`` [S, N, n_pose, 3] of
-    ``model_samples(models, xs, n_samples, seed=sample_seed)`` at the returned ``x`` join every ``results`` the same way."""
+    ``model_samples(models, xs, n_samples, seed=sample_seed)`` at the returned ``x`` join every ``results`` the same way.
+    ``return_reprojection``: ``uv``, ``cov_uv``, ``std_uv``, ``res``, ``mahal2`` and ``flags`` of ``model_reprojection`` at the
+    returned ``x`` join every ``results`` (one more batched call); with ``return_cov`` the covariance runs once and its ``cov_pos``
+    is passed on, without it the report runs with ``cov=False`` (``cov_uv`` and ``std_uv`` are None)."""
     cam_model = _batch_camera_model(models)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -445,18 +566,26 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
         draws = model_samples(models, [r["x"] for r, _i in out], n_samples=n_samples, seed=sample_seed, l1_eps=l1_eps)
         for (res, _info), dr in zip(out, draws):
             res.update(x_samples=dr["x_samples"], pos_samples=dr["pos_samples"])
+    if return_reprojection:
+        ws = None
+        reps = model_reprojection(models, [r["x"] for r, _i in out], cov=bool(return_cov),
+                                  cov_pos=[r["cov_pos"] for r, _i in out] if return_cov else None, l1_eps=l1_eps)
+        for (res, _info), rep in zip(out, reps):
+            res.update({k: rep[k] for k in REPROJ_KEYS})
     return out
 
 
 def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
-                return_cov=False, n_samples=0, sample_seed=0):
+                return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
     failure is the call's).  ``return_cov``: ``cov_x`` / ``cov_pos`` / ``std_pos`` at the returned ``x`` (``model_covariance``)
-    join ``results``; ``n_samples`` > 0: ``x_samples`` / ``pos_samples`` (``model_samples`` with ``seed=sample_seed``) do."""
+    join ``results``; ``n_samples`` > 0: ``x_samples`` / ``pos_samples`` (``model_samples`` with ``seed=sample_seed``) do;
+    ``return_reprojection``: the six arrays of ``model_reprojection`` do (``cov_uv`` / ``std_uv`` None without ``return_cov``)."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
-                        l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed)[0]
+                        l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed,
+                        return_reprojection=return_reprojection)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -542,7 +671,7 @@ def window_residual_px(model, info):
 
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
-                overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, **kw):
+                overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -573,10 +702,20 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     such windows are listed in ``results["cov_singular_windows"]`` and nothing is raised (``owner``: the window every frame was
     taken from; ``window_std_pos``: every window's own bars).
 
+    ``return_reprojection``: ONE ``model_reprojection`` call over the stitched trajectory - one clip of all the frames at
+    ``results["x"]``, the measurements and weights of every frame gathered from the window that owns it - adds ``uv``, ``cov_uv``,
+    ``std_uv``, ``res``, ``mahal2`` and ``flags`` [frames, C, n_pose, ...] to ``results``; with ``return_cov`` the stitched ``cov_pos``
+    is used (NaN bars of a singular window carry over), without it ``cov_uv`` and ``std_uv`` are None.  With ``gate`` (a chi-square
+    quantile with 2 degrees of freedom, e.g. 9.21; needs ``return_reprojection``) also ``outlier_frames``: the frames, relative to
+    first_frame, in which any weighted detection lies outside ``mahal2 <= gate``.  A per-frame report of a stitched trajectory is
+    sound where joint samples are not: every frame's pixels, residuals and bars are those of the window that supplied it.
+
     There is no ``n_samples`` here: a stitched video is not one posterior (every window has its own, and draws of neighbouring
     windows are independent); call ``model_samples`` on the windows' models."""
     if "n_samples" in kw or "sample_seed" in kw:
         raise TypeError("solve_video takes no n_samples: a stitched video is not one posterior (use model_samples per window)")
+    if gate is not None and not return_reprojection:
+        raise ValueError("gate needs return_reprojection=True")
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
     cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
     build_kw["camera_model"] = cam_model
@@ -680,6 +819,19 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
             infos[w_i]["cov_status"] = cv["status"]
         results.update(std_pos=std_pos, cov_pos=cov_pos, owner=owner.copy(), window_std_pos=[cv["std_pos"] for cv in covs],
                        cov_singular_windows=[i for i, cv in enumerate(covs) if cv["status"] == 5])
+    if return_reprojection:
+        local = np.arange(total) - (np.asarray(starts)[owner] - f0)          # every frame's row in its owner window
+        lo_t, hi_t = bounds_table(skel_dict, total)
+        whole = SkeletonModel(**{**models[0].__dict__, "meas": np.stack([models[w_i].meas[r] for w_i, r in zip(owner, local)]),
+                                 "weights": np.stack([models[w_i].weights[r] for w_i, r in zip(owner, local)]), "lo": lo_t,
+                                 "hi": hi_t, "init_x": x.copy(), "start_frame": f0, "x": None, "info": None})
+        rep = model_reprojection([whole], [x], cov=bool(return_cov), cov_pos=[results["cov_pos"]] if return_cov else None,
+                                 l1_eps=kw.get("l1_eps", 1e-2))[0]
+        results.update({k: rep[k] for k in REPROJ_KEYS})
+        if gate is not None:
+            finite = np.isfinite(rep["mahal2"])
+            out_w = finite & (np.where(finite, rep["mahal2"], 0.0) > float(gate)) & ((rep["flags"] & 1) != 0)
+            results["outlier_frames"] = [int(n) for n in np.nonzero(out_w.any(axis=(1, 2)))[0]]
     return results, infos, starts
 
 
@@ -703,8 +855,9 @@ def save_data(file_data, file_path, poses=None, dict=True):
 def solve_optimisation(model, exe_path=None, project_dir=None, poses=None, **solver_kw):
     """build.py:306-335: solve, then save ``data/results/traj_results.pickle`` under ``project_dir`` (when given).
     ``exe_path`` named the IPOPT executable; there is none here.  ``return_cov=True`` (a ``solve_model`` keyword) adds the
-    covariance arrays to the returned ``results``, ``n_samples=S`` (with ``sample_seed``) the posterior samples; the saved pickle
-    keeps the reference's four entries."""
+    covariance arrays to the returned ``results``, ``n_samples=S`` (with ``sample_seed``) the posterior samples,
+    ``return_reprojection=True`` the image-space report of ``model_reprojection``; the saved pickle keeps the reference's four
+    entries."""
     results, info = solve_model(model, **solver_kw)
     model.x, model.info = results, info
     if project_dir is not None:

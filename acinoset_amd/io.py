@@ -153,7 +153,9 @@ def reprojection_to_points_2d_df(uv, flags, start_frame=0, markers=None, likelih
     create_dlc_points_2d_file, rows ordered by camera, frame, marker (in the order of ``markers``): predictions can be fed to everything that eats
     detections (dense_detections reads the table back to the same array, likelihood 0 where a row was left out).  Rows
     whose pixel is NaN (singular plane) or behind the camera (bit 1 of the flags) are left out.  ``markers``: the L names
-    (default: the cheetah's 20); ``likelihood``: a scalar or an array [N,C,L] (default 1.0)."""
+    (default: the cheetah's 20); ``likelihood``: a scalar or an array [N,C,L] (default 1.0).  A skeleton report
+    (build.model_reprojection, or a skeleton solve with return_reprojection=True) is indexed by pose slot: pass
+    ``markers=model.names``."""
     import pandas as pd
     uv = np.asarray(uv.detach().cpu().numpy() if hasattr(uv, "detach") else uv, dtype=np.float64)
     flags = np.asarray(flags.detach().cpu().numpy() if hasattr(flags, "detach") else flags)

@@ -601,6 +601,44 @@ int acino_skel_fte_sample(const acino_skel_fte_params* p, int n_clips, int camer
                           double* d_pos_samples /* [n_clips][S][N][n_pose][3], may be NULL */,
                           int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- a generic-skeleton FTE iterate in image space: predicted pixels, their covariance, residuals, gating ----------------
+ * Evaluated at the iterate d_x[n_clips][N][n_active] (normally the solution of acino_skel_fte_solve*).  Per entry
+ * (b, n, c, l) = (clip, frame, camera, pose slot), the layout of d_meas[n_clips][N][C][n_pose][2] / d_w[n_clips][N][C][n_pose]:
+ *   pose = FK_l(x[b][n])        the link program on the active states, every other state 0
+ *   (uv, J_pi, z_cam)           the projection of camera c (camera_model 0: fisheye records d_cams[C][24], pt3d_to_2d's
+ *                               arithmetic; 1: pinhole records d_cams[C][32], cv2.projectPoints) and its 2 x 3 Jacobian with
+ *                               respect to the world point
+ *   z, w                        the entries of d_meas and d_w; finite: both components of z finite; sing: |z_cam| < 1e-9;
+ *                               wg = (w > 0 ? w : gate_w)
+ * Outputs (any may be NULL, but not all of them):
+ *   d_uv    [..][2]     the predicted pixel; NaN on the singular plane
+ *   d_cov_uv[..][2][2]  J_pi sym(cov_pos[b][n][l]) J_pi^T in px^2, cov_pos = d_cov_pos[n_clips][N][n_pose][3][3] (normally that
+ *                       of acino_skel_fte_covariance at the same d_x); both off-diagonal entries carry the same bits; NaN where uv
+ *                       is NaN; a NaN cov_pos (a singular clip) propagates.  Asking for it with d_cov_pos == NULL is
+ *                       ACINO_ERR_INVALID_ARG
+ *   d_res   [..][2]     uv - z for every finite detection WHATEVER its weight; NaN otherwise and where uv is NaN
+ *   d_mahal2[..]        res^T (cov_uv + (2 / wg^2) I)^-1 res; with d_cov_pos == NULL: res^T res wg^2 / 2; NaN where res is NaN.
+ *                       The stated noise model is Laplace of scale 1 / w per component, variance 2 / w^2: this is a
+ *                       MOMENT-MATCHED gating distance under the posterior predictive, NOT an exact chi-square - the noise is
+ *                       not Gaussian, so a chi-square quantile with 2 degrees of freedom is a convention for the gate, not a
+ *                       coverage statement.  gate_w (> 0, finite) is the scale used for detections the caller gave no positive
+ *                       weight (low likelihood): whether they agree with the trajectory all the same can then be asked
+ *   d_flags [..]  (u8)  bit 0: the assembly weights this row (w != 0, finite, not singular: the solve's own rule);
+ *                       bit 1: z_cam < 1e-6 (behind the camera); bit 2: the singular plane
+ * The L1 objective pulls every weighted detection with the same force w however wrong it is - outliers are not discounted - and
+ * nothing else in a skeleton solve's results says which detections they are.  No factorisation is involved: the call also serves
+ * a skeleton whose covariance is singular (uv / res / flags; NaN cov_uv and mahal2 where the caller's cov_pos is NaN).
+ * h_ops / h_active / d_meas / d_w / d_cams as the solve (d_meas RAW: a NaN detection gives a NaN residual); limits as the solve.
+ * Every argument is validated before any device call (the params block, the link program and the active states as the solve
+ * checks them; n_clips >= 1; camera_model 0 or 1; gate_w; NULL inputs; all outputs NULL).  ONE streaming kernel on `stream`:
+ * the problem description travels as a kernel argument, so the call takes no workspace, allocates nothing, copies nothing and
+ * does not synchronise; the device arrays must stay valid until the stream reaches it. */
+int acino_skel_fte_reprojection(const acino_skel_fte_params* p, int n_clips, int camera_model /* 0 fisheye: d_cams24, 1 pinhole: d_cams32 */,
+                                const acino_skel_op* h_ops, const int32_t* h_active, const double* d_meas, const double* d_w,
+                                const double* d_cams, const double* d_x,
+                                const double* d_cov_pos /* [n_clips][N][n_pose][3][3] or NULL */, double gate_w, double* d_uv,
+                                double* d_cov_uv, double* d_res, double* d_mahal2, uint8_t* d_flags, void* stream);
+
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
  * 75 = 3 x 25 [pose | velocity | acceleration], pose parameters in the order of qb_list (:734-746).  d_det is
