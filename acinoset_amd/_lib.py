@@ -204,6 +204,15 @@ SIGNATURES = {
     "acino_skel_fte_sample_workspace_bytes": (_Z, [C.POINTER(SkelFteParams), _I, _L]),
     "acino_skel_fte_sample": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P, _P,
                                    _P, _L, _P, _P, _P, C.POINTER(C.c_int32), _P, _Z, _P]),
+    "acino_skel_fte_observability_workspace_bytes": (_Z, [C.POINTER(SkelFteParams), _I]),
+    "acino_skel_fte_observability": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P,
+                                          _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "acino_skel_fte_covariance_pinned_workspace_bytes": (_Z, [C.POINTER(SkelFteParams), _I, _I]),
+    "acino_skel_fte_covariance_pinned": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P,
+                                              _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P, _Z, _P, _I, _P]),
+    "acino_skel_fte_sample_pinned_workspace_bytes": (_Z, [C.POINTER(SkelFteParams), _I, _L, _I]),
+    "acino_skel_fte_sample_pinned": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P,
+                                          _P, _P, _L, _P, _P, _P, C.POINTER(C.c_int32), _P, _Z, _P, _I, _P]),
     "acino_skel_fte_reprojection": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P,
                                          _P, _D, _P, _P, _P, _P, _P, _P]),
     "acino_selftest_mfma": (_I, [_P, _P, _I, _P, _P]),

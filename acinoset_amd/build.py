@@ -290,10 +290,20 @@ def _posterior_inputs(models, xs, l1_eps, workspace_bytes):
     return dict(xs=xs, act=act, dev=dev, head=head, tail=(C.c_void_p(ws_ptr), nbytes, stream_ptr()), keep=keep)
 
 
-def _covariance(models, xs, l1_eps, want, raise_numeric=True):
+def _unobserved_lists(mask, act):
+    """Per clip, the sorted full-state indices of the states a [B, n_active] device mask marks."""
+    mh = mask.cpu().numpy()
+    return [[int(a) for a in np.asarray(act)[np.nonzero(row)[0]]] for row in mh]
+
+
+def _covariance(models, xs, l1_eps, want, raise_numeric=True, pin_unobserved=False):
     """model_covariance with the outputs chosen by name (``want``: a subset of cov_x, cov_pos, std_pos).  ``raise_numeric=False``:
-    a singular single clip is reported in its ``status`` like a clip of a batch."""
-    io_ = _posterior_inputs(models, xs, l1_eps, lambda p, B: lib().acino_skel_fte_covariance_workspace_bytes(C.byref(p), B))
+    a singular single clip is reported in its ``status`` like a clip of a batch.  ``pin_unobserved``: the _pinned entry, and
+    ``unobserved`` in every dict."""
+    pin = bool(pin_unobserved)
+    io_ = _posterior_inputs(models, xs, l1_eps,
+                            (lambda p, B: lib().acino_skel_fte_covariance_pinned_workspace_bytes(C.byref(p), B, 1)) if pin else
+                            (lambda p, B: lib().acino_skel_fte_covariance_workspace_bytes(C.byref(p), B)))
     m0, act, dev = models[0], io_["act"], io_["dev"]
     B, N, P = len(models), m0.N, m0.P
     Pa, Lp = len(act), len(m0.names)
@@ -302,10 +312,18 @@ def _covariance(models, xs, l1_eps, want, raise_numeric=True):
     cov_pos = empty(B, N, Lp, 3, 3) if "cov_pos" in want else None
     std_pos = empty(B, N, Lp) if "std_pos" in want else None
     status = (C.c_int32 * B)()
-    rc = lib().acino_skel_fte_covariance(*io_["head"], ptr(cov_x), ptr(cov_pos), ptr(std_pos), status, *io_["tail"])
+    if pin:
+        mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev)
+        rc = lib().acino_skel_fte_covariance_pinned(*io_["head"], ptr(cov_x), ptr(cov_pos), ptr(std_pos), status, *io_["tail"], 1,
+                                                    ptr(mask))
+    else:
+        rc = lib().acino_skel_fte_covariance(*io_["head"], ptr(cov_x), ptr(cov_pos), ptr(std_pos), status, *io_["tail"])
     if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
         check(rc)
     out = [dict(status=int(status[i])) for i in range(B)]
+    if pin:
+        for o, un in zip(out, _unobserved_lists(mask, act)):
+            o["unobserved"] = un
     if cov_x is not None:
         ch = cov_x.cpu().numpy()
         for i in range(B):
@@ -321,7 +339,34 @@ def _covariance(models, xs, l1_eps, want, raise_numeric=True):
     return out
 
 
-def model_covariance(models, xs, std_only=False, l1_eps=1e-2):
+def model_observability(models, xs, l1_eps=1e-2):
+    """Which active states the detections of each clip say anything about, at the iterates ``xs`` (one [N, P] array per model):
+    acino_skel_fte_observability - the Fisher assembly of ``model_covariance`` and one small reduction, no factorisation.  Returns
+    one dict per model: ``info`` [P], the Fisher information sum_n H_F[n][p][p] of every state over the clip's frames (the prior
+    is not in it), ``n_seen`` [P], the number of frames whose own term is above 1e-24 of the clip's largest ``info`` - both in the
+    full-state layout, 0 outside ``model.active`` - and ``unobserved``, the sorted full-state indices of the ACTIVE states with
+    ``info`` <= 1e-24 of the largest: no frame of the clip moves a weighted pixel with them.  The shipped human skeleton has two
+    on every clip (the psi angles of "chin" and "hip2"); a limb no camera detects in the clip adds its joints.  Any such state
+    makes the clip's covariance singular (status 5) unless ``pin_unobserved=True``.  A clip that is singular with an empty
+    ``unobserved`` has a state with ``n_seen`` < 3: the prior's quadratic drift needs three informative frames, and such states are
+    not pinned."""
+    io_ = _posterior_inputs(models, xs, l1_eps, lambda p, B: lib().acino_skel_fte_observability_workspace_bytes(C.byref(p), B))
+    m0, act, dev = models[0], io_["act"], io_["dev"]
+    B, P, Pa = len(models), m0.P, len(io_["act"])
+    info = torch.empty((B, Pa), dtype=torch.float64, device=dev)
+    seen = torch.empty((B, Pa), dtype=torch.int32, device=dev)
+    mask = torch.empty((B, Pa), dtype=torch.uint8, device=dev)
+    check(lib().acino_skel_fte_observability(*io_["head"], ptr(info), ptr(seen), ptr(mask), *io_["tail"]))
+    ih, sh = info.cpu().numpy(), seen.cpu().numpy()
+    out = []
+    for i, un in enumerate(_unobserved_lists(mask, act)):
+        fi, fs = np.zeros(P), np.zeros(P, dtype=np.int32)
+        fi[act], fs[act] = ih[i], sh[i]
+        out.append(dict(info=fi, n_seen=fs, unobserved=un))
+    return out
+
+
+def model_covariance(models, xs, std_only=False, l1_eps=1e-2, pin_unobserved=False):
     """Error bars of the skeleton solve at the iterates ``xs`` (one [N, P] array per model, the layout of ``results["x"]``;
     normally the solutions): acino_skel_fte_covariance, all models in one batched call (one workgroup per clip).  Returns one
     dict per model: ``cov_x`` [N, P, P] - the frame's diagonal block of A^-1 in the full-state layout, zero rows and columns
@@ -333,11 +378,21 @@ def model_covariance(models, xs, std_only=False, l1_eps=1e-2):
     L1 objective is the likelihood of Laplace noise of scale 1 / w), whatever its residual - neither the solver's IRLS curvature
     nor ``l1_eps`` enter the matrix, and outliers above the likelihood threshold are not discounted.  Variables the solver would
     hold at a bound at ``x`` are pinned (zero rows and columns; ``l1_eps`` only enters this rule, through the solver's diagonal).
-    The same batch checks and camera-model selection as ``solve_models``."""
-    return _covariance(models, xs, l1_eps, ("std_pos",) if std_only else ("cov_x", "cov_pos", "std_pos"))
+    The same batch checks and camera-model selection as ``solve_models``.
+
+    ``pin_unobserved=True`` (acino_skel_fte_covariance_pinned): the states of ``model_observability``'s ``unobserved`` are pinned
+    in every frame of their clip, like bound pins and in addition to them - what the shipped human skeleton needs to get bars at
+    all.  Every dict then carries ``unobserved`` (sorted full-state indices): ``cov_x`` has zero rows and columns there, and the
+    list says which zeros mean "undetermined".  A pose slot whose position depends on such a state (a nonzero entry of its
+    Jacobian in that column - the hand of an arm no camera detected) has ``std_pos`` = +inf and NaN ``cov_pos``; every other slot
+    is G cov_x G^T as before; on the shipped skeleton no pose depends on the two psi states and every bar is finite.  The
+    factorisation still decides: a state seen in one or two frames is not pinned and the clip stays status 5
+    (``model_observability``'s ``n_seen`` says which).  The default keeps the definition above unchanged."""
+    return _covariance(models, xs, l1_eps, ("std_pos",) if std_only else ("cov_x", "cov_pos", "std_pos"),
+                       pin_unobserved=pin_unobserved)
 
 
-def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1_eps=1e-2):
+def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1_eps=1e-2, pin_unobserved=False):
     """Joint draws of the whole trajectory from the Laplace posterior of the skeleton solve at the iterates ``xs`` (one [N, P]
     array per model, the layout of ``results["x"]``): acino_skel_fte_sample, all models in ONE batched call.  With A the matrix
     of ``model_covariance`` (Fisher blocks, smoothness prior, bound-active variables pinned) and A = L L^T,
@@ -349,7 +404,12 @@ def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1
     keep ``x``'s values; pinned variables equal ``x`` exactly), ``pos_samples`` [S, N, n_pose, 3] - the forward kinematics of
     every sample, not a linearisation - unless ``positions=False``, and ``status`` (0, or 5: singular, NaN samples; for ONE
     model that is a RuntimeError, as in ``model_covariance``).  Samples are NOT clipped to the limits: the Laplace posterior is
-    a Gaussian and only the pinned variables are held (``np.clip`` to ``model.lo`` / ``model.hi`` if the box matters)."""
+    a Gaussian and only the pinned variables are held (``np.clip`` to ``model.lo`` / ``model.hi`` if the box matters).
+
+    ``pin_unobserved=True`` (acino_skel_fte_sample_pinned): the clip's unobserved states (``model_observability``) are pinned in
+    every frame as in ``model_covariance``; the samples equal ``x`` exactly there whatever z holds, and every dict carries
+    ``unobserved``.  ``pos_samples`` of a pose that depends on an unobserved state show NO spread from that state, because it is
+    held at ``x`` - where ``model_covariance`` reports std_pos = +inf; the caller finds out through ``unobserved``."""
     B = len(models)
     n_act = len(models[0].active) if B else 0
     N = models[0].N if B else 0
@@ -365,13 +425,21 @@ def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1
     if not np.isfinite(z).all():
         raise ValueError("z must be finite")
     S = z.shape[1]
-    io_ = _posterior_inputs(models, xs, l1_eps, lambda p, nb: lib().acino_skel_fte_sample_workspace_bytes(C.byref(p), nb, S))
+    pin = bool(pin_unobserved)
+    io_ = _posterior_inputs(models, xs, l1_eps,
+                            (lambda p, nb: lib().acino_skel_fte_sample_pinned_workspace_bytes(C.byref(p), nb, S, 1)) if pin else
+                            (lambda p, nb: lib().acino_skel_fte_sample_workspace_bytes(C.byref(p), nb, S)))
     m0, act, dev = models[0], io_["act"], io_["dev"]
     zd = torch.as_tensor(z, device=dev)
     xs_d = torch.empty((B, S, N, n_act), dtype=torch.float64, device=dev)
     pos_d = torch.empty((B, S, N, len(m0.names), 3), dtype=torch.float64, device=dev) if positions else None
     status = (C.c_int32 * B)()
-    check(lib().acino_skel_fte_sample(*io_["head"], S, ptr(zd), ptr(xs_d), ptr(pos_d), status, *io_["tail"]))
+    if pin:
+        mask = torch.zeros((B, n_act), dtype=torch.uint8, device=dev)
+        check(lib().acino_skel_fte_sample_pinned(*io_["head"], S, ptr(zd), ptr(xs_d), ptr(pos_d), status, *io_["tail"], 1, ptr(mask)))
+        unobs = _unobserved_lists(mask, act)
+    else:
+        check(lib().acino_skel_fte_sample(*io_["head"], S, ptr(zd), ptr(xs_d), ptr(pos_d), status, *io_["tail"]))
     xh = xs_d.cpu().numpy()
     ph = pos_d.cpu().numpy() if positions else None
     out = []
@@ -381,13 +449,15 @@ def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1
         o = dict(x_samples=full, status=int(status[i]))
         if positions:
             o["pos_samples"] = ph[i]
+        if pin:
+            o["unobserved"] = unobs[i]
         out.append(o)
     return out
 
 REPROJ_KEYS = ("uv", "cov_uv", "std_uv", "res", "mahal2", "flags")
 
 
-def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1e-2):
+def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1e-2, pin_unobserved=False):
     """The skeleton solve seen in the images at the iterates ``xs`` (one [N, P] array per model, the layout of ``results["x"]``):
     acino_skel_fte_reprojection, all models in ONE batched call of one streaming kernel.  Returns one dict per model, every
     array indexed [N, C, n_pose] like ``model.meas`` / ``model.weights``:
@@ -407,7 +477,11 @@ def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1
     computes it first; a clip whose covariance is singular then gets NaN ``cov_uv`` / ``std_uv`` / ``mahal2`` and
     ``cov_status`` 5 in its dict (else 0) - nothing is raised, ``uv`` / ``res`` / ``flags`` stand.  ``cov=False``: ``cov_uv`` and
     ``std_uv`` are None and ``mahal2`` is res^T res / (2 r^2); no factorisation at all, so this also serves the shipped human
-    skeleton, whose covariance is singular by definition.  Batch checks and camera-model selection as ``model_covariance``."""
+    skeleton, whose covariance is singular by definition.  Batch checks and camera-model selection as ``model_covariance``.
+
+    ``pin_unobserved=True`` reaches the covariance this call computes itself (``cov=True`` without ``cov_pos``): the shipped
+    skeleton then gets ``cov_status`` 0 and finite ``cov_uv`` / ``mahal2``; a pose slot that depends on an unobserved state has NaN
+    ``cov_pos`` and therefore NaN ``cov_uv`` / ``std_uv`` / ``mahal2``, and the dict carries ``unobserved`` beside ``cov_status``."""
     if len(models) == 0:
         raise ValueError("no models")
     cam_model = _batch_camera_model(models)
@@ -441,10 +515,12 @@ def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1
         for cp in cov_pos:
             if cp.shape != (N, Lp, 3, 3):
                 raise ValueError(f"every cov_pos must be [{N}, {Lp}, 3, 3]")
-    cov_status = None
+    cov_status = cov_unobs = None
     if cov and cov_pos is None:
-        covs = _covariance(models, xs, l1_eps, ("cov_pos",), raise_numeric=False)
+        covs = _covariance(models, xs, l1_eps, ("cov_pos",), raise_numeric=False, pin_unobserved=pin_unobserved)
         cov_pos, cov_status = [cv["cov_pos"] for cv in covs], [cv["status"] for cv in covs]
+        if pin_unobserved:
+            cov_unobs = [cv["unobserved"] for cv in covs]
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     p = _skel_params(m0, len(act), l1_eps=l1_eps)
@@ -472,6 +548,8 @@ def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1
             o["std_uv"] = np.sqrt(np.maximum(cuv[i][..., 0, 0] + cuv[i][..., 1, 1], 0.0))
         if cov_status is not None:
             o["cov_status"] = cov_status[i]
+        if cov_unobs is not None:
+            o["unobserved"] = cov_unobs[i]
         out.append(o)
     return out
 
@@ -504,7 +582,7 @@ def detection_report(reproj, gate=None):
 
 
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
-                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False):
+                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False):
     """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
@@ -516,7 +594,10 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     ``model_samples(models, xs, n_samples, seed=sample_seed)`` at the returned ``x`` join every ``results`` the same way.
     ``return_reprojection``: ``uv``, ``cov_uv``, ``std_uv``, ``res``, ``mahal2`` and ``flags`` of ``model_reprojection`` at the
     returned ``x`` join every ``results`` (one more batched call); with ``return_cov`` the covariance runs once and its ``cov_pos``
-    is passed on, without it the report runs with ``cov=False`` (``cov_uv`` and ``std_uv`` are None)."""
+    is passed on, without it the report runs with ``cov=False`` (``cov_uv`` and ``std_uv`` are None).
+    ``pin_unobserved``: passed to ``model_covariance`` / ``model_samples`` (it acts only together with ``return_cov`` or
+    ``n_samples``, and through ``return_cov`` on the report; the solve itself never changes); ``results`` then carries
+    ``unobserved``.  ``pos_samples`` of a pose that depends on an unobserved state show no spread from it."""
     cam_model = _batch_camera_model(models)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -558,14 +639,19 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
         out.append((dict(positions=ph[i], x=xf, dx=dx, ddx=ddx), infos[i].as_dict()))
     if return_cov:
         del ws
-        covs = _covariance(models, [r["x"] for r, _i in out], l1_eps, ("cov_x", "cov_pos", "std_pos"))
+        covs = _covariance(models, [r["x"] for r, _i in out], l1_eps, ("cov_x", "cov_pos", "std_pos"), pin_unobserved=pin_unobserved)
         for (res, _info), cv in zip(out, covs):
             res.update(cov_x=cv["cov_x"], cov_pos=cv["cov_pos"], std_pos=cv["std_pos"])
+            if pin_unobserved:
+                res["unobserved"] = cv["unobserved"]
     if n_samples:
         ws = None
-        draws = model_samples(models, [r["x"] for r, _i in out], n_samples=n_samples, seed=sample_seed, l1_eps=l1_eps)
+        draws = model_samples(models, [r["x"] for r, _i in out], n_samples=n_samples, seed=sample_seed, l1_eps=l1_eps,
+                              pin_unobserved=pin_unobserved)
         for (res, _info), dr in zip(out, draws):
             res.update(x_samples=dr["x_samples"], pos_samples=dr["pos_samples"])
+            if pin_unobserved:
+                res["unobserved"] = dr["unobserved"]
     if return_reprojection:
         ws = None
         reps = model_reprojection(models, [r["x"] for r, _i in out], cov=bool(return_cov),
@@ -576,16 +662,17 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
 
 
 def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
-                return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False):
+                return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
     failure is the call's).  ``return_cov``: ``cov_x`` / ``cov_pos`` / ``std_pos`` at the returned ``x`` (``model_covariance``)
     join ``results``; ``n_samples`` > 0: ``x_samples`` / ``pos_samples`` (``model_samples`` with ``seed=sample_seed``) do;
-    ``return_reprojection``: the six arrays of ``model_reprojection`` do (``cov_uv`` / ``std_uv`` None without ``return_cov``)."""
+    ``return_reprojection``: the six arrays of ``model_reprojection`` do (``cov_uv`` / ``std_uv`` None without ``return_cov``).
+    ``pin_unobserved``: as ``solve_models`` (only together with ``return_cov`` or ``n_samples``; ``results["unobserved"]``)."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
                         l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed,
-                        return_reprojection=return_reprojection)[0]
+                        return_reprojection=return_reprojection, pin_unobserved=pin_unobserved)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -671,7 +758,8 @@ def window_residual_px(model, info):
 
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
-                overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, **kw):
+                overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, pin_unobserved=False,
+                **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -700,7 +788,11 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     grow towards the window's ends - which is why the stitch takes each frame from the window in which it is most interior.  A
     window whose covariance is singular (``cov_status`` 5: a state observed in none of its frames) gives NaN bars for its frames;
     such windows are listed in ``results["cov_singular_windows"]`` and nothing is raised (``owner``: the window every frame was
-    taken from; ``window_std_pos``: every window's own bars).
+    taken from; ``window_std_pos``: every window's own bars).  ``pin_unobserved=True`` (acts only with ``return_cov``): every
+    window's unobserved states (``model_observability``) are pinned, ``results["cov_unobserved"]`` lists them per window
+    (full-state indices; [33, 43] for the shipped human skeleton) and ``cov_singular_windows`` keeps its meaning - the windows
+    that are singular all the same, e.g. a limb seen in one or two frames only.  Bars of a pose that depends on an unobserved
+    state are +inf.
 
     ``return_reprojection``: ONE ``model_reprojection`` call over the stitched trajectory - one clip of all the frames at
     ``results["x"]``, the measurements and weights of every frame gathered from the window that owns it - adds ``uv``, ``cov_uv``,
@@ -811,7 +903,7 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     results = dict(positions=pos, x=x, dx=dx, ddx=ddx, start_frame=f0, seams=seams)
     if return_cov:
         covs = _covariance(models, [res["x"] for res, _info in solved], kw.get("l1_eps", 1e-2), ("cov_pos", "std_pos"),
-                           raise_numeric=False)
+                           raise_numeric=False, pin_unobserved=pin_unobserved)
         std_pos, cov_pos = np.full((total, Lp), np.nan), np.full((total, Lp, 3, 3), np.nan)
         for w_i, (st, cv) in enumerate(zip(starts, covs)):
             mine = np.nonzero(owner == w_i)[0]
@@ -819,6 +911,8 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
             infos[w_i]["cov_status"] = cv["status"]
         results.update(std_pos=std_pos, cov_pos=cov_pos, owner=owner.copy(), window_std_pos=[cv["std_pos"] for cv in covs],
                        cov_singular_windows=[i for i, cv in enumerate(covs) if cv["status"] == 5])
+        if pin_unobserved:
+            results["cov_unobserved"] = [cv["unobserved"] for cv in covs]
     if return_reprojection:
         local = np.arange(total) - (np.asarray(starts)[owner] - f0)          # every frame's row in its owner window
         lo_t, hi_t = bounds_table(skel_dict, total)
@@ -856,8 +950,8 @@ def solve_optimisation(model, exe_path=None, project_dir=None, poses=None, **sol
     """build.py:306-335: solve, then save ``data/results/traj_results.pickle`` under ``project_dir`` (when given).
     ``exe_path`` named the IPOPT executable; there is none here.  ``return_cov=True`` (a ``solve_model`` keyword) adds the
     covariance arrays to the returned ``results``, ``n_samples=S`` (with ``sample_seed``) the posterior samples,
-    ``return_reprojection=True`` the image-space report of ``model_reprojection``; the saved pickle keeps the reference's four
-    entries."""
+    ``return_reprojection=True`` the image-space report of ``model_reprojection``, ``pin_unobserved=True`` pins the unobserved
+    states in those (``results["unobserved"]``); the saved pickle keeps the reference's four entries."""
     results, info = solve_model(model, **solver_kw)
     model.x, model.info = results, info
     if project_dir is not None:

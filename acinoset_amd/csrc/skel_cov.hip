@@ -29,6 +29,21 @@
 //                                  by this workgroup one to three frames earlier (L2 hits).
 //   k_skel_cov_out, k_skel_cov_pose  one workgroup per frame, streaming: cov_x from S_nn; G_l (3 x P) from the link operators,
 //                                  G_l cov_x G_l^T and sqrt(trace)
+//   k_skel_observability           (only when the caller asks: acino_skel_fte_observability, or pin_unobserved / d_unobserved of
+//                                  the _pinned entries)  one workgroup of one wave per clip, lane p = state p: info[p] = the
+//                                  sum over the clip's frames, in frame order, of the diagonal entry (p, p) of the Fisher block;
+//                                  the maximum over the states in LDS; a second walk over the same diagonals counts the frames
+//                                  above SK_UNOBS_REL * max.  No atomics.  A small reduction, latency-bound (N dependent adds
+//                                  per lane on strided loads).  The assembly body adds the prior's diagonal 2 q b0 to H in the
+//                                  same statement as the Fisher sum, and (s + c) - c does not give s back, so the diagonals
+//                                  this kernel reads come from a run of k_skel_cov_assemble on a second SkelDev with q = 0:
+//                                  there H IS the Fisher block, bit for bit (s + 2 * 0 * b0).  That run's H, g, hd, opv are
+//                                  overwritten by the real assembly that follows on the same stream.
+//                                  An unobserved state - info[p] <= SK_UNOBS_REL * max_q info[q]: no frame of the clip moves any
+//                                  weighted pixel with it - can be pinned in every frame of the clip (k_skel_cov_build's mask):
+//                                  row and column 0, diagonal 1, the prior's couplings dropped, exactly a bound pin.  A pose slot
+//                                  whose G_l has a nonzero entry in the column of an unobserved state is undetermined under the
+//                                  stated model: std_pos = +inf, cov_pos = NaN (k_skel_cov_pose).
 // A pivot p of the factorisation that is not above SK_PIV_REL * A_pp - non-positive, or positive only by the rounding of the
 // cancellation A_pp - sum L^2 - marks the clip singular (a state observed in no frame of the clip: the prior alone leaves its
 // quadratic drift free): status 5, outputs NaN.  One clip is latency-bound by construction, as the solve; the call is meant
@@ -70,13 +85,57 @@ k_skel_cov_assemble_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __r
 }
 #undef ACINO_SKEL_FISHER
 
+// ---- the host half of a SkelDev (everything before the camera records, 2.9 KB) by value in the kernel-argument segment:
+//      a call that does not synchronise (acino_skel_fte_observability) cannot leave an asynchronous copy reading its stack
+struct SkelDevHead {
+  unsigned long long w[offsetof(SkelDev, cams) / 8];
+};
+static_assert(offsetof(SkelDev, cams) % 8 == 0 && sizeof(SkelDevHead) == offsetof(SkelDev, cams) && sizeof(SkelDevHead) <= 3584,
+              "SkelDev's host half as a kernel argument");
+__global__ void __launch_bounds__(256) k_skel_dev_store(SkelDevHead a, SkelDev* __restrict__ out) {
+  unsigned long long* o = reinterpret_cast<unsigned long long*>(out);
+  for (int e = threadIdx.x; e < (int)(sizeof(SkelDevHead) / 8); e += 256) o[e] = a.w[e];
+}
+
+// ---- which states does the clip observe?  One wave per clip, lane p = active state p.  H: the Fisher blocks [NT][P][P] of an
+//      assembly with q = 0 (only their diagonals are read).  info / n_seen / unobs_a / unobs_b: [n_clips][P], any may be NULL
+__global__ void __launch_bounds__(64)
+k_skel_observability(const SkelDev* __restrict__ dev, const double* __restrict__ H, double* __restrict__ info,
+                     int32_t* __restrict__ n_seen, unsigned char* __restrict__ unobs_a, unsigned char* __restrict__ unobs_b) {
+  const SkelDev& D = *dev;
+  const int b = blockIdx.x, p = threadIdx.x, P = D.n_act, N = D.n_frames;
+  __shared__ double mx[64];
+  const size_t step = (size_t)P * P;
+  const double* Hd = H + (size_t)b * N * step + (size_t)(p < P ? p : 0) * (P + 1);      // entry (p, p) of the clip's first frame
+  double s = 0.0;
+  if (p < P)
+    for (int n = 0; n < N; ++n) s += Hd[(size_t)n * step];
+  mx[p] = p < P ? s : 0.0;
+  __syncthreads();
+  for (int off = 32; off > 0; off >>= 1) {
+    if (p < off) mx[p] = fmax(mx[p], mx[p + off]);
+    __syncthreads();
+  }
+  const double thr = SK_UNOBS_REL * mx[0];
+  if (p >= P) return;
+  int seen = 0;
+  for (int n = 0; n < N; ++n) seen += Hd[(size_t)n * step] > thr ? 1 : 0;
+  const size_t o = (size_t)b * P + p;
+  const unsigned char u = s <= thr ? 1 : 0;
+  if (info) info[o] = s;
+  if (n_seen) n_seen[o] = seen;
+  if (unobs_a) unobs_a[o] = u;
+  if (unobs_b) unobs_b[o] = u;
+}
+
 // ---- the banded system at lam = 0 (k_skel_build's statements): band[n][j] = block (n + j, n), [PT][PT] row-major;
-//      fxm[n][PT] the pin mask; diag0[n][PT] the diagonal of A as built (the pivot test's yardstick)
+//      fxm[n][PT] the pin mask; diag0[n][PT] the diagonal of A as built (the pivot test's yardstick).  unobs: NULL, or the
+//      clips' masks [n_clips][P] of k_skel_observability: such a state is pinned in every frame of its clip
 __global__ void __launch_bounds__(256)
 k_skel_cov_build(const SkelDev* __restrict__ dev, const double* __restrict__ x, const double* __restrict__ g,
                  const double* __restrict__ H, const double* __restrict__ hd, const double* __restrict__ lo,
                  const double* __restrict__ hi, double* __restrict__ band, unsigned char* __restrict__ fxm,
-                 double* __restrict__ diag0) {
+                 double* __restrict__ diag0, const unsigned char* __restrict__ unobs) {
   const SkelDev& D = *dev;
   const int tid = threadIdx.x, n = blockIdx.x, P = D.n_act, PT = D.PT, N = D.n_frames, nl = n % N;
   __shared__ unsigned char fx[4][SK_MAXP];
@@ -87,6 +146,7 @@ k_skel_cov_build(const SkelDev* __restrict__ dev, const double* __restrict__ x, 
       const size_t q = (size_t)(n + j) * P + p;
       f = skel_fixed(x[q], g[q], hd[q], lo[q], hi[q]);
     }
+    if (unobs && unobs[(size_t)(n / N) * P + p]) f = true;
     fx[j][p] = f ? 1 : 0;
   }
   __syncthreads();
@@ -274,11 +334,13 @@ k_skel_cov_out(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ cli
   }
 }
 
-// cov_pos[n][l] = G_l cov_x G_l^T, std_pos[n][l] = sqrt(trace): G_l = [I | d(M off)/d(angle) of the ops on slot l's path]
+// cov_pos[n][l] = G_l cov_x G_l^T, std_pos[n][l] = sqrt(trace): G_l = [I | d(M off)/d(angle) of the ops on slot l's path].
+// unobs: NULL, or the clips' masks [n_clips][P]: a slot with a nonzero entry of G_l in the column of an unobserved state gets
+// std_pos = +inf and cov_pos = NaN (the state is held at x by the pin, but nothing in the clip says where it is)
 __global__ void __launch_bounds__(256)
 k_skel_cov_pose(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, const double* __restrict__ band,
                 const unsigned char* __restrict__ fxm, const double* __restrict__ opv_all, double* __restrict__ cov_pos,
-                double* __restrict__ std_pos) {
+                double* __restrict__ std_pos, const unsigned char* __restrict__ unobs) {
   const SkelDev& D = *dev;
   const int n = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int P = D.n_act, PT = D.PT, NPOSE = D.n_pose, NOPS = D.n_ops;
@@ -304,6 +366,7 @@ k_skel_cov_pose(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ cl
   for (int l0 = 0; l0 < NPOSE; l0 += 4) {
     const int l = l0 + wave;
     const bool on = l < NPOSE;
+    bool dep = false;
     if (on && lane < P) {
       double gc[3] = {lane == 0 ? 1.0 : 0.0, lane == 1 ? 1.0 : 0.0, lane == 2 ? 1.0 : 0.0};
       const unsigned long long path = D.pmask[l];
@@ -321,7 +384,9 @@ k_skel_cov_pose(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ cl
       G[wave][0][lane] = gc[0];
       G[wave][1][lane] = gc[1];
       G[wave][2][lane] = gc[2];
+      if (unobs) dep = unobs[(size_t)(n / D.n_frames) * P + lane] && (gc[0] != 0.0 || gc[1] != 0.0 || gc[2] != 0.0);
     }
+    const bool undet = __any(dep ? 1 : 0) != 0;              // (wave-wide: a wave is one pose slot)
     __syncthreads();
     if (on && lane < P) {
       double t0 = 0.0, t1 = 0.0, t2 = 0.0;
@@ -341,16 +406,17 @@ k_skel_cov_pose(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ cl
       double s = 0.0;
       for (int q = 0; q < P; ++q) s += T[wave][i][q] * G[wave][j][q];
       out9[wave][lane] = s;
-      if (cov_pos) cov_pos[((size_t)n * NPOSE + l) * 9 + lane] = s;
+      if (cov_pos) cov_pos[((size_t)n * NPOSE + l) * 9 + lane] = undet ? __builtin_nan("") : s;
     }
     __syncthreads();
-    if (on && lane == 0 && std_pos) std_pos[(size_t)n * NPOSE + l] = sqrt(fmax(out9[wave][0] + out9[wave][4] + out9[wave][8], 0.0));
+    if (on && lane == 0 && std_pos)
+      std_pos[(size_t)n * NPOSE + l] = undet ? __builtin_inf() : sqrt(fmax(out9[wave][0] + out9[wave][4] + out9[wave][8], 0.0));
     __syncthreads();
   }
 }
 
 static size_t skc_align(size_t v) { return (v + 255) / 256 * 256; }
-SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops) {
+SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops, bool observe) {
   SkelCovLayout L;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -368,14 +434,75 @@ SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops) 
   L.band = take(sizeof(double) * NT * 4 * PT * PT);
   L.diag0 = take(sizeof(double) * NT * PT);
   L.fxm = take(NT * PT);
+  L.dev0 = L.unobs = 0;
+  if (observe) {
+    L.dev0 = take(sizeof(SkelDev));
+    L.unobs = take((size_t)n_clips * P);
+  }
   L.total = off;
   return L;
+}
+
+static int skel_cov_assemble_attr() {
+  static PerDeviceOnce attr;
+  if (attr.first()) {
+    const int big = 160 * 1024;
+    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble_pinhole),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, big));
+  }
+  return ACINO_OK;
+}
+
+// The Fisher assembly with the prior switched off and the reduction over it, all on stream s and without a host buffer that
+// has to outlive the call: h (already compiled by skel_program) travels as a kernel argument with q = 0 to d_dev0, the camera
+// records are copied on the device, the clips' words are cleared (the assembly reads them), k_skel_cov_assemble[_pinhole]
+// writes H = the Fisher blocks to lay.H (g, hd, cost, opv as a by-product) and k_skel_observability reduces their diagonals.
+static int skel_cov_launch_observe(const acino_skel_fte_params* p, int n_clips, int camera_model, const SkelDev& h,
+                                   const double* d_meas, const double* d_w, const double* d_cams, const double* d_x, void* d_ws,
+                                   const SkelCovLayout& lay, size_t dev0_off, hipStream_t s, double* d_info, int32_t* d_n_seen,
+                                   unsigned char* d_unobs_a, unsigned char* d_unobs_b) {
+  const int B = n_clips, P = p->n_active;
+  const size_t NT = (size_t)p->n_frames * B;
+  const size_t lds_asm = skel_assemble_lds(h.n_rows, P) + sizeof(double) * h.n_rows;      // + the Fisher weights
+  ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
+  char* base = (char*)d_ws;
+  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  SkelDev* d_dev0 = reinterpret_cast<SkelDev*>(base + dev0_off);
+  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
+  int rc;
+  if ((rc = skel_cov_assemble_attr())) return rc;
+  SkelDevHead head;
+  SkelDev h0 = h;
+  h0.q = 0.0;                                                 // H_pp = sum w^2 J^2 + 2 * 0 * b0: the Fisher diagonal itself
+  memcpy(&head, &h0, sizeof(head));
+  hipLaunchKernelGGL(k_skel_dev_store, dim3(1), dim3(256), 0, s, head, d_dev0);
+  ACINO_LAUNCH_CHECK();
+  if (camera_model == 1)
+    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev0) + offsetof(SkelDev, pins), d_cams,
+                                   sizeof(double) * ACINO_PINHOLE_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
+  else
+    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev0) + offsetof(SkelDev, cams), d_cams,
+                                   sizeof(double) * ACINO_CAM_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
+  ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)B, s));
+  if (camera_model == 1)
+    hipLaunchKernelGGL(k_skel_cov_assemble_pinhole, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev0, d_clip, 0, d_x, d_x, d_meas,
+                       d_w, D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
+  else
+    hipLaunchKernelGGL(k_skel_cov_assemble, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev0, d_clip, 0, d_x, d_x, d_meas, d_w,
+                       D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
+  ACINO_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_skel_observability, dim3((unsigned)B), dim3(64), 0, s, d_dev0, D(lay.H), d_info, d_n_seen, d_unobs_a,
+                     d_unobs_b);
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
 }
 
 int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
                           const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
                           const double* d_lo, const double* d_hi, const double* d_x, void* d_ws, const SkelCovLayout& lay,
-                          SkelDev& h, hipStream_t s) {
+                          SkelDev& h, hipStream_t s, bool observe, bool pin, uint8_t* d_unobserved) {
   const int B = n_clips, P = p->n_active;
   const size_t NT = (size_t)p->n_frames * B;
   int rc;
@@ -387,16 +514,11 @@ int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camer
   SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
-  {
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-      const int big = 160 * 1024;
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble_pinhole),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
-    }
-  }
+  unsigned char* d_unobs = observe ? reinterpret_cast<unsigned char*>(base + lay.unobs) : nullptr;
+  if ((rc = skel_cov_assemble_attr())) return rc;
+  if (observe && (rc = skel_cov_launch_observe(p, B, camera_model, h, d_meas, d_w, d_cams, d_x, d_ws, lay, lay.dev0, s, nullptr,
+                                               nullptr, d_unobs, d_unobserved)))
+    return rc;
   ACINO_HIP_CHECK(hipMemcpyAsync(d_dev, &h, sizeof(SkelDev), hipMemcpyHostToDevice, s));
   if (camera_model == 1)
     ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, pins), d_cams,
@@ -413,7 +535,7 @@ int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camer
                        D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
   ACINO_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_skel_cov_build, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_x, D(lay.g), D(lay.H), D(lay.hd), d_lo, d_hi,
-                     D(lay.band), d_fxm, D(lay.diag0));
+                     D(lay.band), d_fxm, D(lay.diag0), (const unsigned char*)(pin ? d_unobs : nullptr));
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }
@@ -422,41 +544,98 @@ int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camer
 
 using namespace acino;
 
+static bool skc_limits(const acino_skel_fte_params* p, int n_clips) {
+  return p && p->n_frames >= 1 && p->n_active >= 3 && p->n_active <= SK_MAXP && n_clips >= 1 && p->n_ops >= 0 &&
+         p->n_ops <= ACINO_SKEL_MAX_OPS;
+}
+
 extern "C" {
 
 size_t acino_skel_fte_covariance_workspace_bytes(const acino_skel_fte_params* p, int n_clips) {
-  if (!p || p->n_frames < 1 || p->n_active < 3 || p->n_active > SK_MAXP || n_clips < 1 || p->n_ops < 0 ||
-      p->n_ops > ACINO_SKEL_MAX_OPS)
-    return 0;
+  if (!skc_limits(p, n_clips)) return 0;
   const int PT = (p->n_active + 15) / 16 * 16;
   return skel_cov_layout((size_t)p->n_frames * n_clips, n_clips, p->n_active, PT, p->n_ops).total;
 }
 
-int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
-                              const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
-                              const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x, double* d_cov_pos,
-                              double* d_std_pos, int32_t* h_status, void* d_ws, size_t ws_bytes, void* stream) {
+size_t acino_skel_fte_covariance_pinned_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved) {
+  if (!skc_limits(p, n_clips) || (pin_unobserved != 0 && pin_unobserved != 1)) return 0;
+  const int PT = (p->n_active + 15) / 16 * 16;
+  return skel_cov_layout((size_t)p->n_frames * n_clips, n_clips, p->n_active, PT, p->n_ops, true).total;
+}
+
+// the assembly's arrays only: dev0, clip, H, g, hd, cost, opv (the leading part of the covariance's layout, no band)
+static size_t skc_observe_bytes(const acino_skel_fte_params* p, int n_clips, size_t* dev0_off) {
+  const int PT = (p->n_active + 15) / 16 * 16;
+  const SkelCovLayout lay = skel_cov_layout((size_t)p->n_frames * n_clips, n_clips, p->n_active, PT, p->n_ops);
+  if (dev0_off) *dev0_off = lay.band;                        // (in place of the band, which this call does not build)
+  return lay.band + skc_align(sizeof(SkelDev));
+}
+
+size_t acino_skel_fte_observability_workspace_bytes(const acino_skel_fte_params* p, int n_clips) {
+  if (!skc_limits(p, n_clips)) return 0;
+  return skc_observe_bytes(p, n_clips, nullptr);
+}
+
+int acino_skel_fte_observability(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                 const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                 const double* d_lo, const double* d_hi, const double* d_x, double* d_info, int32_t* d_n_seen,
+                                 uint8_t* d_unobserved, void* d_ws, size_t ws_bytes, void* stream) {
   int rc = skel_validate(p);
   if (rc) return rc;
   ACINO_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips in 1..65535");
   ACINO_REQUIRE(camera_model == 0 || camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
   ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws, "null buffer");
+  ACINO_REQUIRE(d_info || d_n_seen || d_unobserved, "at least one of d_info, d_n_seen, d_unobserved");
+  const size_t NT = (size_t)p->n_frames * n_clips;
+  ACINO_REQUIRE(NT < (size_t)1 << 31, "n_clips * n_frames < 2^31");
+  size_t dev0_off = 0;
+  const size_t need = skc_observe_bytes(p, n_clips, &dev0_off);
+  if (((uintptr_t)d_ws & 255) != 0) {
+    set_error("workspace must be 256-byte aligned");
+    return ACINO_ERR_WORKSPACE;
+  }
+  if (ws_bytes < need) {
+    set_error("workspace too small (acino_skel_fte_observability_workspace_bytes)");
+    return ACINO_ERR_WORKSPACE;
+  }
+  SkelDev h;                                                 // (travels by value: nothing reads it after the return)
+  if ((rc = skel_program(p, h_ops, h_active, h))) return rc;
+  const int PT = (p->n_active + 15) / 16 * 16;
+  const SkelCovLayout lay = skel_cov_layout(NT, n_clips, p->n_active, PT, p->n_ops);
+  return skel_cov_launch_observe(p, n_clips, camera_model, h, d_meas, d_w, d_cams, d_x, d_ws, lay, dev0_off, (hipStream_t)stream,
+                                 d_info, d_n_seen, d_unobserved, nullptr);
+}
+
+int acino_skel_fte_covariance_pinned(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                     const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                     const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x,
+                                     double* d_cov_pos, double* d_std_pos, int32_t* h_status, void* d_ws, size_t ws_bytes,
+                                     void* stream, int pin_unobserved, uint8_t* d_unobserved) {
+  int rc = skel_validate(p);
+  if (rc) return rc;
+  ACINO_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips in 1..65535");
+  ACINO_REQUIRE(camera_model == 0 || camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
+  ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
+  ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws, "null buffer");
   ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos, "at least one of d_cov_x, d_cov_pos, d_std_pos");
   const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16;
   const size_t NT = (size_t)N * B;                           // frames of all clips
   ACINO_REQUIRE(NT < (size_t)1 << 31, "n_clips * n_frames < 2^31");
-  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops);
+  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
+  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
   if (((uintptr_t)d_ws & 255) != 0) {
     set_error("workspace must be 256-byte aligned");
     return ACINO_ERR_WORKSPACE;
   }
   if (ws_bytes < lay.total) {
-    set_error("workspace too small (acino_skel_fte_covariance_workspace_bytes)");
+    set_error(observe ? "workspace too small (acino_skel_fte_covariance_pinned_workspace_bytes)"
+                      : "workspace too small (acino_skel_fte_covariance_workspace_bytes)");
     return ACINO_ERR_WORKSPACE;
   }
   std::vector<SkelDev> hv(1);                                // (lives until the one synchronisation at the end)
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, hv[0], s)))
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, hv[0], s,
+                                  observe, pin, d_unobserved)))
     return rc;
   const size_t lds_inv = skel_factor_lds(PT);
   char* base = (char*)d_ws;
@@ -464,6 +643,7 @@ int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int c
   SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
+  const unsigned char* d_unobs = pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr;
   {
     static PerDeviceOnce attr;
     if (attr.first()) {
@@ -491,7 +671,7 @@ int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int c
   }
   if (d_cov_pos || d_std_pos) {
     hipLaunchKernelGGL(k_skel_cov_pose, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_clip, D(lay.band), d_fxm, D(lay.opv), d_cov_pos,
-                       d_std_pos);
+                       d_std_pos, d_unobs);
     ACINO_LAUNCH_CHECK();
   }
   std::vector<SkelClip> hc(B);
@@ -507,6 +687,14 @@ int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int c
     return ACINO_ERR_NUMERIC;
   }
   return ACINO_OK;
+}
+
+int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                              const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                              const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x, double* d_cov_pos,
+                              double* d_std_pos, int32_t* h_status, void* d_ws, size_t ws_bytes, void* stream) {
+  return acino_skel_fte_covariance_pinned(p, n_clips, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_cov_x,
+                                          d_cov_pos, d_std_pos, h_status, d_ws, ws_bytes, stream, 0, nullptr);
 }
 
 }  // extern "C"

@@ -10,6 +10,10 @@
 namespace acino {
 
 constexpr double SK_PIV_REL = 1e-12;
+// A state whose Fisher information, summed over the clip, is not above SK_UNOBS_REL times the largest such sum of the clip is
+// UNOBSERVED (k_skel_observability): a Jacobian entry that is zero up to rounding is ~1e-16 relative, its square ~1e-32; the
+// weakest genuinely observed state of the test inputs sits at 5e-5.
+constexpr double SK_UNOBS_REL = ACINO_SKEL_UNOBS_REL;         // (acinoset_hip.h: part of the definition the ABI states)
 
 // One 16 x 16 tile product on a wave: acc += sum_{k in [k0, k1)} a_at(k) b_at(k), where lane (li, lk) supplies
 // a_at(k) = opA[row li][k] and b_at(k) = opB[k][col li]; acc[rr] is C[lk + 4 rr][li] (the MFMA layout of the solve).
@@ -136,14 +140,19 @@ __device__ __forceinline__ void skel_band_factor(int N, double* __restrict__ ban
 // ---- host: the workspace both entries use, and the launches up to the band --------------------------------------------
 struct SkelCovLayout {
   size_t dev, clip, H, g, hd, cost, opv, band, diag0, fxm, total;
+  size_t dev0, unobs;              // with `observe` only (appended: the offsets above are the same either way)
 };
-SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops);
+// observe: room for what k_skel_observability needs - a second SkelDev (the prior switched off) and the mask [n_clips][P]
+SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops, bool observe = false);
 // Validates the link program into h (which must live until the caller's synchronisation), uploads it and the cameras, clears
 // the clips' status words and launches k_skel_cov_assemble[_pinhole] and k_skel_cov_build on stream s: on return the
 // workspace holds band, fxm, diag0 and the link operators opv of every frame at d_x.
+// observe (the layout must have been made with it): first the Fisher assembly with the prior off and k_skel_observability;
+// the mask goes to the workspace and, if given, to d_unobserved[n_clips][P].  pin (needs observe): k_skel_cov_build pins the
+// clip's unobserved states in every frame.  Without observe the launches and their arguments are what they were.
 int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
                           const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
                           const double* d_lo, const double* d_hi, const double* d_x, void* d_ws, const SkelCovLayout& lay,
-                          SkelDev& h, hipStream_t s);
+                          SkelDev& h, hipStream_t s, bool observe = false, bool pin = false, uint8_t* d_unobserved = nullptr);
 
 }  // namespace acino

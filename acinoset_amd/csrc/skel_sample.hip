@@ -5,7 +5,9 @@
 // for the caller's z: Cov(delta) = A^-1 for standard-normal z, every cross-frame block included; delta is exactly 0 at pinned
 // variables.  The map is deterministic (the library owns no random generator) and delta(s) depends on z(s) alone.  Samples
 // are NOT clipped to the box: the Laplace posterior is a Gaussian, only the pinned variables are held.
-//   k_skel_cov_assemble[_pinhole], k_skel_cov_build   skel_cov.hip's, unchanged (skel_cov_launch_build)
+//   k_skel_cov_assemble[_pinhole], k_skel_cov_build   skel_cov.hip's (skel_cov_launch_build).  With pin_unobserved the build
+//                           step gets the clips' masks of k_skel_observability and pins those states in every frame: to the
+//                           kernels below a clip-wide pin is a bound pin, delta is exactly 0 there whatever z holds.
 //   k_skel_factor<PT>       one workgroup per clip: skel_band_factor<PT> (skel_factor.hpp, the forward half of k_skel_selinv).
 //                           Afterwards band[n][j] = L_n+j,n, the diagonal 16 x 16 tiles of band[n][0] replaced by
 //                           U_kk = L_kk^-T.  A pivot not above SK_PIV_REL * A_pp: status 5.
@@ -233,15 +235,22 @@ size_t acino_skel_fte_sample_workspace_bytes(const acino_skel_fte_params* p, int
   return acino_skel_fte_covariance_workspace_bytes(p, n_clips);             // (the samples live in the caller's arrays)
 }
 
-int acino_skel_fte_sample(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+size_t acino_skel_fte_sample_pinned_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int64_t n_samples,
+                                                    int pin_unobserved) {
+  if (n_samples < 1) return 0;
+  return acino_skel_fte_covariance_pinned_workspace_bytes(p, n_clips, pin_unobserved);
+}
+
+int acino_skel_fte_sample_pinned(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
                           const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
                           const double* d_lo, const double* d_hi, const double* d_x, int64_t n_samples, const double* d_z,
                           double* d_x_samples, double* d_pos_samples, int32_t* h_status, void* d_ws, size_t ws_bytes,
-                          void* stream) {
+                          void* stream, int pin_unobserved, uint8_t* d_unobserved) {
   int rc = skel_validate(p);
   if (rc) return rc;
   ACINO_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips in 1..65535");
   ACINO_REQUIRE(camera_model == 0 || camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
+  ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
   ACINO_REQUIRE(n_samples >= 1, "n_samples >= 1");
   ACINO_REQUIRE(d_z && d_x_samples, "d_z and d_x_samples must not be NULL");
   ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws, "null buffer");
@@ -254,18 +263,21 @@ int acino_skel_fte_sample(const acino_skel_fte_params* p, int n_clips, int camer
   ACINO_REQUIRE(!overlap(d_z, z_bytes, d_x_samples, z_bytes), "d_z overlaps d_x_samples");
   ACINO_REQUIRE(!d_pos_samples || !overlap(d_z, z_bytes, d_pos_samples, sizeof(double) * rows * p->n_pose * 3),
                 "d_z overlaps d_pos_samples");
-  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops);
+  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
+  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
   if (((uintptr_t)d_ws & 255) != 0) {
     set_error("workspace must be 256-byte aligned");
     return ACINO_ERR_WORKSPACE;
   }
   if (ws_bytes < lay.total) {
-    set_error("workspace too small (acino_skel_fte_sample_workspace_bytes)");
+    set_error(observe ? "workspace too small (acino_skel_fte_sample_pinned_workspace_bytes)"
+                      : "workspace too small (acino_skel_fte_sample_workspace_bytes)");
     return ACINO_ERR_WORKSPACE;
   }
   std::vector<SkelDev> hv(1);                                // (lives until the one synchronisation at the end)
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, hv[0], s)))
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, hv[0], s,
+                                  observe, pin, d_unobserved)))
     return rc;
   char* base = (char*)d_ws;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
@@ -297,6 +309,15 @@ int acino_skel_fte_sample(const acino_skel_fte_params* p, int n_clips, int camer
     return ACINO_ERR_NUMERIC;
   }
   return ACINO_OK;
+}
+
+int acino_skel_fte_sample(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                          const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                          const double* d_lo, const double* d_hi, const double* d_x, int64_t n_samples, const double* d_z,
+                          double* d_x_samples, double* d_pos_samples, int32_t* h_status, void* d_ws, size_t ws_bytes,
+                          void* stream) {
+  return acino_skel_fte_sample_pinned(p, n_clips, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, n_samples,
+                                      d_z, d_x_samples, d_pos_samples, h_status, d_ws, ws_bytes, stream, 0, nullptr);
 }
 
 }  // extern "C"

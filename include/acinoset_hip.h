@@ -601,6 +601,62 @@ int acino_skel_fte_sample(const acino_skel_fte_params* p, int n_clips, int camer
                           double* d_pos_samples /* [n_clips][S][N][n_pose][3], may be NULL */,
                           int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- which states does a clip observe?  Pinning the unobserved ones in the two posterior entries ----------------------------
+ * With H_F[n] the Fisher block of frame n at d_x (sum_{c,l,d} w^2 J^T J: the blocks of acino_skel_fte_covariance WITHOUT the prior)
+ * and ACINO_SKEL_UNOBS_REL = 1e-24, per clip b and active state p:
+ *   info[b][p]       = sum_n H_F[n][p][p], over the clip's frames in frame order (the same bits whatever else shares the batch)
+ *   n_seen[b][p]     = the number of frames with H_F[n][p][p] > ACINO_SKEL_UNOBS_REL * max_q info[b][q]
+ *   unobserved[b][p] = info[b][p] <= ACINO_SKEL_UNOBS_REL * max_q info[b][q]       (1 or 0)
+ * (a Jacobian entry that is zero only up to rounding is ~1e-16 relative, its square ~1e-32; a clip without any weighted detection
+ * has max info = 0 and every state unobserved).  An unobserved state makes A singular - the prior alone leaves its quadratic
+ * drift free - and acino_skel_fte_covariance / _sample report status 5 for the clip.  Two active states of the reference's shipped
+ * human skeleton (the psi angles of "chin" and "hip2": every link they rotate lies along the rotation's own axis) are unobserved
+ * on every clip; so are the joints of a limb no camera detects in the clip.
+ *
+ * acino_skel_fte_observability: the Fisher assembly and one small reduction (one workgroup per clip) on `stream`; no
+ * factorisation, no synchronisation, nothing read from host memory after the return.  Outputs on the device, each
+ * [n_clips][n_active], any may be NULL but not all three: d_info (fp64), d_n_seen (int32), d_unobserved (uint8).  Leading
+ * arguments, limits and workspace rules as acino_skel_fte_covariance (d_lo / d_hi are not read: the rule knows no bounds); both
+ * camera models.  n_seen is the diagnostic for a clip that stays singular although nothing is unobserved: the prior's quadratic
+ * drift needs a state to be seen in three frames.
+ *
+ * acino_skel_fte_covariance_pinned / acino_skel_fte_sample_pinned: the two entries above with two more arguments at the end.
+ *   pin_unobserved  0: the entry above, bit for bit.  1: every unobserved state of a clip is pinned in EVERY frame of the clip,
+ *                   by the rule of a bound pin (row and column 0, diagonal 1, the prior's couplings dropped) and in addition to
+ *                   the bound pins; everything else about A is unchanged.  cov_x has rows and columns exactly 0 there, delta
+ *                   of a sample is exactly 0 there whatever z holds.  A pose slot l of frame n with a nonzero entry of G_l[n] in
+ *                   the column of an unobserved state gets std_pos = +inf and all nine entries of cov_pos NaN: its spread is
+ *                   not finite under the stated model; every other slot gets G_l cov_x G_l^T.  pos_samples of such a slot show
+ *                   NO spread from that state (it is held at x): the mask is how the caller finds out.  The factorisation
+ *                   still decides singularity: a state seen in one or two frames is not pinned, and the clip stays status 5.
+ *                   Any other value: ACINO_ERR_INVALID_ARG.
+ *   d_unobserved    NULL, or [n_clips][n_active] (uint8, device): the mask of the rule above, written whether or not
+ *                   pin_unobserved is set; it tells the zeros that mean "undetermined" from those of a bound pin.
+ * Their workspace queries take pin_unobserved too (0 for a value outside {0, 1}); the size they return covers either value and
+ * a d_unobserved request, and is what these two entries need unless pin_unobserved == 0 and d_unobserved == NULL. */
+#define ACINO_SKEL_UNOBS_REL 1e-24
+size_t acino_skel_fte_observability_workspace_bytes(const acino_skel_fte_params* p, int n_clips);
+int acino_skel_fte_observability(const acino_skel_fte_params* p, int n_clips, int camera_model /* 0 fisheye: d_cams24, 1 pinhole: d_cams32 */,
+                                 const acino_skel_op* h_ops, const int32_t* h_active, const double* d_meas, const double* d_w,
+                                 const double* d_cams, const double* d_lo, const double* d_hi, const double* d_x,
+                                 double* d_info, int32_t* d_n_seen, uint8_t* d_unobserved, void* d_ws, size_t ws_bytes,
+                                 void* stream);
+size_t acino_skel_fte_covariance_pinned_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved);
+int acino_skel_fte_covariance_pinned(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                     const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                     const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x,
+                                     double* d_cov_pos, double* d_std_pos, int32_t* h_status /* [n_clips], may be NULL */,
+                                     void* d_ws, size_t ws_bytes, void* stream, int pin_unobserved,
+                                     uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
+size_t acino_skel_fte_sample_pinned_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int64_t n_samples,
+                                                    int pin_unobserved);
+int acino_skel_fte_sample_pinned(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                 const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                 const double* d_lo, const double* d_hi, const double* d_x, int64_t n_samples,
+                                 const double* d_z, double* d_x_samples, double* d_pos_samples,
+                                 int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes, void* stream,
+                                 int pin_unobserved, uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
+
 /* ---- a generic-skeleton FTE iterate in image space: predicted pixels, their covariance, residuals, gating ----------------
  * Evaluated at the iterate d_x[n_clips][N][n_active] (normally the solution of acino_skel_fte_solve*).  Per entry
  * (b, n, c, l) = (clip, frame, camera, pose slot), the layout of d_meas[n_clips][N][C][n_pose][2] / d_w[n_clips][N][C][n_pose]:
