@@ -251,9 +251,12 @@ def _skel_params(m0, n_act, max_iter=0, lam0=1e-3, ftol=0.0, xtol=0.0, gtol=0.0,
     return p
 
 
-def _posterior_inputs(models, xs, l1_eps, workspace_bytes):
-    """What the two calls at an iterate share (model_covariance, model_samples): the batch checks, the device arrays of the
-    models and of ``xs``, the parameter block and a workspace of ``workspace_bytes(p, B)`` bytes."""
+def _skel_inputs(models, xs, workspace_bytes=None, raw=False, start=False, **params):
+    """What every batched skeleton call shares: the batch checks, the checks on ``xs`` (one [N, P] array per model), the
+    parameter block (``params``: keywords of ``_skel_params``), the device arrays of the models and of ``xs`` and a workspace of
+    ``workspace_bytes(p, B)`` bytes (None: the call has none).  ``raw`` (model_reprojection): the measurements and weights go to
+    the device as they are, NaN kept, and there are no bounds.  ``start`` (the solve): ``xs`` are starting points - the caller's
+    own copies, states outside ``model.active`` must be 0 - not iterates, which must be finite."""
     if len(models) == 0:
         raise ValueError("no models")
     cam_model = _batch_camera_model(models)
@@ -264,30 +267,46 @@ def _posterior_inputs(models, xs, l1_eps, workspace_bytes):
     if len(xs) != B:
         raise ValueError(f"{len(xs)} iterates for {B} models")
     xs = [np.asarray(xf, dtype=np.float64) for xf in xs]
+    inactive = np.setdiff1d(np.arange(P), act)
     for xf in xs:
         if xf.shape != (N, P):
-            raise ValueError(f"every x must be [{N}, {P}] (the full-state layout of results['x'])")
-        if not np.isfinite(xf[:, act]).all():
+            raise ValueError(f"x0 must be [{N}, {P}]" if start else
+                             f"every x must be [{N}, {P}] (the full-state layout of results['x'])")
+        if start and np.any(xf[:, inactive] != 0):
+            raise ValueError("states that move no pose must start (and stay) at 0")
+        if not start and not np.isfinite(xf[:, act]).all():
             raise ValueError("x must be finite")
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
-    p = _skel_params(m0, len(act), l1_eps=l1_eps)
-    nbytes = workspace_bytes(p, B)
-    if nbytes == 0:
-        raise ValueError("problem outside the kernel limits (n_active <= 64)")
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+    p = _skel_params(m0, len(act), **params)
+    ws, tail = None, (stream_ptr(),)
+    if workspace_bytes is not None:
+        nbytes = workspace_bytes(p, B)
+        if nbytes == 0:
+            raise ValueError("problem outside the kernel limits (n_active <= 64)")
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        tail = (C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr())
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)   # noqa: E731
-    meas = t(np.stack([np.nan_to_num(m.meas, nan=0.0) for m in models]))
-    w = t(np.stack([np.where(np.isfinite(m.meas).all(-1), m.weights, 0.0) for m in models]))
+    if raw:                                                               # a NaN detection gives a NaN residual
+        meas, w, bounds = t(np.stack([m.meas for m in models])), t(np.stack([m.weights for m in models])), ()
+    else:
+        meas = t(np.stack([np.nan_to_num(m.meas, nan=0.0) for m in models]))
+        w = t(np.stack([np.where(np.isfinite(m.meas).all(-1), m.weights, 0.0) for m in models]))
+        bounds = (t(np.stack([m.lo[:, act] for m in models])), t(np.stack([m.hi[:, act] for m in models])))
     cams = torch.as_tensor(calib.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
-    lo, hi = t(np.stack([m.lo[:, act] for m in models])), t(np.stack([m.hi[:, act] for m in models]))
     x = t(np.stack([xf[:, act] for xf in xs]))
     act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
-    head = (C.byref(p), B, 1 if cam_model == "pinhole" else 0, _ops_array(m0.prog), act_c, ptr(meas), ptr(w), ptr(cams), ptr(lo),
-            ptr(hi), ptr(x))
-    keep = (p, ws, meas, w, cams, lo, hi, x, act_c)
-    return dict(xs=xs, act=act, dev=dev, head=head, tail=(C.c_void_p(ws_ptr), nbytes, stream_ptr()), keep=keep)
+    head = (C.byref(p), B, 1 if cam_model == "pinhole" else 0, _ops_array(m0.prog), act_c, ptr(meas), ptr(w), ptr(cams),
+            *[ptr(b) for b in bounds], ptr(x))
+    keep = (p, ws, meas, w, cams, bounds, act_c)
+    return dict(xs=xs, act=act, dev=dev, cam_model=cam_model, x=x, head=head, tail=tail, keep=keep)
+
+
+def _attach(out, extras, keys):
+    """Every ``results`` of ``out`` (the (results, info) pairs of a solve) takes ``keys`` from its clip's dict in ``extras``; a
+    key the extras do not carry (``unobserved`` without ``pin_unobserved``) is left out."""
+    for (res, _info), ex in zip(out, extras):
+        res.update({k: ex[k] for k in keys if k in ex})
 
 
 def _unobserved_lists(mask, act):
@@ -301,9 +320,8 @@ def _covariance(models, xs, l1_eps, want, raise_numeric=True, pin_unobserved=Fal
     a singular single clip is reported in its ``status`` like a clip of a batch.  ``pin_unobserved``: the _pinned entry, and
     ``unobserved`` in every dict."""
     pin = bool(pin_unobserved)
-    io_ = _posterior_inputs(models, xs, l1_eps,
-                            (lambda p, B: lib().acino_skel_fte_covariance_pinned_workspace_bytes(C.byref(p), B, 1)) if pin else
-                            (lambda p, B: lib().acino_skel_fte_covariance_workspace_bytes(C.byref(p), B)))
+    io_ = _skel_inputs(models, xs, (lambda p, B: lib().acino_skel_fte_covariance_pinned_workspace_bytes(C.byref(p), B, 1)) if pin else
+                       (lambda p, B: lib().acino_skel_fte_covariance_workspace_bytes(C.byref(p), B)), l1_eps=l1_eps)
     m0, act, dev = models[0], io_["act"], io_["dev"]
     B, N, P = len(models), m0.N, m0.P
     Pa, Lp = len(act), len(m0.names)
@@ -350,7 +368,7 @@ def model_observability(models, xs, l1_eps=1e-2):
     makes the clip's covariance singular (status 5) unless ``pin_unobserved=True``.  A clip that is singular with an empty
     ``unobserved`` has a state with ``n_seen`` < 3: the prior's quadratic drift needs three informative frames, and such states are
     not pinned."""
-    io_ = _posterior_inputs(models, xs, l1_eps, lambda p, B: lib().acino_skel_fte_observability_workspace_bytes(C.byref(p), B))
+    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_observability_workspace_bytes(C.byref(p), B), l1_eps=l1_eps)
     m0, act, dev = models[0], io_["act"], io_["dev"]
     B, P, Pa = len(models), m0.P, len(io_["act"])
     info = torch.empty((B, Pa), dtype=torch.float64, device=dev)
@@ -426,9 +444,8 @@ def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1
         raise ValueError("z must be finite")
     S = z.shape[1]
     pin = bool(pin_unobserved)
-    io_ = _posterior_inputs(models, xs, l1_eps,
-                            (lambda p, nb: lib().acino_skel_fte_sample_pinned_workspace_bytes(C.byref(p), nb, S, 1)) if pin else
-                            (lambda p, nb: lib().acino_skel_fte_sample_workspace_bytes(C.byref(p), nb, S)))
+    io_ = _skel_inputs(models, xs, (lambda p, nb: lib().acino_skel_fte_sample_pinned_workspace_bytes(C.byref(p), nb, S, 1)) if pin else
+                       (lambda p, nb: lib().acino_skel_fte_sample_workspace_bytes(C.byref(p), nb, S)), l1_eps=l1_eps)
     m0, act, dev = models[0], io_["act"], io_["dev"]
     zd = torch.as_tensor(z, device=dev)
     xs_d = torch.empty((B, S, N, n_act), dtype=torch.float64, device=dev)
@@ -484,20 +501,9 @@ def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1
     ``cov_pos`` and therefore NaN ``cov_uv`` / ``std_uv`` / ``mahal2``, and the dict carries ``unobserved`` beside ``cov_status``."""
     if len(models) == 0:
         raise ValueError("no models")
-    cam_model = _batch_camera_model(models)
-    _batch_check(models)
     m0 = models[0]
-    B, N, P = len(models), m0.N, m0.P
+    B, N = len(models), m0.N
     Cn, Lp = int(m0.meas.shape[1]), len(m0.names)
-    act = np.asarray(m0.active, dtype=np.int32)
-    if len(xs) != B:
-        raise ValueError(f"{len(xs)} iterates for {B} models")
-    xs = [np.asarray(xf, dtype=np.float64) for xf in xs]
-    for xf in xs:
-        if xf.shape != (N, P):
-            raise ValueError(f"every x must be [{N}, {P}] (the full-state layout of results['x'])")
-        if not np.isfinite(xf[:, act]).all():
-            raise ValueError("x must be finite")
     if r_gate is None:
         w_max = max(float(np.nanmax(np.asarray(m.weights), initial=0.0)) for m in models)
         if not w_max > 0:
@@ -521,23 +527,15 @@ def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1
         cov_pos, cov_status = [cv["cov_pos"] for cv in covs], [cv["status"] for cv in covs]
         if pin_unobserved:
             cov_unobs = [cv["unobserved"] for cv in covs]
-    _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    p = _skel_params(m0, len(act), l1_eps=l1_eps)
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)   # noqa: E731
-    meas = t(np.stack([m.meas for m in models]))                      # raw: a NaN detection gives a NaN residual
-    w = t(np.stack([m.weights for m in models]))
-    cams = torch.as_tensor(calib.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
-    x = t(np.stack([xf[:, act] for xf in xs]))
-    cp_d = t(np.stack(cov_pos)) if cov else None
+    io_ = _skel_inputs(models, xs, raw=True, l1_eps=l1_eps)
+    dev = io_["dev"]
+    cp_d = torch.as_tensor(np.ascontiguousarray(np.stack(cov_pos), dtype=np.float64), device=dev) if cov else None
     empty = lambda *shape: torch.empty((B, N, Cn, Lp) + shape, dtype=torch.float64, device=dev)   # noqa: E731
     uv, res, m2 = empty(2), empty(2), empty()
     cuv = empty(2, 2) if cov else None
     flags = torch.empty((B, N, Cn, Lp), dtype=torch.uint8, device=dev)
-    act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
-    check(lib().acino_skel_fte_reprojection(C.byref(p), B, 1 if cam_model == "pinhole" else 0, _ops_array(m0.prog), act_c, ptr(meas),
-                                            ptr(w), ptr(cams), ptr(x), ptr(cp_d), 1.0 / r_gate, ptr(uv), ptr(cuv), ptr(res), ptr(m2),
-                                            ptr(flags), stream_ptr()))
+    check(lib().acino_skel_fte_reprojection(*io_["head"], ptr(cp_d), 1.0 / r_gate, ptr(uv), ptr(cuv), ptr(res), ptr(m2), ptr(flags),
+                                            *io_["tail"]))
     uv, res, m2, flags = uv.cpu().numpy(), res.cpu().numpy(), m2.cpu().numpy(), flags.cpu().numpy()
     cuv = cuv.cpu().numpy() if cov else None
     out = []
@@ -598,66 +596,33 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     ``pin_unobserved``: passed to ``model_covariance`` / ``model_samples`` (it acts only together with ``return_cov`` or
     ``n_samples``, and through ``return_cov`` on the report; the solve itself never changes); ``results`` then carries
     ``unobserved``.  ``pos_samples`` of a pose that depends on an unobserved state show no spread from it."""
-    cam_model = _batch_camera_model(models)
-    _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    m0 = models[0]
-    B, N, P = len(models), m0.N, m0.P
-    act = np.asarray(m0.active, dtype=np.int32)
-    prog = m0.prog
-    _batch_check(models)
     xs = [np.array(m.init_x if x0 is None or x0[i] is None else x0[i], dtype=np.float64, copy=True) for i, m in enumerate(models)]
-    inactive = np.setdiff1d(np.arange(P), act)
-    for xf in xs:
-        if xf.shape != (N, P):
-            raise ValueError(f"x0 must be [{N}, {P}]")
-        if np.any(xf[:, inactive] != 0):
-            raise ValueError("states that move no pose must start (and stay) at 0")
-    p = _skel_params(m0, len(act), max_iter, lam0, ftol, xtol, gtol, l1_eps, lam_max)
-    nbytes = lib().acino_skel_fte_workspace_bytes_batch(C.byref(p), B)
-    if nbytes == 0:
-        raise ValueError("problem outside the kernel limits (n_active <= 64)")
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)   # noqa: E731
-    meas = t(np.stack([np.nan_to_num(m.meas, nan=0.0) for m in models]))
-    w = t(np.stack([np.where(np.isfinite(m.meas).all(-1), m.weights, 0.0) for m in models]))
-    cams = torch.as_tensor(calib.camera_records(cam_model, m0.K, m0.D, m0.R, m0.t), device=dev)
-    lo, hi = t(np.stack([m.lo[:, act] for m in models])), t(np.stack([m.hi[:, act] for m in models]))
-    x = t(np.stack([xf[:, act] for xf in xs]))
-    pos = torch.empty((B, N, len(m0.names), 3), dtype=torch.float64, device=dev)
+    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_workspace_bytes_batch(C.byref(p), B), start=True, max_iter=max_iter,
+                       lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol, l1_eps=l1_eps, lam_max=lam_max)
+    m0, act, x = models[0], io_["act"], io_["x"]
+    B = len(models)
+    pos = torch.empty((B, m0.N, len(m0.names), 3), dtype=torch.float64, device=io_["dev"])
     infos = (SkelFteInfo * B)()
-    act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
-    solve = getattr(lib(), calib.CAMERAS[cam_model].skel_fte_solve_batch)
-    check(solve(C.byref(p), B, _ops_array(prog), act_c, ptr(meas), ptr(w), ptr(cams), ptr(lo), ptr(hi), ptr(x), ptr(pos),
-                C.c_void_p(ws_ptr), nbytes, infos, stream_ptr()))
+    solve = getattr(lib(), calib.CAMERAS[io_["cam_model"]].skel_fte_solve_batch)
+    head = io_["head"]
+    check(solve(*head[:2], *head[3:], ptr(pos), *io_["tail"][:2], infos, io_["tail"][2]))      # (the camera model is in the entry's name)
     xh, ph = x.cpu().numpy(), pos.cpu().numpy()
     out = []
     for i, (m, xf) in enumerate(zip(models, xs)):
         xf[:, act] = xh[i]
         dx, ddx = _finite_diff_states(xf, float(m.h))
         out.append((dict(positions=ph[i], x=xf, dx=dx, ddx=ddx), infos[i].as_dict()))
+    io_ = None                                              # (the workspace goes before the next call asks for its own)
+    xs_out = [r["x"] for r, _i in out]
     if return_cov:
-        del ws
-        covs = _covariance(models, [r["x"] for r, _i in out], l1_eps, ("cov_x", "cov_pos", "std_pos"), pin_unobserved=pin_unobserved)
-        for (res, _info), cv in zip(out, covs):
-            res.update(cov_x=cv["cov_x"], cov_pos=cv["cov_pos"], std_pos=cv["std_pos"])
-            if pin_unobserved:
-                res["unobserved"] = cv["unobserved"]
+        _attach(out, _covariance(models, xs_out, l1_eps, ("cov_x", "cov_pos", "std_pos"), pin_unobserved=pin_unobserved),
+                ("cov_x", "cov_pos", "std_pos", "unobserved"))
     if n_samples:
-        ws = None
-        draws = model_samples(models, [r["x"] for r, _i in out], n_samples=n_samples, seed=sample_seed, l1_eps=l1_eps,
-                              pin_unobserved=pin_unobserved)
-        for (res, _info), dr in zip(out, draws):
-            res.update(x_samples=dr["x_samples"], pos_samples=dr["pos_samples"])
-            if pin_unobserved:
-                res["unobserved"] = dr["unobserved"]
+        _attach(out, model_samples(models, xs_out, n_samples=n_samples, seed=sample_seed, l1_eps=l1_eps, pin_unobserved=pin_unobserved),
+                ("x_samples", "pos_samples", "unobserved"))
     if return_reprojection:
-        ws = None
-        reps = model_reprojection(models, [r["x"] for r, _i in out], cov=bool(return_cov),
-                                  cov_pos=[r["cov_pos"] for r, _i in out] if return_cov else None, l1_eps=l1_eps)
-        for (res, _info), rep in zip(out, reps):
-            res.update({k: rep[k] for k in REPROJ_KEYS})
+        _attach(out, model_reprojection(models, xs_out, cov=bool(return_cov),
+                                        cov_pos=[r["cov_pos"] for r, _i in out] if return_cov else None, l1_eps=l1_eps), REPROJ_KEYS)
     return out
 
 

@@ -86,7 +86,8 @@ k_skel_cov_assemble_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __r
 #undef ACINO_SKEL_FISHER
 
 // ---- the host half of a SkelDev (everything before the camera records, 2.9 KB) by value in the kernel-argument segment:
-//      a call that does not synchronise (acino_skel_fte_observability) cannot leave an asynchronous copy reading its stack
+//      an asynchronous copy would read the caller's stack after an early return, or after the return of an entry that does not
+//      synchronise (acino_skel_fte_observability).  skel_upload (skel_host.hpp) is its only launch site, for every entry.
 struct SkelDevHead {
   unsigned long long w[offsetof(SkelDev, cams) / 8];
 };
@@ -415,15 +416,9 @@ k_skel_cov_pose(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ cl
   }
 }
 
-static size_t skc_align(size_t v) { return (v + 255) / 256 * 256; }
 SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops, bool observe) {
   SkelCovLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = skc_align(off + bytes);
-    return o;
-  };
+  SkelTake take;
   L.dev = take(sizeof(SkelDev));
   L.clip = take(sizeof(SkelClip) * (size_t)n_clips);
   L.H = take(sizeof(double) * NT * P * P);
@@ -439,62 +434,88 @@ SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops, 
     L.dev0 = take(sizeof(SkelDev));
     L.unobs = take((size_t)n_clips * P);
   }
-  L.total = off;
+  L.total = take.off;
   return L;
 }
 
-static int skel_cov_assemble_attr() {
-  static PerDeviceOnce attr;
-  if (attr.first()) {
-    const int big = 160 * 1024;
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, big));
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_cov_assemble_pinhole),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, big));
+int skel_upload(const SkelDev& h, const double* d_cams, int camera_model, SkelDev* d_dev, SkelClip* d_clip, int n_clips,
+                hipStream_t s) {
+  SkelDevHead head;
+  memcpy(&head, &h, sizeof(head));
+  hipLaunchKernelGGL(k_skel_dev_store, dim3(1), dim3(256), 0, s, head, d_dev);
+  ACINO_LAUNCH_CHECK();
+  const bool pinhole = camera_model == 1;
+  ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + (pinhole ? offsetof(SkelDev, pins) : offsetof(SkelDev, cams)),
+                                 d_cams, sizeof(double) * (pinhole ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE) * h.n_cams,
+                                 hipMemcpyDeviceToDevice, s));
+  ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)n_clips, s));
+  return ACINO_OK;
+}
+
+int skel_read_status(const SkelClip* d_clip, int n_clips, hipStream_t s, bool per_clip_output, const char* numeric_text,
+                     std::vector<SkelClip>& hc) {
+  hc.resize(n_clips);
+  ACINO_HIP_CHECK(hipMemcpyAsync(hc.data(), d_clip, sizeof(SkelClip) * (size_t)n_clips, hipMemcpyDeviceToHost, s));
+  ACINO_HIP_CHECK(hipStreamSynchronize(s));
+  bool numeric = false;
+  for (const SkelClip& c : hc) numeric = numeric || c.status == 5;
+  if (numeric && (n_clips == 1 || !per_clip_output)) {
+    set_error("%s", numeric_text);
+    return ACINO_ERR_NUMERIC;
   }
   return ACINO_OK;
 }
 
-// The Fisher assembly with the prior switched off and the reduction over it, all on stream s and without a host buffer that
-// has to outlive the call: h (already compiled by skel_program) travels as a kernel argument with q = 0 to d_dev0, the camera
-// records are copied on the device, the clips' words are cleared (the assembly reads them), k_skel_cov_assemble[_pinhole]
-// writes H = the Fisher blocks to lay.H (g, hd, cost, opv as a by-product) and k_skel_observability reduces their diagonals.
-static int skel_cov_launch_observe(const acino_skel_fte_params* p, int n_clips, int camera_model, const SkelDev& h,
-                                   const double* d_meas, const double* d_w, const double* d_cams, const double* d_x, void* d_ws,
-                                   const SkelCovLayout& lay, size_t dev0_off, hipStream_t s, double* d_info, int32_t* d_n_seen,
-                                   unsigned char* d_unobs_a, unsigned char* d_unobs_b) {
-  const int B = n_clips, P = p->n_active;
-  const size_t NT = (size_t)p->n_frames * B;
-  const size_t lds_asm = skel_assemble_lds(h.n_rows, P) + sizeof(double) * h.n_rows;      // + the Fisher weights
+int skel_cov_read_status(const SkelClip* d_clip, int n_clips, hipStream_t s, int32_t* h_status) {
+  std::vector<SkelClip> hc;
+  const int rc = skel_read_status(
+      d_clip, n_clips, s, h_status != nullptr,
+      "pivot not above zero in the banded factorisation of the Fisher information (a state observed in no frame of the clip)", hc);
+  if (h_status && (rc == ACINO_OK || rc == ACINO_ERR_NUMERIC))
+    for (int b = 0; b < n_clips; ++b) h_status[b] = hc[b].status;
+  return rc;
+}
+
+// h to d_dev, then the Fisher assembly at d_x on stream s: H = the Fisher blocks (+ the prior's diagonal 2 q b0), g, hd, cost
+// and the link operators opv of every frame into the workspace.  What the observability pass (q = 0, a SkelDev of its own) and
+// the band's build start with.
+static int skel_cov_assemble_at(const SkelDev& h, int n_clips, int camera_model, const double* d_meas, const double* d_w,
+                                const double* d_cams, const double* d_x, void* d_ws, const SkelCovLayout& lay, SkelDev* d_dev,
+                                hipStream_t s) {
+  const size_t NT = (size_t)h.n_frames * n_clips;
+  const size_t lds_asm = skel_assemble_lds(h.n_rows, h.n_act) + sizeof(double) * h.n_rows;      // + the Fisher weights
   ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
+  static PerDeviceOnce attr;
+  if (attr.first())
+    for (int model = 0; model < 2; ++model)
+      ACINO_HIP_CHECK(hipFuncSetAttribute(
+          reinterpret_cast<const void*>(skel_camera_kernel(model, k_skel_cov_assemble, k_skel_cov_assemble_pinhole)),
+          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   char* base = (char*)d_ws;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
-  SkelDev* d_dev0 = reinterpret_cast<SkelDev*>(base + dev0_off);
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   int rc;
-  if ((rc = skel_cov_assemble_attr())) return rc;
-  SkelDevHead head;
+  if ((rc = skel_upload(h, d_cams, camera_model, d_dev, d_clip, n_clips, s))) return rc;
+  hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_cov_assemble, k_skel_cov_assemble_pinhole), dim3((unsigned)NT),
+                     dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas, d_w, D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd),
+                     D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
+
+// The Fisher assembly with the prior switched off and the reduction over it: h (already compiled by skel_program) goes to the
+// SkelDev at dev0_off with q = 0, so that H IS the Fisher block, and k_skel_observability reduces the diagonals.
+static int skel_cov_launch_observe(int n_clips, int camera_model, const SkelDev& h, const double* d_meas, const double* d_w,
+                                   const double* d_cams, const double* d_x, void* d_ws, const SkelCovLayout& lay, size_t dev0_off,
+                                   hipStream_t s, double* d_info, int32_t* d_n_seen, unsigned char* d_unobs_a,
+                                   unsigned char* d_unobs_b) {
+  SkelDev* d_dev0 = reinterpret_cast<SkelDev*>((char*)d_ws + dev0_off);
   SkelDev h0 = h;
   h0.q = 0.0;                                                 // H_pp = sum w^2 J^2 + 2 * 0 * b0: the Fisher diagonal itself
-  memcpy(&head, &h0, sizeof(head));
-  hipLaunchKernelGGL(k_skel_dev_store, dim3(1), dim3(256), 0, s, head, d_dev0);
-  ACINO_LAUNCH_CHECK();
-  if (camera_model == 1)
-    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev0) + offsetof(SkelDev, pins), d_cams,
-                                   sizeof(double) * ACINO_PINHOLE_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
-  else
-    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev0) + offsetof(SkelDev, cams), d_cams,
-                                   sizeof(double) * ACINO_CAM_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
-  ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)B, s));
-  if (camera_model == 1)
-    hipLaunchKernelGGL(k_skel_cov_assemble_pinhole, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev0, d_clip, 0, d_x, d_x, d_meas,
-                       d_w, D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
-  else
-    hipLaunchKernelGGL(k_skel_cov_assemble, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev0, d_clip, 0, d_x, d_x, d_meas, d_w,
-                       D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
-  ACINO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_skel_observability, dim3((unsigned)B), dim3(64), 0, s, d_dev0, D(lay.H), d_info, d_n_seen, d_unobs_a,
-                     d_unobs_b);
+  int rc;
+  if ((rc = skel_cov_assemble_at(h0, n_clips, camera_model, d_meas, d_w, d_cams, d_x, d_ws, lay, d_dev0, s))) return rc;
+  hipLaunchKernelGGL(k_skel_observability, dim3((unsigned)n_clips), dim3(64), 0, s, d_dev0,
+                     reinterpret_cast<const double*>((char*)d_ws + lay.H), d_info, d_n_seen, d_unobs_a, d_unobs_b);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }
@@ -502,38 +523,20 @@ static int skel_cov_launch_observe(const acino_skel_fte_params* p, int n_clips, 
 int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
                           const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
                           const double* d_lo, const double* d_hi, const double* d_x, void* d_ws, const SkelCovLayout& lay,
-                          SkelDev& h, hipStream_t s, bool observe, bool pin, uint8_t* d_unobserved) {
-  const int B = n_clips, P = p->n_active;
-  const size_t NT = (size_t)p->n_frames * B;
+                          hipStream_t s, bool observe, bool pin, uint8_t* d_unobserved) {
+  const size_t NT = (size_t)p->n_frames * n_clips;
+  SkelDev h;
   int rc;
   if ((rc = skel_program(p, h_ops, h_active, h))) return rc;
-  const size_t lds_asm = skel_assemble_lds(h.n_rows, P) + sizeof(double) * h.n_rows;      // + the Fisher weights
-  ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
   char* base = (char*)d_ws;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
   SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
-  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
   unsigned char* d_unobs = observe ? reinterpret_cast<unsigned char*>(base + lay.unobs) : nullptr;
-  if ((rc = skel_cov_assemble_attr())) return rc;
-  if (observe && (rc = skel_cov_launch_observe(p, B, camera_model, h, d_meas, d_w, d_cams, d_x, d_ws, lay, lay.dev0, s, nullptr,
+  if (observe && (rc = skel_cov_launch_observe(n_clips, camera_model, h, d_meas, d_w, d_cams, d_x, d_ws, lay, lay.dev0, s, nullptr,
                                                nullptr, d_unobs, d_unobserved)))
     return rc;
-  ACINO_HIP_CHECK(hipMemcpyAsync(d_dev, &h, sizeof(SkelDev), hipMemcpyHostToDevice, s));
-  if (camera_model == 1)
-    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, pins), d_cams,
-                                   sizeof(double) * ACINO_PINHOLE_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
-  else
-    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, cams), d_cams,
-                                   sizeof(double) * ACINO_CAM_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
-  ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)B, s));
-  if (camera_model == 1)
-    hipLaunchKernelGGL(k_skel_cov_assemble_pinhole, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas,
-                       d_w, D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
-  else
-    hipLaunchKernelGGL(k_skel_cov_assemble, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas, d_w,
-                       D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd), D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
-  ACINO_LAUNCH_CHECK();
+  if ((rc = skel_cov_assemble_at(h, n_clips, camera_model, d_meas, d_w, d_cams, d_x, d_ws, lay, d_dev, s))) return rc;
   hipLaunchKernelGGL(k_skel_cov_build, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_x, D(lay.g), D(lay.H), D(lay.hd), d_lo, d_hi,
                      D(lay.band), d_fxm, D(lay.diag0), (const unsigned char*)(pin ? d_unobs : nullptr));
   ACINO_LAUNCH_CHECK();
@@ -568,7 +571,7 @@ static size_t skc_observe_bytes(const acino_skel_fte_params* p, int n_clips, siz
   const int PT = (p->n_active + 15) / 16 * 16;
   const SkelCovLayout lay = skel_cov_layout((size_t)p->n_frames * n_clips, n_clips, p->n_active, PT, p->n_ops);
   if (dev0_off) *dev0_off = lay.band;                        // (in place of the band, which this call does not build)
-  return lay.band + skc_align(sizeof(SkelDev));
+  return lay.band + skel_align256(sizeof(SkelDev));
 }
 
 size_t acino_skel_fte_observability_workspace_bytes(const acino_skel_fte_params* p, int n_clips) {
@@ -580,30 +583,19 @@ int acino_skel_fte_observability(const acino_skel_fte_params* p, int n_clips, in
                                  const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
                                  const double* d_lo, const double* d_hi, const double* d_x, double* d_info, int32_t* d_n_seen,
                                  uint8_t* d_unobserved, void* d_ws, size_t ws_bytes, void* stream) {
-  int rc = skel_validate(p);
+  int rc = skel_check_batch(p, n_clips, true, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws);
   if (rc) return rc;
-  ACINO_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips in 1..65535");
-  ACINO_REQUIRE(camera_model == 0 || camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
-  ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws, "null buffer");
   ACINO_REQUIRE(d_info || d_n_seen || d_unobserved, "at least one of d_info, d_n_seen, d_unobserved");
   const size_t NT = (size_t)p->n_frames * n_clips;
-  ACINO_REQUIRE(NT < (size_t)1 << 31, "n_clips * n_frames < 2^31");
   size_t dev0_off = 0;
   const size_t need = skc_observe_bytes(p, n_clips, &dev0_off);
-  if (((uintptr_t)d_ws & 255) != 0) {
-    set_error("workspace must be 256-byte aligned");
-    return ACINO_ERR_WORKSPACE;
-  }
-  if (ws_bytes < need) {
-    set_error("workspace too small (acino_skel_fte_observability_workspace_bytes)");
-    return ACINO_ERR_WORKSPACE;
-  }
-  SkelDev h;                                                 // (travels by value: nothing reads it after the return)
+  if ((rc = skel_check_workspace(d_ws, ws_bytes, need, "acino_skel_fte_observability_workspace_bytes", ACINO_ERR_WORKSPACE))) return rc;
+  SkelDev h;
   if ((rc = skel_program(p, h_ops, h_active, h))) return rc;
   const int PT = (p->n_active + 15) / 16 * 16;
   const SkelCovLayout lay = skel_cov_layout(NT, n_clips, p->n_active, PT, p->n_ops);
-  return skel_cov_launch_observe(p, n_clips, camera_model, h, d_meas, d_w, d_cams, d_x, d_ws, lay, dev0_off, (hipStream_t)stream,
-                                 d_info, d_n_seen, d_unobserved, nullptr);
+  return skel_cov_launch_observe(n_clips, camera_model, h, d_meas, d_w, d_cams, d_x, d_ws, lay, dev0_off, (hipStream_t)stream, d_info,
+                                 d_n_seen, d_unobserved, nullptr);
 }
 
 int acino_skel_fte_covariance_pinned(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
@@ -611,60 +603,39 @@ int acino_skel_fte_covariance_pinned(const acino_skel_fte_params* p, int n_clips
                                      const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x,
                                      double* d_cov_pos, double* d_std_pos, int32_t* h_status, void* d_ws, size_t ws_bytes,
                                      void* stream, int pin_unobserved, uint8_t* d_unobserved) {
-  int rc = skel_validate(p);
+  int rc = skel_check_batch(p, n_clips, true, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws);
   if (rc) return rc;
-  ACINO_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips in 1..65535");
-  ACINO_REQUIRE(camera_model == 0 || camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
   ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
-  ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws, "null buffer");
   ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos, "at least one of d_cov_x, d_cov_pos, d_std_pos");
   const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16;
   const size_t NT = (size_t)N * B;                           // frames of all clips
-  ACINO_REQUIRE(NT < (size_t)1 << 31, "n_clips * n_frames < 2^31");
   const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
   const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
-  if (((uintptr_t)d_ws & 255) != 0) {
-    set_error("workspace must be 256-byte aligned");
-    return ACINO_ERR_WORKSPACE;
-  }
-  if (ws_bytes < lay.total) {
-    set_error(observe ? "workspace too small (acino_skel_fte_covariance_pinned_workspace_bytes)"
-                      : "workspace too small (acino_skel_fte_covariance_workspace_bytes)");
-    return ACINO_ERR_WORKSPACE;
-  }
-  std::vector<SkelDev> hv(1);                                // (lives until the one synchronisation at the end)
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, hv[0], s,
-                                  observe, pin, d_unobserved)))
+  if ((rc = skel_check_workspace(d_ws, ws_bytes, lay.total,
+                                 observe ? "acino_skel_fte_covariance_pinned_workspace_bytes" : "acino_skel_fte_covariance_workspace_bytes",
+                                 ACINO_ERR_WORKSPACE)))
     return rc;
-  const size_t lds_inv = skel_factor_lds(PT);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
+                                  d_unobserved)))
+    return rc;
   char* base = (char*)d_ws;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
   SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
   const unsigned char* d_unobs = pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr;
-  {
+  rc = skel_dispatch_pt(PT, [&](auto pt) -> int {
+    constexpr int T = decltype(pt)::value;
     static PerDeviceOnce attr;
-    if (attr.first()) {
-      const int big_inv = 160 * 1024 - 1024;
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<16>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<32>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<48>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<64>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_inv));
-    }
-  }
-  switch (PT) {
-    case 16: hipLaunchKernelGGL(k_skel_selinv<16>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
-    case 32: hipLaunchKernelGGL(k_skel_selinv<32>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
-    case 48: hipLaunchKernelGGL(k_skel_selinv<48>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
-    default: hipLaunchKernelGGL(k_skel_selinv<64>, dim3(B), dim3(SKC_T), lds_inv, s, d_dev, d_clip, D(lay.band), D(lay.diag0)); break;
-  }
-  ACINO_LAUNCH_CHECK();
+    if (attr.first())
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          160 * 1024 - 1024));
+    hipLaunchKernelGGL(k_skel_selinv<T>, dim3(B), dim3(SKC_T), skel_factor_lds(T), s, d_dev, d_clip, D(lay.band), D(lay.diag0));
+    ACINO_LAUNCH_CHECK();
+    return ACINO_OK;
+  });
+  if (rc) return rc;
   if (d_cov_x) {
     hipLaunchKernelGGL(k_skel_cov_out, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_clip, D(lay.band), d_fxm, d_cov_x);
     ACINO_LAUNCH_CHECK();
@@ -674,19 +645,7 @@ int acino_skel_fte_covariance_pinned(const acino_skel_fte_params* p, int n_clips
                        d_std_pos, d_unobs);
     ACINO_LAUNCH_CHECK();
   }
-  std::vector<SkelClip> hc(B);
-  ACINO_HIP_CHECK(hipMemcpyAsync(hc.data(), d_clip, sizeof(SkelClip) * (size_t)B, hipMemcpyDeviceToHost, s));
-  ACINO_HIP_CHECK(hipStreamSynchronize(s));
-  bool numeric = false;
-  for (int b = 0; b < B; ++b) {
-    numeric = numeric || hc[b].status == 5;
-    if (h_status) h_status[b] = hc[b].status;
-  }
-  if (numeric && (B == 1 || !h_status)) {
-    set_error("pivot not above zero in the banded factorisation of the Fisher information (a state observed in no frame of the clip)");
-    return ACINO_ERR_NUMERIC;
-  }
-  return ACINO_OK;
+  return skel_cov_read_status(d_clip, B, s, h_status);
 }
 
 int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,

@@ -1,6 +1,8 @@
-// What the generic-skeleton kernels of skel_fte.hip (the solve) and skel_cov.hip (the covariance at an iterate) share: the
-// device-resident problem description, the controller state of a clip, the bound-active rule, the argument checks and the
-// host-side compilation of the link program into SkelDev.
+// What the generic-skeleton kernels share - skel_fte.hip (the solve), skel_cov.hip (covariance and observability at an iterate),
+// skel_sample.hip (joint samples) and skel_reproj.hip (the image-space report): the device-resident problem description, the
+// controller state of a clip, the bound-active rule, the link program's forward kinematics, the parameter checks and the
+// host-side compilation of the link program into SkelDev.  The host layer on top of it (entry checks, upload, dispatch,
+// read-back) is skel_host.hpp.
 #pragma once
 #include <cstddef>
 #include <cstring>

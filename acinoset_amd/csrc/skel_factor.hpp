@@ -5,7 +5,7 @@
 #include <algorithm>
 #include <cstddef>
 
-#include "skel_dev.hpp"
+#include "skel_host.hpp"
 
 namespace acino {
 
@@ -144,7 +144,7 @@ struct SkelCovLayout {
 };
 // observe: room for what k_skel_observability needs - a second SkelDev (the prior switched off) and the mask [n_clips][P]
 SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops, bool observe = false);
-// Validates the link program into h (which must live until the caller's synchronisation), uploads it and the cameras, clears
+// Validates the link program, uploads it and the cameras (skel_upload: nothing on the host has to outlive the call), clears
 // the clips' status words and launches k_skel_cov_assemble[_pinhole] and k_skel_cov_build on stream s: on return the
 // workspace holds band, fxm, diag0 and the link operators opv of every frame at d_x.
 // observe (the layout must have been made with it): first the Fisher assembly with the prior off and k_skel_observability;
@@ -153,6 +153,9 @@ SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops, 
 int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
                           const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
                           const double* d_lo, const double* d_hi, const double* d_x, void* d_ws, const SkelCovLayout& lay,
-                          SkelDev& h, hipStream_t s, bool observe = false, bool pin = false, uint8_t* d_unobserved = nullptr);
+                          hipStream_t s, bool observe = false, bool pin = false, uint8_t* d_unobserved = nullptr);
+// The end of both entries: skel_read_status with the Fisher matrix's error text, and the clips' status words to h_status[n_clips]
+// (may be NULL: then a singular clip fails the call whatever the batch).
+int skel_cov_read_status(const SkelClip* d_clip, int n_clips, hipStream_t s, int32_t* h_status);
 
 }  // namespace acino

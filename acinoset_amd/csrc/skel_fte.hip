@@ -27,7 +27,7 @@
 #include <cstring>
 #include <vector>
 
-#include "skel_dev.hpp"
+#include "skel_host.hpp"
 
 namespace acino {
 
@@ -798,16 +798,10 @@ k_skel_poses(const SkelDev* __restrict__ dev, const double* __restrict__ x, doub
 struct SkelLayout {
   size_t dev, clip, x[2], g[2], H[2], hd[2], cost[2], band, rhs, yv, delta, pred, step, gn, total;
 };
-static size_t sk_align(size_t v) { return (v + 255) / 256 * 256; }
 // (N: frames of ALL clips)
 static SkelLayout skel_layout(size_t N, int n_clips, int frames_per_clip, int P, int PT) {
   SkelLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = sk_align(off + bytes);
-    return o;
-  };
+  SkelTake take;
   L.dev = take(sizeof(SkelDev));
   L.clip = take(sizeof(SkelClip) * (size_t)n_clips);
   for (int k = 0; k < 2; ++k) L.x[k] = take(sizeof(double) * N * P);
@@ -823,7 +817,7 @@ static SkelLayout skel_layout(size_t N, int n_clips, int frames_per_clip, int P,
   L.pred = take(sizeof(double) * nt);
   L.step = take(sizeof(double) * nt);
   L.gn = take(sizeof(double) * N);
-  L.total = off;
+  L.total = take.off;
   return L;
 }
 
@@ -847,81 +841,48 @@ size_t acino_skel_fte_workspace_bytes(const acino_skel_fte_params* p) { return a
 static int skel_solve_batch(const acino_skel_fte_params* p, int n_clips, const acino_skel_op* h_ops, const int32_t* h_active,
                             const double* d_meas, const double* d_w, const double* d_cams, const double* d_lo, const double* d_hi,
                             double* d_x, double* d_pos, void* d_workspace, size_t workspace_bytes, acino_skel_fte_info* infos,
-                            void* stream, bool pinhole) {
-  int rc = skel_validate(p);
+                            void* stream, int camera_model) {
+  int rc = skel_check_batch(p, n_clips, true, camera_model,
+                            h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_workspace);
   if (rc) return rc;
-  ACINO_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips in 1..65535");
-  ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_workspace, "null buffer");
-  ACINO_REQUIRE(((uintptr_t)d_workspace & 255) == 0, "workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16;
   const size_t NT = (size_t)N * B;                           // frames of all clips
-  ACINO_REQUIRE(NT < (size_t)1 << 31, "n_clips * n_frames < 2^31");
   const SkelLayout lay = skel_layout(NT, B, N, P, PT);
-  ACINO_REQUIRE(workspace_bytes >= lay.total, "workspace too small (acino_skel_fte_workspace_bytes_batch)");
+  if ((rc = skel_check_workspace(d_workspace, workspace_bytes, lay.total, "acino_skel_fte_workspace_bytes_batch",
+                                 ACINO_ERR_INVALID_ARG)))
+    return rc;
   // ---- the program: active index of every op's parent angles, the ops on every pose's path
-  std::vector<SkelDev> hv(1);
-  SkelDev& h = hv[0];
+  SkelDev h;
   if ((rc = skel_program(p, h_ops, h_active, h))) return rc;
   char* base = (char*)d_workspace;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
   SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
-  ACINO_HIP_CHECK(hipMemcpyAsync(d_dev, &h, sizeof(SkelDev), hipMemcpyHostToDevice, s));
-  if (pinhole)
-    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, pins), d_cams,
-                                   sizeof(double) * ACINO_PINHOLE_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
-  else
-    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + offsetof(SkelDev, cams), d_cams,
-                                   sizeof(double) * ACINO_CAM_STRIDE * p->n_cams, hipMemcpyDeviceToDevice, s));
-  ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)B, s));
-  ACINO_HIP_CHECK(hipStreamSynchronize(s));                // (h lives on this frame)
+  if ((rc = skel_upload(h, d_cams, camera_model, d_dev, d_clip, B, s))) return rc;
   const size_t lds_asm = skel_assemble_lds(h.n_rows, P);
   const size_t lds_solve = sizeof(double) * ((size_t)4 * PT * (PT + 1) + 16 * PT);     // panel, ring, tv, the backward pass's partial sums
   static const bool solve_in_registers = getenv("ACINO_SKEL_OLD_SOLVE") == nullptr;     // (A/B switch: the round-5 kernel walks the band through memory)
+  const int big = 160 * 1024, big_solve = 160 * 1024 - 1024;   // (the solve kernel also has a few static words)
+  using AssembleKernel = decltype(&k_skel_assemble<true>);
+  const AssembleKernel assembly[2][2] = {{k_skel_assemble<true>, k_skel_assemble<false>},      // [camera model][without JAC]
+                                         {k_skel_assemble_pinhole<true>, k_skel_assemble_pinhole<false>}};
   {
     static PerDeviceOnce attr;
-    if (attr.first()) {
-      const int big = 160 * 1024, big_solve = 160 * 1024 - 1024;   // (the solve kernel also has a few static words)
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_assemble<true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_assemble<false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_assemble_pinhole<true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_assemble_pinhole<false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_solve<16>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_solve<32>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_solve<48>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_solve<64>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_solve2<16>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_solve2<32>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_solve2<48>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_solve2<64>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
-    }
+    if (attr.first())
+      for (const auto& model : assembly)
+        for (AssembleKernel k : model)
+          ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, big));
   }
   ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
+  const AssembleKernel k_assemble = skel_camera_kernel(camera_model, assembly[0][0], assembly[1][0]);
   const int n_trial = (int)(((size_t)N * P + 255) / 256);    // blocks per clip
   const int64_t n_el = (int64_t)NT * P;
   const double lam_max = p->lam_max > 0 ? p->lam_max : 1e16;
-  auto assemble = [&](int which) -> int {      // (the current iterate, which = 0, and the trial iterate, 1: the camera's twin)
-    if (pinhole)
-      hipLaunchKernelGGL(k_skel_assemble_pinhole<true>, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, which,
-                         D(lay.x[0]), D(lay.x[1]), d_meas, d_w, D(lay.H[0]), D(lay.H[1]), D(lay.g[0]), D(lay.g[1]), D(lay.hd[0]),
-                         D(lay.hd[1]), D(lay.cost[0]), D(lay.cost[1]));
-    else
-      hipLaunchKernelGGL(k_skel_assemble<true>, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, which, D(lay.x[0]),
-                         D(lay.x[1]), d_meas, d_w, D(lay.H[0]), D(lay.H[1]), D(lay.g[0]), D(lay.g[1]), D(lay.hd[0]), D(lay.hd[1]),
-                         D(lay.cost[0]), D(lay.cost[1]));
+  auto assemble = [&](int which) -> int {      // (the current iterate, which = 0, and the trial iterate, 1)
+    hipLaunchKernelGGL(k_assemble, dim3((unsigned)NT), dim3(256), lds_asm, s, d_dev, d_clip, which, D(lay.x[0]), D(lay.x[1]),
+                       d_meas, d_w, D(lay.H[0]), D(lay.H[1]), D(lay.g[0]), D(lay.g[1]), D(lay.hd[0]), D(lay.hd[1]),
+                       D(lay.cost[0]), D(lay.cost[1]));
     ACINO_LAUNCH_CHECK();
     return ACINO_OK;
   };
@@ -946,22 +907,22 @@ static int skel_solve_batch(const acino_skel_fte_params* p, int n_clips, const a
   std::vector<SkelClip> hc(B);
   for (int it = 1; it <= p->max_iter; ++it) {
     if ((rc = build(0))) return rc;
-    if (solve_in_registers && PT <= 48) {        // (PT = 64: window + operands exceed the 512 registers of a lane; the round-5 kernel)
-      switch (PT) {
-        case 16: hipLaunchKernelGGL(k_skel_solve2<16>, dim3(B), dim3(SK2_T), lds_solve, s, d_dev, d_clip, p->gtol, D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn)); break;
-        case 32: hipLaunchKernelGGL(k_skel_solve2<32>, dim3(B), dim3(SK2_T), lds_solve, s, d_dev, d_clip, p->gtol, D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn)); break;
-        case 48: hipLaunchKernelGGL(k_skel_solve2<48>, dim3(B), dim3(SK2_T), lds_solve, s, d_dev, d_clip, p->gtol, D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn)); break;
-        default: hipLaunchKernelGGL(k_skel_solve2<64>, dim3(B), dim3(SK2_T), lds_solve, s, d_dev, d_clip, p->gtol, D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn)); break;
-      }
-    } else {
-      switch (PT) {
-        case 16: hipLaunchKernelGGL(k_skel_solve<16>, dim3(B), dim3(SK_ST), lds_solve, s, d_dev, d_clip, p->gtol, D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn)); break;
-        case 32: hipLaunchKernelGGL(k_skel_solve<32>, dim3(B), dim3(SK_ST), lds_solve, s, d_dev, d_clip, p->gtol, D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn)); break;
-        case 48: hipLaunchKernelGGL(k_skel_solve<48>, dim3(B), dim3(SK_ST), lds_solve, s, d_dev, d_clip, p->gtol, D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn)); break;
-        default: hipLaunchKernelGGL(k_skel_solve<64>, dim3(B), dim3(SK_ST), lds_solve, s, d_dev, d_clip, p->gtol, D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn)); break;
-      }
-    }
-    ACINO_LAUNCH_CHECK();
+    rc = skel_dispatch_pt(PT, [&](auto pt) -> int {
+      constexpr int T = decltype(pt)::value;
+      using SolveKernel = decltype(&k_skel_solve<T>);
+      const SolveKernel solve[2] = {k_skel_solve<T>, k_skel_solve2<T>};
+      static PerDeviceOnce attr;
+      if (attr.first())
+        for (SolveKernel k : solve)
+          ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, big_solve));
+      // (PT = 64: window + operands exceed the 512 registers of a lane; the round-5 kernel)
+      const bool in_registers = solve_in_registers && T <= 48;
+      hipLaunchKernelGGL(solve[in_registers], dim3(B), dim3(in_registers ? SK2_T : SK_ST), lds_solve, s, d_dev, d_clip, p->gtol,
+                         D(lay.band), D(lay.rhs), D(lay.yv), D(lay.delta), D(lay.gn));
+      ACINO_LAUNCH_CHECK();
+      return ACINO_OK;
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(k_skel_trial, dim3(n_trial, B), dim3(256), 0, s, d_dev, d_clip, D(lay.x[0]), D(lay.x[1]), D(lay.g[0]),
                        D(lay.g[1]), D(lay.hd[0]), D(lay.hd[1]), d_lo, d_hi, D(lay.delta), D(lay.pred), D(lay.step));
     ACINO_LAUNCH_CHECK();
@@ -984,12 +945,13 @@ static int skel_solve_batch(const acino_skel_fte_params* p, int n_clips, const a
     hipLaunchKernelGGL(k_skel_poses, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, s, d_dev, d_x, d_pos, (int64_t)NT);
     ACINO_LAUNCH_CHECK();
   }
-  ACINO_HIP_CHECK(hipMemcpyAsync(hc.data(), d_clip, sizeof(SkelClip) * (size_t)B, hipMemcpyDeviceToHost, s));
-  ACINO_HIP_CHECK(hipStreamSynchronize(s));
-  bool numeric = false;
-  for (int b = 0; b < B; ++b) {
-    numeric = numeric || hc[b].status == 5;
-    if (infos) {
+  // One clip: the failure is the call's.  A batch: every clip's outcome is in infos[b].status (5 = numeric) and the results of
+  // the other clips stand - one degenerate window must not cost the caller the whole video; without infos there is nowhere to
+  // report it per clip, so the call fails as before.
+  rc = skel_read_status(d_clip, B, s, infos != nullptr,
+                        "non-positive pivot in the banded factorisation at every damping up to lam_max (system not positive definite)", hc);
+  if (infos && (rc == ACINO_OK || rc == ACINO_ERR_NUMERIC))
+    for (int b = 0; b < B; ++b) {
       infos[b].cost_initial = hc[b].cost0;
       infos[b].cost_final = hc[b].F;
       infos[b].gnorm_inf = hc[b].gnorm;
@@ -999,15 +961,7 @@ static int skel_solve_batch(const acino_skel_fte_params* p, int n_clips, const a
       infos[b].status = hc[b].status;
       infos[b].pad0 = 0;
     }
-  }
-  // One clip: the failure is the call's.  A batch: every clip's outcome is in infos[b].status (5 = numeric) and the results of
-  // the other clips stand - one degenerate window must not cost the caller the whole video; without infos there is nowhere to
-  // report it per clip, so the call fails as before.
-  if (numeric && (B == 1 || !infos)) {
-    set_error("non-positive pivot in the banded factorisation at every damping up to lam_max (system not positive definite)");
-    return ACINO_ERR_NUMERIC;
-  }
-  return ACINO_OK;
+  return rc;
 }
 
 int acino_skel_fte_solve_batch(const acino_skel_fte_params* p, int n_clips, const acino_skel_op* h_ops, const int32_t* h_active,
@@ -1015,7 +969,7 @@ int acino_skel_fte_solve_batch(const acino_skel_fte_params* p, int n_clips, cons
                                const double* d_hi, double* d_x, double* d_pos, void* d_workspace, size_t workspace_bytes,
                                acino_skel_fte_info* infos, void* stream) {
   return skel_solve_batch(p, n_clips, h_ops, h_active, d_meas, d_w, d_cams24, d_lo, d_hi, d_x, d_pos, d_workspace, workspace_bytes,
-                          infos, stream, false);
+                          infos, stream, 0);
 }
 
 int acino_skel_fte_solve_batch_pinhole(const acino_skel_fte_params* p, int n_clips, const acino_skel_op* h_ops,
@@ -1023,7 +977,7 @@ int acino_skel_fte_solve_batch_pinhole(const acino_skel_fte_params* p, int n_cli
                                        const double* d_lo, const double* d_hi, double* d_x, double* d_pos, void* d_workspace,
                                        size_t workspace_bytes, acino_skel_fte_info* infos, void* stream) {
   return skel_solve_batch(p, n_clips, h_ops, h_active, d_meas, d_w, d_cams32, d_lo, d_hi, d_x, d_pos, d_workspace, workspace_bytes,
-                          infos, stream, true);
+                          infos, stream, 1);
 }
 
 int acino_skel_fte_solve(const acino_skel_fte_params* p, const acino_skel_op* h_ops, const int32_t* h_active,

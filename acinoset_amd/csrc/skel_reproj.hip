@@ -15,7 +15,7 @@
 // atomics.  LDS: SKR_FPB * (64 * 3 + 65 * 3) doubles = 24.2 KB whatever the skeleton (six workgroups per CU by LDS; the
 // register count decides).  A streaming kernel: 24 B of detection and weight and the slot's 72 B of cov_pos (shared by the C
 // cameras through the cache) in, up to 81 B out per entry, a few hundred fp64 operations with one atan in between.
-#include "skel_dev.hpp"
+#include "skel_host.hpp"
 
 namespace acino {
 
@@ -165,34 +165,25 @@ int acino_skel_fte_reprojection(const acino_skel_fte_params* p, int n_clips, int
                                 const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
                                 const double* d_x, const double* d_cov_pos, double gate_w, double* d_uv, double* d_cov_uv,
                                 double* d_res, double* d_mahal2, uint8_t* d_flags, void* stream) {
-  int rc = skel_validate(p);
+  int rc = skel_check_batch(p, n_clips, false, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_x);
   if (rc) return rc;
-  ACINO_REQUIRE(n_clips >= 1, "n_clips >= 1");
-  ACINO_REQUIRE(camera_model == 0 || camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
   ACINO_REQUIRE(gate_w > 0 && gate_w <= 1.79769313486231570e308, "gate_w > 0 and finite");
-  ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_x, "null buffer");
   ACINO_REQUIRE(d_uv || d_cov_uv || d_res || d_mahal2 || d_flags, "no output: at least one of d_uv, d_cov_uv, d_res, d_mahal2, d_flags");
   ACINO_REQUIRE(!d_cov_uv || d_cov_pos, "d_cov_uv needs d_cov_pos");
   const long long NT = (long long)p->n_frames * n_clips;      // frames of all clips
-  ACINO_REQUIRE(NT < (1ll << 31), "n_clips * n_frames < 2^31");
-  std::vector<SkelDev> hv(1);                                // (the host half of the record: the checks of skel_program)
-  if ((rc = skel_program(p, h_ops, h_active, hv[0]))) return rc;
+  SkelDev h;                                                 // (the host half of the record: the checks of skel_program)
+  if ((rc = skel_program(p, h_ops, h_active, h))) return rc;
   SkelReprojArgs a;
   memset(&a, 0, sizeof(a));
   a.n_cams = p->n_cams;
   a.n_pose = p->n_pose;
   a.n_ops = p->n_ops;
   a.n_act = p->n_active;
-  memcpy(a.op, hv[0].op, sizeof(a.op));
-  memcpy(a.amap, hv[0].amap, sizeof(a.amap));
+  memcpy(a.op, h.op, sizeof(a.op));
+  memcpy(a.amap, h.amap, sizeof(a.amap));
   const unsigned nb = (unsigned)((NT + SKR_FPB - 1) / SKR_FPB);
-  hipStream_t s = (hipStream_t)stream;
-  if (camera_model == 1)
-    hipLaunchKernelGGL(k_skel_reproj<true>, dim3(nb), dim3(256), 0, s, a, NT, d_meas, d_w, d_cams, d_x, d_cov_pos, gate_w, d_uv,
-                       d_cov_uv, d_res, d_mahal2, d_flags);
-  else
-    hipLaunchKernelGGL(k_skel_reproj<false>, dim3(nb), dim3(256), 0, s, a, NT, d_meas, d_w, d_cams, d_x, d_cov_pos, gate_w, d_uv,
-                       d_cov_uv, d_res, d_mahal2, d_flags);
+  hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_reproj<false>, k_skel_reproj<true>), dim3(nb), dim3(256), 0,
+                     (hipStream_t)stream, a, NT, d_meas, d_w, d_cams, d_x, d_cov_pos, gate_w, d_uv, d_cov_uv, d_res, d_mahal2, d_flags);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }

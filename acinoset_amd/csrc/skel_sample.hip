@@ -246,17 +246,13 @@ int acino_skel_fte_sample_pinned(const acino_skel_fte_params* p, int n_clips, in
                           const double* d_lo, const double* d_hi, const double* d_x, int64_t n_samples, const double* d_z,
                           double* d_x_samples, double* d_pos_samples, int32_t* h_status, void* d_ws, size_t ws_bytes,
                           void* stream, int pin_unobserved, uint8_t* d_unobserved) {
-  int rc = skel_validate(p);
+  int rc = skel_check_batch(p, n_clips, true, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws);
   if (rc) return rc;
-  ACINO_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips in 1..65535");
-  ACINO_REQUIRE(camera_model == 0 || camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
   ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
   ACINO_REQUIRE(n_samples >= 1, "n_samples >= 1");
   ACINO_REQUIRE(d_z && d_x_samples, "d_z and d_x_samples must not be NULL");
-  ACINO_REQUIRE(h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws, "null buffer");
   const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16;
   const size_t NT = (size_t)N * B;                           // frames of all clips
-  ACINO_REQUIRE(NT < (size_t)1 << 31, "n_clips * n_frames < 2^31");
   ACINO_REQUIRE((uint64_t)n_samples <= (((uint64_t)1 << 31) - 1) * SKS_PANEL, "n_samples: too many sample panels for one launch");
   ACINO_REQUIRE((double)NT * (double)n_samples * (double)std::max(P, 3 * p->n_pose) < 9e18 / sizeof(double), "samples array too large");
   const size_t rows = NT * (size_t)n_samples, z_bytes = sizeof(double) * rows * P;
@@ -265,50 +261,29 @@ int acino_skel_fte_sample_pinned(const acino_skel_fte_params* p, int n_clips, in
                 "d_z overlaps d_pos_samples");
   const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
   const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
-  if (((uintptr_t)d_ws & 255) != 0) {
-    set_error("workspace must be 256-byte aligned");
-    return ACINO_ERR_WORKSPACE;
-  }
-  if (ws_bytes < lay.total) {
-    set_error(observe ? "workspace too small (acino_skel_fte_sample_pinned_workspace_bytes)"
-                      : "workspace too small (acino_skel_fte_sample_workspace_bytes)");
-    return ACINO_ERR_WORKSPACE;
-  }
-  std::vector<SkelDev> hv(1);                                // (lives until the one synchronisation at the end)
+  if ((rc = skel_check_workspace(d_ws, ws_bytes, lay.total,
+                                 observe ? "acino_skel_fte_sample_pinned_workspace_bytes" : "acino_skel_fte_sample_workspace_bytes",
+                                 ACINO_ERR_WORKSPACE)))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, hv[0], s,
-                                  observe, pin, d_unobserved)))
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
+                                  d_unobserved)))
     return rc;
   char* base = (char*)d_ws;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
   SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
-  switch (PT) {
-    case 16: rc = skel_sample_launch<16>(B, n_samples, d_dev, d_clip, D(lay.band), D(lay.diag0), d_fxm, d_x, d_z, d_x_samples, s); break;
-    case 32: rc = skel_sample_launch<32>(B, n_samples, d_dev, d_clip, D(lay.band), D(lay.diag0), d_fxm, d_x, d_z, d_x_samples, s); break;
-    case 48: rc = skel_sample_launch<48>(B, n_samples, d_dev, d_clip, D(lay.band), D(lay.diag0), d_fxm, d_x, d_z, d_x_samples, s); break;
-    default: rc = skel_sample_launch<64>(B, n_samples, d_dev, d_clip, D(lay.band), D(lay.diag0), d_fxm, d_x, d_z, d_x_samples, s); break;
-  }
+  rc = skel_dispatch_pt(PT, [&](auto pt) {
+    return skel_sample_launch<decltype(pt)::value>(B, n_samples, d_dev, d_clip, D(lay.band), D(lay.diag0), d_fxm, d_x, d_z, d_x_samples, s);
+  });
   if (rc) return rc;
   if (d_pos_samples) {
     hipLaunchKernelGGL(k_skel_sample_fk, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_dev, d_clip, d_x_samples,
                        d_pos_samples, (long long)n_samples, (long long)rows);
     ACINO_LAUNCH_CHECK();
   }
-  std::vector<SkelClip> hc(B);
-  ACINO_HIP_CHECK(hipMemcpyAsync(hc.data(), d_clip, sizeof(SkelClip) * (size_t)B, hipMemcpyDeviceToHost, s));
-  ACINO_HIP_CHECK(hipStreamSynchronize(s));
-  bool numeric = false;
-  for (int b = 0; b < B; ++b) {
-    numeric = numeric || hc[b].status == 5;
-    if (h_status) h_status[b] = hc[b].status;
-  }
-  if (numeric && (B == 1 || !h_status)) {
-    set_error("pivot not above zero in the banded factorisation of the Fisher information (a state observed in no frame of the clip)");
-    return ACINO_ERR_NUMERIC;
-  }
-  return ACINO_OK;
+  return skel_cov_read_status(d_clip, B, s, h_status);
 }
 
 int acino_skel_fte_sample(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,

@@ -46,6 +46,23 @@ def generic_skeleton(sk, extra=0):
     return sk
 
 
+# Connected sub-trees of the skeleton (root "chin" included) whose leaves all carry detections, by the padded size PT of their
+# active states (3 + 3 per part that is a parent): the solve, covariance and sampler kernels are templates on PT = 16, 32, 48, 64,
+# and the full skeleton (PT 48) and ``extra=5`` (PT 64) reach only two of them.
+SUB_TREES = {16: ("chin", "forehead", "neck", "shoulder1", "shoulder2", "elbow1"),                          # 15 active states
+             32: ("chin", "forehead", "neck", "shoulder1", "shoulder2", "elbow1", "elbow2", "wrist1", "wrist2")}     # 24
+
+
+def sub_skeleton(sk, keep):
+    """``sk`` cut down to the parts ``keep``.  A part whose only children are left out or carry no detection would keep angles
+    that no pixel observes: ``keep`` must be a connected sub-tree that ends in detected parts (``assert_observed`` checks it)."""
+    keep = set(keep)
+    return dict(links=[list(l) for l in sk["links"] if l[0] in keep and l[1] in keep],
+                dofs={k: list(v) for k, v in sk["dofs"].items() if k in keep},
+                positions={k: list(v) for k, v in sk["positions"].items() if k in keep},
+                markers=[m for m in sk["markers"] if m in keep])
+
+
 def with_extra_detections(det, parts, extra):
     """The detection table with ``extra`` more body parts "extra0" .. (copies of the first columns: the Fisher matrix reads the
     weights, not the pixel values)."""

@@ -107,3 +107,19 @@ def test_python_argument_checks_come_before_the_gpu(fx, refs):
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match="GPU"):
             build.model_covariance([model], [x])
+
+
+@pytest.mark.parametrize("name", ["pt16", "pt16b", "pt16pin", "pt32"])
+def test_sub_tree_inputs_have_the_size_they_are_for_and_the_references_accept_them(golden_dir, name):
+    """The inputs of tests/test_gpu_skel_pt.py, on the CPU: PT as named, every active state observed (``case`` asserts it), and
+    both references' own disagreement below the 1e-8 at which their bars refuse an input."""
+    import skel_sample_cases as scases
+    import skel_sample_ref as sref
+    c = scases.case(golden_dir, name)
+    pt = scases.SUB_TREE_CASES[name][0]
+    n_act = len(c["model"].active)
+    assert {16: 4 <= n_act <= 16, 32: 17 <= n_act <= 32}[pt] and c["model"].N == 12 and c["fixed"].shape == (12, n_act)
+    xa = c["x"][:, c["prob"].ACT]
+    ref.bar(ref.reference(c["prob"], xa)["d0"])                 # (asserts d0 <= 1e-8)
+    z = scases.normal_z(c, 3)
+    assert sref.map_err(sref.banded_map(c["ab"], c["fixed"], z), sref.dense_map(c["ab"], c["fixed"], z)) <= sref.D0_REFUSED
