@@ -315,12 +315,18 @@ def _unobserved_lists(mask, act):
     return [[int(a) for a in np.asarray(act)[np.nonzero(row)[0]]] for row in mh]
 
 
+RATE_KEYS = ("cov_dx", "cov_ddx", "std_dx", "std_ddx", "cov_vel", "std_vel")
+
+
 def _covariance(models, xs, l1_eps, want, raise_numeric=True, pin_unobserved=False):
-    """model_covariance with the outputs chosen by name (``want``: a subset of cov_x, cov_pos, std_pos).  ``raise_numeric=False``:
-    a singular single clip is reported in its ``status`` like a clip of a batch.  ``pin_unobserved``: the _pinned entry, and
-    ``unobserved`` in every dict."""
+    """model_covariance with the outputs chosen by name (``want``: a subset of cov_x, cov_pos, std_pos and of RATE_KEYS).
+    ``raise_numeric=False``: a singular single clip is reported in its ``status`` like a clip of a batch.  ``pin_unobserved``: the
+    _pinned entry, and ``unobserved`` in every dict.  Any of RATE_KEYS in ``want``: acino_skel_fte_covariance_rates (one
+    factorisation for everything); without them the entries and their arguments are what they were."""
     pin = bool(pin_unobserved)
-    io_ = _skel_inputs(models, xs, (lambda p, B: lib().acino_skel_fte_covariance_pinned_workspace_bytes(C.byref(p), B, 1)) if pin else
+    rates = any(k in want for k in RATE_KEYS)
+    io_ = _skel_inputs(models, xs, (lambda p, B: lib().acino_skel_fte_covariance_rates_workspace_bytes(C.byref(p), B, int(pin))) if rates else
+                       (lambda p, B: lib().acino_skel_fte_covariance_pinned_workspace_bytes(C.byref(p), B, 1)) if pin else
                        (lambda p, B: lib().acino_skel_fte_covariance_workspace_bytes(C.byref(p), B)), l1_eps=l1_eps)
     m0, act, dev = models[0], io_["act"], io_["dev"]
     B, N, P = len(models), m0.N, m0.P
@@ -330,8 +336,16 @@ def _covariance(models, xs, l1_eps, want, raise_numeric=True, pin_unobserved=Fal
     cov_pos = empty(B, N, Lp, 3, 3) if "cov_pos" in want else None
     std_pos = empty(B, N, Lp) if "std_pos" in want else None
     status = (C.c_int32 * B)()
-    if pin:
-        mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev)
+    need_dx, need_ddx = "cov_dx" in want or "std_dx" in want, "cov_ddx" in want or "std_ddx" in want
+    cov_dx = empty(B, N, Pa, Pa) if need_dx else None
+    cov_ddx = empty(B, N, Pa, Pa) if need_ddx else None
+    cov_vel = empty(B, N, Lp, 3, 3) if "cov_vel" in want else None
+    std_vel = empty(B, N, Lp) if "std_vel" in want else None
+    mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev) if pin else None
+    if rates:
+        rc = lib().acino_skel_fte_covariance_rates(*io_["head"], ptr(cov_x), ptr(cov_pos), ptr(std_pos), ptr(cov_dx), ptr(cov_ddx),
+                                                   ptr(cov_vel), ptr(std_vel), status, *io_["tail"], int(pin), ptr(mask))
+    elif pin:
         rc = lib().acino_skel_fte_covariance_pinned(*io_["head"], ptr(cov_x), ptr(cov_pos), ptr(std_pos), status, *io_["tail"], 1,
                                                     ptr(mask))
     else:
@@ -342,18 +356,27 @@ def _covariance(models, xs, l1_eps, want, raise_numeric=True, pin_unobserved=Fal
     if pin:
         for o, un in zip(out, _unobserved_lists(mask, act)):
             o["unobserved"] = un
-    if cov_x is not None:
-        ch = cov_x.cpu().numpy()
+    for key, std_key, arr in (("cov_x", None, cov_x), ("cov_dx", "std_dx", cov_dx), ("cov_ddx", "std_ddx", cov_ddx)):
+        if arr is None:
+            continue
+        if key not in want:                                   # the bars alone: only the diagonals leave the device
+            dg = arr.diagonal(dim1=-2, dim2=-1).contiguous().cpu().numpy()
+            for i in range(B):
+                out[i][std_key] = np.zeros((N, P))
+                out[i][std_key][:, act] = np.sqrt(np.maximum(dg[i], 0.0))
+            continue
+        ch = arr.cpu().numpy()
         for i in range(B):
             full = np.zeros((N, P, P))
             full[:, act[:, None], act[None, :]] = ch[i]
-            out[i]["cov_x"] = full
-    if cov_pos is not None:
-        for i, c in enumerate(cov_pos.cpu().numpy()):
-            out[i]["cov_pos"] = c
-    if std_pos is not None:
-        for i, c in enumerate(std_pos.cpu().numpy()):
-            out[i]["std_pos"] = c
+            if key in want:
+                out[i][key] = full
+            if std_key is not None and std_key in want:
+                out[i][std_key] = np.sqrt(np.maximum(np.einsum("npp->np", full), 0.0))
+    for key, arr in (("cov_pos", cov_pos), ("std_pos", std_pos), ("cov_vel", cov_vel), ("std_vel", std_vel)):
+        if arr is not None:
+            for i, c in enumerate(arr.cpu().numpy()):
+                out[i][key] = c
     return out
 
 
@@ -384,7 +407,7 @@ def model_observability(models, xs, l1_eps=1e-2):
     return out
 
 
-def model_covariance(models, xs, std_only=False, l1_eps=1e-2, pin_unobserved=False):
+def model_covariance(models, xs, std_only=False, l1_eps=1e-2, pin_unobserved=False, rates=False):
     """Error bars of the skeleton solve at the iterates ``xs`` (one [N, P] array per model, the layout of ``results["x"]``;
     normally the solutions): acino_skel_fte_covariance, all models in one batched call (one workgroup per clip).  Returns one
     dict per model: ``cov_x`` [N, P, P] - the frame's diagonal block of A^-1 in the full-state layout, zero rows and columns
@@ -405,9 +428,23 @@ def model_covariance(models, xs, std_only=False, l1_eps=1e-2, pin_unobserved=Fal
     Jacobian in that column - the hand of an arm no camera detected) has ``std_pos`` = +inf and NaN ``cov_pos``; every other slot
     is G cov_x G^T as before; on the shipped skeleton no pose depends on the two psi states and every bar is finite.  The
     factorisation still decides: a state seen in one or two frames is not pinned and the clip stays status 5
-    (``model_observability``'s ``n_seen`` says which).  The default keeps the definition above unchanged."""
-    return _covariance(models, xs, l1_eps, ("std_pos",) if std_only else ("cov_x", "cov_pos", "std_pos"),
-                       pin_unobserved=pin_unobserved)
+    (``model_observability``'s ``n_seen`` says which).  The default keeps the definition above unchanged.
+
+    ``rates=True`` (acino_skel_fte_covariance_rates: the same factorisation, one more streaming kernel): every dict gains the
+    error bars of what a solve returns beside ``x`` - ``cov_dx`` and ``cov_ddx`` [N, P, P] in the full-state layout (zero outside
+    ``model.active``; (unit/s)^2 and (unit/s^2)^2), ``std_dx`` and ``std_ddx`` [N, P], the square roots of their diagonals - and of
+    the pose velocities (pose_l(x_n) - pose_l(x_n-1)) / h, frame 0 repeating frame 1: ``cov_vel`` [N, n_pose, 3, 3] in (m/s)^2
+    and ``std_vel`` [N, n_pose] in m/s.  dx and ddx are exactly ``_finite_diff_states``' (the start-up rows included; N = 2:
+    dx_0 = 0, ddx = 0).  sqrt(2 diag cov_x) / h is NOT that bar: the smoothness prior correlates neighbouring frames almost
+    perfectly, and the exact answer uses the cross-frame blocks of A^-1 inside the 3-frame window.  Pinned variables contribute
+    nothing from the frame they are pinned in; with ``pin_unobserved`` the rows and columns of the unobserved states are 0 and
+    a pose that depends on one in either frame has ``std_vel`` = +inf and NaN ``cov_vel``; a singular clip has NaN everywhere.
+    With ``std_only`` only ``std_dx``, ``std_ddx`` and ``std_vel`` are added, and only the diagonals of cov_dx and cov_ddx leave the
+    device."""
+    want = ("std_pos",) if std_only else ("cov_x", "cov_pos", "std_pos")
+    if rates:
+        want += ("std_dx", "std_ddx", "std_vel") if std_only else RATE_KEYS
+    return _covariance(models, xs, l1_eps, want, pin_unobserved=pin_unobserved)
 
 
 def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1_eps=1e-2, pin_unobserved=False):
@@ -580,7 +617,8 @@ def detection_report(reproj, gate=None):
 
 
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
-                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False):
+                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
+                 return_rate_cov=False):
     """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
@@ -595,7 +633,10 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     is passed on, without it the report runs with ``cov=False`` (``cov_uv`` and ``std_uv`` are None).
     ``pin_unobserved``: passed to ``model_covariance`` / ``model_samples`` (it acts only together with ``return_cov`` or
     ``n_samples``, and through ``return_cov`` on the report; the solve itself never changes); ``results`` then carries
-    ``unobserved``.  ``pos_samples`` of a pose that depends on an unobserved state show no spread from it."""
+    ``unobserved``.  ``pos_samples`` of a pose that depends on an unobserved state show no spread from it.
+    ``return_rate_cov``: the six arrays of ``model_covariance(rates=True)`` (``cov_dx``, ``cov_ddx``, ``std_dx``, ``std_ddx``,
+    ``cov_vel``, ``std_vel`` - the bars of the returned ``dx`` / ``ddx`` and of the pose velocities) join every ``results``; with
+    ``return_cov`` both come from one call and one factorisation."""
     xs = [np.array(m.init_x if x0 is None or x0[i] is None else x0[i], dtype=np.float64, copy=True) for i, m in enumerate(models)]
     io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_workspace_bytes_batch(C.byref(p), B), start=True, max_iter=max_iter,
                        lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol, l1_eps=l1_eps, lam_max=lam_max)
@@ -614,9 +655,9 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
         out.append((dict(positions=ph[i], x=xf, dx=dx, ddx=ddx), infos[i].as_dict()))
     io_ = None                                              # (the workspace goes before the next call asks for its own)
     xs_out = [r["x"] for r, _i in out]
-    if return_cov:
-        _attach(out, _covariance(models, xs_out, l1_eps, ("cov_x", "cov_pos", "std_pos"), pin_unobserved=pin_unobserved),
-                ("cov_x", "cov_pos", "std_pos", "unobserved"))
+    if return_cov or return_rate_cov:
+        keys = (("cov_x", "cov_pos", "std_pos") if return_cov else ()) + (RATE_KEYS if return_rate_cov else ())
+        _attach(out, _covariance(models, xs_out, l1_eps, keys, pin_unobserved=pin_unobserved), keys + ("unobserved",))
     if n_samples:
         _attach(out, model_samples(models, xs_out, n_samples=n_samples, seed=sample_seed, l1_eps=l1_eps, pin_unobserved=pin_unobserved),
                 ("x_samples", "pos_samples", "unobserved"))
@@ -627,17 +668,20 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
 
 
 def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
-                return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False):
+                return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
+                return_rate_cov=False):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
     failure is the call's).  ``return_cov``: ``cov_x`` / ``cov_pos`` / ``std_pos`` at the returned ``x`` (``model_covariance``)
     join ``results``; ``n_samples`` > 0: ``x_samples`` / ``pos_samples`` (``model_samples`` with ``seed=sample_seed``) do;
     ``return_reprojection``: the six arrays of ``model_reprojection`` do (``cov_uv`` / ``std_uv`` None without ``return_cov``).
-    ``pin_unobserved``: as ``solve_models`` (only together with ``return_cov`` or ``n_samples``; ``results["unobserved"]``)."""
+    ``pin_unobserved``: as ``solve_models`` (only together with ``return_cov`` or ``n_samples``; ``results["unobserved"]``).
+    ``return_rate_cov``: the bars of ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``) join ``results``."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
                         l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed,
-                        return_reprojection=return_reprojection, pin_unobserved=pin_unobserved)[0]
+                        return_reprojection=return_reprojection, pin_unobserved=pin_unobserved,
+                        return_rate_cov=return_rate_cov)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -724,7 +768,7 @@ def window_residual_px(model, info):
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
                 overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, pin_unobserved=False,
-                **kw):
+                return_rate_cov=False, **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -766,6 +810,12 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     quantile with 2 degrees of freedom, e.g. 9.21; needs ``return_reprojection``) also ``outlier_frames``: the frames, relative to
     first_frame, in which any weighted detection lies outside ``mahal2 <= gate``.  A per-frame report of a stitched trajectory is
     sound where joint samples are not: every frame's pixels, residuals and bars are those of the window that supplied it.
+
+    ``return_rate_cov``: ONE batched ``model_covariance(rates=True)`` call over all windows (the same call as ``return_cov``'s when
+    both are set); ``results`` gains ``std_dx``, ``std_ddx`` [frames, P], ``cov_dx``, ``cov_ddx`` [frames, P, P], ``std_vel``
+    [frames, n_pose] and ``cov_vel`` [frames, n_pose, 3, 3], every frame from the window that supplied its ``dx`` and ``ddx`` (the
+    same depth rule: the bars are those of the window's own differences, never of a difference across a seam); ``cov_status``,
+    ``cov_singular_windows``, ``owner`` and ``cov_unobserved`` as with ``return_cov``.
 
     There is no ``n_samples`` here: a stitched video is not one posterior (every window has its own, and draws of neighbouring
     windows are independent); call ``model_samples`` on the windows' models."""
@@ -866,16 +916,19 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
         infos.append(info)
     seams = [int(n) for n in np.nonzero(np.diff(owner) != 0)[0] + 1]
     results = dict(positions=pos, x=x, dx=dx, ddx=ddx, start_frame=f0, seams=seams)
-    if return_cov:
-        covs = _covariance(models, [res["x"] for res, _info in solved], kw.get("l1_eps", 1e-2), ("cov_pos", "std_pos"),
+    if return_cov or return_rate_cov:
+        keys = (("cov_pos", "std_pos") if return_cov else ()) + (RATE_KEYS if return_rate_cov else ())
+        covs = _covariance(models, [res["x"] for res, _info in solved], kw.get("l1_eps", 1e-2), keys,
                            raise_numeric=False, pin_unobserved=pin_unobserved)
-        std_pos, cov_pos = np.full((total, Lp), np.nan), np.full((total, Lp, 3, 3), np.nan)
+        stitched = {k: np.full((total,) + covs[0][k].shape[1:], np.nan) for k in keys}
         for w_i, (st, cv) in enumerate(zip(starts, covs)):
             mine = np.nonzero(owner == w_i)[0]
-            std_pos[mine], cov_pos[mine] = cv["std_pos"][mine - (st - f0)], cv["cov_pos"][mine - (st - f0)]
+            for k in keys:
+                stitched[k][mine] = cv[k][mine - (st - f0)]
             infos[w_i]["cov_status"] = cv["status"]
-        results.update(std_pos=std_pos, cov_pos=cov_pos, owner=owner.copy(), window_std_pos=[cv["std_pos"] for cv in covs],
-                       cov_singular_windows=[i for i, cv in enumerate(covs) if cv["status"] == 5])
+        results.update(stitched, owner=owner.copy(), cov_singular_windows=[i for i, cv in enumerate(covs) if cv["status"] == 5])
+        if return_cov:
+            results["window_std_pos"] = [cv["std_pos"] for cv in covs]
         if pin_unobserved:
             results["cov_unobserved"] = [cv["unobserved"] for cv in covs]
     if return_reprojection:
@@ -915,7 +968,8 @@ def solve_optimisation(model, exe_path=None, project_dir=None, poses=None, **sol
     """build.py:306-335: solve, then save ``data/results/traj_results.pickle`` under ``project_dir`` (when given).
     ``exe_path`` named the IPOPT executable; there is none here.  ``return_cov=True`` (a ``solve_model`` keyword) adds the
     covariance arrays to the returned ``results``, ``n_samples=S`` (with ``sample_seed``) the posterior samples,
-    ``return_reprojection=True`` the image-space report of ``model_reprojection``, ``pin_unobserved=True`` pins the unobserved
+    ``return_reprojection=True`` the image-space report of ``model_reprojection``, ``return_rate_cov=True`` the error bars of
+    ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``), ``pin_unobserved=True`` pins the unobserved
     states in those (``results["unobserved"]``); the saved pickle keeps the reference's four entries."""
     results, info = solve_model(model, **solver_kw)
     model.x, model.info = results, info

@@ -552,6 +552,71 @@ static bool skc_limits(const acino_skel_fte_params* p, int n_clips) {
          p->n_ops <= ACINO_SKEL_MAX_OPS;
 }
 
+// The body of the covariance entries: one factorisation and recursion, then the output kernels the caller asked for.  rates:
+// NULL (the entries without rates: the launches are what they were), or the four rate outputs of k_skel_cov_rates.
+struct SkelRateOut {
+  double *cov_dx, *cov_ddx, *cov_vel, *std_vel;
+};
+static int skc_covariance(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                          const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                          const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x, double* d_cov_pos,
+                          double* d_std_pos, const SkelRateOut* rates, int32_t* h_status, void* d_ws, size_t ws_bytes, void* stream,
+                          int pin_unobserved, uint8_t* d_unobserved) {
+  int rc = skel_check_batch(p, n_clips, true, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws);
+  if (rc) return rc;
+  ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
+  if (rates)
+    ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos || rates->cov_dx || rates->cov_ddx || rates->cov_vel || rates->std_vel,
+                  "at least one of d_cov_x, d_cov_pos, d_std_pos, d_cov_dx, d_cov_ddx, d_cov_vel, d_std_vel");
+  else
+    ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos, "at least one of d_cov_x, d_cov_pos, d_std_pos");
+  const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16;
+  const size_t NT = (size_t)N * B;                           // frames of all clips
+  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
+  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
+  if ((rc = skel_check_workspace(d_ws, ws_bytes, lay.total,
+                                 rates ? "acino_skel_fte_covariance_rates_workspace_bytes"
+                                 : observe ? "acino_skel_fte_covariance_pinned_workspace_bytes" : "acino_skel_fte_covariance_workspace_bytes",
+                                 ACINO_ERR_WORKSPACE)))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
+                                  d_unobserved)))
+    return rc;
+  char* base = (char*)d_ws;
+  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
+  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
+  unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
+  const unsigned char* d_unobs = pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr;
+  rc = skel_dispatch_pt(PT, [&](auto pt) -> int {
+    constexpr int T = decltype(pt)::value;
+    static PerDeviceOnce attr;
+    if (attr.first())
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          160 * 1024 - 1024));
+    hipLaunchKernelGGL(k_skel_selinv<T>, dim3(B), dim3(SKC_T), skel_factor_lds(T), s, d_dev, d_clip, D(lay.band), D(lay.diag0));
+    ACINO_LAUNCH_CHECK();
+    return ACINO_OK;
+  });
+  if (rc) return rc;
+  if (d_cov_x) {
+    hipLaunchKernelGGL(k_skel_cov_out, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_clip, D(lay.band), d_fxm, d_cov_x);
+    ACINO_LAUNCH_CHECK();
+  }
+  if (d_cov_pos || d_std_pos) {
+    hipLaunchKernelGGL(k_skel_cov_pose, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_clip, D(lay.band), d_fxm, D(lay.opv), d_cov_pos,
+                       d_std_pos, d_unobs);
+    ACINO_LAUNCH_CHECK();
+  }
+  if (rates && (rates->cov_dx || rates->cov_ddx || rates->cov_vel || rates->std_vel) &&
+      (rc = skel_cov_launch_rates(NT, P, d_dev, d_clip, D(lay.band), d_fxm, D(lay.opv), d_unobs, p->h, rates->cov_dx, rates->cov_ddx,
+                                  rates->cov_vel, rates->std_vel, s)))
+    return rc;
+  return skel_cov_read_status(d_clip, B, s, h_status);
+}
+
+
 extern "C" {
 
 size_t acino_skel_fte_covariance_workspace_bytes(const acino_skel_fte_params* p, int n_clips) {
@@ -603,49 +668,23 @@ int acino_skel_fte_covariance_pinned(const acino_skel_fte_params* p, int n_clips
                                      const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x,
                                      double* d_cov_pos, double* d_std_pos, int32_t* h_status, void* d_ws, size_t ws_bytes,
                                      void* stream, int pin_unobserved, uint8_t* d_unobserved) {
-  int rc = skel_check_batch(p, n_clips, true, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws);
-  if (rc) return rc;
-  ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
-  ACINO_REQUIRE(d_cov_x || d_cov_pos || d_std_pos, "at least one of d_cov_x, d_cov_pos, d_std_pos");
-  const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16;
-  const size_t NT = (size_t)N * B;                           // frames of all clips
-  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
-  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
-  if ((rc = skel_check_workspace(d_ws, ws_bytes, lay.total,
-                                 observe ? "acino_skel_fte_covariance_pinned_workspace_bytes" : "acino_skel_fte_covariance_workspace_bytes",
-                                 ACINO_ERR_WORKSPACE)))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
-                                  d_unobserved)))
-    return rc;
-  char* base = (char*)d_ws;
-  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
-  SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
-  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
-  unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
-  const unsigned char* d_unobs = pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr;
-  rc = skel_dispatch_pt(PT, [&](auto pt) -> int {
-    constexpr int T = decltype(pt)::value;
-    static PerDeviceOnce attr;
-    if (attr.first())
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_selinv<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          160 * 1024 - 1024));
-    hipLaunchKernelGGL(k_skel_selinv<T>, dim3(B), dim3(SKC_T), skel_factor_lds(T), s, d_dev, d_clip, D(lay.band), D(lay.diag0));
-    ACINO_LAUNCH_CHECK();
-    return ACINO_OK;
-  });
-  if (rc) return rc;
-  if (d_cov_x) {
-    hipLaunchKernelGGL(k_skel_cov_out, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_clip, D(lay.band), d_fxm, d_cov_x);
-    ACINO_LAUNCH_CHECK();
-  }
-  if (d_cov_pos || d_std_pos) {
-    hipLaunchKernelGGL(k_skel_cov_pose, dim3((unsigned)NT), dim3(256), 0, s, d_dev, d_clip, D(lay.band), d_fxm, D(lay.opv), d_cov_pos,
-                       d_std_pos, d_unobs);
-    ACINO_LAUNCH_CHECK();
-  }
-  return skel_cov_read_status(d_clip, B, s, h_status);
+  return skc_covariance(p, n_clips, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_cov_x, d_cov_pos, d_std_pos,
+                        nullptr, h_status, d_ws, ws_bytes, stream, pin_unobserved, d_unobserved);
+}
+
+size_t acino_skel_fte_covariance_rates_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved) {
+  return acino_skel_fte_covariance_pinned_workspace_bytes(p, n_clips, pin_unobserved);      // (the rates are streamed from the band)
+}
+
+int acino_skel_fte_covariance_rates(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                    const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                    const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x, double* d_cov_pos,
+                                    double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel, double* d_std_vel,
+                                    int32_t* h_status, void* d_ws, size_t ws_bytes, void* stream, int pin_unobserved,
+                                    uint8_t* d_unobserved) {
+  const SkelRateOut rates = {d_cov_dx, d_cov_ddx, d_cov_vel, d_std_vel};
+  return skc_covariance(p, n_clips, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_cov_x, d_cov_pos, d_std_pos,
+                        &rates, h_status, d_ws, ws_bytes, stream, pin_unobserved, d_unobserved);
 }
 
 int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,

@@ -157,5 +157,13 @@ int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camer
 // The end of both entries: skel_read_status with the Fisher matrix's error text, and the clips' status words to h_status[n_clips]
 // (may be NULL: then a singular clip fails the call whatever the batch).
 int skel_cov_read_status(const SkelClip* d_clip, int n_clips, hipStream_t s, int32_t* h_status);
+// dynamic LDS of k_skel_cov_rates (skel_cov_rates.hip): three blocks [P][P + 1]
+inline size_t skel_cov_rates_lds(int P) { return sizeof(double) * (size_t)3 * P * (P + 1); }
+// k_skel_cov_rates on stream s, one workgroup per frame, after k_skel_selinv has left the blocks of the inverse in d_band:
+// covariance of dx, ddx ([NT][P][P]) and of the pose velocities ([NT][n_pose][3][3], [NT][n_pose]); any output may be NULL.
+// d_unobs: NULL, or the clips' masks [n_clips][P] when the unobserved states are pinned.
+int skel_cov_launch_rates(size_t NT, int P, const SkelDev* d_dev, const SkelClip* d_clip, const double* d_band,
+                          const unsigned char* d_fxm, const double* d_opv, const unsigned char* d_unobs, double h, double* d_cov_dx,
+                          double* d_cov_ddx, double* d_cov_vel, double* d_std_vel, hipStream_t s);
 
 }  // namespace acino

@@ -657,6 +657,42 @@ int acino_skel_fte_sample_pinned(const acino_skel_fte_params* p, int n_clips, in
                                  int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes, void* stream,
                                  int pin_unobserved, uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
 
+/* ---- error bars for the rates of the generic-skeleton FTE: dx, ddx and the pose velocities -------------------------------------
+ * acino_skel_fte_covariance_rates: acino_skel_fte_covariance_pinned with four more outputs.  A, the bound pins, pin_unobserved,
+ * the status rules, the limits, both camera models and the workspace rules are exactly those of that entry, and its three
+ * outputs are bit-identical to it.  Let e be the estimation error of a clip, Cov(e) = A^-1 with the rows and columns of pinned
+ * variables 0.  Every new output is the covariance C S_win C^T of a linear map of a window of at most three consecutive frames
+ * of the frame's own clip (a window never reaches into another clip of the batch); h = p->h:
+ *   dx, ddx   what the Python layer returns beside x (build._finite_diff_states; NOT the rule of acino_fte_derivatives):
+ *               N >= 3, n >= 2:  window (n-2, n-1, n);  dx_n = (x_n - x_n-1) / h,  ddx_n = (x_n - 2 x_n-1 + x_n-2) / h^2
+ *               N >= 3, n < 2:   window (0, 1, 2);  ddx_0 = ddx_1 = ddx_2,  dx_1 = (x_1 - x_0) / h,
+ *                                dx_0 = dx_1 - h ddx_1 = (-2 x_0 + 3 x_1 - x_2) / h
+ *               N = 2:           ddx = 0,  dx_1 = (x_1 - x_0) / h,  dx_0 = 0  (the cheetah rule has dx_0 = dx_1)
+ *               N = 1:           everything 0
+ *   v_n,l     the velocity of pose slot l, (pose_l(x_n) - pose_l(x_n-1)) / h, linearised as (G_l(x_n) e_n - G_l(x_n-1) e_n-1) / h
+ *             with G_l the pose Jacobian of d_cov_pos; frame 0 of a clip repeats frame 1; N = 1: 0
+ * Outputs (fp64, device; any of the seven may be NULL, but not all of them):
+ *   d_cov_dx, d_cov_ddx [n_clips][N][n_active][n_active]   (unit/s)^2 and (unit/s^2)^2
+ *   d_cov_vel           [n_clips][N][n_pose][3][3]         (m/s)^2
+ *   d_std_vel           [n_clips][N][n_pose]               sqrt(trace(cov_vel)), m/s
+ * sqrt(2 diag cov_x) / h is NOT a bar on dx: the third-difference prior correlates neighbouring frames almost perfectly, and
+ * the cross-frame blocks of the window - which lie inside the factor's band, so the result is exact - cancel most of it.
+ * A variable pinned in frame a contributes nothing from frame a: block S_ab of A^-1 has row p dropped if p is pinned in frame
+ * a and column q dropped if q is pinned in frame b.  With pin_unobserved = 1, cov_dx and cov_ddx are exactly 0 in the rows and
+ * columns of the unobserved states, and a slot whose G_l has a nonzero entry in such a column in frame n or in frame n-1 gets
+ * std_vel = +inf and cov_vel = NaN (as std_pos).  A singular clip: status 5 and every new output NaN; in a batch with h_status
+ * the other clips stand.  One run of the factorisation serves all outputs; arguments are validated before any device call;
+ * one stream synchronisation.  The workspace query returns what acino_skel_fte_covariance_pinned_workspace_bytes returns: the
+ * rates are streamed from the blocks the recursion leaves in the workspace, one workgroup per frame. */
+size_t acino_skel_fte_covariance_rates_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved);
+int acino_skel_fte_covariance_rates(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                    const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                    const double* d_lo, const double* d_hi, const double* d_x, double* d_cov_x,
+                                    double* d_cov_pos, double* d_std_pos, double* d_cov_dx, double* d_cov_ddx,
+                                    double* d_cov_vel, double* d_std_vel, int32_t* h_status /* [n_clips], may be NULL */,
+                                    void* d_ws, size_t ws_bytes, void* stream, int pin_unobserved,
+                                    uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
+
 /* ---- a generic-skeleton FTE iterate in image space: predicted pixels, their covariance, residuals, gating ----------------
  * Evaluated at the iterate d_x[n_clips][N][n_active] (normally the solution of acino_skel_fte_solve*).  Per entry
  * (b, n, c, l) = (clip, frame, camera, pose slot), the layout of d_meas[n_clips][N][C][n_pose][2] / d_w[n_clips][N][C][n_pose]:
