@@ -12,9 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libacinoset_hip.so")
 BUILD_ID_SOURCE = "camera_kernels.hip"      # defines acino_build_id()
-SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "ekf.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_reproj.hip"]
+SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_reproj.hip"]
 HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "fte_cov.hpp", "fte_reproj.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
-           "pinhole.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "fte_assemble_body.inc", "ekf_forward_body.inc", "skel_assemble_body.inc",
+           "pinhole.hpp", "sba_dev.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "fte_assemble_body.inc", "ekf_forward_body.inc", "skel_assemble_body.inc",
            os.path.join("..", "..", "include", "acinoset_hip.h")]
 
 ABI_VERSION = 3          # ACINO_ABI_VERSION of include/acinoset_hip.h
@@ -100,6 +100,16 @@ class SbaInfo(C.Structure):
         return d
 
 
+class SbaCovInfo(C.Structure):
+    _fields_ = [("sigma2", C.c_double), ("sum_w_r2", C.c_double), ("min_pivot_ratio", C.c_double), ("dof", C.c_int64),
+                ("n_obs_used", C.c_int64), ("n_points_excluded", C.c_int32), ("status", C.c_int32)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["status_name"] = {0: "ok", 5: "numeric"}.get(self.status, "?")
+        return d
+
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -181,6 +191,10 @@ SIGNATURES = {
     "acino_sba_solve": (_I, [C.POINTER(SbaParams), _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P, C.POINTER(SbaInfo), _P]),
     "acino_sba_solve_sharded": (_I, [C.POINTER(SbaParams), _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P, C.POINTER(SbaInfo),
                                      REDUCE_FN, _P, _P]),
+    "acino_sizeof_sba_cov_info": (_Z, []),
+    "acino_sba_covariance_workspace_bytes": (_Z, [_I, _L, _L]),
+    "acino_sba_covariance": (_I, [C.POINTER(SbaParams), _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _Z, _P, _P, _P,
+                                  C.POINTER(SbaCovInfo), _P]),
     "acino_sizeof_ekf_params": (_Z, []),
     "acino_ekf_workspace_bytes": (_Z, [_L, _I]),
     "acino_ekf_run": (_I, [C.POINTER(EkfParams), _P, _P, _P, _P, _Z, _P, _P, _P, _P]),
@@ -342,6 +356,8 @@ def lib():
         raise RuntimeError("libacinoset_hip.so struct layout differs from the Python binding (stale build?)")
     if handle.acino_sizeof_sba_params() != C.sizeof(SbaParams) or handle.acino_sizeof_sba_info() != C.sizeof(SbaInfo):
         raise RuntimeError("libacinoset_hip.so SBA struct layout differs from the Python binding (stale build?)")
+    if handle.acino_sizeof_sba_cov_info() != C.sizeof(SbaCovInfo):
+        raise RuntimeError("libacinoset_hip.so SBA covariance struct layout differs from the Python binding (stale build?)")
     if (handle.acino_sizeof_skel_fte_params() != C.sizeof(SkelFteParams) or
             handle.acino_sizeof_skel_fte_info() != C.sizeof(SkelFteInfo)):
         raise RuntimeError("libacinoset_hip.so skeleton-FTE struct layout differs from the Python binding (stale build?)")

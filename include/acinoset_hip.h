@@ -476,6 +476,50 @@ int acino_sba_solve_sharded(const acino_sba_params* prm, const double* d_intr, d
                             double* d_res_after, acino_sba_info* info, acino_reduce_fn reduce, void* reduce_user,
                             void* stream);
 
+/* ---- error bars of the bundle adjustment: covariance of the extrinsics and of the points at a given iterate ------------
+ * A = J^T W J of the flat residual under the solver's parametrisation (R <- exp([dw]x) R, t <- t + dt; camera parameter
+ * order [dw, dt]), W = the Cauchy IRLS weights 1 / (1 + (r / f_scale)^2), no damping, always fp64 (acino_sba_params is
+ * reused unchanged; lam0, ftol, gtol, max_iter and precision are ignored).  With optimize_cameras A has a 7-dimensional null
+ * space (world translation, rotation, scale); the camera covariance is taken under seven constraints on the camera
+ * parameters, Sigma_c = N (N^T S N)^-1 N^T with S the undamped reduced camera system and N the orthonormal complement of the
+ * 6C x 7 constraint block:
+ *   ACINO_SBA_GAUGE_BASELINE  the pose of ref_cam held and the distance between the centres of ref_cam and scale_cam held
+ *   ACINO_SBA_GAUGE_FREE      the camera rows of the seven generators: Sigma_c is the Moore-Penrose inverse of S
+ *   ACINO_SBA_GAUGE_CUSTOM    h_gauge[6C][7] (HOST memory, row-major): the caller's constraints
+ * Points: Sigma_p = V_p^-1 + Y_p Sigma_c Y_p^T, Y_p = V_p^-1 W_p^T (optimize_cameras = 0: Sigma_p = V_p^-1, no gauge, the
+ * gauge arguments and d_cov_cams are ignored).  A point whose V_p has an LDL^T pivot <= 3 eps max diag V_p (one view or none)
+ * is left out of S, of sigma2 and of dof, counted in n_points_excluded, and gets NaN.
+ * scale = ACINO_SBA_SCALE_RESIDUAL multiplies every covariance by sigma2 = sum w r^2 / (2 M - dof), dof = 3 P' + 6C - 7
+ * (3 P' for points only; P' points kept, M their observations); ACINO_SBA_SCALE_UNIT returns the unit-weight inverse.
+ *   d_cov_cams[6C][6C]   d_cov_points[P][6] (xx xy xz yy yz zz; may be NULL)   d_std_points[P] = sqrt(trace) (may be NULL)
+ * The workspace is the caller's, 256-byte aligned (ACINO_ERR_WORKSPACE otherwise).  A singular problem - 2 M <= dof, gauge
+ * constraints of rank below 7, or a Cholesky pivot of N^T S N at or below (6C - 7) eps max diag (a camera no point sees, too
+ * few points, a constraint block that does not fix the gauge) - is ACINO_ERR_NUMERIC with info->status = 5 and every output
+ * NaN.  optimize_cameras with one camera, ref_cam == scale_cam, an observation list or camera index out of range and two
+ * observations of one point by one camera are ACINO_ERR_INVALID_ARG.  The call synchronises the stream (two or three times).
+ * Sums go through per-workgroup partials added in a fixed order: a repeated call is bit-identical. */
+#define ACINO_SBA_GAUGE_BASELINE 0
+#define ACINO_SBA_GAUGE_FREE 1
+#define ACINO_SBA_GAUGE_CUSTOM 2
+#define ACINO_SBA_SCALE_RESIDUAL 0
+#define ACINO_SBA_SCALE_UNIT 1
+typedef struct acino_sba_cov_info {
+  double sigma2;              /* sum_w_r2 / (2 n_obs_used - dof); NaN when 2 M <= dof */
+  double sum_w_r2;
+  double min_pivot_ratio;     /* smallest Cholesky pivot of N^T S N over its largest diagonal entry (NaN for points only) */
+  int64_t dof;
+  int64_t n_obs_used;         /* observations of the points kept */
+  int32_t n_points_excluded;
+  int32_t status;             /* 0 ok, 5 numeric */
+} acino_sba_cov_info;
+size_t acino_sizeof_sba_cov_info(void);
+size_t acino_sba_covariance_workspace_bytes(int n_cams, int64_t n_points, int64_t n_obs);
+int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, const double* d_Rt, const double* d_pts,
+                         const double* d_uv, const int32_t* d_cam_idx, const int32_t* d_pt_start, const int32_t* d_pt_obs,
+                         int gauge, int ref_cam, int scale_cam, const double* h_gauge, int scale, void* d_ws, size_t ws_bytes,
+                         double* d_cov_cams, double* d_cov_points, double* d_std_points, acino_sba_cov_info* info,
+                         void* stream);
+
 /* ---- generic-skeleton forward kinematics (src/build.py:28-86) ---------------------------
  * The host compiles a skeleton dictionary into <= ACINO_SKEL_MAX_OPS link operations, evaluated in order for every
  * frame:  pose[child] = pose[parent] + M @ off,  M = R_loc or R_loc^T of the PARENT part's own angles

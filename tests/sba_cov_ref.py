@@ -1,0 +1,256 @@
+"""Numpy reference of the bundle-adjustment covariance (acinoset_amd.sba.covariance), independent of the kernels.
+
+A = J^T W J over the FULL parameter vector [dw_c, dt_c per camera | dX_p per point], J a dense Jacobian of
+``oracle.sba.residuals`` under the solver's parametrisation (R <- exp([dw]x) R, t <- t + dt) by central differences,
+Richardson-extrapolated from the steps 1e-4 and 2e-4 ((4 J_h - J_2h) / 3: the h^2 term cancels; the generators of the
+gauge freedom then annihilate A to ~5e-12 relative, the plain 1e-6 difference reaches 2e-10).  The covariance is
+N_full (N_full^T A N_full)^-1 N_full^T with N_full the orthonormal complement of the seven constraints, which are placed on
+the camera parameters only.  The two forms of J differ by <= 1.1e-8 in covariance scaled by std_i std_j: FLOOR, the
+reference's own noise level.
+"""
+import functools
+
+import numpy as np
+
+from acinoset_amd import synth
+from oracle import camera as ocam
+from oracle import sba as osba
+
+EPS = np.finfo(np.float64).eps
+FLOOR = 1.1e-8
+PINHOLE_D = np.array([0.05, -0.02, 1e-3, -5e-4, 0.01, 0.02, -0.01, 0.005])     # (the pinhole SBA test's 8 coefficients)
+
+
+def make_problem(n_cams, n_pts, seed, model="fisheye", single_view=False, blind_cam=None):
+    """synth.make_rig (cameras beyond the sixth: copies of the first ones, moved), a seeded rng, ragged visibility (2 .. C
+    views), 1 px noise and a handful of 15 px outliers so that the weights matter; the iterate is off the truth by 3 cm /
+    0.01 rad / 1 cm.  ``single_view``: the last point keeps one view.  ``blind_cam``: no point is seen by that camera."""
+    rng = np.random.default_rng(seed)
+    K6, D6, R6, t6 = synth.make_rig()
+    C, P = n_cams, n_pts
+    sel = np.arange(C) % 6
+    K, R, t = K6[sel], R6[sel].copy(), t6[sel].reshape(C, 3, 1).copy()
+    for c in range(6, C):
+        R[c] = ocam.rodrigues(rng.normal(0, 0.04, 3)) @ R[c]
+        t[c] = t[c] + rng.normal(0, 0.25, (3, 1))
+    if model == "fisheye":
+        D, ofun = D6[sel], ocam.project_points_fisheye
+    else:
+        D, ofun = np.tile(PINHOLE_D, (C, 1)), ocam.project_points
+    X = np.array([2.0, 6.5, 0.7]) + rng.normal(0, 0.6, (P, 3))
+    cams_ok = [c for c in range(C) if c != blind_cam]
+    pi, ci = [], []
+    for p in range(P):
+        cams = np.sort(rng.choice(cams_ok, size=rng.integers(2, len(cams_ok) + 1), replace=False))
+        if single_view and p == P - 1:
+            cams = cams[:1]
+        pi += [p] * len(cams)
+        ci += list(cams)
+    pi, ci = np.array(pi), np.array(ci)
+    uv = np.stack([ofun(X[p:p + 1], K[c], D[c], R[c], t[c])[0] for p, c in zip(pi, ci)]) + rng.normal(0, 1.0, (len(pi), 2))
+    n_out = min(5, len(uv) // 4)
+    uv[rng.choice(len(uv), n_out, replace=False)] += rng.uniform(-15, 15, (n_out, 2))
+    X0 = X + rng.normal(0, 0.03, X.shape)
+    R0 = np.array([ocam.rodrigues(rng.normal(0, 0.01, 3)) @ R[c] for c in range(C)])
+    t0 = t + rng.normal(0, 0.01, t.shape)
+    return dict(C=C, P=P, K=K, D=D, R=R0, t=t0, X=X0, pi=pi, ci=ci, uv=uv, ofun=ofun, model=model)
+
+
+def residual(prob, X=None, R=None, t=None):
+    return osba.residuals(prob["X"] if X is None else X, prob["R"] if R is None else R, prob["t"] if t is None else t,
+                          prob["K"], prob["D"], prob["pi"], prob["ci"], prob["uv"], project_func=prob["ofun"])
+
+
+def apply(prob, dc, dp):
+    """The solver's update (k_sba_apply_cams): R <- exp([dw]x) R, t <- t + dt, X <- X + dX."""
+    C, P = prob["C"], prob["P"]
+    Rn = np.array([ocam.rodrigues(dc[6 * c:6 * c + 3]) @ prob["R"][c] for c in range(C)])
+    return prob["X"] + dp.reshape(P, 3), Rn, prob["t"] + dc.reshape(C, 6)[:, 3:].reshape(C, 3, 1)
+
+
+def _central(prob, h, cameras):
+    C, P = prob["C"], prob["P"]
+    n = 6 * C + 3 * P
+    r0 = residual(prob)
+    J = np.zeros((r0.size, n))
+    rows_of = [np.nonzero(np.repeat(prob["pi"] == p, 2))[0] for p in range(P)]
+    for k in range(n):
+        if k < 6 * C and not cameras:
+            continue
+        e = np.zeros(n)
+        e[k] = h
+        d = (residual(prob, *apply(prob, e[:6 * C], e[6 * C:])) - residual(prob, *apply(prob, -e[:6 * C], -e[6 * C:]))) / (2 * h)
+        if k >= 6 * C:                                      # (a point moves its own observations only: exact zeros elsewhere)
+            rows = rows_of[(k - 6 * C) // 3]
+            J[rows, k] = d[rows]
+        else:
+            J[:, k] = d
+    return J
+
+
+def jacobian(prob, cameras=True, richardson=True):
+    if not richardson:
+        return _central(prob, 1e-6, cameras)
+    return (4.0 * _central(prob, 1e-4, cameras) - _central(prob, 2e-4, cameras)) / 3.0
+
+
+def weights(prob, f_scale):
+    r = residual(prob)
+    return 1.0 / (1.0 + (r / f_scale) ** 2), r
+
+
+def skew(v):
+    return np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def generators(prob):
+    """[6C + 3P, 7]: world translation (3), rotation (3), scale (1)."""
+    C, P = prob["C"], prob["P"]
+    G = np.zeros((6 * C + 3 * P, 7))
+    for k in range(3):
+        e = np.eye(3)[k]
+        for c in range(C):
+            G[6 * c + 3:6 * c + 6, k] = -prob["R"][c] @ e
+            G[6 * c:6 * c + 3, 3 + k] = -prob["R"][c] @ e
+        for p in range(P):
+            G[6 * C + 3 * p:6 * C + 3 * p + 3, k] = e
+            G[6 * C + 3 * p:6 * C + 3 * p + 3, 3 + k] = np.cross(e, prob["X"][p])
+    for c in range(C):
+        G[6 * c + 3:6 * c + 6, 6] = prob["t"][c].reshape(3)
+    G[6 * C:, 6] = prob["X"].reshape(-1)
+    return G
+
+
+def centres(R, t):
+    return np.array([-R[c].T @ np.asarray(t[c]).reshape(3) for c in range(len(R))])
+
+
+def constraints(prob, gauge="baseline", ref_cam=0, scale_cam=1):
+    """The 6C x 7 constraint block on the camera parameters."""
+    C = prob["C"]
+    if not isinstance(gauge, str):
+        return np.asarray(gauge, dtype=np.float64)
+    if gauge == "free":
+        return generators(prob)[:6 * C]
+    G = np.zeros((6 * C, 7))
+    G[6 * ref_cam:6 * ref_cam + 6, :6] = np.eye(6)
+    cen = centres(prob["R"], prob["t"])
+    u = cen[scale_cam] - cen[ref_cam]
+    u /= np.linalg.norm(u)
+    Ru = prob["R"][scale_cam] @ u
+    G[6 * scale_cam:6 * scale_cam + 3, 6] = np.cross(prob["t"][scale_cam].reshape(3), Ru)
+    G[6 * scale_cam + 3:6 * scale_cam + 6, 6] = -Ru
+    return G
+
+
+def complement(Cg):
+    """Orthonormal basis of the complement of the columns of Cg."""
+    q, _r = np.linalg.qr(Cg, mode="complete")
+    return q[:, Cg.shape[1]:]
+
+
+def excluded_points(A, C, P, views=None):
+    """A point whose V_p has an LDL^T pivot <= 3 eps max diag V_p (and, given the view counts, a point with fewer than two views)."""
+    out = np.zeros(P, dtype=bool) if views is None else np.asarray(views) < 2     # (one view: rank 2 exactly)
+    for p in range(P):
+        s = 6 * C + 3 * p
+        V = A[s:s + 3, s:s + 3].copy()
+        tol = 3 * EPS * np.diag(V).max()
+        for k in range(3):
+            if not V[k, k] > tol:
+                out[p] = True
+                break
+            V[k + 1:, k + 1:] -= np.outer(V[k + 1:, k], V[k, k + 1:]) / V[k, k]
+    return out
+
+
+def centre_jacobian(R, t):
+    """d(centre) = -R^T [t]x dw - R^T dt."""
+    return np.hstack([-R.T @ skew(np.asarray(t).reshape(3)), -R.T])
+
+
+def reference(prob, optimize_cameras=True, f_scale=1.0, gauge="baseline", ref_cam=0, scale_cam=1, scale="residual", J=None):
+    """The dict of sba.covariance from the dense matrix."""
+    C, P = prob["C"], prob["P"]
+    nc = 6 * C
+    J = jacobian(prob, cameras=optimize_cameras) if J is None else J
+    w, r = weights(prob, f_scale)
+    A = J.T @ (w[:, None] * J)
+    excl = excluded_points(A, C, P, np.bincount(prob["pi"], minlength=P))
+    rows = np.repeat(~excl[prob["pi"]], 2)
+    cols = np.concatenate([np.full(nc, bool(optimize_cameras)), np.repeat(~excl, 3)])
+    Jk = J[rows][:, cols]
+    A = Jk.T @ (w[rows, None] * Jk)
+    n_kept, m2 = int((~excl).sum()), int(rows.sum())
+    dof = 3 * n_kept + (nc - 7 if optimize_cameras else 0)
+    sum_w_r2 = float((w[rows] * r[rows] ** 2).sum())
+    sigma2 = sum_w_r2 / (m2 - dof)
+    mult = sigma2 if scale == "residual" else 1.0
+    out = dict(sigma2=sigma2, dof=dof, sum_w_r2=sum_w_r2, n_points_excluded=int(excl.sum()), excluded=excl)
+    if optimize_cameras:
+        Cfull = np.vstack([constraints(prob, gauge, ref_cam, scale_cam), np.zeros((3 * n_kept, 7))])
+        N = complement(Cfull)
+        cov = mult * (N @ np.linalg.solve(N.T @ A @ N, N.T))
+        cc, pp = cov[:nc, :nc], cov[nc:, nc:]
+        blocks = np.stack([cc[6 * c:6 * c + 6, 6 * c:6 * c + 6] for c in range(C)])
+        jac = np.stack([centre_jacobian(prob["R"][c], prob["t"][c]) for c in range(C)])
+        cen = np.einsum("cia,cab,cjb->cij", jac, blocks, jac)
+        out.update(cov_cams=cc, cov_cam=blocks, cov_center=cen, std_center=np.sqrt(np.einsum("cii->c", cen)),
+                   std_rot_deg=np.degrees(np.sqrt(np.einsum("cii->c", blocks[:, :3, :3]))))
+    else:
+        pp = mult * np.linalg.inv(A)
+    cov_points = np.full((P, 3, 3), np.nan)
+    for q, p in enumerate(np.nonzero(~excl)[0]):
+        cov_points[p] = pp[3 * q:3 * q + 3, 3 * q:3 * q + 3]
+    out.update(cov_points=cov_points, std_points=np.sqrt(np.einsum("pii->p", cov_points)))
+    return out
+
+
+def schur(prob, J, f_scale=1.0, gauge="baseline", ref_cam=0, scale_cam=1):
+    """The route of the kernels, in numpy: S, Sigma_c = N (N^T S N)^-1 N^T, Sigma_p = V^-1 + Y Sigma_c Y^T (unit weight; every
+    point must be kept)."""
+    C, P = prob["C"], prob["P"]
+    nc = 6 * C
+    w, _r = weights(prob, f_scale)
+    A = J.T @ (w[:, None] * J)
+    U, W, V = A[:nc, :nc], A[:nc, nc:], A[nc:, nc:]
+    Vi = np.zeros_like(V)
+    for p in range(P):
+        Vi[3 * p:3 * p + 3, 3 * p:3 * p + 3] = np.linalg.inv(V[3 * p:3 * p + 3, 3 * p:3 * p + 3])
+    S = U - W @ Vi @ W.T
+    N = complement(constraints(prob, gauge, ref_cam, scale_cam))
+    cc = N @ np.linalg.solve(N.T @ S @ N, N.T)
+    Y = Vi @ W.T
+    full = Vi + Y @ cc @ Y.T
+    return S, cc, np.stack([full[3 * p:3 * p + 3, 3 * p:3 * p + 3] for p in range(P)])
+
+
+def relative_rotation_cov(cov_cams, R, a, b):
+    """Covariance of dw_a - R_a R_b^T dw_b, the change of the rotation of camera a relative to camera b: gauge-invariant."""
+    L = np.zeros((3, cov_cams.shape[0]))
+    L[:, 6 * a:6 * a + 3] = np.eye(3)
+    L[:, 6 * b:6 * b + 3] = -R[a] @ R[b].T
+    return L @ cov_cams @ L.T
+
+
+def scaled_error(S, Sref, floor=None):
+    """max |S - Sref| / (std_i std_j), std from the reference's diagonal.  A parameter the gauge holds has zero variance: a
+    std is floored at 1e-6 of the largest one (of all blocks, for a stack of blocks), so that its rows are held to zero on the
+    scale of the others."""
+    S, Sref = np.asarray(S), np.asarray(Sref)
+    if S.ndim == 3:
+        live = [k for k in range(len(Sref)) if np.isfinite(Sref[k]).all()]
+        floor = 1e-6 * np.sqrt(max(np.abs(np.diag(Sref[k])).max() for k in live))
+        return max(scaled_error(S[k], Sref[k], floor) for k in live)
+    d = np.sqrt(np.abs(np.diag(Sref)))
+    d = np.maximum(d, 1e-6 * d.max() if floor is None else floor)
+    return float(np.abs((S - Sref) / np.outer(d, d)).max())
+
+
+@functools.lru_cache(maxsize=None)
+def cached(n_cams, n_pts, seed, model="fisheye", single_view=False, blind_cam=None, cameras=True):
+    """(problem, Richardson Jacobian): computed once per shape, shared by the tests, never modified."""
+    prob = make_problem(n_cams, n_pts, seed, model, single_view, blind_cam)
+    J = jacobian(prob, cameras=cameras)
+    J.setflags(write=False)
+    return prob, J
