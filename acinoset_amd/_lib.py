@@ -12,8 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libacinoset_hip.so")
 BUILD_ID_SOURCE = "camera_kernels.hip"      # defines acino_build_id()
-SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_reproj.hip"]
-HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "fte_cov.hpp", "fte_reproj.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
+SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_calib.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_reproj.hip"]
+HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "fte_cov.hpp", "fte_cov_dev.hpp", "fte_calib.hpp", "fte_reproj.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
            "pinhole.hpp", "sba_dev.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "fte_assemble_body.inc", "ekf_forward_body.inc", "skel_assemble_body.inc",
            os.path.join("..", "..", "include", "acinoset_hip.h")]
 
@@ -162,6 +162,8 @@ SIGNATURES = {
     "acino_fte_covariance_rates": (_I, [_P, C.c_double, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
     "acino_fte_sample_workspace_bytes": (_Z, [C.POINTER(FteParams)]),
     "acino_fte_sample": (_I, [_P, _L, _P, _P, _Z, _P, _P, _P]),
+    "acino_fte_calibration_workspace_bytes": (_Z, [C.POINTER(FteParams)]),
+    "acino_fte_calibration_sensitivity": (_I, [_P, _P, _P, _Z, _P, _P, _P, _P, _P]),
     "acino_fte_reprojection": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "acino_fte_derivatives": (_I, [_P, _L, _D, _P, _P, _P]),
     "acino_fte_load_x": (_I, [_P, _P, _P]),

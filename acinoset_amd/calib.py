@@ -275,6 +275,26 @@ def triangulate_reproject_dense(det, thresh, k_arr, d_arr, r_arr, t_arr):
     return _ret(tri, det), _ret(npairs, det), _ret(mask, det), _ret(res, det), _ret(sums, det)
 
 
+def extrinsic_cov(n_cams, std_rot_deg, std_t_m, fixed=()):
+    """A diagonal covariance of the extrinsics of ``n_cams`` cameras for ``FTEContext.calibration_sensitivity`` /
+    ``fte_solve(cov_cams=...)`` when no bundle-adjustment covariance is at hand: [6 n_cams, 6 n_cams] float64 in the order
+    and units of ``sba.covariance``'s ``cov_cams`` - per camera (dw [rad], dt [m]) with R <- exp([dw]x) R, t <- t + dt -,
+    ``std_rot_deg`` degrees per rotation axis and ``std_t_m`` metres per translation axis, uncorrelated.  The cameras
+    listed in ``fixed`` (held by the gauge, e.g. ``(0,)``) get zero rows and columns."""
+    n_cams = int(n_cams)
+    if n_cams < 1:
+        raise ValueError("n_cams must be >= 1")
+    if not (np.isfinite(std_rot_deg) and np.isfinite(std_t_m)) or std_rot_deg < 0 or std_t_m < 0:
+        raise ValueError("std_rot_deg and std_t_m must be finite and >= 0")
+    fixed = [int(c) for c in fixed]
+    if any(c < 0 or c >= n_cams for c in fixed):
+        raise ValueError(f"fixed cameras must lie in 0..{n_cams - 1}")
+    var = np.tile(np.r_[np.full(3, np.deg2rad(float(std_rot_deg)) ** 2), np.full(3, float(std_t_m) ** 2)], n_cams)
+    for c in fixed:
+        var[6 * c:6 * c + 6] = 0.0
+    return np.diag(var)
+
+
 def dataframe_to_dense(points_2d_df, n_cameras):
     """Long DataFrame [frame, camera, marker, x, y, (likelihood)] -> dense det[N,C,L,3] plus the sorted
     frame and marker keys.  Rows absent from the frame get likelihood -inf (never valid)."""

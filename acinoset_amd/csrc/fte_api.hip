@@ -6,6 +6,7 @@
 
 #include "bcr.hpp"
 #include "chunk.hpp"
+#include "fte_calib.hpp"
 #include "fte_cov.hpp"
 #include "fte_reproj.hpp"
 #include "seplevel.hpp"
@@ -1472,6 +1473,42 @@ int acino_fte_sample(acino_fte_ctx* ctx, int64_t n_samples, const double* d_z, v
   ACINO_HIP_CHECK(hipStreamSynchronize(s));
   if (flag) {
     set_error("acino_fte_sample: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive definite)");
+    return ACINO_ERR_NUMERIC;
+  }
+  return ACINO_OK;
+}
+
+// ---- sensitivity to the camera extrinsics (csrc/fte_calib.hip) ----
+size_t acino_fte_calibration_workspace_bytes(const acino_fte_params* p) {
+  const size_t cov = acino_fte_covariance_workspace_bytes(p);
+  if (!cov || p->n_cams < 1 || p->n_cams > ACINO_MAX_CAMS) return 0;
+  return calib_workspace_bytes(p->n_frames, p->clip_len, p->n_cams);
+}
+
+int acino_fte_calibration_sensitivity(acino_fte_ctx* ctx, const double* d_cov_cams, void* d_ws, size_t ws_bytes,
+                                      double* d_sens, double* d_cov_x_cal, double* d_cov_pos_cal, double* d_std_pos_cal,
+                                      void* stream) {
+  ACINO_REQUIRE(ctx && d_ws, "null");
+  ACINO_REQUIRE(d_sens || d_cov_x_cal || d_cov_pos_cal || d_std_pos_cal, "no output asked for");
+  ACINO_REQUIRE(d_cov_cams || !(d_cov_x_cal || d_cov_pos_cal || d_std_pos_cal), "a cov / std output needs d_cov_cams");
+  int rc = cov_supported(ctx->h, "acino_fte_calibration_sensitivity");
+  if (rc) return rc;
+  const size_t need = calib_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len, ctx->h.n_cams);
+  if (ws_bytes < need || ((uintptr_t)d_ws & 255) != 0) {
+    set_error("calibration workspace too small or misaligned: need %zu bytes at a 256-byte boundary, got %zu", need, ws_bytes);
+    return ACINO_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const Buffers& b = ctx->b;
+  rc = launch_fte_calib(b.cst, ctx->h, b.state, ctx->d_det, b.x, b.H, b.g, d_ws, d_cov_cams, d_sens, d_cov_x_cal,
+                        d_cov_pos_cal, d_std_pos_cal, s);
+  if (rc) return rc;
+  int flag = 0;
+  ACINO_HIP_CHECK(hipMemcpyAsync(&flag, d_ws, sizeof(int), hipMemcpyDeviceToHost, s));
+  ACINO_HIP_CHECK(hipStreamSynchronize(s));
+  if (flag) {
+    set_error("acino_fte_calibration_sensitivity: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive "
+              "definite)");
     return ACINO_ERR_NUMERIC;
   }
   return ACINO_OK;

@@ -28,13 +28,13 @@
 // for the head position.
 //
 // k_fte_cov_rates (below the combine) reads the same corrections for the covariance of dx, ddx and the marker velocities.
+// The sampler (k_fte_sample_factors, k_fte_sample_backsub) and the column solve (k_fte_sample_fwdsub) follow further down.
 //
 // No workgroup waits for another inside a kernel; a non-positive pivot sets the error word (chol80) and NaNs run through
 // the remaining nodes - no trap, no abort.  A translation unit of its own: nothing here is shared with the LM step's kernels
 // beyond the device functions of dense80.hpp / bcr_dev.hpp, which stay as they are.
-#include "bcr_dev.hpp"
-#include "cheetah_fk.hpp"
 #include "fte_cov.hpp"
+#include "fte_cov_dev.hpp"
 
 namespace acino {
 
@@ -66,9 +66,6 @@ struct CovArgs {
   double inv_ts;
 };
 
-struct CovIn {
-  const double *x, *g, *H;
-};
 __device__ __forceinline__ CovIn cov_inputs(const CovArgs& A) {
   const int cur = A.st->cur;
   return CovIn{cur ? A.x1 : A.x0, cur ? A.g1 : A.g0, cur ? A.H1 : A.H0};
@@ -76,23 +73,6 @@ __device__ __forceinline__ CovIn cov_inputs(const CovArgs& A) {
 
 constexpr int COV_TAB = 232;                                        // 9 * NP doubles, padded
 constexpr size_t COV_LDS = (2 * MAT + COV_TAB) * sizeof(double) + 2 * BS * sizeof(int);
-
-// code[row] of a node whose first frame is global frame f0 and which holds nlive frames of its clip:
-// 0 free, 1 bound-active (the solve's rule: build_finish, oracle active_set), 2 padding / no such frame
-__device__ __forceinline__ void cov_codes(int* code, const CovIn& in, const FteConst& K, int64_t f0, int nlive, int tid) {
-  if (tid < BS) {
-    int c = 2;
-    const int fr = tid / NP, p = tid % NP;
-    if (tid < 3 * NP && fr < nlive) {
-      const int64_t n = f0 + fr;
-      const double d = in.H[n * HPAIRS + hpair(p, p)];              // (measurement part + smoothness diagonal)
-      const double xv = in.x[(n + HALO) * NP + p], gv = in.g[n * NP + p];
-      const double gtol = GRAD_ZERO_REL * d;
-      c = ((xv <= K.lo[p] && gv > gtol) || (xv >= K.hi[p] && gv < -gtol)) ? 1 : 0;
-    }
-    code[tid] = c;
-  }
-}
 
 // D_k into Lm (ACC: on top of what is there), both triangles.  r0: the node's first frame counted inside its clip.
 template <bool ACC>
@@ -230,21 +210,6 @@ __global__ void __launch_bounds__(256) k_fte_cov_sweep(CovArgs A) {
     k = kn;
   }
 }
-
-namespace {
-struct CovFrame {
-  static constexpr bool kHasOm = true;
-  double sc[22][2];
-  double pos[21][3];
-  double om[22][3];
-};
-// the rotation group whose frame carries marker l (cheetah_fk.hpp: fk_columns)
-__device__ __forceinline__ int cov_marker_grp(int l) {
-  // {0, 0, 0, 1, 2, 3, 4, 5, 2, 6, 7, 2, 8, 9, 3, 10 | 11, 3, 12, 13}, one nibble per marker (arithmetic, not a table)
-  const unsigned long long lo = 0xA398276254321000ull, hi = 0xDC3Bull;
-  return (int)(((l < 16 ? lo : hi) >> (4 * (l & 15))) & 15);
-}
-}  // namespace
 
 // grid = n_nodes: Sigma_k = (D_k - CF_k - CB_k)^-1, its three diagonal blocks, the markers' covariances.
 __global__ void __launch_bounds__(256) k_fte_cov_combine(CovArgs A) {
@@ -395,17 +360,6 @@ struct RateBatch {
   double c0, c1, c2;
   int loc0, loc1, loc2;
 };
-
-__device__ __forceinline__ double rate_jac(const CovFrame& F, int l, int i, int p) {
-  if (p < 3) return p == i ? 1.0 : 0.0;
-  const int ga = c_state_grp[p], gm = cov_marker_grp(l);
-  if (!((c_ancmask[gm] >> ga) & 1)) return 0.0;
-  const double* w = F.om[p - 3];
-  const double* c = F.pos[c_grp_pivot[ga]];
-  const double* m = F.pos[l];
-  const double d0 = m[0] - c[0], d1 = m[1] - c[1], d2 = m[2] - c[2];
-  return i == 0 ? w[1] * d2 - w[2] * d1 : (i == 1 ? w[2] * d0 - w[0] * d2 : w[0] * d1 - w[1] * d0);
-}
 
 // entry (row c of the batch, column col of node k - 1 (part 0) / node k (part 1)) of the coefficient matrix.
 // F[0]: last frame of node k - 1, F[1 + t]: frame t of node k
@@ -665,6 +619,9 @@ __global__ void __launch_bounds__(256) k_fte_cov_rates(CovArgs A) {
 // k_fte_cov_sweep<true> (one workgroup per clip) leaves CF_k; k_fte_sample_factors, one workgroup per node, all in
 // parallel, stores U_k^T = L_k^-1 as its 15 lower tiles in the CB half of the workspace (which the forward-only sweep does
 // not write); k_fte_sample_backsub, grid (clips, panels of 64 samples), walks the nodes from last to first.
+// A fourth kernel uses the same factors for whole solves A^-1 B (launch_fte_solve_columns, further down; the extrinsic
+// sensitivity of fte_calib.hip): k_fte_sample_fwdsub, the forward substitution L y = b on the same grid, walks the nodes from
+// first to last, and k_fte_sample_backsub<true> then writes L^-T y without x_hat.
 namespace {
 struct SampleIo {
   const double* z;                                       // [S][N][25]
@@ -710,19 +667,24 @@ __device__ __forceinline__ void sample_w_tile(double* W, const double* V, const 
 }
 
 // delta = W U^T, tile IB: kept as rows for the next node and written out as x_hat + delta for the node's live frames
-template <int IB>
+// (DELTA: as delta alone, exactly 0 for a pinned variable - the solve of launch_fte_solve_columns)
+template <int IB, bool DELTA>
 __device__ __forceinline__ void sample_d_tile(double* D, const double* W, const double* Lt, const SampleNode& nd, int li,
                                               int lk) {
   const d4 acc = sample_mul_ut<IB>(W, Lt, li, lk);
   const int c = IB * 16 + li;
   const bool out = c < 3 * NP && c / NP < nd.nlive;
   const bool free_var = nd.code[c] == 0;
-  const double xh = out ? nd.xhat[(nd.f0 + c / NP + HALO) * NP + c % NP] : 0.0;
+  const double xh = (out && !DELTA) ? nd.xhat[(nd.f0 + c / NP + HALO) * NP + c % NP] : 0.0;
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     D[(lk + 4 * rr) * LD + c] = acc[rr];
     const long long s = nd.s_first + lk + 4 * rr;
-    if (out && s < nd.n_samples) nd.xs[(s * nd.n_frames + nd.f0) * NP + c] = free_var ? xh + acc[rr] : xh;
+    if (DELTA) {
+      if (out && s < nd.n_samples) nd.xs[(s * nd.n_frames + nd.f0) * NP + c] = free_var ? acc[rr] : 0.0;
+    } else {
+      if (out && s < nd.n_samples) nd.xs[(s * nd.n_frames + nd.f0) * NP + c] = free_var ? xh + acc[rr] : xh;
+    }
   }
 }
 }  // namespace
@@ -760,6 +722,8 @@ __global__ void __launch_bounds__(256) k_fte_sample_factors(CovArgs A) {
 // grid = (n_clips, panels): the backward substitution of one clip for 64 samples, wave w the samples 16 w .. 16 w + 15 of
 // the panel.  A wave reads and writes its own rows of the two panel buffers only; the barriers order the shared factor,
 // stencil table and codes.  U_k-1's tiles are requested into registers while node k computes.
+// DELTA = false: the sampler (xs = x_hat + delta); true: xs = delta (the second half of a solve A^-1 b).
+template <bool DELTA>
 __global__ void __launch_bounds__(256) k_fte_sample_backsub(CovArgs A, SampleIo io) {
   extern __shared__ __attribute__((aligned(16))) double cov_smem[];
   double* Lt = cov_smem;
@@ -864,11 +828,11 @@ __global__ void __launch_bounds__(256) k_fte_sample_backsub(CovArgs A, SampleIo 
     __syncthreads();
     if (live) {
       const SampleNode nd{in.x, code, io.xs, S, N, s_first, f0, nlive};
-      sample_d_tile<0>(Db, Wb, Lt, nd, li, lk);
-      sample_d_tile<1>(Db, Wb, Lt, nd, li, lk);
-      sample_d_tile<2>(Db, Wb, Lt, nd, li, lk);
-      sample_d_tile<3>(Db, Wb, Lt, nd, li, lk);
-      sample_d_tile<4>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<0, DELTA>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<1, DELTA>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<2, DELTA>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<3, DELTA>(Db, Wb, Lt, nd, li, lk);
+      sample_d_tile<4, DELTA>(Db, Wb, Lt, nd, li, lk);
     }
     {                                                    // delta_k is the next node's source; this node's codes its neighbour's
       double* sw = Wb;
@@ -905,7 +869,7 @@ int launch_fte_sample(const FteConst* d_c, const FteConst& h_c, const acino_fte_
   const int64_t panels = (n_samples + SPB - 1) / SPB;
   ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep<true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_sample_backsub),
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_sample_backsub<false>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS));
   ACINO_HIP_CHECK(hipMemsetAsync(d_ws, 0, COV_HEAD_BYTES, s));
   if (gr.nodes_per_clip > 1) {
@@ -914,7 +878,193 @@ int launch_fte_sample(const FteConst* d_c, const FteConst& h_c, const acino_fte_
   }
   hipLaunchKernelGGL(k_fte_sample_factors, dim3((unsigned)gr.n_nodes()), dim3(256), SAMPLE_FACT_LDS, s, A);
   ACINO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_fte_sample_backsub, dim3((unsigned)gr.n_clips, (unsigned)panels), dim3(256), SAMPLE_LDS, s, A, io);
+  hipLaunchKernelGGL(k_fte_sample_backsub<false>, dim3((unsigned)gr.n_clips, (unsigned)panels), dim3(256), SAMPLE_LDS, s, A, io);
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
+
+// ---- A^-1 B for panels of right-hand sides: forward substitution, then the sampler's backward substitution ------------
+// With A = L L^T and the factors above, L y = b is
+//   y_0 = U_0^T b_0,   y_k+1 = U_k+1^T (b_k+1 - E_k^T (U_k y_k))
+// - again products of the triangular factors only (never G = U U^T on a right-hand side) -, and k_fte_sample_backsub<true>
+// on y gives L^-T y = A^-1 b.  k_fte_sample_fwdsub is the mirror image of the backward substitution: grid (n_clips,
+// panels of 64 columns), the columns held as ROWS, 16 per wave, a wave reading and writing its own rows of the two panel
+// buffers only, U_k+1's tiles requested into registers while node k computes.  b of a pinned variable counts as 0 (y and
+// the solution are exactly 0 there).  No pivot is taken here: the error word is the factors'.
+namespace {
+// y = W U, tile JB of the wave's 16 rows: kept as rows for the next product and written out for the node's live frames
+template <int JB>
+__device__ __forceinline__ void fwd_y_tile(double* Y, const double* W, const double* Lt, const int* code, const SampleIo& io,
+                                           long long s_first, long long f0, int nlive, int li, int lk) {
+  const d4 acc = sample_mul_u<JB>(W, Lt, li, lk);
+  const int c = JB * 16 + li;
+  const bool out = c < 3 * NP && c / NP < nlive;
+  const bool free_var = code[c] == 0;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    Y[(lk + 4 * rr) * LD + c] = acc[rr];
+    const long long s = s_first + lk + 4 * rr;
+    if (out && s < io.n_samples) io.xs[(s * io.n_frames + f0) * NP + c] = free_var ? acc[rr] : 0.0;
+  }
+}
+// T = Y U^T, tile IB
+template <int IB>
+__device__ __forceinline__ void fwd_t_tile(double* T, const double* Y, const double* Lt, int li, int lk) {
+  const d4 acc = sample_mul_ut<IB>(Y, Lt, li, lk);
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) T[(lk + 4 * rr) * LD + IB * 16 + li] = acc[rr];
+}
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_fte_sample_fwdsub(CovArgs A, SampleIo io) {
+  extern __shared__ __attribute__((aligned(16))) double cov_smem[];
+  double* Lt = cov_smem;
+  double* P0 = Lt + MAT;
+  double* P1 = P0 + SPB * LD;
+  double* wtab = P1 + SPB * LD;                          // [(s * 3 + t) * NP + p]: frame s of node k - 1 with frame t of node k
+  int* code = reinterpret_cast<int*>(wtab + COV_TAB);
+  int* codep = code + BS;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int clip_i = (int)blockIdx.x;
+  if (clip_i >= A.n_clips) return;
+  const FteConst& K = *A.cst;
+  const CovIn in = cov_inputs(A);
+  const int M = A.nodes_per_clip;
+  const int64_t clip = A.clip, fclip = (int64_t)clip_i * clip;
+  const size_t n_nodes = (size_t)A.n_clips * M;
+  const long long S = io.n_samples, N = io.n_frames;
+  const long long s_first = (long long)blockIdx.y * SPB + 16 * wave;
+  const bool live = s_first < S;                         // (wave-uniform; a dead wave only keeps the barriers)
+  double* Tb = P0 + 16 * wave * LD;                      // (U_k-1 y_k-1) as rows, then y_k ...
+  double* Wb = P1 + 16 * wave * LD;                      // ... b_k - E^T (U y), then U_k y_k: the two trade places every node
+  const double2* ut = reinterpret_cast<const double2*>(A.terms + (n_nodes + (size_t)clip_i * M) * COV_TERM_DOUBLES);
+  constexpr int NQ = (LOWER_ITEMS + 255) / 256;
+  constexpr size_t T2 = COV_TERM_DOUBLES / 2;
+  constexpr int NB = 16 * BS / 64;                       // entries of the wave's 16 x 80 rows per lane
+  double2 uf[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int idx = tid + 256 * q;
+    if (idx < LOWER_ITEMS) uf[q] = ut[idx];
+  }
+  for (int k = 0; k < M; ++k) {
+    const int64_t r0 = 3 * (int64_t)k, f0 = fclip + r0;
+    const int nlive = (int)min((int64_t)3, clip - r0);
+    cov_codes(code, in, K, f0, nlive, tid);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int idx = tid + 256 * q;
+      if (idx < LOWER_ITEMS) {
+        int row, col;
+        lower_item(idx, row, col);
+        Lt[row * LD + col] = uf[q].x;
+        Lt[row * LD + col + 1] = uf[q].y;
+      }
+    }
+    if (k + 1 < M) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int idx = tid + 256 * q;
+        if (idx < LOWER_ITEMS) uf[q] = ut[(size_t)(k + 1) * T2 + idx];
+      }
+    }
+    double bv[NB];                                       // entry e = lane + 64 i of the rows: column sl = e / 80, variable r = e % 80
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int e = lane + 64 * i, sl = e / BS, r = e % BS;
+      const long long s = s_first + sl;
+      bv[i] = (s < S && r < 3 * NP && r / NP < nlive) ? io.z[(s * N + f0) * NP + r] : 0.0;
+    }
+    __syncthreads();
+    if (k > 0) {
+      for (int e = tid; e < 9 * NP; e += 256) {
+        const int s = e / (3 * NP), t = (e / NP) % 3, p = e % NP;
+        const int dist = 3 + t - s;
+        double v = 0.0;
+        if (dist <= 3 && codep[s * NP + p] == 0 && code[t * NP + p] == 0) v = 2.0 * K.q_w[p] * band_coef(r0 - 3 + s, dist, clip);
+        wtab[e] = v;
+      }
+      __syncthreads();
+    }
+    if (live) {                                          // W = b_k - E_k-1^T (U_k-1 y_k-1), <= 3 stencil terms per entry
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        const int e = lane + 64 * i, sl = e / BS, r = e % BS;
+        double v = 0.0;
+        if (k > 0 && r < 3 * NP) {
+          const int t = r / NP, p = r % NP;
+#pragma unroll
+          for (int s = 0; s < 3; ++s) v += wtab[(s * 3 + t) * NP + p] * Tb[sl * LD + s * NP + p];
+        }
+        Wb[sl * LD + r] = (code[r] == 0 ? bv[i] : 0.0) - v;
+      }
+    }
+    __syncthreads();
+    if (live) {                                          // y_k = U_k^T W as rows: W U; kept for the next product and written out
+      fwd_y_tile<0>(Tb, Wb, Lt, code, io, s_first, f0, nlive, li, lk);
+      fwd_y_tile<1>(Tb, Wb, Lt, code, io, s_first, f0, nlive, li, lk);
+      fwd_y_tile<2>(Tb, Wb, Lt, code, io, s_first, f0, nlive, li, lk);
+      fwd_y_tile<3>(Tb, Wb, Lt, code, io, s_first, f0, nlive, li, lk);
+      fwd_y_tile<4>(Tb, Wb, Lt, code, io, s_first, f0, nlive, li, lk);
+    }
+    __syncthreads();
+    if (live && k + 1 < M) {                             // U_k y_k as rows: y U^T, the next node's source
+      fwd_t_tile<0>(Wb, Tb, Lt, li, lk);
+      fwd_t_tile<1>(Wb, Tb, Lt, li, lk);
+      fwd_t_tile<2>(Wb, Tb, Lt, li, lk);
+      fwd_t_tile<3>(Wb, Tb, Lt, li, lk);
+      fwd_t_tile<4>(Wb, Tb, Lt, li, lk);
+    }
+    {
+      double* sw = Tb;
+      Tb = Wb;
+      Wb = sw;
+      int* sc = code;
+      code = codep;
+      codep = sc;
+    }
+    __syncthreads();
+  }
+}
+
+int launch_fte_solve_columns(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
+                             double* const H[2], double* const g[2], void* d_ws, int64_t n_cols, double* d_b, double* d_y,
+                             hipStream_t s) {
+  const CovGrid gr = cov_grid(h_c.n_frames, h_c.clip_len);
+  CovArgs A = {};
+  A.cst = d_c;
+  A.st = d_st;
+  A.x0 = x[0];
+  A.x1 = x[1];
+  A.g0 = g[0];
+  A.g1 = g[1];
+  A.H0 = H[0];
+  A.H1 = H[1];
+  A.err = reinterpret_cast<int*>(d_ws);
+  A.terms = reinterpret_cast<double*>(reinterpret_cast<char*>(d_ws) + COV_HEAD_BYTES);
+  A.n_clips = gr.n_clips;
+  A.nodes_per_clip = gr.nodes_per_clip;
+  A.clip = gr.clip;
+  A.inv_ts = 1.0;
+  const SampleIo fwd{d_b, d_y, (long long)n_cols, (long long)h_c.n_frames};
+  const SampleIo back{d_y, d_b, (long long)n_cols, (long long)h_c.n_frames};
+  const dim3 grid((unsigned)gr.n_clips, (unsigned)((n_cols + SPB - 1) / SPB));
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_sample_fwdsub),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS));
+  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_sample_backsub<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS));
+  ACINO_HIP_CHECK(hipMemsetAsync(d_ws, 0, COV_HEAD_BYTES, s));
+  if (gr.nodes_per_clip > 1) {
+    hipLaunchKernelGGL(k_fte_cov_sweep<true>, dim3(gr.n_clips), dim3(256), COV_LDS, s, A);
+    ACINO_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_fte_sample_factors, dim3((unsigned)gr.n_nodes()), dim3(256), SAMPLE_FACT_LDS, s, A);
+  ACINO_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_fte_sample_fwdsub, grid, dim3(256), SAMPLE_LDS, s, A, fwd);
+  ACINO_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_fte_sample_backsub<true>, grid, dim3(256), SAMPLE_LDS, s, A, back);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }

@@ -38,4 +38,12 @@ int launch_fte_sample(const FteConst* d_c, const FteConst& h_c, const acino_fte_
                       double* const H[2], double* const g[2], void* d_ws, int64_t n_samples, const double* d_z,
                       double* d_x_samples, hipStream_t s);
 
+// A^-1 B for n_cols right-hand sides: d_b[n_cols][N][25] holds B on entry (column-major: one trajectory-shaped vector per
+// column; entries of pinned variables count as 0) and A^-1 B on return (exactly 0 for pinned variables), d_y[n_cols][N][25]
+// is scratch (L^-1 B).  The sampler's forward sweep and factors, one forward substitution (k_fte_sample_fwdsub) and the
+// sampler's backward substitution per clip and panel of 64 columns.  Workspace and error word as launch_fte_cov.
+int launch_fte_solve_columns(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
+                             double* const H[2], double* const g[2], void* d_ws, int64_t n_cols, double* d_b, double* d_y,
+                             hipStream_t s);
+
 }  // namespace acino

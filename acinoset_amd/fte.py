@@ -423,6 +423,41 @@ class FTEContext:
             out.update(dx=dx, ddx=ddx)
         return out
 
+    def calibration_sensitivity(self, cov_cams=None):
+        """Sensitivity of the CURRENT iterate to the camera extrinsics (acino_fte_calibration_sensitivity) and the error
+        bars a calibration covariance adds.  ``sens`` [N,25,6C] = S = -A^-1 G: the shift of the minimiser of the solver's own
+        quadratic model (``A`` the matrix ``covariance()`` inverts, bound-active rows exactly 0) per unit change of
+        c = [dw_0, dt_0, ..., dw_C-1, dt_C-1] with R_c <- exp([dw]x) R_c, t_c <- t_c + dt - the order and parametrisation of
+        ``sba.covariance``.  It is not a derivative of the LM end point.  ``cov_cams``: an [6C, 6C] array or tensor, or the
+        dict ``sba.covariance`` / ``return_cov=True`` returns (its ``"cov_cams"`` is used); a wrong shape, a non-finite entry
+        or an asymmetric matrix is a ValueError before any launch.  Returns a dict of tensors on the context's device:
+        ``sens``, ``cov_x_cal`` [N,25,25] = S_n cov_cams S_n^T, ``cov_pos_cal`` [N,20,3,3] = J_l cov_x_cal J_l^T and
+        ``std_pos_cal`` [N,20] = sqrt(trace) in metres - the last three None without ``cov_cams``.  For a calibration that
+        came from OTHER data the total is ``cov_x + cov_x_cal``; for extrinsics refined on the same clips
+        (``refine_extrinsics_from_clips``) it is not valid.  The solver state is not touched.  Whole-sequence fp64 contexts
+        only (RuntimeError otherwise)."""
+        dev = self.device
+        sigma = _cov_cams_matrix(cov_cams, self.C)
+        if sigma is not None:
+            sigma = torch.as_tensor(sigma, dtype=torch.float64, device=dev).contiguous()
+        nbytes = lib().acino_fte_calibration_workspace_bytes(C.byref(self.params))
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        W = 6 * self.C
+
+        def new(*shape):
+            return None if sigma is None else torch.empty((self.N,) + shape, dtype=torch.float64, device=dev)
+
+        sens = torch.empty((self.N, N_ACTIVE, W), dtype=torch.float64, device=dev)
+        cov_x, cov_pos, std_pos = new(N_ACTIVE, N_ACTIVE), new(N_MARKERS, 3, 3), new(N_MARKERS)
+        check(lib().acino_fte_calibration_sensitivity(self._h, ptr(sigma), C.c_void_p(ws_ptr), nbytes, ptr(sens), ptr(cov_x),
+                                                      ptr(cov_pos), ptr(std_pos), stream_ptr()))
+        return dict(sens=sens, cov_x_cal=cov_x, cov_pos_cal=cov_pos, std_pos_cal=std_pos)
+
+    def _calibration(self, cov_cams):
+        """The calibration term as the solve entries return it, or None."""
+        return None if cov_cams is None else self.calibration_sensitivity(cov_cams)
+
     def reprojection(self, cov=True, cov_pos=None):
         """The CURRENT iterate in image space (acino_fte_reprojection), per (frame, camera, marker): a dict of tensors on
         the context's device - ``uv`` [N,C,20,2] the predicted pixel (NaN on a camera's singular plane), ``cov_uv``
@@ -473,6 +508,34 @@ class FTEContext:
             out = self.covariance_rates(with_cov=bool(return_cov))
             return (out[1], out[0]) if return_cov else (None, out)
         return (self.covariance() if return_cov else None), None
+
+
+def _cov_cams_matrix(cov_cams, n_cams):
+    """``cov_cams`` as a checked float64 numpy [6C, 6C] matrix (None stays None): host arithmetic, no launch."""
+    if cov_cams is None:
+        return None
+    if isinstance(cov_cams, dict):
+        if "cov_cams" not in cov_cams:
+            raise ValueError('cov_cams given as a dict must hold "cov_cams" (the dict of sba.covariance)')
+        cov_cams = cov_cams["cov_cams"]
+    a = cov_cams.detach().cpu().numpy() if isinstance(cov_cams, torch.Tensor) else np.asarray(cov_cams)
+    a = np.asarray(a, dtype=np.float64)
+    W = 6 * int(n_cams)
+    if a.shape != (W, W):
+        raise ValueError(f"cov_cams must be [{W}, {W}] (6 per camera: dw, dt), got {tuple(a.shape)}")
+    if not np.isfinite(a).all():
+        raise ValueError("cov_cams has a non-finite entry")
+    if not np.allclose(a, a.T, rtol=1e-12, atol=1e-12 * max(float(np.abs(a).max()), 1e-300)):
+        raise ValueError("cov_cams is not symmetric")
+    return np.ascontiguousarray(a)
+
+
+def _calib_results(res, cal, cov, conv, sl=slice(None)):
+    if cal is not None:
+        res.update(sens_cams=conv(cal["sens"][sl]), cov_x_calib=conv(cal["cov_x_cal"][sl]),
+                   cov_positions_calib=conv(cal["cov_pos_cal"][sl]), std_positions_calib=conv(cal["std_pos_cal"][sl]))
+        if cov is not None:
+            res["std_positions_total"] = conv(torch.sqrt(cov[2][sl] ** 2 + cal["std_pos_cal"][sl] ** 2))
 
 
 def _cov_results(res, cov, rate_cov, conv, sl=slice(None)):
@@ -676,7 +739,8 @@ def _initial_x0(det, x0, init, rig, dlc_thresh, start_frame, camera_model, shape
 
 def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thresh=0.5, start_frame=0,
               max_iter=100, init="nose_line", return_numpy=True, reuse_context=False, camera_model=None, project_func=None,
-              return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, **kw):
+              return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, cov_cams=None,
+              **kw):
     """The FTE solve call.
 
     meas[N,C,20,2] pixel detections, likelihood[N,C,20], cameras as in the scene file (k_arr[C,3,3],
@@ -695,7 +759,12 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     ``seed=sample_seed``; sample axis first).  ``return_reprojection``: results gain the solve in image space -
     ``uv`` [N,C,20,2], ``cov_uv`` [N,C,20,2,2], ``std_uv`` [N,C,20], ``residuals`` and ``weights`` [N,C,20,2], ``mahal2``
     and ``flags`` [N,C,20] (FTEContext.reprojection; ``detection_report`` summarises them); with ``return_cov`` as well the
-    covariance sweeps run once."""
+    covariance sweeps run once.  ``cov_cams`` (an [6C,6C] covariance of the extrinsics, or the dict of ``sba.covariance``;
+    ``calib.extrinsic_cov`` builds a diagonal one): results gain ``sens_cams`` [N,25,6C], ``cov_x_calib`` [N,25,25],
+    ``cov_positions_calib`` [N,20,3,3] and ``std_positions_calib`` [N,20] (FTEContext.calibration_sensitivity: what the
+    uncertainty of the calibration adds), and with ``return_cov`` as well ``std_positions_total`` =
+    sqrt(std_positions^2 + std_positions_calib^2) - valid when the calibration came from other data than these clips."""
+    _cov_cams_matrix(cov_cams, len(k_arr))       # (a malformed matrix fails before the solve, not after)
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     meas_t = meas if isinstance(meas, torch.Tensor) else torch.as_tensor(np.asarray(meas, dtype=np.float64))
     lik_t = likelihood if isinstance(likelihood, torch.Tensor) else torch.as_tensor(np.asarray(likelihood, dtype=np.float64))
@@ -718,6 +787,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         cov, rate_cov = ctx._covariances(return_cov, return_rate_cov) if info["status"] != 5 else (None, None)
         samples = ctx._samples(n_samples, sample_seed) if info["status"] != 5 else None
         reproj = ctx._reprojection(return_reprojection, cov) if info["status"] != 5 else None
+        cal = ctx._calibration(cov_cams) if info["status"] != 5 else None
     except Exception:
         # (the initial guess's flag is read after the solve - no synchronisation in front of it -, but whatever a solve from an
         #  all-zero start ran into must not hide the real cause)
@@ -736,6 +806,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     _cov_results(results, cov, rate_cov, conv)
     _sample_results(results, samples, conv)
     _reproj_results(results, reproj, conv)
+    _calib_results(results, cal, cov, conv)
     return results, info
 
 
@@ -747,7 +818,7 @@ def _derivatives(x_clip, Ts):
 
 def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
                     init="nose_line", return_numpy=True, camera_model=None, project_func=None, return_cov=False,
-                    return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, **kw):
+                    return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, cov_cams=None, **kw):
     """Equal-length clips of one rig solved as ONE problem (BASELINE config 5's batched FTE at full width): the clips
     are laid end to end on the frame axis, the smoothness prior is cut at the clip boundaries (``clip_len``), and the
     block-cyclic reduction runs over the whole chain - every launch is as wide as all clips together, so the narrow
@@ -757,7 +828,9 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     ``camera_model`` / ``project_func`` / ``return_cov`` / ``return_rate_cov`` as in fte_solve (the covariance per clip: the
     clips are independent, so it is the one a solve of the clip alone would give at the same x).  ``n_samples`` / ``sample_seed``
     as in fte_solve: every clip gets its slice of the frame axis of one call's samples.  ``return_reprojection`` as in
-    fte_solve, sliced per clip in the same way."""
+    fte_solve, sliced per clip in the same way.  ``cov_cams`` as in fte_solve (one call; the calibration term of a clip does
+    not depend on the other clips)."""
+    _cov_cams_matrix(cov_cams, len(k_arr))
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     B = len(dets)
     if B == 0:
@@ -792,6 +865,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
         cov, rate_cov = ctx._covariances(return_cov, return_rate_cov)
         samples = ctx._samples(n_samples, sample_seed)
         reproj = ctx._reprojection(return_reprojection, cov)
+        cal = ctx._calibration(cov_cams)
         conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
         out = []
         for b in range(B):
@@ -802,6 +876,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
             _cov_results(res, cov, rate_cov, conv, slice(b * S, (b + 1) * S))
             _sample_results(res, samples, conv, slice(b * S, (b + 1) * S))
             _reproj_results(res, reproj, conv, slice(b * S, (b + 1) * S))
+            _calib_results(res, cal, cov, conv, slice(b * S, (b + 1) * S))
             out.append((res, dict(info, clips=B, cost_is_sum_over_clips=True)))
         return out
     finally:
@@ -810,7 +885,8 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
 
 def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0.5, start_frames=None, max_iter=100,
                     init="nose_line", n_streams=8, peek_every=8, return_numpy=True, camera_model=None, project_func=None,
-                    return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, **kw):
+                    return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False,
+                    cov_cams=None, **kw):
     """Several independent sequences (BASELINE config 5's "batched FTE": one rig, many clips) solved concurrently
     on ONE GPU.  Every sequence gets its own context and runs on one of ``n_streams`` HIP streams; a Levenberg-
     Marquardt step never synchronises with the host (the accept/reject controller is a device kernel and the step is
@@ -819,7 +895,8 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     keep all of them busy whatever the stream-to-queue assignment).  ``dets``: list of det[N_b, C, 20, 3] (lengths may differ).
     Returns a list of (results, info) exactly as ``fte_solve`` would for each sequence alone.  The reference solves
     clips one after another (src/all_optimizations.py:22, one ``fte()`` call per data directory).  ``camera_model`` /
-    ``project_func`` / ``return_cov`` / ``return_rate_cov`` / ``n_samples`` / ``sample_seed`` / ``return_reprojection`` as in fte_solve."""
+    ``project_func`` / ``return_cov`` / ``return_rate_cov`` / ``n_samples`` / ``sample_seed`` / ``return_reprojection`` / ``cov_cams`` as in fte_solve."""
+    _cov_cams_matrix(cov_cams, len(k_arr))
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     _lib.require_gpu()
     B = len(dets)
@@ -872,6 +949,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
                 _cov_results(res, cov, rate_cov, conv)
                 _sample_results(res, ctxs[b]._samples(n_samples, sample_seed), conv)
                 _reproj_results(res, ctxs[b]._reprojection(return_reprojection, cov), conv)
+                _calib_results(res, ctxs[b]._calibration(cov_cams), cov, conv)
                 out.append((res, infos[b]))
         for s in streams:
             torch.cuda.current_stream().wait_stream(s)

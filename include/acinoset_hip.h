@@ -331,6 +331,45 @@ int acino_fte_covariance_rates(acino_fte_ctx* ctx, double ts, void* d_ws, size_t
 size_t acino_fte_sample_workspace_bytes(const acino_fte_params* p);
 int acino_fte_sample(acino_fte_ctx* ctx, int64_t n_samples, const double* d_z, void* d_ws, size_t ws_bytes,
                      double* d_x_samples, double* d_pos_samples, void* stream);
+/* Error bars that include the CALIBRATION: the sensitivity S = d x_hat / d c of the whole trajectory to the camera
+ * extrinsics, and the "consider" covariance S Sigma_c S^T it gives for a covariance Sigma_c of the extrinsics.
+ * All quantities are at the context's CURRENT iterate.  A, the pinned (bound-active) set and the node grid are those of
+ * acino_fte_covariance.
+ * Camera parameters are c = [dw_0, dt_0, ..., dw_C-1, dt_C-1], applied as R_c <- exp([dw]x) R_c, t_c <- t_c + dt.  This is
+ * the order and parametrisation of acino_sba_covariance, so cov_cams plugs in unchanged.
+ * For a detection (n, c, l) with world point p = FK_l(x_n):
+ *   J_x = J_pi J_l (2 x 25).
+ *   J_c = J_pi R_c^T [ -[R_c p]x | I_3 ] (2 x 6), the derivative of the predicted pixel with respect to (dw_c, dt_c).
+ *   J_pi = d uv / d p in the world frame, from the context's own camera model, fisheye or pinhole.
+ *   The per-component weight is w^2 h, with w and h exactly as the assembly forms them.  h is the weight
+ *   acino_fte_reprojection reports; w = 0 below the likelihood threshold, for non-finite pixels and on the singular plane.
+ * The cross term and the solve:
+ *   G_n[:, 6c:6c+6] = sum over l and both pixel components of J_x^T (w^2 h) J_c, shape [25, 6C] per frame.
+ *   S = -A^-1 G, shape [N, 25, 6C].
+ *   Rows of G for pinned variables are 0, so rows of S for pinned variables are exactly 0.
+ * S is the shift of the minimiser of the solver's own quadratic model per unit change of the extrinsics.  It uses the same
+ * Gauss-Newton / secant-weight approximation that A^-1 itself makes.  S is NOT a derivative of the Levenberg-Marquardt end
+ * point: a finite difference of re-solves with perturbed cameras agrees with it on well-determined states (about 1 %) and
+ * is meaningless along the flat valleys of the objective, where the end point depends on the path.
+ * Given Sigma_c = d_cov_cams[6C][6C] (e.g. cov_cams of acino_sba_covariance; only PSD - a held camera has zero rows - so it
+ * is multiplied, T = S_n Sigma_c, then T S_n^T, never factored):
+ *   d_sens[N][25][6C]          S
+ *   d_cov_x_cal[N][25][25]     S_n Sigma_c S_n^T, symmetric to the bit
+ *   d_cov_pos_cal[N][20][3][3] J_l cov_x_cal[n] J_l^T, symmetric to the bit
+ *   d_std_pos_cal[N][20]       sqrt(trace(cov_pos_cal)), metres
+ * Any output may be NULL, but not all of them; a cov / std output without d_cov_cams is ACINO_ERR_INVALID_ARG.  Argument
+ * checks come before any device call.  The total covariance of a trajectory solved on a calibration that came from OTHER data
+ * is cov_x + cov_x_cal; it is NOT valid for extrinsics refined on the same clips (the two errors are then correlated).
+ * The calibration term is perfectly correlated across frames: smoothing does not average it out.
+ * Launches: k_fte_calib_rhs (-G as 6C columns), the sampler's forward sweep and factors, one forward and one backward
+ * substitution per clip and panel of 64 columns, k_fte_calib_combine.  Every clip on its own node grid; the result for one
+ * clip does not depend on the others.  Workspace: the covariance workspace + 2 * 6C * N * 25 doubles, 256-byte aligned
+ * (ACINO_ERR_WORKSPACE otherwise); ACINO_ERR_UNSUPPORTED, ACINO_ERR_NUMERIC, the one synchronisation and what the call leaves
+ * untouched (solver state, buffers, captured graphs): as acino_fte_covariance. */
+size_t acino_fte_calibration_workspace_bytes(const acino_fte_params* p);
+int acino_fte_calibration_sensitivity(acino_fte_ctx* ctx, const double* d_cov_cams /* [6C][6C] or NULL */, void* d_ws,
+                                      size_t ws_bytes, double* d_sens, double* d_cov_x_cal, double* d_cov_pos_cal,
+                                      double* d_std_pos_cal, void* stream);
 /* The solve seen in IMAGE space, at the CURRENT iterate: for every (frame n, camera c, marker l), with p = FK_l(x_n) (the
  * FK of acino_fk_active) and (uv, J_pi, z_cam) the projection of the context's own camera model - the device function the
  * assembly calls: the reference's pt3d_to_2d for acino_fte_create, cv2.projectPoints for acino_fte_create_pinhole -,
