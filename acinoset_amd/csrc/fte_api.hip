@@ -1377,7 +1377,7 @@ int acino_fte_get_grad_hess(acino_fte_ctx* ctx, double* d_g, double* d_h, void* 
 }
 
 // ---- posterior covariance (csrc/fte_cov.hip) ----
-static int cov_supported(const FteConst& h, const char* who = "acino_fte_covariance") {
+static int cov_supported(const FteConst& h, const char* who) {
   const char* why = nullptr;
   if (h.pin_left || h.pin_right || h.n_global != h.n_frames || h.n_offset != 0) why = "a sharded context (one rank's part of a sequence)";
   else if (h.own_lo != 0 || h.own_hi != h.n_frames) why = "a windowed context (own range)";
@@ -1385,6 +1385,34 @@ static int cov_supported(const FteConst& h, const char* who = "acino_fte_covaria
   if (why) {
     set_error("%s: not supported for %s; it needs the whole sequence in one fp64 context", who, why);
     return ACINO_ERR_UNSUPPORTED;
+  }
+  return ACINO_OK;
+}
+
+// What the launchers of fte_cov.hip, fte_calib.hip and fte_reproj.hip read of a context
+static PostIn post_in(const acino_fte_ctx* ctx) {
+  const Buffers& b = ctx->b;
+  return PostIn{b.cst, &ctx->h, b.state, ctx->d_det, b.x, b.H, b.g};
+}
+
+// The entries with a workspace, after their own ACINO_REQUIREs: the context, then the workspace - the last test before the
+// first device call.  post_finish: the error word of the factorisations, the call's one synchronisation.
+static int post_begin(const char* who, const acino_fte_ctx* ctx, const void* d_ws, size_t ws_bytes, size_t need) {
+  if (int rc = cov_supported(ctx->h, who)) return rc;
+  if (ws_bytes < need || ((uintptr_t)d_ws & 255) != 0) {
+    set_error("%s: workspace too small or misaligned: need %zu bytes at a 256-byte boundary, got %zu", who, need, ws_bytes);
+    return ACINO_ERR_WORKSPACE;
+  }
+  return ACINO_OK;
+}
+
+static int post_finish(const char* who, const void* d_ws, hipStream_t s) {
+  int flag = 0;
+  ACINO_HIP_CHECK(hipMemcpyAsync(&flag, d_ws, sizeof(int), hipMemcpyDeviceToHost, s));
+  ACINO_HIP_CHECK(hipStreamSynchronize(s));
+  if (flag) {
+    set_error("%s: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive definite)", who);
+    return ACINO_ERR_NUMERIC;
   }
   return ACINO_OK;
 }
@@ -1398,26 +1426,12 @@ size_t acino_fte_covariance_workspace_bytes(const acino_fte_params* p) {
 static int cov_run(const char* who, acino_fte_ctx* ctx, double ts, void* d_ws, size_t ws_bytes, double* d_cov_x,
                    double* d_cov_pos, double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel,
                    double* d_std_vel, void* stream) {
-  int rc = cov_supported(ctx->h);
-  if (rc) return rc;
-  const size_t need = cov_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len);
-  if (ws_bytes < need || ((uintptr_t)d_ws & 255) != 0) {
-    set_error("covariance workspace too small or misaligned: need %zu bytes at a 256-byte boundary, got %zu", need, ws_bytes);
-    return ACINO_ERR_WORKSPACE;
-  }
+  if (int rc = post_begin(who, ctx, d_ws, ws_bytes, cov_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const Buffers& b = ctx->b;
-  rc = launch_fte_cov_rates(b.cst, ctx->h, b.state, b.x, b.H, b.g, d_ws, d_cov_x, d_cov_pos, d_std_pos, d_cov_dx, d_cov_ddx,
-                            d_cov_vel, d_std_vel, ts, s);
-  if (rc) return rc;
-  int flag = 0;
-  ACINO_HIP_CHECK(hipMemcpyAsync(&flag, d_ws, sizeof(int), hipMemcpyDeviceToHost, s));
-  ACINO_HIP_CHECK(hipStreamSynchronize(s));
-  if (flag) {
-    set_error("%s: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive definite)", who);
-    return ACINO_ERR_NUMERIC;
-  }
-  return ACINO_OK;
+  if (int rc = launch_fte_cov_rates(post_in(ctx), d_ws, d_cov_x, d_cov_pos, d_std_pos, d_cov_dx, d_cov_ddx, d_cov_vel, d_std_vel,
+                                    ts, s))
+    return rc;
+  return post_finish(who, d_ws, s);
 }
 
 int acino_fte_covariance(acino_fte_ctx* ctx, void* d_ws, size_t ws_bytes, double* d_cov_x, double* d_cov_pos,
@@ -1448,34 +1462,19 @@ size_t acino_fte_sample_workspace_bytes(const acino_fte_params* p) {
 
 int acino_fte_sample(acino_fte_ctx* ctx, int64_t n_samples, const double* d_z, void* d_ws, size_t ws_bytes,
                      double* d_x_samples, double* d_pos_samples, void* stream) {
+  const char* who = "acino_fte_sample";
   ACINO_REQUIRE(ctx && d_ws, "null");
   ACINO_REQUIRE(n_samples >= 1, "n_samples");
   ACINO_REQUIRE(d_z && d_x_samples, "null buffer");
   ACINO_REQUIRE((n_samples + 63) / 64 <= 65535, "n_samples (at most 65535 panels of 64)");
   ACINO_REQUIRE(d_z != d_x_samples, "d_z must not alias d_x_samples");
-  int rc = cov_supported(ctx->h, "acino_fte_sample");
-  if (rc) return rc;
-  const size_t need = cov_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len);
-  if (ws_bytes < need || ((uintptr_t)d_ws & 255) != 0) {
-    set_error("sample workspace too small or misaligned: need %zu bytes at a 256-byte boundary, got %zu", need, ws_bytes);
-    return ACINO_ERR_WORKSPACE;
-  }
+  if (int rc = post_begin(who, ctx, d_ws, ws_bytes, cov_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const Buffers& b = ctx->b;
-  rc = launch_fte_sample(b.cst, ctx->h, b.state, b.x, b.H, b.g, d_ws, n_samples, d_z, d_x_samples, s);
-  if (rc) return rc;
+  if (int rc = launch_fte_sample(post_in(ctx), d_ws, n_samples, d_z, d_x_samples, s)) return rc;
   if (d_pos_samples) {
-    rc = launch_fk_active(d_x_samples - HALO * NP, n_samples * (int64_t)ctx->h.n_frames, d_pos_samples, s);
-    if (rc) return rc;
+    if (int rc = launch_fk_active(d_x_samples - HALO * NP, n_samples * (int64_t)ctx->h.n_frames, d_pos_samples, s)) return rc;
   }
-  int flag = 0;
-  ACINO_HIP_CHECK(hipMemcpyAsync(&flag, d_ws, sizeof(int), hipMemcpyDeviceToHost, s));
-  ACINO_HIP_CHECK(hipStreamSynchronize(s));
-  if (flag) {
-    set_error("acino_fte_sample: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive definite)");
-    return ACINO_ERR_NUMERIC;
-  }
-  return ACINO_OK;
+  return post_finish(who, d_ws, s);
 }
 
 // ---- sensitivity to the camera extrinsics (csrc/fte_calib.hip) ----
@@ -1488,30 +1487,15 @@ size_t acino_fte_calibration_workspace_bytes(const acino_fte_params* p) {
 int acino_fte_calibration_sensitivity(acino_fte_ctx* ctx, const double* d_cov_cams, void* d_ws, size_t ws_bytes,
                                       double* d_sens, double* d_cov_x_cal, double* d_cov_pos_cal, double* d_std_pos_cal,
                                       void* stream) {
+  const char* who = "acino_fte_calibration_sensitivity";
   ACINO_REQUIRE(ctx && d_ws, "null");
   ACINO_REQUIRE(d_sens || d_cov_x_cal || d_cov_pos_cal || d_std_pos_cal, "no output asked for");
   ACINO_REQUIRE(d_cov_cams || !(d_cov_x_cal || d_cov_pos_cal || d_std_pos_cal), "a cov / std output needs d_cov_cams");
-  int rc = cov_supported(ctx->h, "acino_fte_calibration_sensitivity");
-  if (rc) return rc;
-  const size_t need = calib_workspace_bytes(ctx->h.n_frames, ctx->h.clip_len, ctx->h.n_cams);
-  if (ws_bytes < need || ((uintptr_t)d_ws & 255) != 0) {
-    set_error("calibration workspace too small or misaligned: need %zu bytes at a 256-byte boundary, got %zu", need, ws_bytes);
-    return ACINO_ERR_WORKSPACE;
-  }
+  const FteConst& h = ctx->h;
+  if (int rc = post_begin(who, ctx, d_ws, ws_bytes, calib_workspace_bytes(h.n_frames, h.clip_len, h.n_cams))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const Buffers& b = ctx->b;
-  rc = launch_fte_calib(b.cst, ctx->h, b.state, ctx->d_det, b.x, b.H, b.g, d_ws, d_cov_cams, d_sens, d_cov_x_cal,
-                        d_cov_pos_cal, d_std_pos_cal, s);
-  if (rc) return rc;
-  int flag = 0;
-  ACINO_HIP_CHECK(hipMemcpyAsync(&flag, d_ws, sizeof(int), hipMemcpyDeviceToHost, s));
-  ACINO_HIP_CHECK(hipStreamSynchronize(s));
-  if (flag) {
-    set_error("acino_fte_calibration_sensitivity: non-positive pivot (the Gauss-Newton matrix at this iterate is not positive "
-              "definite)");
-    return ACINO_ERR_NUMERIC;
-  }
-  return ACINO_OK;
+  if (int rc = launch_fte_calib(post_in(ctx), d_ws, d_cov_cams, d_sens, d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal, s)) return rc;
+  return post_finish(who, d_ws, s);
 }
 
 // ---- the iterate in image space (csrc/fte_reproj.hip): one launch, no synchronisation, no workspace ----
@@ -1520,9 +1504,7 @@ int acino_fte_reprojection(acino_fte_ctx* ctx, const double* d_cov_pos, double* 
   ACINO_REQUIRE(ctx, "null context");
   ACINO_REQUIRE(d_uv || d_cov_uv || d_res || d_weight || d_mahal2 || d_flags, "no output asked for");
   ACINO_REQUIRE(!d_cov_uv || d_cov_pos, "d_cov_uv needs d_cov_pos");
-  const Buffers& b = ctx->b;
-  return launch_fte_reproj(b.cst, ctx->h, b.state, ctx->d_det, b.x, d_cov_pos, d_uv, d_cov_uv, d_res, d_weight, d_mahal2,
-                           d_flags, (hipStream_t)stream);
+  return launch_fte_reproj(post_in(ctx), d_cov_pos, d_uv, d_cov_uv, d_res, d_weight, d_mahal2, d_flags, (hipStream_t)stream);
 }
 
 int acino_fte_get_result(acino_fte_ctx* ctx, double ts, double* d_x, double* d_pos, double* d_dx, double* d_ddx,

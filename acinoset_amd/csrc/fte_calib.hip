@@ -15,7 +15,7 @@
 //
 // J_c = d uv / d (dw_c, dt_c) for R_c <- exp([dw]x) R_c, t_c <- t_c + dt: the camera-frame point moves by dw x (R_c p) + dt,
 // so with j the camera-frame Jacobian row of a pixel component J_c = [ (R_c p) x j | j ].
-// No workgroup waits for another; NaNs of a failed factorisation run through (the error word is launch_fte_cov's).
+// No workgroup waits for another; NaNs of a failed factorisation run through (the error word is launch_fte_cov_rates').
 #include "fte_calib.hpp"
 
 #include "fte_cov_dev.hpp"
@@ -207,32 +207,23 @@ k_fte_calib_combine(const FteConst* __restrict__ cst, const acino_fte_state* __r
   if (std_pos && tid < NL) std_pos[n * NL + tid] = sqrt(fmax(Cp[tid * 9] + Cp[tid * 9 + 4] + Cp[tid * 9 + 8], 0.0));
 }
 
-int launch_fte_calib(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, const double* d_det,
-                     double* const x[2], double* const H[2], double* const g[2], void* d_ws, const double* d_cov_cams,
-                     double* d_sens, double* d_cov_x_cal, double* d_cov_pos_cal, double* d_std_pos_cal, hipStream_t s) {
+int launch_fte_calib(const PostIn& in, void* d_ws, const double* d_cov_cams, double* d_sens, double* d_cov_x_cal,
+                     double* d_cov_pos_cal, double* d_std_pos_cal, hipStream_t s) {
+  const FteConst& h_c = *in.h_c;
   const int N = h_c.n_frames, C = h_c.n_cams;
   if (N == 0) return ACINO_OK;
   double* d_b = reinterpret_cast<double*>(reinterpret_cast<char*>(d_ws) + cov_workspace_bytes(N, h_c.clip_len));
   double* d_y = d_b + (size_t)(6 * C) * N * NP;
   const size_t lds_rhs = calib_rhs_lds(C), lds_comb = calib_combine_lds(C);
-  if (h_c.camera_model == CAMERA_PINHOLE) {
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_calib_rhs<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rhs));
-    hipLaunchKernelGGL(k_fte_calib_rhs<true>, dim3(N), dim3(256), lds_rhs, s, d_c, d_st, d_det, x[0], x[1], g[0], g[1], H[0],
-                       H[1], d_b);
-  } else {
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_calib_rhs<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rhs));
-    hipLaunchKernelGGL(k_fte_calib_rhs<false>, dim3(N), dim3(256), lds_rhs, s, d_c, d_st, d_det, x[0], x[1], g[0], g[1], H[0],
-                       H[1], d_b);
-  }
+  const auto k_rhs = h_c.camera_model == CAMERA_PINHOLE ? k_fte_calib_rhs<true> : k_fte_calib_rhs<false>;
+  ACINO_HIP_CHECK(set_dyn_lds(k_rhs, lds_rhs));
+  hipLaunchKernelGGL(k_rhs, dim3(N), dim3(256), lds_rhs, s, in.d_c, in.d_st, in.d_det, in.x[0], in.x[1], in.g[0], in.g[1],
+                     in.H[0], in.H[1], d_b);
   ACINO_LAUNCH_CHECK();
-  int rc = launch_fte_solve_columns(d_c, h_c, d_st, x, H, g, d_ws, 6 * C, d_b, d_y, s);
-  if (rc) return rc;
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_calib_combine),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_comb));
-  hipLaunchKernelGGL(k_fte_calib_combine, dim3(N), dim3(256), lds_comb, s, d_c, d_st, x[0], x[1], d_b, d_cov_cams, d_sens,
-                     d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal);
+  if (int rc = launch_fte_solve_columns(in, d_ws, 6 * C, d_b, d_y, s)) return rc;
+  ACINO_HIP_CHECK(set_dyn_lds(k_fte_calib_combine, lds_comb));
+  hipLaunchKernelGGL(k_fte_calib_combine, dim3(N), dim3(256), lds_comb, s, in.d_c, in.d_st, in.x[0], in.x[1], d_b, d_cov_cams,
+                     d_sens, d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }

@@ -9,10 +9,9 @@ namespace acino {
 size_t calib_workspace_bytes(int64_t n_frames, int64_t clip_len, int n_cams);
 
 // S = -A^-1 G on stream s at the CURRENT iterate (st->cur selects the buffers), then the products with d_cov_cams[6C][6C]
-// (may be null: then only d_sens is written).  d_det[N][C][20][3] the context's detections.  Outputs as in acinoset_hip.h,
-// any may be null.  d_ws: calib_workspace_bytes, 256-byte aligned; its first int is the error word of launch_fte_cov.
-int launch_fte_calib(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, const double* d_det,
-                     double* const x[2], double* const H[2], double* const g[2], void* d_ws, const double* d_cov_cams,
-                     double* d_sens, double* d_cov_x_cal, double* d_cov_pos_cal, double* d_std_pos_cal, hipStream_t s);
+// (may be null: then only d_sens is written).  in.d_det[N][C][20][3] the context's detections.  Outputs as in acinoset_hip.h,
+// any may be null.  d_ws: calib_workspace_bytes, 256-byte aligned; its first int is the error word of launch_fte_cov_rates.
+int launch_fte_calib(const PostIn& in, void* d_ws, const double* d_cov_cams, double* d_sens, double* d_cov_x_cal,
+                     double* d_cov_pos_cal, double* d_std_pos_cal, hipStream_t s);
 
 }  // namespace acino

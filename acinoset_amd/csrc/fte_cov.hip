@@ -846,39 +846,51 @@ __global__ void __launch_bounds__(256) k_fte_sample_backsub(CovArgs A, SampleIo 
   }
 }
 
-int launch_fte_sample(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
-                      double* const H[2], double* const g[2], void* d_ws, int64_t n_samples, const double* d_z,
-                      double* d_x_samples, hipStream_t s) {
-  const CovGrid gr = cov_grid(h_c.n_frames, h_c.clip_len);
+namespace {
+// The arguments every kernel here takes: inputs, error word, corrections and node grid; no output, inv_ts = 1.
+CovArgs cov_args(const PostIn& in, void* d_ws) {
+  const CovGrid gr = cov_grid(in.h_c->n_frames, in.h_c->clip_len);
   CovArgs A = {};
-  A.cst = d_c;
-  A.st = d_st;
-  A.x0 = x[0];
-  A.x1 = x[1];
-  A.g0 = g[0];
-  A.g1 = g[1];
-  A.H0 = H[0];
-  A.H1 = H[1];
+  A.cst = in.d_c;
+  A.st = in.d_st;
+  A.x0 = in.x[0];
+  A.x1 = in.x[1];
+  A.g0 = in.g[0];
+  A.g1 = in.g[1];
+  A.H0 = in.H[0];
+  A.H1 = in.H[1];
   A.err = reinterpret_cast<int*>(d_ws);
   A.terms = reinterpret_cast<double*>(reinterpret_cast<char*>(d_ws) + COV_HEAD_BYTES);
   A.n_clips = gr.n_clips;
   A.nodes_per_clip = gr.nodes_per_clip;
   A.clip = gr.clip;
   A.inv_ts = 1.0;
-  const SampleIo io{d_z, d_x_samples, (long long)n_samples, (long long)h_c.n_frames};
-  const int64_t panels = (n_samples + SPB - 1) / SPB;
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_sample_backsub<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS));
-  ACINO_HIP_CHECK(hipMemsetAsync(d_ws, 0, COV_HEAD_BYTES, s));
-  if (gr.nodes_per_clip > 1) {
-    hipLaunchKernelGGL(k_fte_cov_sweep<true>, dim3(gr.n_clips), dim3(256), COV_LDS, s, A);
+  return A;
+}
+
+unsigned cov_nodes(const CovArgs& A) { return (unsigned)((int64_t)A.n_clips * A.nodes_per_clip); }
+
+// What the sampler and the column solve start with: the error word cleared, CF_k from the forward sweep, U_k^T of every node
+int sample_factors(const CovArgs& A, hipStream_t s) {
+  ACINO_HIP_CHECK(set_dyn_lds(k_fte_cov_sweep<true>, COV_LDS));
+  ACINO_HIP_CHECK(hipMemsetAsync(A.err, 0, COV_HEAD_BYTES, s));
+  if (A.nodes_per_clip > 1) {
+    hipLaunchKernelGGL(k_fte_cov_sweep<true>, dim3(A.n_clips), dim3(256), COV_LDS, s, A);
     ACINO_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_fte_sample_factors, dim3((unsigned)gr.n_nodes()), dim3(256), SAMPLE_FACT_LDS, s, A);
+  hipLaunchKernelGGL(k_fte_sample_factors, dim3(cov_nodes(A)), dim3(256), SAMPLE_FACT_LDS, s, A);
   ACINO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_fte_sample_backsub<false>, dim3((unsigned)gr.n_clips, (unsigned)panels), dim3(256), SAMPLE_LDS, s, A, io);
+  return ACINO_OK;
+}
+}  // namespace
+
+int launch_fte_sample(const PostIn& in, void* d_ws, int64_t n_samples, const double* d_z, double* d_x_samples, hipStream_t s) {
+  const CovArgs A = cov_args(in, d_ws);
+  const SampleIo io{d_z, d_x_samples, (long long)n_samples, (long long)in.h_c->n_frames};
+  const int64_t panels = (n_samples + SPB - 1) / SPB;
+  ACINO_HIP_CHECK(set_dyn_lds(k_fte_sample_backsub<false>, SAMPLE_LDS));
+  if (int rc = sample_factors(A, s)) return rc;
+  hipLaunchKernelGGL(k_fte_sample_backsub<false>, dim3((unsigned)A.n_clips, (unsigned)panels), dim3(256), SAMPLE_LDS, s, A, io);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }
@@ -1027,41 +1039,14 @@ __global__ void __launch_bounds__(256) k_fte_sample_fwdsub(CovArgs A, SampleIo i
   }
 }
 
-int launch_fte_solve_columns(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
-                             double* const H[2], double* const g[2], void* d_ws, int64_t n_cols, double* d_b, double* d_y,
-                             hipStream_t s) {
-  const CovGrid gr = cov_grid(h_c.n_frames, h_c.clip_len);
-  CovArgs A = {};
-  A.cst = d_c;
-  A.st = d_st;
-  A.x0 = x[0];
-  A.x1 = x[1];
-  A.g0 = g[0];
-  A.g1 = g[1];
-  A.H0 = H[0];
-  A.H1 = H[1];
-  A.err = reinterpret_cast<int*>(d_ws);
-  A.terms = reinterpret_cast<double*>(reinterpret_cast<char*>(d_ws) + COV_HEAD_BYTES);
-  A.n_clips = gr.n_clips;
-  A.nodes_per_clip = gr.nodes_per_clip;
-  A.clip = gr.clip;
-  A.inv_ts = 1.0;
-  const SampleIo fwd{d_b, d_y, (long long)n_cols, (long long)h_c.n_frames};
-  const SampleIo back{d_y, d_b, (long long)n_cols, (long long)h_c.n_frames};
-  const dim3 grid((unsigned)gr.n_clips, (unsigned)((n_cols + SPB - 1) / SPB));
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_sample_fwdsub),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS));
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_sample_backsub<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS));
-  ACINO_HIP_CHECK(hipMemsetAsync(d_ws, 0, COV_HEAD_BYTES, s));
-  if (gr.nodes_per_clip > 1) {
-    hipLaunchKernelGGL(k_fte_cov_sweep<true>, dim3(gr.n_clips), dim3(256), COV_LDS, s, A);
-    ACINO_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_fte_sample_factors, dim3((unsigned)gr.n_nodes()), dim3(256), SAMPLE_FACT_LDS, s, A);
-  ACINO_LAUNCH_CHECK();
+int launch_fte_solve_columns(const PostIn& in, void* d_ws, int64_t n_cols, double* d_b, double* d_y, hipStream_t s) {
+  const CovArgs A = cov_args(in, d_ws);
+  const SampleIo fwd{d_b, d_y, (long long)n_cols, (long long)in.h_c->n_frames};
+  const SampleIo back{d_y, d_b, (long long)n_cols, (long long)in.h_c->n_frames};
+  const dim3 grid((unsigned)A.n_clips, (unsigned)((n_cols + SPB - 1) / SPB));
+  ACINO_HIP_CHECK(set_dyn_lds(k_fte_sample_fwdsub, SAMPLE_LDS));
+  ACINO_HIP_CHECK(set_dyn_lds(k_fte_sample_backsub<true>, SAMPLE_LDS));
+  if (int rc = sample_factors(A, s)) return rc;
   hipLaunchKernelGGL(k_fte_sample_fwdsub, grid, dim3(256), SAMPLE_LDS, s, A, fwd);
   ACINO_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_fte_sample_backsub<true>, grid, dim3(256), SAMPLE_LDS, s, A, back);
@@ -1069,32 +1054,9 @@ int launch_fte_solve_columns(const FteConst* d_c, const FteConst& h_c, const aci
   return ACINO_OK;
 }
 
-int launch_fte_cov(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
-                   double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
-                   double* d_std_pos, hipStream_t s) {
-  return launch_fte_cov_rates(d_c, h_c, d_st, x, H, g, d_ws, d_cov_x, d_cov_pos, d_std_pos, nullptr, nullptr, nullptr,
-                              nullptr, 1.0, s);
-}
-
-int launch_fte_cov_rates(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, double* const x[2],
-                         double* const H[2], double* const g[2], void* d_ws, double* d_cov_x, double* d_cov_pos,
-                         double* d_std_pos, double* d_cov_dx, double* d_cov_ddx, double* d_cov_vel, double* d_std_vel,
-                         double ts, hipStream_t s) {
-  const CovGrid gr = cov_grid(h_c.n_frames, h_c.clip_len);
-  CovArgs A;
-  A.cst = d_c;
-  A.st = d_st;
-  A.x0 = x[0];
-  A.x1 = x[1];
-  A.g0 = g[0];
-  A.g1 = g[1];
-  A.H0 = H[0];
-  A.H1 = H[1];
-  A.err = reinterpret_cast<int*>(d_ws);
-  A.terms = reinterpret_cast<double*>(reinterpret_cast<char*>(d_ws) + COV_HEAD_BYTES);
-  A.n_clips = gr.n_clips;
-  A.nodes_per_clip = gr.nodes_per_clip;
-  A.clip = gr.clip;
+int launch_fte_cov_rates(const PostIn& in, void* d_ws, double* d_cov_x, double* d_cov_pos, double* d_std_pos, double* d_cov_dx,
+                         double* d_cov_ddx, double* d_cov_vel, double* d_std_vel, double ts, hipStream_t s) {
+  CovArgs A = cov_args(in, d_ws);
   A.cov_x = d_cov_x;
   A.cov_pos = d_cov_pos;
   A.std_pos = d_std_pos;
@@ -1104,23 +1066,20 @@ int launch_fte_cov_rates(const FteConst* d_c, const FteConst& h_c, const acino_f
   A.std_vel = d_std_vel;
   A.inv_ts = 1.0 / ts;
   const bool blocks = d_cov_x || d_cov_pos || d_std_pos, rates = d_cov_dx || d_cov_ddx || d_cov_vel || d_std_vel;
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_sweep<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_combine),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_LDS));
+  ACINO_HIP_CHECK(set_dyn_lds(k_fte_cov_sweep<false>, COV_LDS));
+  ACINO_HIP_CHECK(set_dyn_lds(k_fte_cov_combine, COV_LDS));
   ACINO_HIP_CHECK(hipMemsetAsync(d_ws, 0, COV_HEAD_BYTES, s));
-  if (gr.nodes_per_clip > 1) {
-    hipLaunchKernelGGL(k_fte_cov_sweep<false>, dim3(2 * gr.n_clips), dim3(256), COV_LDS, s, A);
+  if (A.nodes_per_clip > 1) {
+    hipLaunchKernelGGL(k_fte_cov_sweep<false>, dim3(2 * A.n_clips), dim3(256), COV_LDS, s, A);
     ACINO_LAUNCH_CHECK();
   }
   if (blocks) {
-    hipLaunchKernelGGL(k_fte_cov_combine, dim3((unsigned)gr.n_nodes()), dim3(256), COV_LDS, s, A);
+    hipLaunchKernelGGL(k_fte_cov_combine, dim3(cov_nodes(A)), dim3(256), COV_LDS, s, A);
     ACINO_LAUNCH_CHECK();
   }
   if (rates) {
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_cov_rates),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)COV_RATES_LDS));
-    hipLaunchKernelGGL(k_fte_cov_rates, dim3((unsigned)gr.n_nodes()), dim3(256), COV_RATES_LDS, s, A);
+    ACINO_HIP_CHECK(set_dyn_lds(k_fte_cov_rates, COV_RATES_LDS));
+    hipLaunchKernelGGL(k_fte_cov_rates, dim3(cov_nodes(A)), dim3(256), COV_RATES_LDS, s, A);
     ACINO_LAUNCH_CHECK();
   }
   return ACINO_OK;

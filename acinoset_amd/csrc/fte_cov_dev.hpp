@@ -53,4 +53,10 @@ __device__ __forceinline__ double rate_jac(const CovFrame& F, int l, int i, int 
   return i == 0 ? w[1] * d2 - w[2] * d1 : (i == 1 ? w[2] * d0 - w[0] * d2 : w[0] * d1 - w[1] * d0);
 }
 
+// Host: the opt-in of one kernel to `bytes` of dynamic LDS on the current device.  Made per call, beside the launch.
+template <class Kernel>
+inline hipError_t set_dyn_lds(Kernel* kernel, size_t bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
 }  // namespace acino

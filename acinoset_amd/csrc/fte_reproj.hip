@@ -140,17 +140,13 @@ k_fte_reproj(const FteConst* __restrict__ cst, const acino_fte_state* __restrict
   }
 }
 
-int launch_fte_reproj(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, const double* d_det,
-                      double* const x[2], const double* d_cov_pos, double* d_uv, double* d_cov_uv, double* d_res,
+int launch_fte_reproj(const PostIn& in, const double* d_cov_pos, double* d_uv, double* d_cov_uv, double* d_res,
                       double* d_weight, double* d_mahal2, uint8_t* d_flags, hipStream_t s) {
-  const int nb = (h_c.n_frames + FPB - 1) / FPB;
+  const int nb = (in.h_c->n_frames + FPB - 1) / FPB;
   if (nb == 0) return ACINO_OK;
-  if (h_c.camera_model == CAMERA_PINHOLE)
-    hipLaunchKernelGGL(k_fte_reproj<true>, dim3(nb), dim3(256), 0, s, d_c, d_st, d_det, x[0], x[1], d_cov_pos, d_uv, d_cov_uv,
-                       d_res, d_weight, d_mahal2, d_flags);
-  else
-    hipLaunchKernelGGL(k_fte_reproj<false>, dim3(nb), dim3(256), 0, s, d_c, d_st, d_det, x[0], x[1], d_cov_pos, d_uv, d_cov_uv,
-                       d_res, d_weight, d_mahal2, d_flags);
+  const auto k = in.h_c->camera_model == CAMERA_PINHOLE ? k_fte_reproj<true> : k_fte_reproj<false>;
+  hipLaunchKernelGGL(k, dim3(nb), dim3(256), 0, s, in.d_c, in.d_st, in.d_det, in.x[0], in.x[1], d_cov_pos, d_uv, d_cov_uv, d_res,
+                     d_weight, d_mahal2, d_flags);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }

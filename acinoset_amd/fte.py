@@ -327,6 +327,11 @@ class FTEContext:
         check(lib().acino_fte_get_grad_hess(self._h, ptr(g), ptr(h), stream_ptr()))
         return g, h
 
+    def _workspace(self, nbytes):
+        """A fresh device buffer for one call: (the tensor that owns it, its first 256-byte aligned address)."""
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        return ws, C.c_void_p((ws.data_ptr() + 255) // 256 * 256)
+
     def covariance(self, std_only=False):
         """Laplace covariance of the CURRENT iterate (acino_fte_covariance): the inverse of the Gauss-Newton matrix
         blockdiag(H_n) + 2 q (x) D3^T D3 with the bound-active variables pinned, no Marquardt term.  Returns
@@ -335,12 +340,11 @@ class FTEContext:
         touched.  Whole-sequence fp64 contexts only (RuntimeError otherwise)."""
         dev = self.device
         nbytes = lib().acino_fte_covariance_workspace_bytes(C.byref(self.params))
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        ws, ws_ptr = self._workspace(nbytes)
         cov_x = None if std_only else torch.empty((self.N, N_ACTIVE, N_ACTIVE), dtype=torch.float64, device=dev)
         cov_pos = None if std_only else torch.empty((self.N, N_MARKERS, 3, 3), dtype=torch.float64, device=dev)
         std_pos = torch.empty((self.N, N_MARKERS), dtype=torch.float64, device=dev)
-        check(lib().acino_fte_covariance(self._h, C.c_void_p(ws_ptr), nbytes, ptr(cov_x), ptr(cov_pos), ptr(std_pos),
+        check(lib().acino_fte_covariance(self._h, ws_ptr, nbytes, ptr(cov_x), ptr(cov_pos), ptr(std_pos),
                                          stream_ptr()))
         return cov_x, cov_pos, std_pos
 
@@ -354,8 +358,7 @@ class FTEContext:
         of ``covariance()`` from the SAME call (one run of the sweeps), returned as a second tuple."""
         dev = self.device
         nbytes = lib().acino_fte_covariance_rates_workspace_bytes(C.byref(self.params))
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        ws, ws_ptr = self._workspace(nbytes)
 
         def new(*shape, skip=False):
             return None if skip else torch.empty((self.N,) + shape, dtype=torch.float64, device=dev)
@@ -367,7 +370,7 @@ class FTEContext:
         cov_ddx = new(N_ACTIVE, N_ACTIVE, skip=std_only)
         cov_vel = new(N_MARKERS, 3, 3, skip=std_only)
         std_vel = new(N_MARKERS)
-        check(lib().acino_fte_covariance_rates(self._h, self.Ts, C.c_void_p(ws_ptr), nbytes, ptr(cov_x), ptr(cov_pos),
+        check(lib().acino_fte_covariance_rates(self._h, self.Ts, ws_ptr, nbytes, ptr(cov_x), ptr(cov_pos),
                                                ptr(std_pos), ptr(cov_dx), ptr(cov_ddx), ptr(cov_vel), ptr(std_vel),
                                                stream_ptr()))
         rates = (cov_dx, cov_ddx, cov_vel, std_vel)
@@ -398,12 +401,11 @@ class FTEContext:
                 raise ValueError(f"z must be float64 [{S}, {self.N}, 25]")
             z = z.contiguous()
         nbytes = lib().acino_fte_sample_workspace_bytes(C.byref(self.params))
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        ws, ws_ptr = self._workspace(nbytes)
         x = torch.empty((S, self.N, N_ACTIVE), dtype=torch.float64, device=dev)
         fk_now = bool(positions) and not clip
         pos = torch.empty((S, self.N, N_MARKERS, 3), dtype=torch.float64, device=dev) if positions else None
-        check(lib().acino_fte_sample(self._h, S, ptr(z), C.c_void_p(ws_ptr), nbytes, ptr(x), ptr(pos if fk_now else None),
+        check(lib().acino_fte_sample(self._h, S, ptr(z), ws_ptr, nbytes, ptr(x), ptr(pos if fk_now else None),
                                      stream_ptr()))
         if clip:
             lo = torch.tensor(list(self.params.lo), dtype=torch.float64, device=dev)
@@ -441,8 +443,7 @@ class FTEContext:
         if sigma is not None:
             sigma = torch.as_tensor(sigma, dtype=torch.float64, device=dev).contiguous()
         nbytes = lib().acino_fte_calibration_workspace_bytes(C.byref(self.params))
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        ws, ws_ptr = self._workspace(nbytes)
         W = 6 * self.C
 
         def new(*shape):
@@ -450,13 +451,9 @@ class FTEContext:
 
         sens = torch.empty((self.N, N_ACTIVE, W), dtype=torch.float64, device=dev)
         cov_x, cov_pos, std_pos = new(N_ACTIVE, N_ACTIVE), new(N_MARKERS, 3, 3), new(N_MARKERS)
-        check(lib().acino_fte_calibration_sensitivity(self._h, ptr(sigma), C.c_void_p(ws_ptr), nbytes, ptr(sens), ptr(cov_x),
+        check(lib().acino_fte_calibration_sensitivity(self._h, ptr(sigma), ws_ptr, nbytes, ptr(sens), ptr(cov_x),
                                                       ptr(cov_pos), ptr(std_pos), stream_ptr()))
         return dict(sens=sens, cov_x_cal=cov_x, cov_pos_cal=cov_pos, std_pos_cal=std_pos)
-
-    def _calibration(self, cov_cams):
-        """The calibration term as the solve entries return it, or None."""
-        return None if cov_cams is None else self.calibration_sensitivity(cov_cams)
 
     def reprojection(self, cov=True, cov_pos=None):
         """The CURRENT iterate in image space (acino_fte_reprojection), per (frame, camera, marker): a dict of tensors on
@@ -489,25 +486,36 @@ class FTEContext:
         std_uv = torch.sqrt(cov_uv[..., 0, 0] + cov_uv[..., 1, 1]) if cov else None
         return dict(uv=uv, cov_uv=cov_uv, std_uv=std_uv, res=res, weight=weight, mahal2=mahal2, flags=flags)
 
-    def _reprojection(self, return_reprojection, cov):
-        """The report as the solve entries return it, or None; ``cov``: what _covariances gave (its sweeps are not run twice)."""
-        if not return_reprojection:
-            return None
-        return self.reprojection(cov_pos=None if cov is None else cov[1])
-
-    def _samples(self, n_samples, sample_seed):
-        """(x_samples, positions_samples) as the solve entries return them, or None."""
-        if not n_samples:
-            return None
-        out = self.sample(n_samples, seed=sample_seed)
-        return out["x"], out["positions"]
-
-    def _covariances(self, return_cov, return_rate_cov):
-        """(cov, rate_cov) as the solve entries return them: either may be None; both from one call when both are asked."""
+    def _posterior(self, return_cov=False, return_rate_cov=False, n_samples=0, sample_seed=0, return_reprojection=False,
+                   cov_cams=None):
+        """The extras of the solve entries at the CURRENT iterate: a dict of device tensors under the names they have in
+        ``results`` (_attach_posterior joins them), the frame axis first - second for ``x_samples`` / ``positions_samples``.
+        The only place for two rules: covariance and rates come from ONE call when both are asked for, and the reprojection
+        takes ``cov_positions`` from that call when it is there - the sweeps never run twice."""
+        cov = rates = None
         if return_rate_cov:
             out = self.covariance_rates(with_cov=bool(return_cov))
-            return (out[1], out[0]) if return_cov else (None, out)
-        return (self.covariance() if return_cov else None), None
+            rates, cov = out if return_cov else (out, None)
+        elif return_cov:
+            cov = self.covariance()
+        post = {}
+        if cov is not None:
+            post.update(zip(("cov_x", "cov_positions", "std_positions"), cov))
+        if rates is not None:
+            post.update(zip(("cov_dx", "cov_ddx", "cov_velocities", "std_velocities"), rates))
+        if n_samples:
+            draws = self.sample(n_samples, seed=sample_seed)
+            post.update(x_samples=draws["x"], positions_samples=draws["positions"])
+        if return_reprojection:
+            report = self.reprojection(cov_pos=post.get("cov_positions"))
+            post.update({name: report[k] for k, name in _REPROJ_KEYS.items()})
+        if cov_cams is not None:
+            cal = self.calibration_sensitivity(cov_cams)
+            post.update(sens_cams=cal["sens"], cov_x_calib=cal["cov_x_cal"], cov_positions_calib=cal["cov_pos_cal"],
+                        std_positions_calib=cal["std_pos_cal"])
+            if cov is not None:
+                post["std_positions_total"] = torch.sqrt(cov[2] ** 2 + cal["std_pos_cal"] ** 2)
+        return post
 
 
 def _cov_cams_matrix(cov_cams, n_cams):
@@ -530,28 +538,13 @@ def _cov_cams_matrix(cov_cams, n_cams):
     return np.ascontiguousarray(a)
 
 
-def _calib_results(res, cal, cov, conv, sl=slice(None)):
-    if cal is not None:
-        res.update(sens_cams=conv(cal["sens"][sl]), cov_x_calib=conv(cal["cov_x_cal"][sl]),
-                   cov_positions_calib=conv(cal["cov_pos_cal"][sl]), std_positions_calib=conv(cal["std_pos_cal"][sl]))
-        if cov is not None:
-            res["std_positions_total"] = conv(torch.sqrt(cov[2][sl] ** 2 + cal["std_pos_cal"][sl] ** 2))
-
-
-def _cov_results(res, cov, rate_cov, conv, sl=slice(None)):
-    if cov is not None:
-        res.update(cov_x=conv(cov[0][sl]), cov_positions=conv(cov[1][sl]), std_positions=conv(cov[2][sl]))
-    if rate_cov is not None:
-        res.update(cov_dx=conv(rate_cov[0][sl]), cov_ddx=conv(rate_cov[1][sl]), cov_velocities=conv(rate_cov[2][sl]),
-                   std_velocities=conv(rate_cov[3][sl]))
-
-
 _REPROJ_KEYS = dict(uv="uv", cov_uv="cov_uv", std_uv="std_uv", res="residuals", weight="weights", mahal2="mahal2", flags="flags")
 
 
-def _reproj_results(res, reproj, conv, sl=slice(None)):
-    if reproj is not None:
-        res.update({name: conv(reproj[k][sl]) for k, name in _REPROJ_KEYS.items()})
+def _attach_posterior(res, post, conv, sl=slice(None)):
+    """Frames ``sl`` of what FTEContext._posterior returned (None or empty: nothing) into one ``results``."""
+    for name, a in (post or {}).items():
+        res[name] = conv(a[:, sl] if name in ("x_samples", "positions_samples") else a[sl])
 
 
 def detection_report(reproj, gate=None):
@@ -584,11 +577,6 @@ def detection_report(reproj, gate=None):
                    n_unweighted_inside=(inside & ~weighted).sum(axis=0),
                    n_unweighted_outside=(outside & ~weighted).sum(axis=0))
     return out
-
-
-def _sample_results(res, samples, conv, sl=slice(None)):
-    if samples is not None:
-        res.update(x_samples=conv(samples[0][:, sl]), positions_samples=conv(samples[1][:, sl]))
 
 
 def cheetah_fk(q):
@@ -765,6 +753,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
     uncertainty of the calibration adds), and with ``return_cov`` as well ``std_positions_total`` =
     sqrt(std_positions^2 + std_positions_calib^2) - valid when the calibration came from other data than these clips."""
     _cov_cams_matrix(cov_cams, len(k_arr))       # (a malformed matrix fails before the solve, not after)
+    extras = (return_cov, return_rate_cov, n_samples, sample_seed, return_reprojection, cov_cams)     # FTEContext._posterior
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     meas_t = meas if isinstance(meas, torch.Tensor) else torch.as_tensor(np.asarray(meas, dtype=np.float64))
     lik_t = likelihood if isinstance(likelihood, torch.Tensor) else torch.as_tensor(np.asarray(likelihood, dtype=np.float64))
@@ -784,10 +773,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         ctx.set_x(xa0)
         info = ctx.solve(max_iter)
         x, pos, dx, ddx = ctx.result()
-        cov, rate_cov = ctx._covariances(return_cov, return_rate_cov) if info["status"] != 5 else (None, None)
-        samples = ctx._samples(n_samples, sample_seed) if info["status"] != 5 else None
-        reproj = ctx._reprojection(return_reprojection, cov) if info["status"] != 5 else None
-        cal = ctx._calibration(cov_cams) if info["status"] != 5 else None
+        post = ctx._posterior(*extras) if info["status"] != 5 else None
     except Exception:
         # (the initial guess's flag is read after the solve - no synchronisation in front of it -, but whatever a solve from an
         #  all-zero start ran into must not hide the real cause)
@@ -803,10 +789,7 @@ def fte_solve(meas, likelihood, k_arr, d_arr, r_arr, t_arr, Ts, x0=None, dlc_thr
         raise RuntimeError("FTE: block factorisation hit a non-positive pivot")
     conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
     results = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frame)
-    _cov_results(results, cov, rate_cov, conv)
-    _sample_results(results, samples, conv)
-    _reproj_results(results, reproj, conv)
-    _calib_results(results, cal, cov, conv)
+    _attach_posterior(results, post, conv)
     return results, info
 
 
@@ -831,6 +814,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     fte_solve, sliced per clip in the same way.  ``cov_cams`` as in fte_solve (one call; the calibration term of a clip does
     not depend on the other clips)."""
     _cov_cams_matrix(cov_cams, len(k_arr))
+    extras = (return_cov, return_rate_cov, n_samples, sample_seed, return_reprojection, cov_cams)     # FTEContext._posterior
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     B = len(dets)
     if B == 0:
@@ -862,10 +846,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
         x, pos, _dx, _ddx = ctx.result()
         if info["status"] == 5:
             raise RuntimeError("FTE: block factorisation hit a non-positive pivot")
-        cov, rate_cov = ctx._covariances(return_cov, return_rate_cov)
-        samples = ctx._samples(n_samples, sample_seed)
-        reproj = ctx._reprojection(return_reprojection, cov)
-        cal = ctx._calibration(cov_cams)
+        post = ctx._posterior(*extras)
         conv = (lambda a: a.cpu().numpy()) if return_numpy else (lambda a: a)
         out = []
         for b in range(B):
@@ -873,10 +854,7 @@ def fte_solve_clips(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
             dxb, ddxb = _derivatives(xb, Ts)                     # per clip: no differences across a clip boundary
             res = dict(positions=conv(pos[b * S:(b + 1) * S]), x=conv(xb), dx=conv(dxb), ddx=conv(ddxb),
                        start_frame=start_frames[b])
-            _cov_results(res, cov, rate_cov, conv, slice(b * S, (b + 1) * S))
-            _sample_results(res, samples, conv, slice(b * S, (b + 1) * S))
-            _reproj_results(res, reproj, conv, slice(b * S, (b + 1) * S))
-            _calib_results(res, cal, cov, conv, slice(b * S, (b + 1) * S))
+            _attach_posterior(res, post, conv, slice(b * S, (b + 1) * S))
             out.append((res, dict(info, clips=B, cost_is_sum_over_clips=True)))
         return out
     finally:
@@ -897,6 +875,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
     clips one after another (src/all_optimizations.py:22, one ``fte()`` call per data directory).  ``camera_model`` /
     ``project_func`` / ``return_cov`` / ``return_rate_cov`` / ``n_samples`` / ``sample_seed`` / ``return_reprojection`` / ``cov_cams`` as in fte_solve."""
     _cov_cams_matrix(cov_cams, len(k_arr))
+    extras = (return_cov, return_rate_cov, n_samples, sample_seed, return_reprojection, cov_cams)     # FTEContext._posterior
     model = camera_model_of(camera_model, project_func, kw.get("precision", "f64"))
     _lib.require_gpu()
     B = len(dets)
@@ -945,11 +924,7 @@ def fte_solve_batch(dets, k_arr, d_arr, r_arr, t_arr, Ts, x0s=None, dlc_thresh=0
                     raise RuntimeError(f"FTE: block factorisation hit a non-positive pivot (sequence {b})")
                 x, pos, dx, ddx = ctxs[b].result()
                 res = dict(positions=conv(pos), x=conv(x), dx=conv(dx), ddx=conv(ddx), start_frame=start_frames[b])
-                cov, rate_cov = ctxs[b]._covariances(return_cov, return_rate_cov)
-                _cov_results(res, cov, rate_cov, conv)
-                _sample_results(res, ctxs[b]._samples(n_samples, sample_seed), conv)
-                _reproj_results(res, ctxs[b]._reprojection(return_reprojection, cov), conv)
-                _calib_results(res, ctxs[b]._calibration(cov_cams), cov, conv)
+                _attach_posterior(res, ctxs[b]._posterior(*extras), conv)
                 out.append((res, infos[b]))
         for s in streams:
             torch.cuda.current_stream().wait_stream(s)

@@ -63,7 +63,7 @@ def test_python_interface_defaults_off_and_value_errors():
     for fn in (fte.fte_solve, fte.fte_solve_clips, fte.fte_solve_batch):
         assert inspect.signature(fn).parameters["cov_cams"].default is None
     res = {}
-    fte._calib_results(res, None, None, lambda a: a)
+    fte._attach_posterior(res, None, lambda a: a)
     assert res == {}
     good = calib.extrinsic_cov(6, 0.05, 2e-3, fixed=(0,))
     assert fte._cov_cams_matrix(None, 6) is None
@@ -85,6 +85,88 @@ def test_python_interface_defaults_off_and_value_errors():
         fte.fte_solve_clips([z, z], *rig, 1 / 90, cov_cams=bad_asym)
     with pytest.raises(ValueError, match="cov_cams"):
         fte.fte_solve_batch([z, z], *rig, 1 / 90, cov_cams=bad_nan)
+
+
+class _FakeContext:
+    """The five public calls FTEContext._posterior composes, on the CPU: constants of the documented shapes, every call logged."""
+
+    def __init__(self, n=10, c=6):
+        import torch
+        self.calls = []
+        self._new = lambda *shape: torch.ones((n,) + shape, dtype=torch.float64)
+        self.n, self.c = n, c
+
+    def _cov(self):
+        return self._new(25, 25), self._new(20, 3, 3), 3.0 * self._new(20)
+
+    def _rates(self):
+        return self._new(25, 25), self._new(25, 25), self._new(20, 3, 3), self._new(20)
+
+    def covariance(self):
+        self.calls.append("covariance")
+        self.cov = self._cov()
+        return self.cov
+
+    def covariance_rates(self, with_cov=False):
+        self.calls.append(("covariance_rates", with_cov))
+        self.cov = self._cov() if with_cov else None
+        return (self._rates(), self.cov) if with_cov else self._rates()
+
+    def reprojection(self, cov_pos=None):
+        self.calls.append("reprojection")
+        self.cov_pos_given = cov_pos
+        s = (self.c, 20)
+        return dict(uv=self._new(*s, 2), cov_uv=self._new(*s, 2, 2), std_uv=self._new(*s), res=self._new(*s, 2),
+                    weight=self._new(*s, 2), mahal2=self._new(*s), flags=self._new(*s))
+
+    def calibration_sensitivity(self, cov_cams=None):
+        self.calls.append("calibration_sensitivity")
+        return dict(sens=self._new(25, 6 * self.c), cov_x_cal=self._new(25, 25), cov_pos_cal=self._new(20, 3, 3),
+                    std_pos_cal=4.0 * self._new(20))
+
+
+COV_KEYS = {"cov_x", "cov_positions", "std_positions"}
+RATE_KEYS = {"cov_dx", "cov_ddx", "cov_velocities", "std_velocities"}
+REPROJ_KEYS = {"uv", "cov_uv", "std_uv", "residuals", "weights", "mahal2", "flags"}
+CALIB_KEYS = {"sens_cams", "cov_x_calib", "cov_positions_calib", "std_positions_calib"}
+
+
+def test_posterior_composition_rules():
+    """FTEContext._posterior on a context of CPU stand-ins: covariance and rates come from ONE covariance_rates(with_cov=True)
+    (the three and the four keys), the reprojection is handed that call's cov_positions, std_positions_total exists only when both the covariance
+    and the calibration term do and is sqrt(3^2 + 4^2) = 5 here; _attach_posterior slices every key on the frame axis."""
+    from acinoset_amd import fte
+    post_of = fte.FTEContext._posterior
+    sigma = np.eye(36)
+    ctx = _FakeContext()
+    assert post_of(ctx) == {} and ctx.calls == []
+    post = post_of(ctx, return_cov=True, return_rate_cov=True)
+    assert ctx.calls == [("covariance_rates", True)] and set(post) == COV_KEYS | RATE_KEYS and len(post) == 7
+    assert post["cov_positions"] is ctx.cov[1]
+    ctx = _FakeContext()
+    assert set(post_of(ctx, return_cov=True)) == COV_KEYS and ctx.calls == ["covariance"]
+    ctx = _FakeContext()
+    assert set(post_of(ctx, return_rate_cov=True)) == RATE_KEYS and ctx.calls == [("covariance_rates", False)]
+    ctx = _FakeContext()
+    post = post_of(ctx, return_cov=True, return_reprojection=True)
+    assert ctx.calls == ["covariance", "reprojection"] and ctx.cov_pos_given is ctx.cov[1]
+    assert set(post) == COV_KEYS | REPROJ_KEYS
+    ctx = _FakeContext()
+    assert set(post_of(ctx, return_reprojection=True)) == REPROJ_KEYS and ctx.cov_pos_given is None
+    ctx = _FakeContext()
+    assert set(post_of(ctx, cov_cams=sigma)) == CALIB_KEYS and ctx.calls == ["calibration_sensitivity"]
+    ctx = _FakeContext()
+    assert set(post_of(ctx, return_rate_cov=True, cov_cams=sigma)) == RATE_KEYS | CALIB_KEYS
+    ctx = _FakeContext()
+    post = post_of(ctx, return_cov=True, return_rate_cov=True, return_reprojection=True, cov_cams=sigma)
+    assert ctx.calls == [("covariance_rates", True), "reprojection", "calibration_sensitivity"]
+    assert ctx.cov_pos_given is ctx.cov[1]
+    assert set(post) == COV_KEYS | RATE_KEYS | REPROJ_KEYS | CALIB_KEYS | {"std_positions_total"}
+    res = {}
+    fte._attach_posterior(res, post, lambda a: a.numpy(), slice(5, 10))
+    assert set(res) == set(post) and all(v.shape[0] == 5 for v in res.values())
+    assert res["sens_cams"].shape == (5, 25, 36) and res["cov_uv"].shape == (5, 6, 20, 2, 2)
+    assert res["std_positions_total"].shape == (5, 20) and np.all(res["std_positions_total"] == 5.0)
 
 
 def test_extrinsic_cov():

@@ -5,6 +5,7 @@ import ctypes as C
 import inspect
 import os
 import re
+import types
 
 import numpy as np
 import pytest
@@ -51,12 +52,17 @@ def test_python_interface_defaults_off():
     for fn in (fte.fte_solve, fte.fte_solve_clips, fte.fte_solve_batch):
         assert inspect.signature(fn).parameters["return_reprojection"].default is False
     res = {}
-    fte._reproj_results(res, None, lambda a: a)
+    fte._attach_posterior(res, None, lambda a: a)
+    fte._attach_posterior(res, {}, lambda a: a)
     assert res == {}
     rep = dict(uv=np.zeros((10, 6, 20, 2)), cov_uv=np.zeros((10, 6, 20, 2, 2)), std_uv=np.zeros((10, 6, 20)),
                res=np.zeros((10, 6, 20, 2)), weight=np.zeros((10, 6, 20, 2)), mahal2=np.zeros((10, 6, 20)),
                flags=np.zeros((10, 6, 20), dtype=np.uint8))
-    fte._reproj_results(res, rep, lambda a: a, slice(5, 10))
+    asked = []                                               # a context that has only the report: no covariance to hand on
+    ctx = types.SimpleNamespace(reprojection=lambda cov_pos=None: asked.append(cov_pos) or rep)
+    post = fte.FTEContext._posterior(ctx, return_reprojection=True)
+    assert asked == [None]
+    fte._attach_posterior(res, post, lambda a: a, slice(5, 10))
     assert set(res) == {"uv", "cov_uv", "std_uv", "residuals", "weights", "mahal2", "flags"}
     assert res["uv"].shape == (5, 6, 20, 2) and res["cov_uv"].shape == (5, 6, 20, 2, 2) and res["flags"].shape == (5, 6, 20)
     sig = inspect.signature(io.reprojection_to_points_2d_df).parameters

@@ -5,6 +5,7 @@ import ctypes as C
 import inspect
 import os
 import re
+import types
 
 import numpy as np
 import pytest
@@ -61,10 +62,16 @@ def test_python_interface_defaults_off():
         assert inspect.signature(fn).parameters["n_samples"].default == 0
         assert inspect.signature(fn).parameters["sample_seed"].default == 0
     res = {}
-    fte._sample_results(res, None, lambda a: a)
+    fte._attach_posterior(res, None, lambda a: a)
     assert res == {}
     xs, ps = np.zeros((3, 10, 25)), np.zeros((3, 10, 20, 3))
-    fte._sample_results(res, (xs, ps), lambda a: a, slice(5, 10))
+    asked = []
+    ctx = types.SimpleNamespace(sample=lambda n, seed=0: asked.append((n, seed)) or dict(x=xs, positions=ps))
+    assert fte.FTEContext._posterior(ctx, n_samples=0, sample_seed=7) == {} and asked == []
+    post = fte.FTEContext._posterior(ctx, n_samples=3, sample_seed=7)
+    assert asked == [(3, 7)]
+    fte._attach_posterior(res, post, lambda a: a, slice(5, 10))
+    assert set(res) == {"x_samples", "positions_samples"}
     assert res["x_samples"].shape == (3, 5, 25) and res["positions_samples"].shape == (3, 5, 20, 3)
 
 
