@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "bcr_dev.hpp"
 #include "trio80.hpp"
@@ -51,19 +52,6 @@ void ChunkPlan::build(int nodes_total, int chunk_nodes, bool pin_l, bool pin_r) 
 }
 
 // ---- tile helpers on LDS matrices (leading dimension LD): one 16x16 output tile per call, all operands read first ----
-// (U U^T)(ib, jb), jb <= ib:  sum_{k >= 16 ib} U[ib16 + i][k] U[jb16 + j][k]
-__device__ __forceinline__ d4 tile_u_ut(const double* X, int ib, int jb, int li, int lk) {
-  const double* pa = X + (ib * 16 + li) * LD + ib * 16 + lk;
-  const double* pb = X + (jb * 16 + li) * LD + ib * 16 + lk;
-  const d4 z = {0, 0, 0, 0};
-  switch (ib) {
-    case 0: return mma_seq<20, false>(z, pa, 4, pb, 4);
-    case 1: return mma_seq<16, false>(z, pa, 4, pb, 4);
-    case 2: return mma_seq<12, false>(z, pa, 4, pb, 4);
-    case 3: return mma_seq<8, false>(z, pa, 4, pb, 4);
-    default: return mma_seq<4, false>(z, pa, 4, pb, 4);
-  }
-}
 __device__ __forceinline__ void tile_store(double* M, int ib, int jb, const d4& a, int li, int lk) {
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) M[(ib * 16 + lk + 4 * rr) * LD + jb * 16 + li] = a[rr];
@@ -82,6 +70,28 @@ __device__ __forceinline__ int opaque(int x) {
   return x;
 }
 
+__device__ __forceinline__ unsigned opaque_u(unsigned x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+// One state pair of the next-node build, packed by k_chunk_sweep once per run: p | p' << 5 | owned << 10 | diagonal << 11 |
+// (p LD + p') << 12 | e << 23 (e < 325 = the pair's index in the assembly's H).
+struct BuildSlot {
+  int pr, pc, base, e;
+  bool own, dg;
+  static __device__ __forceinline__ BuildSlot unpack(unsigned w) {
+    BuildSlot s;
+    s.pr = w & 31;
+    s.pc = (w >> 5) & 31;
+    s.own = (w >> 10) & 1;
+    s.dg = (w >> 11) & 1;
+    s.base = (w >> 12) & 2047;
+    s.e = w >> 23;
+    return s;
+  }
+};
+static_assert((NP - 1) * LD + NP - 1 < 2048 && 13 * NP <= 512 && NP <= 32, "BuildSlot's bit fields");
+
 constexpr int SW_T = 512;
 // accumulators of a run's FIRST node start from zero (a select behind the unconditional loads: a conditional load compiles to
 // a branch per element with a full wait in front)
@@ -95,8 +105,8 @@ __device__ __forceinline__ void syrk_mask_n(d4 (&acc)[NQ], bool load) {
 // ================================================================================================================
 // The sweep kernel: TWO TEAMS of waves that run their own loops over the nodes of a run and meet only through LDS counters.
 //   D team (waves 0, 4 | 1, 5): the chain  U_k -> G_k = U_k U_k^T -> D~_k+1 = D_k+1 - E^T G_k E -> Cholesky -> U_k+1.
-//     Per node: G_k as a queue of tiles (below), the next node built from the 325 unordered state pairs straight into Xf
-//     (256 threads), then chol80_trio - wave 0 the pivot chains, waves 1 and 5 the helpers - while wave 4, the pivot chain's
+//     Per node: G_k on a fixed schedule of tiles (below), the next node built from the 325 unordered state pairs straight
+//     into Xf (one pair per lane, a second one in waves 4 and 5), then chol80_trio - wave 0 the pivot chains, waves 1 and 5 the helpers - while wave 4, the pivot chain's
 //     SIMD mate, which therefore carries no matrix work during the chains, streams G_k to HBM.
 //   S team (waves 2, 6 | 3, 7): the spike of node k as soon as G_k is complete.  Wave 2 holds strip 1 of the spike (16 columns),
 //     wave 6 strips 2 and 0, wave 3 strip 3, wave 7 strip 4.  T strips by spike_gf (the F strip in registers - the accumulator
@@ -107,7 +117,7 @@ __device__ __forceinline__ void syrk_mask_n(d4 (&acc)[NQ], bool load) {
 // instructions slows a latency-bound mate 2 - 5x (measured: scripts/mfma64_rate.hip, NOTES_perf.md round 5).  So the pivot
 // chain shares with a wave that only moves data, the two helpers share with each other (the older one has the deadline), and
 // the four strip waves share among themselves.
-// Hand-offs (monotonic counters): g_open / g_ticket / g_done: the queue of G_k's tiles; gfdone (a strip wave is through with
+// Hand-offs (monotonic counters): g_open / g_done: G_k may start / its finished tiles; gfdone (a strip wave is through with
 // Xg) S -> D, which then overwrites Xg with G_k+1; c_bv (next node built: its right-hand side bv[(k+1) & 1] is there) D -> S for
 // the stencil pass; tdone (a wave's tiles of F^T T are finished: the strips it read may be overwritten) and fready (a wave's
 // strips of F_k+1 are complete) among the S waves.  No workgroup barrier inside the node loop: the S team's tail (T -> Y,
@@ -187,32 +197,68 @@ struct AlTiles {
 // a wave that streams fp64 matrix instructions holds its SIMD 64 cycles at a time, and every instruction of its SIMD mate,
 // vector or matrix, waits for the slot: latency-bound work and matrix streams do not share a SIMD
 __device__ __forceinline__ int role8(int wave) { return (0x75236410u >> (4 * wave)) & 15; }   // {0, 1, 4, 6, 3, 2, 5, 7}
-// G_k = U_k U_k^T as a QUEUE of its 15 lower tiles, most expensive first (tile t costs 4 (5 - tri_i(t)) matrix instructions):
-// whoever is free draws the next ticket - the four D waves as soon as the factorisation is over and the strip waves are
-// through with Xg (g_open), the strip waves when they have finished the previous node's spike and would otherwise wait for
-// G_k: two more matrix pipes for the tail of the queue.  g_done counts finished tiles: 15 (k + 1) = G_k complete in Xg.
-struct GramQueue {
-  int *open, *ticket, *done;
+// G_k = U_k U_k^T on a FIXED SCHEDULE of its 15 lower tiles (tile t costs 4 (5 - tri_i(t)) matrix instructions, 140 in all),
+// level per SIMD over the three SIMDs that take part - the D team's two and the one of strip waves 3 and 7, which carries two
+// strips only; waves 2 and 6 (three strips: the S team's bottleneck) take none:
+//   wave 0 (role 0): t 0, 10 (24)    wave 4 (role 3): t 3, 6, 11 (24)         SIMD of the pivot chain: 48
+//   wave 1 (role 1): t 1, 7 (24)     wave 5 (role 2): t 4, 8, 12 (24)         SIMD of the helpers: 48
+//   wave 3 (role 6): t 2, 13 (20)    wave 7 (role 7): t 5, 9, 14 (24)         SIMD of strips 3 and 4: 44
+// (a run without a left separator has only wave 7 alive in the S team: it takes wave 3's two tiles as well).  Every wave
+// requests the operands of its next tile before the matrix instructions of the current one and reports all its tiles with
+// one add: g_done counts finished tiles as before, 15 (k + 1) = G_k complete in Xg; g_open (U_k complete, Xg free) stays the
+// start signal of the strip waves.  (Until the fixed schedule the tiles were drawn one by one through an LDS ticket: an
+// atomic round trip and an exposed operand latency per draw, two uneven rounds of eight takers - 2.6 us for 1.0 us of
+// matrix-pipe time.)
+constexpr int ctri_i(int t) { return (t >= 1) + (t >= 3) + (t >= 6) + (t >= 10); }
+template <int T>
+struct GramTile {
+  static constexpr int ib = ctri_i(T), jb = T - ib * (ib + 1) / 2, ns = 4 * (NT - ib);
 };
-__device__ __forceinline__ void gram_help(const GramQueue& q, const double* Xf, double* Xg, int k, int li, int lk, int lane) {
-  for (;;) {
-    int t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add(q.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    t = __builtin_amdgcn_readfirstlane(t) - 15 * k;
-    if (t >= 15) {
-      // (tickets drawn beyond the node's 15 are handed back: the next node's queue starts at 15 (k + 1))
-      if (lane == 0) __hip_atomic_fetch_add(q.ticket, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      return;
-    }
-    const int ib = tri_i(t), jb = tri_j(t);
-    const d4 g = tile_u_ut(Xf, ib, jb, li, lk);
+template <int T>
+__device__ __forceinline__ void gram_fetch(const double* X, int li, int lk, double (&a)[GramTile<T>::ns], double (&b)[GramTile<T>::ns]) {
+  const double* pa = X + (GramTile<T>::ib * 16 + li) * LD + GramTile<T>::ib * 16 + lk;      // (U U^T)(ib, jb), jb <= ib: sum_{k >= 16 ib} U[ib16 + i][k] U[jb16 + j][k]
+  const double* pb = X + (GramTile<T>::jb * 16 + li) * LD + GramTile<T>::ib * 16 + lk;
 #pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      Xg[(ib * 16 + lk + 4 * rr) * LD + jb * 16 + li] = g[rr];
-      if (ib != jb) Xg[(jb * 16 + li) * LD + ib * 16 + lk + 4 * rr] = g[rr];
-    }
-    lds_signal(q.done, lane);
+  for (int s = 0; s < GramTile<T>::ns; ++s) {
+    a[s] = pa[4 * s];
+    b[s] = pb[4 * s];
   }
+}
+template <int T>
+__device__ __forceinline__ void gram_tile(double* Xg, int li, int lk, const double (&a)[GramTile<T>::ns], const double (&b)[GramTile<T>::ns]) {
+  constexpr int ib = GramTile<T>::ib, jb = GramTile<T>::jb;
+  d4 g = {0, 0, 0, 0};
+#pragma unroll
+  for (int s = 0; s < GramTile<T>::ns; ++s) g = mfma(a[s], b[s], g);
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    Xg[(ib * 16 + lk + 4 * rr) * LD + jb * 16 + li] = g[rr];
+    if (ib != jb) Xg[(jb * 16 + li) * LD + ib * 16 + lk + 4 * rr] = g[rr];
+  }
+}
+template <int T0, int... REST>
+__device__ __forceinline__ void gram_chain(const double* Xf, double* Xg, int li, int lk, const double (&a)[GramTile<T0>::ns],
+                                           const double (&b)[GramTile<T0>::ns]) {
+  if constexpr (sizeof...(REST) > 0) {
+    constexpr int rest[] = {REST...};
+    double an[GramTile<rest[0]>::ns], bn[GramTile<rest[0]>::ns];
+    gram_fetch<rest[0]>(Xf, li, lk, an, bn);
+    __builtin_amdgcn_sched_barrier(0);
+    gram_tile<T0>(Xg, li, lk, a, b);
+    __builtin_amdgcn_sched_barrier(0);
+    gram_chain<REST...>(Xf, Xg, li, lk, an, bn);
+  } else {
+    gram_tile<T0>(Xg, li, lk, a, b);
+  }
+}
+template <int T0, int... REST>
+__device__ __forceinline__ void gram_fixed(const double* Xf, double* Xg, int* done, int li, int lk, int lane) {
+  double a[GramTile<T0>::ns], b[GramTile<T0>::ns];
+  gram_fetch<T0>(Xf, li, lk, a, b);
+  gram_chain<T0, REST...>(Xf, Xg, li, lk, a, b);
+  asm volatile("" ::: "memory");
+  if (lane == 0) __hip_atomic_fetch_add(done, 1 + (int)sizeof...(REST), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  asm volatile("" ::: "memory");
 }
 
 // The spike of one node on one strip wave (ROLE 4: wave 2, strip 1 | 5: wave 6, strips 2 and 0 | 6: wave 3, strip 3 | 7: wave 7,
@@ -226,7 +272,7 @@ struct SpikeArgs {
   const double* bvn;
   double* zk;
   int *c_gfdone, *c_fready, *c_bv, *tdone;           // tdone[0 .. 2]: tile batches finished by roles 4, 6, 7
-  GramQueue gq;
+  int *g_open, *g_done;
   const double* Xf;
   int k, n_s;
   bool hasL, has_next;
@@ -255,10 +301,15 @@ __device__ __forceinline__ void spike_node(const SpikeArgs& A, int& tsb, int ln)
     al.fetch(li, lk);
     if (two) al0.fetch(li, lk);
   }
-  // G_k: help with its tiles once the queue is open, then wait for the last one
-  lds_wait(A.gq.open, A.k + 1);
-  gram_help(A.gq, A.Xf, const_cast<double*>(A.Xg), A.k, li, lk, ln);
-  lds_wait(A.gq.done, 15 * (A.k + 1));
+  // G_k: this wave's tiles of the fixed schedule once U_k is complete and Xg free (waves 3 and 7), then wait for the last one
+  if (ROLE >= 6) {
+    double* const Xg = const_cast<double*>(A.Xg);
+    lds_wait(A.g_open, A.k + 1);
+    if (ROLE == 6) gram_fixed<2, 13>(A.Xf, Xg, A.g_done, li, lk, ln);
+    else if (A.hasL) gram_fixed<5, 9, 14>(A.Xf, Xg, A.g_done, li, lk, ln);
+    else gram_fixed<2, 5, 9, 13, 14>(A.Xf, Xg, A.g_done, li, lk, ln);     // (wave 3 is not alive)
+  }
+  lds_wait(A.g_done, 15 * (A.k + 1));
   stamp(16 + 4 * (ROLE - 4));
   d4 T0[NT], T1[NT];
   {
@@ -369,8 +420,7 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
   int* const cB = sync + 5;                            // barrier of the four D waves
   int* const tdone = sync + 2;                         // [3]: tile batches of F^T T finished by roles 4, 6, 7 (sync[2 .. 4])
   int* const g_done = sync + 6;                        // tiles of G finished (15 per node)
-  int* const g_open = sync + 10;                       // queue of node k open: U_k complete, Xg free
-  int* const g_ticket = sync + 1;
+  int* const g_open = sync + 10;                       // G_k may start: U_k complete, Xg free (sync[1] is unused)
   int* const c_gfdone = sync + 7;
   int* const c_fready = sync + 8;
   int* const c_bv = sync + 9;
@@ -436,6 +486,28 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
     if (dbgp && tid == 0) lst[61] = (long long)wall_clock64();
   }
 
+  // ---- who builds which of the 325 unordered state pairs {p, p'} of a node (pair e = 13 p + d is p, p' = p + d mod 25: every
+  // cyclic distance d = 0 .. 12 once).  Constant over the run, so it is decomposed ONCE, here, and kept packed in one register
+  // per slot (BuildSlot below).  Every D wave owns one pair per lane (slot 0), and the 69 pairs left over are a second slot of
+  // ONE wave per SIMD - wave 4 (role 3) and wave 5 (role 2, the helper that starts later), never the pivot-chain wave -, so
+  // that each of the two D SIMDs issues three wave-slots of the build.  The 25 diagonal pairs (d = 0: damping, bound fixing,
+  // right-hand side, the three band coefficients) are lanes 0 .. 24 of wave 1 and of no other wave: one wave executes that
+  // divergent block.  The off-diagonal pairs follow in the order of e: number n = 0 .. 299 is e = 13 (n / 12) + 1 + n % 12, slot 0
+  // of role 0 holds n = lane, role 2 64 + lane, role 3 128 + lane, role 1 (lanes 25 ..) 192 + lane - 25; slot 1 of role 3
+  // n = 231 + lane < 266, of role 2 n = 266 + lane < 300.
+  unsigned slot0 = 0, slot1 = 0;
+  if (builder) {
+    auto pack = [](int e, bool own, bool dg) {
+      const int pa = e / 13, dd = e % 13, pc = pa + dd >= NP ? pa + dd - NP : pa + dd;
+      return (unsigned)pa | (unsigned)pc << 5 | (unsigned)own << 10 | (unsigned)dg << 11 | (unsigned)(pa * LD + pc) << 12 | (unsigned)e << 23;
+    };
+    auto offdiag = [](int n) { return 13 * (n / 12) + 1 + n % 12; };
+    const bool dg0 = role == 1 && lane < NP;
+    const int n0 = role == 1 ? 192 + lane - NP : (role == 0 ? 0 : (role == 2 ? 64 : 128)) + lane;
+    slot0 = pack(dg0 ? 13 * lane : offdiag(n0), true, dg0);
+    const bool own1 = (role == 3 && lane < 35) || (role == 2 && lane < 34);
+    slot1 = pack(own1 ? offdiag((role == 3 ? 231 : 266) + lane) : 0, own1, false);
+  }
   int tb = 0, tsb = 0;                       // rounds of the builders' barrier
 #pragma unroll 1
   for (int k = 0; k < n_int; ++k) {
@@ -450,26 +522,14 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       const int bw = role;                             // 0 chain, 1, 2 helpers, 3 the chain's SIMD mate (wave 4)
       const int bt = bw * 64 + ln;                     // builder thread
       const int fb_next = 3 * (next - node0);          // (node t holds the local frames 3 (t - pin_left) ..)
-      // The next node is symmetric: its 3 x 3 frame blocks are built for the 325 UNORDERED state pairs {p, p'} only - pair e (thread
-      // bt owns e = bt and e = bt + 256 < 325) is p = e / 13, p' = p + e % 13 mod 25: every cyclic distance 0 .. 12 once - and
-      // written to both places (block (p', p) is the transpose).
+      // The next node is symmetric: its 3 x 3 frame blocks are built for the 325 UNORDERED state pairs only (dealt above: slot 0 in
+      // every D wave, slot 1 in waves 4 and 5) and written to both places (block (p', p) is the transpose).  The packed slots
+      // are unpacked per node - a few bit-field extracts - from an opaque copy: the addresses derived from them stay out of the
+      // loop's live registers.
+      const BuildSlot s0 = BuildSlot::unpack(opaque_u(slot0)), s1 = BuildSlot::unpack(opaque_u(slot1));
+      const bool two = bw >= 2;                        // this wave has a second slot
       double hq[2][3] = {{0, 0, 0}, {0, 0, 0}}, xq[3] = {0, 0, 0}, gq[3] = {0, 0, 0}, cvq[3] = {0, 0, 0}, lamq = 0.0;
       bool liveq[3] = {false, false, false}, ownq[3] = {false, false, false};
-      int pdq[2], pcq[2];
-      bool ownp[2], dgp[2];
-      int pdg = 0;
-      bool anydg = false;
-#pragma unroll
-      for (int sl = 0; sl < 2; ++sl) {
-        const int e = bt + 256 * sl;
-        ownp[sl] = e < 13 * NP;
-        const int pa = ownp[sl] ? e / 13 : 0, dd = ownp[sl] ? e % 13 : 0;
-        pdq[sl] = pa;
-        pcq[sl] = pa + dd >= NP ? pa + dd - NP : pa + dd;
-        dgp[sl] = ownp[sl] && dd == 0;
-        if (dgp[sl]) pdg = pa;                         // (a thread owns at most one diagonal pair: e = 13 p, and 256 = 9 mod 13)
-        anydg = anydg || dgp[sl];
-      }
       if (has_next) {
         const int cur = ch.st->cur;
         const double* Hg = cur ? ch.H1 : ch.H0;
@@ -477,11 +537,11 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
 #pragma unroll
         for (int j = 0; j < 3; ++j)
           if (fb_next + j < K.n_frames) {
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl)
-              if (ownp[sl]) hq[sl][j] = Hg[(size_t)(fb_next + j) * HPAIRS + bt + 256 * sl];   // (pair e = 13 p + d: as stored)
+            hq[0][j] = Hg[(size_t)(fb_next + j) * HPAIRS + s0.e];                   // (pair e = 13 p + d: as stored)
+            if (two && s1.own) hq[1][j] = Hg[(size_t)(fb_next + j) * HPAIRS + s1.e];
           }
-        if (anydg) {
+        if (s0.dg) {
+          const int pdg = s0.pr;
           const double* xg = cur ? ch.x1 : ch.x0;
           const double* gg = cur ? ch.g1 : ch.g0;
 #pragma unroll
@@ -509,10 +569,12 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       lds_barrier(cB, tb, 4, ln);
       lds_wait(c_gfdone, n_s * k);
       if (bw == 0) SW_STAMP(1);
-      const GramQueue gqu{g_open, g_ticket, g_done};
       if (bt == 0) __hip_atomic_fetch_add(g_open, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (k > 0 && !uni_tables) fill_coupling_coef<256>(nullptr, cRk, K, node, bt, kq);
-      gram_help(gqu, Xf, Xg, k, li, lk, ln);
+      if (bw == 0) gram_fixed<0, 10>(Xf, Xg, g_done, li, lk, ln);
+      else if (bw == 1) gram_fixed<1, 7>(Xf, Xg, g_done, li, lk, ln);
+      else if (bw == 2) gram_fixed<4, 8, 12>(Xf, Xg, g_done, li, lk, ln);
+      else gram_fixed<3, 6, 11>(Xf, Xg, g_done, li, lk, ln);
       SW_STAMP(32 + wave);
       lds_barrier(cB, tb, 4, ln);                      // (the tables of this node in place)
       lds_wait(g_done, 15 * (k + 1));                  // G_k in Xg, every read of U_k (Xf) done
@@ -522,58 +584,64 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       asm volatile("" : "+v"(lamq));
       if (has_next) {
         double* const bvn = bvb + ((k + 1) & 1) * BS;
-        // S = E^T G_k E on the thread's blocks (reads Xg), the next node written straight into Xf.  Every LDS read of the three
-        // slots first (unconditional: a slot the thread does not own reads pair (0, 0)), then the arithmetic, the stores guarded
+        // S = E^T G_k E on the thread's blocks (reads Xg), the next node written straight into Xf.  Per slot every LDS read first,
+        // then the arithmetic, the stores guarded (a lane of slot 1 that owns no pair reads pair (0, 0)); the second slot's
+        // reads follow the first slot's stores: both slots' operands in flight together cost 31 more registers and spilled
         double ca[2][6], cb[2][6], gv[2][3][3];
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-          const int pr = pdq[sl], pc = pcq[sl];
-          ca[sl][0] = cRk[0 * NP + pr]; ca[sl][1] = cRk[1 * NP + pr]; ca[sl][2] = cRk[2 * NP + pr];
-          ca[sl][3] = cRk[4 * NP + pr]; ca[sl][4] = cRk[5 * NP + pr]; ca[sl][5] = cRk[8 * NP + pr];
-          cb[sl][0] = cRk[0 * NP + pc]; cb[sl][1] = cRk[1 * NP + pc]; cb[sl][2] = cRk[2 * NP + pc];
-          cb[sl][3] = cRk[4 * NP + pc]; cb[sl][4] = cRk[5 * NP + pc]; cb[sl][5] = cRk[8 * NP + pc];
+        auto slot_reads = [&](const BuildSlot& sl, double (&a)[6], double (&b)[6], double (&g)[3][3]) {
+          const double *ta = cRk + sl.pr, *tb_ = cRk + sl.pc;
+          a[0] = ta[0 * NP]; a[1] = ta[1 * NP]; a[2] = ta[2 * NP];
+          a[3] = ta[4 * NP]; a[4] = ta[5 * NP]; a[5] = ta[8 * NP];
+          b[0] = tb_[0 * NP]; b[1] = tb_[1 * NP]; b[2] = tb_[2 * NP];
+          b[3] = tb_[4 * NP]; b[4] = tb_[5 * NP]; b[5] = tb_[8 * NP];
+          const double* gp0 = Xg + sl.base;
 #pragma unroll
           for (int jj = 0; jj < 3; ++jj) {
-            const double* gp = Xg + (jj * NP + pr) * LD + pc;
-            gv[sl][jj][0] = gp[0];
-            gv[sl][jj][1] = gp[NP];
-            gv[sl][jj][2] = gp[2 * NP];
+            const double* gp = gp0 + jj * NP * LD;
+            g[jj][0] = gp[0];
+            g[jj][1] = gp[NP];
+            g[jj][2] = gp[2 * NP];
           }
-        }
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-          const int pr = pdq[sl], pc = pcq[sl];
-          const bool dg = dgp[sl];
-          const double a00 = ca[sl][0], a01 = ca[sl][1], a02 = ca[sl][2], a11 = ca[sl][3], a12 = ca[sl][4], a22 = ca[sl][5];
-          const double b00 = cb[sl][0], b01 = cb[sl][1], b02 = cb[sl][2], b11 = cb[sl][3], b12 = cb[sl][4], b22 = cb[sl][5];
-          double mm[3][3], S[3][3];
+        };
+        // (DIAG: the slot may hold a diagonal pair - slot 0 only)
+        auto slot_finish = [&](const BuildSlot& sl, auto may_diag, const double (&a)[6], const double (&b)[6], const double (&g)[3][3],
+                               const double (&h)[3]) {
+          // (the order of the operations and every fused multiply-add written out, contraction off: the node is the same bits
+          //  whatever the compiler would choose to fuse around this code - sums of products take their SECOND product as the
+          //  plain multiplication and fuse the others onto it, first then third)
+#pragma clang fp contract(off)
+          constexpr bool DIAG = decltype(may_diag)::value;
+          const int pr = sl.pr;
+          const bool dg = DIAG && sl.dg;
+          const double a00 = a[0], a01 = a[1], a02 = a[2], a11 = a[3], a12 = a[4], a22 = a[5];
+          const double b00 = b[0], b01 = b[1], b02 = b[2], b11 = b[3], b12 = b[4], b22 = b[5];
+          double mm[3][3], S[2][3];
 #pragma unroll
           for (int jj = 0; jj < 3; ++jj) {
-            const double g0 = gv[sl][jj][0], g1 = gv[sl][jj][1], g2 = gv[sl][jj][2];
-            mm[jj][0] = g0 * b00 + g1 * b01 + g2 * b02;
-            mm[jj][1] = g1 * b11 + g2 * b12;
+            const double g0 = g[jj][0], g1 = g[jj][1], g2 = g[jj][2];
+            mm[jj][0] = __builtin_fma(g2, b02, __builtin_fma(g0, b00, g1 * b01));      // g0 b00 + g1 b01 + g2 b02
+            mm[jj][1] = __builtin_fma(g1, b11, g2 * b12);                               // g1 b11 + g2 b12
             mm[jj][2] = g2 * b22;
           }
 #pragma unroll
           for (int ii = 0; ii < 3; ++ii) {
-            S[0][ii] = a00 * mm[0][ii] + a01 * mm[1][ii] + a02 * mm[2][ii];
-            S[1][ii] = a11 * mm[1][ii] + a12 * mm[2][ii];
-            S[2][ii] = a22 * mm[2][ii];
+            S[0][ii] = __builtin_fma(a02, mm[2][ii], __builtin_fma(a00, mm[0][ii], a01 * mm[1][ii]));   // a00 mm0 + a01 mm1 + a02 mm2
+            S[1][ii] = __builtin_fma(a11, mm[1][ii], a12 * mm[2][ii]);                                  // a11 mm1 + a12 mm2
           }
           double v[3][3];
 #pragma unroll
           for (int j = 0; j < 3; ++j)
 #pragma unroll
-            for (int jp = 0; jp < 3; ++jp) v[j][jp] = (j == jp ? hq[sl][j] : 0.0);
+            for (int jp = 0; jp < 3; ++jp) v[j][jp] = (j == jp ? h[j] : 0.0);
           if (dg) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
               double d = 1.0, bb = 0.0;
               if (liveq[j]) {
-                d = hq[sl][j];
+                d = h[j];
                 const double gtol = GRAD_ZERO_REL * d;
                 const bool fixed = (xq[j] <= klo[pr] && gq[j] > gtol) || (xq[j] >= khi[pr] && gq[j] < -gtol);
-                d = d + lamq * fmax(d, DIAG_FLOOR);
+                d = __builtin_fma(lamq, fmax(d, DIAG_FLOOR), d);
                 if (fixed) d *= FIX_SCALE;
                 bb = fixed ? 0.0 : -gq[j];
                 if (ownq[j]) gmax_run = fmax(gmax_run, fabs(bb));   // (window sharding: owned frames only)
@@ -585,16 +653,34 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
             v[0][2] = v[2][0] = cvq[1];
             v[1][2] = v[2][1] = cvq[2];
           }
-          if (ownp[sl]) {
+          // v - S; row 2 of S is the single product a22 mm2: fused into the subtraction in columns 0 and 2, not in column 1
+          double val[3][3];
+#pragma unroll
+          for (int jp = 0; jp < 3; ++jp) {
+            val[0][jp] = v[0][jp] - S[0][jp];
+            val[1][jp] = v[1][jp] - S[1][jp];
+          }
+          val[2][0] = __builtin_fma(-a22, mm[2][0], v[2][0]);
+          val[2][1] = v[2][1] - a22 * mm[2][1];
+          val[2][2] = __builtin_fma(-a22, mm[2][2], v[2][2]);
+          if (sl.own) {
+            double* const xa = Xf + sl.base;                     // block (p, p'): entry (j, jp) at (j NP + p) LD + jp NP + p'
+            double* const xt = Xf + sl.pc * LD + pr;             // its transpose
 #pragma unroll
             for (int j = 0; j < 3; ++j)
 #pragma unroll
               for (int jp = 0; jp < 3; ++jp) {
-                const double val = v[j][jp] - S[j][jp];
-                Xf[(j * NP + pr) * LD + jp * NP + pc] = val;
-                if (!dg) Xf[(jp * NP + pc) * LD + j * NP + pr] = val;
+                xa[j * NP * LD + jp * NP] = val[j][jp];
+                if (!dg) xt[jp * NP * LD + j * NP] = val[j][jp];
               }
           }
+        };
+        const BuildSlot b0 = BuildSlot::unpack(opaque_u(slot0)), b1 = BuildSlot::unpack(opaque_u(slot1));
+        slot_reads(b0, ca[0], cb[0], gv[0]);
+        slot_finish(b0, std::true_type{}, ca[0], cb[0], gv[0], hq[0]);
+        if (two) {
+          slot_reads(b1, ca[1], cb[1], gv[1]);
+          slot_finish(b1, std::false_type{}, ca[1], cb[1], gv[1], hq[1]);
         }
         // (padding rows / columns 75 .. 79: the factorisation left an identity block there; the diagonal is rewritten all the same,
         //  and the padding of the right-hand side is zero in both buffers)
@@ -627,7 +713,7 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       // ============================== the spike of node k ==============================
       SpikeArgs sa;
       sa.Xg = Xg; sa.Y = Y; sa.Ag = sp.AL + (size_t)(hasL ? opaque(sL) : 0) * MB; sa.cRk = cRk; sa.bvn = bvb + ((k + 1) & 1) * BS;
-      sa.zk = ch.b + (size_t)node * BS; sa.gq = GramQueue{g_open, g_ticket, g_done}; sa.Xf = Xf; sa.c_gfdone = c_gfdone; sa.c_fready = c_fready; sa.c_bv = c_bv; sa.tdone = tdone;
+      sa.zk = ch.b + (size_t)node * BS; sa.g_open = g_open; sa.g_done = g_done; sa.Xf = Xf; sa.c_gfdone = c_gfdone; sa.c_fready = c_fready; sa.c_bv = c_bv; sa.tdone = tdone;
       sa.k = k; sa.n_s = n_s; sa.hasL = hasL; sa.has_next = has_next; sa.stamps = (dbgp && k == dbg_k) ? lst : nullptr;
       if (role == 4) spike_node<4>(sa, tsb, ln);
       else if (role == 5) spike_node<5>(sa, tsb, ln);

@@ -30,7 +30,7 @@ names = {0: "D: iteration starts (loads of the next node requested)", 1: "D: U_k
          2: "D: G_k complete", 4: "D: next node built"}
 for w in (0, 1, 5, 4):
     names[8 + w] = f"D wave {w}: node done"
-    names[32 + w] = f"D wave {w}: no tile of G_k left to draw"
+    names[32 + w] = f"D wave {w}: its tiles of G_k done"
 who = ["wave 2 (strip 1)", "wave 6 (strips 2, 0)", "wave 3 (strip 3)", "wave 7 (strip 4)"]
 for r in range(4):
     names[16 + 4 * r] = f"S {who[r]}: G_k complete"; names[17 + 4 * r] = f"S {who[r]}: T = G F done"
