@@ -12,6 +12,9 @@
 // of them).  TABLE (more cameras, or ACINO_SBA_UNFUSED=1 as an independent cross-check): one thread per POINT walks its
 // observations (CSR built by the host), the coupling blocks W_pc (6 x 3) live in a dense table [point][camera], camera-block
 // sums go through 16 lane-private copies in LDS, the Schur complement is added with LDS atomics.
+// Both paths are driven by one Levenberg-Marquardt controller (sba_lm, in the host layer at the end of this file) and differ
+// in what a linearisation, a trial step and an accepted step cost them; the argument check and the workspace carve are shared
+// with the covariance entry (sba_host.hpp).
 // History (config 5, 1.28 M points, 6.5 M observations, per LM iteration): table + LDS atomics 6.1 ms; table + matrix-core GEMM
 // over the table 2.2 ms (round 4, W written once and read twice: 456 B per observation); fused 1.0 ms of kernels.
 #include <algorithm>
@@ -21,6 +24,7 @@
 #include "common.hpp"
 #include "dense80.hpp"
 #include "sba_dev.hpp"
+#include "sba_host.hpp"
 
 namespace acino {
 
@@ -927,7 +931,303 @@ __global__ void k_sba_apply_cams(SbaBuf B, const double* __restrict__ Rt, double
   for (int j = 0; j < 3; ++j) Ro[9 + j] = R[9 + j] + dt[j];
 }
 
-static size_t a256(size_t v) { return (v + 255) / 256 * 256; }
+// ---- Host layer.  acino_sba_solve_sharded = sba_check_problem, the carve at sba_layout's offsets, k_sba_check, then ONE Levenberg-
+//      Marquardt controller (sba_lm) that one of the two paths (sba_fused_path, sba_table_path) drives through three closures.
+
+// the fused path: at most seven cameras (6 C + 1 rows fit three 16-row tiles); ACINO_SBA_UNFUSED=1 keeps the table form
+static bool sba_fused(int n_cams) {
+  static const bool unfused = getenv("ACINO_SBA_UNFUSED") != nullptr;
+  return 6 * n_cams + 1 <= 48 && !unfused;
+}
+
+struct SbaLayout {
+  size_t V, Vinv, gp, dp, pts_t, table, Spart, part3, U, dc, S, Rt_t, scal, total;
+};
+static SbaLayout sba_layout(int n_cams, size_t P) {
+  const size_t C = (size_t)n_cams, n = 6 * C;
+  SbaTake take;
+  SbaLayout L;
+  L.V = take(P * 6 * 8);
+  L.Vinv = take(P * 6 * 8);
+  L.gp = take(P * 3 * 8);
+  L.dp = take(P * 3 * 8);
+  L.pts_t = take(P * 3 * 8);                                                     // the trial points
+  L.table = take(sba_fused(n_cams) ? P * C * 4 : P * C * 18 * 8);                // slot [P][C]  |  Wpc [P][C][18]
+  L.Spart = take((size_t)(SBA_SCHUR_WG + 32) * (n * n + n + 27 * C) * 8);        // partial sums (+ 32 intermediate records)
+  L.part3 = take((size_t)SBA_SCHUR_WG * 4 * 8);                                  // cost / prediction / trial-cost partials
+  L.U = take(sba_align256(C * 21 * 8) + sba_align256(n * 8));                    // [U | gc] contiguous: one reduction
+  L.dc = take(n * 8);
+  L.S = take(sba_align256(n * n * 8) + sba_align256(n * 8));                     // [S | rhs] contiguous: one reduction
+  L.Rt_t = take(C * 12 * 8);                                                     // the trial poses
+  L.scal = take(64);
+  L.total = take.off + 1024;
+  return L;
+}
+
+// ---- one solve: the buffers, the stream, the ranks' reduction, and the steps that both paths are made of
+struct SbaRun {
+  SbaBuf B;
+  hipStream_t s;
+  acino_reduce_fn reduce;
+  void* reduce_user;
+  double *Rt, *pts;        // the iterate: the caller's arrays, updated in place
+  double *Rt_t, *pts_t;    // the trial iterate
+  double* res_before;
+  size_t n;                // 6 C
+  int nblk;                // workgroups of the one-thread-per-point kernels
+
+  // global sum (op 0) or maximum (op 1) over the ranks that share the cameras (no-op for a single process)
+  int greduce(double* d_buf, size_t cnt, int op) const {
+    if (!reduce) return ACINO_OK;
+    ACINO_HIP_CHECK(hipStreamSynchronize(s));
+    if (reduce(reduce_user, d_buf, (int64_t)cnt, op, (void*)s) != 0) {
+      set_error("SBA: the reduction callback failed");
+      return ACINO_ERR_CALLBACK;
+    }
+    return ACINO_OK;
+  }
+  // hs <- B.scal; *gmax (where asked for) <- max |gradient| over the points (hs[2]) and, when the cameras move, over g_c.
+  // One synchronisation.
+  int read_back(double hs[8], double* gmax) const {
+    double hgc[6 * SBA_MAXC];
+    const bool cams = gmax && B.opt_cams;
+    ACINO_HIP_CHECK(hipMemcpyAsync(hs, B.scal, 64, hipMemcpyDeviceToHost, s));
+    if (cams) ACINO_HIP_CHECK(hipMemcpyAsync(hgc, B.gc, n * 8, hipMemcpyDeviceToHost, s));
+    ACINO_HIP_CHECK(hipStreamSynchronize(s));
+    if (gmax) *gmax = hs[2];
+    if (cams)
+      for (size_t i = 0; i < n; ++i) *gmax = fmax(*gmax, fabs(hgc[i]));
+    return ACINO_OK;
+  }
+  // k_sba_point at (Rt_e, pts_e): hs[0] = the cost; with gmax also V, gp, Wpc, U, g_c and the gradient norm; optionally the residuals
+  int eval(const double* Rt_e, const double* pts_e, double* res, double hs[8], double* gmax) const {
+    typedef void (*PointKernel)(SbaBuf, const double*, const double*, double*);
+    const bool jac = gmax != nullptr, f64 = B.prec == ACINO_PREC_F64;
+    const PointKernel k = !jac ? k_sba_point<false, ACINO_PREC_F64>                         // (cost only: fp64)
+                               : f64 ? k_sba_point<true, ACINO_PREC_F64> : k_sba_point<true, ACINO_PREC_BF16_ROWS>;
+    ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
+    if (jac) ACINO_HIP_CHECK(hipMemsetAsync(B.U, 0, (B.C * 21 + n) * 8, s));                // [U | gc]
+    hipLaunchKernelGGL(k, dim3(nblk), dim3(256), jac ? (size_t)16 * B.C * 27 * (f64 ? 8 : 4) : 0, s, B, Rt_e, pts_e, res);
+    ACINO_LAUNCH_CHECK();
+    if (int e = greduce(B.scal, 1, 0)) return e;
+    if (jac) {
+      if (int e = greduce(B.scal + 2, 1, 1)) return e;
+      if (B.opt_cams)
+        if (int e = greduce(B.U, B.C * 21 + n, 0)) return e;
+    }
+    return read_back(hs, gmax);
+  }
+  int keep_trial() const {   // the trial iterate becomes the iterate
+    ACINO_HIP_CHECK(hipMemcpyAsync(pts, pts_t, (size_t)B.P * 3 * 8, hipMemcpyDeviceToDevice, s));
+    ACINO_HIP_CHECK(hipMemcpyAsync(Rt, Rt_t, (size_t)B.C * 12 * 8, hipMemcpyDeviceToDevice, s));
+    return ACINO_OK;
+  }
+};
+
+// ---- the Levenberg-Marquardt controller.  It owns F, lam, nu, the gain ratio, accept / reject, the four exits and every write
+//      to info; a path supplies three closures (each returns an ACINO code):
+//        linearise(lam, step, cur)  brings cur up to date - gmax, and F where it is not known yet.  step: a trial at this damping
+//                                   follows (false after the loop)
+//        trial(lam, tr)             the step at damping lam from that linearisation
+//        accept(tr, cur)            the trial iterate becomes the iterate: cur.F, cur.fresh
+struct SbaIterate {
+  double F = 0.0, gmax = 0.0;   // cost and max |gradient| (points and cameras)
+  bool have_F = false;          // F is the cost of the iterate (false until the first linearisation)
+  bool fresh = false;           // gmax describes the iterate
+};
+struct SbaTrial {
+  double pred, Ft;              // predicted reduction (points + cameras), cost of the trial iterate (INFINITY with not_pd)
+  bool not_pd;                  // the damped reduced camera system lost definiteness to round-off along the free gauge (7 DoF when
+};                              // every camera moves): a rejected step
+
+template <class Linearise, class Trial, class Accept>
+static int sba_lm(const acino_sba_params* prm, acino_sba_info* info, Linearise linearise, Trial trial, Accept accept) {
+  SbaIterate cur;
+  double lam = prm->lam0, nu = 2.0;
+  int rc = ACINO_OK;
+  info->iterations = info->accepted = info->status = 0;
+  auto bring_up = [&](bool step) {
+    const bool first = !cur.have_F;
+    if ((rc = linearise(lam, step, cur)) == ACINO_OK && first) info->cost_initial = cur.F;
+    return rc;
+  };
+  for (int it = 0; it < prm->max_iter; ++it) {
+    if (bring_up(true)) return rc;
+    if (cur.gmax <= prm->gtol) {
+      info->status = 3;
+      break;
+    }
+    info->iterations = it + 1;
+    SbaTrial tr;
+    if ((rc = trial(lam, tr))) return rc;
+    const double F0 = cur.F, gain = tr.pred > 0 ? (F0 - tr.Ft) / tr.pred : -1.0;
+    if (tr.Ft < F0) {
+      if ((rc = accept(tr, cur))) return rc;
+      info->accepted += 1;
+      const double t = 2.0 * gain - 1.0;
+      lam *= fmax(1.0 / 3.0, 1.0 - t * t * t);
+      nu = 2.0;
+      if (F0 - tr.Ft <= prm->ftol * fabs(cur.F)) {
+        info->status = 1;
+        break;
+      }
+    } else {
+      lam *= nu;
+      nu *= 2.0;
+      if (lam > 1e16) {
+        info->status = tr.not_pd ? 5 : 4;
+        if (tr.not_pd) set_error("SBA: reduced camera system not positive definite at any damping");
+        break;
+      }
+    }
+  }
+  if (!cur.fresh && bring_up(false)) return rc;   // gradient norm (and, with max_iter = 0, the cost) of the final iterate
+  info->cost_final = cur.F;
+  info->gnorm_inf = cur.gmax;
+  info->lam = lam;
+  return ACINO_OK;
+}
+
+// ---- fused path: per LM iteration ONE pass that linearises with lam baked in and reduces (k_sba_fused + the two-stage sum), the
+//      camera solve, the trial poses, ONE pass that back-substitutes and prices the trial iterate; one host read-back.  So the
+//      linearisation runs every iteration, whether or not the iterate moved, and the trial comes with it.
+static int sba_fused_path(const SbaRun& r, const acino_sba_params* prm, acino_sba_info* info) {
+  typedef void (*FusedKernel)(SbaBuf, const double*, const double*, double, int);
+  typedef void (*BacksubKernel)(SbaBuf, double, const double*, const double*, const double*, double*, int);
+  static_assert(ACINO_PREC_F64 == 0 && ACINO_PREC_BF16_ROWS == 1, "the kernel tables are indexed by the precision code");
+  const FusedKernel fused[2][2][2] = {                                                  // [precision][camera model][with the cost]
+      {{k_sba_fused<ACINO_PREC_F64, 0, false>, k_sba_fused<ACINO_PREC_F64, 0, true>},
+       {k_sba_fused<ACINO_PREC_F64, 1, false>, k_sba_fused<ACINO_PREC_F64, 1, true>}},
+      {{k_sba_fused<ACINO_PREC_BF16_ROWS, 0, false>, k_sba_fused<ACINO_PREC_BF16_ROWS, 0, true>},
+       {k_sba_fused<ACINO_PREC_BF16_ROWS, 1, false>, k_sba_fused<ACINO_PREC_BF16_ROWS, 1, true>}}};
+  const BacksubKernel backsub[2][2] = {{k_sba_backsub_fused<ACINO_PREC_F64, 0>, k_sba_backsub_fused<ACINO_PREC_F64, 1>},
+                                       {k_sba_backsub_fused<ACINO_PREC_BF16_ROWS, 0>, k_sba_backsub_fused<ACINO_PREC_BF16_ROWS, 1>}};
+  const SbaBuf& B = r.B;
+  hipStream_t s = r.s;
+  const int C = B.C;
+  const size_t P = (size_t)B.P, n = r.n;
+  ACINO_HIP_CHECK(hipMemsetAsync(B.slot, 0xFF, P * C * 4, s));
+  hipLaunchKernelGGL(k_sba_slots, dim3(r.nblk), dim3(256), 0, s, B);
+  ACINO_LAUNCH_CHECK();
+  double hs[8];
+  if (r.res_before)
+    if (int e = r.eval(r.Rt, r.pts, r.res_before, hs, nullptr)) return e;
+  const int ppp = 64 / C;
+  const size_t batches = (P + ppp - 1) / ppp;
+  const int waves = (int)std::min<size_t>((size_t)SBA_SCHUR_WG * 4, batches);
+  const int ppw = (int)((batches + waves - 1) / waves) * ppp, n_wg = (int)((P + (size_t)4 * ppw - 1) / ((size_t)4 * ppw));
+  const int tail = 27 * C;
+  const unsigned rblk = (unsigned)((n * n + n + tail + 255) / 256);
+
+  auto linearise = [&](double lam, bool step, SbaIterate& cur) -> int {
+    const bool with_cost = !cur.have_F;                   // the first cost comes with the first linearisation
+    ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
+    const FusedKernel k_fused = fused[B.prec][B.model][with_cost];
+    hipLaunchKernelGGL(k_fused, dim3(n_wg), dim3(FU_T), fused_lds_bytes(C), s, B, r.Rt, r.pts, lam, ppw);
+    ACINO_LAUNCH_CHECK();
+    if (with_cost) {
+      hipLaunchKernelGGL(k_sba_sum_parts, dim3(1), dim3(256), 0, s, B, n_wg, 0, 0, -1, 0);
+      ACINO_LAUNCH_CHECK();
+    }
+    if (B.opt_cams) {
+      hipLaunchKernelGGL(k_sba_schur_reduce, dim3(rblk, 32), dim3(256), 0, s, B, n_wg, 0, tail);
+      ACINO_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_sba_schur_reduce, dim3(rblk, 1), dim3(256), 0, s, B, n_wg, 1, tail);
+      ACINO_LAUNCH_CHECK();
+    }
+    if (with_cost)
+      if (int e = r.greduce(B.scal, 1, 0)) return e;
+    if (int e = r.greduce(B.scal + 2, 1, 1)) return e;
+    if (B.opt_cams) {
+      if (int e = r.greduce(B.U, C * 21 + n, 0)) return e;
+      if (int e = r.greduce(B.S, n * n + n, 0)) return e;
+    }
+    if (step) {
+      if (B.opt_cams) {
+        if (n <= (size_t)CS_N) hipLaunchKernelGGL(k_sba_cam_solve_wave, dim3(1), dim3(64), 0, s, B, lam);
+        else hipLaunchKernelGGL(k_sba_cam_solve, dim3(1), dim3(256), (n * (n + 1) + n) * 8, s, B, lam);
+        ACINO_LAUNCH_CHECK();
+      }
+      hipLaunchKernelGGL(k_sba_apply_cams, dim3(1), dim3(64), 0, s, B, r.Rt, r.Rt_t);
+      ACINO_LAUNCH_CHECK();
+      const BacksubKernel k_backsub = backsub[B.prec][B.model];
+      hipLaunchKernelGGL(k_backsub, dim3(n_wg), dim3(FU_T), 0, s, B, lam, r.Rt, r.Rt_t, r.pts, r.pts_t, ppw);
+      ACINO_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_sba_sum_parts, dim3(1), dim3(256), 0, s, B, n_wg, 1, 1, 2, 6);
+      ACINO_LAUNCH_CHECK();
+      if (int e = r.greduce(B.scal + 1, 1, 0)) return e;
+      if (int e = r.greduce(B.scal + 6, 1, 0)) return e;
+    }
+    if (int e = r.read_back(hs, &cur.gmax)) return e;
+    cur.fresh = true;
+    if (with_cost) {
+      cur.F = hs[0];
+      cur.have_F = true;
+    }
+    return ACINO_OK;
+  };
+  auto trial = [&](double, SbaTrial& tr) -> int {         // (already on the host: no launch)
+    tr.pred = hs[1] + hs[4];
+    tr.not_pd = hs[3] != 0.0;
+    tr.Ft = tr.not_pd ? INFINITY : hs[6];
+    return ACINO_OK;
+  };
+  auto accept = [&](const SbaTrial& tr, SbaIterate& cur) -> int {
+    cur.F = tr.Ft;
+    cur.fresh = false;
+    return r.keep_trial();
+  };
+  return sba_lm(prm, info, linearise, trial, accept);
+}
+
+// ---- table path: k_sba_point<true> linearises without the damping, so only when the iterate moved - gmax is known before the
+//      step -; k_sba_schur(lam) forms the damped Schur complement every iteration; the trial iterate is priced by an evaluation
+//      of its own (skipped when the not-PD flag is set), and an accepted iterate is re-linearised at once: its cost is the
+//      re-evaluated one, which is also what ftol is tested against.
+static int sba_table_path(const SbaRun& r, const acino_sba_params* prm, acino_sba_info* info) {
+  const SbaBuf& B = r.B;
+  hipStream_t s = r.s;
+  const size_t n = r.n;
+  auto linearise = [&](double, bool, SbaIterate& cur) -> int {
+    if (cur.fresh) return ACINO_OK;
+    double hs[8];
+    if (int e = r.eval(r.Rt, r.pts, cur.have_F ? nullptr : r.res_before, hs, &cur.gmax)) return e;
+    cur.F = hs[0];
+    cur.have_F = cur.fresh = true;
+    return ACINO_OK;
+  };
+  auto trial = [&](double lam, SbaTrial& tr) -> int {
+    ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
+    if (B.opt_cams) ACINO_HIP_CHECK(hipMemsetAsync(B.S, 0, (n * n + n) * 8, s));
+    hipLaunchKernelGGL(k_sba_schur, dim3(r.nblk), dim3(256), (n * n + n) * 8, s, B, lam);
+    ACINO_LAUNCH_CHECK();
+    if (B.opt_cams) {
+      if (int e = r.greduce(B.S, n * n + n, 0)) return e;
+      hipLaunchKernelGGL(k_sba_cam_solve, dim3(1), dim3(256), (n * (n + 1) + n) * 8, s, B, lam);
+      ACINO_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_sba_backsub, dim3(r.nblk), dim3(256), 0, s, B, lam, r.pts, r.pts_t);
+    ACINO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sba_apply_cams, dim3(1), dim3(64), 0, s, B, r.Rt, r.Rt_t);
+    ACINO_LAUNCH_CHECK();
+    if (int e = r.greduce(B.scal + 1, 1, 0)) return e;
+    double hs[8];
+    if (int e = r.read_back(hs, nullptr)) return e;
+    tr.pred = hs[1] + hs[4];
+    tr.not_pd = hs[3] != 0.0;
+    tr.Ft = INFINITY;
+    if (tr.not_pd) return ACINO_OK;
+    if (int e = r.eval(r.Rt_t, r.pts_t, nullptr, hs, nullptr)) return e;
+    tr.Ft = hs[0];
+    return ACINO_OK;
+  };
+  auto accept = [&](const SbaTrial&, SbaIterate& cur) -> int {
+    if (int e = r.keep_trial()) return e;
+    cur.fresh = false;
+    return linearise(0.0, false, cur);
+  };
+  return sba_lm(prm, info, linearise, trial, accept);
+}
 
 }  // namespace acino
 
@@ -938,23 +1238,9 @@ extern "C" {
 size_t acino_sizeof_sba_params(void) { return sizeof(acino_sba_params); }
 size_t acino_sizeof_sba_info(void) { return sizeof(acino_sba_info); }
 
-// the fused path: at most seven cameras (6 C + 1 rows fit three 16-row tiles); ACINO_SBA_UNFUSED=1 keeps the table form
-static bool sba_fused(int n_cams) {
-  static const bool unfused = getenv("ACINO_SBA_UNFUSED") != nullptr;
-  return 6 * n_cams + 1 <= 48 && !unfused;
-}
-
 size_t acino_sba_workspace_bytes(int n_cams, int64_t n_points, int64_t n_obs) {
   if (n_cams < 1 || n_points < 0 || n_obs < 0) return 0;
-  const size_t P = (size_t)n_points, M = (size_t)n_obs, n = 6 * (size_t)n_cams;
-  size_t b = 0;
-  (void)M;
-  b += a256(P * 6 * 8) * 2 + a256(P * 3 * 8) * 3;                                      // V, Vinv, gp, dp, pts_t
-  b += sba_fused(n_cams) ? a256(P * n_cams * 4) : a256(P * n_cams * 18 * 8);           // slot [P][C]  |  Wpc [P][C][18]
-  b += a256((size_t)(SBA_SCHUR_WG + 32) * (n * n + n + 27 * (size_t)n_cams) * 8);      // partial sums (+ 32 intermediate records)
-  b += a256((size_t)SBA_SCHUR_WG * 4 * 8);                                               // cost / prediction / trial-cost partials
-  b += a256(n_cams * 21 * 8) + a256(n * 8) * 3 + a256(n * n * 8) + a256(n_cams * 12 * 8) + a256(64);
-  return b + 1024;
+  return sba_layout(n_cams, (size_t)n_points).total;
 }
 
 // Solves in place: d_Rt[C][12] (R row-major | t) and d_pts[P][3].  d_res_before / d_res_after [M][2] may be NULL.
@@ -971,28 +1257,20 @@ int acino_sba_solve_sharded(const acino_sba_params* prm, const double* d_intr, d
                             const int32_t* d_pt_obs, void* d_ws, size_t ws_bytes, double* d_res_before,
                             double* d_res_after, acino_sba_info* info, acino_reduce_fn reduce, void* reduce_user,
                             void* stream) {
-  ACINO_REQUIRE(prm && info, "params/info");
-  ACINO_REQUIRE(prm->n_cams >= 1 && prm->n_cams <= SBA_MAXC, "n_cams in 1..16");
-  ACINO_REQUIRE(prm->n_points >= 1 && prm->n_obs >= 1, "sizes (a rank without points cannot take part)");
-  ACINO_REQUIRE(prm->f_scale > 0 && prm->lam0 > 0 && prm->max_iter >= 0, "f_scale, lam0, max_iter");
-  ACINO_REQUIRE(prm->camera_model == 0 || prm->camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
+  if (int e = sba_check_problem(prm, info, d_intr && d_Rt && d_pts && d_uv && d_cam_idx && d_pt_start && d_pt_obs && d_ws, d_ws,
+                                ws_bytes, acino_sba_workspace_bytes, ACINO_ERR_INVALID_ARG, "invalid argument: "))
+    return e;
+  ACINO_REQUIRE(prm->lam0 > 0 && prm->max_iter >= 0, "lam0, max_iter");
   ACINO_REQUIRE(prm->precision == ACINO_PREC_F64 || prm->precision == ACINO_PREC_BF16_ROWS, "precision: 0 f64, 1 bf16 rows");
-  ACINO_REQUIRE(d_intr && d_Rt && d_pts && d_uv && d_cam_idx && d_pt_start && d_pt_obs && d_ws, "null buffer");
-  ACINO_REQUIRE(((uintptr_t)d_ws & 255) == 0, "workspace must be 256-byte aligned");
-  ACINO_REQUIRE(ws_bytes >= acino_sba_workspace_bytes(prm->n_cams, prm->n_points, prm->n_obs), "workspace too small");
-  hipStream_t s = (hipStream_t)stream;
   const int C = prm->n_cams;
-  const size_t P = (size_t)prm->n_points, M = (size_t)prm->n_obs, n = 6 * (size_t)C;
+  const size_t P = (size_t)prm->n_points, n = 6 * (size_t)C;
+  const SbaLayout L = sba_layout(C, P);
+  const bool fused = sba_fused(C);
   char* w = (char*)d_ws;
-  auto take = [&](size_t bytes) {
-    char* p = w;
-    w += a256(bytes);
-    return p;
-  };
   SbaBuf B;
   B.C = C;
   B.P = (int)P;
-  B.M = (int)M;
+  B.M = (int)prm->n_obs;
   B.opt_cams = prm->optimize_cameras ? 1 : 0;
   B.model = prm->camera_model;
   B.prec = prm->precision;
@@ -1002,313 +1280,39 @@ int acino_sba_solve_sharded(const acino_sba_params* prm, const double* d_intr, d
   B.cam_idx = d_cam_idx;
   B.pt_start = d_pt_start;
   B.pt_obs = d_pt_obs;
-  B.V = (double*)take(P * 6 * 8);
-  B.Vinv = (double*)take(P * 6 * 8);
-  B.gp = (double*)take(P * 3 * 8);
-  B.dp = (double*)take(P * 3 * 8);
-  double* pts_t = (double*)take(P * 3 * 8);
-  const bool fused = sba_fused(C);
-  B.Wpc = nullptr;
-  B.slot = nullptr;
-  if (fused) B.slot = (int*)take(P * C * 4);
-  else B.Wpc = (double*)take(P * C * 18 * 8);
-  B.Spart = (double*)take((size_t)(SBA_SCHUR_WG + 32) * (n * n + n + 27 * (size_t)C) * 8);
-  B.part3 = (double*)take((size_t)SBA_SCHUR_WG * 4 * 8);
-  // (the dense W table: slots of cameras that do not see a point are never written - zero them once)
-  if (!fused && B.opt_cams) ACINO_HIP_CHECK(hipMemsetAsync(B.Wpc, 0, P * C * 18 * 8, s));
-  B.U = (double*)take((C * 21 + n) * 8);      // [U | gc] contiguous: one reduction
+  B.V = (double*)(w + L.V);
+  B.Vinv = (double*)(w + L.Vinv);
+  B.gp = (double*)(w + L.gp);
+  B.dp = (double*)(w + L.dp);
+  B.slot = fused ? (int*)(w + L.table) : nullptr;
+  B.Wpc = fused ? nullptr : (double*)(w + L.table);
+  B.Spart = (double*)(w + L.Spart);
+  B.part3 = (double*)(w + L.part3);
+  B.U = (double*)(w + L.U);
   B.gc = B.U + C * 21;
-  B.dc = (double*)take(n * 8);
-  B.S = (double*)take((n * n + n) * 8);        // [S | rhs] contiguous: one reduction
+  B.dc = (double*)(w + L.dc);
+  B.S = (double*)(w + L.S);
   B.rhs = B.S + n * n;
-  double* Rt_t = (double*)take(C * 12 * 8);
-  B.scal = (double*)take(64);                  // 0 cost, 1 predicted reduction (points), 2 max |g_point|, 3 not-PD flag,
-                                               // 4 predicted reduction (cameras; identical on every rank)
-  // global sums / maxima over the ranks that share the cameras (no-op for a single process)
-  auto greduce = [&](double* d_buf, size_t cnt, int op) -> int {
-    if (!reduce) return ACINO_OK;
-    ACINO_HIP_CHECK(hipStreamSynchronize(s));
-    if (reduce(reduce_user, d_buf, (int64_t)cnt, op, stream) != 0) {
-      set_error("SBA: the reduction callback failed");
-      return ACINO_ERR_CALLBACK;
-    }
-    return ACINO_OK;
-  };
-  const int nblk = (int)((P + 255) / 256);
-  const size_t lds_s = (n * n + n) * 8, lds_c = (n * (n + 1) + n) * 8;
+  B.scal = (double*)(w + L.scal);              // 0 cost, 1 predicted reduction (points), 2 max |g_point|, 3 not-PD flag,
+                                               // 4 predicted reduction (cameras; identical on every rank), 6 trial cost, 7 bad input
+  const SbaRun r{B, (hipStream_t)stream, reduce, reduce_user, d_Rt, d_pts, (double*)(w + L.Rt_t), (double*)(w + L.pts_t),
+                 d_res_before, n, (int)((P + 255) / 256)};
+  // (the dense W table: slots of cameras that do not see a point are never written - zero them once)
+  if (!fused && B.opt_cams) ACINO_HIP_CHECK(hipMemsetAsync(B.Wpc, 0, P * C * 18 * 8, r.s));
 
-  auto eval = [&](const double* Rt, const double* pts, bool jac, double* res, double h[4]) -> int {
-    ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
-    if (jac) {
-      ACINO_HIP_CHECK(hipMemsetAsync(B.U, 0, C * 21 * 8, s));
-      ACINO_HIP_CHECK(hipMemsetAsync(B.gc, 0, n * 8, s));
-      if (B.prec == ACINO_PREC_F64) hipLaunchKernelGGL((k_sba_point<true, ACINO_PREC_F64>), dim3(nblk), dim3(256), 16 * C * 27 * 8, s, B, Rt, pts, res);
-      else hipLaunchKernelGGL((k_sba_point<true, ACINO_PREC_BF16_ROWS>), dim3(nblk), dim3(256), 16 * C * 27 * 4, s, B, Rt, pts, res);
-    } else {
-      hipLaunchKernelGGL((k_sba_point<false, ACINO_PREC_F64>), dim3(nblk), dim3(256), 0, s, B, Rt, pts, res);   // (cost only: fp64)
-    }
-    ACINO_LAUNCH_CHECK();
-    if (int e = greduce(B.scal, 1, 0)) return e;
-    if (jac) {
-      if (int e = greduce(B.scal + 2, 1, 1)) return e;
-      if (B.opt_cams)
-        if (int e = greduce(B.U, C * 21 + n, 0)) return e;
-    }
-    ACINO_HIP_CHECK(hipMemcpyAsync(h, B.scal, 32, hipMemcpyDeviceToHost, s));
-    ACINO_HIP_CHECK(hipStreamSynchronize(s));
-    return ACINO_OK;
-  };
+  // ---- input check, both paths; the flag is combined over the ranks (max) BEFORE anyone returns: a rank that left early
+  //      would leave the others waiting in the first reduction of the solve
+  double hs[8];
+  ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, r.s));
+  hipLaunchKernelGGL(k_sba_check, dim3(r.nblk), dim3(256), 0, r.s, B);
+  ACINO_LAUNCH_CHECK();
+  if (int e = r.greduce(B.scal + 7, 1, 1)) return e;
+  if (int e = r.read_back(hs, nullptr)) return e;
+  ACINO_REQUIRE(hs[7] == 0.0, "SBA: two observations of one point by one camera, or a camera index out of range");
 
-  {
-    // ---- input check, both paths; the flag is combined over the ranks (max) BEFORE anyone returns: a rank that left early
-    //      would leave the others waiting in the first reduction of the solve
-    ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
-    hipLaunchKernelGGL(k_sba_check, dim3(nblk), dim3(256), 0, s, B);
-    ACINO_LAUNCH_CHECK();
-    if (int e = greduce(B.scal + 7, 1, 1)) return e;
-    double dup = 0.0;
-    ACINO_HIP_CHECK(hipMemcpyAsync(&dup, B.scal + 7, 8, hipMemcpyDeviceToHost, s));
-    ACINO_HIP_CHECK(hipStreamSynchronize(s));
-    ACINO_REQUIRE(dup == 0.0, "SBA: two observations of one point by one camera, or a camera index out of range");
-  }
-  if (fused) {
-    // ---- fused path: per LM iteration ONE pass that linearises and reduces (k_sba_fused + the two-stage sum), the camera
-    //      solve, the trial poses, ONE pass that back-substitutes and prices the trial iterate; one host read-back.
-    ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
-    ACINO_HIP_CHECK(hipMemsetAsync(B.slot, 0xFF, P * C * 4, s));
-    hipLaunchKernelGGL(k_sba_slots, dim3(nblk), dim3(256), 0, s, B);
-    ACINO_LAUNCH_CHECK();
-    double hd[4];
-    int rc = ACINO_OK;
-    if (d_res_before) {
-      rc = eval(d_Rt, d_pts, false, d_res_before, hd);
-      if (rc) return rc;
-    }
-    const int ppp = 64 / C;
-    const size_t batches = (P + ppp - 1) / ppp;
-    const int waves = (int)std::min<size_t>((size_t)SBA_SCHUR_WG * 4, batches);
-    const int ppw = (int)((batches + waves - 1) / waves) * ppp, n_wg = (int)((P + (size_t)4 * ppw - 1) / ((size_t)4 * ppw));
-    const size_t lds_f = fused_lds_bytes(C);
-    const int tail = 27 * C;
-    const unsigned rblk = (unsigned)((n * n + n + tail + 255) / 256);
-    auto linearise = [&](double lam, bool with_cost) -> int {
-      ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
-#define ACINO_SBA_FUSED(PRECV, MODELV)                                                                                            \
-  do {                                                                                                                            \
-    if (with_cost) hipLaunchKernelGGL((k_sba_fused<PRECV, MODELV, true>), dim3(n_wg), dim3(FU_T), lds_f, s, B, d_Rt, d_pts, lam, ppw); \
-    else hipLaunchKernelGGL((k_sba_fused<PRECV, MODELV, false>), dim3(n_wg), dim3(FU_T), lds_f, s, B, d_Rt, d_pts, lam, ppw);     \
-  } while (0)
-      if (B.prec == ACINO_PREC_F64) {
-        if (B.model == 0) ACINO_SBA_FUSED(ACINO_PREC_F64, 0);
-        else ACINO_SBA_FUSED(ACINO_PREC_F64, 1);
-      } else {
-        if (B.model == 0) ACINO_SBA_FUSED(ACINO_PREC_BF16_ROWS, 0);
-        else ACINO_SBA_FUSED(ACINO_PREC_BF16_ROWS, 1);
-      }
-#undef ACINO_SBA_FUSED
-      ACINO_LAUNCH_CHECK();
-      if (with_cost) {
-        hipLaunchKernelGGL(k_sba_sum_parts, dim3(1), dim3(256), 0, s, B, n_wg, 0, 0, -1, 0);
-        ACINO_LAUNCH_CHECK();
-      }
-      if (B.opt_cams) {
-        hipLaunchKernelGGL(k_sba_schur_reduce, dim3(rblk, 32), dim3(256), 0, s, B, n_wg, 0, tail);
-        ACINO_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_sba_schur_reduce, dim3(rblk, 1), dim3(256), 0, s, B, n_wg, 1, tail);
-        ACINO_LAUNCH_CHECK();
-      }
-      if (with_cost)
-        if (int e = greduce(B.scal, 1, 0)) return e;
-      if (int e = greduce(B.scal + 2, 1, 1)) return e;
-      if (B.opt_cams) {
-        if (int e = greduce(B.U, C * 21 + n, 0)) return e;
-        if (int e = greduce(B.S, n * n + n, 0)) return e;
-      }
-      return ACINO_OK;
-    };
-    auto read_back = [&](double hs[8], double& gmax) -> int {
-      double hgc[6 * SBA_MAXC];
-      ACINO_HIP_CHECK(hipMemcpyAsync(hs, B.scal, 64, hipMemcpyDeviceToHost, s));
-      if (B.opt_cams) ACINO_HIP_CHECK(hipMemcpyAsync(hgc, B.gc, n * 8, hipMemcpyDeviceToHost, s));
-      ACINO_HIP_CHECK(hipStreamSynchronize(s));
-      gmax = hs[2];
-      if (B.opt_cams)
-        for (size_t i = 0; i < n; ++i) gmax = fmax(gmax, fabs(hgc[i]));
-      return ACINO_OK;
-    };
-    double F = 0.0, lam = prm->lam0, nu = 2.0, gmax = 0.0, hs[8];
-    bool fresh = false;                                   // hs / gmax describe the CURRENT iterate
-    info->iterations = 0;
-    info->accepted = 0;
-    info->status = 0;
-    for (int it = 0; it < prm->max_iter; ++it) {
-      if ((rc = linearise(lam, it == 0))) return rc;
-      if (B.opt_cams) {
-        if (n <= (size_t)CS_N) hipLaunchKernelGGL(k_sba_cam_solve_wave, dim3(1), dim3(64), 0, s, B, lam);
-        else hipLaunchKernelGGL(k_sba_cam_solve, dim3(1), dim3(256), lds_c, s, B, lam);
-        ACINO_LAUNCH_CHECK();
-      }
-      hipLaunchKernelGGL(k_sba_apply_cams, dim3(1), dim3(64), 0, s, B, d_Rt, Rt_t);
-      ACINO_LAUNCH_CHECK();
-#define ACINO_SBA_BACK(PRECV, MODELV) \
-  hipLaunchKernelGGL((k_sba_backsub_fused<PRECV, MODELV>), dim3(n_wg), dim3(FU_T), 0, s, B, lam, d_Rt, Rt_t, d_pts, pts_t, ppw)
-      if (B.prec == ACINO_PREC_F64) {
-        if (B.model == 0) ACINO_SBA_BACK(ACINO_PREC_F64, 0);
-        else ACINO_SBA_BACK(ACINO_PREC_F64, 1);
-      } else {
-        if (B.model == 0) ACINO_SBA_BACK(ACINO_PREC_BF16_ROWS, 0);
-        else ACINO_SBA_BACK(ACINO_PREC_BF16_ROWS, 1);
-      }
-#undef ACINO_SBA_BACK
-      ACINO_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_sba_sum_parts, dim3(1), dim3(256), 0, s, B, n_wg, 1, 1, 2, 6);
-      ACINO_LAUNCH_CHECK();
-      if (int e = greduce(B.scal + 1, 1, 0)) return e;
-      if (int e = greduce(B.scal + 6, 1, 0)) return e;
-      if ((rc = read_back(hs, gmax))) return rc;
-      fresh = true;
-      if (it == 0) {
-        F = hs[0];
-        info->cost_initial = F;
-      }
-      if (gmax <= prm->gtol) {
-        info->status = 3;
-        break;
-      }
-      info->iterations = it + 1;
-      const double pred = hs[1] + hs[4];
-      // (hs[3] != 0: the damped reduced camera system lost definiteness to round-off along the free gauge - 7 DoF when every
-      //  camera moves -: a rejected step)
-      const double Ft = hs[3] == 0.0 ? hs[6] : INFINITY;
-      const double gain = pred > 0 ? (F - Ft) / pred : -1.0;
-      if (Ft < F) {
-        const double dF = F - Ft;
-        ACINO_HIP_CHECK(hipMemcpyAsync(d_pts, pts_t, P * 3 * 8, hipMemcpyDeviceToDevice, s));
-        ACINO_HIP_CHECK(hipMemcpyAsync(d_Rt, Rt_t, C * 12 * 8, hipMemcpyDeviceToDevice, s));
-        F = Ft;
-        fresh = false;
-        info->accepted += 1;
-        const double t = 2.0 * gain - 1.0;
-        lam *= fmax(1.0 / 3.0, 1.0 - t * t * t);
-        nu = 2.0;
-        if (dF <= prm->ftol * fabs(F)) {
-          info->status = 1;
-          break;
-        }
-      } else {
-        lam *= nu;
-        nu *= 2.0;
-        if (lam > 1e16) {
-          info->status = hs[3] != 0.0 ? 5 : 4;
-          if (info->status == 5) set_error("SBA: reduced camera system not positive definite at any damping");
-          break;
-        }
-      }
-    }
-    if (!fresh) {                                          // gradient norm (and, with max_iter = 0, the cost) of the final iterate
-      const bool first = prm->max_iter == 0;
-      if ((rc = linearise(lam, first))) return rc;
-      if ((rc = read_back(hs, gmax))) return rc;
-      if (first) {
-        F = hs[0];
-        info->cost_initial = F;
-      }
-    }
-    if (d_res_after) {
-      rc = eval(d_Rt, d_pts, false, d_res_after, hd);
-      if (rc) return rc;
-    }
-    info->cost_final = F;
-    info->gnorm_inf = gmax;
-    info->lam = lam;
-    return info->status == 5 ? ACINO_ERR_NUMERIC : ACINO_OK;
-  }
-
-  double h[4];
-  int rc = eval(d_Rt, d_pts, true, d_res_before, h);
-  if (rc) return rc;
-  double F = h[0], lam = prm->lam0, nu = 2.0;
-  info->cost_initial = F;
-  info->iterations = 0;
-  info->accepted = 0;
-  info->status = 0;
-  double gmax = h[2];
-  if (B.opt_cams) {
-    double hgc[6 * SBA_MAXC];
-    ACINO_HIP_CHECK(hipMemcpyAsync(hgc, B.gc, n * 8, hipMemcpyDeviceToHost, s));
-    ACINO_HIP_CHECK(hipStreamSynchronize(s));
-    for (size_t i = 0; i < n; ++i) gmax = fmax(gmax, fabs(hgc[i]));
-  }
-  for (int it = 0; it < prm->max_iter; ++it) {
-    if (gmax <= prm->gtol) {
-      info->status = 3;
-      break;
-    }
-    info->iterations = it + 1;
-    ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
-    if (B.opt_cams) ACINO_HIP_CHECK(hipMemsetAsync(B.S, 0, (n * n + n) * 8, s));
-    hipLaunchKernelGGL(k_sba_schur, dim3(nblk), dim3(256), lds_s, s, B, lam);
-    ACINO_LAUNCH_CHECK();
-    if (B.opt_cams) {
-      if (int e = greduce(B.S, n * n + n, 0)) return e;
-      hipLaunchKernelGGL(k_sba_cam_solve, dim3(1), dim3(256), lds_c, s, B, lam);
-      ACINO_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_sba_backsub, dim3(nblk), dim3(256), 0, s, B, lam, d_pts, pts_t);
-    ACINO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sba_apply_cams, dim3(1), dim3(64), 0, s, B, d_Rt, Rt_t);
-    ACINO_LAUNCH_CHECK();
-    if (int e = greduce(B.scal + 1, 1, 0)) return e;
-    double hp[5];
-    ACINO_HIP_CHECK(hipMemcpyAsync(hp, B.scal, 40, hipMemcpyDeviceToHost, s));
-    ACINO_HIP_CHECK(hipStreamSynchronize(s));
-    const double pred = hp[1] + hp[4];
-    double ht[4] = {INFINITY, 0, 0, 0};
-    if (hp[3] == 0.0) {   // else: the damped reduced camera system lost definiteness to round-off along the free
-      rc = eval(Rt_t, pts_t, false, nullptr, ht);   // gauge (7 DoF when every camera moves) - a rejected step
-      if (rc) return rc;
-    }
-    const double Ft = ht[0];
-    const double gain = pred > 0 ? (F - Ft) / pred : -1.0;
-    if (Ft < F) {
-      const double dF = F - Ft;
-      ACINO_HIP_CHECK(hipMemcpyAsync(d_pts, pts_t, P * 3 * 8, hipMemcpyDeviceToDevice, s));
-      ACINO_HIP_CHECK(hipMemcpyAsync(d_Rt, Rt_t, C * 12 * 8, hipMemcpyDeviceToDevice, s));
-      rc = eval(d_Rt, d_pts, true, nullptr, h);
-      if (rc) return rc;
-      F = h[0];
-      gmax = h[2];
-      if (B.opt_cams) {
-        double hgc[6 * SBA_MAXC];
-        ACINO_HIP_CHECK(hipMemcpyAsync(hgc, B.gc, n * 8, hipMemcpyDeviceToHost, s));
-        ACINO_HIP_CHECK(hipStreamSynchronize(s));
-        for (size_t i = 0; i < n; ++i) gmax = fmax(gmax, fabs(hgc[i]));
-      }
-      info->accepted += 1;
-      const double t = 2.0 * gain - 1.0;
-      lam *= fmax(1.0 / 3.0, 1.0 - t * t * t);
-      nu = 2.0;
-      if (dF <= prm->ftol * fabs(F)) {
-        info->status = 1;
-        break;
-      }
-    } else {
-      lam *= nu;
-      nu *= 2.0;
-      if (lam > 1e16) {
-        info->status = hp[3] != 0.0 ? 5 : 4;
-        if (info->status == 5) set_error("SBA: reduced camera system not positive definite at any damping");
-        break;
-      }
-    }
-  }
-  if (d_res_after) {
-    rc = eval(d_Rt, d_pts, false, d_res_after, h);
-    if (rc) return rc;
-  }
-  info->cost_final = F;
-  info->gnorm_inf = gmax;
-  info->lam = lam;
+  if (int e = fused ? sba_fused_path(r, prm, info) : sba_table_path(r, prm, info)) return e;
+  if (d_res_after)
+    if (int e = r.eval(d_Rt, d_pts, d_res_after, hs, nullptr)) return e;
   return info->status == 5 ? ACINO_ERR_NUMERIC : ACINO_OK;
 }
 

@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "sba_dev.hpp"
+#include "sba_host.hpp"
 
 namespace acino {
 
@@ -473,7 +474,23 @@ k_sbacov_points(CovBuf B, const double* __restrict__ covc, double scale, double*
   }
 }
 
-static size_t cv_a256(size_t v) { return (v + 255) / 256 * 256; }
+struct CovLayout {
+  size_t Spart, scalpart, S, N, T1, Bm, scal, total;
+};
+static CovLayout cov_layout(int n_cams) {
+  const size_t nn = (size_t)36 * n_cams * n_cams;
+  SbaTake take;
+  CovLayout L;
+  L.Spart = take((size_t)CV_WG * nn * 8);                  // partial records
+  L.scalpart = take((size_t)CV_WG * 4 * 8);                // scalar partials
+  L.S = take(nn * 8);
+  L.N = take(nn * 8);                                      // the gauge complement N [n][n - 7]
+  L.T1 = take(nn * 8);
+  L.Bm = take(nn * 8);                                     // B = L^-1 N^T
+  L.scal = take(64);
+  L.total = take.off + 1024;
+  return L;
+}
 
 // Orthonormal complement of the n x 7 constraint block G (row-major, overwritten): Householder QR, N = columns 7 .. n - 1 of Q
 // as [n][n - 7] row-major.  false when G has rank below 7 (a diagonal entry of R at or below n eps max column norm).
@@ -533,9 +550,7 @@ size_t acino_sizeof_sba_cov_info(void) { return sizeof(acino_sba_cov_info); }
 
 size_t acino_sba_covariance_workspace_bytes(int n_cams, int64_t n_points, int64_t n_obs) {
   if (n_cams < 1 || n_cams > SBA_MAXC || n_points < 0 || n_obs < 0) return 0;
-  const size_t nn = (size_t)36 * n_cams * n_cams;
-  // partial records | scalar partials | S | N | T1 | B | scalars
-  return cv_a256((size_t)CV_WG * nn * 8) + cv_a256((size_t)CV_WG * 4 * 8) + 4 * cv_a256(nn * 8) + cv_a256(64) + 1024;
+  return cov_layout(n_cams).total;
 }
 
 int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, const double* d_Rt, const double* d_pts,
@@ -543,13 +558,10 @@ int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, cons
                          int gauge, int ref_cam, int scale_cam, const double* h_gauge, int scale, void* d_ws, size_t ws_bytes,
                          double* d_cov_cams, double* d_cov_points, double* d_std_points, acino_sba_cov_info* info,
                          void* stream) {
-  ACINO_REQUIRE(prm && info, "params/info");
-  ACINO_REQUIRE(prm->n_cams >= 1 && prm->n_cams <= SBA_MAXC, "n_cams in 1..16");
-  ACINO_REQUIRE(prm->n_points >= 1 && prm->n_obs >= 1 && prm->n_points < (int64_t)1 << 31 && prm->n_obs < (int64_t)1 << 31, "sizes");
-  ACINO_REQUIRE(prm->f_scale > 0, "f_scale");
-  ACINO_REQUIRE(prm->camera_model == 0 || prm->camera_model == 1, "camera_model: 0 fisheye, 1 pinhole");
+  if (int e = sba_check_problem(prm, info, d_intr && d_Rt && d_pts && d_uv && d_cam_idx && d_pt_start && d_pt_obs && d_ws, d_ws,
+                                ws_bytes, acino_sba_covariance_workspace_bytes, ACINO_ERR_WORKSPACE, "SBA covariance: "))
+    return e;
   ACINO_REQUIRE(scale == ACINO_SBA_SCALE_RESIDUAL || scale == ACINO_SBA_SCALE_UNIT, "scale: 0 residual, 1 unit");
-  ACINO_REQUIRE(d_intr && d_Rt && d_pts && d_uv && d_cam_idx && d_pt_start && d_pt_obs && d_ws, "null buffer");
   const int C = prm->n_cams, opt = prm->optimize_cameras ? 1 : 0, n = 6 * C, m = n - 7;
   if (opt) {
     ACINO_REQUIRE(C >= 2, "the covariance of the extrinsics needs at least two cameras");
@@ -561,18 +573,10 @@ int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, cons
                     "ref_cam and scale_cam: two different cameras");
     if (gauge == ACINO_SBA_GAUGE_CUSTOM) ACINO_REQUIRE(h_gauge, "custom gauge without a constraint matrix");
   }
-  if (((uintptr_t)d_ws & 255) != 0 || ws_bytes < acino_sba_covariance_workspace_bytes(C, prm->n_points, prm->n_obs)) {
-    set_error("SBA covariance: workspace too small or not 256-byte aligned");
-    return ACINO_ERR_WORKSPACE;
-  }
   hipStream_t s = (hipStream_t)stream;
   const size_t P = (size_t)prm->n_points, nn = (size_t)n * n;
+  const CovLayout L = cov_layout(C);
   char* w = (char*)d_ws;
-  auto take = [&](size_t bytes) {
-    char* p = w;
-    w += cv_a256(bytes);
-    return p;
-  };
   CovBuf B;
   B.C = C;
   B.P = (int)P;
@@ -586,13 +590,11 @@ int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, cons
   B.cam_idx = d_cam_idx;
   B.pt_start = d_pt_start;
   B.pt_obs = d_pt_obs;
-  B.Spart = (double*)take((size_t)CV_WG * nn * 8);
-  B.scalpart = (double*)take((size_t)CV_WG * 4 * 8);
-  B.S = (double*)take(nn * 8);
-  double* d_N = (double*)take(nn * 8);
-  double* d_T1 = (double*)take(nn * 8);
-  double* d_Bm = (double*)take(nn * 8);
-  B.scal = (double*)take(64);
+  B.Spart = (double*)(w + L.Spart);
+  B.scalpart = (double*)(w + L.scalpart);
+  B.S = (double*)(w + L.S);
+  double *d_N = (double*)(w + L.N), *d_T1 = (double*)(w + L.T1), *d_Bm = (double*)(w + L.Bm);
+  B.scal = (double*)(w + L.scal);
 
   info->status = 0;
   info->n_points_excluded = 0;
@@ -610,6 +612,10 @@ int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, cons
     return ACINO_ERR_NUMERIC;
   };
 
+  typedef void (*LinKernel)(CovBuf, int, int);
+  typedef void (*PointsKernel)(CovBuf, const double*, double, double*, double*, int, int);
+  const LinKernel lin_k[2] = {k_sbacov_lin<0>, k_sbacov_lin<1>};                 // [camera model]
+  const PointsKernel points_k[2] = {k_sbacov_points<0>, k_sbacov_points<1>};
   static PerDeviceOnce once;
   if (once.first()) {                                      // more than 64 KB of dynamic LDS: the largest any camera count asks for
     size_t lin = 0, pts = 0;
@@ -617,10 +623,10 @@ int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, cons
       lin = std::max(lin, cov_lin_lds(c));
       pts = std::max(pts, cov_pts_lds(c));
     }
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sbacov_lin<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lin));
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sbacov_lin<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lin));
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sbacov_points<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pts));
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sbacov_points<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pts));
+    for (int k = 0; k < 2; ++k) {
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(lin_k[k]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lin));
+      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(points_k[k]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pts));
+    }
   }
 
   // ---- (a) linearisation at zero damping
@@ -628,8 +634,7 @@ int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, cons
   const int n_batch = (int)((P + NB - 1) / NB);
   const int bpw = (n_batch + CV_WG - 1) / CV_WG, n_wg = (n_batch + bpw - 1) / bpw;
   ACINO_HIP_CHECK(hipMemsetAsync(B.scal, 0, 64, s));
-  if (prm->camera_model == 0) hipLaunchKernelGGL(k_sbacov_lin<0>, dim3(n_wg), dim3(CV_T), cov_lin_lds(C), s, B, bpw, n_batch);
-  else hipLaunchKernelGGL(k_sbacov_lin<1>, dim3(n_wg), dim3(CV_T), cov_lin_lds(C), s, B, bpw, n_batch);
+  hipLaunchKernelGGL(lin_k[prm->camera_model], dim3(n_wg), dim3(CV_T), cov_lin_lds(C), s, B, bpw, n_batch);
   ACINO_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sbacov_reduce, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, B, n_wg);
   ACINO_LAUNCH_CHECK();
@@ -703,10 +708,7 @@ int acino_sba_covariance(const acino_sba_params* prm, const double* d_intr, cons
   if (d_cov_points || d_std_points) {
     const double* covc = opt ? d_cov_cams : nullptr;
     const size_t lds = cov_pts_lds(opt ? C : 0);
-    if (prm->camera_model == 0)
-      hipLaunchKernelGGL(k_sbacov_points<0>, dim3(n_wg), dim3(CV_T), lds, s, B, covc, mult, d_cov_points, d_std_points, bpw, n_batch);
-    else
-      hipLaunchKernelGGL(k_sbacov_points<1>, dim3(n_wg), dim3(CV_T), lds, s, B, covc, mult, d_cov_points, d_std_points, bpw, n_batch);
+    hipLaunchKernelGGL(points_k[prm->camera_model], dim3(n_wg), dim3(CV_T), lds, s, B, covc, mult, d_cov_points, d_std_points, bpw, n_batch);
     ACINO_LAUNCH_CHECK();
   }
   return ACINO_OK;

@@ -19,6 +19,7 @@ Error bars: ``covariance(...)`` evaluates the covariance of the extrinsics and o
 the iterate they return.
 """
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -110,28 +111,43 @@ def _cov_options(n_cams, optimize_cameras, gauge="baseline", ref_cam=0, scale_ca
     return name, mat
 
 
-def _covariance_device(n_cams, model, f_scale, optimize_cameras, d_intr, d_Rt, d_pts, d_uv, d_cam, d_start, d_order,
-                       gauge="baseline", ref_cam=0, scale_cam=1, scale="residual", points=True, raise_numeric=True):
-    """acino_sba_covariance on device tensors (the iterate d_Rt[C, 12], d_pts[P, 3]); returns the dict of ``covariance``."""
-    name, mat = _cov_options(n_cams, optimize_cameras, gauge, ref_cam, scale_cam, scale)
-    dev = d_pts.device
-    n_points, n_obs, n = int(d_pts.shape[0]), int(d_uv.shape[0]), 6 * n_cams
-    prm = SbaParams(n_cams=n_cams, optimize_cameras=int(bool(optimize_cameras)), n_points=n_points, n_obs=n_obs,
-                    f_scale=float(f_scale), lam0=1e-3, ftol=0.0, gtol=0.0, max_iter=0,
-                    camera_model=calib.CAMERAS[model].code, precision=0)
-    nbytes = lib().acino_sba_covariance_workspace_bytes(n_cams, n_points, n_obs)
+def _workspace(nbytes, dev):
+    """``nbytes`` of device memory from a 256-byte boundary: (the tensor that owns them, the aligned address)."""
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-    empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+    return ws, C.c_void_p((ws.data_ptr() + 255) // 256 * 256)
+
+
+def _device_problem(intr, Rt, pts, uv, cam_idx, start, order, model, optimize_cameras, f_scale, lam0=1e-3, ftol=0.0, gtol=0.0,
+                    max_iter=0, precision="f64"):
+    """The problem as the library takes it: the seven arrays on the current device (host arrays are uploaded, device tensors
+    stay where they are), ``acino_sba_params`` and ``head``, the leading arguments of both library entries.  A solve updates
+    ``Rt[C, 12]`` and ``pts[P, 3]`` in place; the covariance reads them (and none of the solver's keywords)."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    p = SimpleNamespace(model=model, optimize_cameras=bool(optimize_cameras), f_scale=float(f_scale), n_cams=len(intr), dev=dev)
+    p.intr, p.Rt, p.pts, p.uv, p.cam, p.start, p.order = (torch.as_tensor(a, device=dev)
+                                                          for a in (intr, Rt, pts, uv, cam_idx, start, order))
+    p.n_points, p.n_obs = int(p.pts.shape[0]), int(p.uv.shape[0])
+    p.prm = SbaParams(n_cams=p.n_cams, optimize_cameras=int(p.optimize_cameras), n_points=p.n_points, n_obs=p.n_obs,
+                      f_scale=p.f_scale, lam0=float(lam0), ftol=float(ftol), gtol=float(gtol), max_iter=int(max_iter),
+                      camera_model=calib.CAMERAS[model].code, precision=PRECISIONS[precision])
+    p.head = (C.byref(p.prm), ptr(p.intr), ptr(p.Rt), ptr(p.pts), ptr(p.uv), ptr(p.cam), ptr(p.start), ptr(p.order))
+    return p
+
+
+def _covariance_device(p, gauge="baseline", ref_cam=0, scale_cam=1, scale="residual", points=True, raise_numeric=True):
+    """acino_sba_covariance at the iterate of a device problem; returns the dict of ``covariance``."""
+    n_cams, optimize_cameras, n_points, n = p.n_cams, p.optimize_cameras, p.n_points, 6 * p.n_cams
+    name, mat = _cov_options(n_cams, optimize_cameras, gauge, ref_cam, scale_cam, scale)
+    nbytes = lib().acino_sba_covariance_workspace_bytes(n_cams, n_points, p.n_obs)
+    _ws, ws_ptr = _workspace(nbytes, p.dev)
+    empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=p.dev)   # noqa: E731
     cov_cams = empty(n, n) if optimize_cameras else None
     cov_pts = empty(n_points, 6) if points else None
     std_pts = empty(n_points) if points else None
     info = SbaCovInfo()
-    rc = lib().acino_sba_covariance(C.byref(prm), ptr(d_intr), ptr(d_Rt), ptr(d_pts), ptr(d_uv), ptr(d_cam), ptr(d_start),
-                                    ptr(d_order), GAUGES[name], int(ref_cam), int(scale_cam),
+    rc = lib().acino_sba_covariance(*p.head, GAUGES[name], int(ref_cam), int(scale_cam),
                                     mat.ctypes.data_as(C.c_void_p) if mat is not None else C.c_void_p(0), SCALES[scale],
-                                    C.c_void_p(ws_ptr), nbytes, ptr(cov_cams), ptr(cov_pts), ptr(std_pts), C.byref(info),
-                                    stream_ptr())
+                                    ws_ptr, nbytes, ptr(cov_cams), ptr(cov_pts), ptr(std_pts), C.byref(info), stream_ptr())
     if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: the status word and NaN outputs are set)
         check(rc)
     torch.cuda.current_stream().synchronize()
@@ -141,7 +157,7 @@ def _covariance_device(n_cams, model, f_scale, optimize_cameras, d_intr, d_Rt, d
                gauge=name if optimize_cameras else None, scale=scale, status_name=info.as_dict()["status_name"])
     if optimize_cameras:
         cc = cov_cams.cpu().numpy()
-        Rt = d_Rt.cpu().numpy()
+        Rt = p.Rt.cpu().numpy()
         blocks = np.stack([cc[6 * c:6 * c + 6, 6 * c:6 * c + 6] for c in range(n_cams)])
         # camera centre c = -R^T t: dc = -R^T [t]x dw - R^T dt
         jac = np.zeros((n_cams, 3, 6))
@@ -214,86 +230,76 @@ def covariance(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_
     trace, m), sigma2, dof, n_points_excluded, gauge, scale, status_name.  A singular problem (a camera no point sees, too few
     points, constraints that do not fix the gauge) raises RuntimeError, or with ``raise_numeric=False`` returns NaN arrays and
     status_name "numeric"."""
-    n_cams = len(k_arr)
-    _cov_options(n_cams, optimize_cameras, gauge, ref_cam, scale_cam, scale)
+    _cov_options(len(k_arr), optimize_cameras, gauge, ref_cam, scale_cam, scale)
     model = calib.camera_model_of(None, project_func, by_name=True)
+    p = _problem(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr, optimize_cameras, f_scale,
+                 model)
+    return _covariance_device(p, gauge, ref_cam, scale_cam, scale, points, raise_numeric)
+
+
+def _problem(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr, optimize_cameras, f_scale,
+             model, camera_range=True, duplicates=False, **solver_kw):
+    """The device problem of the list-based entries: the arrays normalised, one entry per observation, the optional host checks,
+    the observations grouped by point (CSR), the camera tables; everything that can be refused is refused before the device
+    is asked for."""
+    n_cams = len(k_arr)
     pts0 = np.ascontiguousarray(np.asarray(points_3d, dtype=np.float64).reshape(-1, 3))
     uv = np.ascontiguousarray(np.asarray(points_2d, dtype=np.float64).reshape(-1, 2))
     cam_idx = np.ascontiguousarray(np.asarray(camera_indices, dtype=np.int32).reshape(-1))
-    n_points, n_obs = pts0.shape[0], uv.shape[0]
+    n_obs = uv.shape[0]
     if cam_idx.size != n_obs or len(point_3d_indices) != n_obs:
         raise ValueError("points_2d, point_3d_indices and camera_indices must have one entry per observation")
-    if n_obs and (cam_idx.min() < 0 or cam_idx.max() >= n_cams):
+    if camera_range and n_obs and (cam_idx.min() < 0 or cam_idx.max() >= n_cams):
         raise ValueError("camera_indices out of range")
-    start, order = _csr_by_point(point_3d_indices, n_points)
+    if duplicates and n_obs:
+        # one GPU lane per (point, camera) slot (csrc/sba.hip): one observation per pair
+        key = np.asarray(point_3d_indices, dtype=np.int64).reshape(-1) * n_cams + cam_idx
+        if np.unique(key).size != key.size:
+            raise ValueError("a point is observed twice by the same camera: merge the duplicate observations first")
+    start, order = _csr_by_point(point_3d_indices, pts0.shape[0])
     intr, Rt = _camera_tables(k_arr, d_arr, r_arr, t_arr, model, bool(optimize_cameras))
     _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    d = lambda a: torch.as_tensor(a, device=dev)   # noqa: E731
-    return _covariance_device(n_cams, model, f_scale, optimize_cameras, d(intr), d(Rt), d(pts0), d(uv), d(cam_idx), d(start),
-                              d(order), gauge, ref_cam, scale_cam, scale, points, raise_numeric)
+    return _device_problem(intr, Rt, pts0, uv, cam_idx, start, order, model, optimize_cameras, f_scale, **solver_kw)
+
+
+def _run_solve(p, sharded=False, group=None):
+    """acino_sba_solve_sharded on a device problem, in place (``acino_sba_solve`` is this call with a null callback): the
+    residuals before and after [M, 2] and the reduction hook (None unless ``sharded``); sets ``last_info``."""
+    global last_info
+    nbytes = lib().acino_sba_workspace_bytes(p.n_cams, p.n_points, p.n_obs)
+    ws, ws_ptr = _workspace(nbytes, p.dev)
+    res_b = torch.empty((p.n_obs, 2), dtype=torch.float64, device=p.dev)
+    res_a = torch.empty((p.n_obs, 2), dtype=torch.float64, device=p.dev)
+    info = SbaInfo()
+    hook = ReduceHook(ws, group) if sharded else None
+    status = lib().acino_sba_solve_sharded(*p.head, ws_ptr, nbytes, ptr(res_b), ptr(res_a), C.byref(info),
+                                           hook.fn if hook else _lib.REDUCE_FN(0), None, stream_ptr())
+    if hook is not None and hook.error is not None:
+        raise hook.error
+    check(status)
+    torch.cuda.current_stream().synchronize()
+    last_info = info.as_dict()
+    return res_b, res_a, hook
 
 
 def _solve(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr, optimize_cameras,
            f_scale, max_iter, ftol, gtol, lam0=1e-3, model="fisheye", group=None, sharded=False, precision="f64", host_checks=True,
            cov_kw=None):
-    """``cov_kw``: the keywords of ``_covariance_device`` - the covariance at the returned iterate is appended to the result."""
-    global last_info
-    if cov_kw is not None:
-        _cov_options(len(k_arr), optimize_cameras, group=group, **cov_kw)
-    _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
+    """``cov_kw``: the keywords of ``_covariance_device`` - the covariance at the returned iterate is appended to the result.
+    ``host_checks=False`` leaves the camera-range and duplicate tests to the library, which makes them itself on the device -
+    the C ABI's own guard, exercised by the tests - and answers ACINO_ERR_INVALID_ARG = ValueError."""
     n_cams = len(k_arr)
-    pts0 = np.ascontiguousarray(np.asarray(points_3d, dtype=np.float64).reshape(-1, 3))
-    uv = np.ascontiguousarray(np.asarray(points_2d, dtype=np.float64).reshape(-1, 2))
-    cam_idx = np.ascontiguousarray(np.asarray(camera_indices, dtype=np.int32).reshape(-1))
-    n_points, n_obs = pts0.shape[0], uv.shape[0]
-    if cam_idx.size != n_obs or len(point_3d_indices) != n_obs:
-        raise ValueError("points_2d, point_3d_indices and camera_indices must have one entry per observation")
-    # (host_checks=False leaves both tests below to the library, which makes them itself on the device - the C ABI's own
-    #  guard, exercised by the tests - and answers ACINO_ERR_INVALID_ARG = ValueError)
-    if host_checks and n_obs and (cam_idx.min() < 0 or cam_idx.max() >= n_cams):
-        raise ValueError("camera_indices out of range")
-    if host_checks and n_obs:
-        # one GPU lane per (point, camera) slot (csrc/sba.hip): one observation per pair
-        key = np.asarray(point_3d_indices, dtype=np.int64).reshape(-1) * n_cams + cam_idx
-        if np.unique(key).size != key.size:
-            raise ValueError("a point is observed twice by the same camera: merge the duplicate observations first")
-    intr, Rt = _camera_tables(k_arr, d_arr, r_arr, t_arr, model, bool(optimize_cameras))
-    start, order = _csr_by_point(point_3d_indices, n_points)
-
-    prm = SbaParams(n_cams=n_cams, optimize_cameras=int(bool(optimize_cameras)), n_points=n_points, n_obs=n_obs,
-                    f_scale=float(f_scale), lam0=float(lam0), ftol=float(ftol), gtol=float(gtol), max_iter=int(max_iter),
-                    camera_model=calib.CAMERAS[model].code, precision=PRECISIONS[precision])
-    nbytes = lib().acino_sba_workspace_bytes(n_cams, n_points, n_obs)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-    d = lambda a: torch.as_tensor(a, device=dev)
-    d_intr, d_Rt, d_pts, d_uv = d(intr), d(Rt), d(pts0), d(uv)
-    d_cam, d_start, d_order = d(cam_idx), d(start), d(order)
-    res_b = torch.empty((n_obs, 2), dtype=torch.float64, device=dev)
-    res_a = torch.empty((n_obs, 2), dtype=torch.float64, device=dev)
-    info = SbaInfo()
-    if sharded:
-        hook = ReduceHook(ws, group)
-        status = lib().acino_sba_solve_sharded(C.byref(prm), ptr(d_intr), ptr(d_Rt), ptr(d_pts), ptr(d_uv), ptr(d_cam),
-                                               ptr(d_start), ptr(d_order), C.c_void_p(ws_ptr), nbytes, ptr(res_b),
-                                               ptr(res_a), C.byref(info), hook.fn, None, stream_ptr())
-        if hook.error is not None:
-            raise hook.error
-        check(status)
-    else:
-        check(lib().acino_sba_solve(C.byref(prm), ptr(d_intr), ptr(d_Rt), ptr(d_pts), ptr(d_uv), ptr(d_cam),
-                                    ptr(d_start), ptr(d_order), C.c_void_p(ws_ptr), nbytes, ptr(res_b), ptr(res_a),
-                                    C.byref(info), stream_ptr()))
-    torch.cuda.current_stream().synchronize()
-    last_info = info.as_dict()
-    Rt_o = d_Rt.cpu().numpy()
-    out = (d_pts.cpu().numpy(), Rt_o[:, :9].reshape(n_cams, 3, 3).copy(), Rt_o[:, 9:].reshape(n_cams, 3, 1).copy(),
+    if cov_kw is not None:
+        _cov_options(n_cams, optimize_cameras, group=group, **cov_kw)
+    p = _problem(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr, optimize_cameras, f_scale,
+                 model, camera_range=host_checks, duplicates=host_checks, lam0=lam0, ftol=ftol, gtol=gtol, max_iter=max_iter,
+                 precision=precision)
+    res_b, res_a, _hook = _run_solve(p, sharded, group)
+    Rt_o = p.Rt.cpu().numpy()
+    out = (p.pts.cpu().numpy(), Rt_o[:, :9].reshape(n_cams, 3, 3).copy(), Rt_o[:, 9:].reshape(n_cams, 3, 1).copy(),
            dict(before=res_b.cpu().numpy().ravel(), after=res_a.cpu().numpy().ravel()))
     if cov_kw is not None:
-        out += (_covariance_device(n_cams, model, f_scale, optimize_cameras, d_intr, d_Rt, d_pts, d_uv, d_cam, d_start,
-                                   d_order, **cov_kw),)
+        out += (_covariance_device(p, **cov_kw),)
     return out
 
 
@@ -461,71 +467,36 @@ def bundle_adjust_dense_points_and_extrinsics(det, points_3d, k_arr, d_arr, r_ar
     ``return_cov=True``: info["cov"] = the covariance dict of ``covariance`` at the returned iterate (fp64, the same f_scale),
     with cov_points / std_points scattered back to [N, L, 3, 3] / [N, L] (NaN where a point was not kept); together with
     ``group`` it is a ValueError before any device work."""
-    global last_info
     model = calib.camera_model_of(camera_model, precision=precision)
+    n_cams = len(k_arr)
     if return_cov:
-        _cov_options(len(k_arr), True, gauge, ref_cam, scale_cam, scale, group=group)
+        _cov_options(n_cams, True, gauge, ref_cam, scale_cam, scale, group=group)
+    intr, Rt = _camera_tables(k_arr, d_arr, r_arr, t_arr, model, True)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     det = calib._to_dev(det, dev)
     pts_all = calib._to_dev(points_3d, dev).to(torch.float64).contiguous().clone()
-    n_cams = len(k_arr)
     if det.dim() != 4 or det.shape[1] != n_cams or tuple(pts_all.shape) != (det.shape[0], det.shape[2], 3):
         raise ValueError("det must be [N, C, L, 3] and points_3d [N, L, 3] for the C cameras of the rig")
     keep, uv, cam_idx, pt_start, pt_obs = dense_observations(det, float(dlc_thresh), min_views)
-    n_points, n_obs = int(pt_start.numel() - 1), int(uv.shape[0])
-    if n_points < 1:
+    if pt_start.numel() < 2:
         raise ValueError("no point is seen by enough cameras")
-    intr = np.zeros((n_cams, 16))
-    Rt = np.zeros((n_cams, 12))
-    for c in range(n_cams):
-        k = np.asarray(k_arr[c], dtype=np.float64)
-        intr[c, :4] = [k[0, 0], k[1, 1], k[0, 2], k[1, 2]]
-        if model == "fisheye":
-            intr[c, 4:8] = np.asarray(d_arr[c], dtype=np.float64).reshape(-1)[:4]
-        else:                                     # (as _solve for the pinhole model)
-            dist = np.asarray(d_arr[c], dtype=np.float64).reshape(-1)
-            if dist.size not in (4, 5, 8, 12):
-                raise ValueError("pinhole distortion vector must have 4, 5, 8 or 12 entries (cv2.projectPoints)")
-            intr[c, 4:4 + dist.size] = dist
-        r = np.asarray(r_arr[c], dtype=np.float64)
-        u, _s, vt = np.linalg.svd(calib._rodrigues(r) if r.size == 3 else r)     # (as _solve: cv2.Rodrigues' SO(3) projection)
-        Rt[c, :9] = (u @ vt).reshape(-1)
-        Rt[c, 9:] = np.asarray(t_arr[c], dtype=np.float64).reshape(-1)
-    d_intr, d_Rt = torch.as_tensor(intr, device=dev), torch.as_tensor(Rt, device=dev)
-    d_pts = pts_all[keep].contiguous()
-    prm = SbaParams(n_cams=n_cams, optimize_cameras=1, n_points=n_points, n_obs=n_obs, f_scale=float(f_scale),
-                    lam0=float(lam0), ftol=float(ftol), gtol=float(gtol), max_iter=int(max_iter),
-                    camera_model=calib.CAMERAS[model].code, precision=PRECISIONS[precision])
-    nbytes = lib().acino_sba_workspace_bytes(n_cams, n_points, n_obs)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-    res_b = torch.empty((n_obs, 2), dtype=torch.float64, device=dev)
-    res_a = torch.empty((n_obs, 2), dtype=torch.float64, device=dev)
-    info = SbaInfo()
-    hook = ReduceHook(ws, group) if group is not None else None
-    status = lib().acino_sba_solve_sharded(C.byref(prm), ptr(d_intr), ptr(d_Rt), ptr(d_pts), ptr(uv), ptr(cam_idx),
-                                           ptr(pt_start), ptr(pt_obs), C.c_void_p(ws_ptr), nbytes, ptr(res_b), ptr(res_a),
-                                           C.byref(info), hook.fn if hook else _lib.REDUCE_FN(0), None, stream_ptr())
-    if hook is not None and hook.error is not None:
-        raise hook.error
-    check(status)
-    torch.cuda.current_stream().synchronize()
-    last_info = info.as_dict()
-    out = dict(last_info, n_points=n_points, n_obs=n_obs, precision=precision,
+    p = _device_problem(intr, Rt, pts_all[keep].contiguous(), uv, cam_idx, pt_start, pt_obs, model, True, f_scale, lam0=lam0,
+                        ftol=ftol, gtol=gtol, max_iter=max_iter, precision=precision)
+    res_b, res_a, hook = _run_solve(p, group is not None, group)
+    out = dict(last_info, n_points=p.n_points, n_obs=p.n_obs, precision=precision,
                rms_before=float(res_b.pow(2).mean().sqrt()), rms_after=float(res_a.pow(2).mean().sqrt()),
                reduce_calls=hook.calls if hook else 0, reduce_sizes=sorted(set(hook.sizes)) if hook else [])
     if return_cov:
-        cov = _covariance_device(n_cams, model, f_scale, True, d_intr, d_Rt, d_pts, uv, cam_idx, pt_start, pt_obs, gauge,
-                                 ref_cam, scale_cam, scale)
+        cov = _covariance_device(p, gauge, ref_cam, scale_cam, scale)
         keep_h = keep.cpu().numpy()
         for key, tail in (("cov_points", (3, 3)), ("std_points", ())):
             full = np.full(keep_h.shape + tail, np.nan)
             full[keep_h] = cov[key]
             cov[key] = full
         out["cov"] = cov
-    pts_all[keep] = d_pts
-    Rt_o = d_Rt.cpu().numpy()
+    pts_all[keep] = p.pts
+    Rt_o = p.Rt.cpu().numpy()
     return pts_all, Rt_o[:, :9].reshape(n_cams, 3, 3).copy(), Rt_o[:, 9:].reshape(n_cams, 3, 1).copy(), out
 
 

@@ -241,22 +241,23 @@ def test_first_lm_step_equals_a_dense_numpy_step(gsba, model):
     assert np.abs(pts - (X0 + dp.reshape(P, 3))).max() < 1e-6
 
 
-@pytest.mark.parametrize("n_cams", [2, 4, 5, 6, 7])
+@pytest.mark.parametrize("n_cams", [2, 4, 5, 6, 7, 8, 9])
 def test_first_lm_step_with_ragged_visibility_for_every_camera_count(gsba, n_cams):
     """The fused kernels deal 64 / C points to a wave and feed the matrix cores in chunks of five points: every camera count
-    of the fused path (two tile rows up to five cameras, three from six on; a short last chunk for 4, 5 and 7 cameras), a
-    point count that fills neither the last batch nor the last wave, and points that some cameras do not see - one LM step
-    against the dense numpy step built from central differences, as above."""
+    of the fused path (2 to 7 cameras: two tile rows up to five cameras, three from six on; a short last chunk for 4, 5 and 7
+    cameras), a point count that fills neither the last batch nor the last wave, and points that some cameras do not see - one
+    LM step against the dense numpy step built from central differences, as above.  8 and 9 cameras are the TABLE path (one
+    thread per point, the coupling table, k_sba_schur and k_sba_backsub): the same step through the same controller."""
     sba, calib = gsba
     from acinoset_amd import synth
     rng = np.random.default_rng(100 + n_cams)
     K6, D6, R6, t6 = synth.make_rig()
     C, P, fs, lam = n_cams, 37, 1.0, 1e-3
-    sel = np.arange(C) % 6                                  # (a seventh camera: a copy of the first one, moved)
+    sel = np.arange(C) % 6                                  # (from the seventh camera on: copies of cameras 0, 1, 2, moved)
     K, D, R, t = K6[sel], D6[sel], R6[sel].copy(), t6[sel].reshape(C, 3, 1).copy()
-    if C == 7:
-        R[6] = ocam.rodrigues(np.array([0.02, -0.05, 0.03])) @ R[6]
-        t[6] = t[6] + np.array([[0.3], [-0.2], [0.1]])
+    for c in range(6, C):
+        R[c] = ocam.rodrigues(np.array([0.02, -0.05, 0.03])) @ R[c]
+        t[c] = t[c] + np.array([[0.3], [-0.2], [0.1]])
     ofun, proj = ocam.project_points_fisheye, calib.project_points_fisheye
     X = np.array([2.0, 6.5, 0.7]) + rng.normal(0, 0.6, (P, 3))
     pi, ci = [], []
@@ -298,6 +299,61 @@ def test_first_lm_step_with_ragged_visibility_for_every_camera_count(gsba, n_cam
     if c1 < c0:
         assert abs(info["cost_final"] - c1) < 1e-6 * c1, (info, c0, c1)
         assert np.abs(pts - Xn).max() < 1e-6 and np.abs(rm - Rn).max() < 1e-6 and np.abs(tt - tn).max() < 1e-6
+
+
+@pytest.mark.parametrize("n_cams", [6, 8])
+def test_lm_controller_exits_on_both_paths(gsba, n_cams):
+    """The one Levenberg-Marquardt controller behind the fused path (6 cameras) and the table path (8 cameras), through its
+    exits: max_iter = 0 (evaluation only), gtol (known after the iteration's kernels on the fused path, before the step on the
+    table path - either way before anything moves), ftol (at the first accepted step), and a points-only solve.  12 points seen
+    by every camera, 0.5 px of noise, points and poses started off the truth."""
+    sba, calib = gsba
+    from acinoset_amd import synth
+    rng = np.random.default_rng(41)
+    K6, D6, R6, t6 = synth.make_rig()
+    idx = np.arange(n_cams) % 6
+    K, D, R = K6[idx], D6[idx], R6[idx]
+    t = t6.reshape(6, 3, 1)[idx] + rng.normal(0, 0.05, (n_cams, 3, 1)) * (np.arange(n_cams) >= 6)[:, None, None]
+    X = np.array([2.0, 6.5, 0.7]) + rng.normal(0, 0.4, (12, 3))
+    pi, ci = np.repeat(np.arange(12), n_cams), np.tile(np.arange(n_cams), 12)
+    uv = np.stack([ocam.project_points_fisheye(X[p:p + 1], K[c], D[c], R[c], t[c])[0] for p, c in zip(pi, ci)])
+    uv += rng.normal(0, 0.5, uv.shape)
+    X0 = X + rng.normal(0, 0.02, X.shape)
+    R0 = np.array([ocam.rodrigues(rng.normal(0, 0.005, 3)) @ R[c] for c in range(n_cams)])
+    t0 = t + rng.normal(0, 0.01, t.shape)
+
+    def solve(**kw):
+        out = sba.bundle_adjust_points_and_extrinsics(uv, X0, pi, ci, K, D, R0, t0, **kw)
+        return out, dict(sba.last_info)
+
+    def unmoved(out):
+        return np.array_equal(out[0], X0) and np.abs(out[1] - R0).max() < 1e-12 and np.array_equal(out[2], t0)
+
+    c0 = 0.5 * np.log1p(osba.residuals(X0, R0, t0, K, D, pi, ci, uv) ** 2).sum()
+    out, ev = solve(max_iter=0)
+    assert ev["iterations"] == 0 and ev["accepted"] == 0 and ev["status_name"] == "max_iter"
+    assert abs(ev["cost_initial"] - c0) < 1e-9 * c0 and ev["cost_final"] == ev["cost_initial"]
+    assert ev["gnorm_inf"] > 0 and unmoved(out)
+    # gtol: the gradient norm of the start is already below it
+    out, info = solve(max_iter=5, ftol=0.0, gtol=2.0 * ev["gnorm_inf"])
+    assert info["status_name"] == "gtol" and info["iterations"] == 0 and info["accepted"] == 0, info
+    assert info["cost_final"] == info["cost_initial"] and abs(info["cost_initial"] - c0) < 1e-9 * c0 and unmoved(out)
+    # ftol = 1e30: every accepted step satisfies dF <= ftol |F|, so the solve ends at its first accepted step - found here as
+    # the first iteration limit at which a solve that cannot stop on ftol or gtol accepts one
+    for first in range(1, 40):
+        _o, ref = solve(max_iter=first, ftol=0.0, gtol=0.0)
+        assert ref["status_name"] == "max_iter" and ref["iterations"] == first
+        if ref["accepted"]:
+            break
+    assert ref["accepted"] == 1
+    out, info = solve(max_iter=40, ftol=1e30, gtol=0.0)
+    assert info["status_name"] == "ftol" and info["accepted"] == 1 and info["iterations"] == first, (info, first)
+    assert info["cost_final"] < info["cost_initial"] and abs(info["cost_initial"] - c0) < 1e-9 * c0 and not unmoved(out)
+    # points only: the cost falls, the cameras are untouched
+    out = sba._solve(uv, X0, pi, ci, K, D, R0, t0, False, 1.0, 10, 1e-15, 1e-10)
+    info = dict(sba.last_info)
+    assert info["cost_final"] < info["cost_initial"] and info["accepted"] >= 1 and not np.array_equal(out[0], X0)
+    assert np.array_equal(out[1], R0) and np.array_equal(out[2], t0)
 
 
 def test_pinhole_model_bundle_adjustment(gsba):
