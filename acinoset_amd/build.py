@@ -508,6 +508,83 @@ def model_samples(models, xs, n_samples=None, z=None, seed=0, positions=True, l1
         out.append(o)
     return out
 
+
+CALIB_KEYS = ("sens_cams", "cov_x_calib", "cov_pos_calib", "std_pos_calib")
+
+
+def model_calibration_sensitivity(models, xs, cov_cams=None, l1_eps=1e-2, pin_unobserved=False):
+    """The calibration's share of the skeleton solve's error bars at the iterates ``xs`` (one [N, P] array per model, the layout of
+    ``results["x"]``): acino_skel_fte_calibration_sensitivity, all models in ONE batched call.  With A the matrix of
+    ``model_covariance`` (Fisher blocks with w^2, smoothness prior, bound pins; ``pin_unobserved`` as there),
+    ``sens_cams`` [N, P, 6C] = S = -A^-1 G is the shift of the minimiser of the expected (Fisher) quadratic model per unit change
+    of c = [dw_0, dt_0, ..., dw_C-1, dt_C-1] with R_c <- exp([dw]x) R_c, t_c <- t_c + dt - the order and units of
+    ``sba.covariance`` and ``calib.extrinsic_cov``.  It is consistent with the A^-1 the covariance reports (weights w^2, neither
+    the residuals nor ``l1_eps`` enter G); it is not a derivative of the L1 / LM end point.  ``cov_cams``: a [6C, 6C] array or
+    tensor, or the dict ``sba.covariance`` returns (its ``"cov_cams"`` is used); a wrong shape, a non-finite entry or an
+    asymmetric matrix is a ValueError before any launch (``calib.cov_cams_matrix``, the validator of the cheetah path).
+    Returns one dict per model: ``sens_cams``, ``cov_x_calib`` [N, P, P] = S_n cov_cams S_n^T - both in the full-state layout,
+    zero rows (and columns) outside ``model.active`` and, exactly, at pinned variables -, ``cov_pos_calib`` [N, n_pose, 3, 3] =
+    G_l cov_x_calib G_l^T, ``std_pos_calib`` [N, n_pose] = sqrt(trace) in metres - the last three None without ``cov_cams`` - and
+    ``status`` (0, or 5: singular clip, NaN arrays; for ONE model a RuntimeError, as ``model_covariance``).  With
+    ``pin_unobserved`` every dict carries ``unobserved`` and a pose slot that depends on such a state has ``std_pos_calib`` = +inf
+    and NaN ``cov_pos_calib``.
+
+    The total is ``cov + cov_calib`` (``std_pos_total = sqrt(std_pos^2 + std_pos_calib^2)``) ONLY for a calibration obtained from
+    other data than the clips being solved; for extrinsics refined on the same clips the two errors are correlated and the sum
+    is not valid.  The calibration term is perfectly correlated across frames: smoothing does not average it out."""
+    return _calibration(models, xs, cov_cams, l1_eps, pin_unobserved)
+
+
+def _calibration(models, xs, cov_cams, l1_eps, pin_unobserved, raise_numeric=True):
+    """model_calibration_sensitivity.  ``raise_numeric=False``: a singular single clip is reported in its ``status`` like a clip
+    of a batch (solve_video's one-window case)."""
+    if len(models) == 0:
+        raise ValueError("no models")
+    Cn = int(models[0].meas.shape[1])
+    sigma = calib.cov_cams_matrix(cov_cams, Cn)
+    pin = bool(pin_unobserved)
+    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_calibration_workspace_bytes(C.byref(p), B, int(pin)), l1_eps=l1_eps)
+    m0, act, dev = models[0], io_["act"], io_["dev"]
+    B, N, P = len(models), m0.N, m0.P
+    Pa, Lp, W = len(act), len(m0.names), 6 * Cn
+    empty = lambda *shape: torch.empty((B, N) + shape, dtype=torch.float64, device=dev)   # noqa: E731
+    sig_d = None if sigma is None else torch.as_tensor(sigma, dtype=torch.float64, device=dev).contiguous()
+    sens = empty(Pa, W)
+    cov_x, cov_pos, std_pos = (None, None, None) if sigma is None else (empty(Pa, Pa), empty(Lp, 3, 3), empty(Lp))
+    status = (C.c_int32 * B)()
+    mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev) if pin else None
+    rc = lib().acino_skel_fte_calibration_sensitivity(*io_["head"], ptr(sig_d), ptr(sens), ptr(cov_x), ptr(cov_pos), ptr(std_pos), status,
+                                                      *io_["tail"], int(pin), ptr(mask))
+    if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
+        check(rc)
+    sh = sens.cpu().numpy()
+    out = []
+    for i in range(B):
+        full = np.zeros((N, P, W))
+        full[:, act] = sh[i]
+        out.append(dict(sens_cams=full, cov_x_calib=None, cov_pos_calib=None, std_pos_calib=None, status=int(status[i])))
+    if sigma is not None:
+        ch, ph, th = cov_x.cpu().numpy(), cov_pos.cpu().numpy(), std_pos.cpu().numpy()
+        for i, o in enumerate(out):
+            full = np.zeros((N, P, P))
+            full[:, act[:, None], act[None, :]] = ch[i]
+            o.update(cov_x_calib=full, cov_pos_calib=ph[i], std_pos_calib=th[i])
+    if pin:
+        for o, un in zip(out, _unobserved_lists(mask, act)):
+            o["unobserved"] = un
+    return out
+
+
+def _attach_calibration(out, models, xs, cov_cams, l1_eps, pin_unobserved, with_total):
+    """The four CALIB_KEYS of ``model_calibration_sensitivity`` into every ``results`` of ``out``, and ``std_pos_total`` beside a
+    ``std_pos`` that is already there (``with_total``)."""
+    _attach(out, model_calibration_sensitivity(models, xs, cov_cams, l1_eps=l1_eps, pin_unobserved=pin_unobserved),
+            CALIB_KEYS + ("unobserved",))
+    if with_total:
+        for res, _info in out:
+            res["std_pos_total"] = np.sqrt(res["std_pos"] ** 2 + res["std_pos_calib"] ** 2)
+
+
 REPROJ_KEYS = ("uv", "cov_uv", "std_uv", "res", "mahal2", "flags")
 
 
@@ -618,7 +695,7 @@ def detection_report(reproj, gate=None):
 
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
                  return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
-                 return_rate_cov=False):
+                 return_rate_cov=False, cov_cams=None):
     """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
@@ -636,7 +713,14 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     ``unobserved``.  ``pos_samples`` of a pose that depends on an unobserved state show no spread from it.
     ``return_rate_cov``: the six arrays of ``model_covariance(rates=True)`` (``cov_dx``, ``cov_ddx``, ``std_dx``, ``std_ddx``,
     ``cov_vel``, ``std_vel`` - the bars of the returned ``dx`` / ``ddx`` and of the pose velocities) join every ``results``; with
-    ``return_cov`` both come from one call and one factorisation."""
+    ``return_cov`` both come from one call and one factorisation.
+    ``cov_cams`` (a [6C, 6C] covariance of the extrinsics, or the dict of ``sba.covariance``; a malformed one is a ValueError
+    before the solve): ``sens_cams``, ``cov_x_calib``, ``cov_pos_calib`` and ``std_pos_calib`` of
+    ``model_calibration_sensitivity`` at the returned ``x`` join every ``results`` (one more batched call), and with
+    ``return_cov`` also ``std_pos_total`` = sqrt(std_pos^2 + std_pos_calib^2) - valid only for a calibration that came from other
+    data than these clips.  Without ``cov_cams`` the keys are what they were."""
+    if len(models) and cov_cams is not None:
+        calib.cov_cams_matrix(cov_cams, int(models[0].meas.shape[1]))      # (a malformed matrix fails before the solve, not after)
     xs = [np.array(m.init_x if x0 is None or x0[i] is None else x0[i], dtype=np.float64, copy=True) for i, m in enumerate(models)]
     io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_workspace_bytes_batch(C.byref(p), B), start=True, max_iter=max_iter,
                        lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol, l1_eps=l1_eps, lam_max=lam_max)
@@ -664,12 +748,14 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     if return_reprojection:
         _attach(out, model_reprojection(models, xs_out, cov=bool(return_cov),
                                         cov_pos=[r["cov_pos"] for r, _i in out] if return_cov else None, l1_eps=l1_eps), REPROJ_KEYS)
+    if cov_cams is not None:
+        _attach_calibration(out, models, xs_out, cov_cams, l1_eps, pin_unobserved, with_total=bool(return_cov))
     return out
 
 
 def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
-                return_rate_cov=False):
+                return_rate_cov=False, cov_cams=None):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
@@ -677,11 +763,13 @@ def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10,
     join ``results``; ``n_samples`` > 0: ``x_samples`` / ``pos_samples`` (``model_samples`` with ``seed=sample_seed``) do;
     ``return_reprojection``: the six arrays of ``model_reprojection`` do (``cov_uv`` / ``std_uv`` None without ``return_cov``).
     ``pin_unobserved``: as ``solve_models`` (only together with ``return_cov`` or ``n_samples``; ``results["unobserved"]``).
-    ``return_rate_cov``: the bars of ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``) join ``results``."""
+    ``return_rate_cov``: the bars of ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``) join ``results``.
+    ``cov_cams``: the calibration's share (``model_calibration_sensitivity``; ``std_pos_total`` with ``return_cov``), as
+    ``solve_models``."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
                         l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed,
                         return_reprojection=return_reprojection, pin_unobserved=pin_unobserved,
-                        return_rate_cov=return_rate_cov)[0]
+                        return_rate_cov=return_rate_cov, cov_cams=cov_cams)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -768,7 +856,7 @@ def window_residual_px(model, info):
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
                 overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, pin_unobserved=False,
-                return_rate_cov=False, **kw):
+                return_rate_cov=False, cov_cams=None, **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -817,6 +905,12 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     same depth rule: the bars are those of the window's own differences, never of a difference across a seam); ``cov_status``,
     ``cov_singular_windows``, ``owner`` and ``cov_unobserved`` as with ``return_cov``.
 
+    ``cov_cams`` (as ``solve_models``; checked before the solve): ONE batched ``model_calibration_sensitivity`` call over all
+    windows at their final iterates; ``results`` gains ``sens_cams`` [frames, P, 6C], ``cov_x_calib`` [frames, P, P],
+    ``cov_pos_calib`` [frames, n_pose, 3, 3] and ``std_pos_calib`` [frames, n_pose], every frame from the window that supplied its
+    ``positions``, and with ``return_cov`` ``std_pos_total`` = sqrt(std_pos^2 + std_pos_calib^2).  A singular window gives NaN
+    for its frames, as with ``return_cov``.  It is NOT passed on to the windows' solves.
+
     There is no ``n_samples`` here: a stitched video is not one posterior (every window has its own, and draws of neighbouring
     windows are independent); call ``model_samples`` on the windows' models."""
     if "n_samples" in kw or "sample_seed" in kw:
@@ -826,6 +920,10 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
     cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
     build_kw["camera_model"] = cam_model
+    if cov_cams is not None:                                  # (a malformed matrix fails before the solve, not after)
+        if scene is None:
+            scene = io.load_scene(os.path.join(project_dir, "data", "4_cam_scene_static_sba.json"))[:4]
+        calib.cov_cams_matrix(cov_cams, len(scene[0]))
     if dlc_tables is None:
         paths = sorted(glob.glob(os.path.join(project_dir, "data", "*.h5")))
         dlc_tables = [io.read_dlc_table(p) for p in paths]
@@ -931,6 +1029,16 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
             results["window_std_pos"] = [cv["std_pos"] for cv in covs]
         if pin_unobserved:
             results["cov_unobserved"] = [cv["unobserved"] for cv in covs]
+    if cov_cams is not None:
+        cals = _calibration(models, [res["x"] for res, _info in solved], cov_cams, kw.get("l1_eps", 1e-2), pin_unobserved,
+                            raise_numeric=False)
+        for k in CALIB_KEYS:
+            results[k] = np.full((total,) + cals[0][k].shape[1:], np.nan)
+            for w_i, (st, cal) in enumerate(zip(starts, cals)):
+                mine = np.nonzero(owner == w_i)[0]
+                results[k][mine] = cal[k][mine - (st - f0)]
+        if return_cov:
+            results["std_pos_total"] = np.sqrt(results["std_pos"] ** 2 + results["std_pos_calib"] ** 2)
     if return_reprojection:
         local = np.arange(total) - (np.asarray(starts)[owner] - f0)          # every frame's row in its owner window
         lo_t, hi_t = bounds_table(skel_dict, total)
@@ -970,7 +1078,8 @@ def solve_optimisation(model, exe_path=None, project_dir=None, poses=None, **sol
     covariance arrays to the returned ``results``, ``n_samples=S`` (with ``sample_seed``) the posterior samples,
     ``return_reprojection=True`` the image-space report of ``model_reprojection``, ``return_rate_cov=True`` the error bars of
     ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``), ``pin_unobserved=True`` pins the unobserved
-    states in those (``results["unobserved"]``); the saved pickle keeps the reference's four entries."""
+    states in those (``results["unobserved"]``), ``cov_cams=Sigma`` adds the calibration's share of the bars
+    (``model_calibration_sensitivity``); the saved pickle keeps the reference's four entries."""
     results, info = solve_model(model, **solver_kw)
     model.x, model.info = results, info
     if project_dir is not None:

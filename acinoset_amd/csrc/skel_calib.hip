@@ -1,0 +1,465 @@
+// Sensitivity of a generic-skeleton FTE trajectory to the camera extrinsics (gfx950, fp64): S = -A^-1 G, and the "consider"
+// covariance S Sigma S^T it gives for a covariance Sigma of the extrinsics (acinoset_hip.h:
+// acino_skel_fte_calibration_sensitivity).  A, the bound pins, pin_unobserved and the status rules are those of skel_cov.hip;
+// the factor A = L L^T is skel_sample.hip's k_skel_factor.  Camera parameters c = [dw_0, dt_0, ..., dw_C-1, dt_C-1],
+// R_c <- exp([dw]x) R_c, t_c <- t_c + dt: the camera-frame point moves by dw x (R_c p) + dt, so with j the camera-frame
+// Jacobian row of a pixel component J_c = [ (R_c p) x j | j ].  The weight of a kept row is the Fisher weight w^2 (the
+// statement A makes), not the IRLS curvature.
+//   k_skel_cov_assemble[_pinhole], k_skel_cov_build   skel_cov.hip's (skel_cov_launch_build): band, pin mask and the link
+//                           operators opv of every frame, the unobserved states pinned when the caller asks
+//   k_skel_calib_rhs<PINHOLE>  one workgroup per frame of every clip.  Poses from opv (the link program, in program order), the
+//                           pose Jacobians G_l (skel_pose_jac_col, as k_skel_cov_pose) into LDS, per (camera, slot) the 3 x 6
+//                           block J_pi^T w^2 J_c with the assembly's dropped rows (w = 0, non-finite measurement,
+//                           |z_cam| < 1e-9), then -G_n[p, col] = -sum_l G_l[:, p] . block[:, col] in slot order, no atomics,
+//                           as column `col` of the right-hand side [B][6C][N][n_act] (the layout of the sampler's z, columns
+//                           in the place of samples); rows of pinned variables 0.
+//                           LDS: (n_ops 12 + n_pose 3 + n_pose 3 n_act + n_cams n_pose 18) doubles, at most 123 KB.
+//   k_skel_factor<PT>       skel_sample.hip's (skel_launch_factor)
+//   k_skel_fwdsub<PT>       y = L^-1 b, grid (panels of SKS_PANEL = 64 columns, clips), SKS_W = 4 waves, 16 columns per wave:
+//                           the mirror image of k_skel_sample_back.  It walks n = 0 .. N-1; per frame the four blocks L_nn,
+//                           L_n,n-1 .. L_n,n-3 (band[n-j][j]) go to LDS once for all four waves, then every wave on its columns
+//                               r = b_n - sum_{j=1..3} L_n,n-j y_n-j
+//                               y_kb = U_kk^T (r_kb - sum_{t < kb} L(kb, t) y_t),      kb = 0 .. NTP-1
+//                           every product an fp64 16 x 16 x 4 MFMA, the last three y blocks kept in accumulator registers as
+//                           the B operands of the next frames.  The A operand of a product is now a tile of L read ALONG its
+//                           rows (A[m][k] = L[m][k]), so the blocks go to LDS TRANSPOSED (entry (m, k) at SksShape::at(k, m))
+//                           and the diagonal tiles U_kk as they are: every read is then the sampler's, lanes li along a row of
+//                           LDS, with its rotation of the odd rows.  b is read and y written once each through the per-wave
+//                           staging tile (b masked by the pin mask and the padding rows on the way in).
+//                           LDS: SksShape<PT>::lds = 4 PT^2 + SKS_W * 16 * ST doubles: 50 / 99 KB at PT = 32 / 48 and the
+//                           whole 160 KB at PT = 64.
+//   k_skel_sample_back<PT, false>  skel_sample.hip's, without the "+ x" (skel_launch_back_columns): L^-T y
+//   k_skel_calib_combine    one workgroup per frame: S_n [n_act][6C] out, T = S_n Sigma (Sigma is only PSD - a held camera has
+//                           zero rows - and is multiplied, never factored), cov_x_cal = T S_n^T on one triangle and mirrored,
+//                           then per pose slot (one wave each) G_l cov_x_cal G_l^T on its upper triangle, mirrored, and
+//                           sqrt(trace); with pin_unobserved a slot that depends on an unobserved state gets +inf / NaN
+//                           (k_skel_cov_pose's rule).  A singular clip: NaN in every output.
+//                           LDS: (2 n_act 6C + n_act (n_act + 1) + n_ops 12 + 4 (6 n_act + 9)) doubles: 147 KB at n_act = 64
+//                           with 16 cameras, so S_n and T both fit and Sigma is read from memory untiled.
+// n_cams <= ACINO_MAX_CAMS = 16 (96 columns).  No workgroup waits for another; vector stores only; the result of a clip is the
+// same bits whatever else shares the call (every kernel's arithmetic on a clip reads that clip's data alone).
+#include <cstddef>
+#include <cstdint>
+
+#include "skel_factor.hpp"
+
+namespace acino {
+
+static size_t skel_calib_rhs_lds(int n_ops, int n_pose, int n_cams, int P) {
+  return sizeof(double) * ((size_t)n_ops * 12 + (size_t)n_pose * 3 + (size_t)n_pose * 3 * P + (size_t)n_cams * n_pose * 18);
+}
+static size_t skel_calib_combine_lds(int n_ops, int W, int P) {
+  return sizeof(double) * ((size_t)2 * P * W + (size_t)P * (P + 1) + (size_t)n_ops * 12 + 4 * (6 * (size_t)P + 9));
+}
+
+template <bool PINHOLE>
+__global__ void __launch_bounds__(256)
+k_skel_calib_rhs(const SkelDev* __restrict__ dev, const double* __restrict__ x, const double* __restrict__ meas,
+                 const double* __restrict__ wgt, const double* __restrict__ opv_all, const unsigned char* __restrict__ fxm,
+                 double* __restrict__ rhs) {
+  extern __shared__ __attribute__((aligned(16))) double skc_smem[];
+  const SkelDev& D = *dev;
+  const int tid = threadIdx.x, n = blockIdx.x;
+  const int P = D.n_act, PT = D.PT, C = D.n_cams, NPOSE = D.n_pose, NOPS = D.n_ops, N = D.n_frames, W = 6 * C;
+  double* opv = skc_smem;                                    // [n_ops][4][3]
+  double* pos = opv + NOPS * 12;                             // [n_pose][3]
+  double* G = pos + NPOSE * 3;                               // [(l * 3 + i) * P + p]
+  double* Mb = G + (size_t)NPOSE * 3 * P;                    // [(c * n_pose + l) * 18 + i * 6 + j]
+  for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
+  __syncthreads();
+  if (tid < 3) {                                             // poses, coordinate by coordinate, in program order
+    const double root = x[(size_t)n * P + tid];
+    for (int s = 0; s < NPOSE; ++s) pos[s * 3 + tid] = root;
+    for (int k = 0; k < NOPS; ++k) pos[D.op[k].child * 3 + tid] = pos[D.op[k].parent * 3 + tid] + opv[(k * 4) * 3 + tid];
+  }
+  for (int e = tid; e < NPOSE * P; e += 256) {
+    const int l = e / P, p = e - l * P;
+    double gc[3];
+    skel_pose_jac_col(D, opv, l, p, gc);
+    G[(l * 3) * P + p] = gc[0];
+    G[(l * 3 + 1) * P + p] = gc[1];
+    G[(l * 3 + 2) * P + p] = gc[2];
+  }
+  __syncthreads();
+  for (int task = tid; task < C * NPOSE; task += 256) {
+    const int c = task / NPOSE, l = task - c * NPOSE;
+    const double px = pos[l * 3], py = pos[l * 3 + 1], pz = pos[l * 3 + 2];
+    const size_t e = ((size_t)n * C + c) * NPOSE + l;
+    const double um = meas[2 * e], vm = meas[2 * e + 1];
+    double w = wgt[e];
+    if (!(m_finite(um) && m_finite(vm))) w = 0.0;
+    const double* Rc = PINHOLE ? D.pins[c].R : D.cams[c].R;
+    const double* tc = PINHOLE ? D.pins[c].t : D.cams[c].t;
+    const double q0 = Rc[0] * px + Rc[1] * py + Rc[2] * pz;              // R_c p
+    const double q1 = Rc[3] * px + Rc[4] * py + Rc[5] * pz;
+    const double q2 = Rc[6] * px + Rc[7] * py + Rc[8] * pz;
+    const double xc = q0 + tc[0], yc = q1 + tc[1], zc = q2 + tc[2];
+    if (fabs(zc) < 1e-9) w = 0.0;
+    double* M = Mb + (size_t)task * 18;
+    if (w == 0.0) {
+#pragma unroll
+      for (int k = 0; k < 18; ++k) M[k] = 0.0;
+      continue;
+    }
+    double jc[2][3];
+    if (PINHOLE) {
+      double uv[2];
+      pinhole_project<true>(D.pins[c], xc, yc, zc, uv, jc);
+    } else {
+      FisheyeNlp fp;
+      double u, v;
+      fisheye_nlp_uv(D.cams[c], xc, yc, zc, fp, u, v);
+      fisheye_nlp_jac(D.cams[c], fp, jc[0], jc[1]);
+    }
+    double ju[3], jv[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      ju[j] = jc[0][0] * Rc[j] + jc[0][1] * Rc[3 + j] + jc[0][2] * Rc[6 + j];
+      jv[j] = jc[1][0] * Rc[j] + jc[1][1] * Rc[3 + j] + jc[1][2] * Rc[6 + j];
+    }
+    const double cu[6] = {q1 * jc[0][2] - q2 * jc[0][1], q2 * jc[0][0] - q0 * jc[0][2], q0 * jc[0][1] - q1 * jc[0][0],
+                          jc[0][0], jc[0][1], jc[0][2]};
+    const double cv[6] = {q1 * jc[1][2] - q2 * jc[1][1], q2 * jc[1][0] - q0 * jc[1][2], q0 * jc[1][1] - q1 * jc[1][0],
+                          jc[1][0], jc[1][1], jc[1][2]};
+    const double w2 = w * w;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) M[i * 6 + j] = w2 * (ju[i] * cu[j] + jv[i] * cv[j]);
+  }
+  __syncthreads();
+  const int b = n / N, nl = n - b * N;
+  for (int task = tid; task < W * P; task += 256) {
+    const int col = task / P, p = task - col * P;
+    const int c = col / 6, j = col - 6 * c;
+    double acc = 0.0;
+    if (!fxm[(size_t)n * PT + p]) {
+      const double* M = Mb + (size_t)c * NPOSE * 18 + j;
+      for (int l = 0; l < NPOSE; ++l) {
+        acc += G[(l * 3) * P + p] * M[l * 18];
+        acc += G[(l * 3 + 1) * P + p] * M[l * 18 + 6];
+        acc += G[(l * 3 + 2) * P + p] * M[l * 18 + 12];
+      }
+      acc = -acc;
+    }
+    rhs[(((size_t)b * W + col) * N + nl) * P + p] = acc;
+  }
+}
+
+// y = L^-1 b on the factor of k_skel_factor<PT>: see the head of the file.  b_all, y_all: [n_clips][S][N][n_act]
+template <int PT>
+__global__ void __launch_bounds__(SKS_T)
+k_skel_fwdsub(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, const double* __restrict__ band_all,
+              const unsigned char* __restrict__ fxm_all, const double* __restrict__ b_all, double* __restrict__ y_all,
+              long long S) {
+  using Sh = SksShape<PT>;
+  constexpr int NTP = PT / 16, BB = PT * PT;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int N = dev->n_frames, P = dev->n_act, b = blockIdx.y;
+  if (clip[b].status != 0) return;                                         // singular clip (uniform): the combine writes NaN
+  const long long s0 = (long long)blockIdx.x * SKS_PANEL + wave * 16;      // this wave's first column
+  const size_t fr0 = (size_t)b * N;
+  const double* const band = band_all + fr0 * 4 * BB;
+  const unsigned char* const fxm = fxm_all + fr0 * PT;
+  const size_t row0 = ((size_t)b * (size_t)S + (size_t)s0) * N * P;        // (b, s0, 0, 0) of b and y
+  const size_t srow = (size_t)N * P;                                       // from one column to the next
+  double* const Lb = reinterpret_cast<double*>(smem_raw);                  // [4][PT][PT], Sh::at, transposed
+  double* const stage = Lb + 4 * BB + wave * 16 * Sh::ST;                   // [16][ST], Sh::st: this wave's
+  const bool busy = s0 < S;
+  d4 d[3][NTP];                                                            // y_n-1, y_n-2, y_n-3: tiles of 16 rows
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+#pragma unroll
+    for (int t = 0; t < NTP; ++t) d[j][t] = d4{0, 0, 0, 0};
+  for (int n = 0; n < N; ++n) {
+    __syncthreads();                                                       // the previous frame's blocks have been read
+    // 8 x 8 patches: a lane reads runs of 8 doubles and writes them down 8 rows of LDS
+    for (int e = tid; e < 4 * BB; e += SKS_T) {
+      const int j = e / BB, rem = e % BB, patch = rem >> 6, in = rem & 63;
+      if (n - j < 0) break;                                                // (e grows with j: nothing further to load)
+      const int m = (patch / (PT / 8)) * 8 + (in >> 3), k = (patch % (PT / 8)) * 8 + (in & 7);      // entry (m, k) of L_n,n-j
+      const double v = band[((size_t)(n - j) * 4 + j) * BB + m * PT + k];
+      const bool diag = j == 0 && (k >> 4) == (m >> 4);                     // U_kk stays as it is: its transpose is the operand
+      Lb[j * BB + (diag ? Sh::at(m, k) : Sh::at(k, m))] = v;
+    }
+    __syncthreads();
+    if (!busy) continue;
+    // ---- b_n of the wave's 16 columns -> staging (rows along p), masked; then r in the accumulator layout
+    for (int e = lane; e < 16 * PT; e += 64) {
+      const int c = e / PT, p = e % PT;
+      double v = 0.0;
+      if (s0 + c < S && p < P && !fxm[(size_t)n * PT + p]) v = b_all[row0 + c * srow + (size_t)n * P + p];
+      stage[Sh::st(c, p)] = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    d4 r[NTP];
+#pragma unroll
+    for (int kb = 0; kb < NTP; ++kb)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) r[kb][rr] = stage[Sh::st(li, kb * 16 + lk + 4 * rr)];
+    // ---- r -= L_n,n-j y_n-j
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+      if (n - j < 0) break;
+      const double* Lj = Lb + j * BB;
+#pragma unroll
+      for (int kb = 0; kb < NTP; ++kb)
+#pragma unroll
+        for (int t = 0; t < NTP; ++t) {
+          double av[4];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) av[s] = Lj[Sh::at(t * 16 + 4 * s + lk, kb * 16 + li)];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) r[kb] = mfma(-av[s], d[j - 1][t][s], r[kb]);
+        }
+    }
+    // ---- y_kb = U_kk^T (r_kb - sum_{t < kb} L(kb, t) y_t), first tile first
+    d4 dn[NTP];
+#pragma unroll
+    for (int kb = 0; kb < NTP; ++kb) {
+      d4 acc = r[kb];
+#pragma unroll
+      for (int t = 0; t < kb; ++t) {
+        double av[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) av[s] = Lb[Sh::at(t * 16 + 4 * s + lk, kb * 16 + li)];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = mfma(-av[s], dn[t][s], acc);
+      }
+      double uv[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) uv[s] = Lb[Sh::at(kb * 16 + 4 * s + lk, kb * 16 + li)];     // U_kk[k][li] = U_kk^T[li][k]
+      d4 o = {0, 0, 0, 0};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) o = mfma(uv[s], acc[s], o);
+      dn[kb] = o;
+    }
+    // ---- y_n -> memory through the staging tile
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int kb = 0; kb < NTP; ++kb)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) stage[Sh::st(li, kb * 16 + lk + 4 * rr)] = dn[kb][rr];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int e = lane; e < 16 * PT; e += 64) {
+      const int c = e / PT, p = e % PT;
+      if (s0 + c < S && p < P) y_all[row0 + c * srow + (size_t)n * P + p] = stage[Sh::st(c, p)];
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < NTP; ++t) {
+      d[2][t] = d[1][t];
+      d[1][t] = d[0][t];
+      d[0][t] = dn[t];
+    }
+  }
+}
+
+// sol: [n_clips][W][N][n_act] (the columns of -A^-1 G); sigma: [W][W] or NULL; unobs: NULL, or the clips' masks [n_clips][P]
+__global__ void __launch_bounds__(256)
+k_skel_calib_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, const double* __restrict__ sol,
+                     const double* __restrict__ sigma, const double* __restrict__ opv_all, const unsigned char* __restrict__ unobs,
+                     double* __restrict__ sens, double* __restrict__ cov_x, double* __restrict__ cov_pos,
+                     double* __restrict__ std_pos) {
+  extern __shared__ __attribute__((aligned(16))) double skc_smem[];
+  const SkelDev& D = *dev;
+  const int n = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, N = D.n_frames, W = 6 * D.n_cams, LDC = P + 1;
+  const int b = n / N, nl = n - b * N;
+  if (clip[b].status != 0) {
+    const double nan = __builtin_nan("");
+    for (int e = tid; e < P * W; e += 256)
+      if (sens) sens[(size_t)n * P * W + e] = nan;
+    for (int e = tid; e < P * P; e += 256)
+      if (cov_x) cov_x[(size_t)n * P * P + e] = nan;
+    for (int e = tid; e < NPOSE * 9; e += 256)
+      if (cov_pos) cov_pos[(size_t)n * NPOSE * 9 + e] = nan;
+    for (int e = tid; e < NPOSE; e += 256)
+      if (std_pos) std_pos[(size_t)n * NPOSE + e] = nan;
+    return;
+  }
+  double* Sm = skc_smem;                                     // S_n [P][W]
+  double* Tm = Sm + (size_t)P * W;                           // S_n Sigma [P][W]
+  double* Cx = Tm + (size_t)P * W;                           // cov_x_cal [P][P + 1]
+  double* opv = Cx + (size_t)P * LDC;                        // [n_ops][4][3]
+  double* Gw = opv + NOPS * 12 + wave * (6 * P + 9);         // this wave's G_l [3][P], G_l cov_x_cal [3][P], out [9]
+  double* Tw = Gw + 3 * P;
+  double* out9 = Tw + 3 * P;
+  for (int e = tid; e < P * W; e += 256) {
+    const int col = e / P, p = e - col * P;
+    Sm[p * W + col] = sol[(((size_t)b * W + col) * N + nl) * P + p];
+  }
+  __syncthreads();
+  if (sens)
+    for (int e = tid; e < P * W; e += 256) sens[(size_t)n * P * W + e] = Sm[e];
+  if (!sigma) return;
+  for (int e = tid; e < P * W; e += 256) {
+    const int p = e / W, j = e - p * W;
+    double acc = 0.0;
+    for (int i = 0; i < W; ++i) acc += Sm[p * W + i] * sigma[(size_t)i * W + j];
+    Tm[e] = acc;
+  }
+  __syncthreads();
+  for (int e = tid; e < P * P; e += 256) {
+    const int p = e / P, q = e - p * P;
+    if (p <= q) {
+      double acc = 0.0;
+      for (int j = 0; j < W; ++j) acc += Tm[p * W + j] * Sm[q * W + j];
+      Cx[p * LDC + q] = acc;
+      Cx[q * LDC + p] = acc;
+    }
+  }
+  __syncthreads();
+  if (cov_x)
+    for (int e = tid; e < P * P; e += 256) cov_x[(size_t)n * P * P + e] = Cx[(e / P) * LDC + e % P];
+  if (!cov_pos && !std_pos) return;
+  for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
+  __syncthreads();
+  for (int l0 = 0; l0 < NPOSE; l0 += 4) {                   // a wave is one pose slot; no workgroup barrier inside
+    const int l = l0 + wave;
+    if (l >= NPOSE) break;
+    bool dep = false;
+    if (lane < P) {
+      double gc[3];
+      skel_pose_jac_col(D, opv, l, lane, gc);
+      Gw[lane] = gc[0];
+      Gw[P + lane] = gc[1];
+      Gw[2 * P + lane] = gc[2];
+      if (unobs) dep = unobs[(size_t)b * P + lane] && (gc[0] != 0.0 || gc[1] != 0.0 || gc[2] != 0.0);
+    }
+    const bool undet = __any(dep ? 1 : 0) != 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < P) {
+      double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+      for (int q = 0; q < P; ++q) {
+        const double c = Cx[q * LDC + lane];
+        t0 += Gw[q] * c;
+        t1 += Gw[P + q] * c;
+        t2 += Gw[2 * P + q] * c;
+      }
+      Tw[lane] = t0;
+      Tw[P + lane] = t1;
+      Tw[2 * P + lane] = t2;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 6) {                                          // the upper triangle, mirrored
+      const int i = lane < 3 ? 0 : (lane < 5 ? 1 : 2), j = lane < 3 ? lane : (lane < 5 ? lane - 2 : 2);
+      double s = 0.0;
+      for (int q = 0; q < P; ++q) s += Tw[i * P + q] * Gw[j * P + q];
+      out9[3 * i + j] = s;
+      out9[3 * j + i] = s;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 9 && cov_pos) cov_pos[((size_t)n * NPOSE + l) * 9 + lane] = undet ? __builtin_nan("") : out9[lane];
+    if (lane == 0 && std_pos)
+      std_pos[(size_t)n * NPOSE + l] = undet ? __builtin_inf() : sqrt(fmax(out9[0] + out9[4] + out9[8], 0.0));
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+template <int PT>
+static int skel_fwdsub_launch(int B, long long S, const SkelDev* d_dev, const SkelClip* d_clip, const double* d_band,
+                              const unsigned char* d_fxm, const double* d_b, double* d_y, hipStream_t s) {
+  static PerDeviceOnce attr;
+  if (attr.first())
+    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_fwdsub<PT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024));
+  static_assert(SksShape<PT>::lds <= 160 * 1024, "LDS");
+  const long long panels = (S + SKS_PANEL - 1) / SKS_PANEL;
+  hipLaunchKernelGGL(k_skel_fwdsub<PT>, dim3((unsigned)panels, (unsigned)B), dim3(SKS_T), SksShape<PT>::lds, s, d_dev, d_clip, d_band,
+                     d_fxm, d_b, d_y, S);
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
+
+}  // namespace acino
+
+using namespace acino;
+
+static size_t skc_column_bytes(const acino_skel_fte_params* p, int n_clips) {
+  return skel_align256(sizeof(double) * (size_t)n_clips * 6 * p->n_cams * p->n_frames * p->n_active);
+}
+
+extern "C" {
+
+size_t acino_skel_fte_calibration_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved) {
+  const size_t cov = acino_skel_fte_covariance_pinned_workspace_bytes(p, n_clips, pin_unobserved);
+  if (cov == 0 || p->n_cams < 1 || p->n_cams > ACINO_MAX_CAMS) return 0;
+  return cov + 2 * skc_column_bytes(p, n_clips);
+}
+
+int acino_skel_fte_calibration_sensitivity(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                           const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                           const double* d_lo, const double* d_hi, const double* d_x, const double* d_cov_cams,
+                                           double* d_sens, double* d_cov_x_cal, double* d_cov_pos_cal, double* d_std_pos_cal,
+                                           int32_t* h_status, void* d_ws, size_t ws_bytes, void* stream, int pin_unobserved,
+                                           uint8_t* d_unobserved) {
+  int rc = skel_check_batch(p, n_clips, true, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws);
+  if (rc) return rc;
+  ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
+  ACINO_REQUIRE(d_sens || d_cov_x_cal || d_cov_pos_cal || d_std_pos_cal,
+                "at least one of d_sens, d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal");
+  ACINO_REQUIRE(d_cov_cams || !(d_cov_x_cal || d_cov_pos_cal || d_std_pos_cal), "a cov / std output needs d_cov_cams");
+  ACINO_REQUIRE(p->n_cams <= ACINO_MAX_CAMS, "n_cams <= 16 (96 columns)");
+  const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16, W = 6 * p->n_cams;
+  const size_t NT = (size_t)N * B;                           // frames of all clips
+  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
+  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
+  const size_t col_bytes = skc_column_bytes(p, B);
+  if ((rc = skel_check_workspace(d_ws, ws_bytes, lay.total + 2 * col_bytes, "acino_skel_fte_calibration_workspace_bytes",
+                                 ACINO_ERR_WORKSPACE)))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
+                                  d_unobserved)))
+    return rc;
+  char* base = (char*)d_ws;
+  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
+  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
+  unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
+  const unsigned char* d_unobs = pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr;
+  double* d_b = D(lay.total);                                // -G, then S: [B][W][N][P]
+  double* d_y = D(lay.total + col_bytes);                    // L^-1 (-G)
+  const size_t lds_rhs = skel_calib_rhs_lds(p->n_ops, p->n_pose, p->n_cams, P), lds_comb = skel_calib_combine_lds(p->n_ops, W, P);
+  static_assert(sizeof(double) * ((size_t)ACINO_SKEL_MAX_OPS * 12 + (ACINO_SKEL_MAX_OPS + 1) * 3 * (1 + SK_MAXP) + (SK_MAXROWS / 2) * 18) <=
+                        160 * 1024 &&
+                    sizeof(double) * ((size_t)2 * SK_MAXP * 6 * ACINO_MAX_CAMS + SK_MAXP * (SK_MAXP + 1) + ACINO_SKEL_MAX_OPS * 12 +
+                                      4 * (6 * SK_MAXP + 9)) <= 160 * 1024,
+                "LDS of k_skel_calib_rhs / k_skel_calib_combine at the limits");
+  static PerDeviceOnce attr;
+  if (attr.first()) {
+    for (int model = 0; model < 2; ++model)
+      ACINO_HIP_CHECK(hipFuncSetAttribute(
+          reinterpret_cast<const void*>(skel_camera_kernel(model, k_skel_calib_rhs<false>, k_skel_calib_rhs<true>)),
+          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_calib_combine), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024));
+  }
+  hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_calib_rhs<false>, k_skel_calib_rhs<true>), dim3((unsigned)NT), dim3(256),
+                     lds_rhs, s, d_dev, d_x, d_meas, d_w, D(lay.opv), d_fxm, d_b);
+  ACINO_LAUNCH_CHECK();
+  if ((rc = skel_launch_factor(PT, B, d_dev, d_clip, D(lay.band), D(lay.diag0), s))) return rc;
+  rc = skel_dispatch_pt(PT, [&](auto pt) {
+    return skel_fwdsub_launch<decltype(pt)::value>(B, W, d_dev, d_clip, D(lay.band), d_fxm, d_b, d_y, s);
+  });
+  if (rc) return rc;
+  if ((rc = skel_launch_back_columns(PT, B, W, d_dev, d_clip, D(lay.band), d_fxm, d_y, d_b, s))) return rc;
+  hipLaunchKernelGGL(k_skel_calib_combine, dim3((unsigned)NT), dim3(256), lds_comb, s, d_dev, d_clip, d_b, d_cov_cams, D(lay.opv),
+                     d_unobs, d_sens, d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal);
+  ACINO_LAUNCH_CHECK();
+  return skel_cov_read_status(d_clip, B, s, h_status);
+}
+
+}  // extern "C"

@@ -369,19 +369,8 @@ k_skel_cov_pose(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ cl
     const bool on = l < NPOSE;
     bool dep = false;
     if (on && lane < P) {
-      double gc[3] = {lane == 0 ? 1.0 : 0.0, lane == 1 ? 1.0 : 0.0, lane == 2 ? 1.0 : 0.0};
-      const unsigned long long path = D.pmask[l];
-      for (int k = 0; k < NOPS; ++k) {
-        if (!((path >> k) & 1ull)) continue;
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax)
-          if (D.amap[k][ax] == lane) {
-            const double* dv = opv + (k * 4 + 1 + ax) * 3;
-            gc[0] += dv[0];
-            gc[1] += dv[1];
-            gc[2] += dv[2];
-          }
-      }
+      double gc[3];
+      skel_pose_jac_col(D, opv, l, lane, gc);
       G[wave][0][lane] = gc[0];
       G[wave][1][lane] = gc[1];
       G[wave][2][lane] = gc[2];

@@ -1,6 +1,6 @@
 // What the generic-skeleton kernels share - skel_fte.hip (the solve), skel_cov.hip (covariance and observability at an iterate),
-// skel_sample.hip (joint samples) and skel_reproj.hip (the image-space report): the device-resident problem description, the
-// controller state of a clip, the bound-active rule, the link program's forward kinematics, the parameter checks and the
+// skel_sample.hip (joint samples), skel_calib.hip (the sensitivity to the extrinsics) and skel_reproj.hip (the image-space
+// report): the device-resident problem description, the controller state of a clip, the bound-active rule, the link program's forward kinematics, the parameter checks and the
 // host-side compilation of the link program into SkelDev.  The host layer on top of it (entry checks, upload, dispatch,
 // read-back) is skel_host.hpp.
 #pragma once
@@ -74,6 +74,26 @@ __device__ __forceinline__ void skel_pose_row(const SkelDev& D, const double* __
                                      : Rm[0][i] * o.off[0] + Rm[1][i] * o.off[1] + Rm[2][i] * o.off[2];
       out[o.child * 3 + i] = out[o.parent * 3 + i] + d;
     }
+  }
+}
+
+// column p of the pose Jacobian G_l (3 x n_act) of slot l: [I | d(M off)/d(angle) of the ops on the slot's path], from the link
+// operators opv[n_ops][4][3] the assembly leaves (k_skel_cov_pose, k_skel_calib_rhs, k_skel_calib_combine)
+__device__ __forceinline__ void skel_pose_jac_col(const SkelDev& D, const double* __restrict__ opv, int l, int p, double (&gc)[3]) {
+  gc[0] = p == 0 ? 1.0 : 0.0;
+  gc[1] = p == 1 ? 1.0 : 0.0;
+  gc[2] = p == 2 ? 1.0 : 0.0;
+  const unsigned long long path = D.pmask[l];
+  for (int k = 0; k < D.n_ops; ++k) {
+    if (!((path >> k) & 1ull)) continue;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+      if (D.amap[k][ax] == p) {
+        const double* dv = opv + (k * 4 + 1 + ax) * 3;
+        gc[0] += dv[0];
+        gc[1] += dv[1];
+        gc[2] += dv[2];
+      }
   }
 }
 

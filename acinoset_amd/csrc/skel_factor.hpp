@@ -1,6 +1,7 @@
-// What the two uses of the skeleton FTE's Fisher matrix share (skel_cov.hip: the selected inverse; skel_sample.hip: joint
-// posterior samples): the 16 x 16 tile product, the banded block Cholesky A = L L^T as a device function template, the
-// workspace layout and the launches that build the band at an iterate.
+// What the uses of the skeleton FTE's Fisher matrix share (skel_cov.hip: the selected inverse; skel_sample.hip: joint
+// posterior samples; skel_calib.hip: the sensitivity to the extrinsics): the 16 x 16 tile product, the banded block Cholesky
+// A = L L^T as a device function template, the shape of the triangular solves on it, the workspace layout and the launches
+// that build the band at an iterate.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -137,6 +138,22 @@ __device__ __forceinline__ void skel_band_factor(int N, double* __restrict__ ban
   }
 }
 
+// ---- the triangular solves on the factor, 64 right-hand-side columns per workgroup: k_skel_sample_back (skel_sample.hip,
+//      L^-T) and k_skel_fwdsub (skel_calib.hip, L^-1) share the shape of a workgroup and the LDS layout of the blocks
+constexpr int SKS_W = 4, SKS_T = 64 * SKS_W, SKS_PANEL = 16 * SKS_W;
+
+template <int PT>
+struct SksShape {
+  static constexpr bool ROT = PT % 32 == 0;        // L rows of 32 or 64 doubles: odd rows rotated by 16 columns
+  static constexpr bool SROT = PT == 64;           // staging rows: padded by 2 doubles, or (no room at PT = 64) rotated by 2 li
+  static constexpr int ST = SROT ? PT : PT + 2;
+  static constexpr size_t lds = sizeof(double) * ((size_t)4 * PT * PT + (size_t)SKS_W * 16 * ST);
+  // entry (k, m) of a block in LDS; m0 + li with m0 a multiple of 16 stays contiguous in li
+  __device__ static __forceinline__ int at(int k, int m) { return k * PT + (ROT ? ((m + 16 * (k & 1)) & (PT - 1)) : m); }
+  // entry (sample column c, state p) of a wave's staging tile
+  __device__ static __forceinline__ int st(int c, int p) { return c * ST + (SROT ? ((p + 2 * c) & (PT - 1)) : p); }
+};
+
 // ---- host: the workspace both entries use, and the launches up to the band --------------------------------------------
 struct SkelCovLayout {
   size_t dev, clip, H, g, hd, cost, opv, band, diag0, fxm, total;
@@ -157,6 +174,13 @@ int skel_cov_launch_build(const acino_skel_fte_params* p, int n_clips, int camer
 // The end of both entries: skel_read_status with the Fisher matrix's error text, and the clips' status words to h_status[n_clips]
 // (may be NULL: then a singular clip fails the call whatever the batch).
 int skel_cov_read_status(const SkelClip* d_clip, int n_clips, hipStream_t s, int32_t* h_status);
+// k_skel_factor<PT> on stream s (skel_sample.hip), one workgroup per clip: band <- the factor, a failed pivot -> status 5.
+int skel_launch_factor(int PT, int n_clips, const SkelDev* d_dev, SkelClip* d_clip, double* d_band, const double* d_diag0,
+                       hipStream_t s);
+// k_skel_sample_back<PT> without the "+ x" on stream s: d_out[b][c] = L_b^-T d_y[b][c] for the n_cols columns
+// [n_clips][n_cols][N][n_act] (the layout of the sampler's z, pinned rows masked to 0; NaN for a clip whose status is not 0).
+int skel_launch_back_columns(int PT, int n_clips, long long n_cols, const SkelDev* d_dev, const SkelClip* d_clip,
+                             const double* d_band, const unsigned char* d_fxm, const double* d_y, double* d_out, hipStream_t s);
 // dynamic LDS of k_skel_cov_rates (skel_cov_rates.hip): three blocks [P][P + 1]
 inline size_t skel_cov_rates_lds(int P) { return sizeof(double) * (size_t)3 * P * (P + 1); }
 // k_skel_cov_rates on stream s, one workgroup per frame, after k_skel_selinv has left the blocks of the inverse in d_band:

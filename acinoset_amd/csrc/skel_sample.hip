@@ -26,7 +26,8 @@
 //                           that the two rows a half-wave reads fall into different banks.  z is read and x + delta written
 //                           once each, rows of P contiguous doubles, through a per-wave staging tile [16][P] in LDS (z masked
 //                           by the pin mask and the padding rows p >= P on the way in).
-//                           LDS: 4 PT^2 + SKS_W * 16 * ST doubles (ST = PT + 2, or PT with rotated rows at PT = 64):
+//                           LDS (SksShape<PT> of skel_factor.hpp, shared with k_skel_fwdsub of skel_calib.hip):
+//                           4 PT^2 + SKS_W * 16 * ST doubles (ST = PT + 2, or PT with rotated rows at PT = 64):
 //                           50 / 99 KB at PT = 32 / 48, and at PT = 64 the blocks' 128 KB + 32 KB = the whole 160 KB.
 //   k_skel_sample_fk        one thread per (clip, sample, frame): the real forward kinematics of the sample (the link
 //                           program on the sample's active states), not the linearisation.
@@ -53,21 +54,8 @@ k_skel_factor(const SkelDev* __restrict__ dev, SkelClip* __restrict__ clip, doub
   if (threadIdx.x == 0 && __hip_atomic_load(&cs.pivot_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) cs.status = 5;
 }
 
-constexpr int SKS_W = 4, SKS_T = 64 * SKS_W, SKS_PANEL = 16 * SKS_W;
-
-template <int PT>
-struct SksShape {
-  static constexpr bool ROT = PT % 32 == 0;        // L rows of 32 or 64 doubles: odd rows rotated by 16 columns
-  static constexpr bool SROT = PT == 64;           // staging rows: padded by 2 doubles, or (no room at PT = 64) rotated by 2 li
-  static constexpr int ST = SROT ? PT : PT + 2;
-  static constexpr size_t lds = sizeof(double) * ((size_t)4 * PT * PT + (size_t)SKS_W * 16 * ST);
-  // entry (k, m) of a block in LDS; m0 + li with m0 a multiple of 16 stays contiguous in li
-  __device__ static __forceinline__ int at(int k, int m) { return k * PT + (ROT ? ((m + 16 * (k & 1)) & (PT - 1)) : m); }
-  // entry (sample column c, state p) of a wave's staging tile
-  __device__ static __forceinline__ int st(int c, int p) { return c * ST + (SROT ? ((p + 2 * c) & (PT - 1)) : p); }
-};
-
-template <int PT>
+// ADDX: x + delta (the samples); false: delta alone (skel_launch_back_columns: x_all is not read)
+template <int PT, bool ADDX>
 __global__ void __launch_bounds__(SKS_T)
 k_skel_sample_back(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, const double* __restrict__ band_all,
                    const unsigned char* __restrict__ fxm_all, const double* __restrict__ x_all, const double* __restrict__ z_all,
@@ -172,7 +160,10 @@ k_skel_sample_back(const SkelDev* __restrict__ dev, const SkelClip* __restrict__
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     for (int e = lane; e < 16 * PT; e += 64) {
       const int c = e / PT, p = e % PT;
-      if (s0 + c < S && p < P) xs_all[row0 + c * srow + (size_t)n * P + p] = x[(size_t)n * P + p] + stage[Sh::st(c, p)];
+      if (s0 + c < S && p < P) {
+        if constexpr (ADDX) xs_all[row0 + c * srow + (size_t)n * P + p] = x[(size_t)n * P + p] + stage[Sh::st(c, p)];
+        else xs_all[row0 + c * srow + (size_t)n * P + p] = stage[Sh::st(c, p)];
+      }
     }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -200,23 +191,42 @@ k_skel_sample_fk(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ c
 }
 
 template <int PT>
-static int skel_sample_launch(int B, long long S, const SkelDev* d_dev, SkelClip* d_clip, double* d_band, const double* d_diag0,
-                              const unsigned char* d_fxm, const double* d_x, const double* d_z, double* d_xs, hipStream_t s) {
+static int skel_factor_launch(int B, const SkelDev* d_dev, SkelClip* d_clip, double* d_band, const double* d_diag0, hipStream_t s) {
   static PerDeviceOnce attr;
-  if (attr.first()) {
+  if (attr.first())
     ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_factor<PT>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_sample_back<PT>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  }
-  static_assert(SksShape<PT>::lds <= 160 * 1024 && sizeof(double) * 4 * PT * (PT + 1) <= 160 * 1024, "LDS");
+  static_assert(sizeof(double) * 4 * PT * (PT + 1) <= 160 * 1024, "LDS");
   hipLaunchKernelGGL(k_skel_factor<PT>, dim3(B), dim3(SKC_T), skel_factor_lds(PT), s, d_dev, d_clip, d_band, d_diag0);
   ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
+
+template <int PT, bool ADDX>
+static int skel_back_launch(int B, long long S, const SkelDev* d_dev, const SkelClip* d_clip, const double* d_band,
+                            const unsigned char* d_fxm, const double* d_x, const double* d_z, double* d_xs, hipStream_t s) {
+  static PerDeviceOnce attr;
+  if (attr.first())
+    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_sample_back<PT, ADDX>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  static_assert(SksShape<PT>::lds <= 160 * 1024, "LDS");
   const long long panels = (S + SKS_PANEL - 1) / SKS_PANEL;
-  hipLaunchKernelGGL(k_skel_sample_back<PT>, dim3((unsigned)panels, (unsigned)B), dim3(SKS_T), SksShape<PT>::lds, s, d_dev, d_clip,
-                     d_band, d_fxm, d_x, d_z, d_xs, S);
+  hipLaunchKernelGGL((k_skel_sample_back<PT, ADDX>), dim3((unsigned)panels, (unsigned)B), dim3(SKS_T), SksShape<PT>::lds, s, d_dev,
+                     d_clip, d_band, d_fxm, d_x, d_z, d_xs, S);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
+}
+
+int skel_launch_factor(int PT, int n_clips, const SkelDev* d_dev, SkelClip* d_clip, double* d_band, const double* d_diag0,
+                       hipStream_t s) {
+  return skel_dispatch_pt(PT, [&](auto pt) { return skel_factor_launch<decltype(pt)::value>(n_clips, d_dev, d_clip, d_band, d_diag0, s); });
+}
+
+int skel_launch_back_columns(int PT, int n_clips, long long n_cols, const SkelDev* d_dev, const SkelClip* d_clip,
+                             const double* d_band, const unsigned char* d_fxm, const double* d_y, double* d_out, hipStream_t s) {
+  return skel_dispatch_pt(PT, [&](auto pt) {
+    return skel_back_launch<decltype(pt)::value, false>(n_clips, n_cols, d_dev, d_clip, d_band, d_fxm, nullptr, d_y, d_out, s);
+  });
 }
 
 static bool overlap(const void* a, size_t na, const void* b, size_t nb) {
@@ -274,8 +284,9 @@ int acino_skel_fte_sample_pinned(const acino_skel_fte_params* p, int n_clips, in
   SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
+  if ((rc = skel_launch_factor(PT, B, d_dev, d_clip, D(lay.band), D(lay.diag0), s))) return rc;
   rc = skel_dispatch_pt(PT, [&](auto pt) {
-    return skel_sample_launch<decltype(pt)::value>(B, n_samples, d_dev, d_clip, D(lay.band), D(lay.diag0), d_fxm, d_x, d_z, d_x_samples, s);
+    return skel_back_launch<decltype(pt)::value, true>(B, n_samples, d_dev, d_clip, D(lay.band), d_fxm, d_x, d_z, d_x_samples, s);
   });
   if (rc) return rc;
   if (d_pos_samples) {

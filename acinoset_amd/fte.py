@@ -518,24 +518,7 @@ class FTEContext:
         return post
 
 
-def _cov_cams_matrix(cov_cams, n_cams):
-    """``cov_cams`` as a checked float64 numpy [6C, 6C] matrix (None stays None): host arithmetic, no launch."""
-    if cov_cams is None:
-        return None
-    if isinstance(cov_cams, dict):
-        if "cov_cams" not in cov_cams:
-            raise ValueError('cov_cams given as a dict must hold "cov_cams" (the dict of sba.covariance)')
-        cov_cams = cov_cams["cov_cams"]
-    a = cov_cams.detach().cpu().numpy() if isinstance(cov_cams, torch.Tensor) else np.asarray(cov_cams)
-    a = np.asarray(a, dtype=np.float64)
-    W = 6 * int(n_cams)
-    if a.shape != (W, W):
-        raise ValueError(f"cov_cams must be [{W}, {W}] (6 per camera: dw, dt), got {tuple(a.shape)}")
-    if not np.isfinite(a).all():
-        raise ValueError("cov_cams has a non-finite entry")
-    if not np.allclose(a, a.T, rtol=1e-12, atol=1e-12 * max(float(np.abs(a).max()), 1e-300)):
-        raise ValueError("cov_cams is not symmetric")
-    return np.ascontiguousarray(a)
+_cov_cams_matrix = calib.cov_cams_matrix       # (the one validator of a calibration covariance, shared with build.py)
 
 
 _REPROJ_KEYS = dict(uv="uv", cov_uv="cov_uv", std_uv="std_uv", res="residuals", weight="weights", mahal2="mahal2", flags="flags")

@@ -776,6 +776,51 @@ int acino_skel_fte_covariance_rates(const acino_skel_fte_params* p, int n_clips,
                                     void* d_ws, size_t ws_bytes, void* stream, int pin_unobserved,
                                     uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
 
+/* ---- generic-skeleton FTE error bars that include the calibration: sensitivity to the camera extrinsics ---------------------
+ * acino_skel_fte_calibration_sensitivity: S = -A^-1 G, the sensitivity of the trajectory to the extrinsics, and the "consider"
+ * covariance S Sigma S^T it gives for a covariance Sigma of the extrinsics.  All quantities are at the caller's iterate
+ * d_x[n_clips][N][n_active].  A, the bound pins, pin_unobserved, the status rules, the limits, both camera models and the
+ * leading arguments are exactly those of acino_skel_fte_covariance_pinned.
+ * Camera parameters are c = [dw_0, dt_0, ..., dw_C-1, dt_C-1], applied as R_c <- exp([dw]x) R_c, t_c <- t_c + dt: the order
+ * and units of acino_sba_covariance (and calib.extrinsic_cov), so its cov_cams plugs in unchanged.
+ * For a row (n, c, l, d) that the assembly keeps - it drops a row when w = 0, when the measurement is non-finite, or when
+ * |z_cam| < 1e-9 - with p = pose_l(x_n):
+ *   J_x = J_pi G_l (2 x n_active), J_pi and G_l those of the Fisher assembly and of d_cov_pos.
+ *   J_c = J_pi R_c^T [ -[R_c p]x | I_3 ] (2 x 6), the derivative of the predicted pixel with respect to (dw_c, dt_c).
+ *   The weight is w^2: the Fisher weight of the stated Laplace model, the same statement A makes.  It is NOT the IRLS
+ *   curvature; it depends neither on the residual nor on l1_eps.
+ *   G_n[:, 6c:6c+6] = sum over l, d of J_x^T w^2 J_c;  S = -A^-1 G, shape [n_clips][N][n_active][6C].
+ *   Rows of G for pinned variables (bound pins and, with pin_unobserved, unobserved pins) are 0: rows of S are EXACTLY 0 there.
+ * S is the shift of the minimiser of the expected (Fisher) quadratic model per unit change of the extrinsics, consistent with
+ * the A^-1 the covariance reports.  It is NOT a derivative of the L1 / Levenberg-Marquardt end point.
+ * With Sigma = d_cov_cams[6C][6C] (e.g. cov_cams of acino_sba_covariance; only PSD - a held camera has zero rows - so it is
+ * multiplied, T = S_n Sigma, then T S_n^T, and never factored):
+ *   d_sens       [n_clips][N][n_active][6C]         S
+ *   d_cov_x_cal  [n_clips][N][n_active][n_active]   S_n Sigma S_n^T, symmetric to the bit
+ *   d_cov_pos_cal[n_clips][N][n_pose][3][3]         G_l cov_x_cal G_l^T, symmetric to the bit
+ *   d_std_pos_cal[n_clips][N][n_pose]               sqrt(trace(cov_pos_cal)), metres
+ * Any output may be NULL, but not all of them; a cov / std output without d_cov_cams is ACINO_ERR_INVALID_ARG.  With
+ * pin_unobserved = 1 a slot whose G_l has a nonzero entry in the column of an unobserved state gets std_pos_cal = +inf and NaN
+ * cov_pos_cal (the rule of d_std_pos).  A singular clip gets status 5 and NaN in every output; in a batch with h_status the
+ * other clips stand.  The result of one clip is the same bits whatever else shares the call.
+ * The total covariance of a trajectory is cov + cov_cal ONLY for a calibration obtained from OTHER data than the clips being
+ * solved; it is not valid for extrinsics refined on the same clips (the two errors are then correlated).  The calibration term
+ * is perfectly correlated across frames: smoothing does not average it out.
+ * Limit: n_cams <= ACINO_MAX_CAMS = 16 (96 columns), checked with every other argument before any device call.  Launches on
+ * `stream`: the Fisher assembly and build of the covariance, k_skel_calib_rhs (-G as 6C columns), k_skel_factor, one forward
+ * (k_skel_fwdsub) and one backward substitution per clip and panel of 64 columns, k_skel_calib_combine; one synchronisation.
+ * Workspace: the pinned covariance workspace plus two column buffers [n_clips][6C][N][n_active], 256-byte aligned
+ * (ACINO_ERR_WORKSPACE otherwise); the query returns 0 outside the limits. */
+size_t acino_skel_fte_calibration_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved);
+int acino_skel_fte_calibration_sensitivity(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                           const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                           const double* d_lo, const double* d_hi, const double* d_x,
+                                           const double* d_cov_cams /* [6C][6C] or NULL */, double* d_sens, double* d_cov_x_cal,
+                                           double* d_cov_pos_cal, double* d_std_pos_cal,
+                                           int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes,
+                                           void* stream, int pin_unobserved,
+                                           uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
+
 /* ---- a generic-skeleton FTE iterate in image space: predicted pixels, their covariance, residuals, gating ----------------
  * Evaluated at the iterate d_x[n_clips][N][n_active] (normally the solution of acino_skel_fte_solve*).  Per entry
  * (b, n, c, l) = (clip, frame, camera, pose slot), the layout of d_meas[n_clips][N][C][n_pose][2] / d_w[n_clips][N][C][n_pose]:
