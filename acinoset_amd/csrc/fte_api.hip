@@ -1,5 +1,11 @@
 // FTE solve: context, Levenberg-Marquardt controller (device-resident) and the C ABI.
 // Reference: the Pyomo model + IPOPT solve of src/all_optimizations.py:283-556 in reduced form.
+//
+// Host layer, one place per decision: Layout / carve (plan, schedule, workspace of a parameter set), reduced_chain (the
+// chain `sched` reduces), fresh_state (the LM state of create and load_x), replay (hipGraph capture / replay of the four
+// sharded phases and of the single-shard step, one GraphSlot each), drop_graphs (the one invalidation: destroy,
+// set_precision, debug_stamps, sep_tail_fall_back), sep_schedule (the cross-rank separator chain's schedule with its
+// packed ints), sep_tail_fall_back (acino_fte_solve when k_sep_tail was refused the compute units it counted on).
 #include <algorithm>
 #include <map>
 #include <new>
@@ -54,15 +60,15 @@ struct acino_fte_ctx {
   int n_pred;         // entries of pred_part / step_part: blocks of k_trial, or runs of the chunked back-substitution (which folds it in)
   size_t ws_bytes;
   acino::Profiler prof;
-  bool graph_on = false;            // replay the LM step as a hipGraph (single-shard contexts, non-null stream)
-  hipGraphExec_t gexec = nullptr;
-  hipStream_t gstream = nullptr;
-  // the four phases of a SHARDED iteration (between the collectives), each captured once per buffer set
-  struct SegGraph {
+  bool graph_on = false;            // replay fixed launch sequences as hipGraphs (non-null stream, profiler off)
+  // captured once per stream and buffer set (key): slots 0..3 the four phases of a SHARDED iteration (between the collectives),
+  // STEP_SLOT the whole LM step of a single-shard context; slot i is bit i of acino_fte_graphs_active
+  struct GraphSlot {
     hipGraphExec_t exec = nullptr;
     hipStream_t stream = nullptr;
     uintptr_t key[6] = {0, 0, 0, 0, 0, 0};
-  } seg[4];
+  } graph[5];
+  static constexpr int STEP_SLOT = 4;
 };
 
 namespace acino {
@@ -675,6 +681,28 @@ static int validate(const acino_fte_params* p) {
 
 using namespace acino;
 
+// The chain `sched` reduces: a chunked context's separator chain (the pins are its first / last node), else the 3-frame nodes
+static BcrChain& reduced_chain(acino_fte_ctx* ctx) { return ctx->plan.active() ? ctx->sepchain : ctx->chain; }
+
+// The LM state of a context that has taken no step: what create and every new start iterate (load_x) upload.
+static acino_fte_state fresh_state(double lam0) {
+  acino_fte_state st;
+  memset(&st, 0, sizeof(st));
+  st.lam = lam0;
+  st.nu = 2.0;
+  return st;
+}
+
+// A captured graph bakes in the assembly kernel (precision), sep_tail with its flags and the chains' stamp pointers: whoever
+// changes one of them drops every capture, and the next replay() captures again.
+static void drop_graphs(acino_fte_ctx* ctx) {
+  for (auto& g : ctx->graph)
+    if (g.exec) {
+      (void)hipGraphExecDestroy(g.exec);
+      g.exec = nullptr;
+    }
+}
+
 static int eval_iterate(acino_fte_ctx* ctx, int which, bool need_jac, bool with_step, bool respect_status,
                         hipStream_t s, int fused_control = -1) {
   const Buffers& b = ctx->b;
@@ -747,10 +775,7 @@ static int fte_create(acino_fte_ctx** out, const acino_fte_params* p, const doub
     return ACINO_ERR_HIP;
   }
   fill_const(p, h_cams, camera_model, &ctx->h);
-  acino_fte_state st;
-  memset(&st, 0, sizeof(st));
-  st.lam = p->lam0;
-  st.nu = 2.0;
+  const acino_fte_state st = fresh_state(p->lam0);
   e = hipMemcpyAsync(ctx->b.cst, &ctx->h, sizeof(FteConst), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->b.state, &st, sizeof(st), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemsetAsync(ctx->b.nbehind, 0, 4 * sizeof(int), s);
@@ -772,7 +797,7 @@ static int fte_create(acino_fte_ctx** out, const acino_fte_params* p, const doub
     return ACINO_ERR_HIP;
   }
   {
-    BcrChain& red = ctx->plan.active() ? ctx->sepchain : ctx->chain;   // the chain the schedule reduces
+    BcrChain& red = reduced_chain(ctx);
     ctx->sched.bind(ctx->b.sched, red);
     ctx->n_trunc = red.n_pairs;
     red.refine_buf = ctx->b.refine_buf;
@@ -844,18 +869,14 @@ int acino_fte_plan(const acino_fte_params* p, int32_t* out) {
 }
 
 int acino_fte_destroy(acino_fte_ctx* ctx) {
-  if (ctx && ctx->gexec) (void)hipGraphExecDestroy(ctx->gexec);
-  if (ctx)
-    for (auto& g : ctx->seg)
-      if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  if (ctx) drop_graphs(ctx);
   delete ctx;
   return ACINO_OK;
 }
 
 int acino_fte_graphs_active(acino_fte_ctx* ctx) {
-  if (!ctx) return 0;
-  int m = ctx->gexec ? 16 : 0;
-  for (int i = 0; i < 4; ++i) m |= ctx->seg[i].exec ? (1 << i) : 0;
+  int m = 0;
+  for (int i = 0; ctx && i < 5; ++i) m |= ctx->graph[i].exec ? (1 << i) : 0;      // (phases 1, 2, 4, 8; the step 16)
   return m;
 }
 
@@ -868,10 +889,7 @@ int acino_fte_enable_graph(acino_fte_ctx* ctx, int on) {
 int acino_fte_load_x(acino_fte_ctx* ctx, const double* d_x0, void* stream) {
   ACINO_REQUIRE(ctx && d_x0, "null");
   hipStream_t s = (hipStream_t)stream;
-  acino_fte_state st;
-  memset(&st, 0, sizeof(st));
-  st.lam = ctx->lam0;
-  st.nu = 2.0;
+  const acino_fte_state st = fresh_state(ctx->lam0);
   ACINO_HIP_CHECK(hipMemcpyAsync(ctx->b.state, &st, sizeof(st), hipMemcpyHostToDevice, s));
   ACINO_HIP_CHECK(hipStreamSynchronize(s));   // st lives on this stack frame
   ACINO_HIP_CHECK(hipMemsetAsync(ctx->b.nbehind, 0, 4 * sizeof(int), s));
@@ -904,15 +922,7 @@ int acino_fte_set_precision(acino_fte_ctx* ctx, int precision) {
   ACINO_REQUIRE(ctx->h.camera_model != CAMERA_PINHOLE || precision == ACINO_PREC_F64,
                 "the pinhole camera model is assembled in fp64 only (precision ACINO_PREC_F64)");
   ctx->h.precision = precision;            // the assembly kernel is chosen on the host; the device block does not need it
-  if (ctx->gexec) {
-    (void)hipGraphExecDestroy(ctx->gexec);
-    ctx->gexec = nullptr;
-  }
-  for (auto& g : ctx->seg)
-    if (g.exec) {
-      (void)hipGraphExecDestroy(g.exec);
-      g.exec = nullptr;
-    }
+  drop_graphs(ctx);
   return ACINO_OK;
 }
 
@@ -984,24 +994,28 @@ int acino_fte_export_separators(acino_fte_ctx* ctx, double* d_sep, int rank, int
                 "pins must match the rank position");
   double* rec_left = ctx->h.pin_left ? d_sep + (size_t)(rank - 1) * ACINO_SEP_DOUBLES : nullptr;
   double* rec_right = ctx->h.pin_right ? d_sep + (size_t)rank * ACINO_SEP_DOUBLES : nullptr;
-  // (chunked solver: the pins are the first / last node of the separator chain)
-  const BcrChain& pc = ctx->plan.active() ? ctx->sepchain : ctx->chain;
+  const BcrChain& pc = reduced_chain(ctx);
   hipLaunchKernelGGL(k_export_sep, dim3(8), dim3(256), 0, (hipStream_t)stream, pc, 0, pc.n_nodes - 1, rec_left, rec_right);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }
 
 namespace acino {
-static const BcrSchedule& sep_schedule(int n_sep) {
-  static thread_local std::map<int, BcrSchedule> cache;   // schedules are immutable once built
+struct SepSchedule {        // of a chain of n_sep cross-rank separators: built and packed once per thread and n_sep
+  BcrSchedule sch;
+  std::vector<int> ints;    // sch.pack()
+};
+static const SepSchedule& sep_schedule(int n_sep) {
+  static thread_local std::map<int, SepSchedule> cache;   // schedules are immutable once built
   auto it = cache.find(n_sep);
   if (it == cache.end()) {
-    BcrSchedule sch;
+    SepSchedule ss;
     // (GENERAL 80 x 80 blocks: the fused narrow levels of seplevel.hip need the identity padding of FTE nodes - their right-hand
     //  side rides in the padding column - so this chain keeps the per-phase kernels, and the per-level back-substitution)
-    sch.build(n_sep, false, false);
-    sch.backsub_tail = false;
-    it = cache.emplace(n_sep, std::move(sch)).first;
+    ss.sch.build(n_sep, false, false);
+    ss.sch.backsub_tail = false;
+    ss.ints = ss.sch.pack();
+    it = cache.emplace(n_sep, std::move(ss)).first;
   }
   return it->second;
 }
@@ -1009,12 +1023,12 @@ static const BcrSchedule& sep_schedule(int n_sep) {
 
 size_t acino_sep_scratch_bytes(int n_sep) {
   if (n_sep < 1) return 0;
-  const size_t ints = sep_schedule(n_sep).pack().size();
+  const size_t ints = sep_schedule(n_sep).ints.size();
   return 6 * align_up((size_t)n_sep * BS * BS * sizeof(double)) + align_up(ints * sizeof(int)) + 1024;   // D U Cpl Wl Wr, b
 }
 
 namespace acino {
-static BcrChain sep_chain(void* d_scratch, int n_sep, const BcrSchedule& sch) {
+static BcrChain sep_chain(void* d_scratch, int n_sep, const SepSchedule& ss) {
   Carver c{(char*)d_scratch, 0};
   BcrChain ch;
   ch.n_nodes = n_sep;
@@ -1024,7 +1038,7 @@ static BcrChain sep_chain(void* d_scratch, int n_sep, const BcrSchedule& sch) {
   ch.Wl = c.take<double>((size_t)n_sep * BS * BS);
   ch.Wr = c.take<double>((size_t)n_sep * BS * BS);
   ch.b = c.take<double>((size_t)n_sep * BS);
-  sch.bind(c.take<int>(sch.pack().size()), ch);
+  ss.sch.bind(c.take<int>(ss.ints.size()), ch);
   ch.implicit_couplings = 0;
   ch.dbg = nullptr;
   ch.st = nullptr;
@@ -1043,11 +1057,11 @@ struct SchedArg {
 __global__ void k_write_schedule(SchedArg a, int* __restrict__ dst) {
   for (int i = threadIdx.x; i < a.n; i += blockDim.x) dst[i] = a.v[i];
 }
-static bool sep_schedule_fits_arg(const BcrSchedule& sch) { return sch.pack().size() <= SchedArg::cap; }
-static int sep_upload_schedule(const BcrChain& ch, const BcrSchedule& sch, hipStream_t s) {
+static bool sep_schedule_fits_arg(const SepSchedule& ss) { return ss.ints.size() <= SchedArg::cap; }
+static int sep_upload_schedule(const BcrChain& ch, const SepSchedule& ss, hipStream_t s) {
   int* d_sched = const_cast<int*>(ch.d_elim);
-  const std::vector<int> v = sch.pack();
-  if (v.size() <= SchedArg::cap) {
+  const std::vector<int>& v = ss.ints;
+  if (sep_schedule_fits_arg(ss)) {
     SchedArg a;
     a.n = (int)v.size();
     std::copy(v.begin(), v.end(), a.v);
@@ -1056,11 +1070,13 @@ static int sep_upload_schedule(const BcrChain& ch, const BcrSchedule& sch, hipSt
     return ACINO_OK;
   }
   ACINO_HIP_CHECK(hipMemcpyAsync(d_sched, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, s));
-  ACINO_HIP_CHECK(hipStreamSynchronize(s));       // (v is a local; chains this long are not graph-captured)
+  ACINO_HIP_CHECK(hipStreamSynchronize(s));       // (the copy has left the thread's cache on return; chains this long are not graph-captured)
   return ACINO_OK;
 }
-static int sep_launch(const BcrChain& ch, const BcrSchedule& sch, const double* d_sep, int n_sep, double* d_sep_x,
+static int sep_launch(const BcrChain& ch, const SepSchedule& ss, const double* d_sep, int n_sep, double* d_sep_x,
                       hipStream_t s) {
+  const BcrSchedule& sch = ss.sch;
+  if (int rc = sep_upload_schedule(ch, ss, s)) return rc;
   hipLaunchKernelGGL(k_import_sep, dim3(8, n_sep), dim3(256), 0, s, d_sep, n_sep, ch);
   ACINO_LAUNCH_CHECK();
   int rc = bcr_reduce(ch, sch, nullptr, nullptr, nullptr, s);
@@ -1080,25 +1096,23 @@ int acino_solve_separators(const double* d_sep, int n_sep, double* d_sep_x, void
   ACINO_REQUIRE(scratch_bytes >= acino_sep_scratch_bytes(n_sep), "separator scratch too small");
   ACINO_REQUIRE(((uintptr_t)d_scratch & 255) == 0, "scratch must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  const BcrSchedule& sch = sep_schedule(n_sep);
-  BcrChain ch = sep_chain(d_scratch, n_sep, sch);
+  const SepSchedule& ss = sep_schedule(n_sep);
+  const BcrChain ch = sep_chain(d_scratch, n_sep, ss);
   if (int rc = bcr_set_func_attributes()) return rc;
-  if (int rc = sep_upload_schedule(ch, sch, s)) return rc;
-  return sep_launch(ch, sch, d_sep, n_sep, d_sep_x, s);
+  return sep_launch(ch, ss, d_sep, n_sep, d_sep_x, s);
 }
 
 int acino_fte_backsub_local(acino_fte_ctx* ctx, const double* d_sep_x, int rank, int world, void* stream) {
   ACINO_REQUIRE(ctx, "null");
   hipStream_t s = (hipStream_t)stream;
+  const BcrChain& pc = reduced_chain(ctx);
   if (ctx->h.pin_left) {
     ACINO_REQUIRE(d_sep_x && rank >= 1, "separator solution");
-    hipLaunchKernelGGL(k_set_node_x, dim3(1), dim3(128), 0, s, ctx->plan.active() ? ctx->sepchain : ctx->chain, 0,
-                       d_sep_x + (size_t)(rank - 1) * BS);
+    hipLaunchKernelGGL(k_set_node_x, dim3(1), dim3(128), 0, s, pc, 0, d_sep_x + (size_t)(rank - 1) * BS);
     ACINO_LAUNCH_CHECK();
   }
   if (ctx->h.pin_right) {
     ACINO_REQUIRE(d_sep_x && rank + 1 < world, "separator solution");
-    const BcrChain& pc = ctx->plan.active() ? ctx->sepchain : ctx->chain;
     hipLaunchKernelGGL(k_set_node_x, dim3(1), dim3(128), 0, s, pc, pc.n_nodes - 1, d_sep_x + (size_t)rank * BS);
     ACINO_LAUNCH_CHECK();
   }
@@ -1131,35 +1145,46 @@ int acino_fte_export_edges(acino_fte_ctx* ctx, int which, double* d_edge, void* 
   return ACINO_OK;
 }
 
-// ---- the four phases of a sharded iteration ------------------------------------------------
-// A phase is a fixed launch sequence on caller-owned buffers; with graphs enabled it is captured once per buffer set
-// and replayed, so a rank issues 4 graph launches + 3 collectives per iteration instead of ~50 kernel launches.
+// ---- captured launch sequences: the four phases of a sharded iteration and the LM step -----------
+// Each is a fixed launch sequence (buffer selection and the accept / reject decision live on the device) on the context's
+// and on caller-owned buffers - the key; with graphs enabled it is captured once per stream and key and replayed: a rank
+// issues 4 graph launches + 3 collectives per iteration instead of ~50 kernel launches, a single-shard step one instead of ~40.
+// A capture that fails (another thread of the process touching the runtime, an unsupported call - nothing captured has
+// executed): a phase runs eagerly, now and from now on; the step fails the call.  A body that fails in a capture returns its
+// own code (a phase: from its eager run); the partial graph is destroyed either way.
+enum CaptureFailure { RUN_EAGERLY, FAIL_THE_CALL };
+
 extern "C++" {
 template <class F>
-static int run_phase(acino_fte_ctx* ctx, int id, const uintptr_t (&key)[6], hipStream_t s, F&& body) {
+static int replay(acino_fte_ctx* ctx, int slot, const uintptr_t (&key)[6], hipStream_t s, CaptureFailure on_failure, F&& body) {
   if (!(ctx->graph_on && !ctx->prof.on && s != nullptr)) return body();
-  acino_fte_ctx::SegGraph& g = ctx->seg[id];
+  acino_fte_ctx::GraphSlot& g = ctx->graph[slot];
   if (!g.exec || g.stream != s || memcmp(g.key, key, sizeof(key)) != 0) {
-    if (g.exec) {
-      (void)hipGraphExecDestroy(g.exec);
-      g.exec = nullptr;
-    }
-    // capture; if anything about it fails (another thread of the process touching the runtime, an unsupported
-    // call) the phase simply runs eagerly from now on - nothing captured has executed
-    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    if (ok) {
-      const int rc = body();
+    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    g.exec = nullptr;
+    const char* what = "hipStreamBeginCapture";
+    hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    int rc = ACINO_OK;
+    if (e == hipSuccess) {
+      rc = body();
       hipGraph_t graph = nullptr;
-      const hipError_t e = hipStreamEndCapture(s, &graph);
-      ok = rc == ACINO_OK && e == hipSuccess && graph != nullptr;
-      if (ok) ok = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) == hipSuccess;
+      what = "hipStreamEndCapture";
+      e = hipStreamEndCapture(s, &graph);
+      if (rc == ACINO_OK && e == hipSuccess) {
+        what = "hipGraphInstantiate";
+        e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
+      }
       if (graph) (void)hipGraphDestroy(graph);
     }
-    if (!ok) {
-      (void)hipGetLastError();
+    if (rc != ACINO_OK || e != hipSuccess) {
       g.exec = nullptr;
-      ctx->graph_on = false;
-      return body();
+      if (on_failure == RUN_EAGERLY) {
+        (void)hipGetLastError();
+        ctx->graph_on = false;
+        return body();
+      }
+      if (rc == ACINO_OK) set_error("%s failed: %s", what, hipGetErrorString(e));
+      return rc != ACINO_OK ? rc : ACINO_ERR_HIP;
     }
     g.stream = s;
     memcpy(g.key, key, sizeof(key));
@@ -1173,7 +1198,7 @@ int acino_fte_shard_reduce(acino_fte_ctx* ctx, double* d_sep, int rank, int worl
   ACINO_REQUIRE(ctx && d_sep && world >= 2, "args");
   hipStream_t s = (hipStream_t)stream;
   const uintptr_t key[6] = {(uintptr_t)d_sep, (uintptr_t)rank, (uintptr_t)world, 0, 0, 0};
-  return run_phase(ctx, 0, key, s, [&]() -> int {
+  return replay(ctx, 0, key, s, RUN_EAGERLY, [&]() -> int {
     ACINO_HIP_CHECK(hipMemsetAsync(d_sep, 0, sizeof(double) * (size_t)(world - 1) * ACINO_SEP_DOUBLES, s));
     if (int rc = acino_fte_reduce_local(ctx, stream)) return rc;
     return acino_fte_export_separators(ctx, d_sep, rank, world, stream);
@@ -1187,19 +1212,18 @@ int acino_fte_shard_solve(acino_fte_ctx* ctx, const double* d_sep, double* d_sep
   ACINO_REQUIRE(scratch_bytes >= acino_sep_scratch_bytes(n_sep), "separator scratch too small");
   ACINO_REQUIRE(((uintptr_t)d_scratch & 255) == 0, "scratch must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  const BcrSchedule& sch = sep_schedule(n_sep);
-  const BcrChain ch = sep_chain(d_scratch, n_sep, sch);
+  const SepSchedule& ss = sep_schedule(n_sep);
+  const BcrChain ch = sep_chain(d_scratch, n_sep, ss);
   const uintptr_t key[6] = {(uintptr_t)d_sep, (uintptr_t)d_sep_x, (uintptr_t)d_scratch, (uintptr_t)d_edge_out,
                             (uintptr_t)rank, (uintptr_t)world};
   auto body = [&]() -> int {
-    if (int rc = sep_upload_schedule(ch, sch, s)) return rc;
-    if (int rc = sep_launch(ch, sch, d_sep, n_sep, d_sep_x, s)) return rc;
+    if (int rc = sep_launch(ch, ss, d_sep, n_sep, d_sep_x, s)) return rc;
     if (int rc = acino_fte_backsub_local(ctx, d_sep_x, rank, world, stream)) return rc;
     if (int rc = acino_fte_trial(ctx, stream)) return rc;
     return acino_fte_export_edges(ctx, 1, d_edge_out, stream);
   };
-  if (!sep_schedule_fits_arg(sch)) return body();     // (host copy inside: run eagerly)
-  return run_phase(ctx, 1, key, s, body);
+  if (!sep_schedule_fits_arg(ss)) return body();     // (host copy inside: run eagerly)
+  return replay(ctx, 1, key, s, RUN_EAGERLY, body);
 }
 
 int acino_fte_shard_eval(acino_fte_ctx* ctx, int which, const double* d_all_edges, int rank, int world,
@@ -1211,7 +1235,7 @@ int acino_fte_shard_eval(acino_fte_ctx* ctx, int which, const double* d_all_edge
   const double* hr = rank + 1 < world ? d_all_edges + (size_t)(rank + 1) * 6 * NP : nullptr;     // right rank's first 3
   const uintptr_t key[6] = {(uintptr_t)d_all_edges, (uintptr_t)d_partial_out, (uintptr_t)rank, (uintptr_t)world,
                             (uintptr_t)which, 0};
-  return run_phase(ctx, 2, key, s, [&]() -> int {
+  return replay(ctx, 2, key, s, RUN_EAGERLY, [&]() -> int {
     if (int rc = acino_fte_set_halo(ctx, which, hl, hr, stream)) return rc;
     if (int rc = acino_fte_eval(ctx, which, stream)) return rc;
     return acino_fte_export_partials(ctx, d_partial_out, stream);
@@ -1222,7 +1246,7 @@ int acino_fte_shard_control(acino_fte_ctx* ctx, const double* d_all_partials, in
   ACINO_REQUIRE(ctx && d_all_partials && world >= 1, "args");
   hipStream_t s = (hipStream_t)stream;
   const uintptr_t key[6] = {(uintptr_t)d_all_partials, (uintptr_t)world, (uintptr_t)init, 0, 0, 0};
-  return run_phase(ctx, 3, key, s, [&]() -> int {
+  return replay(ctx, 3, key, s, RUN_EAGERLY, [&]() -> int {
     ProfSpan sp(&ctx->prof, PC_CONTROL, s);
     hipLaunchKernelGGL(k_control_gathered, dim3(1), dim3(64), 0, s, ctx->b.cst, ctx->b.state, d_all_partials, world,
                        ctx->b.numeric_err, init);
@@ -1244,46 +1268,34 @@ static int step_eager(acino_fte_ctx* ctx, void* stream) {
 int acino_fte_step(acino_fte_ctx* ctx, void* stream) {
   ACINO_REQUIRE(ctx, "null");
   ACINO_REQUIRE(!ctx->h.pin_left && !ctx->h.pin_right, "sharded contexts are stepped by the multi-GPU driver");
-  hipStream_t s = (hipStream_t)stream;
-  // The step is a fixed launch sequence (buffer selection and the accept/reject decision live on the
-  // device), so it can be captured once and replayed: ~40 launch boundaries shrink to graph-node edges.
-  if (ctx->graph_on && !ctx->prof.on && s != nullptr) {
-    if (!ctx->gexec || ctx->gstream != s) {
-      if (ctx->gexec) {
-        (void)hipGraphExecDestroy(ctx->gexec);
-        ctx->gexec = nullptr;
-      }
-      ACINO_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      int rc = step_eager(ctx, stream);
-      hipGraph_t graph = nullptr;
-      hipError_t e = hipStreamEndCapture(s, &graph);
-      if (rc) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return rc;
-      }
-      if (e != hipSuccess) {
-        set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e));
-        return ACINO_ERR_HIP;
-      }
-      e = hipGraphInstantiate(&ctx->gexec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) {
-        ctx->gexec = nullptr;
-        set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e));
-        return ACINO_ERR_HIP;
-      }
-      ctx->gstream = s;
-    }
-    ACINO_HIP_CHECK(hipGraphLaunch(ctx->gexec, s));
-    return ACINO_OK;
-  }
-  return step_eager(ctx, stream);
+  const uintptr_t key[6] = {0, 0, 0, 0, 0, 0};       // (the step touches the context's own buffers only)
+  return replay(ctx, acino_fte_ctx::STEP_SLOT, key, (hipStream_t)stream, FAIL_THE_CALL,
+                [&]() -> int { return step_eager(ctx, stream); });
 }
 
 int acino_fte_get_state(acino_fte_ctx* ctx, acino_fte_state* out, void* stream) {
   ACINO_REQUIRE(ctx && out, "null");
   ACINO_HIP_CHECK(hipMemcpyAsync(out, ctx->b.state, sizeof(*out), hipMemcpyDeviceToHost, (hipStream_t)stream));
   ACINO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  return ACINO_OK;
+}
+
+// The single-launch back-substitution of the separator chain (k_sep_tail: numeric_err bit 3) waited in vain for another
+// workgroup (something else holds the compute units it counted on): the refused step changed nothing but the counters -
+// fall back to the per-level kernels for the rest of this context's life and go on from the same iterate: sep_tail off,
+// its flags cleared, the state (*st: as read back after the refused step) rewound by that step, the captures dropped.
+// (The other bounded wait - the d_done tail of bcr.hip - has no such alternative: status 6 is returned.)
+static int sep_tail_fall_back(acino_fte_ctx* ctx, acino_fte_state* st, hipStream_t s) {
+  ctx->sched.sep_tail = false;
+  ctx->sep.flags = nullptr;
+  ctx->sep.n_flags = 0;
+  drop_graphs(ctx);
+  st->status = 0;
+  st->iter -= 1;
+  ACINO_HIP_CHECK(hipMemcpyAsync(ctx->b.state, st, sizeof(*st), hipMemcpyHostToDevice, s));
+  ACINO_HIP_CHECK(hipMemsetAsync(ctx->b.numeric_err, 0, sizeof(int), s));
+  ACINO_HIP_CHECK(hipMemsetAsync(ctx->b.st_flags, 0, sizeof(int) * (size_t)ctx->b.n_st_flags, s));
+  ACINO_HIP_CHECK(hipStreamSynchronize(s));
   return ACINO_OK;
 }
 
@@ -1317,24 +1329,8 @@ int acino_fte_solve(acino_fte_ctx* ctx, int max_iter, acino_fte_state* out, void
     ACINO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   }
   if (st.status == 6 && (ne & 8) && ctx->sched.sep_tail && max_iter > 0) {
-    // the single-launch back-substitution of the separator chain (k_sep_tail: numeric_err bit 3) waited in vain for another
-    // workgroup (something else holds the compute units it counted on): the refused step changed nothing but the counters -
-    // fall back to the per-level kernels for the rest of this context's life and go on from the same iterate.  (The other
-    // bounded wait - the d_done tail of bcr.hip - has no such alternative: status 6 is returned.)
-    ctx->sched.sep_tail = false;
-    ctx->sep.flags = nullptr;
-    ctx->sep.n_flags = 0;
-    if (ctx->gexec) {
-      (void)hipGraphExecDestroy(ctx->gexec);
-      ctx->gexec = nullptr;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    st.status = 0;
-    st.iter -= 1;
-    ACINO_HIP_CHECK(hipMemcpyAsync(ctx->b.state, &st, sizeof(st), hipMemcpyHostToDevice, s));
-    ACINO_HIP_CHECK(hipMemsetAsync(ctx->b.numeric_err, 0, sizeof(int), s));
-    ACINO_HIP_CHECK(hipMemsetAsync(ctx->b.st_flags, 0, sizeof(int) * (size_t)ctx->b.n_st_flags, s));
-    ACINO_HIP_CHECK(hipStreamSynchronize(s));
+    rc = sep_tail_fall_back(ctx, &st, (hipStream_t)stream);
+    if (rc) return rc;
     const int done = st.iter - iter_at_entry;          // steps of this call that were applied before the refused one
     return acino_fte_solve(ctx, max_iter > done ? max_iter - done : 1, out, stream);
   }
@@ -1535,11 +1531,13 @@ int acino_fte_get_result(acino_fte_ctx* ctx, double ts, double* d_x, double* d_p
 
 // Debug: phase timestamps (100 MHz wall clock) go to d_dbg[0..63] of a caller buffer of ACINO_DEBUG_STAMP_ENTRIES (72)
 // entries; the selectors are d_dbg[64] = workgroup index and d_dbg[65] = reduction level (k_bcr_elim) / node of the run
-// (k_chunk_sweep).
+// (k_chunk_sweep).  The pointer is a kernel argument: captured graphs are dropped, so that none keeps stamping into a
+// buffer the caller has switched off or freed.
 int acino_fte_debug_stamps(acino_fte_ctx* ctx, long long* d_dbg) {
   ACINO_REQUIRE(ctx, "null");
   ctx->chain.dbg = d_dbg;
   ctx->sepchain.dbg = d_dbg;       // (k_sep_level, k_sep_tail: selectors in their own comments)
+  drop_graphs(ctx);
   return ACINO_OK;
 }
 
@@ -1549,7 +1547,8 @@ int acino_fte_debug_stamps(acino_fte_ctx* ctx, long long* d_dbg) {
 int acino_fte_debug_read(acino_fte_ctx* ctx, int what, double* d_out, int64_t n, void* stream) {
   ACINO_REQUIRE(ctx && d_out && n >= 0, "args");
   const size_t MB = (size_t)BS * BS;
-  const size_t T = ctx->chain.n_nodes, S = ctx->plan.active() ? (size_t)ctx->plan.n_sep : 0;
+  // (S: the separators - the nodes of the reduced chain of a chunked context, which is `sepchain` then)
+  const size_t T = ctx->chain.n_nodes, S = ctx->plan.active() ? (size_t)reduced_chain(ctx).n_nodes : 0;
   const double* src = nullptr;
   size_t cnt = 0;
   switch (what) {

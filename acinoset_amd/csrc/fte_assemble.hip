@@ -131,6 +131,22 @@ k_fk(const double* __restrict__ q, int64_t n_frames, int stride, int halo, int a
 
 int n_assemble_blocks(int n_frames) { return (n_frames + FPB - 1) / FPB; }
 
+// The 16 assembly kernels: [ACINO_PREC_* of the fisheye model, then the pinhole model][need_jac][SPLIT - 1]
+using AssembleKernel = void (*)(const FteConst*, const acino_fte_state*, int, const double*, const double*, const double*,
+                                double*, double*, double*, double*, double*, double*, double*, int*, int);
+constexpr int ASM_ROW_PINHOLE = 3;
+static_assert(ACINO_PREC_F64 == 0 && ACINO_PREC_BF16_ROWS == 1 && ACINO_PREC_BF16_RES == 2, "rows of kAssemble");
+static const AssembleKernel kAssemble[4][2][2] = {
+    {{k_fte_assemble<false, ACINO_PREC_F64, 1>, k_fte_assemble<false, ACINO_PREC_F64, 2>},
+     {k_fte_assemble<true, ACINO_PREC_F64, 1>, k_fte_assemble<true, ACINO_PREC_F64, 2>}},
+    {{k_fte_assemble<false, ACINO_PREC_BF16_ROWS, 1>, k_fte_assemble<false, ACINO_PREC_BF16_ROWS, 2>},
+     {k_fte_assemble<true, ACINO_PREC_BF16_ROWS, 1>, k_fte_assemble<true, ACINO_PREC_BF16_ROWS, 2>}},
+    {{k_fte_assemble<false, ACINO_PREC_BF16_RES, 1>, k_fte_assemble<false, ACINO_PREC_BF16_RES, 2>},
+     {k_fte_assemble<true, ACINO_PREC_BF16_RES, 1>, k_fte_assemble<true, ACINO_PREC_BF16_RES, 2>}},
+    {{k_fte_assemble_pinhole<false, 1>, k_fte_assemble_pinhole<false, 2>},
+     {k_fte_assemble_pinhole<true, 1>, k_fte_assemble_pinhole<true, 2>}},
+};
+
 int launch_assemble(const FteConst* d_c, const FteConst& h_c, const acino_fte_state* d_st, int which,
                     const double* d_det, double* const x[2], double* const H[2], double* const g[2],
                     double* const hd[2], double* d_cost_partials, int* d_nbehind, bool need_jac, bool respect_status, hipStream_t s) {
@@ -142,24 +158,10 @@ int launch_assemble(const FteConst* d_c, const FteConst& h_c, const acino_fte_st
   int dev = 0;
   ACINO_HIP_CHECK(hipGetDevice(&dev));
   if (attr.first()) {
-#define ACINO_ASM_ATTR(J, P, S)                                                                                       \
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_assemble<J, P, S>),                           \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-    ACINO_ASM_ATTR(true, ACINO_PREC_F64, 1);        ACINO_ASM_ATTR(false, ACINO_PREC_F64, 1);
-    ACINO_ASM_ATTR(true, ACINO_PREC_BF16_ROWS, 1);  ACINO_ASM_ATTR(false, ACINO_PREC_BF16_ROWS, 1);
-    ACINO_ASM_ATTR(true, ACINO_PREC_BF16_RES, 1);   ACINO_ASM_ATTR(false, ACINO_PREC_BF16_RES, 1);
-    ACINO_ASM_ATTR(true, ACINO_PREC_F64, 2);        ACINO_ASM_ATTR(false, ACINO_PREC_F64, 2);
-    ACINO_ASM_ATTR(true, ACINO_PREC_BF16_ROWS, 2);  ACINO_ASM_ATTR(false, ACINO_PREC_BF16_ROWS, 2);
-    ACINO_ASM_ATTR(true, ACINO_PREC_BF16_RES, 2);   ACINO_ASM_ATTR(false, ACINO_PREC_BF16_RES, 2);
-#undef ACINO_ASM_ATTR
-#define ACINO_ASM_ATTR_PIN(J, S)                                                                                      \
-  ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fte_assemble_pinhole<J, S>),                      \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-    ACINO_ASM_ATTR_PIN(true, 1);                    ACINO_ASM_ATTR_PIN(false, 1);
-    ACINO_ASM_ATTR_PIN(true, 2);                    ACINO_ASM_ATTR_PIN(false, 2);
-#undef ACINO_ASM_ATTR_PIN
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fk),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(FrameLds) * FPB)));
+    for (const auto& by_jac : kAssemble)
+      for (const auto& by_split : by_jac)
+        for (AssembleKernel k : by_split)
+          ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int cus = 0;
     ACINO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     if (dev >= 0 && dev < 64) cus_of[dev] = cus;
@@ -169,39 +171,12 @@ int launch_assemble(const FteConst* d_c, const FteConst& h_c, const acino_fte_st
   // CU it loses already - 3 331 frames: 30 -> 43 us)
   int split = (dev >= 0 && dev < 64 && nb <= cus_of[dev]) ? 2 : 1;
   if (const char* e = getenv("ACINO_ASM_SPLIT")) split = atoi(e) == 2 ? 2 : 1;
-#define ACINO_LAUNCH_ASSEMBLE(J, P)                                                                                   \
-  do {                                                                                                                \
-    if (split == 2)                                                                                                   \
-      hipLaunchKernelGGL((k_fte_assemble<J, P, 2>), dim3(nb), dim3(2 * FPB * NL), lds, s, d_c, d_st, which, d_det, x[0], x[1], \
-                         H[0], H[1], g[0], g[1], hd[0], hd[1], d_cost_partials, d_nbehind, respect_status ? 1 : 0);     \
-    else                                                                                                              \
-      hipLaunchKernelGGL((k_fte_assemble<J, P, 1>), dim3(nb), dim3(256), lds, s, d_c, d_st, which, d_det, x[0], x[1],  \
-                         H[0], H[1], g[0], g[1], hd[0], hd[1], d_cost_partials, d_nbehind, respect_status ? 1 : 0);     \
-  } while (0)
-#define ACINO_LAUNCH_ASSEMBLE_PIN(J)                                                                                  \
-  do {                                                                                                                \
-    if (split == 2)                                                                                                   \
-      hipLaunchKernelGGL((k_fte_assemble_pinhole<J, 2>), dim3(nb), dim3(2 * FPB * NL), lds, s, d_c, d_st, which, d_det, x[0], \
-                         x[1], H[0], H[1], g[0], g[1], hd[0], hd[1], d_cost_partials, d_nbehind, respect_status ? 1 : 0); \
-    else                                                                                                              \
-      hipLaunchKernelGGL((k_fte_assemble_pinhole<J, 1>), dim3(nb), dim3(256), lds, s, d_c, d_st, which, d_det, x[0], x[1], \
-                         H[0], H[1], g[0], g[1], hd[0], hd[1], d_cost_partials, d_nbehind, respect_status ? 1 : 0);     \
-  } while (0)
-  if (h_c.camera_model == CAMERA_PINHOLE) {       // (fp64 only: acino_fte_create_pinhole / set_precision refuse the rest)
-    if (need_jac) ACINO_LAUNCH_ASSEMBLE_PIN(true);
-    else ACINO_LAUNCH_ASSEMBLE_PIN(false);
-  } else if (h_c.precision == ACINO_PREC_BF16_ROWS) {
-    if (need_jac) ACINO_LAUNCH_ASSEMBLE(true, ACINO_PREC_BF16_ROWS);
-    else ACINO_LAUNCH_ASSEMBLE(false, ACINO_PREC_BF16_ROWS);
-  } else if (h_c.precision == ACINO_PREC_BF16_RES) {
-    if (need_jac) ACINO_LAUNCH_ASSEMBLE(true, ACINO_PREC_BF16_RES);
-    else ACINO_LAUNCH_ASSEMBLE(false, ACINO_PREC_BF16_RES);
-  } else {
-    if (need_jac) ACINO_LAUNCH_ASSEMBLE(true, ACINO_PREC_F64);
-    else ACINO_LAUNCH_ASSEMBLE(false, ACINO_PREC_F64);
-  }
-#undef ACINO_LAUNCH_ASSEMBLE
-#undef ACINO_LAUNCH_ASSEMBLE_PIN
+  // (the pinhole model is fp64 only: acino_fte_create_pinhole / set_precision refuse the rest)
+  const bool bf16 = h_c.precision == ACINO_PREC_BF16_ROWS || h_c.precision == ACINO_PREC_BF16_RES;
+  const int row = h_c.camera_model == CAMERA_PINHOLE ? ASM_ROW_PINHOLE : (bf16 ? h_c.precision : ACINO_PREC_F64);
+  hipLaunchKernelGGL(kAssemble[row][need_jac ? 1 : 0][split - 1], dim3(nb), dim3(split == 2 ? 2 * FPB * NL : 256), lds, s, d_c,
+                     d_st, which, d_det, x[0], x[1], H[0], H[1], g[0], g[1], hd[0], hd[1], d_cost_partials, d_nbehind,
+                     respect_status ? 1 : 0);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
 }
