@@ -67,7 +67,7 @@ class SkelOp(C.Structure):
 
 class SkelFteParams(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("n_cams", C.c_int32), ("n_pose", C.c_int32), ("n_ops", C.c_int32),
-                ("n_angles", C.c_int32), ("n_active", C.c_int32), ("max_iter", C.c_int32), ("pad0", C.c_int32),
+                ("n_angles", C.c_int32), ("n_active", C.c_int32), ("max_iter", C.c_int32), ("loss", C.c_int32),
                 ("h", C.c_double), ("model_weight", C.c_double), ("l1_eps", C.c_double), ("lam0", C.c_double),
                 ("ftol", C.c_double), ("xtol", C.c_double), ("gtol", C.c_double), ("lam_max", C.c_double)]
 
@@ -237,6 +237,8 @@ SIGNATURES = {
                                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P, _Z, _P, _I, _P]),
     "acino_skel_fte_reprojection": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P,
                                          _P, _D, _P, _P, _P, _P, _P, _P]),
+    "acino_skel_fte_reprojection_weights": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P,
+                                                 _P, _P, _D, _P, _P, _P, _P, _P, _P, _P]),
     "acino_selftest_mfma": (_I, [_P, _P, _I, _P, _P]),
     "acino_debug_poison_lds": (_I, [_I, _I, _P]),
     "acino_debug_level_split": (_I, [_I, _P]),

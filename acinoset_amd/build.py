@@ -26,6 +26,7 @@ R_MEAS = 3.0                # :142
 LIK_THRESH = 0.4            # :145, :187
 H_STEP = 1.0 / 120.0        # :131
 START_FRAME, N_FRAMES = 60, 100     # :132-133
+LOSSES = {"l1": 0, "redescending": 1}      # ACINO_SKEL_LOSS_L1 / ACINO_SKEL_LOSS_REDESCENDING (include/acinoset_hip.h)
 
 
 def load_skeleton(skel_file):
@@ -133,12 +134,16 @@ def _scene_distortion(camera_model, k_arr, d_arr, r_arr, t_arr):
 
 def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_frames=N_FRAMES, start_frame=START_FRAME,
                 h=H_STEP, pairing="reference", lik_thresh=LIK_THRESH, r_meas=R_MEAS, model_weight=MODEL_WEIGHT, initial_line=True,
-                camera_model=None, project_func=None):
+                camera_model=None, project_func=None, loss="l1"):
     """build.py:28-304.  ``project_dir`` is the reference's: ``data/4_cam_scene_static_sba.json`` and ``data/*.h5`` are read
     from it (:97-109); alternatively pass ``scene = (k_arr, d_arr, r_arr, t_arr)`` and ``dlc_tables`` = one
     ``(bodyparts, values[frames, K, 3])`` per camera.  ``camera_model`` "fisheye" (the default) or "pinhole", or
     ``project_func`` = calib.project_points_fisheye / calib.project_points, as calib.camera_model_of; the model keeps it as
-    ``camera_model`` and every triangulation here uses it.  Returns ``(model, pose_to_3d)`` as the reference does."""
+    ``camera_model`` and every triangulation here uses it.  ``loss``: the measurement loss the model states, kept as
+    ``model.loss`` and read by every call on the model - "l1" (the reference's, :299) or "redescending" (its
+    ``redescending_loss`` with a, b, c = 3, 10, 20 on the residuals scaled by 1 / ``r_meas``, commented out at :307; see
+    ``solve_models``).  Returns ``(model, pose_to_3d)`` as the reference does."""
+    _loss_kind(loss)
     cam_model = calib.camera_model_of(camera_model, project_func)
     prog = skeleton.compile_skeleton(skel_dict)
     names = prog["names"]
@@ -191,7 +196,7 @@ def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_f
     model = SkeletonModel(skel=skel_dict, prog=prog, names=names, active=active_states(skel_dict), meas=meas, weights=w,
                           K=k_arr, D=d_arr, R=r_arr, t=t_arr, h=float(h), lo=lo, hi=hi, init_x=init_x,
                           start_frame=int(start_frame), model_weight=float(model_weight), pairing=pair, camera_model=cam_model,
-                          x=None, info=None)
+                          loss=loss, x=None, info=None)
 
     def pose_to_3d(*states):
         return np.asarray(skeleton.skeleton_fk(prog, np.asarray(states, dtype=np.float64)[None, :]))[0]
@@ -230,8 +235,28 @@ def _batch_camera_model(models):
     return cam_model
 
 
+def _loss_kind(loss):
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {tuple(LOSSES)} (got {loss!r})")
+    return LOSSES[loss]
+
+
+def model_loss(model):
+    """The measurement loss a model states: ``model.loss``, "l1" for a model without the attribute."""
+    loss = getattr(model, "loss", "l1")
+    _loss_kind(loss)
+    return loss
+
+
+def _with_loss(model, loss):
+    return SkeletonModel(**{**model.__dict__, "loss": loss})
+
+
 def _batch_check(models):
     m0 = models[0]
+    losses = {model_loss(m) for m in models}
+    if len(losses) > 1:
+        raise ValueError("the models of one batch share the loss (got " + " and ".join(sorted(losses)) + ")")
     for m in models:
         if ((m.N, m.P) != (m0.N, m0.P) or repr(m.prog["ops"]) != repr(m0.prog["ops"]) or list(m.active) != list(m0.active)
                 or m.meas.shape != m0.meas.shape):
@@ -248,6 +273,7 @@ def _skel_params(m0, n_act, max_iter=0, lam0=1e-3, ftol=0.0, xtol=0.0, gtol=0.0,
     p.n_angles, p.n_active, p.max_iter = m0.prog["n_angles"], int(n_act), int(max_iter)
     p.h, p.model_weight, p.l1_eps = float(m0.h), float(m0.model_weight), float(l1_eps)
     p.lam0, p.ftol, p.xtol, p.gtol, p.lam_max = float(lam0), float(ftol), float(xtol), float(gtol), float(lam_max)
+    p.loss = _loss_kind(model_loss(m0))
     return p
 
 
@@ -421,6 +447,13 @@ def model_covariance(models, xs, std_only=False, l1_eps=1e-2, pin_unobserved=Fal
     hold at a bound at ``x`` are pinned (zero rows and columns; ``l1_eps`` only enters this rule, through the solver's diagonal).
     The same batch checks and camera-model selection as ``solve_models``.
 
+    Models whose ``loss`` is "redescending": the blocks are sum w^2 h(e) J^T J, the Gauss-Newton curvature of the stated objective
+    at ``x`` (the definition of ``fte.FTEContext.covariance``) - the loss is e^2 / 2 in its core, i.e. Gaussian noise of scale
+    1 / w, and a detection the solve has rejected (h ~ 0, ``model_reprojection``'s ``weight``) adds no information, so a wrong
+    detection no longer SHRINKS the bars.  Unlike the L1 Fisher matrix this one depends on the residuals: ``x`` should be the robust
+    solution.  Pins, ``pin_unobserved`` (which goes by w^2: a row is observed whatever its h), ``rates``, ``model_samples`` and
+    ``model_observability`` follow through the same build; ``model_calibration_sensitivity`` is L1 only.
+
     ``pin_unobserved=True`` (acino_skel_fte_covariance_pinned): the states of ``model_observability``'s ``unobserved`` are pinned
     in every frame of their clip, like bound pins and in addition to them - what the shipped human skeleton needs to get bars at
     all.  Every dict then carries ``unobserved`` (sorted full-state indices): ``cov_x`` has zero rows and columns there, and the
@@ -535,11 +568,19 @@ def model_calibration_sensitivity(models, xs, cov_cams=None, l1_eps=1e-2, pin_un
     return _calibration(models, xs, cov_cams, l1_eps, pin_unobserved)
 
 
+def _refuse_robust_calibration(models):
+    for m in models:
+        if model_loss(m) != "l1":
+            raise ValueError(f"the calibration sensitivity (cov_cams) is defined for the l1 loss only; the model's loss is "
+                             f"{model_loss(m)!r}")
+
+
 def _calibration(models, xs, cov_cams, l1_eps, pin_unobserved, raise_numeric=True):
     """model_calibration_sensitivity.  ``raise_numeric=False``: a singular single clip is reported in its ``status`` like a clip
     of a batch (solve_video's one-window case)."""
     if len(models) == 0:
         raise ValueError("no models")
+    _refuse_robust_calibration(models)
     Cn = int(models[0].meas.shape[1])
     sigma = calib.cov_cams_matrix(cov_cams, Cn)
     pin = bool(pin_unobserved)
@@ -585,7 +626,7 @@ def _attach_calibration(out, models, xs, cov_cams, l1_eps, pin_unobserved, with_
             res["std_pos_total"] = np.sqrt(res["std_pos"] ** 2 + res["std_pos_calib"] ** 2)
 
 
-REPROJ_KEYS = ("uv", "cov_uv", "std_uv", "res", "mahal2", "flags")
+REPROJ_KEYS = ("uv", "cov_uv", "std_uv", "res", "mahal2", "flags", "weight")
 
 
 def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1e-2, pin_unobserved=False):
@@ -612,7 +653,13 @@ def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1
 
     ``pin_unobserved=True`` reaches the covariance this call computes itself (``cov=True`` without ``cov_pos``): the shipped
     skeleton then gets ``cov_status`` 0 and finite ``cov_uv`` / ``mahal2``; a pose slot that depends on an unobserved state has NaN
-    ``cov_pos`` and therefore NaN ``cov_uv`` / ``std_uv`` / ``mahal2``, and the dict carries ``unobserved`` beside ``cov_status``."""
+    ``cov_pos`` and therefore NaN ``cov_uv`` / ``std_uv`` / ``mahal2``, and the dict carries ``unobserved`` beside ``cov_status``.
+
+    ``weight`` [.., 2] (acino_skel_fte_reprojection_weights): what each component of a detection counts for in the curvature of
+    the model's loss at ``x``.  A "redescending" model: h(w res_d) in [0, 1] for a weighted detection - 1: it counts fully, ~0: the
+    solve has rejected it - and 0 for the others; the covariance of such a model uses exactly w^2 h.  An "l1" model: 1 for a
+    weighted detection (L1 rejects nothing), 0 otherwise.  For a "redescending" model ``mahal2`` uses the noise variance r^2 in place
+    of 2 r^2 (the loss is e^2 / 2 in its core: Gaussian noise of scale r), ``cov=False``: res^T res / r^2."""
     if len(models) == 0:
         raise ValueError("no models")
     m0 = models[0]
@@ -648,13 +695,14 @@ def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1
     uv, res, m2 = empty(2), empty(2), empty()
     cuv = empty(2, 2) if cov else None
     flags = torch.empty((B, N, Cn, Lp), dtype=torch.uint8, device=dev)
-    check(lib().acino_skel_fte_reprojection(*io_["head"], ptr(cp_d), 1.0 / r_gate, ptr(uv), ptr(cuv), ptr(res), ptr(m2), ptr(flags),
-                                            *io_["tail"]))
-    uv, res, m2, flags = uv.cpu().numpy(), res.cpu().numpy(), m2.cpu().numpy(), flags.cpu().numpy()
+    wt = empty(2)
+    check(lib().acino_skel_fte_reprojection_weights(*io_["head"], ptr(cp_d), 1.0 / r_gate, ptr(uv), ptr(cuv), ptr(res), ptr(m2),
+                                                    ptr(flags), ptr(wt), *io_["tail"]))
+    uv, res, m2, flags, wt = uv.cpu().numpy(), res.cpu().numpy(), m2.cpu().numpy(), flags.cpu().numpy(), wt.cpu().numpy()
     cuv = cuv.cpu().numpy() if cov else None
     out = []
     for i in range(B):
-        o = dict(uv=uv[i], cov_uv=None, std_uv=None, res=res[i], mahal2=m2[i], flags=flags[i])
+        o = dict(uv=uv[i], cov_uv=None, std_uv=None, res=res[i], mahal2=m2[i], flags=flags[i], weight=wt[i])
         if cov:
             o["cov_uv"] = cuv[i]
             o["std_uv"] = np.sqrt(np.maximum(cuv[i][..., 0, 0] + cuv[i][..., 1, 1], 0.0))
@@ -666,7 +714,7 @@ def model_reprojection(models, xs, cov=True, cov_pos=None, r_gate=None, l1_eps=1
     return out
 
 
-def detection_report(reproj, gate=None):
+def detection_report(reproj, gate=None, reject=0.1):
     """Summary of one dict of ``model_reprojection`` (or of the ``uv`` ... ``flags`` entries of a solve's results) per (camera,
     pose slot), as a dict of numpy arrays [C, n_pose]: ``n_weighted`` the detections the solve weighted (bit 0 of the flags),
     ``mean_abs_res_px`` the mean of |res| over their components - the quantity the L1 objective sums, and what
@@ -674,7 +722,10 @@ def detection_report(reproj, gate=None):
     chi-square quantile with 2 degrees of freedom the caller picks, e.g. 9.21 - also the finite detections inside / outside
     ``mahal2 <= gate``, split by bit 0: ``n_weighted_inside``, ``n_weighted_outside``, ``n_unweighted_inside`` (low-likelihood
     detections that agree with the trajectory all the same) and ``n_unweighted_outside``, as ``fte.detection_report`` counts
-    them.  Host arithmetic on the arrays given; no kernel."""
+    them.  With ``weight`` in the dict (``model_reprojection`` returns it for every model) also ``mean_weight``, the mean of the
+    curvature weights over the components of the weighted detections (NaN where nothing is weighted; 1 for an "l1" model), and
+    ``n_rejected``, the weighted detections with a component below ``reject``: what a "redescending" solve has switched off.
+    Host arithmetic on the arrays given; no kernel."""
     res, flags = np.asarray(reproj["res"]), np.asarray(reproj["flags"])
     weighted = (flags & 1) != 0
     n_w = weighted.sum(axis=0)
@@ -690,12 +741,18 @@ def detection_report(reproj, gate=None):
         out.update(n_weighted_inside=(inside & weighted).sum(axis=0), n_weighted_outside=(outside & weighted).sum(axis=0),
                    n_unweighted_inside=(inside & ~weighted).sum(axis=0),
                    n_unweighted_outside=(outside & ~weighted).sum(axis=0))
+    if reproj.get("weight") is not None:
+        wt = np.asarray(reproj["weight"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["mean_weight"] = np.where(n_w > 0, np.where(weighted[..., None], wt, 0.0).sum(axis=(0, -1)) / (2 * np.maximum(n_w, 1)),
+                                          np.nan)
+        out["n_rejected"] = (weighted & (wt.min(axis=-1) < float(reject))).sum(axis=0)
     return out
 
 
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
                  return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
-                 return_rate_cov=False, cov_cams=None):
+                 return_rate_cov=False, cov_cams=None, l1_start=True):
     """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
@@ -718,26 +775,29 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     before the solve): ``sens_cams``, ``cov_x_calib``, ``cov_pos_calib`` and ``std_pos_calib`` of
     ``model_calibration_sensitivity`` at the returned ``x`` join every ``results`` (one more batched call), and with
     ``return_cov`` also ``std_pos_total`` = sqrt(std_pos^2 + std_pos_calib^2) - valid only for a calibration that came from other
-    data than these clips.  Without ``cov_cams`` the keys are what they were."""
+    data than these clips.  Without ``cov_cams`` the keys are what they were.
+
+    Models whose ``loss`` is "redescending" (``build_model(loss=...)``; one batch, one loss) are solved under the redescending
+    measurement loss - a wrong detection above the likelihood threshold stops pulling once it is far enough off (beyond c = 20
+    scaled units its force is ~0) - in two stages: ``l1_start=True`` (read for such models only) first runs the L1 solve of the
+    same models from ``x0`` with the same tolerances and ``max_iter``, then the robust solve from its result; ``info["l1"]`` holds
+    the first stage's info.  The first stage is part of the method: from the straight-line start every residual lies beyond c,
+    where the loss is constant and its curvature 0, and Levenberg-Marquardt crawls.  A clip whose L1 stage ends "numeric" keeps
+    that result and status.  ``l1_start=False`` starts the robust solve at ``x0`` directly (for a caller who brings the L1 end
+    point).  Everything attached afterwards is evaluated under the model's loss: the covariance, rates and samples are those
+    of the Gauss-Newton curvature sum w^2 h J^T J (``model_covariance``), the report carries the weights h; ``cov_cams`` is
+    refused for such models (ValueError before any device call)."""
     if len(models) and cov_cams is not None:
+        _refuse_robust_calibration(models)
         calib.cov_cams_matrix(cov_cams, int(models[0].meas.shape[1]))      # (a malformed matrix fails before the solve, not after)
-    xs = [np.array(m.init_x if x0 is None or x0[i] is None else x0[i], dtype=np.float64, copy=True) for i, m in enumerate(models)]
-    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_workspace_bytes_batch(C.byref(p), B), start=True, max_iter=max_iter,
-                       lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol, l1_eps=l1_eps, lam_max=lam_max)
-    m0, act, x = models[0], io_["act"], io_["x"]
-    B = len(models)
-    pos = torch.empty((B, m0.N, len(m0.names), 3), dtype=torch.float64, device=io_["dev"])
-    infos = (SkelFteInfo * B)()
-    solve = getattr(lib(), calib.CAMERAS[io_["cam_model"]].skel_fte_solve_batch)
-    head = io_["head"]
-    check(solve(*head[:2], *head[3:], ptr(pos), *io_["tail"][:2], infos, io_["tail"][2]))      # (the camera model is in the entry's name)
-    xh, ph = x.cpu().numpy(), pos.cpu().numpy()
-    out = []
-    for i, (m, xf) in enumerate(zip(models, xs)):
-        xf[:, act] = xh[i]
-        dx, ddx = _finite_diff_states(xf, float(m.h))
-        out.append((dict(positions=ph[i], x=xf, dx=dx, ddx=ddx), infos[i].as_dict()))
-    io_ = None                                              # (the workspace goes before the next call asks for its own)
+    lm = dict(max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol, l1_eps=l1_eps, lam_max=lam_max)
+    if len(models) and l1_start and all(model_loss(m) != "l1" for m in models):
+        first = _lm_solve([_with_loss(m, "l1") for m in models], x0, **lm)
+        out = _lm_solve(models, [r["x"] for r, _i in first], **lm)
+        for i, (res1, info1) in enumerate(first):
+            out[i] = (res1, dict(info1, l1=info1)) if info1["status_name"] == "numeric" else (out[i][0], dict(out[i][1], l1=info1))
+    else:
+        out = _lm_solve(models, x0, **lm)
     xs_out = [r["x"] for r, _i in out]
     if return_cov or return_rate_cov:
         keys = (("cov_x", "cov_pos", "std_pos") if return_cov else ()) + (RATE_KEYS if return_rate_cov else ())
@@ -753,9 +813,30 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     return out
 
 
+def _lm_solve(models, x0, **lm):
+    """One batched Levenberg-Marquardt call (acino_skel_fte_solve_batch*) under the models' loss: ``[(results, info), ...]``."""
+    xs = [np.array(m.init_x if x0 is None or x0[i] is None else x0[i], dtype=np.float64, copy=True) for i, m in enumerate(models)]
+    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_workspace_bytes_batch(C.byref(p), B), start=True,
+                       **lm)
+    m0, act, x = models[0], io_["act"], io_["x"]
+    B = len(models)
+    pos = torch.empty((B, m0.N, len(m0.names), 3), dtype=torch.float64, device=io_["dev"])
+    infos = (SkelFteInfo * B)()
+    solve = getattr(lib(), calib.CAMERAS[io_["cam_model"]].skel_fte_solve_batch)
+    head = io_["head"]
+    check(solve(*head[:2], *head[3:], ptr(pos), *io_["tail"][:2], infos, io_["tail"][2]))      # (the camera model is in the entry's name)
+    xh, ph = x.cpu().numpy(), pos.cpu().numpy()
+    out = []
+    for i, (m, xf) in enumerate(zip(models, xs)):
+        xf[:, act] = xh[i]
+        dx, ddx = _finite_diff_states(xf, float(m.h))
+        out.append((dict(positions=ph[i], x=xf, dx=dx, ddx=ddx), infos[i].as_dict()))
+    return out
+
+
 def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
-                return_rate_cov=False, cov_cams=None):
+                return_rate_cov=False, cov_cams=None, l1_start=True):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
@@ -765,11 +846,12 @@ def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10,
     ``pin_unobserved``: as ``solve_models`` (only together with ``return_cov`` or ``n_samples``; ``results["unobserved"]``).
     ``return_rate_cov``: the bars of ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``) join ``results``.
     ``cov_cams``: the calibration's share (``model_calibration_sensitivity``; ``std_pos_total`` with ``return_cov``), as
-    ``solve_models``."""
+    ``solve_models``.  A model whose ``loss`` is "redescending" is solved in two stages, L1 first (``l1_start``, ``info["l1"]``), as
+    ``solve_models`` describes."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
                         l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed,
                         return_reprojection=return_reprojection, pin_unobserved=pin_unobserved,
-                        return_rate_cov=return_rate_cov, cov_cams=cov_cams)[0]
+                        return_rate_cov=return_rate_cov, cov_cams=cov_cams, l1_start=l1_start)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -790,7 +872,9 @@ def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_out
     a LOWER cost (an L1 objective on real detections has many stationary points); the whole 6 240-frame video does NOT
     reach ``xtol_outer`` in 40 outer iterations (9 s; the cost still falls by ~0.4 % per outer iteration): where a stretch of
     the video has no detections the trajectory is held by the smoothness term alone (weight 0.002 / h^4 = 4e5) and
-    information crosses it half a window per outer iteration - ``solve_video`` (free windows) is the practical entry for that."""
+    information crosses it half a window per outer iteration - ``solve_video`` (free windows) is the practical entry for that.
+    The windows and the whole-clip evaluation follow ``model.loss``: a "redescending" model's windows are solved in two stages
+    (``solve_models``; pass ``l1_start=False`` in ``solver_kw`` when ``x0`` is an L1 end point already)."""
     if "max_iter" in solver_kw:
         raise TypeError("solve_model_parallel: the inner iteration budget is first_max_iter / later_max_iter (and outer_max), not max_iter")
     N, P = model.N, model.P
@@ -856,7 +940,7 @@ def window_residual_px(model, info):
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
                 overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, pin_unobserved=False,
-                return_rate_cov=False, cov_cams=None, **kw):
+                return_rate_cov=False, cov_cams=None, loss="l1", **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -911,12 +995,23 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     ``positions``, and with ``return_cov`` ``std_pos_total`` = sqrt(std_pos^2 + std_pos_calib^2).  A singular window gives NaN
     for its frames, as with ``return_cov``.  It is NOT passed on to the windows' solves.
 
+    ``loss="redescending"``: the windows are built, solved, retried and warm-started exactly as above under L1 - which window
+    is kept and ``mean_abs_residual_px`` are the L1 stage's - then ONE batched robust call (``solve_models`` on the same windows
+    with ``loss="redescending"``, ``l1_start=False``) runs from the windows' L1 end states before the stitching, and everything
+    after it (the stitch, the covariance, the report with its ``weight``) is the robust models'.  Every info is the robust
+    stage's with the L1 stage's under ``"l1"``; a window that fails numerically there keeps its L1 result and info and is listed
+    in ``results["robust_failed_windows"]``.  ``cov_cams`` is refused (ValueError).
+
     There is no ``n_samples`` here: a stitched video is not one posterior (every window has its own, and draws of neighbouring
     windows are independent); call ``model_samples`` on the windows' models."""
     if "n_samples" in kw or "sample_seed" in kw:
         raise TypeError("solve_video takes no n_samples: a stitched video is not one posterior (use model_samples per window)")
     if gate is not None and not return_reprojection:
         raise ValueError("gate needs return_reprojection=True")
+    _loss_kind(loss)
+    if loss != "l1" and cov_cams is not None:
+        raise ValueError(f"the calibration sensitivity (cov_cams) is defined for the l1 loss only; loss is {loss!r}")
+    kw.pop("l1_start", None)                                  # (the stages are this function's own)
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
     cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
     build_kw["camera_model"] = cam_model
@@ -995,6 +1090,15 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
                 solved[i], px[i], warm_from[i], improved = (res, info), p_new, j, True
         if not improved:
             break
+    robust_failed = []
+    if loss != "l1":
+        models = [_with_loss(m, loss) for m in models]
+        second = solve_models(models, [res["x"] for res, _info in solved], l1_start=False, **kw)
+        for i, (res2, info2) in enumerate(second):
+            if info2["status_name"] == "numeric":
+                robust_failed.append(i)
+            else:
+                solved[i] = (res2, dict(info2, l1=solved[i][1]))
     Lp, P = len(models[0].names), models[0].P
     pos, x, dx, ddx = np.zeros((total, Lp, 3)), np.zeros((total, P)), np.zeros((total, P)), np.zeros((total, P))
     depth = np.full(total, -1.0)
@@ -1014,6 +1118,8 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
         infos.append(info)
     seams = [int(n) for n in np.nonzero(np.diff(owner) != 0)[0] + 1]
     results = dict(positions=pos, x=x, dx=dx, ddx=ddx, start_frame=f0, seams=seams)
+    if loss != "l1":
+        results["robust_failed_windows"] = robust_failed
     if return_cov or return_rate_cov:
         keys = (("cov_pos", "std_pos") if return_cov else ()) + (RATE_KEYS if return_rate_cov else ())
         covs = _covariance(models, [res["x"] for res, _info in solved], kw.get("l1_eps", 1e-2), keys,
@@ -1079,7 +1185,8 @@ def solve_optimisation(model, exe_path=None, project_dir=None, poses=None, **sol
     ``return_reprojection=True`` the image-space report of ``model_reprojection``, ``return_rate_cov=True`` the error bars of
     ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``), ``pin_unobserved=True`` pins the unobserved
     states in those (``results["unobserved"]``), ``cov_cams=Sigma`` adds the calibration's share of the bars
-    (``model_calibration_sensitivity``); the saved pickle keeps the reference's four entries."""
+    (``model_calibration_sensitivity``); the saved pickle keeps the reference's four entries.  A model built with
+    ``loss="redescending"`` is solved in two stages (``solve_models``: ``l1_start``, ``info["l1"]``)."""
     results, info = solve_model(model, **solver_kw)
     model.x, model.info = results, info
     if project_dir is not None:

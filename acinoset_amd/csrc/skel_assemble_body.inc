@@ -6,6 +6,10 @@
 // With ACINO_SKEL_FISHER 1 (k_skel_cov_assemble*, skel_cov.hip; the solve's kernels leave it undefined and compile to what they
 // were) the block that goes to H is the Fisher information J^T diag(w^2) J of the stated Laplace model instead of the IRLS
 // curvature - g, hd and the cost stay the solver's own, they feed its pin rule - and the link operators go to opv_out.
+// With ACINO_SKEL_ROBUST 1 (k_skel_assemble_redesc*, k_skel_cov_assemble_redesc*; undefined or 0 the kernels compile to what
+// they were) the measurement loss is the redescending rho of common.hpp on the same scaled residual e: cost rho(e), gradient
+// w rho'(|e|) sign(e), curvature w^2 h(e) with the clipped secant h - and under ACINO_SKEL_FISHER that curvature, not w^2, is
+// what goes to H.  A dropped row (w = 0) contributes nothing, as under L1.
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const SkelDev& D = *dev;
   const int tid = threadIdx.x, n = blockIdx.x;
@@ -107,17 +111,31 @@
       double uv[2], Jc[2][3];
       pinhole_project<JAC>(cam, xc, yc, zc, uv, Jc);
       const double eu = w * (uv[0] - um), ev = w * (uv[1] - vm);
+#if defined(ACINO_SKEL_ROBUST) && ACINO_SKEL_ROBUST
+      double rho_u, rho_v, drho_u = 0, drho_v = 0, h_u = 0, h_v = 0;
+      redescending<JAC>(D.loss, eu, rho_u, drho_u, h_u);
+      redescending<JAC>(D.loss, ev, rho_v, drho_v, h_v);
+      my_cost = rho_u + rho_v;
+#else
       my_cost = fabs(eu) + fabs(ev);
+#endif
       if (JAC) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           ju[j] = Jc[0][0] * cam.R[j] + Jc[0][1] * cam.R[3 + j] + Jc[0][2] * cam.R[6 + j];
           jv[j] = Jc[1][0] * cam.R[j] + Jc[1][1] * cam.R[3 + j] + Jc[1][2] * cam.R[6 + j];
         }
+#if defined(ACINO_SKEL_ROBUST) && ACINO_SKEL_ROBUST
+        gu = w * drho_u * (eu > 0 ? 1.0 : (eu < 0 ? -1.0 : 0.0));
+        gv = w * drho_v * (ev > 0 ? 1.0 : (ev < 0 ? -1.0 : 0.0));
+        hu = w * w * h_u;
+        hv = w * w * h_v;
+#else
         gu = w * (eu > 0 ? 1.0 : (eu < 0 ? -1.0 : 0.0));
         gv = w * (ev > 0 ? 1.0 : (ev < 0 ? -1.0 : 0.0));
         hu = w * w / fmax(fabs(eu), D.l1_eps);
         hv = w * w / fmax(fabs(ev), D.l1_eps);
+#endif
       }
     }
 #else
@@ -130,7 +148,14 @@
       const double poly = 1 + th2 * (cam.k1 + th2 * (cam.k2 + th2 * (cam.k3 + th2 * cam.k4)));
       const double thD = th * poly, m = thD * ir;
       const double eu = w * (cam.fx * a * m + cam.cx - um), ev = w * (cam.fy * b * m + cam.cy - vm);
+#if defined(ACINO_SKEL_ROBUST) && ACINO_SKEL_ROBUST
+      double rho_u, rho_v, drho_u = 0, drho_v = 0, h_u = 0, h_v = 0;
+      redescending<JAC>(D.loss, eu, rho_u, drho_u, h_u);
+      redescending<JAC>(D.loss, ev, rho_v, drho_v, h_v);
+      my_cost = rho_u + rho_v;
+#else
       my_cost = fabs(eu) + fabs(ev);
+#endif
       if (JAC) {
         const double dthD = 1 + th2 * (3 * cam.k1 + th2 * (5 * cam.k2 + th2 * (7 * cam.k3 + th2 * 9 * cam.k4)));
         const double dm_dr = (dthD / (1 + r2) * r - thD) * (ir * ir);
@@ -144,10 +169,17 @@
           ju[j] = uc0 * cam.R[j] + uc1 * cam.R[3 + j] + uc2 * cam.R[6 + j];
           jv[j] = vc0 * cam.R[j] + vc1 * cam.R[3 + j] + vc2 * cam.R[6 + j];
         }
+#if defined(ACINO_SKEL_ROBUST) && ACINO_SKEL_ROBUST
+        gu = w * drho_u * (eu > 0 ? 1.0 : (eu < 0 ? -1.0 : 0.0));
+        gv = w * drho_v * (ev > 0 ? 1.0 : (ev < 0 ? -1.0 : 0.0));
+        hu = w * w * h_u;
+        hv = w * w * h_v;
+#else
         gu = w * (eu > 0 ? 1.0 : (eu < 0 ? -1.0 : 0.0));
         gv = w * (ev > 0 ? 1.0 : (ev < 0 ? -1.0 : 0.0));
         hu = w * w / fmax(fabs(eu), D.l1_eps);
         hv = w * w / fmax(fabs(ev), D.l1_eps);
+#endif
       }
     }
 #endif
@@ -162,7 +194,12 @@
       hwr[r0] = hu;
       hwr[r0 + 1] = hv;
 #if defined(ACINO_SKEL_FISHER) && ACINO_SKEL_FISHER
+#if defined(ACINO_SKEL_ROBUST) && ACINO_SKEL_ROBUST
+      fwr[r0] = hu;                        // w^2 h(e): the Gauss-Newton curvature of the stated objective, u and v separately
+      fwr[r0 + 1] = hv;
+#else
       fwr[r0] = fwr[r0 + 1] = w * w;
+#endif
 #endif
     }
   }

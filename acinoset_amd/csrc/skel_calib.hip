@@ -407,6 +407,8 @@ int acino_skel_fte_calibration_sensitivity(const acino_skel_fte_params* p, int n
                                            uint8_t* d_unobserved) {
   int rc = skel_check_batch(p, n_clips, true, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws);
   if (rc) return rc;
+  // (the cross term G carries the Fisher weights w^2 of the L1 model; its counterpart under the redescending loss is not built)
+  ACINO_REQUIRE(p->loss == ACINO_SKEL_LOSS_L1, "the calibration sensitivity is defined for the L1 loss only (loss = redescending)");
   ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
   ACINO_REQUIRE(d_sens || d_cov_x_cal || d_cov_pos_cal || d_std_pos_cal,
                 "at least one of d_sens, d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal");

@@ -12,6 +12,11 @@
 // Bound-active variables are pinned exactly as the solver pins them - skel_fixed(x, g, hd, lo, hi) with the solver's own
 // gradient g (L1 + smoothness) and IRLS diagonal hd at x: row and column zeroed, diagonal 1 - and their rows and columns are
 // exactly 0 in every output.
+// Under the redescending loss (acino_skel_fte_params::loss; k_skel_cov_assemble_redesc[_pinhole]) the blocks are
+// sum w^2 h(e) J^T J: the Gauss-Newton curvature of the stated objective at x, fte_cov.hip's definition.  The loss is e^2 / 2 in
+// its core (Gaussian noise of scale 1 / w, h = 1) and constant beyond c (h = 0): a detection the solve has rejected adds no
+// information, and the matrix depends on the residuals.  Kept rows, pins, factorisation and outputs are the same; the
+// observability pass stays on w^2 (a row is observed whatever its h).
 //   k_skel_cov_assemble[_pinhole]  one workgroup per frame: the assembly body with ACINO_SKEL_FISHER: H_F, g, hd, link operators
 //   k_skel_cov_build               k_skel_build at lam = 0 with H_F for H: band blocks, pin mask, the original diagonal
 //   k_skel_selinv<PT>              ONE workgroup per clip.  Forward: the banded block Cholesky of k_skel_solve (panel in LDS,
@@ -83,6 +88,34 @@ k_skel_cov_assemble_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __r
 #include "skel_assemble_body.inc"
 #undef ACINO_SKEL_PINHOLE
 }
+// The same two under the redescending loss: the block that goes to H is the Gauss-Newton curvature sum w^2 h(e) J^T J of the
+// stated objective (fte_cov.hip's definition; unlike the L1 Fisher block it depends on the residuals), g / hd / cost the robust
+// solver's own.
+#define ACINO_SKEL_ROBUST 1
+__global__ void __launch_bounds__(256)
+k_skel_cov_assemble_redesc(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
+                           const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
+                           const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1,
+                           double* __restrict__ g0, double* __restrict__ g1, double* __restrict__ hd0, double* __restrict__ hd1,
+                           double* __restrict__ c0, double* __restrict__ c1, double* __restrict__ opv_out) {
+  constexpr bool JAC = true;
+#define ACINO_SKEL_PINHOLE 0
+#include "skel_assemble_body.inc"
+#undef ACINO_SKEL_PINHOLE
+}
+__global__ void __launch_bounds__(256)
+k_skel_cov_assemble_redesc_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
+                                   const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
+                                   const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1,
+                                   double* __restrict__ g0, double* __restrict__ g1, double* __restrict__ hd0,
+                                   double* __restrict__ hd1, double* __restrict__ c0, double* __restrict__ c1,
+                                   double* __restrict__ opv_out) {
+  constexpr bool JAC = true;
+#define ACINO_SKEL_PINHOLE 1
+#include "skel_assemble_body.inc"
+#undef ACINO_SKEL_PINHOLE
+}
+#undef ACINO_SKEL_ROBUST
 #undef ACINO_SKEL_FISHER
 
 // ---- the host half of a SkelDev (everything before the camera records, 2.9 KB) by value in the kernel-argument segment:
@@ -93,9 +126,16 @@ struct SkelDevHead {
 };
 static_assert(offsetof(SkelDev, cams) % 8 == 0 && sizeof(SkelDevHead) == offsetof(SkelDev, cams) && sizeof(SkelDevHead) <= 3584,
               "SkelDev's host half as a kernel argument");
-__global__ void __launch_bounds__(256) k_skel_dev_store(SkelDevHead a, SkelDev* __restrict__ out) {
+// (the loss record sits behind the camera records, so that every offset before it stayed: it travels as a second argument)
+struct SkelDevTail {
+  unsigned long long w[(sizeof(SkelDev) - offsetof(SkelDev, loss)) / 8];
+};
+static_assert(offsetof(SkelDev, loss) % 8 == 0 && sizeof(SkelDevTail) == sizeof(SkelDev) - offsetof(SkelDev, loss),
+              "SkelDev's loss record as a kernel argument");
+__global__ void __launch_bounds__(256) k_skel_dev_store(SkelDevHead a, SkelDevTail t, SkelDev* __restrict__ out) {
   unsigned long long* o = reinterpret_cast<unsigned long long*>(out);
   for (int e = threadIdx.x; e < (int)(sizeof(SkelDevHead) / 8); e += 256) o[e] = a.w[e];
+  for (int e = threadIdx.x; e < (int)(sizeof(SkelDevTail) / 8); e += 256) o[offsetof(SkelDev, loss) / 8 + e] = t.w[e];
 }
 
 // ---- which states does the clip observe?  One wave per clip, lane p = active state p.  H: the Fisher blocks [NT][P][P] of an
@@ -431,7 +471,9 @@ int skel_upload(const SkelDev& h, const double* d_cams, int camera_model, SkelDe
                 hipStream_t s) {
   SkelDevHead head;
   memcpy(&head, &h, sizeof(head));
-  hipLaunchKernelGGL(k_skel_dev_store, dim3(1), dim3(256), 0, s, head, d_dev);
+  SkelDevTail tail;
+  memcpy(&tail, &h.loss, sizeof(tail));
+  hipLaunchKernelGGL(k_skel_dev_store, dim3(1), dim3(256), 0, s, head, tail, d_dev);
   ACINO_LAUNCH_CHECK();
   const bool pinhole = camera_model == 1;
   ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + (pinhole ? offsetof(SkelDev, pins) : offsetof(SkelDev, cams)),
@@ -474,18 +516,21 @@ static int skel_cov_assemble_at(const SkelDev& h, int n_clips, int camera_model,
   const size_t NT = (size_t)h.n_frames * n_clips;
   const size_t lds_asm = skel_assemble_lds(h.n_rows, h.n_act) + sizeof(double) * h.n_rows;      // + the Fisher weights
   ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
+  using AssembleKernel = decltype(&k_skel_cov_assemble);
+  const AssembleKernel assembly[2][2] = {{k_skel_cov_assemble, k_skel_cov_assemble_pinhole},      // [loss][camera model]
+                                         {k_skel_cov_assemble_redesc, k_skel_cov_assemble_redesc_pinhole}};
   static PerDeviceOnce attr;
   if (attr.first())
-    for (int model = 0; model < 2; ++model)
-      ACINO_HIP_CHECK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(skel_camera_kernel(model, k_skel_cov_assemble, k_skel_cov_assemble_pinhole)),
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (const auto& loss : assembly)
+      for (AssembleKernel k : loss)
+        ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   char* base = (char*)d_ws;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   int rc;
   if ((rc = skel_upload(h, d_cams, camera_model, d_dev, d_clip, n_clips, s))) return rc;
-  hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_cov_assemble, k_skel_cov_assemble_pinhole), dim3((unsigned)NT),
+  const AssembleKernel* by_model = assembly[h.loss_kind == ACINO_SKEL_LOSS_REDESCENDING];
+  hipLaunchKernelGGL(skel_camera_kernel(camera_model, by_model[0], by_model[1]), dim3((unsigned)NT),
                      dim3(256), lds_asm, s, d_dev, d_clip, 0, d_x, d_x, d_meas, d_w, D(lay.H), D(lay.H), D(lay.g), D(lay.g), D(lay.hd),
                      D(lay.hd), D(lay.cost), D(lay.cost), D(lay.opv));
   ACINO_LAUNCH_CHECK();
@@ -501,6 +546,7 @@ static int skel_cov_launch_observe(int n_clips, int camera_model, const SkelDev&
   SkelDev* d_dev0 = reinterpret_cast<SkelDev*>((char*)d_ws + dev0_off);
   SkelDev h0 = h;
   h0.q = 0.0;                                                 // H_pp = sum w^2 J^2 + 2 * 0 * b0: the Fisher diagonal itself
+  h0.loss_kind = ACINO_SKEL_LOSS_L1;                          // a row is observed by the kept-row rule, whatever its h: w^2, not w^2 h
   int rc;
   if ((rc = skel_cov_assemble_at(h0, n_clips, camera_model, d_meas, d_w, d_cams, d_x, d_ws, lay, d_dev0, s))) return rc;
   hipLaunchKernelGGL(k_skel_observability, dim3((unsigned)n_clips), dim3(64), 0, s, d_dev0,

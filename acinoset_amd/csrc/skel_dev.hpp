@@ -25,6 +25,8 @@ struct SkelDev {                   // device-resident description of one problem
   unsigned long long pmask[ACINO_SKEL_MAX_OPS + 1];  // per pose slot: the ops on its path from the root
   Cam cams[ACINO_MAX_CAMS];
   Pin pins[ACINO_MAX_CAMS];        // the pinhole model's records (k_skel_assemble_pinhole); appended: the offsets above stay
+  LossC loss;                      // the redescending loss's constants (a, b, c = 3, 10, 20); appended: the offsets above stay
+  int32_t loss_kind, pad1;         // ACINO_SKEL_LOSS_L1 / ACINO_SKEL_LOSS_REDESCENDING: which measurement loss the problem states
 };
 
 struct SkelClip {                  // controller state of one clip (device)
@@ -115,6 +117,7 @@ inline int skel_validate(const acino_skel_fte_params* p) {
   ACINO_REQUIRE(p->n_pose * p->n_cams <= 256, "n_pose * n_cams <= 256");
   ACINO_REQUIRE(p->h > 0 && p->model_weight >= 0 && p->l1_eps > 0, "h > 0, model_weight >= 0, l1_eps > 0");
   ACINO_REQUIRE(p->lam0 > 0 && p->max_iter >= 0, "lam0 > 0, max_iter >= 0");
+  ACINO_REQUIRE(p->loss == ACINO_SKEL_LOSS_L1 || p->loss == ACINO_SKEL_LOSS_REDESCENDING, "loss: 0 L1, 1 redescending");
   return ACINO_OK;
 }
 
@@ -133,6 +136,8 @@ inline int skel_program(const acino_skel_fte_params* p, const acino_skel_op* h_o
   h.q = p->model_weight / (p->h * p->h * p->h * p->h);
   h.l1_eps = p->l1_eps;
   h.lam_floor = DIAG_FLOOR;
+  h.loss = make_loss(3.0, 10.0, 20.0);                       // the reference's only call (build.py:307); the scale is r_meas
+  h.loss_kind = p->loss;
   ACINO_REQUIRE(h_active[0] == 0 && h_active[1] == 1 && h_active[2] == 2, "the first three active states are x, y, z");
   std::vector<int> where(3 + 3 * L, -1);
   for (int a = 0; a < P; ++a) {

@@ -15,6 +15,8 @@
 // atomics.  LDS: SKR_FPB * (64 * 3 + 65 * 3) doubles = 24.2 KB whatever the skeleton (six workgroups per CU by LDS; the
 // register count decides).  A streaming kernel: 24 B of detection and weight and the slot's 72 B of cov_pos (shared by the C
 // cameras through the cache) in, up to 81 B out per entry, a few hundred fp64 operations with one atan in between.
+// acino_skel_fte_reprojection_weights adds the curvature weights of the params block's loss (16 B per entry more; under the
+// redescending loss two exp per weighted entry).
 #include "skel_host.hpp"
 
 namespace acino {
@@ -28,12 +30,16 @@ struct SkelReprojArgs {            // by value in the kernel-argument segment (l
 };
 static_assert(sizeof(SkelReprojArgs) <= 3072, "the kernel-argument segment holds 4 KB");
 
-template <bool PINHOLE>
+// ROBUST (acino_skel_fte_params::loss = ACINO_SKEL_LOSS_REDESCENDING): weight_out takes the curvature weight h(w res_d) the
+// robust solve gives each component of a weighted detection (fte_reproj.hip's `weight`), and the gating distance uses the
+// Gaussian core of that loss - rho(e) = e^2 / 2 near 0: noise of scale 1 / w, variance 1 / w^2 - in place of the Laplace
+// variance 2 / w^2.  Without it weight_out, when asked for, is 1 for a weighted detection: L1 rejects nothing.
+template <bool PINHOLE, bool ROBUST = false>
 __global__ void __launch_bounds__(256)
 k_skel_reproj(const SkelReprojArgs A, long long n_total, const double* __restrict__ meas, const double* __restrict__ wgt,
               const double* __restrict__ cams, const double* __restrict__ x, const double* __restrict__ cov_pos, double gate_w,
               double* __restrict__ uv_out, double* __restrict__ cov_out, double* __restrict__ res_out,
-              double* __restrict__ m2_out, uint8_t* __restrict__ flags_out) {
+              double* __restrict__ m2_out, uint8_t* __restrict__ flags_out, const LossC loss, double* __restrict__ weight_out) {
   __shared__ double opv[SKR_FPB][ACINO_SKEL_MAX_OPS][3];          // M off of every op
   __shared__ double pos[SKR_FPB][ACINO_SKEL_MAX_OPS + 1][3];      // poses
   const int tid = threadIdx.x;
@@ -94,6 +100,7 @@ k_skel_reproj(const SkelReprojArgs A, long long n_total, const double* __restric
     const bool behind = zc < 1e-6, sing = fabs(zc) < 1e-9;
     const bool weighted = w != 0.0 && finite && !sing;            // the assembly's rule (skel_assemble_body.inc)
     double u = nan, v = nan, ru = nan, rv = nan, m2 = nan, s00 = nan, s01 = nan, s11 = nan;
+    double hu = weighted ? 1.0 : 0.0, hv = hu;
     if (!sing) {
       double jc[2][3];
       if (PINHOLE) {
@@ -110,6 +117,11 @@ k_skel_reproj(const SkelReprojArgs A, long long n_total, const double* __restric
       if (finite) {
         ru = u - um;
         rv = v - vm;
+      }
+      if (ROBUST && weighted) {
+        double rho, drho;
+        redescending<true>(loss, w * (u - um), rho, drho, hu);
+        redescending<true>(loss, w * (v - vm), rho, drho, hv);
       }
       const double wg = w > 0.0 ? w : gate_w;
       if (cov_pos) {
@@ -129,11 +141,11 @@ k_skel_reproj(const SkelReprojArgs A, long long n_total, const double* __restric
         s00 = ju[0] * tu[0] + ju[1] * tu[1] + ju[2] * tu[2];
         s11 = jv[0] * tv[0] + jv[1] * tv[1] + jv[2] * tv[2];
         s01 = 0.5 * ((ju[0] * tv[0] + ju[1] * tv[1] + ju[2] * tv[2]) + (jv[0] * tu[0] + jv[1] * tu[1] + jv[2] * tu[2]));
-        const double r2 = 2.0 / (wg * wg);                         // variance of Laplace noise of scale 1 / wg
+        const double r2 = (ROBUST ? 1.0 : 2.0) / (wg * wg);        // variance of Laplace noise of scale 1 / wg (ROBUST: Gaussian)
         const double a00 = s00 + r2, a11 = s11 + r2;
         m2 = (a11 * ru * ru - 2.0 * s01 * ru * rv + a00 * rv * rv) / (a00 * a11 - s01 * s01);
       } else {
-        m2 = (ru * ru + rv * rv) * (0.5 * wg * wg);
+        m2 = (ru * ru + rv * rv) * ((ROBUST ? 1.0 : 0.5) * wg * wg);
       }
     }
     if (uv_out) {
@@ -152,6 +164,10 @@ k_skel_reproj(const SkelReprojArgs A, long long n_total, const double* __restric
     }
     if (m2_out) m2_out[e] = m2;
     if (flags_out) flags_out[e] = (uint8_t)((weighted ? 1 : 0) | (behind ? 2 : 0) | (sing ? 4 : 0));
+    if (weight_out) {
+      weight_out[2 * e] = hu;
+      weight_out[2 * e + 1] = hv;
+    }
   }
 }
 
@@ -159,16 +175,16 @@ k_skel_reproj(const SkelReprojArgs A, long long n_total, const double* __restric
 
 using namespace acino;
 
-extern "C" {
-
-int acino_skel_fte_reprojection(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
-                                const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
-                                const double* d_x, const double* d_cov_pos, double gate_w, double* d_uv, double* d_cov_uv,
-                                double* d_res, double* d_mahal2, uint8_t* d_flags, void* stream) {
+// the body of both entries (d_weight: NULL from the entry without it)
+static int skel_reproject(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                          const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                          const double* d_x, const double* d_cov_pos, double gate_w, double* d_uv, double* d_cov_uv,
+                          double* d_res, double* d_mahal2, uint8_t* d_flags, double* d_weight, void* stream) {
   int rc = skel_check_batch(p, n_clips, false, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_x);
   if (rc) return rc;
   ACINO_REQUIRE(gate_w > 0 && gate_w <= 1.79769313486231570e308, "gate_w > 0 and finite");
-  ACINO_REQUIRE(d_uv || d_cov_uv || d_res || d_mahal2 || d_flags, "no output: at least one of d_uv, d_cov_uv, d_res, d_mahal2, d_flags");
+  ACINO_REQUIRE(d_uv || d_cov_uv || d_res || d_mahal2 || d_flags || d_weight,
+                "no output: at least one of d_uv, d_cov_uv, d_res, d_mahal2, d_flags");
   ACINO_REQUIRE(!d_cov_uv || d_cov_pos, "d_cov_uv needs d_cov_pos");
   const long long NT = (long long)p->n_frames * n_clips;      // frames of all clips
   SkelDev h;                                                 // (the host half of the record: the checks of skel_program)
@@ -182,10 +198,31 @@ int acino_skel_fte_reprojection(const acino_skel_fte_params* p, int n_clips, int
   memcpy(a.op, h.op, sizeof(a.op));
   memcpy(a.amap, h.amap, sizeof(a.amap));
   const unsigned nb = (unsigned)((NT + SKR_FPB - 1) / SKR_FPB);
-  hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_reproj<false>, k_skel_reproj<true>), dim3(nb), dim3(256), 0,
-                     (hipStream_t)stream, a, NT, d_meas, d_w, d_cams, d_x, d_cov_pos, gate_w, d_uv, d_cov_uv, d_res, d_mahal2, d_flags);
+  const auto kernel = p->loss == ACINO_SKEL_LOSS_REDESCENDING
+                          ? skel_camera_kernel(camera_model, k_skel_reproj<false, true>, k_skel_reproj<true, true>)
+                          : skel_camera_kernel(camera_model, k_skel_reproj<false>, k_skel_reproj<true>);
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, NT, d_meas, d_w, d_cams, d_x, d_cov_pos, gate_w, d_uv,
+                     d_cov_uv, d_res, d_mahal2, d_flags, h.loss, d_weight);
   ACINO_LAUNCH_CHECK();
   return ACINO_OK;
+}
+
+extern "C" {
+
+int acino_skel_fte_reprojection(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                const double* d_x, const double* d_cov_pos, double gate_w, double* d_uv, double* d_cov_uv,
+                                double* d_res, double* d_mahal2, uint8_t* d_flags, void* stream) {
+  return skel_reproject(p, n_clips, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_x, d_cov_pos, gate_w, d_uv, d_cov_uv, d_res,
+                        d_mahal2, d_flags, nullptr, stream);
+}
+
+int acino_skel_fte_reprojection_weights(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                        const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                        const double* d_x, const double* d_cov_pos, double gate_w, double* d_uv, double* d_cov_uv,
+                                        double* d_res, double* d_mahal2, uint8_t* d_flags, double* d_weight, void* stream) {
+  return skel_reproject(p, n_clips, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_x, d_cov_pos, gate_w, d_uv, d_cov_uv, d_res,
+                        d_mahal2, d_flags, d_weight, stream);
 }
 
 }  // extern "C"

@@ -585,10 +585,20 @@ int acino_skeleton_fk(const double* d_q, int64_t n_frames, int n_angles, int n_p
  * d_x[N][n_active]: initial iterate in, solution out.  d_pos[N][n_pose][3] (may be NULL): poses of the solution.
  * Solved by the projected Levenberg-Marquardt of the cheetah path (L1 loss: IRLS curvature w^2 / max(|e|, l1_eps), cost
  * and gradient those of |e|); the controller runs on the device (one status word per clip read back per iteration).
- * Limits: n_active <= 64, 2 n_pose C <= 256. */
+ * Limits: n_active <= 64, 2 n_pose C <= 256.
+ * The measurement loss is the params block's `loss`, read by EVERY acino_skel_fte_* entry.  ACINO_SKEL_LOSS_L1 (0) is the problem
+ * above.  ACINO_SKEL_LOSS_REDESCENDING replaces |e| by the reference's redescending_loss rho(e) (build.py:382-395, commented out at
+ * :307) with its only constants a, b, c = 3, 10, 20 in scaled residual units (the scale is the caller's 1 / w): cost sum rho(e)
+ * over the kept rows, d cost / d e = rho'(|e|) sign(e), Gauss-Newton curvature w^2 h(e) with h = clip((rho'(e) - rho'(0+)) / e,
+ * 0, 1) - the loss and the conventions of acino_fte_*; l1_eps is then not read.  Prior, bounds, pin rule, controller and
+ * factorisation are the same.  From a far start every residual lies beyond c, where rho is constant: the solve is meant to start
+ * at the L1 solution (build.solve_models does that).  Any other value of `loss` is ACINO_ERR_INVALID_ARG. */
+#define ACINO_SKEL_LOSS_L1 0
+#define ACINO_SKEL_LOSS_REDESCENDING 1
 typedef struct acino_skel_fte_params {
   int32_t n_frames, n_cams, n_pose, n_ops, n_angles, n_active;
-  int32_t max_iter, pad0;
+  int32_t max_iter;
+  int32_t loss;               /* ACINO_SKEL_LOSS_L1 (0: what the field held while it was reserved) or _REDESCENDING */
   double h;                   /* time step (build.py:131: 1/120)                           */
   double model_weight;        /* build.py:186-191: 0.002 for every state                    */
   double l1_eps;              /* floor of |e| in the IRLS weight (scaled residual units)     */
@@ -649,7 +659,12 @@ int acino_skel_fte_solve_batch_pinhole(const acino_skel_fte_params* p, int n_cli
  * workspace is the caller's, 256-byte aligned (ACINO_ERR_WORKSPACE otherwise).  A pivot that is not above zero (a state observed
  * in no frame of the clip) makes the clip singular: h_status[b] = 5 (else 0) and its outputs are NaN; with n_clips > 1 and
  * h_status given the call returns ACINO_OK and the other clips stand, otherwise ACINO_ERR_NUMERIC.  One stream synchronisation,
- * to read the status words.  One workgroup per clip walks the factorisation and the Takahashi recursion: meant for batches. */
+ * to read the status words.  One workgroup per clip walks the factorisation and the Takahashi recursion: meant for batches.
+ * With p->loss = ACINO_SKEL_LOSS_REDESCENDING the blocks are sum w^2 h(e) J^T J - the Gauss-Newton curvature of the stated
+ * objective at d_x, the definition of acino_fte_covariance: a detection the loss rejects (h ~ 0) adds nothing, and unlike the L1
+ * Fisher matrix A depends on the residuals.  Which rows are kept, the pin rule (with the robust solver's own g and diagonal),
+ * the outputs and the status rules are the same, and so they are for acino_skel_fte_sample*, _covariance_pinned and
+ * _covariance_rates; acino_skel_fte_observability and pin_unobserved go by the kept rows (w^2), whatever their h. */
 size_t acino_skel_fte_covariance_workspace_bytes(const acino_skel_fte_params* p, int n_clips);
 int acino_skel_fte_covariance(const acino_skel_fte_params* p, int n_clips, int camera_model /* 0 fisheye: d_cams24, 1 pinhole: d_cams32 */,
                               const acino_skel_op* h_ops, const int32_t* h_active, const double* d_meas, const double* d_w,
@@ -810,7 +825,9 @@ int acino_skel_fte_covariance_rates(const acino_skel_fte_params* p, int n_clips,
  * `stream`: the Fisher assembly and build of the covariance, k_skel_calib_rhs (-G as 6C columns), k_skel_factor, one forward
  * (k_skel_fwdsub) and one backward substitution per clip and panel of 64 columns, k_skel_calib_combine; one synchronisation.
  * Workspace: the pinned covariance workspace plus two column buffers [n_clips][6C][N][n_active], 256-byte aligned
- * (ACINO_ERR_WORKSPACE otherwise); the query returns 0 outside the limits. */
+ * (ACINO_ERR_WORKSPACE otherwise); the query returns 0 outside the limits.
+ * Defined for the L1 loss only: with p->loss != ACINO_SKEL_LOSS_L1 the call returns ACINO_ERR_INVALID_ARG (the message names the
+ * loss) before any device call. */
 size_t acino_skel_fte_calibration_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved);
 int acino_skel_fte_calibration_sensitivity(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
                                            const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
@@ -858,6 +875,17 @@ int acino_skel_fte_reprojection(const acino_skel_fte_params* p, int n_clips, int
                                 const double* d_cams, const double* d_x,
                                 const double* d_cov_pos /* [n_clips][N][n_pose][3][3] or NULL */, double gate_w, double* d_uv,
                                 double* d_cov_uv, double* d_res, double* d_mahal2, uint8_t* d_flags, void* stream);
+/* The same call with one more output, which may be NULL (and counts as an output):
+ *   d_weight[..][2]     the curvature weight of each component of the detection under the params block's loss: with
+ *                       ACINO_SKEL_LOSS_REDESCENDING h(w res_d) in [0, 1] for a row the assembly weights (bit 0 of the flags) - 1: the
+ *                       detection counts fully, ~0: the solve has rejected it - and 0 otherwise; with ACINO_SKEL_LOSS_L1 1 for a
+ *                       weighted row (L1 rejects nothing) and 0 otherwise.
+ * Under ACINO_SKEL_LOSS_REDESCENDING BOTH entries use the noise variance 1 / wg^2 in d_mahal2 in place of 2 / wg^2 (the loss is
+ * e^2 / 2 in its core: Gaussian noise of scale 1 / w); without d_cov_pos: res^T res wg^2.  Everything else is as above. */
+int acino_skel_fte_reprojection_weights(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                        const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                        const double* d_x, const double* d_cov_pos, double gate_w, double* d_uv, double* d_cov_uv,
+                                        double* d_res, double* d_mahal2, uint8_t* d_flags, double* d_weight, void* stream);
 
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
