@@ -324,12 +324,22 @@
           for (int r = 0; r < 4; ++r) {
             const int row = 16 * ti + lk + 4 * r;
             P[row * PLD + colB] = acc[q][r];
-            if (row < ES && colB < ES) P_est[(size_t)f * ES * ES + row * ES + colB] = acc[q][r];   // the smoother's input
           }
         }
       }
     }
     if (tid < ES) x_est[(size_t)f * ES + tid] = xs[tid];
+    __syncthreads();
+    // P - V Ptop is symmetric only in exact arithmetic: where the prior collapses the two triangles come out 1e-8 apart
+    // (relative to sqrt(P_ii P_jj)).  Both Cholesky factorisations, here and in the smoother, read the lower triangle
+    // while the products read whole rows and columns, so the filter would go on with two different matrices.  The lower
+    // triangle is the covariance: mirror it, and store that as the smoother's input.
+    for (int e = tid; e < ES * ES; e += 256) {
+      const int r = e / ES, c = e % ES;
+      const double v = r < c ? P[c * PLD + r] : P[r * PLD + c];
+      if (r < c) P[r * PLD + c] = v;       // (upper entries are only written, lower ones only read: no order needed)
+      P_est[(size_t)f * ES * ES + e] = v;
+    }
     __syncthreads();
   }
   // outlier count: one pair per thread per frame

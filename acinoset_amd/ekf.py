@@ -60,12 +60,49 @@ def initial_state(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, start_frame=
     return s
 
 
+def _a256(v):
+    return (v + 255) // 256 * 256
+
+
+def workspace_layout(n_frames, n_seq):
+    """The read-back contract of the workspace after a successful ``acino_ekf_run`` (include/acinoset_hip.h, EKF section):
+    name -> (byte offset, shape) of the three float64 arrays the kernels leave there, each rounded up to 256 bytes -
+    ``P_est`` [n_seq, N, 75, 75], ``rts_gain_T`` [n_seq, N, 75, 75] (the smoother gains, stored TRANSPOSED, written for the
+    frames 1 .. N-2 only) and ``x_pred`` [n_seq, N, 75].  ``private`` is the offset at which the library's own part begins
+    (a second state-sized slot, then 1024 bytes of flags); ``end`` + 1024 = ``acino_ekf_workspace_bytes``."""
+    n = int(n_frames) * int(n_seq)
+    if n_frames < 1 or n_seq < 1:
+        raise ValueError("n_frames and n_seq must be at least 1")
+    mat, vec = _a256(n * N_EKF_STATES * N_EKF_STATES * 8), _a256(n * N_EKF_STATES * 8)
+    shape = (int(n_seq), int(n_frames), N_EKF_STATES)
+    return dict(P_est=(0, shape + (N_EKF_STATES,)), rts_gain_T=(mat, shape + (N_EKF_STATES,)), x_pred=(2 * mat, shape),
+                private=2 * mat + vec, end=2 * mat + 2 * vec)
+
+
+def _read_internals(ws, base, n_frames, n_seq):
+    """x_pred, P_est and the un-transposed smoother gains of one launch from its workspace (``workspace_layout``).  The
+    kernel writes no gain for the frames 0 and N-1 (none at all when N < 3): those are NaN here."""
+    lay = workspace_layout(n_frames, n_seq)
+    arr = {}
+    for name in ("P_est", "rts_gain_T", "x_pred"):
+        off, shape = lay[name]
+        arr[name] = ws[base + off:base + off + int(np.prod(shape)) * 8].cpu().numpy().view(np.float64).reshape(shape)
+    gain = np.ascontiguousarray(np.swapaxes(arr["rts_gain_T"], 2, 3))
+    gain[:, :1] = np.nan
+    gain[:, max(n_frames - 1, 1):] = np.nan
+    return arr["x_pred"], arr["P_est"], gain
+
+
 def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, start_frames=None, states0=None,
-              with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None):
+              with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None, return_internals=False):
     """Filter + smooth several clips of the same rig.  ``dets``: list of det[N_b, C, 20, 3] (x, y, likelihood);
     clips of equal length share one launch.  Returns one result dictionary per clip.  ``camera_model`` "fisheye" (the
     default) or "pinhole", or ``project_func`` = calib.project_points_fisheye / calib.project_points (calib.camera_model_of:
-    a contradiction is a ValueError, any other function NotImplementedError, both before any device work)."""
+    a contradiction is a ValueError, any other function NotImplementedError, both before any device work).
+    ``return_internals`` adds what the kernels left in the workspace (``workspace_layout``): ``x_pred`` [N, 75] the float32-
+    rounded predictions, ``P_est`` [N, 75, 75] the filtered covariances and ``rts_gain`` [N, 75, 75] the smoother gains
+    A_i = P_est[i] F^T inv(P_pred[i+1]) (NaN where the kernel writes none: frames 0 and N-1, every frame when N < 3).  The
+    same launches either way; the internals cost three more read-backs."""
     model = calib.camera_model_of(camera_model, project_func)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -111,6 +148,8 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
         check(run(C.byref(prm), ptr(det), ptr(cams), ptr(st0), C.c_void_p(ws_ptr), nbytes, ptr(est), ptr(smo),
                   C.c_void_p(outl.data_ptr()), stream_ptr()))
         est_h, smo_h, outl_h = est.cpu().numpy(), smo.cpu().numpy(), outl.cpu().numpy()
+        if return_internals:
+            xp_h, pe_h, gain_h = _read_internals(ws, ws_ptr - ws.data_ptr(), n_frames, len(members))
         for j, b in enumerate(members):
             r = dict(x=est_h[j, :, :N_POSE], dx=est_h[j, :, N_POSE:2 * N_POSE], ddx=est_h[j, :, 2 * N_POSE:],
                      smoothed_x=smo_h[j, :, :N_POSE], smoothed_dx=smo_h[j, :, N_POSE:2 * N_POSE],
@@ -118,13 +157,16 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
             if with_positions:
                 r["positions"] = get_3d_marker_coords(r["x"])
                 r["smoothed_positions"] = get_3d_marker_coords(r["smoothed_x"])
+            if return_internals:
+                r.update(x_pred=xp_h[j], P_est=pe_h[j], rts_gain=gain_h[j])
             out[b] = r
     return out
 
 
 def ekf(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, start_frame=0, states0=None,
-        with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None):
-    """One clip: det[N, C, 20, 3] for the frames start_frame .. start_frame + N - 1 (camera model as ``ekf_batch``)."""
+        with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None, return_internals=False):
+    """One clip: det[N, C, 20, 3] for the frames start_frame .. start_frame + N - 1 (camera model and ``return_internals``
+    as ``ekf_batch``)."""
     return ekf_batch([det], k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, [start_frame],
                      None if states0 is None else [states0], with_positions, smoother_pivoting, camera_model=camera_model,
-                     project_func=project_func)[0]
+                     project_func=project_func, return_internals=return_internals)[0]

@@ -894,7 +894,21 @@ int acino_skel_fte_reprojection_weights(const acino_skel_fte_params* p, int n_cl
  * (:700-711), d_est / d_smooth [n_seq][n_frames][75] the filtered and the smoothed states (:848-856 slices them into
  * x, dx, ddx), d_outliers [n_seq] the gated pixel pairs (:818).  Model constants (P0, Q, R, the 3-sigma gate, the
  * forward-difference step 1e-3) are the reference's literals.  The predicted covariances are not stored: the smoother
- * rebuilds P_pred[i+1] = F P_est[i] F^T + Q from the filtered one with the filter's own arithmetic. */
+ * rebuilds P_pred[i+1] = F P_est[i] F^T + Q from the filtered one with the filter's own arithmetic.
+ *
+ * Workspace read-back contract.  After acino_ekf_run / acino_ekf_run_pinhole has returned ACINO_OK, the caller-owned
+ * workspace holds, from its first byte and in this order, three arrays of doubles, each rounded up to a multiple of
+ * 256 bytes (T = n_seq * n_frames):
+ *   P_est  [n_seq][n_frames][75][75]  at 0                     the filtered covariances (:829), exactly symmetric (the lower
+ *                                                              triangle of the update, mirrored)
+ *   A      [n_seq][n_frames][75][75]  at a256(T*75*75*8)       the smoother gains A_i = P_est[i] F^T inv(P_pred[i+1]) (:840),
+ *                                                              each stored TRANSPOSED (element [c][r] is A_i[r][c]) and
+ *                                                              written for the frames 1 .. n_frames-2 only: the slots of
+ *                                                              frame 0 and frame n_frames-1, and every slot when
+ *                                                              n_frames < 3, keep whatever the caller's buffer held
+ *   x_pred [n_seq][n_frames][75]      at 2 * a256(T*75*75*8)   the predicted states, rounded to float32 (:628)
+ * with a256(v) = (v + 255) / 256 * 256.  Everything behind x_pred, from 2 * a256(T*75*75*8) + a256(T*75*8) to
+ * acino_ekf_workspace_bytes, is private to the library and may change without notice. */
 typedef struct acino_ekf_params {
   int64_t n_frames;
   int32_t n_seq;

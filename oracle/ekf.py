@@ -107,7 +107,8 @@ def initial_state(nose_frames, nose_xyz, start_frame, sT):
 def ekf(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, cam_width, states0, keep_cov=False, P_init=None):
     """det[N, C, 20, 3] (x, y, likelihood) for the frames to filter -> dict of x, dx, ddx, smoothed_x, smoothed_dx,
     smoothed_ddx [N, 25] in EKF_ORDER, plus ``outliers_ignored``.  ``P_init`` replaces P0 (used by the one-step
-    checks against the reference's stored per-frame covariances)."""
+    checks against the reference's stored per-frame covariances).  ``keep_cov`` adds P_est, P_pred, x_pred and, per frame,
+    ``gate_margin`` = min_j | |r_j| - 3 sigma_j | / (3 sigma_j): how far the residual nearest to its gate is from it."""
     det = np.asarray(det, dtype=np.float64)
     n_frames, n_cams, n_markers, _ = det.shape
     sT = 1.0 / fps
@@ -126,6 +127,7 @@ def ekf(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, cam_width, states0, ke
     states_pred_hist = states_est_hist.copy()
     P_est_hist = np.zeros((n_frames, N_STATES, N_STATES))
     P_pred_hist = P_est_hist.copy()
+    gate_margin = np.zeros(n_frames)
     outliers_ignored = 0
     for i in range(n_frames):
         acc = states[2 * N_POSE:]
@@ -149,6 +151,7 @@ def ekf(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, cam_width, states0, ke
         residual = z_k - h
         S = (H @ P @ H.T) + R
         temp = sigma_bound * np.sqrt(np.diag(S))
+        gate_margin[i] = np.min(np.abs(np.abs(residual) - temp) / temp)    # distance of the nearest residual from its gate
         for j in range(0, len(residual), 2):
             if np.abs(residual[j]) > temp[j] or np.abs(residual[j + 1]) > temp[j + 1]:
                 residual[j:j + 2] = 0
@@ -166,5 +169,5 @@ def ekf(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, cam_width, states0, ke
                smoothed_x=smooth[:, :N_POSE], smoothed_dx=smooth[:, N_POSE:2 * N_POSE], smoothed_ddx=smooth[:, 2 * N_POSE:],
                outliers_ignored=outliers_ignored)
     if keep_cov:
-        out.update(P_est=P_est_hist, P_pred=P_pred_hist, x_pred=states_pred_hist)
+        out.update(P_est=P_est_hist, P_pred=P_pred_hist, x_pred=states_pred_hist, gate_margin=gate_margin)
     return out
