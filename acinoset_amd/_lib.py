@@ -12,9 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libacinoset_hip.so")
 BUILD_ID_SOURCE = "camera_kernels.hip"      # defines acino_build_id()
-SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_calib.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_calib.hip", "skel_reproj.hip"]
+SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_calib.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "ekf_cov.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_calib.hip", "skel_reproj.hip"]
 HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "fte_cov.hpp", "fte_cov_dev.hpp", "fte_calib.hpp", "fte_reproj.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
-           "pinhole.hpp", "sba_dev.hpp", "sba_host.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "fte_assemble_body.inc", "ekf_forward_body.inc", "skel_assemble_body.inc",
+           "pinhole.hpp", "ekf_dev.hpp", "sba_dev.hpp", "sba_host.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "fte_assemble_body.inc", "ekf_forward_body.inc", "skel_assemble_body.inc",
            os.path.join("..", "..", "include", "acinoset_hip.h")]
 
 ABI_VERSION = 3          # ACINO_ABI_VERSION of include/acinoset_hip.h
@@ -201,6 +201,8 @@ SIGNATURES = {
     "acino_ekf_workspace_bytes": (_Z, [_L, _I]),
     "acino_ekf_run": (_I, [C.POINTER(EkfParams), _P, _P, _P, _P, _Z, _P, _P, _P, _P]),
     "acino_ekf_run_pinhole": (_I, [C.POINTER(EkfParams), _P, _P, _P, _P, _Z, _P, _P, _P, _P]),
+    "acino_ekf_smoothed_covariance": (_I, [C.POINTER(EkfParams), _P, _Z, _P, _P]),
+    "acino_ekf_marker_covariance": (_I, [C.POINTER(EkfParams), _P, _P, _P, _P, _P, _P]),
     "acino_skeleton_fk": (_I, [_P, _L, _I, _I, C.POINTER(SkelOp), _I, _P, _P]),
     "acino_sizeof_skel_fte_params": (_Z, []),
     "acino_sizeof_skel_fte_info": (_Z, []),

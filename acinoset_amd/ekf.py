@@ -93,8 +93,41 @@ def _read_internals(ws, base, n_frames, n_seq):
     return arr["x_pred"], arr["P_est"], gain
 
 
+def _check_return_cov(return_cov):
+    """False, "bars" or True -> None, "bars" or "full"; anything else is a ValueError (before any device work)."""
+    if isinstance(return_cov, (bool, np.bool_)):
+        return "full" if return_cov else None
+    if isinstance(return_cov, str) and return_cov == "bars":
+        return "bars"
+    raise ValueError(f'return_cov must be False, True or "bars", not {return_cov!r}')
+
+
+def _covariances(prm, ws_ptr, nbytes, est, smo, full):
+    """The covariance pass of one launch (csrc/ekf_cov.hip) on the workspace ``acino_ekf_run`` has just filled: the smoothed
+    covariances by the second half of Rauch-Tung-Striebel, then the marker bars of (est, P_est) and (smo, P_s).  Returns
+    host arrays keyed as the result dictionary, each with the leading axis of the launch's sequences."""
+    n_seq, n_frames = est.shape[0], est.shape[1]
+    ps = torch.empty((n_seq, n_frames, N_EKF_STATES, N_EKF_STATES), dtype=torch.float64, device=est.device)
+    check(lib().acino_ekf_smoothed_covariance(C.byref(prm), C.c_void_p(ws_ptr), nbytes, ptr(ps), stream_ptr()))
+    out = {}
+    for prefix, states, cov_ptr in (("", est, C.c_void_p(ws_ptr)), ("smoothed_", smo, ptr(ps))):
+        cov_pos = torch.empty((n_seq, n_frames, 20, 3, 3), dtype=torch.float64, device=est.device)
+        std_pos = torch.empty((n_seq, n_frames, 20), dtype=torch.float64, device=est.device)
+        std_state = torch.empty((n_seq, n_frames, N_EKF_STATES), dtype=torch.float64, device=est.device)
+        check(lib().acino_ekf_marker_covariance(C.byref(prm), ptr(states), cov_ptr, ptr(cov_pos), ptr(std_pos), ptr(std_state),
+                                                stream_ptr()))
+        std_h = std_state.cpu().numpy()
+        out[prefix + "std_x"], out[prefix + "std_dx"], out[prefix + "std_ddx"] = (
+            std_h[..., :N_POSE], std_h[..., N_POSE:2 * N_POSE], std_h[..., 2 * N_POSE:])
+        out[prefix + "cov_positions"], out[prefix + "std_positions"] = cov_pos.cpu().numpy(), std_pos.cpu().numpy()
+    if full:
+        out["smoothed_cov"] = ps.cpu().numpy()
+    return out
+
+
 def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, start_frames=None, states0=None,
-              with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None, return_internals=False):
+              with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None, return_internals=False,
+              return_cov=False):
     """Filter + smooth several clips of the same rig.  ``dets``: list of det[N_b, C, 20, 3] (x, y, likelihood);
     clips of equal length share one launch.  Returns one result dictionary per clip.  ``camera_model`` "fisheye" (the
     default) or "pinhole", or ``project_func`` = calib.project_points_fisheye / calib.project_points (calib.camera_model_of:
@@ -102,7 +135,25 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
     ``return_internals`` adds what the kernels left in the workspace (``workspace_layout``): ``x_pred`` [N, 75] the float32-
     rounded predictions, ``P_est`` [N, 75, 75] the filtered covariances and ``rts_gain`` [N, 75, 75] the smoother gains
     A_i = P_est[i] F^T inv(P_pred[i+1]) (NaN where the kernel writes none: frames 0 and N-1, every frame when N < 3).  The
-    same launches either way; the internals cost three more read-backs."""
+    same launches either way; the internals cost three more read-backs.
+
+    ``return_cov`` = "bars" adds the error bars of both state sequences (csrc/ekf_cov.hip, one more pass over the same
+    workspace; everything above is bit for bit what it is without the flag): ``std_x``, ``std_dx``, ``std_ddx`` [N, 25] =
+    sqrt(diag) of the filtered covariance, ``cov_positions`` [N, 20, 3, 3] = J P[:25, :25] J^T with J the analytic Jacobian
+    of the marker positions at ``x`` and ``std_positions`` [N, 20] = sqrt(trace) of it (metres; the definition of the FTE's
+    ``std_positions``), and the same five with the prefix ``smoothed_`` from the smoothed covariance
+    P_s[i] = P_est[i] + A_i (P_s[i+1] - P_pred[i+1]) A_i^T at ``smoothed_x``.  ``return_cov=True`` adds ``cov`` and
+    ``smoothed_cov`` [N, 75, 75] on top.  Any other value is a ValueError.  Three things to know about these bars:
+
+    * they are the filter's OWN belief under the reference's literal constants - a measurement sigma of 25 px per
+      coordinate (R = 25^2 px^2), ``camera_resolution[0]`` px under the likelihood threshold, the process noise of
+      ``qb_list`` - not a calibrated detector noise;
+    * the 3-sigma gate does not change them: a gated pair has its residual zeroed, the gain and (I - K H) P keep its rows;
+    * frames 0 and N-1 carry the filtered covariance (``smoothed_cov[i]`` == ``cov[i]`` there, every frame when N < 3),
+      because the reference's smoother returns the filtered state at both ends.
+
+    Bars of the marker velocities are not computed."""
+    cov_mode = _check_return_cov(return_cov)
     model = calib.camera_model_of(camera_model, project_func)
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -150,6 +201,11 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
         est_h, smo_h, outl_h = est.cpu().numpy(), smo.cpu().numpy(), outl.cpu().numpy()
         if return_internals:
             xp_h, pe_h, gain_h = _read_internals(ws, ws_ptr - ws.data_ptr(), n_frames, len(members))
+        if cov_mode:
+            cov_h = _covariances(prm, ws_ptr, nbytes, est, smo, cov_mode == "full")
+            if cov_mode == "full":
+                base, (off, shape) = ws_ptr - ws.data_ptr(), workspace_layout(n_frames, len(members))["P_est"]
+                cov_h["cov"] = ws[base + off:base + off + int(np.prod(shape)) * 8].cpu().numpy().view(np.float64).reshape(shape)
         for j, b in enumerate(members):
             r = dict(x=est_h[j, :, :N_POSE], dx=est_h[j, :, N_POSE:2 * N_POSE], ddx=est_h[j, :, 2 * N_POSE:],
                      smoothed_x=smo_h[j, :, :N_POSE], smoothed_dx=smo_h[j, :, N_POSE:2 * N_POSE],
@@ -159,14 +215,18 @@ def ekf_batch(dets, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resoluti
                 r["smoothed_positions"] = get_3d_marker_coords(r["smoothed_x"])
             if return_internals:
                 r.update(x_pred=xp_h[j], P_est=pe_h[j], rts_gain=gain_h[j])
+            if cov_mode:
+                r.update({key: val[j] for key, val in cov_h.items()})
             out[b] = r
     return out
 
 
 def ekf(det, k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, start_frame=0, states0=None,
-        with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None, return_internals=False):
-    """One clip: det[N, C, 20, 3] for the frames start_frame .. start_frame + N - 1 (camera model and ``return_internals``
-    as ``ekf_batch``)."""
+        with_positions=True, smoother_pivoting=False, camera_model=None, project_func=None, return_internals=False,
+        return_cov=False):
+    """One clip: det[N, C, 20, 3] for the frames start_frame .. start_frame + N - 1 (camera model, ``return_internals`` and
+    ``return_cov`` - False, "bars" or True: the error bars and covariances of both state sequences - as ``ekf_batch``)."""
+    _check_return_cov(return_cov)
     return ekf_batch([det], k_arr, d_arr, r_arr, t_arr, fps, dlc_thresh, camera_resolution, [start_frame],
                      None if states0 is None else [states0], with_positions, smoother_pivoting, camera_model=camera_model,
-                     project_func=project_func, return_internals=return_internals)[0]
+                     project_func=project_func, return_internals=return_internals, return_cov=return_cov)[0]

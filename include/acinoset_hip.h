@@ -929,6 +929,31 @@ int acino_ekf_run(const acino_ekf_params* prm, const double* d_det, const double
  * parameters, workspace size and smoother.  fp64. */
 int acino_ekf_run_pinhole(const acino_ekf_params* prm, const double* d_det, const double* d_cams32, const double* d_states0,
                           void* d_ws, size_t ws_bytes, double* d_est, double* d_smooth, int32_t* d_outliers, void* stream);
+/* Covariances of the filter and the smoother: an opt-in second pass, no change to the calls above.  Both functions are
+ * stream-ordered (no host synchronisation), keep no state and need no workspace of their own.  fp64.
+ *
+ * acino_ekf_smoothed_covariance reads P_est and A from the workspace of a run that returned ACINO_OK (same prm, the
+ * read-back contract above; d_ws 256-byte aligned, ws_bytes >= acino_ekf_workspace_bytes) and writes
+ * d_P_smooth [n_seq][n_frames][75][75], the second half of Rauch-Tung-Striebel:
+ *   P_s[i] = P_est[i] + A_i (P_s[i+1] - P_pred[i+1]) A_i^T   for i = n_frames-2 .. 1,
+ * P_pred[i+1] = F P_est[i] F^T + Q rebuilt with the filter's own arithmetic.  Every P_s[i] is exactly symmetric.  The
+ * frames 0 and n_frames-1 (every frame when n_frames < 3) receive P_est bit for bit: the reference's smoother returns
+ * the filtered state there (:836-839), and this is the covariance of the state d_smooth reports.  The 3-sigma gate does
+ * not enter any covariance: a gated pair has its residual zeroed, the gain and (I - K H) P keep its rows of H.
+ *
+ * acino_ekf_marker_covariance maps states d_states [n_seq][n_frames][75] with covariances d_P [n_seq][n_frames][75][75]
+ * (d_est with P_est from the workspace, or d_smooth with d_P_smooth) to the markers: with J_l the ANALYTIC Jacobian of
+ * the forward kinematics of marker l at the given pose (not the filter's 1e-3 forward difference),
+ *   d_cov_pos   [n_seq][n_frames][20][3][3]  J_l P[:25, :25] J_l^T
+ *   d_std_pos   [n_seq][n_frames][20]        sqrt(trace of that)
+ *   d_std_state [n_seq][n_frames][75]        sqrt(diag P)
+ * Any output may be NULL; all three NULL is ACINO_ERR_INVALID_ARG.  Of prm only n_frames and n_seq are read.  The
+ * covariances are the filter's belief under the reference's literal constants (R = 25^2 px^2 per coordinate, cam_width^2
+ * under the likelihood threshold), not a calibrated detector noise. */
+int acino_ekf_smoothed_covariance(const acino_ekf_params* prm, const void* d_ws, size_t ws_bytes, double* d_P_smooth,
+                                  void* stream);
+int acino_ekf_marker_covariance(const acino_ekf_params* prm, const double* d_states, const double* d_P, double* d_cov_pos,
+                                double* d_std_pos, double* d_std_state, void* stream);
 
 /* The same sharded iteration as FOUR fused phases with the three collectives between them; each phase is a fixed
  * launch sequence on caller-owned buffers and is captured into a hipGraph (acino_fte_enable_graph) per buffer set:
