@@ -17,7 +17,9 @@ LOOK_AT = np.array([2.0, 6.5, 0.7])
 
 
 def make_rig(n_cams=6):
-    """Ring rig with the geometry of the reference's configs/dummy_scene.json (identical intrinsics)."""
+    """Ring rig with the geometry of the reference's configs/dummy_scene.json (identical intrinsics: one K and one D tiled
+    over the cameras, so a kernel reading another camera's row computes the same numbers - a test of per-camera indexing
+    must use tests/unlike_rig.py)."""
     K = np.tile(K_DUMMY, (n_cams, 1, 1))
     D = np.tile(D_DUMMY, (n_cams, 1))
     R = np.zeros((n_cams, 3, 3))

@@ -54,7 +54,9 @@ typedef enum acino_status {
 /* ---- camera records -------------------------------------------------------------------------
  * Fisheye camera: 24 doubles  [fx fy cx cy | k1 k2 k3 k4 | R(9,row-major) | t(3) | alpha 0 0 0]
  * Pinhole camera: 32 doubles  [fx fy cx cy | d(14: k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 tx ty) | R(9) | t(3) | 0 0]
- * (alpha = K[0][1]/fx, OpenCV's skew; zero for every reference rig.) */
+ * (alpha = K[0][1]/fx, OpenCV's skew; zero for every reference rig.  The point-wise, pair and EKF kernels honour it; the
+ * FTE NLP projection and every pinhole path ignore it, as their references do; the bundle adjustment refuses it.  All of it
+ * under test on unlike, skewed cameras: tests/test_gpu_unlike_rig.py.) */
 #define ACINO_CAM_STRIDE 24
 #define ACINO_PINHOLE_STRIDE 32
 #define ACINO_MAX_CAMS 16

@@ -32,7 +32,9 @@ def load_scene_json(path):
 
 def make_rig(n_cams=6):
     """Programmatic ring rig with the geometry of configs/dummy_scene.json: identical intrinsics,
-    cameras at CAM_CENTRES looking at LOOK_AT, image x to the right, y down, z forward."""
+    cameras at CAM_CENTRES looking at LOOK_AT, image x to the right, y down, z forward.  One K and one D are tiled over the
+    cameras, so a kernel reading another camera's row computes the same numbers: a test of per-camera indexing must use
+    tests/unlike_rig.py."""
     K = np.tile(K_DUMMY, (n_cams, 1, 1))
     D = np.tile(D_DUMMY, (n_cams, 1))
     R = np.zeros((n_cams, 3, 3))

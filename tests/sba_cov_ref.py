@@ -21,22 +21,27 @@ FLOOR = 1.1e-8
 PINHOLE_D = np.array([0.05, -0.02, 1e-3, -5e-4, 0.01, 0.02, -0.01, 0.005])     # (the pinhole SBA test's 8 coefficients)
 
 
-def make_problem(n_cams, n_pts, seed, model="fisheye", single_view=False, blind_cam=None):
+def make_problem(n_cams, n_pts, seed, model="fisheye", single_view=False, blind_cam=None, rig=None):
     """synth.make_rig (cameras beyond the sixth: copies of the first ones, moved), a seeded rng, ragged visibility (2 .. C
     views), 1 px noise and a handful of 15 px outliers so that the weights matter; the iterate is off the truth by 3 cm /
-    0.01 rad / 1 cm.  ``single_view``: the last point keeps one view.  ``blind_cam``: no point is seen by that camera."""
+    0.01 rad / 1 cm.  ``single_view``: the last point keeps one view.  ``blind_cam``: no point is seen by that camera.
+    ``rig``: (K, D, R, t) of n_cams cameras of ``model`` in the place of synth.make_rig (tests/unlike_rig.py); the cameras
+    beyond the sixth are moved all the same."""
     rng = np.random.default_rng(seed)
-    K6, D6, R6, t6 = synth.make_rig()
     C, P = n_cams, n_pts
     sel = np.arange(C) % 6
-    K, R, t = K6[sel], R6[sel].copy(), t6[sel].reshape(C, 3, 1).copy()
+    if rig is None:
+        K6, D6, R6, t6 = synth.make_rig()
+        K, R, t = K6[sel], R6[sel].copy(), t6[sel].reshape(C, 3, 1).copy()
+        D_rig = D6[sel] if model == "fisheye" else np.tile(PINHOLE_D, (C, 1))
+    else:
+        K, D_rig, R, t = (np.array(a, dtype=np.float64) for a in rig)
+        assert len(K) == C
+        t = t.reshape(C, 3, 1)
     for c in range(6, C):
         R[c] = ocam.rodrigues(rng.normal(0, 0.04, 3)) @ R[c]
         t[c] = t[c] + rng.normal(0, 0.25, (3, 1))
-    if model == "fisheye":
-        D, ofun = D6[sel], ocam.project_points_fisheye
-    else:
-        D, ofun = np.tile(PINHOLE_D, (C, 1)), ocam.project_points
+    D, ofun = D_rig, (ocam.project_points_fisheye if model == "fisheye" else ocam.project_points)
     X = np.array([2.0, 6.5, 0.7]) + rng.normal(0, 0.6, (P, 3))
     cams_ok = [c for c in range(C) if c != blind_cam]
     pi, ci = [], []
