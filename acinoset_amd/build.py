@@ -121,6 +121,11 @@ def _forehead_union(tabs, lik_thresh, k_arr, d_arr, r_arr, t_arr, camera_model="
     return frames, np.asarray(tri.cpu().numpy() if isinstance(tri, torch.Tensor) else tri)[:, 0]
 
 
+def _load_scene(project_dir):
+    """``(k_arr, d_arr, r_arr, t_arr)`` of the reference's scene file (build.py:97-100)."""
+    return io.load_scene(os.path.join(project_dir, "data", "4_cam_scene_static_sba.json"))[:4]
+
+
 def _scene_distortion(camera_model, k_arr, d_arr, r_arr, t_arr):
     """The rig's distortion vectors as the model reads them: fisheye k1..k4 (the reference's ``reshape((-1, 4))``, :100), or
     the whole OpenCV pinhole vector of every camera (4, 5, 8, 12 or 14 entries; calib.pinhole_record refuses the others and
@@ -148,7 +153,7 @@ def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_f
     prog = skeleton.compile_skeleton(skel_dict)
     names = prog["names"]
     if scene is None:
-        scene = io.load_scene(os.path.join(project_dir, "data", "4_cam_scene_static_sba.json"))[:4]
+        scene = _load_scene(project_dir)
     k_arr, d_arr, r_arr, t_arr = (np.asarray(a, dtype=np.float64) for a in scene)
     d_arr = _scene_distortion(cam_model, k_arr, d_arr, r_arr, t_arr)
     if dlc_tables is None:
@@ -884,7 +889,7 @@ def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_out
     starts = video_windows(0, N - 1, window, window // 2)
     x = np.array(model.init_x if x0 is None else x0, dtype=np.float64, copy=True)
     x[:, act] = np.clip(x[:, act], model.lo[:, act], model.hi[:, act])
-    depth_w = np.minimum(np.arange(window), window - 1 - np.arange(window)).astype(np.float64)
+    owner = _window_owner(starts, window, 0, N)
     history = []
     res_full, info_full = None, None
     for outer in range(outer_max):
@@ -898,13 +903,7 @@ def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_out
             subs.append(SkeletonModel(**{**model.__dict__, "meas": model.meas[st:st + window], "weights": model.weights[st:st + window],
                                          "lo": lo, "hi": hi, "init_x": x[st:st + window].copy(), "x": None, "info": None}))
         solved = solve_models(subs, max_iter=first_max_iter if outer == 0 else later_max_iter, **solver_kw)
-        xn = x.copy()
-        depth = np.full(N, -1.0)
-        for st, (res, _i) in zip(starts, solved):
-            sl = slice(st, st + window)
-            take = depth_w > depth[sl]
-            xn[sl][take] = res["x"][take]
-            depth[sl] = np.maximum(depth[sl], depth_w)
+        xn = _stitch(owner, starts, 0, [res for res, _i in solved], ("x",))["x"]
         change = float(np.abs(xn - x).max())
         x = xn
         res_full, info_full = solve_model(model, x0=x, max_iter=0, **solver_kw)      # whole-clip cost and gradient norm at x
@@ -936,6 +935,102 @@ def window_residual_px(model, info):
     on every detection above the threshold (x and y are two rows each), plus a smoothness term that is small beside it."""
     n_rows = 2 * int((np.asarray(model.weights) > 0).sum())
     return float(info["cost_final"]) * R_MEAS / max(n_rows, 1)
+
+
+def _window_owner(starts, window, first_frame, total):
+    """The depth rule, owner[total]: every frame belongs to the window in which it lies deepest, the earlier window wins a tie.
+    Window w covers frames ``starts[w] - first_frame ... + window`` (relative to first_frame), its row r has depth
+    min(r, window - 1 - r), and a frame changes owner only for a strictly greater depth."""
+    d = np.minimum(np.arange(window), window - 1 - np.arange(window))
+    depth, owner = np.full(total, -1), np.full(total, -1)
+    for w, st in enumerate(starts):
+        sl = slice(st - first_frame, st - first_frame + window)
+        take = d > depth[sl]
+        owner[sl][take] = w
+        depth[sl] = np.maximum(depth[sl], d)
+    assert (owner >= 0).all(), "the windows do not cover every frame"
+    return owner
+
+
+def _stitch(owner, starts, first_frame, per_window, keys, fill=0.0):
+    """The gather by owner: for every key of ``keys`` frame n takes row n - (starts[w] - first_frame) of its owner window w's
+    array ``per_window[w][key]``.  The stitched arrays have the per-window arrays' trailing shape and dtype (``fill``: what a
+    frame without an owner would keep)."""
+    out = {k: np.full((len(owner),) + per_window[0][k].shape[1:], fill, dtype=per_window[0][k].dtype) for k in keys}
+    for w, (st, arrays) in enumerate(zip(starts, per_window)):
+        mine = np.nonzero(owner == w)[0]
+        for k in keys:
+            out[k][mine] = arrays[k][mine - (st - first_frame)]
+    return out
+
+
+def _warm_pairs(px, warm_px):
+    """Which window is retried from which neighbour, ``[(i, j), ...]``: window i when ``px[i] > warm_px`` (a NaN is not), from
+    the neighbour j of i - 1, i + 1 with ``px[j] < px[i]`` and ``px[j] <= warm_px`` - the one with the smaller px, i - 1 on a tie."""
+    pairs = []
+    for i in range(len(px)):
+        if not (px[i] > warm_px):
+            continue
+        cand = [j for j in (i - 1, i + 1) if 0 <= j < len(px) and px[j] < px[i] and px[j] <= warm_px]
+        if cand:
+            pairs.append((i, min(cand, key=lambda q: px[q])))
+    return pairs
+
+
+def _warm_x0(x0_own, st, x_donor, st_donor, window, act, lo, hi):
+    """The initial point of the window at ``st`` retried from a donor window's end state ``x_donor`` (at ``st_donor``; the two
+    share frames): the window's own first initial point, then the donor's joint angles (active states >= 3) at the shared frame
+    nearest to the rest of the window - the last shared frame of a donor that starts earlier, the first of a later one - held
+    over all rows, then the shared frames as the donor left them (whole rows), then the active states clipped to ``lo`` / ``hi``."""
+    lo_g, hi_g = max(st, st_donor), min(st, st_donor) + window            # shared frames [lo_g, hi_g) (global numbering)
+    x0 = x0_own.copy()
+    edge = x_donor[(hi_g - 1 if st_donor < st else lo_g) - st_donor]      # the donor's state at the shared frame nearest to the rest
+    x0[:, act[act >= 3]] = edge[act[act >= 3]][None, :]                   # its joint angles held over the window ...
+    x0[lo_g - st:hi_g - st] = x_donor[lo_g - st_donor:hi_g - st_donor]    # ... and the shared frames as the donor left them
+    x0[:, act] = np.clip(x0[:, act], lo[:, act], hi[:, act])
+    return x0
+
+
+def _warm_passes(models, x0s, starts, window, solved, px, warm_px, passes, kw):
+    """solve_video's warm starts, on ``solved`` and ``px`` in place: up to ``passes`` times, one batched solve of the windows
+    of ``_warm_pairs`` that share frames with their donor from ``_warm_x0``, the better of the two end states kept; it ends
+    with the first pass that retries or improves nothing.  Returns the donor every window's kept state was started from (or None)."""
+    warm_from = [None] * len(starts)
+    act = np.asarray(models[0].active, dtype=np.int64)
+    for _pass in range(int(passes)):
+        redo = [(i, j) for i, j in _warm_pairs(px, warm_px) if abs(starts[i] - starts[j]) < window]
+        if not redo:
+            break
+        x0r = [_warm_x0(x0s[i], starts[i], solved[j][0]["x"], starts[j], window, act, models[i].lo, models[i].hi) for i, j in redo]
+        again = solve_models([models[i] for i, _j in redo], x0r, **kw)
+        improved = False
+        for (i, j), (res, info) in zip(redo, again):
+            p_new = window_residual_px(models[i], info)
+            if info["status_name"] != "numeric" and p_new < px[i]:
+                solved[i], px[i], warm_from[i], improved = (res, info), p_new, j, True
+        if not improved:
+            break
+    return warm_from
+
+
+def _video_forehead(dlc_tables, idx, f0, f1, scene, lik_thresh, cam_model):
+    """The forehead of frames f0 .. f1, triangulated once and its gaps interpolated, [frames, 3] (the reference's initial point
+    uses the same marker, build.py:143-166) - or None without the marker, a second camera or two frames that see it.  Every
+    table must hold f0 .. f1 (ValueError)."""
+    tabs3 = [(list(tb[0]), np.asarray(tb[1], dtype=np.float64), ix) for tb, ix in zip(dlc_tables, idx)]
+    rows3 = [_rows_by_frame_value(ix, np.arange(f0, f1 + 1)) for _parts, _vals, ix in tabs3]
+    if not all("forehead" in parts for parts, _v, _i in tabs3) or len(tabs3) < 2:
+        return None
+    k_arr, d_arr, r_arr, t_arr = (np.asarray(a, dtype=np.float64) for a in scene)
+    cols = [vals[rw, parts.index("forehead")][:, None, :] for (parts, vals, _ix), rw in zip(tabs3, rows3)]
+    tri = calib.triangulate_pairs_dense(np.stack(cols, axis=1), lik_thresh, k_arr, _scene_distortion(cam_model, k_arr, d_arr, r_arr, t_arr),
+                                        r_arr, t_arr, return_masks=False, model=cam_model)
+    tri = np.asarray(tri.cpu().numpy() if isinstance(tri, torch.Tensor) else tri)[:, 0]
+    ok = np.isfinite(tri).all(1)
+    if ok.sum() < 2:
+        return None
+    fr = np.arange(f1 - f0 + 1, dtype=np.float64)
+    return np.stack([np.interp(fr, fr[ok], tri[ok, j]) for j in range(3)], axis=1)
 
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
@@ -1015,13 +1110,13 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
     cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
     build_kw["camera_model"] = cam_model
+    l1_eps = kw.get("l1_eps", 1e-2)
+    if scene is None:
+        scene = _load_scene(project_dir)
     if cov_cams is not None:                                  # (a malformed matrix fails before the solve, not after)
-        if scene is None:
-            scene = io.load_scene(os.path.join(project_dir, "data", "4_cam_scene_static_sba.json"))[:4]
         calib.cov_cams_matrix(cov_cams, len(scene[0]))
     if dlc_tables is None:
-        paths = sorted(glob.glob(os.path.join(project_dir, "data", "*.h5")))
-        dlc_tables = [io.read_dlc_table(p) for p in paths]
+        dlc_tables = [io.read_dlc_table(p) for p in sorted(glob.glob(os.path.join(project_dir, "data", "*.h5")))]
     idx = [np.arange(np.asarray(tb[1]).shape[0]) if len(tb) < 3 or tb[2] is None else np.asarray(tb[2]) for tb in dlc_tables]
     f0 = max(int(i.min()) for i in idx) if first_frame is None else int(first_frame)
     f1 = min(int(i.max()) for i in idx) if last_frame is None else int(last_frame)
@@ -1029,130 +1124,53 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     if total < window:
         raise ValueError(f"{total} frames, windows of {window}")
     starts = video_windows(f0, f1, window, overlap)
-    # the forehead of every frame, triangulated once (the reference's initial point uses the same marker, build.py:143-166)
-    head = None
-    tabs3 = [(list(tb[0]), np.asarray(tb[1], dtype=np.float64), ix) for tb, ix in zip(dlc_tables, idx)]
-    want = np.arange(f0, f1 + 1)
-    rows3 = [_rows_by_frame_value(ix, want) for _parts, _vals, ix in tabs3]       # (every table must hold f0 .. f1: ValueError)
-    if all("forehead" in parts for parts, _v, _i in tabs3) and len(tabs3) >= 2:
-        if scene is None:
-            scene = io.load_scene(os.path.join(project_dir, "data", "4_cam_scene_static_sba.json"))[:4]
-        k_arr, d_arr, r_arr, t_arr = (np.asarray(a, dtype=np.float64) for a in scene)
-        cols = [vals[rw, parts.index("forehead")][:, None, :] for (parts, vals, _ix), rw in zip(tabs3, rows3)]
-        tri = calib.triangulate_pairs_dense(np.stack(cols, axis=1), build_kw.get("lik_thresh", LIK_THRESH), k_arr,
-                                            _scene_distortion(cam_model, k_arr, d_arr, r_arr, t_arr), r_arr, t_arr,
-                                            return_masks=False, model=cam_model)
-        tri = np.asarray(tri.cpu().numpy() if isinstance(tri, torch.Tensor) else tri)[:, 0]
-        ok = np.isfinite(tri).all(1)
-        if ok.sum() >= 2:
-            fr = np.arange(total, dtype=np.float64)
-            head = np.stack([np.interp(fr, fr[ok], tri[ok, j]) for j in range(3)], axis=1)
-    models, x0s = [], []
-    for st in starts:
-        m, _ = build_model(skel_dict, project_dir, scene=scene, dlc_tables=dlc_tables, n_frames=window, start_frame=st,
-                           initial_line=head is None, **build_kw)
-        x0 = m.init_x.copy()
-        if head is not None:
-            x0[:, :3] = head[st - f0:st - f0 + window]
-        models.append(m)
-        x0s.append(x0)
+    head = _video_forehead(dlc_tables, idx, f0, f1, scene, build_kw.get("lik_thresh", LIK_THRESH), cam_model)
+    models = [build_model(skel_dict, project_dir, scene=scene, dlc_tables=dlc_tables, n_frames=window, start_frame=st,
+                          initial_line=head is None, **build_kw)[0] for st in starts]
+    x0s = [m.init_x.copy() for m in models]
+    for st, x0 in zip(starts, x0s if head is not None else []):
+        x0[:, :3] = head[st - f0:st - f0 + window]
     solved = solve_models(models, x0s, **kw)
     px = [window_residual_px(m, i) for m, (_r, i) in zip(models, solved)]
-    warm_from = [None] * len(starts)
-    act = np.asarray(models[0].active, dtype=np.int64)
-    for _pass in range(int(warm_passes)):
-        redo, x0r = [], []
-        for i, st in enumerate(starts):
-            if not (px[i] > warm_px):
-                continue
-            cand = [j for j in (i - 1, i + 1) if 0 <= j < len(starts) and px[j] < px[i] and px[j] <= warm_px]
-            if not cand:
-                continue
-            j = min(cand, key=lambda q: px[q])
-            xj, sj = solved[j][0]["x"], starts[j]
-            lo_g, hi_g = max(st, sj), min(st, sj) + window            # shared frames [lo_g, hi_g) (global numbering)
-            if hi_g <= lo_g:
-                continue
-            x0 = x0s[i].copy()
-            edge = xj[(hi_g - 1 if sj < st else lo_g) - sj]           # the neighbour's state at the shared frame nearest to the rest
-            x0[:, act[act >= 3]] = edge[act[act >= 3]][None, :]        # its joint angles held over the window ...
-            x0[lo_g - st:hi_g - st] = xj[lo_g - sj:hi_g - sj]          # ... and the shared frames as the neighbour left them
-            x0[:, act] = np.clip(x0[:, act], models[i].lo[:, act], models[i].hi[:, act])
-            redo.append((i, j))
-            x0r.append(x0)
-        if not redo:
-            break
-        again = solve_models([models[i] for i, _j in redo], x0r, **kw)
-        improved = False
-        for (i, j), (res, info) in zip(redo, again):
-            p_new = window_residual_px(models[i], info)
-            if info["status_name"] != "numeric" and p_new < px[i]:
-                solved[i], px[i], warm_from[i], improved = (res, info), p_new, j, True
-        if not improved:
-            break
+    warm_from = _warm_passes(models, x0s, starts, window, solved, px, warm_px, warm_passes, kw)
     robust_failed = []
-    if loss != "l1":
+    if loss != "l1":                                          # the robust stage: one batched call from the L1 end states
         models = [_with_loss(m, loss) for m in models]
-        second = solve_models(models, [res["x"] for res, _info in solved], l1_start=False, **kw)
-        for i, (res2, info2) in enumerate(second):
+        for i, (res2, info2) in enumerate(solve_models(models, [res["x"] for res, _info in solved], l1_start=False, **kw)):
             if info2["status_name"] == "numeric":
                 robust_failed.append(i)
             else:
                 solved[i] = (res2, dict(info2, l1=solved[i][1]))
-    Lp, P = len(models[0].names), models[0].P
-    pos, x, dx, ddx = np.zeros((total, Lp, 3)), np.zeros((total, P)), np.zeros((total, P)), np.zeros((total, P))
-    depth = np.full(total, -1.0)
-    owner = np.full(total, -1)
-    for w_i, (st, (res, _info)) in enumerate(zip(starts, solved)):
-        d = np.minimum(np.arange(window), window - 1 - np.arange(window)).astype(np.float64)
-        sl = slice(st - f0, st - f0 + window)
-        take = d > depth[sl]
-        pos[sl][take], x[sl][take] = res["positions"][take], res["x"][take]
-        dx[sl][take], ddx[sl][take] = res["dx"][take], res["ddx"][take]
-        owner[sl][take] = w_i
-        depth[sl] = np.maximum(depth[sl], d)
-    infos = []
-    for i, (_r, info) in enumerate(solved):
-        info = dict(info)
-        info["mean_abs_residual_px"], info["warm_started_from"] = px[i], warm_from[i]
-        infos.append(info)
-    seams = [int(n) for n in np.nonzero(np.diff(owner) != 0)[0] + 1]
-    results = dict(positions=pos, x=x, dx=dx, ddx=ddx, start_frame=f0, seams=seams)
+    xs_final = [res["x"] for res, _info in solved]
+    owner = _window_owner(starts, window, f0, total)
+    results = _stitch(owner, starts, f0, [res for res, _info in solved], ("positions", "x", "dx", "ddx"))
+    results.update(start_frame=f0, seams=[int(n) for n in np.nonzero(np.diff(owner) != 0)[0] + 1])
+    infos = [dict(info, mean_abs_residual_px=px[i], warm_started_from=warm_from[i]) for i, (_r, info) in enumerate(solved)]
     if loss != "l1":
         results["robust_failed_windows"] = robust_failed
     if return_cov or return_rate_cov:
         keys = (("cov_pos", "std_pos") if return_cov else ()) + (RATE_KEYS if return_rate_cov else ())
-        covs = _covariance(models, [res["x"] for res, _info in solved], kw.get("l1_eps", 1e-2), keys,
-                           raise_numeric=False, pin_unobserved=pin_unobserved)
-        stitched = {k: np.full((total,) + covs[0][k].shape[1:], np.nan) for k in keys}
-        for w_i, (st, cv) in enumerate(zip(starts, covs)):
-            mine = np.nonzero(owner == w_i)[0]
-            for k in keys:
-                stitched[k][mine] = cv[k][mine - (st - f0)]
-            infos[w_i]["cov_status"] = cv["status"]
-        results.update(stitched, owner=owner.copy(), cov_singular_windows=[i for i, cv in enumerate(covs) if cv["status"] == 5])
+        covs = _covariance(models, xs_final, l1_eps, keys, raise_numeric=False, pin_unobserved=pin_unobserved)
+        for info, cv in zip(infos, covs):
+            info["cov_status"] = cv["status"]
+        results.update(_stitch(owner, starts, f0, covs, keys, fill=np.nan), owner=owner.copy(),
+                       cov_singular_windows=[i for i, cv in enumerate(covs) if cv["status"] == 5])
         if return_cov:
             results["window_std_pos"] = [cv["std_pos"] for cv in covs]
         if pin_unobserved:
             results["cov_unobserved"] = [cv["unobserved"] for cv in covs]
     if cov_cams is not None:
-        cals = _calibration(models, [res["x"] for res, _info in solved], cov_cams, kw.get("l1_eps", 1e-2), pin_unobserved,
-                            raise_numeric=False)
-        for k in CALIB_KEYS:
-            results[k] = np.full((total,) + cals[0][k].shape[1:], np.nan)
-            for w_i, (st, cal) in enumerate(zip(starts, cals)):
-                mine = np.nonzero(owner == w_i)[0]
-                results[k][mine] = cal[k][mine - (st - f0)]
+        cals = _calibration(models, xs_final, cov_cams, l1_eps, pin_unobserved, raise_numeric=False)
+        results.update(_stitch(owner, starts, f0, cals, CALIB_KEYS, fill=np.nan))
         if return_cov:
             results["std_pos_total"] = np.sqrt(results["std_pos"] ** 2 + results["std_pos_calib"] ** 2)
-    if return_reprojection:
-        local = np.arange(total) - (np.asarray(starts)[owner] - f0)          # every frame's row in its owner window
+    if return_reprojection:                                   # one clip of all the frames, every frame's detections its owner's
         lo_t, hi_t = bounds_table(skel_dict, total)
-        whole = SkeletonModel(**{**models[0].__dict__, "meas": np.stack([models[w_i].meas[r] for w_i, r in zip(owner, local)]),
-                                 "weights": np.stack([models[w_i].weights[r] for w_i, r in zip(owner, local)]), "lo": lo_t,
-                                 "hi": hi_t, "init_x": x.copy(), "start_frame": f0, "x": None, "info": None})
-        rep = model_reprojection([whole], [x], cov=bool(return_cov), cov_pos=[results["cov_pos"]] if return_cov else None,
-                                 l1_eps=kw.get("l1_eps", 1e-2))[0]
+        seen = _stitch(owner, starts, f0, [m.__dict__ for m in models], ("meas", "weights"))
+        whole = SkeletonModel(**{**models[0].__dict__, **seen, "lo": lo_t, "hi": hi_t, "init_x": results["x"].copy(), "start_frame": f0,
+                                 "x": None, "info": None})
+        rep = model_reprojection([whole], [results["x"]], cov=bool(return_cov), cov_pos=[results["cov_pos"]] if return_cov else None,
+                                 l1_eps=l1_eps)[0]
         results.update({k: rep[k] for k in REPROJ_KEYS})
         if gate is not None:
             finite = np.isfinite(rep["mahal2"])
