@@ -244,6 +244,7 @@ SIGNATURES = {
     "acino_selftest_mfma": (_I, [_P, _P, _I, _P, _P]),
     "acino_debug_poison_lds": (_I, [_I, _I, _P]),
     "acino_debug_level_split": (_I, [_I, _P]),
+    "acino_debug_coupling_table": (_I, [_L, _L, _L, _L, _I, _I, _P, _P]),
 }
 
 _lib = None

@@ -202,12 +202,38 @@ static __device__ __forceinline__ bool coupling_tables_uniform(const FteConst& K
 // True when the RIGHT table of one node is that of an interior node (every frame of the node and of its right neighbour alive, in
 // one clip, no third-difference row cut by an end of the sequence / clip): the entry (ii, jj), ii <= jj, is then
 // 2 q_p {-1, 6, -15}[jj - ii] - what right_table_interior writes.
-static __device__ __forceinline__ bool right_table_is_interior(const FteConst& K, int node) {
-  const int loc = 3 * (node - K.pin_left);
-  const int64_t f = K.n_offset + (int64_t)loc;
-  const int64_t len = K.clip_len > 0 ? K.clip_len : K.n_global;
-  const int64_t r = K.clip_len > 0 ? f % K.clip_len : f;
-  return f >= 0 && r <= len - 6 && f + 5 < K.n_global && loc + 5 < K.n_frames;
+// (TableGeom: the five numbers the test reads, so that a kernel can keep them in registers over a loop of nodes and the host
+//  can evaluate the same code - acino_debug_coupling_table.)  The test is exact: the six frames node .. node + 1 holds, f .. f + 5,
+// must exist locally and globally and lie in one clip; band_coef's interior branch then holds for every entry of the table
+// (its rows start at f + jj <= len - 4 and reach f + 3 + ii >= 3).
+struct TableGeom {
+  int64_t n_global, n_offset, clip_len;
+  int32_t n_frames, pin_left;
+};
+static __host__ __device__ __forceinline__ TableGeom table_geom(const FteConst& K) {
+  return TableGeom{K.n_global, K.n_offset, K.clip_len, K.n_frames, K.pin_left};
+}
+static __host__ __device__ __forceinline__ bool right_table_is_interior(const TableGeom& G, int node) {
+  const int loc = 3 * (node - G.pin_left);
+  const int64_t f = G.n_offset + (int64_t)loc;
+  const int64_t len = G.clip_len > 0 ? G.clip_len : G.n_global;
+  const int64_t r = G.clip_len > 0 ? f % G.clip_len : f;
+  return f >= 0 && r <= len - 6 && f + 5 < G.n_global && loc + 5 < G.n_frames;
+}
+static __host__ __device__ __forceinline__ bool right_table_is_interior(const FteConst& K, int node) {
+  return right_table_is_interior(table_geom(K), node);
+}
+// The LEFT table of a node couples frame jj of node - 1 with frame ii of the node: entry for entry the right table of node - 1
+// (fill_coupling_coef_q: the same frames, the same band, alive under the same condition), also where node - 1 is a left pin's
+// separator or lies before the window.
+static __host__ __device__ __forceinline__ bool left_table_is_interior(const TableGeom& G, int node) {
+  return right_table_is_interior(G, node - 1);
+}
+// The unscaled entry (ii, jj) of a node's right table, as fill_coupling_coef_q forms it (there times 2 q_p).
+static __host__ __device__ __forceinline__ double right_table_band(const TableGeom& G, int node, int ii, int jj) {
+  const int loc = 3 * (node - G.pin_left);
+  if (ii > jj || loc + 3 + ii >= G.n_frames) return 0.0;
+  return band_coef_clip(G.n_offset + (int64_t)loc + jj, 3 + ii - jj, G.n_global, G.clip_len);
 }
 template <int NTH, class QW>
 static __device__ __forceinline__ void right_table_interior(double* coefR, int tid, QW qw) {

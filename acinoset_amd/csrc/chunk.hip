@@ -271,6 +271,8 @@ struct SpikeArgs {
   const double* cRk;
   const double* bvn;
   double* zk;
+  double *Cg, *bR;                                   // the run's last node, right separator: block(R, L) (null: no left separator) and
+                                                     // its right-hand side in HBM; both null at every other node
   int *c_gfdone, *c_fready, *c_bv, *tdone;           // tdone[0 .. 2]: tile batches finished by roles 4, 6, 7
   int *g_open, *g_done;
   const double* Xf;
@@ -401,6 +403,21 @@ __device__ __forceinline__ void spike_node(const SpikeArgs& A, int& tsb, int ln)
   }
   lds_signal(A.c_fready, ln);
   stamp(19 + 4 * (ROLE - 4));
+  // After the run's last node F is block(R, L) of the right separator, and this wave's strips of it are final: -> HBM by their
+  // owner, now (columns >= 75 are not part of the separator's coupling: zero), the separator's right-hand side (column 79) by
+  // strip 4's.  (LDS operations of one wave complete in order: the lanes read what other lanes of the wave have just written.)
+  // The wave with two strips is the last one out of the node: its strips are stored by the idle D waves, which wait for it.
+  if (A.bR) {
+    if (A.Cg && !two) {
+      const int cc = 16 * j0 + li;
+#pragma unroll 5
+      for (int r = lk; r < BS; r += 4) A.Cg[r * BS + cc] = cc < 3 * NP ? Y[r * LD + cc] : 0.0;
+    }
+    if (ROLE == 7) {
+      A.bR[ln] = Y[ln * LD + (BS - 1)];
+      if (ln < 16) A.bR[64 + ln] = Y[(64 + ln) * LD + (BS - 1)];
+    }
+  }
 }
 
 
@@ -412,8 +429,8 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
   double* const Xf = reinterpret_cast<double*>(smem_raw);   // D~_k -> [L \ U_k] -> D~_k+1
   double* const Xg = Xf + MAT;                               // G_k
   double* const Y = Xg + MAT;                                // spike: F_k -> T_k -> F_k+1; column 79 = right-hand side
-  double* const cL = Y + MAT;                          // left tables of the first node; afterwards the odd nodes' right tables
-  double* const cR0 = cL + 9 * NP;                     // right tables of the even nodes (of every node when they are uniform)
+  double* const cL = Y + MAT;                          // left table of the first node; afterwards one of the two buffers of right
+  double* const cR0 = cL + 9 * NP;                     // tables (tab_cur below); the first node's right table
   double* const bvb = cR0 + 9 * NP;                    // [2][80] right-hand side of the node built last, by node parity
   double* const red = bvb + 2 * BS;                    // [8]
   int* const sync = reinterpret_cast<int*>(red + 8);   // 16 counters, named below ([0] and [11 .. 15]: the factor trio's)
@@ -438,7 +455,14 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
   const int sL = c - 1 + node0, sR = c + node0;                    // separator-chain indices of the run's two ends
   const size_t MB = (size_t)BS * BS;
   const int role = __builtin_amdgcn_readfirstlane(role8(wave));   // 0 chain, 1 / 2 helpers, 3 chain's mate, 4 .. 7 strip waves
-  const bool uni_tables = coupling_tables_uniform(K, first, first + n_int - 1);   // (then the tables of `first` serve every node)
+  // Coupling tables, per node and exact: a node whose right table is interior (right_table_is_interior: nearly every node of a
+  // long sequence) takes the constant table 2 q {-1, 6, -15}; fill_coupling_coef runs only for a node at an end of the sequence, of a
+  // clip or of a window.  Two buffers, cR0 and cL (the left table of `first` until the loop starts); tab_cur is the one of the
+  // node before, tab_int says which of them hold the constant table - wave-uniform, the same in all eight waves.
+  const TableGeom TG = table_geom(K);
+  const bool left_int = left_table_is_interior(TG, first);
+  int tab_cur = 0;
+  bool tab_int0 = right_table_is_interior(TG, first), tab_int1 = left_int;
   const int n_s = hasL ? 4 : 1;              // first run: only the right-hand side column (strip 4, role 7) is alive
   const bool builder = role <= 3;            // the D team
   const bool strips = role >= 4 && (hasL || role == 7);
@@ -469,7 +493,14 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
   {  // ---- first node of the run, its spike F_0 = E_l (dense form) with the right-hand side in column 79
     NodeFetch f;
     build_fetch<SW_T>(f, ch, K, first, tid);
-    fill_coupling_coef<SW_T>(cL, cR0, K, first, tid, kq);
+    if (left_int && tab_int0) {                        // both tables in one pass (cR0 follows cL), one entry per thread
+      if (tid < 2 * 9 * NP) {
+        const int q = tid % (9 * NP), pair = q / NP, p = q % NP, ii = pair / 3, jj = pair % 3;
+        cL[tid] = ii <= jj ? 2.0 * kq[p] * (jj == ii ? -1.0 : (jj - ii == 1 ? 6.0 : -15.0)) : 0.0;
+      }
+    } else {                                           // a node at an end: both evaluated (an interior one comes out as the constants)
+      fill_coupling_coef<SW_T>(cL, cR0, K, first, tid, kq);
+    }
     for (int e = tid; e < MAT; e += SW_T) Y[e] = 0.0;
     gmax_run = build_finish<SW_T>(Xf, bvb, f, K, first, tid, kq, klo, khi);
     __syncthreads();                                   // node, bv, tables, zeros complete
@@ -516,7 +547,20 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
     const bool has_next = !last || hasR;
     const int ln = opaque(lane);
     const int li = ln & 15, lk = ln >> 4;
-    double* const cRk = (uni_tables || !(k & 1)) ? cR0 : cL;
+    // This node's right table: the buffer of the node before if both are the constant table (nothing is written), else the other
+    // buffer - the strip waves may still read the previous node's in their stencil pass, and they are through with the one before
+    // that (c_gfdone) when the D waves write -, written only if it does not hold the constant table already.
+    bool tab_write = false, tab_interior = false;
+    if (k > 0) {
+      tab_interior = right_table_is_interior(TG, node);
+      if (!(tab_interior && (tab_cur ? tab_int1 : tab_int0))) {
+        tab_cur ^= 1;
+        tab_write = !(tab_interior && (tab_cur ? tab_int1 : tab_int0));
+        if (tab_cur) tab_int1 = tab_interior;
+        else tab_int0 = tab_interior;
+      }
+    }
+    double* const cRk = tab_cur ? cL : cR0;
     if (builder) {
       // ============================== G_k and the next node: the four D waves ==============================
       const int bw = role;                             // 0 chain, 1, 2 helpers, 3 the chain's SIMD mate (wave 4)
@@ -570,7 +614,10 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       lds_wait(c_gfdone, n_s * k);
       if (bw == 0) SW_STAMP(1);
       if (bt == 0) __hip_atomic_fetch_add(g_open, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (k > 0 && !uni_tables) fill_coupling_coef<256>(nullptr, cRk, K, node, bt, kq);
+      if (tab_write) {
+        if (tab_interior) right_table_interior<256>(cRk, bt, [&](int p) { return kq[p]; });
+        else fill_coupling_coef<256>(nullptr, cRk, K, node, bt, kq);
+      }
       if (bw == 0) gram_fixed<0, 10>(Xf, Xg, g_done, li, lk, ln);
       else if (bw == 1) gram_fixed<1, 7>(Xf, Xg, g_done, li, lk, ln);
       else if (bw == 2) gram_fixed<4, 8, 12>(Xf, Xg, g_done, li, lk, ln);
@@ -694,7 +741,28 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       if (bw == 0) SW_STAMP(4);
       if (bw < 3) {
         // (no closing barrier of the trio: the four D waves meet at the top of the next iteration, before anyone reads the factor)
-        if (!last) chol80_trio<false>(Xf, bw, ln, numeric_err, sync, tsy, (dbgp && k == dbg_k) ? lst : nullptr);
+        if (!last) {
+          chol80_trio<false>(Xf, bw, ln, numeric_err, sync, tsy, (dbgp && k == dbg_k) ? lst : nullptr);
+        } else if (hasR) {
+          // the node built last is the right separator: its diagonal block is final in Xf -> HBM now, by the three waves that
+          // have no factorisation to do, while the strip waves finish the spike
+          double2* d2 = reinterpret_cast<double2*>(sp.D + (size_t)sR * MB);
+          for (int idx = bt; idx < BS * BS / 2; idx += 192) {
+            const int e = 2 * idx, r = e / BS, cc = e % BS;
+            d2[idx] = make_double2(Xf[r * LD + cc], Xf[r * LD + cc + 1]);
+          }
+          if (hasL) {
+            // strips 2 and 0 of block(R, L), the two of wave 6, once every strip wave is through with its stencil pass (the other
+            // strips are stored by their owners, spike_node): 2 x 80 rows x 8 two-double items
+            double* const Cg = sp.Cpl + (size_t)sL * MB;
+            lds_wait(c_fready, n_s * (k + 1));
+#pragma unroll 7
+            for (int idx = bt; idx < 2 * BS * 8; idx += 192) {
+              const int h = idx / (BS * 8), rem = idx % (BS * 8), r = rem >> 3, cc = (h ? 32 : 0) + 2 * (rem & 7);
+              *reinterpret_cast<double2*>(Cg + r * BS + cc) = make_double2(Y[r * LD + cc], Y[r * LD + cc + 1]);
+            }
+          }
+        }
         SW_STAMP(8 + wave);
       } else if (bw == 3) {
         // G_k -> HBM, lower tiles only (G is symmetric: the back-substitution mirrors them): the chain's SIMD mate, 30 items per lane
@@ -714,6 +782,8 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       SpikeArgs sa;
       sa.Xg = Xg; sa.Y = Y; sa.Ag = sp.AL + (size_t)(hasL ? opaque(sL) : 0) * MB; sa.cRk = cRk; sa.bvn = bvb + ((k + 1) & 1) * BS;
       sa.zk = ch.b + (size_t)node * BS; sa.g_open = g_open; sa.g_done = g_done; sa.Xf = Xf; sa.c_gfdone = c_gfdone; sa.c_fready = c_fready; sa.c_bv = c_bv; sa.tdone = tdone;
+      sa.bR = (last && hasR) ? sp.b + (size_t)sR * BS : nullptr;
+      sa.Cg = (last && hasR && hasL) ? sp.Cpl + (size_t)sL * MB : nullptr;
       sa.k = k; sa.n_s = n_s; sa.hasL = hasL; sa.has_next = has_next; sa.stamps = (dbgp && k == dbg_k) ? lst : nullptr;
       if (role == 4) spike_node<4>(sa, tsb, ln);
       else if (role == 5) spike_node<5>(sa, tsb, ln);
@@ -727,23 +797,9 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
     __syncthreads();
     if (tid < 64 && lst[tid]) dbgp[tid] = lst[tid];
   }
-  if (hasR) {                                          // the node built last is the right separator
-    {
-      double2* d2 = reinterpret_cast<double2*>(sp.D + (size_t)sR * MB);
-      for (int idx = tid; idx < BS * BS / 2; idx += SW_T) {
-        const int e = 2 * idx, r = e / BS, cc = e % BS;
-        d2[idx] = make_double2(Xf[r * LD + cc], Xf[r * LD + cc + 1]);
-      }
-    }
-    if (tid < BS) sp.b[(size_t)sR * BS + tid] = Y[tid * LD + (BS - 1)];
-    if (hasL) {
-      double* Cg = sp.Cpl + (size_t)sL * MB;           // block(R, L): rows R, columns L
-      for (int e = tid; e < BS * BS; e += SW_T) {
-        const int r = e / BS, cc = e % BS;
-        Cg[e] = cc < 3 * NP ? Y[r * LD + cc] : 0.0;
-      }
-    }
-  }
+  // (The right separator - the node built last - left for HBM inside the last iteration, each part when it was final: the
+  //  diagonal block by the D waves after the build, block(R, L) and the right-hand side strip by strip after the stencil pass.  A
+  //  run with a right separator has at least one interior node: ChunkPlan::build.)
 #undef SW_STAMP
   publish_gmax<SW_T>(gmax_run, red, ch.gn_part, c, tid);
   if (dbgp && tid == 0) dbgp[71] = (long long)wall_clock64();
@@ -1222,3 +1278,17 @@ int chunk_backsub(const BcrChain& ch, const ChunkPlan& pl, const SepView& sp, co
 }
 
 }  // namespace acino
+
+extern "C" int acino_debug_coupling_table(int64_t n_global, int64_t n_frames, int64_t n_offset, int64_t clip_len, int pin_left,
+                                          int node, int32_t* interior, double* coef) {
+  using namespace acino;
+  ACINO_REQUIRE(interior && coef, "outputs");
+  ACINO_REQUIRE(n_global >= 1 && n_frames >= 1 && n_frames <= INT32_MAX && n_offset >= 0 && n_offset + n_frames <= n_global &&
+                    clip_len >= 0 && (pin_left == 0 || pin_left == 1),
+                "a window of n_frames frames at n_offset inside n_global frames");
+  const TableGeom G{n_global, n_offset, clip_len, (int32_t)n_frames, pin_left};
+  *interior = right_table_is_interior(G, node) ? 1 : 0;
+  for (int ii = 0; ii < 3; ++ii)
+    for (int jj = 0; jj < 3; ++jj) coef[3 * ii + jj] = right_table_band(G, node, ii, jj);
+  return ACINO_OK;
+}

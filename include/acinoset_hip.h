@@ -984,6 +984,14 @@ int acino_selftest_mfma(const double* d_a, const double* d_b, int k, double* d_c
  * [W_l | W_r] it computes (bit s < 5: columns 16 s .. of W_l, bit 5 + s: of W_r), bit mask of the strips it stores, number
  * of product tiles, then the tile codes (0 .. 24 P_l(a, b) = 5 a + b with a >= b; 25 .. 49 P_r; 50 .. 74 X(a, b)). */
 int acino_debug_level_split(int T, int32_t* out);
+/* Host only (tests): the right coupling table of chain node `node` (csrc/bcr_dev.hpp) for a window of n_frames frames at
+ * n_offset of a sequence of n_global frames (clip_len > 0: clips of that many frames; pin_left: node 0 is a separator).
+ * *interior: the value of the test by which the chunk sweep and its back-substitution take the constant table
+ * 2 q {-1, 6, -15} in place of evaluating the band; coef[3 ii + jj]: the unscaled entry (frame jj of the node with frame ii of
+ * node + 1) as the evaluation gives it, 0 for ii > jj and for a frame slot beyond the window.  The LEFT table of a node is
+ * the right table of node - 1 (node = pin_left - 1 is valid). */
+int acino_debug_coupling_table(int64_t n_global, int64_t n_frames, int64_t n_offset, int64_t clip_len, int pin_left, int node,
+                               int32_t* interior, double* coef);
 
 #ifdef __cplusplus
 }
