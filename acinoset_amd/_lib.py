@@ -14,8 +14,10 @@ SO_PATH = os.path.join(_HERE, "libacinoset_hip.so")
 BUILD_ID_SOURCE = "camera_kernels.hip"      # defines acino_build_id()
 SOURCES = ["camera_kernels.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_calib.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "ekf_cov.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_calib.hip", "skel_reproj.hip"]
 HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "fte_cov.hpp", "fte_cov_dev.hpp", "fte_calib.hpp", "fte_reproj.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
-           "pinhole.hpp", "ekf_dev.hpp", "sba_dev.hpp", "sba_host.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "fte_assemble_body.inc", "ekf_forward_body.inc", "skel_assemble_body.inc",
+           "pinhole.hpp", "ekf_dev.hpp", "sba_dev.hpp", "sba_host.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "skel_assemble.hpp",
            os.path.join("..", "..", "include", "acinoset_hip.h")]
+
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DNDEBUG"]      # scripts/isa_diff.py compiles with the same
 
 ABI_VERSION = 3          # ACINO_ABI_VERSION of include/acinoset_hip.h
 N_ACTIVE = 25
@@ -299,7 +301,7 @@ def build(force=False, verbose=False):
             hdr.update(f.read())
     objdir = os.path.join(_CSRC, "_obj")
     os.makedirs(objdir, exist_ok=True)
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DNDEBUG"]
+    flags = HIPCC_FLAGS
     jobs = []
     for src in SOURCES:
         with open(os.path.join(_CSRC, src), "rb") as f:

@@ -79,8 +79,9 @@ k_fte_calib_rhs(const FteConst* __restrict__ cst, const acino_fte_state* __restr
     const double* d = det + ((n * C + ci) * NL + l) * 3;
     const double um = d[0], vm = d[1], lik = d[2];
     double w = (lik > K.dlc_thresh && isfinite(um) && isfinite(vm)) ? K.inv_r : 0.0;
-    const double* Rc = PINHOLE ? K.pcams[ci].R : K.cams[ci].R;
-    const double* tc = PINHOLE ? K.pcams[ci].t : K.cams[ci].t;
+    const auto& cam = cam_rec<PINHOLE>(K, ci);
+    const double* Rc = cam.R;
+    const double* tc = cam.t;
     const double xc = Rc[0] * px + Rc[1] * py + Rc[2] * pz + tc[0];
     const double yc = Rc[3] * px + Rc[4] * py + Rc[5] * pz + tc[1];
     const double zc = Rc[6] * px + Rc[7] * py + Rc[8] * pz + tc[2];
@@ -91,17 +92,9 @@ k_fte_calib_rhs(const FteConst* __restrict__ cst, const acino_fte_state* __restr
       for (int e = 0; e < 18; ++e) M[e] = 0.0;
       continue;
     }
-    double u, v, jc[2][3];
-    if (PINHOLE) {
-      double uv[2];
-      pinhole_project<true>(K.pcams[ci], xc, yc, zc, uv, jc);
-      u = uv[0];
-      v = uv[1];
-    } else {
-      FisheyeNlp fp;
-      fisheye_nlp_uv(K.cams[ci], xc, yc, zc, fp, u, v);
-      fisheye_nlp_jac(K.cams[ci], fp, jc[0], jc[1]);
-    }
+    double uv[2], jc[2][3];
+    project_jac(cam, xc, yc, zc, uv, jc);
+    const double u = uv[0], v = uv[1];
     double rho, drho, h_u = 0.0, h_v = 0.0;
     redescending<true>(K.loss, w * (u - um), rho, drho, h_u);
     redescending<true>(K.loss, w * (v - vm), rho, drho, h_v);

@@ -50,6 +50,12 @@ struct FteConst {
   int32_t pad3;
 };
 enum { CAMERA_FISHEYE = 0, CAMERA_PINHOLE = 1 };
+// record of camera ci under the model a kernel is instantiated for (a reference: the parentheses keep it one)
+template <bool PINHOLE>
+__host__ __device__ __forceinline__ decltype(auto) cam_rec(const FteConst& K, int ci) {
+  if constexpr (PINHOLE) return (K.pcams[ci]);
+  else return (K.cams[ci]);
+}
 
 // (D3^T D3)[n, n+k] for global frame n, 0 <= k <= 3, sequence length ng (stencil -1, 3, -3, 1).
 __host__ __device__ inline double band_coef(int64_t n, int k, int64_t ng) {

@@ -65,8 +65,9 @@ k_fte_reproj(const FteConst* __restrict__ cst, const acino_fte_state* __restrict
     const double um = d[0], vm = d[1], lik = d[2];
     const bool finite = isfinite(um) && isfinite(vm);
     double w = (lik > K.dlc_thresh && finite) ? K.inv_r : 0.0;
-    const double* Rc = PINHOLE ? K.pcams[ci].R : K.cams[ci].R;
-    const double* tc = PINHOLE ? K.pcams[ci].t : K.cams[ci].t;
+    const auto& cam = cam_rec<PINHOLE>(K, ci);
+    const double* Rc = cam.R;
+    const double* tc = cam.t;
     double xc = Rc[0] * px + Rc[1] * py + Rc[2] * pz + tc[0];
     double yc = Rc[3] * px + Rc[4] * py + Rc[5] * pz + tc[1];
     double zc = Rc[6] * px + Rc[7] * py + Rc[8] * pz + tc[2];
@@ -75,15 +76,15 @@ k_fte_reproj(const FteConst* __restrict__ cst, const acino_fte_state* __restrict
     double u = nan, v = nan, ru = nan, rv = nan, hu = 0.0, hv = 0.0, m2 = nan, s00 = nan, s01 = nan, s11 = nan;
     if (!sing) {
       double jc[2][3];
-      if (PINHOLE) {
+      if constexpr (PINHOLE) {
         double uv[2];
-        pinhole_project<true>(K.pcams[ci], xc, yc, zc, uv, jc);
+        pinhole_project<true>(cam, xc, yc, zc, uv, jc);
         u = uv[0];
         v = uv[1];
       } else {
         FisheyeNlp fp;
-        fisheye_nlp_uv(K.cams[ci], xc, yc, zc, fp, u, v);
-        fisheye_nlp_jac(K.cams[ci], fp, jc[0], jc[1]);
+        fisheye_nlp_uv(cam, xc, yc, zc, fp, u, v);
+        fisheye_nlp_jac(cam, fp, jc[0], jc[1]);
       }
       if (finite) {
         ru = u - um;

@@ -1,6 +1,9 @@
 // The OpenCV "standard" pinhole camera (cv2.projectPoints: rational + tangential + thin-prism distortion), shared by the
-// point-wise camera kernels and the FTE assembly.
+// point-wise camera kernels and the FTE assembly; and what a kernel template needs to take the camera model as a parameter:
+// the record type of a model (CamRec) and one projection-with-Jacobian call for either record (project_jac).
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace acino {
@@ -47,6 +50,21 @@ __device__ __forceinline__ void pinhole_project(const Pin& c, double xc, double 
     J[1][1] = dv_db * iz;
     J[1][2] = -(dv_da * a + dv_db * b) * iz;
   }
+}
+
+// ---- the camera model as a template parameter: PINHOLE ? Pin : Cam.  The structs that hold both kinds of record give the
+//      record of camera ci by cam_rec<PINHOLE>(owner, ci) (fte_kernels.hpp: FteConst, skel_dev.hpp: SkelDev).
+template <bool PINHOLE>
+using CamRec = std::conditional_t<PINHOLE, Pin, Cam>;
+
+// Pixel and d(uv)/d(X_cam) of a camera-frame point, the report kernels' call: the FTE assembly's own functions in its order.
+__device__ __forceinline__ void project_jac(const Cam& c, double xc, double yc, double zc, double uv[2], double J[2][3]) {
+  FisheyeNlp fp;
+  fisheye_nlp_uv(c, xc, yc, zc, fp, uv[0], uv[1]);
+  fisheye_nlp_jac(c, fp, J[0], J[1]);
+}
+__device__ __forceinline__ void project_jac(const Pin& c, double xc, double yc, double zc, double uv[2], double J[2][3]) {
+  pinhole_project<true>(c, xc, yc, zc, uv, J);
 }
 
 }  // namespace acino

@@ -5,7 +5,7 @@
 // R_c <- exp([dw]x) R_c, t_c <- t_c + dt: the camera-frame point moves by dw x (R_c p) + dt, so with j the camera-frame
 // Jacobian row of a pixel component J_c = [ (R_c p) x j | j ].  The weight of a kept row is the Fisher weight w^2 (the
 // statement A makes), not the IRLS curvature.
-//   k_skel_cov_assemble[_pinhole], k_skel_cov_build   skel_cov.hip's (skel_cov_launch_build): band, pin mask and the link
+//   k_skel_assemble<.., double>, k_skel_cov_build   skel_cov.hip's (skel_cov_launch_build): band, pin mask and the link
 //                           operators opv of every frame, the unobserved states pinned when the caller asks
 //   k_skel_calib_rhs<PINHOLE>  one workgroup per frame of every clip.  Poses from opv (the link program, in program order), the
 //                           pose Jacobians G_l (skel_pose_jac_col, as k_skel_cov_pose) into LDS, per (camera, slot) the 3 x 6
@@ -88,8 +88,9 @@ k_skel_calib_rhs(const SkelDev* __restrict__ dev, const double* __restrict__ x, 
     const double um = meas[2 * e], vm = meas[2 * e + 1];
     double w = wgt[e];
     if (!(m_finite(um) && m_finite(vm))) w = 0.0;
-    const double* Rc = PINHOLE ? D.pins[c].R : D.cams[c].R;
-    const double* tc = PINHOLE ? D.pins[c].t : D.cams[c].t;
+    const auto& cam = cam_rec<PINHOLE>(D, c);
+    const double* Rc = cam.R;
+    const double* tc = cam.t;
     const double q0 = Rc[0] * px + Rc[1] * py + Rc[2] * pz;              // R_c p
     const double q1 = Rc[3] * px + Rc[4] * py + Rc[5] * pz;
     const double q2 = Rc[6] * px + Rc[7] * py + Rc[8] * pz;
@@ -101,16 +102,8 @@ k_skel_calib_rhs(const SkelDev* __restrict__ dev, const double* __restrict__ x, 
       for (int k = 0; k < 18; ++k) M[k] = 0.0;
       continue;
     }
-    double jc[2][3];
-    if (PINHOLE) {
-      double uv[2];
-      pinhole_project<true>(D.pins[c], xc, yc, zc, uv, jc);
-    } else {
-      FisheyeNlp fp;
-      double u, v;
-      fisheye_nlp_uv(D.cams[c], xc, yc, zc, fp, u, v);
-      fisheye_nlp_jac(D.cams[c], fp, jc[0], jc[1]);
-    }
+    double uv[2], jc[2][3];                                              // (the pixel itself is not used here)
+    project_jac(cam, xc, yc, zc, uv, jc);
     double ju[3], jv[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {

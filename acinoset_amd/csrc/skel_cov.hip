@@ -1,7 +1,7 @@
 // Error bars for the generic-skeleton FTE (gfx950, fp64): per-frame covariance of the active states and of every pose slot,
 // evaluated at a given iterate x (normally the solution of skel_fte.hip).  With the unknowns frame-major,
 //     A = blockdiag_n( sum_{c,l,d} w_ncl^2 J_ncld^T J_ncld )  +  2 q D3^T D3 ,      q = model_weight / h^4
-// J_ncld = d(pi_c(pose_l(x_n))_d)/dx_n from the solve's own assembly statements (skel_assemble_body.inc: same link program,
+// J_ncld = d(pi_c(pose_l(x_n))_d)/dx_n from the solve's own assembly statements (skel_assemble.hpp: same link program,
 // same camera functions, same dropped rows: w = 0, non-finite measurements, |z_cam| < 1e-9), D3 the third-difference operator
 // of a clip with band_coef's coefficients.  This is the FISHER information of the model the objective states plus the prior:
 // sum |w r| is the negative log-likelihood of Laplace noise of scale 1 / w, whose information for location is w^2, and A^-1
@@ -12,12 +12,12 @@
 // Bound-active variables are pinned exactly as the solver pins them - skel_fixed(x, g, hd, lo, hi) with the solver's own
 // gradient g (L1 + smoothness) and IRLS diagonal hd at x: row and column zeroed, diagonal 1 - and their rows and columns are
 // exactly 0 in every output.
-// Under the redescending loss (acino_skel_fte_params::loss; k_skel_cov_assemble_redesc[_pinhole]) the blocks are
+// Under the redescending loss (acino_skel_fte_params::loss; k_skel_assemble<true, ., true, double>) the blocks are
 // sum w^2 h(e) J^T J: the Gauss-Newton curvature of the stated objective at x, fte_cov.hip's definition.  The loss is e^2 / 2 in
 // its core (Gaussian noise of scale 1 / w, h = 1) and constant beyond c (h = 0): a detection the solve has rejected adds no
 // information, and the matrix depends on the residuals.  Kept rows, pins, factorisation and outputs are the same; the
 // observability pass stays on w^2 (a row is observed whatever its h).
-//   k_skel_cov_assemble[_pinhole]  one workgroup per frame: the assembly body with ACINO_SKEL_FISHER: H_F, g, hd, link operators
+//   k_skel_assemble<.., double>    one workgroup per frame: the assembly kernel with FISHER: H_F, g, hd, link operators
 //   k_skel_cov_build               k_skel_build at lam = 0 with H_F for H: band blocks, pin mask, the original diagonal
 //   k_skel_selinv<PT>              ONE workgroup per clip.  Forward: the banded block Cholesky of k_skel_solve (panel in LDS,
 //                                  diagonal tiles by the register pivot chain, window update in memory), factored panels to
@@ -41,7 +41,7 @@
 //                                  above SK_UNOBS_REL * max.  No atomics.  A small reduction, latency-bound (N dependent adds
 //                                  per lane on strided loads).  The assembly body adds the prior's diagonal 2 q b0 to H in the
 //                                  same statement as the Fisher sum, and (s + c) - c does not give s back, so the diagonals
-//                                  this kernel reads come from a run of k_skel_cov_assemble on a second SkelDev with q = 0:
+//                                  this kernel reads come from a run of the Fisher assembly on a second SkelDev with q = 0:
 //                                  there H IS the Fisher block, bit for bit (s + 2 * 0 * b0).  That run's H, g, hd, opv are
 //                                  overwritten by the real assembly that follows on the same stream.
 //                                  An unobserved state - info[p] <= SK_UNOBS_REL * max_q info[q]: no frame of the clip moves any
@@ -60,63 +60,15 @@
 #include <limits>
 #include <vector>
 
+#include "skel_assemble.hpp"
 #include "skel_factor.hpp"
 
 namespace acino {
 
-// ---- Fisher assembly: the solve's assembly body, current iterate only (the clip words are all zero: status 0, buffer 0)
-#define ACINO_SKEL_FISHER 1
-__global__ void __launch_bounds__(256)
-k_skel_cov_assemble(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which, const double* __restrict__ x0,
-                    const double* __restrict__ x1, const double* __restrict__ meas, const double* __restrict__ wgt,
-                    double* __restrict__ H0, double* __restrict__ H1, double* __restrict__ g0, double* __restrict__ g1,
-                    double* __restrict__ hd0, double* __restrict__ hd1, double* __restrict__ c0, double* __restrict__ c1,
-                    double* __restrict__ opv_out) {
-  constexpr bool JAC = true;
-#define ACINO_SKEL_PINHOLE 0
-#include "skel_assemble_body.inc"
-#undef ACINO_SKEL_PINHOLE
-}
-__global__ void __launch_bounds__(256)
-k_skel_cov_assemble_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
-                            const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
-                            const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1,
-                            double* __restrict__ g0, double* __restrict__ g1, double* __restrict__ hd0, double* __restrict__ hd1,
-                            double* __restrict__ c0, double* __restrict__ c1, double* __restrict__ opv_out) {
-  constexpr bool JAC = true;
-#define ACINO_SKEL_PINHOLE 1
-#include "skel_assemble_body.inc"
-#undef ACINO_SKEL_PINHOLE
-}
-// The same two under the redescending loss: the block that goes to H is the Gauss-Newton curvature sum w^2 h(e) J^T J of the
-// stated objective (fte_cov.hip's definition; unlike the L1 Fisher block it depends on the residuals), g / hd / cost the robust
-// solver's own.
-#define ACINO_SKEL_ROBUST 1
-__global__ void __launch_bounds__(256)
-k_skel_cov_assemble_redesc(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
-                           const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
-                           const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1,
-                           double* __restrict__ g0, double* __restrict__ g1, double* __restrict__ hd0, double* __restrict__ hd1,
-                           double* __restrict__ c0, double* __restrict__ c1, double* __restrict__ opv_out) {
-  constexpr bool JAC = true;
-#define ACINO_SKEL_PINHOLE 0
-#include "skel_assemble_body.inc"
-#undef ACINO_SKEL_PINHOLE
-}
-__global__ void __launch_bounds__(256)
-k_skel_cov_assemble_redesc_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
-                                   const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
-                                   const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1,
-                                   double* __restrict__ g0, double* __restrict__ g1, double* __restrict__ hd0,
-                                   double* __restrict__ hd1, double* __restrict__ c0, double* __restrict__ c1,
-                                   double* __restrict__ opv_out) {
-  constexpr bool JAC = true;
-#define ACINO_SKEL_PINHOLE 1
-#include "skel_assemble_body.inc"
-#undef ACINO_SKEL_PINHOLE
-}
-#undef ACINO_SKEL_ROBUST
-#undef ACINO_SKEL_FISHER
+// ---- Fisher assembly: the solve's assembly kernel with the trailing opv_out argument, k_skel_assemble<true, PINHOLE, ROBUST, double>
+//      of skel_assemble.hpp, current iterate only (the clip words are all zero: status 0, buffer 0).  Under the redescending loss
+//      the block that goes to H is the Gauss-Newton curvature sum w^2 h(e) J^T J of the stated objective (fte_cov.hip's
+//      definition; unlike the L1 Fisher block it depends on the residuals), g / hd / cost the robust solver's own.
 
 // ---- the host half of a SkelDev (everything before the camera records, 2.9 KB) by value in the kernel-argument segment:
 //      an asynchronous copy would read the caller's stack after an early return, or after the return of an entry that does not
@@ -516,9 +468,10 @@ static int skel_cov_assemble_at(const SkelDev& h, int n_clips, int camera_model,
   const size_t NT = (size_t)h.n_frames * n_clips;
   const size_t lds_asm = skel_assemble_lds(h.n_rows, h.n_act) + sizeof(double) * h.n_rows;      // + the Fisher weights
   ACINO_REQUIRE(lds_asm <= 160 * 1024, "residual rows x active states do not fit the assembly's LDS");
-  using AssembleKernel = decltype(&k_skel_cov_assemble);
-  const AssembleKernel assembly[2][2] = {{k_skel_cov_assemble, k_skel_cov_assemble_pinhole},      // [loss][camera model]
-                                         {k_skel_cov_assemble_redesc, k_skel_cov_assemble_redesc_pinhole}};
+  using AssembleKernel = SkelFisherKernel;
+  const AssembleKernel assembly[2][2] = {                                  // [loss][camera model] of <JAC, PINHOLE, ROBUST, double>
+      {k_skel_assemble<true, false, false, double>, k_skel_assemble<true, true, false, double>},
+      {k_skel_assemble<true, false, true, double>, k_skel_assemble<true, true, true, double>}};
   static PerDeviceOnce attr;
   if (attr.first())
     for (const auto& loss : assembly)

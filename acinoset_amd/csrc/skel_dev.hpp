@@ -24,10 +24,16 @@ struct SkelDev {                   // device-resident description of one problem
   int8_t amap[ACINO_SKEL_MAX_OPS][4];              // per op: active index of the parent's phi, theta, psi (-1: none)
   unsigned long long pmask[ACINO_SKEL_MAX_OPS + 1];  // per pose slot: the ops on its path from the root
   Cam cams[ACINO_MAX_CAMS];
-  Pin pins[ACINO_MAX_CAMS];        // the pinhole model's records (k_skel_assemble_pinhole); appended: the offsets above stay
+  Pin pins[ACINO_MAX_CAMS];        // the pinhole model's records (k_skel_assemble<., true, ...>); appended: the offsets above stay
   LossC loss;                      // the redescending loss's constants (a, b, c = 3, 10, 20); appended: the offsets above stay
   int32_t loss_kind, pad1;         // ACINO_SKEL_LOSS_L1 / ACINO_SKEL_LOSS_REDESCENDING: which measurement loss the problem states
 };
+
+template <bool PINHOLE>
+__host__ __device__ __forceinline__ decltype(auto) cam_rec(const SkelDev& D, int c) {
+  if constexpr (PINHOLE) return (D.pins[c]);
+  else return (D.cams[c]);
+}
 
 struct SkelClip {                  // controller state of one clip (device)
   double F, lam, nu, gnorm, cost0, Ft, pred, step;
@@ -99,7 +105,7 @@ __device__ __forceinline__ void skel_pose_jac_col(const SkelDev& D, const double
   }
 }
 
-// dynamic LDS of the assembly kernels (skel_assemble_body.inc), without the Fisher weights of the covariance's assembly
+// dynamic LDS of the assembly kernels (skel_assemble.hpp), without the Fisher weights of the covariance's assembly
 inline size_t skel_assemble_lds(int n_rows, int P) {
   return sizeof(double) * (SK_MAXP + ACINO_SKEL_MAX_OPS * 12 + (ACINO_SKEL_MAX_OPS + 1) * 3 + SK_MAXROWS * 5 + 8 +
                            (size_t)n_rows * (P | 1));

@@ -162,7 +162,7 @@ struct SkelCovLayout {
 // observe: room for what k_skel_observability needs - a second SkelDev (the prior switched off) and the mask [n_clips][P]
 SkelCovLayout skel_cov_layout(size_t NT, int n_clips, int P, int PT, int n_ops, bool observe = false);
 // Validates the link program, uploads it and the cameras (skel_upload: nothing on the host has to outlive the call), clears
-// the clips' status words and launches k_skel_cov_assemble[_pinhole] and k_skel_cov_build on stream s: on return the
+// the clips' status words and launches k_skel_assemble<.., double> and k_skel_cov_build on stream s: on return the
 // workspace holds band, fxm, diag0 and the link operators opv of every frame at d_x.
 // observe (the layout must have been made with it): first the Fisher assembly with the prior off and k_skel_observability;
 // the mask goes to the workspace and, if given, to d_unobserved[n_clips][P].  pin (needs observe): k_skel_cov_build pins the

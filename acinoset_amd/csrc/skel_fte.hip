@@ -18,8 +18,8 @@
 //   k_skel_trial, k_skel_reduce   trial iterate, predicted reduction, the sums the controller needs
 //   k_skel_control   the Levenberg-Marquardt controller, one workgroup per clip (the sums above, accept / reject, damping)
 // acino_skel_fte_params::loss = ACINO_SKEL_LOSS_REDESCENDING swaps the measurement loss for the reference's redescending_loss
-// (build.py:382-395, commented out at :307; a, b, c = 3, 10, 20 on the same scaled residual): k_skel_assemble_redesc* are the
-// assembly body with ACINO_SKEL_ROBUST - cost rho(e), gradient w rho'(|e|) sign(e), curvature w^2 h(e) with the clipped secant h
+// (build.py:382-395, commented out at :307; a, b, c = 3, 10, 20 on the same scaled residual): k_skel_assemble<., ., true> is the
+// assembly with ROBUST - cost rho(e), gradient w rho'(|e|) sign(e), curvature w^2 h(e) with the clipped secant h
 // of common.hpp, the cheetah path's conventions - and nothing else in the iteration changes.  Far from the solution every
 // residual is beyond c, rho is constant and the step is the prior's alone: the Python layer runs the L1 solve first.
 // A call solves n_clips independent clips of n_frames frames each (same skeleton, same cameras): every kernel but the solve
@@ -32,63 +32,12 @@
 #include <cstring>
 #include <vector>
 
+#include "skel_assemble.hpp"
 #include "skel_host.hpp"
 
 namespace acino {
 
-// ---- assembly ---------------------------------------------------------------------------------------------------
-// (frame index n runs over the frames of all clips; `which` = 0: the clips' current iterate, 1: their trial iterate)
-template <bool JAC>
-__global__ void __launch_bounds__(256)
-k_skel_assemble(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which, const double* __restrict__ x0,
-                const double* __restrict__ x1, const double* __restrict__ meas, const double* __restrict__ wgt,
-                double* __restrict__ H0, double* __restrict__ H1, double* __restrict__ g0, double* __restrict__ g1,
-                double* __restrict__ hd0, double* __restrict__ hd1, double* __restrict__ c0, double* __restrict__ c1) {
-#define ACINO_SKEL_PINHOLE 0
-#include "skel_assemble_body.inc"
-#undef ACINO_SKEL_PINHOLE
-}
-
-// The OpenCV pinhole camera (cv2.projectPoints, SkelDev::pins): a kernel name of its own, so that the fisheye kernels' names
-// and code stay as they are.  Every other skeleton kernel is camera-free and serves both.
-template <bool JAC>
-__global__ void __launch_bounds__(256)
-k_skel_assemble_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
-                        const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
-                        const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1, double* __restrict__ g0,
-                        double* __restrict__ g1, double* __restrict__ hd0, double* __restrict__ hd1, double* __restrict__ c0,
-                        double* __restrict__ c1) {
-#define ACINO_SKEL_PINHOLE 1
-#include "skel_assemble_body.inc"
-#undef ACINO_SKEL_PINHOLE
-}
-
-// The redescending measurement loss (acino_skel_fte_params::loss = ACINO_SKEL_LOSS_REDESCENDING; common.hpp: redescending<>
-// with a, b, c = 3, 10, 20): the same two bodies with ACINO_SKEL_ROBUST 1, under names of their own for the same reason.
-#define ACINO_SKEL_ROBUST 1
-template <bool JAC>
-__global__ void __launch_bounds__(256)
-k_skel_assemble_redesc(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
-                       const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
-                       const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1, double* __restrict__ g0,
-                       double* __restrict__ g1, double* __restrict__ hd0, double* __restrict__ hd1, double* __restrict__ c0,
-                       double* __restrict__ c1) {
-#define ACINO_SKEL_PINHOLE 0
-#include "skel_assemble_body.inc"
-#undef ACINO_SKEL_PINHOLE
-}
-template <bool JAC>
-__global__ void __launch_bounds__(256)
-k_skel_assemble_redesc_pinhole(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, int which,
-                               const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ meas,
-                               const double* __restrict__ wgt, double* __restrict__ H0, double* __restrict__ H1,
-                               double* __restrict__ g0, double* __restrict__ g1, double* __restrict__ hd0, double* __restrict__ hd1,
-                               double* __restrict__ c0, double* __restrict__ c1) {
-#define ACINO_SKEL_PINHOLE 1
-#include "skel_assemble_body.inc"
-#undef ACINO_SKEL_PINHOLE
-}
-#undef ACINO_SKEL_ROBUST
+// ---- assembly: k_skel_assemble<JAC, PINHOLE, ROBUST> of skel_assemble.hpp (the covariance's Fisher assembly is the same template)
 
 // ---- the damped system ----------------------------------------------------------------------------------------------
 // band[n][j] (j = 0..3): block (n + j, n), [PT][PT] row-major; rhs[n][PT]; gn_part[n] = max |projected gradient|.
@@ -896,11 +845,12 @@ static int skel_solve_batch(const acino_skel_fte_params* p, int n_clips, const a
   const size_t lds_solve = sizeof(double) * ((size_t)4 * PT * (PT + 1) + 16 * PT);     // panel, ring, tv, the backward pass's partial sums
   static const bool solve_in_registers = getenv("ACINO_SKEL_OLD_SOLVE") == nullptr;     // (A/B switch: the round-5 kernel walks the band through memory)
   const int big = 160 * 1024, big_solve = 160 * 1024 - 1024;   // (the solve kernel also has a few static words)
-  using AssembleKernel = decltype(&k_skel_assemble<true>);
-  const AssembleKernel assembly[2][2][2] = {                                                    // [loss][camera model][without JAC]
-      {{k_skel_assemble<true>, k_skel_assemble<false>}, {k_skel_assemble_pinhole<true>, k_skel_assemble_pinhole<false>}},
-      {{k_skel_assemble_redesc<true>, k_skel_assemble_redesc<false>},
-       {k_skel_assemble_redesc_pinhole<true>, k_skel_assemble_redesc_pinhole<false>}}};
+  using AssembleKernel = SkelAssembleKernel;
+  const AssembleKernel assembly[2][2][2] = {             // [loss][camera model][without JAC] of <JAC, PINHOLE, ROBUST>
+      {{k_skel_assemble<true, false, false>, k_skel_assemble<false, false, false>},
+       {k_skel_assemble<true, true, false>, k_skel_assemble<false, true, false>}},
+      {{k_skel_assemble<true, false, true>, k_skel_assemble<false, false, true>},
+       {k_skel_assemble<true, true, true>, k_skel_assemble<false, true, true>}}};
   {
     static PerDeviceOnce attr;
     if (attr.first())

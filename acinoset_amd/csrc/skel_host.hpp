@@ -61,7 +61,7 @@ inline int skel_dispatch_pt(int PT, F&& f) {
   }
 }
 
-// ---- the camera model's twin of a kernel (0 fisheye: SkelDev::cams, 1 pinhole: SkelDev::pins); same signature, one launch line
+// ---- the camera model's instantiation of a kernel template (0 fisheye: SkelDev::cams, 1 pinhole: SkelDev::pins); one launch line
 template <class K>
 inline K skel_camera_kernel(int camera_model, K fisheye, K pinhole) {
   return camera_model == 1 ? pinhole : fisheye;

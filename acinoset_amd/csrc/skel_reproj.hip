@@ -98,7 +98,7 @@ k_skel_reproj(const SkelReprojArgs A, long long n_total, const double* __restric
     const double yc = Rc[3] * px + Rc[4] * py + Rc[5] * pz + tc[1];
     const double zc = Rc[6] * px + Rc[7] * py + Rc[8] * pz + tc[2];
     const bool behind = zc < 1e-6, sing = fabs(zc) < 1e-9;
-    const bool weighted = w != 0.0 && finite && !sing;            // the assembly's rule (skel_assemble_body.inc)
+    const bool weighted = w != 0.0 && finite && !sing;            // the assembly's rule (skel_assemble.hpp)
     double u = nan, v = nan, ru = nan, rv = nan, m2 = nan, s00 = nan, s01 = nan, s11 = nan;
     double hu = weighted ? 1.0 : 0.0, hv = hu;
     if (!sing) {

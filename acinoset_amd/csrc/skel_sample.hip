@@ -5,7 +5,7 @@
 // for the caller's z: Cov(delta) = A^-1 for standard-normal z, every cross-frame block included; delta is exactly 0 at pinned
 // variables.  The map is deterministic (the library owns no random generator) and delta(s) depends on z(s) alone.  Samples
 // are NOT clipped to the box: the Laplace posterior is a Gaussian, only the pinned variables are held.
-//   k_skel_cov_assemble[_pinhole], k_skel_cov_build   skel_cov.hip's (skel_cov_launch_build).  With pin_unobserved the build
+//   k_skel_assemble<.., double>, k_skel_cov_build   skel_cov.hip's (skel_cov_launch_build).  With pin_unobserved the build
 //                           step gets the clips' masks of k_skel_observability and pins those states in every frame: to the
 //                           kernels below a clip-wide pin is a bound pin, delta is exactly 0 there whatever z holds.
 //   k_skel_factor<PT>       one workgroup per clip: skel_band_factor<PT> (skel_factor.hpp, the forward half of k_skel_selinv).

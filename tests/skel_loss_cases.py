@@ -24,19 +24,22 @@ def with_loss(model, loss):
     return m
 
 
-def cov_case(golden_dir, pt=16, seed=3):
-    key = ("cov", pt)
+def cov_case(golden_dir, pt=16, seed=3, camera_model="fisheye", n_frames=None, x_seed=0):
+    """``n_frames``: fewer frames than the 12 of the sub-tree (the iterate's seed ``x_seed`` then decides whether the two CPU
+    references still agree to skel_cov_ref.bar's 1e-8: the caller asserts it)."""
+    key = ("cov", pt, camera_model, n_frames, x_seed)
     if key in _CACHE:
         return _CACHE[key]
     g, sk0, det = scases.fixture(golden_dir)
-    sc = scases.scene(g)
+    sc = scases.scene(g, camera_model)
     if pt == 48:
         sk, n = cases.generic_skeleton(sk0), 40
     else:
         sk, n = cases.sub_skeleton(cases.generic_skeleton(sk0), cases.SUB_TREES[pt]), 12
-    base = cases.make_model(g, sk, det, n, cases.SLICE_STARTS[0], "fisheye", sc)
-    x = cases.iterate(g, base)
-    rep = rref.reprojection(sk, x, base.meas, base.weights, sc, "fisheye", gate_w=1.0)
+    n = n if n_frames is None else n_frames
+    base = cases.make_model(g, sk, det, n, cases.SLICE_STARTS[0], camera_model, sc)
+    x = cases.iterate(g, base, seed=x_seed)
+    rep = rref.reprojection(sk, x, base.meas, base.weights, sc, camera_model, gate_w=1.0)
     rng = np.random.default_rng(seed)
     weighted = (rep["flags"] & 1) != 0
     meas = rep["uv"] + 0.15 * rng.standard_normal(rep["uv"].shape)
@@ -50,8 +53,8 @@ def cov_case(golden_dir, pt=16, seed=3):
     robust.meas = np.where(np.isfinite(base.meas), meas, base.meas)         # (a missing detection stays missing)
     twin = with_loss(robust, "l1")
     twin.weights = np.where(is_out, 0.0, robust.weights)
-    prob = lref.problem(sk, robust, sc)
-    prob_twin = cases.problem(sk, twin, sc)
+    prob = lref.problem(sk, robust, sc, camera_model)
+    prob_twin = cases.problem(sk, twin, sc, camera_model)
     xa = x[:, prob.ACT]
     cases.assert_observed(prob_twin, xa)
     _CACHE[key] = dict(sk=sk, scene=sc, model=robust, twin=twin, x=x, prob=prob, prob_twin=prob_twin, is_out=is_out, weighted=weighted,

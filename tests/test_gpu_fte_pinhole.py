@@ -1,4 +1,4 @@
-"""The FTE solve on the OpenCV pinhole camera (k_fte_assemble_pinhole, acino_fte_create_pinhole, camera_model="pinhole")
+"""The FTE solve on the OpenCV pinhole camera (k_fte_assemble<JAC, 0, SPLIT, true>, acino_fte_create_pinhole, camera_model="pinhole")
 against the test-side numpy reference tests/pinhole_fte_ref.py (oracle.fte on oracle.camera.project_points)."""
 import numpy as np
 import pytest
@@ -151,7 +151,7 @@ def _rms(a, b):
 @pytest.mark.parametrize("init", ["nose_line", "triangulation"])
 def test_pinhole_end_to_end_recovers_markers(mods, init):
     """Initial guess and solve on the pinhole rig (calib.triangulate_pairs_dense(model="pinhole") and
-    k_fte_assemble_pinhole), from detections made by calib.project_points with synth's noise and outliers: the ground
+    k_fte_assemble<., 0, ., true>), from detections made by calib.project_points with synth's noise and outliers: the ground
     truth is recovered as well as the fisheye solve recovers the same trajectory seen through the fisheye rig."""
     calib, fte, synth = mods
     n = 99

@@ -955,6 +955,51 @@ def test_bf16_rows_assembly_is_a_rounded_version_of_the_fp64_one(mods):
         fte.make_params(10, 6, 1 / 120, precision="fp8")
 
 
+@pytest.mark.parametrize("split", [1, 2])
+def test_every_precision_of_the_assembly_on_nine_frames_and_three_cameras(mods, monkeypatch, split):
+    """k_fte_assemble<JAC, PREC, SPLIT> for the three precisions, with the Jacobian (set_x) and without (ctx.cost), in both launch
+    shapes: seven of these twelve no other test launches (fp64 cost-only at SPLIT 1, bf16 rows cost-only, all of bf16 residuals).
+    Nine frames - the second workgroup of eight holds one - and three cameras - the split's halves are 2 + 1.  fp64 against the
+    oracle at test_fte_cost_gradient_hessian's tolerances; the mixed modes against the oracle at
+    test_bf16_rows_assembly_is_a_rounded_version_of_the_fp64_one's (they hold a fortiori for bf16 residuals, whose Jacobian rows
+    are not rounded), and each mode is told from the others by its gradient."""
+    calib, fte, synth = mods
+    monkeypatch.setenv("ACINO_ASM_SPLIT", str(split))
+    n, cams = 9, [0, 2, 4]
+    seq = synth.make_sequence(n, "trot", seed=5)
+    det = seq["det"][:, cams]
+    rig = tuple(a[cams] for a in (seq["K"], seq["D"], seq["R"], seq["t"]))
+    prob = ofte.FTEProblem(det[..., :2], det[..., 2], *rig, seq["Ts"])
+    rng = np.random.default_rng(2)
+    xa = np.clip(seq["q_true"][:, ofk.ACTIVE] + rng.normal(0, 0.02, (n, 25)), prob.lo, prob.hi)
+    xb = np.clip(xa + rng.normal(0, 0.01, xa.shape), prob.lo, prob.hi)
+    Fo, go, Ho, _ = prob.evaluate(xa)
+    Fb = prob.evaluate(xb, need_jac=False)[0]
+    idx = np.arange(25)
+    Ho[:, idx, idx] += 2 * prob.q_w[None, :] * prob.s_band()[0][:, None]
+    got = {}
+    for prec in ("f64", "bf16", "bf16_residuals"):
+        ctx = fte.FTEContext(det, *rig, seq["Ts"], precision=prec)
+        try:
+            ctx.set_x(xa)
+            cost, cost_b = ctx.state()["cost"], ctx.cost(xb)
+            g, h = (a.cpu().numpy() for a in ctx.grad_hess())
+        finally:
+            ctx.close()
+        got[prec] = g
+        e = dict(cost=abs(cost - Fo) / abs(Fo), cost_b=abs(cost_b - Fb) / abs(Fb), g_max=np.abs(g - go).max() / np.abs(go).max(),
+                 g=np.linalg.norm(g - go) / np.linalg.norm(go), h_max=np.abs(h - Ho).max() / np.abs(Ho).max(),
+                 h=np.linalg.norm(h - Ho) / np.linalg.norm(Ho))
+        print(f"SPLIT {split}, {prec}: " + ", ".join(f"{k} {v:.2e}" for k, v in e.items()))
+        if prec == "f64":
+            assert e["cost"] < 1e-12 and e["cost_b"] < 1e-12 and e["g_max"] < 1e-11 and e["h_max"] < 1e-11
+        else:
+            assert e["cost"] < 3e-6 and e["cost_b"] < 3e-6                     # fp32 projection, fp64 sum
+            assert 0 < e["g_max"] < 2e-2 and e["g"] < 4e-3 and e["h"] < 4e-3
+    assert not np.array_equal(got["bf16"], got["f64"]) and not np.array_equal(got["bf16_residuals"], got["f64"])
+    assert not np.array_equal(got["bf16"], got["bf16_residuals"])
+
+
 def test_config5_bf16_rows_solve_lands_on_the_fp64_solution(mods):
     """BASELINE config 5's FTE half at its size: 64 clips x 1 000 frames as one chain (fte_solve_clips), solved with
     bf16 residual / Jacobian rows + fp32 accumulation and with fp64, from the same nose-line start.  (The smoothness

@@ -1,7 +1,7 @@
 """GPU (-m gpu): the EKF + RTS smoother, the skeleton FTE and the dense bundle adjustment on the OpenCV pinhole camera.
 
-The EKF (k_ekf_forward_pinhole) against oracle.ekf with the pinhole measurement function (tests/pinhole_ekf_ref.py), the
-skeleton solve (k_skel_assemble_pinhole) against oracle.skel_fte's Levenberg-Marquardt with the pinhole camera
+The EKF (k_ekf_forward<true>) against oracle.ekf with the pinhole measurement function (tests/pinhole_ekf_ref.py), the
+skeleton solve (k_skel_assemble<., true, false>) against oracle.skel_fte's Levenberg-Marquardt with the pinhole camera
 (tests/pinhole_skel_ref.py), both at the tolerances of their fisheye tests; recovery of synthetic motion; the dense SBA and
 the config 5 chain on a pinhole rig against the scipy oracle; and the default (no keyword) calls equal the fisheye ones bit for
 bit.  The pinhole model is pinned to oracle/camera.py's restatement of cv2.projectPoints, not to OpenCV itself."""

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the skeleton FTE under the redescending measurement loss (build_model(loss="redescending");
-k_skel_assemble_redesc*, k_skel_cov_assemble_redesc*, k_skel_reproj<., true>) against the CPU reference tests/skel_loss_ref.py.
+k_skel_assemble<., ., true> and its Fisher form <true, ., true, double>, k_skel_reproj<., true>) against the CPU reference tests/skel_loss_ref.py.
 
     1  the HIP solve walks oracle.fte.lm_solve's path on the robust problem, at the tolerances of the L1 path test
        (tests/test_skel_fte.py): from the saturated straight-line start, from the GPU's own L1 end point, on a pinhole rig
@@ -194,6 +194,32 @@ def test_covariance_is_the_curvature_of_the_robust_objective(gpu_lib, golden_dir
     assert e_a <= tol and e_b <= tol and e_p <= tol and e_s <= tol
     assert 0.99 <= ratio.min() and ratio.max() <= 1.01 and 0.99 <= ratio_p.min() and ratio_p.max() <= 1.01
     assert (plain["std_pos"] <= twin["std_pos"] * (1 + 1e-12)).all()       # L1 counts the outliers fully: its bars only shrink
+
+
+def test_covariance_of_the_robust_objective_on_the_pinhole_rig(gpu_lib, golden_dir):
+    """k_skel_assemble<true, true, true, double>, the Fisher assembly under the redescending loss on the pinhole camera, which
+    no other test launches: the PT 16 sub-tree on 5 frames (the shortest clip with a third difference) and the fixture's 2
+    cameras, judged as the test above.  With 5 frames most iterates leave the two CPU references further apart than the bar's
+    1e-8 condition (d0 2e-8 .. 1e-5 for the seeds 0 .. 5 of skel_cov_cases.iterate); seed 82 is one that does not (2.6e-9, the
+    12-frame case's figure) - chosen on the CPU references alone."""
+    from acinoset_amd import build
+    c = lcases.cov_case(golden_dir, 16, camera_model="pinhole", n_frames=5, x_seed=82)
+    model, x, r, act = c["model"], c["x"], c["ref"], c["prob"].ACT
+    assert model.camera_model == "pinhole" and model.loss == "redescending" and model.N == 5 and model.meas.shape[1] == 2
+    assert r["d0"] <= 1e-8 and c["is_out"].sum() >= 1
+    tol = cref.bar(r["d0"])
+    out = build.model_covariance([model], [x])[0]
+    cov = out["cov_x"][:, act[:, None], act[None, :]]
+    e_a, e_b = cref.rel_err(cov, r["Sa"]), cref.rel_err(cov[r["frames"]], r["Sb"])
+    e_p = cref.rel_err(out["cov_pos"].reshape(model.N, -1), r["cov_pos"].reshape(model.N, -1))
+    e_s = float(np.max(np.abs(out["std_pos"] - r["std_pos"]) / r["std_pos"]))
+    print(f"pinhole, 5 frames: d0 {r['d0']:.2e}, bar {tol:.2e}; cov_x vs dense {e_a:.2e}, vs probes {e_b:.2e}; cov_pos {e_p:.2e}; "
+          f"std_pos {e_s:.2e}; {int(c['is_out'].sum())} outliers of {int(c['weighted'].sum())}")
+    assert out["status"] == 0
+    assert e_a <= tol and e_b <= tol and e_p <= tol and e_s <= tol
+    # the outliers carry no information (h = 0): the matrix is not the L1 Fisher matrix of the same detections
+    plain = build.model_covariance([lcases.with_loss(model, "l1")], [x])[0]
+    assert (plain["std_pos"] < out["std_pos"]).any()
 
 
 def test_rates_and_samples_share_the_robust_matrix(gpu_lib, golden_dir):

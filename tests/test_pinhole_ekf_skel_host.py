@@ -5,6 +5,7 @@ references (tests/pinhole_ekf_ref.py, tests/pinhole_skel_ref.py) are self-consis
 import ctypes as C
 import json
 import os
+import re
 
 import numpy as np
 import pytest
@@ -43,8 +44,15 @@ def test_new_entries_are_declared_exported_and_bound_like_their_fisheye_twins():
         fn, fn_twin = getattr(h, name), getattr(h, twin)
         assert fn.restype is C.c_int and fn.argtypes == fn_twin.argtypes
     assert h.acino_abi_version() == 3 and _lib.ABI_VERSION == 3
-    for inc in ("ekf_forward_body.inc", "skel_assemble_body.inc"):
-        assert inc in _lib.HEADERS                       # part of source_hash() and the object cache key
+    # every file a source or header includes is part of source_hash() and the object cache key
+    csrc = os.path.join(_lib._HERE, "csrc")
+    listed = {os.path.basename(h) for h in _lib.HEADERS}
+    assert "skel_assemble.hpp" in listed and "pinhole.hpp" in listed
+    for name in _lib.SOURCES + [h for h in _lib.HEADERS if os.sep not in h]:
+        with open(os.path.join(csrc, name)) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M):
+                assert os.path.basename(inc) in listed, (name, inc)
+    assert sorted(n for n in os.listdir(csrc) if n.endswith((".hpp", ".inc"))) == sorted(listed - {"acinoset_hip.h"})
 
 
 def _ekf_params(n_cams=6):
