@@ -239,6 +239,79 @@ def triangulate_pairs_dense(det, thresh, k_arr, d_arr, r_arr, t_arr, return_mask
     return _ret(tri, det), _ret(npairs, det), _ret(mask, det)
 
 
+R_MEAS = 5.0        # the FTE's measurement sigma in pixels (fte.R_MEAS, asserted equal by the tests): default sigma_px
+
+
+def triangulate_multiview_dense(det, thresh, k_arr, d_arr, r_arr, t_arr, model="fisheye", f_scale=5.0, sigma_px=R_MEAS,
+                                max_iter=60, xtol=1e-10, cov_cams=None, return_sens=False):
+    """Robust N-view triangulation of det[N,C,L,3] (x, y, likelihood) with an error bar per point: per (frame, marker) the
+    minimiser of the per-coordinate Cauchy cost (scale ``f_scale`` px) of the calibration-level reprojection residuals over
+    ALL cameras with a valid detection (likelihood > thresh, finite pixel, undistortion succeeded) - not only adjacent pairs -,
+    from the N-view ray midpoint, by one damped Gauss-Newton solver per point in one launch (include/acinoset_hip.h:
+    acino_triangulate_multiview).  ``model``: "fisheye" (project_points_fisheye, with the skew) or "pinhole"
+    (project_points).  Returns a dict:
+
+      points [N,L,3]; cov [N,L,3,3] = sigma_px^2 (sum J^T W J)^-1, W the Cauchy IRLS weights at the point - the matrix of
+      ``sba.covariance(optimize_cameras=False)``; std [N,L] = sqrt(trace cov) in metres; n_views, status, iters uint8 [N,L]
+      (status 0 stopped on ``xtol``, 1 ``max_iter`` reached, 2 fewer than two views, 3 numeric; points / cov / std / wssr are
+      NaN for 2 and 3); wssr [N,L] = sum w r^2; sigma2_hat = sum wssr / (2 sum n_views - 3 P) over the P points returned.
+
+    The default ``sigma_px`` is the FTE's R_MEAS, so the bars compare with ``fte_solve(..., return_cov=True)``.  With
+    ``cov_cams`` (the forms ``fte_solve`` takes: [6C,6C] per camera (dw, dt), or the dict of ``sba.covariance``) or
+    ``return_sens``: sens_cams [N,L,3,6C], the derivative of the point with respect to every camera's extrinsics (exact zeros
+    for the cameras that do not see it), and with ``cov_cams`` cov_calib = S Sigma S^T [N,L,3,3], std_calib and std_total =
+    sqrt(std^2 + std_calib^2).  numpy in, numpy out; CUDA tensors in, CUDA tensors out with no host copy."""
+    if model not in CAMERAS:
+        raise ValueError(f"model must be one of {CAMERA_MODELS}")
+    shape = tuple(det.shape) if hasattr(det, "shape") else np.shape(det)
+    if len(shape) != 4 or shape[-1] != 3:
+        raise ValueError("det must be [N, C, L, 3]")
+    N, Cn, L, _ = shape
+    if not 1 <= Cn <= _lib.MAX_CAMS:
+        raise ValueError(f"det holds {Cn} cameras: 1..{_lib.MAX_CAMS} are supported")
+    if len(k_arr) != Cn:
+        raise ValueError("camera count mismatch")
+    for name, val in (("f_scale", f_scale), ("sigma_px", sigma_px), ("xtol", xtol)):
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError(f"{name} must be finite and > 0")
+    if int(max_iter) != max_iter or not 1 <= max_iter <= 255:
+        raise ValueError("max_iter must be an integer in 1..255")
+    if np.isnan(thresh):
+        raise ValueError("thresh must not be NaN")
+    sigma_c = cov_cams_matrix(cov_cams, Cn)
+    recs = camera_records(model, k_arr, d_arr, r_arr, t_arr)
+    want_sens = return_sens or sigma_c is not None
+    dev = _dev()
+    d = _to_dev(det, dev)
+    cams = torch.as_tensor(recs, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    pts, cov, wssr = torch.empty((N, L, 3), **f64), torch.empty((N, L, 3, 3), **f64), torch.empty((N, L), **f64)
+    nviews, status, iters = torch.empty((N, L), **u8), torch.empty((N, L), **u8), torch.empty((N, L), **u8)
+    sens = torch.empty((N, L, 3, 6 * Cn), **f64) if want_sens else None
+    prm = _lib.TriMvParams(CAMERAS[model].code, int(max_iter), float(thresh), float(f_scale), float(sigma_px), float(xtol))
+    check(lib().acino_triangulate_multiview(prm, ptr(d), N, Cn, L, ptr(cams), ptr(pts), ptr(cov), ptr(wssr), ptr(nviews),
+                                            ptr(status), ptr(iters), ptr(sens), stream_ptr()))
+    var = (cov[..., 0, 0] + cov[..., 1, 1]) + cov[..., 2, 2]
+    got = status < 2
+    dof = 2 * (nviews * got).sum(dtype=torch.float64) - 3 * got.sum(dtype=torch.float64)
+    sigma2 = torch.where(got, wssr, torch.zeros_like(wssr)).sum() / dof
+    out = dict(points=pts, cov=cov, std=torch.sqrt(var), n_views=nviews, status=status, iters=iters, wssr=wssr,
+               sigma2_hat=sigma2)
+    if want_sens:
+        out["sens_cams"] = sens
+    if sigma_c is not None:
+        cc = torch.einsum("nlia,ab,nljb->nlij", sens, torch.as_tensor(sigma_c, device=dev), sens)
+        cc = 0.5 * (cc + cc.transpose(-1, -2))
+        vc = (cc[..., 0, 0] + cc[..., 1, 1]) + cc[..., 2, 2]
+        out.update(cov_calib=cc, std_calib=torch.sqrt(vc), std_total=torch.sqrt(var + vc))
+    if isinstance(det, torch.Tensor):
+        return out
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    out["sigma2_hat"] = float(out["sigma2_hat"])
+    return out
+
+
 def reproject_residuals(pts3, det, thresh, k_arr, d_arr, r_arr, t_arr):
     """pts3[N,L,3], det[N,C,L,3] -> residuals[N,C,L,2] (NaN where invalid) and
     sums = (count, sum r, sum r^2, 0.5*sum log1p(r^2))."""
@@ -357,3 +430,25 @@ def get_pairwise_3d_points_from_df(points_2d_df, k_arr, d_arr, r_arr, t_arr, tri
     n_i, l_i = np.nonzero(has)
     return pd.DataFrame({"frame": np.asarray(frames, dtype=np.float64)[n_i], "marker": markers[l_i],
                          "x": tri[n_i, l_i, 0], "y": tri[n_i, l_i, 1], "z": tri[n_i, l_i, 2]})
+
+
+def get_multiview_3d_points_from_df(points_2d_df, k_arr, d_arr, r_arr, t_arr, triangulate_func=None, **kw):
+    """``triangulate_multiview_dense`` of a long detections DataFrame, with the conventions of
+    ``get_pairwise_3d_points_from_df``: every row present is valid, the rows of the result are sorted by (frame, marker),
+    ``frame`` is float64, and ``triangulate_func`` (``triangulate_points_fisheye``, the default, or ``triangulate_points``)
+    selects the camera model.  Columns frame, marker, x, y, z, std, n_views, for the points with status 0 or 1 - every marker
+    seen by two or more cameras, adjacent or not.  ``kw``: the keywords of ``triangulate_multiview_dense`` (f_scale, sigma_px,
+    max_iter, xtol).  Raises KeyError when there is no such point."""
+    import pandas as pd
+    model = camera_model_of(project_func=triangulate_func, seams=(triangulate_points_fisheye, triangulate_points))
+    det, frames, markers = dataframe_to_dense(points_2d_df, len(k_arr))
+    det[..., 2] = np.where(np.isfinite(det[..., 2]), np.inf, -np.inf)   # presence == valid
+    out = triangulate_multiview_dense(det, 0.0, k_arr, d_arr, r_arr, t_arr, model=model, **kw)
+    has = out["status"] < 2
+    if not has.any():
+        raise KeyError("['frame', 'marker'] not in index")
+    n_i, l_i = np.nonzero(has)
+    pts = out["points"]
+    return pd.DataFrame({"frame": np.asarray(frames, dtype=np.float64)[n_i], "marker": markers[l_i],
+                         "x": pts[n_i, l_i, 0], "y": pts[n_i, l_i, 1], "z": pts[n_i, l_i, 2], "std": out["std"][n_i, l_i],
+                         "n_views": out["n_views"][n_i, l_i]})

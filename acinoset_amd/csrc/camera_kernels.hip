@@ -16,27 +16,6 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
-// ---- pinhole (rational) model (record: pinhole.hpp) ---------------------------------------------
-__device__ __forceinline__ void undistort_pinhole_pt(const Pin& c, double u, double v, double& x, double& y) {
-  const double* k = c.d;
-  double x0 = (u - c.cx) / c.fx, y0 = (v - c.cy) / c.fy;
-  x = x0;
-  y = y0;
-  for (int j = 0; j < 5; ++j) {  // OpenCV default criteria (MAX_ITER, 5, 0.01)
-    double r2 = x * x + y * y;
-    double icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
-    if (icdist < 0) {
-      x = x0;
-      y = y0;
-      break;
-    }
-    double dx = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x) + k[8] * r2 + k[9] * r2 * r2;
-    double dy = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y + k[10] * r2 + k[11] * r2 * r2;
-    x = (x0 - dx) * icdist;
-    y = (y0 - dy) * icdist;
-  }
-}
-
 __global__ void __launch_bounds__(256) k_undistort_fisheye(const double* __restrict__ pts, int64_t m, const double* __restrict__ cam,
                                     double* __restrict__ out, int max_iter, double eps) {
   __shared__ Cam c;
@@ -378,13 +357,6 @@ k_reproject_residuals(const double* __restrict__ pts3, const double* __restrict_
       atomicAdd(&sums[threadIdx.x], t);
     }
   }
-}
-
-static inline int grid_for(int64_t work, int block) {
-  int64_t g = (work + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > 256 * 8) g = 256 * 8;  // 256 CUs x 8 blocks, grid-stride beyond
-  return (int)g;
 }
 
 }  // namespace acino

@@ -40,6 +40,14 @@ void set_error(const char* fmt, ...);
     }                                                                                    \
   } while (0)
 
+// Workgroups of a grid-stride launch over ``work`` items, ``block`` per workgroup.
+inline int grid_for(int64_t work, int block) {
+  int64_t g = (work + block - 1) / block;
+  if (g < 1) g = 1;
+  if (g > 256 * 8) g = 256 * 8;  // 256 CUs x 8 blocks, grid-stride beyond
+  return (int)g;
+}
+
 // ---- fisheye camera record (24 doubles, see acinoset_hip.h) -------------------------------
 struct Cam {
   double fx, fy, cx, cy;

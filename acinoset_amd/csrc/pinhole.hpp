@@ -52,6 +52,27 @@ __device__ __forceinline__ void pinhole_project(const Pin& c, double xc, double 
   }
 }
 
+// cv2.undistortPoints of one pixel (no R / P): the 5-step fixed point of OpenCV's default criteria (MAX_ITER, 5, 0.01).
+__device__ __forceinline__ void undistort_pinhole_pt(const Pin& c, double u, double v, double& x, double& y) {
+  const double* k = c.d;
+  double x0 = (u - c.cx) / c.fx, y0 = (v - c.cy) / c.fy;
+  x = x0;
+  y = y0;
+  for (int j = 0; j < 5; ++j) {
+    double r2 = x * x + y * y;
+    double icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
+    if (icdist < 0) {
+      x = x0;
+      y = y0;
+      break;
+    }
+    double dx = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x) + k[8] * r2 + k[9] * r2 * r2;
+    double dy = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y + k[10] * r2 + k[11] * r2 * r2;
+    x = (x0 - dx) * icdist;
+    y = (y0 - dy) * icdist;
+  }
+}
+
 // ---- the camera model as a template parameter: PINHOLE ? Pin : Cam.  The structs that hold both kinds of record give the
 //      record of camera ci by cam_rec<PINHOLE>(owner, ci) (fte_kernels.hpp: FteConst, skel_dev.hpp: SkelDev).
 template <bool PINHOLE>

@@ -14,6 +14,8 @@
  *   acino_triangulate_pairs_pinhole  get_pairwise_3d_points_from_df   src/calib/calib.py:394-423 (triangulate_func = triangulate_points; app.py:215-218)
  *   acino_reproject_residuals        project(triangulate(.)) - pts    src/calib/calib.py:312-316 (cost_func_points_only)
  *   acino_triangulate_reproject      the two above fused (one pass over the detections)
+ *   acino_triangulate_multiview      (no counterpart) robust N-view triangulation with a covariance per point, from the
+ *                                    same dense detections as acino_triangulate_pairs
  *   acino_cheetah_fk                 pose_to_3d                       src/all_optimizations.py:66-190
  *   acino_fte_*                      the Pyomo model + opt.solve()    src/all_optimizations.py:283-556
  *
@@ -122,6 +124,37 @@ int acino_triangulate_reproject(const double* d_det, int64_t n_frames, int n_cam
 int acino_reproject_residuals(const double* d_pts3, const double* d_det, int64_t n_frames, int n_cams,
                               int n_markers, double thresh, const double* d_cams24, double* d_res,
                               double* d_sums, void* stream);
+
+/* ---- robust N-view triangulation with a covariance per point (csrc/triangulate_mv.hip) -------
+ * Per (frame, marker), over V = the cameras whose detection has likelihood > thresh, finite pixels and a successful
+ * undistortion (fisheye: the OpenCV criteria (10, 1e-8); pinhole: always): the minimiser X of
+ *   F(X) = sum_{c in V} 0.5 f^2 (log1p(r_u^2 / f^2) + log1p(r_v^2 / f^2)),  r = pi_c(X) - (u, v),  f = f_scale,
+ * pi_c the calibration-level projection (acino_project_fisheye with the record's skew / acino_project_pinhole).  Start: the
+ * N-view ray midpoint.  Iteration: a damped Gauss-Newton per point on sum J^T h J, h = max(rho'', 0.1 w); a trial that
+ * raises F or leaves the front of a camera of V is rejected; it ends on a step shorter than xtol [m] or after max_iter
+ * trials.  One launch, no synchronisation.  At the returned X, with W the Cauchy IRLS weights w = 1 / (1 + r^2 / f^2):
+ *   d_points[N][L][3]
+ *   d_cov[N][L][3][3]    sigma_px^2 (sum J_c^T W_c J_c)^-1, symmetric bit for bit (the matrix of acino_sba_covariance with
+ *                        the cameras fixed)
+ *   d_wssr[N][L]         sum w r^2
+ *   d_nviews[N][L]       |V|
+ *   d_status[N][L]       0 stopped on xtol, 1 max_iter reached, 2 fewer than two views, 3 numeric (the start's matrix or A
+ *                        with a pivot d_i of L D L^T at or below 1e-12 of its trace, or a non-finite value);
+ *                        points, cov, wssr (and sens) are NaN for 2 and 3
+ *   d_iters[N][L]        trials made
+ *   d_sens[N][L][3][6C]  -A^-1 [G_0 .. G_{C-1}], G_c = J_c^T W_c Jc_c, Jc_c the derivative with respect to (dw, dt) under
+ *                        R <- exp([dw]x) R, t <- t + dt (the parametrisation of acino_sba_covariance); the columns of the
+ *                        cameras outside V are exactly 0
+ * d_cov, d_wssr, d_iters, d_sens may be NULL.  1 <= n_cams <= ACINO_MAX_CAMS. */
+typedef struct acino_tri_mv_params {
+  int32_t camera_model;   /* 0 fisheye (24-double records), 1 pinhole (32) */
+  int32_t max_iter;       /* 1..255 */
+  double thresh, f_scale, sigma_px, xtol;
+} acino_tri_mv_params;
+size_t acino_sizeof_tri_mv_params(void);
+int acino_triangulate_multiview(const acino_tri_mv_params* prm, const double* d_det, int64_t n_frames, int n_cams,
+                                int n_markers, const double* d_cams, double* d_points, double* d_cov, double* d_wssr,
+                                uint8_t* d_nviews, uint8_t* d_status, uint8_t* d_iters, double* d_sens, void* stream);
 
 /* ---- cheetah forward kinematics (a-4) ---------------------------------------------------------
  * d_q[N][45] full state -> d_pos[N][20][3]. */
