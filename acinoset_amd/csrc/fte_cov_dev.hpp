@@ -53,6 +53,23 @@ __device__ __forceinline__ double rate_jac(const CovFrame& F, int l, int i, int 
   return i == 0 ? w[1] * d2 - w[2] * d1 : (i == 1 ? w[2] * d0 - w[0] * d2 : w[0] * d1 - w[1] * d0);
 }
 
+// rate_jac in two halves, for a caller that walks the tables once and evaluates many frames: the index into F.pos of the
+// pivot of angle p (>= 3) when marker l hangs on it, else -1 ...
+__device__ __forceinline__ int rate_pivot(int l, int p) {
+  const int ga = c_state_grp[p];
+  return ((c_ancmask[cov_marker_grp(l)] >> ga) & 1) ? c_grp_pivot[ga] : -1;
+}
+// ... and d FK_l / d x_p = omega_p x (p_l - pivot), all three components
+__device__ __forceinline__ void rate_cross(const CovFrame& F, int l, int p, int pivot, double out[3]) {
+  const double* w = F.om[p - 3];
+  const double* c = F.pos[pivot];
+  const double* m = F.pos[l];
+  const double d0 = m[0] - c[0], d1 = m[1] - c[1], d2 = m[2] - c[2];
+  out[0] = w[1] * d2 - w[2] * d1;
+  out[1] = w[2] * d0 - w[0] * d2;
+  out[2] = w[0] * d1 - w[1] * d0;
+}
+
 // Host: the opt-in of one kernel to `bytes` of dynamic LDS on the current device.  Made per call, beside the launch.
 template <class Kernel>
 inline hipError_t set_dyn_lds(Kernel* kernel, size_t bytes) {

@@ -634,6 +634,104 @@ def triangulation_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, camera_model
     return x0
 
 
+def pose_fit(points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01, min_markers=1, max_iter=100, ftol=1e-10,
+             xtol=1e-10, lam0=1e-3, return_cov=True):
+    """Per-frame pose of the cheetah model from 3-D marker points with a covariance each (include/acinoset_hip.h:
+    acino_cheetah_pose_fit): per frame the minimiser over the 25 active states, inside the box of ``bounds45()[ACTIVE]``, of
+
+        F(x) = 1/2 sum_{l enters} (FK_l(x) - y_l)^T W_l (FK_l(x) - y_l) + 1/2 sum_{p = 3..24} (x_p - m_p)^2 / prior_sigma^2
+
+    by one projected Levenberg-Marquardt per frame (the controller of the FTE solve) in one launch.  ``points`` [N,20,3] in
+    metres and ``cov`` [N,20,3,3] are the ``points`` / ``cov`` of ``calib.triangulate_multiview_dense``, whose dict is
+    accepted in place of ``points``; a marker enters when its values are finite and its covariance positive definite
+    (W = cov^-1), and with ``cov=None`` every finite point enters with W = I / sigma_iso^2.  ``x0`` [N,25] is the start and,
+    clipped to the box, the centre m of the ridge on the 22 angles (``prior_sigma`` rad), which defines the states no
+    entering marker moves; default: the head at the mean of the entering markers among eyes and nose (of all entering markers
+    without them), psi_0 along neck_base -> nose, every other state 0.  Returns a dict:
+
+      x [N,25], x_full [N,45], positions [N,20,3], cost [N]; n_markers, status, iters uint8 [N] (status 0 stopped on
+      ``ftol`` / ``xtol``, 1 ``max_iter`` reached or lam overflowed, 2 fewer than ``min_markers`` enter, 3 numeric; every
+      floating-point output of a frame is NaN for 2 and 3); pinned uint8 [N,25], the bound-active states at x; and with
+      ``return_cov`` cov_x [N,25,25] = A_free^-1 (rows and columns of pinned states exactly 0), cov_positions [N,20,3,3] =
+      J cov_x J^T and std_positions [N,20] in metres.
+
+    numpy in, numpy out; CUDA tensors in, CUDA tensors out with no host copy."""
+    if isinstance(points, dict):
+        if cov is not None:
+            raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
+        points, cov = points["points"], points["cov"]
+    shape = tuple(points.shape) if hasattr(points, "shape") else np.shape(points)
+    if len(shape) != 3 or shape[1:] != (N_MARKERS, 3):
+        raise ValueError("points must be [N, 20, 3]")
+    N = shape[0]
+    if cov is not None and (tuple(cov.shape) if hasattr(cov, "shape") else np.shape(cov)) != (N, N_MARKERS, 3, 3):
+        raise ValueError("cov must be [N, 20, 3, 3]")
+    if x0 is not None and (tuple(x0.shape) if hasattr(x0, "shape") else np.shape(x0)) != (N, N_ACTIVE):
+        raise ValueError("x0 must be [N, 25] (the active states)")
+    for name, val in (("prior_sigma", prior_sigma), ("sigma_iso", sigma_iso), ("ftol", ftol), ("xtol", xtol), ("lam0", lam0)):
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError(f"{name} must be finite and > 0")
+    if int(max_iter) != max_iter or not 1 <= max_iter <= 255:
+        raise ValueError("max_iter must be an integer in 1..255")
+    if int(min_markers) != min_markers or not 1 <= min_markers <= N_MARKERS:
+        raise ValueError("min_markers must be an integer in 1..20")
+    dev = calib._dev()
+    pts = calib._to_dev(points, dev)
+    cv = None if cov is None else calib._to_dev(cov, dev)
+    xs = None if x0 is None else calib._to_dev(x0, dev)
+    f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+    x, cost, pos = torch.empty((N, N_ACTIVE), **f64), torch.empty((N,), **f64), torch.empty((N, N_MARKERS, 3), **f64)
+    nm, status, iters, pinned = (torch.empty(sh, **u8) for sh in ((N,), (N,), (N,), (N, N_ACTIVE)))
+    cov_x = torch.empty((N, N_ACTIVE, N_ACTIVE), **f64) if return_cov else None
+    cov_pos = torch.empty((N, N_MARKERS, 3, 3), **f64) if return_cov else None
+    std_pos = torch.empty((N, N_MARKERS), **f64) if return_cov else None
+    prm = _lib.PoseFitParams(int(max_iter), int(min_markers), float(lam0), float(ftol), float(xtol), float(prior_sigma),
+                             float(sigma_iso))
+    check(lib().acino_cheetah_pose_fit(prm, ptr(pts), ptr(cv), ptr(xs), N, ptr(x), ptr(cost), ptr(nm), ptr(status), ptr(iters),
+                                       ptr(pinned), ptr(cov_x), ptr(pos), ptr(cov_pos), ptr(std_pos), stream_ptr()))
+    x_full = torch.zeros((N, N_STATES), **f64)
+    x_full[:, torch.as_tensor(ACTIVE, device=dev)] = x
+    out = dict(x=x, x_full=x_full, positions=pos, cost=cost, n_markers=nm, status=status, iters=iters, pinned=pinned)
+    if return_cov:
+        out.update(cov_x=cov_x, cov_positions=cov_pos, std_positions=std_pos)
+    if isinstance(points, torch.Tensor):
+        return out
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+PSI_COLUMNS = [int(np.nonzero(ACTIVE == PSI + k)[0][0]) for k in (0, 1, 3, 4, 5)]     # the psi states among the active ones
+
+
+def fill_unfitted_frames(x, fitted):
+    """The rule of ``pose_fit_init`` for the frames without a fit: x [N,25] with the rows where ``fitted`` is False filled by
+    np.interp over the frames that have one (held flat at the ends), the five psi columns unwrapped over the fitted frames
+    first.  ValueError when no frame has a fit."""
+    x = np.array(x, dtype=np.float64, copy=True)
+    fitted = np.asarray(fitted, dtype=bool)
+    if not fitted.any():
+        raise ValueError("no frame has a pose fit: no marker was triangulated in the whole sequence")
+    idx = np.arange(len(x))
+    for p in range(x.shape[1]):
+        col = np.unwrap(x[fitted, p]) if p in PSI_COLUMNS else x[fitted, p]
+        x[:, p] = np.interp(idx, idx[fitted], col)
+    return x
+
+
+def pose_fit_init(det, k_arr, d_arr, r_arr, t_arr, dlc_thresh, camera_model="fisheye", **fit_kw):
+    """Per-frame initial guess from a pose fit of every frame: ``calib.triangulate_multiview_dense`` of the detections, then
+    ``pose_fit`` of its points with their covariances (``fit_kw`` goes to ``pose_fit``); the frames without a fit (status >= 2)
+    are filled by ``fill_unfitted_frames``.  All 25 active states start near the markers, not only the head and psi_0 - the
+    redescending loss of the FTE gives a detection further than c = 20 from its prediction neither gradient nor curvature.
+    Returns x0[N,45] (numpy).  ``camera_model`` as in nose_line_init."""
+    tri = calib.triangulate_multiview_dense(det, dlc_thresh, k_arr, d_arr, r_arr, t_arr, model=camera_model)
+    fit = pose_fit(tri, return_cov=False, **fit_kw)
+    host = (lambda a: a.cpu().numpy()) if isinstance(fit["x"], torch.Tensor) else (lambda a: a)
+    xa = fill_unfitted_frames(host(fit["x"]), host(fit["status"]) < 2)
+    x0 = np.zeros((xa.shape[0], N_STATES))
+    x0[:, ACTIVE] = np.clip(xa, *(b[ACTIVE] for b in bounds45()))
+    return x0
+
+
 # Contexts kept alive between solves (fte_solve(..., reuse_context=True)): a second sequence of the same shape on the same rig
 # finds its workspace, its uploaded constants and its captured hipGraph in place - what is left outside the LM loop is the
 # copy of the detections, the initial evaluation and the outputs.  One context per key; clear_context_cache() frees them.
@@ -699,8 +797,10 @@ def _initial_x0(det, x0, init, rig, dlc_thresh, start_frame, camera_model, shape
             x0 = nose_line_init(det, *rig, dlc_thresh, start_frame=start_frame, camera_model=camera_model)
         elif init == "triangulation":
             x0 = triangulation_init(det, *rig, dlc_thresh, camera_model=camera_model)
+        elif init == "pose_fit":
+            x0 = pose_fit_init(det, *rig, dlc_thresh, camera_model=camera_model)
         else:
-            raise ValueError("init must be 'nose_line' or 'triangulation'")
+            raise ValueError("init must be 'nose_line', 'triangulation' or 'pose_fit'")
     x0 = np.asarray(x0.cpu().numpy() if isinstance(x0, torch.Tensor) else x0, dtype=np.float64)
     if x0.shape != (det.shape[0], N_STATES):
         raise ValueError(shape_error)

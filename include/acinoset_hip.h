@@ -16,6 +16,8 @@
  *   acino_triangulate_reproject      the two above fused (one pass over the detections)
  *   acino_triangulate_multiview      (no counterpart) robust N-view triangulation with a covariance per point, from the
  *                                    same dense detections as acino_triangulate_pairs
+ *   acino_cheetah_pose_fit           (no counterpart) per-frame pose with error bars from 3-D marker points and their
+ *                                    covariances (the outputs of acino_triangulate_multiview)
  *   acino_cheetah_fk                 pose_to_3d                       src/all_optimizations.py:66-190
  *   acino_fte_*                      the Pyomo model + opt.solve()    src/all_optimizations.py:283-556
  *
@@ -155,6 +157,42 @@ size_t acino_sizeof_tri_mv_params(void);
 int acino_triangulate_multiview(const acino_tri_mv_params* prm, const double* d_det, int64_t n_frames, int n_cams,
                                 int n_markers, const double* d_cams, double* d_points, double* d_cov, double* d_wssr,
                                 uint8_t* d_nviews, uint8_t* d_status, uint8_t* d_iters, double* d_sens, void* stream);
+
+/* ---- per-frame cheetah pose fit from 3-D markers with a covariance each (csrc/pose_fit.hip) -------
+ * Per frame n, from d_points[N][20][3] (metres) and d_cov[N][20][3][3] - the points / cov layout of
+ * acino_triangulate_multiview -, over the 25 active states x (the order of acino_fk_active) inside the box of the FTE:
+ *   F(x) = 1/2 sum_{l enters} (FK_l(x) - y_l)^T W_l (FK_l(x) - y_l) + 1/2 sum_{p = 3..24} (x_p - m_p)^2 / prior_sigma^2.
+ * A marker enters when its 3 + 9 values are finite and S_l = L D L^T has every pivot above 1e-12 of its trace (the rule of
+ * acino_triangulate_multiview); W_l = S_l^-1, or I / sigma_iso^2 for every finite point with d_cov NULL.  m = the start
+ * clipped to the box: the ridge acts on the 22 angles only, defines the states no entering marker moves and keeps A
+ * positive definite whenever one marker enters.  F is a negative log-posterior as it stands (acino_fte_covariance).
+ * Start: d_x0[N][25], or with d_x0 NULL the mean of the entering markers among 0, 1, 2 (of all entering markers when none of
+ * them enters) in columns 0..2, psi_0 = atan2 of (marker 2 - marker 3) when both enter, every other state 0.
+ * Iteration: the projected Levenberg-Marquardt of acino_fte_solve per frame - active set "at a bound with the gradient
+ * pushing outward, |g_p| > 1e-14 A_pp", (A + lam diag A) d = -g on the free states with A = sum J_l^T W_l J_l + the ridge,
+ * the trial clipped to the box and accepted when F falls, Nielsen's damping; it ends on dF <= ftol |F|, on a step <= xtol,
+ * on lam > 1e16 or after max_iter trials.  One launch (one 64-lane wave per frame), no synchronisation.  At the returned x:
+ *   d_x[N][25], d_cost[N], d_nmarkers[N] (markers that entered), d_iters[N] (trials made)
+ *   d_status[N]           0 stopped on ftol or xtol, 1 max_iter reached or lam overflowed, 2 fewer than min_markers enter,
+ *                         3 numeric (a pivot not above zero or a non-finite value); every floating-point output of the
+ *                         frame is NaN (and d_pinned 0) for 2 and 3
+ *   d_pinned[N][25]       the active set
+ *   d_cov_x[N][25][25]    A_free^-1 without a Marquardt term, rows and columns of pinned states exactly 0 (as
+ *                         acino_fte_covariance), symmetric bit for bit
+ *   d_pos[N][20][3]       FK(x)
+ *   d_cov_pos[N][20][3][3]  J_l cov_x J_l^T, symmetric bit for bit;  d_std_pos[N][20] = sqrt((c00 + c11) + c22)
+ * Any output but d_x and d_status may be NULL.  Argument validation happens before any device call; n_frames == 0 is a
+ * no-op. */
+typedef struct acino_pose_fit_params {
+  int32_t max_iter;       /* 1..255 */
+  int32_t min_markers;    /* 1..20 */
+  double lam0, ftol, xtol, prior_sigma, sigma_iso;   /* all > 0; prior_sigma [rad], sigma_iso [m] */
+} acino_pose_fit_params;
+size_t acino_sizeof_pose_fit_params(void);
+int acino_cheetah_pose_fit(const acino_pose_fit_params* prm, const double* d_points, const double* d_cov,
+                           const double* d_x0, int64_t n_frames, double* d_x, double* d_cost, uint8_t* d_nmarkers,
+                           uint8_t* d_status, uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x, double* d_pos,
+                           double* d_cov_pos, double* d_std_pos, void* stream);
 
 /* ---- cheetah forward kinematics (a-4) ---------------------------------------------------------
  * d_q[N][45] full state -> d_pos[N][20][3]. */
