@@ -1181,8 +1181,8 @@ __global__ void k_bcr_refine_copy(BcrChain ch, const int* __restrict__ iso, cons
 // ---- the whole back-substitution of a truncated + refined reduction as ONE launch -------------------------------------
 // (separator chain of the chunked solver: <= ~240 nodes, every kernel of it a latency chain.)  What were 2 + r + K launches
 // - truncated solve of the isolated nodes, r block-Jacobi sweeps, K back-substitution levels, each re-reading its three
-// 51 KB matrices - is one workgroup per node that loads its matrices ONCE into LDS and then only trades 80-double vectors
-// with its neighbours through memory:
+// 51 KB matrices - is one workgroup per node that loads its matrices ONCE (they end in the registers of the products, see
+// st_fetch below) and then only trades 80-double vectors with its neighbours through memory:
 //   isolated node p (blocks 0 .. n_iso-1):  x0 = U y;  sweep s = 1..r:  x(s) = x0 - U U^T (C_l x_l(s-1) + C_r x_r(s-1));
 //     version s of the node's iterate goes to buffer s & 1 of the node, every value in a pair of 64-bit words that carry the
 //     version's tag next to the data (ll_put / ll_get below: no flag, no fence); a neighbour writes version s only after it
@@ -1258,96 +1258,95 @@ __device__ __forceinline__ void st_wait(const int* flag, int need, int* numeric_
     }
   }
 }
+// The kernel's 80 x 80 products - G t, U t, U^T t, a coupling pair times the neighbours' vectors - are 80 rows of ST_P parts of
+// ST_W terms each.  A (row, part) belongs to ONE lane for the whole kernel: wave w holds the rows 10 w .. 10 w + 9, the six
+// parts of a row sit in neighbouring lanes (lanes 60 .. 63 hold zeros).  The lane's ST_W entries of every matrix go to
+// registers ONCE (a level node's and the unfused path's straight from memory; G, which is formed in LDS, and the staged
+// coupling blocks of a fused isolated node from there) - between the sweeps they do not change - so a product reads
+// nothing but the vector from LDS, and the six partial sums of a row are added across the lanes,
+// p0 + p1 + ... + p5 as the per-launch kernels add them (k_bcr_refine: row_sum), without a round trip through LDS and its
+// two barriers.  Within a part: q ascending, one fused multiply-add per term; a slot outside the matrix' pattern (the short
+// last part, the other triangle of U) holds 0.0 and meets a finite vector entry (the vectors carry four zeros behind their
+// 80 entries), so it adds nothing.  The row's sum, its x0 and its iterate live in the lane of part 0 ("own").
+constexpr int ST_R = BS / (ST_T / 64);      // rows per wave
+constexpr int ST_VS = ST_P * ST_W;          // a vector in LDS: 80 entries and the zeros the last part reads
+static_assert(ST_R * (ST_T / 64) == BS && ST_R * ST_P <= 64 && ST_VS >= BS && ST_W * (ST_P - 1) < BS, "k_sep_tail: lane layout");
+struct StLane {
+  int row, k0;       // the lane's row and the first column of its part
+  bool act, own;     // holds a part at all; holds part 0
+};
+__device__ __forceinline__ StLane st_lane(int tid) {
+  const int ln = tid & 63;
+  StLane L;
+  L.row = ST_R * (tid >> 6) + min(ln / ST_P, ST_R - 1);
+  L.k0 = ST_W * (ln % ST_P);
+  L.act = ln < ST_R * ST_P;
+  L.own = L.act && ln % ST_P == 0;
+  return L;
+}
+// request the lane's entries src[row * rs + k * cs], k = k0 .. k0 + ST_W - 1 (a k past the matrix: any entry inside it) ...
+__device__ __forceinline__ void st_fetch(double (&m)[ST_W], const double* __restrict__ src, int rs, int cs, const StLane& L) {
+#pragma unroll
+  for (int q = 0; q < ST_W; ++q) m[q] = src[L.row * rs + (L.k0 + q < BS ? L.k0 + q : L.k0) * cs];
+}
+// ... and keep those with klo <= k < khi (everything else, and every entry of an idle lane: 0.0).  Apart, so that the loads
+// of st_fetch stay in flight across whatever stands between the two.
+__device__ __forceinline__ void st_mask(double (&m)[ST_W], const StLane& L, int klo, int khi) {
+  khi = L.act ? min(khi, BS) : 0;
+#pragma unroll
+  for (int q = 0; q < ST_W; ++q) m[q] = (L.k0 + q >= klo && L.k0 + q < khi) ? m[q] : 0.0;
+}
+// the lane's part of (M v)[row]; v: the vector in LDS
+__device__ __forceinline__ double st_dot(const double (&m)[ST_W], const double* v, const StLane& L) {
+  double s = 0.0;
+#pragma unroll
+  for (int q = 0; q < ST_W; ++q) s = __builtin_fma(m[q], v[L.k0 + q], s);
+  return s;
+}
+// the row's sum of its ST_P parts, valid in the lane that owns the row (every lane of the wave takes part in the moves)
+__device__ __forceinline__ double st_row_sum(double v) {
+  double r = v;
+#pragma unroll
+  for (int q = 1; q < ST_P; ++q) r += __shfl_down(v, q, 64);
+  return r;
+}
 __global__ void __launch_bounds__(ST_T)
 k_sep_tail(BcrChain ch, SepTailArgs a, const int* __restrict__ status, int* __restrict__ numeric_err) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   if (status && *status != 0) return;
-  double* Ml = reinterpret_cast<double*>(smem_raw);
+  double* Ml = reinterpret_cast<double*>(smem_raw);       // the coupling blocks of a fused isolated node, on their way to the registers
   double* Mr = Ml + MAT;
-  double* Mu = Mr + MAT;
-  double* xl = Mu + MAT;          // [80] each
-  double* xr = xl + BS;
-  double* tv = xr + BS;
-  double* part = tv + BS;         // [ST_P][80]
+  double* Mu = Mr + MAT;          // D_j, its factor, then G (fused isolated node)
+  double* xl = Mu + MAT;          // [ST_VS] each
+  double* xr = xl + ST_VS;
+  double* tv = xr + ST_VS;
+  double* wt = tv + ST_VS;
+  double* red = wt + ST_VS;       // [ST_T / 64][6]: the norms of the waves
   const int tid = threadIdx.x;
+  const StLane L = st_lane(tid);
   const size_t MB = (size_t)BS * BS;
   const unsigned tag0 = (unsigned)*a.epoch << 6;          // tags of this launch: + 1 + s iterate of sweep s, + 63 a node's solution
   unsigned long long* const fin = a.ll + (size_t)2 * a.n_iso * BS * 2;
-#define ST_STAMP(k) do { if (ch.dbg && tid == 0 && (long long)blockIdx.x == ch.dbg[64] && ch.dbg[65] == 100) ch.dbg[k] = (long long)wall_clock64(); } while (0)
+  // (the selectors are read once: a stamp that loads them waits for every load in flight, the coupling blocks' included)
+  const bool st_on = ch.dbg && tid == 0 && (long long)blockIdx.x == ch.dbg[64] && ch.dbg[65] == 100;
+#define ST_STAMP(k) do { if (st_on) ch.dbg[k] = (long long)wall_clock64(); } while (0)
   ST_STAMP(6);
   if (ch.dbg && tid == 0 && blockIdx.x == 0 && ch.dbg[65] == 100) ch.dbg[7] = (long long)wall_clock64();    // (workgroup 0's start: the common time base)
-  const int row = tid % BS, pr = tid / BS, k0 = ST_W * pr, k1 = min(k0 + ST_W, BS);
-  auto row_sum = [&](int r) {     // the ST_P partial sums of row r, fixed order
-    double v = part[r];
-#pragma unroll
-    for (int q = 1; q < ST_P; ++q) v += part[q * BS + r];
-    return v;
-  };
-  auto load3 = [&](const double* m0, const double* m1, const double* m2) {   // all three matrices in flight before the first LDS write
-    const double2* s0 = reinterpret_cast<const double2*>(m0);
-    const double2* s1 = reinterpret_cast<const double2*>(m1);
-    const double2* s2 = reinterpret_cast<const double2*>(m2);
-    double2 v0[ST_V], v1[ST_V], v2[ST_V];
-#pragma unroll
-    for (int k = 0; k < ST_V; ++k) {
-      const int idx = tid + ST_T * k;
-      if (idx < BS * BS / 2) {
-        v0[k] = m0 ? s0[idx] : make_double2(0.0, 0.0);
-        v1[k] = m1 ? s1[idx] : make_double2(0.0, 0.0);
-        v2[k] = s2[idx];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < ST_V; ++k) {
-      const int idx = tid + ST_T * k;
-      if (idx < BS * BS / 2) {
-        const int e = 2 * idx, rr = e / BS, c = e % BS;
-        Ml[rr * LD + c] = v0[k].x;  Ml[rr * LD + c + 1] = v0[k].y;
-        Mr[rr * LD + c] = v1[k].x;  Mr[rr * LD + c + 1] = v1[k].y;
-        Mu[rr * LD + c] = v2[k].x;  Mu[rr * LD + c + 1] = v2[k].y;
-      }
-    }
-  };
-  // x = U t (U upper triangular, t in tv) -> value of row tid for tid < 80 (two barriers inside)
-  auto upper_matvec = [&]() {
-    if (tid < ST_P * BS) {
-      double s = 0.0;
-#pragma unroll
-      for (int q = 0; q < ST_W; ++q) {
-        const bool on = k0 + q >= row && k0 + q < k1;
-        const int k = on ? k0 + q : row;
-        s += (on ? 1.0 : 0.0) * Mu[row * LD + k] * tv[k];
-      }
-      part[tid] = s;
-    }
-    __syncthreads();
-    const double v = tid < BS ? row_sum(tid) : 0.0;
-    __syncthreads();
-    return v;
-  };
-  // x = G t for a FULL symmetric G in Mu (fused isolated level: G = D^-1 replaces the factor, one product instead of two)
-  auto full_matvec = [&]() {
-    if (tid < ST_P * BS) {
-      double s = 0.0;
-#pragma unroll
-      for (int q = 0; q < ST_W; ++q) {
-        const int k = k0 + (k0 + q < k1 ? q : 0);
-        s += (k0 + q < k1 ? 1.0 : 0.0) * Mu[row * LD + k] * tv[k];
-      }
-      part[tid] = s;
-    }
-    __syncthreads();
-    const double v = tid < BS ? row_sum(tid) : 0.0;
-    __syncthreads();
-    return v;
-  };
+  if (tid < ST_VS - BS) xl[BS + tid] = xr[BS + tid] = tv[BS + tid] = wt[BS + tid] = 0.0;    // (a barrier stands before every product)
   if ((int)blockIdx.x < a.n_iso) {
     // ---------------- isolated node: truncated solve + refinement sweeps ----------------
     const int p = blockIdx.x, n_iso = a.n_iso;
     const int j = a.iso[3 * p], l = p > 0 ? a.iso[3 * (p - 1)] : -1, r = p + 1 < n_iso ? a.iso[3 * (p + 1)] : -1;
+    const bool use_g = a.fused != 0;
+    // block(j, l) = Cpl[.] (rows j), block(j, r) = Cpl[.]^T; Gm: G = D_j^-1 (fused) or U_j; Ut: U_j^T (not fused only)
+    double Cl[ST_W], Cr[ST_W], Gm[ST_W], Ut[ST_W];
     ST_STAMP(0);
-    if (a.fused) {
+    if (use_g) {
       const int fl = a.iso_loc[2 * p];
+      // The coupling blocks are staged through LDS, whole rows per request, and go to the registers later (below).  Straight
+      // from memory in the layout of the products - 112-byte pieces of a row per lane, the transposed block strided - the
+      // requests of a wave touch ~60 cache lines each instead of 16, and the waves stood 1.0 us longer in front of the barrier
+      // below, wherever the requests were placed (before or behind the node's own loads).
       const double2* s0 = reinterpret_cast<const double2*>(ch.Cpl + (size_t)(l >= 0 ? a.iso_loc[2 * (p - 1) + 1] : 0) * MB);
       const double2* s1 = reinterpret_cast<const double2*>(ch.Cpl + (size_t)(r >= 0 ? a.iso_loc[2 * p + 1] : 0) * MB);
       double2 v0[ST_V], v1[ST_V];
@@ -1411,21 +1410,37 @@ k_sep_tail(BcrChain ch, SepTailArgs a, const int* __restrict__ status, int* __re
           }
         }
       }
+      __syncthreads();
+      st_fetch(Gm, Mu, LD, 1, L);
+      st_mask(Gm, L, 0, BS);
     } else {
-      load3(l >= 0 ? ch.Cpl + (size_t)l * MB : nullptr, r >= 0 ? ch.Cpl + (size_t)j * MB : nullptr, ch.U + (size_t)j * MB);
+      const double* Uj = ch.U + (size_t)j * MB;
+      st_fetch(Cl, ch.Cpl + (size_t)(l >= 0 ? l : j) * MB, BS, 1, L);
+      st_fetch(Cr, ch.Cpl + (size_t)j * MB, 1, BS, L);
+      st_fetch(Gm, Uj, BS, 1, L);
+      st_fetch(Ut, Uj, 1, BS, L);
       if (tid < BS) tv[tid] = ybuf(ch)[(size_t)j * BS + tid];     // y_j = U^T b_j (written by the reduction)
+      st_mask(Gm, L, L.row, BS);                                  // U: upper triangular
+      st_mask(Ut, L, 0, L.row + 1);
+      __syncthreads();
     }
-    __syncthreads();
-    const bool use_g = a.fused != 0;
-    const double x0 = use_g ? full_matvec() : upper_matvec();    // truncated solve (fused: G b; else U y)
+    const double x0 = st_row_sum(st_dot(Gm, tv, L));             // truncated solve (fused: G b; else U y)
     ST_STAMP(3);
-    double xcur = x0, dabs = 0.0, dabs_prev = 0.0, xabs = fabs(x0), xabs_prev = 0.0, d_first = 0.0, d_second = 0.0;
+    double xcur = x0, dabs = 0.0, dabs_prev = 0.0, xabs = L.own ? fabs(x0) : 0.0, xabs_prev = 0.0, d_first = 0.0, d_second = 0.0;
     unsigned long long* xb0 = a.ll;
     unsigned long long* xb1 = a.ll + (size_t)n_iso * BS * 2;
     if (a.refine > 0) {
-      if (tid < BS) ll_put(xb0 + ((size_t)p * BS + tid) * 2, x0, tag0 + 1);
+      if (L.own) ll_put(xb0 + ((size_t)p * BS + L.row) * 2, x0, tag0 + 1);
       if (p == 0 && tid == 0) st_raise(a.ver, 1);          // (a throttle, not a hand-off: nothing is read behind it)
     }
+    if (use_g) {           // the staged coupling blocks -> registers, while x0 travels to the neighbours and theirs to this node
+      st_fetch(Cl, Ml, LD, 1, L);
+      st_fetch(Cr, Mr, 1, LD, L);
+    }
+    st_mask(Cl, L, 0, l >= 0 ? BS : 0);
+    st_mask(Cr, L, 0, r >= 0 ? BS : 0);
+    // Two barriers per sweep: (A) the neighbours' vectors are in LDS, (B) t is.  xl / xr are read before (B) and written again
+    // after it; tv is read after (B) and written again after the next (A): no barrier closes the sweep.
     for (int s = 1; s <= a.refine; ++s) {
       const unsigned long long* src = (s - 1) & 1 ? xb1 : xb0;
       unsigned long long* dst = s & 1 ? xb1 : xb0;
@@ -1434,43 +1449,21 @@ k_sep_tail(BcrChain ch, SepTailArgs a, const int* __restrict__ status, int* __re
                   tag0 + (unsigned)s, numeric_err, tid);
       __syncthreads();
       if (s == 2) ST_STAMP(11);
-      if (tid < ST_P * BS) {         // t = block(j, l) x_l + block(j, r) x_r ;  block(j, r) = Cpl[j]^T
-        double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-        for (int q = 0; q < ST_W; ++q) {
-          const int k = k0 + (k0 + q < k1 ? q : 0);
-          const double w = k0 + q < k1 ? 1.0 : 0.0;
-          s0 += w * Ml[row * LD + k] * xl[k];
-          s1 += w * Mr[k * LD + row] * xr[k];
-        }
-        part[tid] = s0 + s1;
-      }
+      const double t = st_row_sum(st_dot(Cl, xl, L) + st_dot(Cr, xr, L));     // t = block(j, l) x_l + block(j, r) x_r
+      if (L.own) tv[L.row] = t;
       __syncthreads();
-      if (tid < BS) tv[tid] = row_sum(tid);
-      __syncthreads();
+      if (s == 2) ST_STAMP(9);
       double d;
       if (use_g) {
-        d = full_matvec();                                       // d = G t
+        d = st_row_sum(st_dot(Gm, tv, L));                       // d = G t
       } else {
-        if (tid < ST_P * BS) {       // w = U^T t  (rows <= column)
-          double sm = 0.0;
-          const int c1 = min(k1, row + 1);
-#pragma unroll
-          for (int q = 0; q < ST_W; ++q) {
-            const bool on = k0 + q < c1;
-            const int k = k0 + (on ? q : 0);
-            sm += (on ? 1.0 : 0.0) * Mu[k * LD + row] * tv[k];
-          }
-          part[tid] = sm;
-        }
+        const double w = st_row_sum(st_dot(Ut, tv, L));          // w = U^T t
+        if (L.own) wt[L.row] = w;
         __syncthreads();
-        const double w = tid < BS ? row_sum(tid) : 0.0;
-        __syncthreads();
-        if (tid < BS) tv[tid] = w;
-        __syncthreads();
-        d = upper_matvec();                                      // d = U w
+        d = st_row_sum(st_dot(Gm, wt, L));                       // d = U w
       }
-      if (tid < BS) {
+      if (s == 2) ST_STAMP(10);
+      if (L.own) {
         const double x = x0 - d;
         dabs_prev = dabs;
         xabs_prev = xabs;
@@ -1479,16 +1472,16 @@ k_sep_tail(BcrChain ch, SepTailArgs a, const int* __restrict__ status, int* __re
         xcur = x;
         if (s == 1) d_first = dabs;
         if (s == 2) d_second = dabs;
-        if (s < a.refine) ll_put(dst + ((size_t)p * BS + tid) * 2, x, tag0 + 1 + (unsigned)s);
+        if (s < a.refine) ll_put(dst + ((size_t)p * BS + L.row) * 2, x, tag0 + 1 + (unsigned)s);
       }
       if (s == 2) ST_STAMP(12);
     }
-    if (tid < BS) {
-      ll_put(fin + ((size_t)j * BS + tid) * 2, xcur, tag0 + 63);
-      ch.b[(size_t)j * BS + tid] = xcur;
+    if (L.own) {
+      ll_put(fin + ((size_t)j * BS + L.row) * 2, xcur, tag0 + 63);
+      ch.b[(size_t)j * BS + L.row] = xcur;
     }
     ST_STAMP(4);
-    if (a.norms && a.refine > 0) {            // (waves 0 and 1 hold the 80 rows)
+    if (a.norms && a.refine > 0) {            // (maxima: the lanes that own no row hold 0.0)
       for (int off = 32; off > 0; off >>= 1) {
         dabs = fmax(dabs, __shfl_down(dabs, off, 64));
         xabs = fmax(xabs, __shfl_down(xabs, off, 64));
@@ -1497,8 +1490,8 @@ k_sep_tail(BcrChain ch, SepTailArgs a, const int* __restrict__ status, int* __re
         d_first = fmax(d_first, __shfl_down(d_first, off, 64));
         d_second = fmax(d_second, __shfl_down(d_second, off, 64));
       }
-      if ((tid & 63) == 0 && tid < 128) {
-        double* q6 = part + 6 * (tid >> 6);
+      if ((tid & 63) == 0) {
+        double* q6 = red + 6 * (tid >> 6);
         q6[0] = dabs;
         q6[1] = xabs;
         q6[2] = dabs_prev;
@@ -1508,14 +1501,20 @@ k_sep_tail(BcrChain ch, SepTailArgs a, const int* __restrict__ status, int* __re
       }
       __syncthreads();
       if (tid == 0) {             // (layout: bcr_backsub, the per-sweep launches)
-        a.norms[p] = fmax(part[0], part[6]);
-        a.norms[n_iso + p] = fmax(part[1], part[7]);
-        if (a.refine >= 2) {
-          a.norms[2 * n_iso + p] = fmax(part[2], part[8]);
-          a.norms[3 * n_iso + p] = fmax(part[3], part[9]);
+        double m6[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          m6[k] = red[k];
+          for (int w = 1; w < ST_T / 64; ++w) m6[k] = fmax(m6[k], red[6 * w + k]);
         }
-        if (a.refine >= 3) a.norms[4 * n_iso + p] = fmax(part[4], part[10]);
-        if (a.refine >= 4) a.norms[5 * n_iso + p] = fmax(part[5], part[11]);
+        a.norms[p] = m6[0];
+        a.norms[n_iso + p] = m6[1];
+        if (a.refine >= 2) {
+          a.norms[2 * n_iso + p] = m6[2];
+          a.norms[3 * n_iso + p] = m6[3];
+        }
+        if (a.refine >= 3) a.norms[4 * n_iso + p] = m6[4];
+        if (a.refine >= 4) a.norms[5 * n_iso + p] = m6[5];
       }
     }
     return;
@@ -1527,38 +1526,33 @@ k_sep_tail(BcrChain ch, SepTailArgs a, const int* __restrict__ status, int* __re
   const int* en = ch.d_elim + 3 * (a.lv_off[lvl] + q);
   const int i = en[0], l = en[1], r = en[2];
   if (a.fused && a.refine > 0) {
-    // The isolated workgroups of this launch are the critical path and start with ~200 KB of loads each; the 3 x 51 KB of every
+    // The isolated workgroups of this launch are the critical path and start with ~150 KB of loads each; the 3 x 51 KB of every
     // level node are not needed before the sweeps are over.  Hold them back until the first isolated node has published its
     // truncated solve (its factorisation is done by then), so the two sets of loads do not share the memory system.
     if (tid == 0) st_wait(a.ver, 1, nullptr);
     __syncthreads();
   }
-  load3(l >= 0 ? ch.Wl + (size_t)i * MB : nullptr, r >= 0 ? ch.Wr + (size_t)i * MB : nullptr, ch.U + (size_t)i * MB);
-  const double yi = tid < BS ? ybuf(ch)[(size_t)i * BS + tid] : 0.0;
+  // W_l, W_r and U go straight to the registers of the products, in flight while the neighbours are polled
+  double Wl[ST_W], Wr[ST_W], Uu[ST_W];
+  const double* Ui = ch.U + (size_t)i * MB;
+  st_fetch(Wl, l >= 0 ? ch.Wl + (size_t)i * MB : Ui, BS, 1, L);
+  st_fetch(Wr, r >= 0 ? ch.Wr + (size_t)i * MB : Ui, BS, 1, L);
+  st_fetch(Uu, Ui, BS, 1, L);
+  const double yi = L.own ? ybuf(ch)[(size_t)i * BS + L.row] : 0.0;
   ll_get_pair(xl, xr, l >= 0 ? fin + (size_t)l * BS * 2 : nullptr, r >= 0 ? fin + (size_t)r * BS * 2 : nullptr, tag0 + 63,
               numeric_err, tid);
+  st_mask(Wl, L, 0, l >= 0 ? BS : 0);
+  st_mask(Wr, L, 0, r >= 0 ? BS : 0);
+  st_mask(Uu, L, L.row, BS);
   __syncthreads();
   ST_STAMP(1);                  // (level node: both neighbours' solutions in LDS)
-  if (tid < ST_P * BS) {
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int qq = 0; qq < ST_W; ++qq) {
-      const int k = k0 + (k0 + qq < k1 ? qq : 0);
-      const double w = k0 + qq < k1 ? 1.0 : 0.0;
-      s0 += w * Ml[row * LD + k] * xl[k];
-      s1 += w * Mr[row * LD + k] * xr[k];
-    }
-    part[tid] = s0 + s1;
-  }
+  const double t = yi - st_row_sum(st_dot(Wl, xl, L) + st_dot(Wr, xr, L));
+  if (L.own) tv[L.row] = t;
   __syncthreads();
-  const double t = tid < BS ? yi - row_sum(tid) : 0.0;
-  __syncthreads();
-  if (tid < BS) tv[tid] = t;
-  __syncthreads();
-  const double x = upper_matvec();
-  if (tid < BS) {
-    ll_put(fin + ((size_t)i * BS + tid) * 2, x, tag0 + 63);
-    ch.b[(size_t)i * BS + tid] = x;
+  const double x = st_row_sum(st_dot(Uu, tv, L));
+  if (L.own) {
+    ll_put(fin + ((size_t)i * BS + L.row) * 2, x, tag0 + 63);
+    ch.b[(size_t)i * BS + L.row] = x;
   }
   ST_STAMP(5);
 #undef ST_STAMP

@@ -38,6 +38,7 @@ for wg in (0, 1, 30, 58, 59, 60, 100, 118, 119, 150, 200, 237):
     if d[0]:
         if d[8]:
             print(f"   sweep 2 of wg {wg}: starts {(d[8] - base) / 100.0:.2f}, neighbours' iterates in LDS {(d[11] - base) / 100.0:.2f}, "
+                  f"t done {(d[9] - base) / 100.0:.2f}, d done {(d[10] - base) / 100.0:.2f}, "
                   f"new iterate stored {(d[12] - base) / 100.0:.2f}")
         print(f"k_sep_tail wg {wg} (isolated): enters {(d[6] - base) / 100.0:.2f}, " + ", ".join(f"{tl_names[k]} {(d[k] - base) / 100.0:.2f}" for k in range(1, 5) if d[k]))
     else:
