@@ -18,7 +18,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, calib, io, skeleton
+from . import _lib, calib, fte, io, skeleton
 from ._lib import SkelFteInfo, SkelFteParams, SkelOp, check, lib, ptr, stream_ptr
 
 MODEL_WEIGHT = 0.002        # build.py:186-191
@@ -755,9 +755,147 @@ def detection_report(reproj, gate=None, reject=0.1):
     return out
 
 
+INITS = ("line", "pose_fit")
+
+
+def _check_init(init):
+    if init not in INITS:
+        raise ValueError(f"init must be 'line' or 'pose_fit' (got {init!r})")
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def pose_fit(model, points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01, min_markers=1, max_iter=100, ftol=1e-10,
+             xtol=1e-10, lam0=1e-3, return_cov=True):
+    """Per-frame pose of a ``SkeletonModel`` from 3-D points with a covariance each (include/acinoset_hip.h:
+    acino_skel_pose_fit; ``fte.pose_fit`` for a skeleton): per frame the minimiser over the ``model.active`` states, inside the
+    frame's box ``model.lo`` / ``model.hi``, of
+
+        F(x) = 1/2 sum_{l enters} (FK_l(x) - y_l)^T W_l (FK_l(x) - y_l) + 1/2 sum_{p >= 3} (x_p - m_p)^2 / prior_sigma^2
+
+    by one projected Levenberg-Marquardt per frame in one launch: one frame, a frame range or a clip too short for the
+    smoothness prior gets a pose.  ``points`` [N, n_pose, 3] in metres (slot l is pose slot l, ``model.names``; N =
+    ``model.N``) and ``cov`` [N, n_pose, 3, 3] are the ``points`` / ``cov`` of ``calib.triangulate_multiview_dense`` -
+    ``model_triangulation(model)`` -, whose dict is accepted in place of ``points``; a slot enters when its values are finite
+    and its covariance positive definite (W = cov^-1), and with ``cov=None`` every finite point enters with
+    W = I / sigma_iso^2.  ``x0`` [N, n_active] is the start and, clipped to the box, the centre m of the ridge on the angles
+    (``prior_sigma`` rad; never on x, y, z): it gives a state that moves no pose - the psi angles of "chin" and "hip2" of the
+    shipped human skeleton - the value m and the variance prior_sigma^2; default: every angle 0 and the root at the mean of
+    (point - rest pose) over the entering slots.  The valley along a poorly observed angle is flat under the default
+    ``prior_sigma`` = pi: a quarter of such frames is still descending after the default 100 trials (status 1; README), and
+    ``prior_sigma=1.0, max_iter=255`` finishes most of them.  Returns a dict:
+
+      x [N, n_active], x_full [N, 3 + 3 L] (0 outside ``model.active``), positions [N, n_pose, 3], cost [N]; n_markers,
+      status, iters uint8 [N] (status 0 stopped on ``ftol`` / ``xtol``, 1 ``max_iter`` reached or lam overflowed, 2 fewer than
+      ``min_markers`` enter, 3 numeric; every floating-point output of a frame is NaN for 2 and 3); pinned uint8
+      [N, n_active], the bound-active states at x; and with ``return_cov`` cov_x [N, n_active, n_active] = A_free^-1 (rows and
+      columns of pinned states exactly 0), cov_positions [N, n_pose, 3, 3] = G cov_x G^T for every slot and std_positions
+      [N, n_pose] in metres.
+
+    numpy in, numpy out; CUDA tensors in, CUDA tensors out with no host copy."""
+    if isinstance(points, dict):
+        if cov is not None:
+            raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
+        points, cov = points["points"], points["cov"]
+    act = np.asarray(model.active, dtype=np.int32)
+    N, Pa, Lp = model.N, len(act), len(model.names)
+    if _shape(points) != (N, Lp, 3):
+        raise ValueError(f"points must be [{N}, {Lp}, 3] (model.N frames, one slot per pose)")
+    if cov is not None and _shape(cov) != (N, Lp, 3, 3):
+        raise ValueError(f"cov must be [{N}, {Lp}, 3, 3]")
+    if x0 is not None and _shape(x0) != (N, Pa):
+        raise ValueError(f"x0 must be [{N}, {Pa}] (the active states)")
+    for name, val in (("prior_sigma", prior_sigma), ("sigma_iso", sigma_iso), ("ftol", ftol), ("xtol", xtol), ("lam0", lam0)):
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError(f"{name} must be finite and > 0")
+    if int(max_iter) != max_iter or not 1 <= max_iter <= 255:
+        raise ValueError("max_iter must be an integer in 1..255")
+    if int(min_markers) != min_markers or not 1 <= min_markers <= Lp:
+        raise ValueError(f"min_markers must be an integer in 1..{Lp}")
+    dev = calib._dev()
+    pts = calib._to_dev(points, dev)
+    cv = None if cov is None else calib._to_dev(cov, dev)
+    xs = None if x0 is None else calib._to_dev(x0, dev)
+    lo, hi = calib._to_dev(model.lo[:, act], dev), calib._to_dev(model.hi[:, act], dev)
+    p = _skel_params(model, Pa)
+    nbytes = lib().acino_skel_pose_fit_workspace_bytes(C.byref(p))
+    if nbytes == 0:
+        raise ValueError("problem outside the kernel limits (n_active <= 64)")
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+    x, cost, pos = torch.empty((N, Pa), **f64), torch.empty((N,), **f64), torch.empty((N, Lp, 3), **f64)
+    nm, status, iters, pinned = (torch.empty(sh, **u8) for sh in ((N,), (N,), (N,), (N, Pa)))
+    cov_x = torch.empty((N, Pa, Pa), **f64) if return_cov else None
+    cov_pos = torch.empty((N, Lp, 3, 3), **f64) if return_cov else None
+    std_pos = torch.empty((N, Lp), **f64) if return_cov else None
+    prm = _lib.PoseFitParams(int(max_iter), int(min_markers), float(lam0), float(ftol), float(xtol), float(prior_sigma),
+                             float(sigma_iso))
+    act_c = (C.c_int32 * Pa)(*[int(a) for a in act])
+    check(lib().acino_skel_pose_fit(prm, C.byref(p), _ops_array(model.prog), act_c, ptr(pts), ptr(cv), ptr(xs), ptr(lo), ptr(hi), N,
+                                    ptr(x), ptr(cost), ptr(nm), ptr(status), ptr(iters), ptr(pinned), ptr(cov_x), ptr(pos),
+                                    ptr(cov_pos), ptr(std_pos), C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
+    x_full = torch.zeros((N, model.P), **f64)
+    x_full[:, torch.as_tensor(act.astype(np.int64), device=dev)] = x
+    out = dict(x=x, x_full=x_full, positions=pos, cost=cost, n_markers=nm, status=status, iters=iters, pinned=pinned)
+    if return_cov:
+        out.update(cov_x=cov_x, cov_positions=cov_pos, std_positions=std_pos)
+    if isinstance(points, torch.Tensor):               # (the workspace goes back to the allocator of this very stream)
+        return out
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def model_triangulation(model, f_scale=5.0, sigma_px=None, **kw):
+    """``calib.triangulate_multiview_dense`` of the model's own per-slot detections: det = [``model.meas``,
+    ``model.weights`` > 0] with threshold 0.5 (a weighted detection is a valid one), the model's cameras and camera model.
+    ``sigma_px`` defaults to 1 / max(``model.weights``), the model's r_meas, so that the covariances are those of the noise the
+    solve states.  ``kw`` goes to the triangulation (``max_iter``, ``xtol``).  The detections go to the device as a tensor:
+    the dict holds CUDA tensors (points [N, n_pose, 3], cov [N, n_pose, 3, 3], ...), what ``pose_fit`` takes."""
+    w = np.asarray(model.weights, dtype=np.float64)
+    if sigma_px is None:
+        w_max = float(np.nanmax(w, initial=0.0))
+        if not w_max > 0:
+            raise ValueError("no positive weight in the model: pass sigma_px (px), the noise scale of a detection")
+        sigma_px = 1.0 / w_max
+    det = np.concatenate([np.asarray(model.meas, dtype=np.float64), (w > 0).astype(np.float64)[..., None]], axis=-1)
+    dev = calib._dev()
+    return calib.triangulate_multiview_dense(torch.as_tensor(np.ascontiguousarray(det), device=dev), 0.5, model.K, model.D, model.R,
+                                             model.t, model=getattr(model, "camera_model", "fisheye"), f_scale=f_scale,
+                                             sigma_px=float(sigma_px), **kw)
+
+
+def pose_fit_start(model, **fit_kw):
+    """A starting point of the solve from a pose fit of every frame, ``init_x`` [N, 3 + 3 L]: ``model_triangulation``, then
+    ``pose_fit`` of its points with their covariances (``fit_kw`` goes to ``pose_fit``); the frames without a fit (status >= 2)
+    are filled by ``fte.fill_unfitted_frames`` (interpolated over the fitted frames, the psi angles unwrapped first; ValueError
+    when no frame has a fit) and the result is clipped to the box.  Every active state starts near the detections instead of
+    at 0 - the redescending loss gives a detection further than c = 20 from its prediction neither gradient nor curvature."""
+    init_x = _pose_fit_start(model, fit_kw)
+    if init_x is None:
+        raise ValueError("no frame has a pose fit: no slot was triangulated in the whole clip")
+    return init_x
+
+
+def _pose_fit_start(model, fit_kw):
+    """``pose_fit_start``; None when no frame of the model has a fit."""
+    act = np.asarray(model.active, dtype=np.int64)
+    if not (np.asarray(model.weights) > 0).any():              # (no weighted detection: nothing to triangulate)
+        return None
+    fit = pose_fit(model, model_triangulation(model), return_cov=False, **fit_kw)
+    fitted = fit["status"].cpu().numpy() < 2
+    if not fitted.any():
+        return None
+    L = model.prog["n_angles"]
+    xa = fte.fill_unfitted_frames(fit["x"].cpu().numpy(), fitted, psi_columns=[int(c) for c in np.nonzero(act >= 3 + 2 * L)[0]])
+    init_x = np.zeros((model.N, model.P))
+    init_x[:, act] = np.clip(xa, model.lo[:, act], model.hi[:, act])
+    return init_x
+
+
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
                  return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
-                 return_rate_cov=False, cov_cams=None, l1_start=True):
+                 return_rate_cov=False, cov_cams=None, l1_start=True, init="line"):
     """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
@@ -791,7 +929,14 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     that result and status.  ``l1_start=False`` starts the robust solve at ``x0`` directly (for a caller who brings the L1 end
     point).  Everything attached afterwards is evaluated under the model's loss: the covariance, rates and samples are those
     of the Gauss-Newton curvature sum w^2 h J^T J (``model_covariance``), the report carries the weights h; ``cov_cams`` is
-    refused for such models (ValueError before any device call)."""
+    refused for such models (ValueError before any device call).
+
+    ``init``: where a model without an ``x0`` starts - "line" (the default): its ``init_x``, the reference's line through the
+    triangulated forehead with every angle 0; "pose_fit": ``pose_fit_start(model)`` and nothing else, a pose fit of every
+    frame of the model's own detections (README: what that start was measured to be worth).  Any other value is a ValueError."""
+    _check_init(init)
+    if init == "pose_fit":
+        x0 = [pose_fit_start(m) if x0 is None or x0[i] is None else x0[i] for i, m in enumerate(models)]
     if len(models) and cov_cams is not None:
         _refuse_robust_calibration(models)
         calib.cov_cams_matrix(cov_cams, int(models[0].meas.shape[1]))      # (a malformed matrix fails before the solve, not after)
@@ -841,7 +986,7 @@ def _lm_solve(models, x0, **lm):
 
 def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
-                return_rate_cov=False, cov_cams=None, l1_start=True):
+                return_rate_cov=False, cov_cams=None, l1_start=True, init="line"):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
@@ -852,11 +997,11 @@ def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10,
     ``return_rate_cov``: the bars of ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``) join ``results``.
     ``cov_cams``: the calibration's share (``model_calibration_sensitivity``; ``std_pos_total`` with ``return_cov``), as
     ``solve_models``.  A model whose ``loss`` is "redescending" is solved in two stages, L1 first (``l1_start``, ``info["l1"]``), as
-    ``solve_models`` describes."""
+    ``solve_models`` describes.  ``init``: "line" or "pose_fit", as ``solve_models``."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
                         l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed,
                         return_reprojection=return_reprojection, pin_unobserved=pin_unobserved,
-                        return_rate_cov=return_rate_cov, cov_cams=cov_cams, l1_start=l1_start)[0]
+                        return_rate_cov=return_rate_cov, cov_cams=cov_cams, l1_start=l1_start, init=init)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -1035,7 +1180,7 @@ def _video_forehead(dlc_tables, idx, f0, f1, scene, lik_thresh, cam_model):
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
                 overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, pin_unobserved=False,
-                return_rate_cov=False, cov_cams=None, loss="l1", **kw):
+                return_rate_cov=False, cov_cams=None, loss="l1", init="line", **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -1097,8 +1242,15 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     stage's with the L1 stage's under ``"l1"``; a window that fails numerically there keeps its L1 result and info and is listed
     in ``results["robust_failed_windows"]``.  ``cov_cams`` is refused (ValueError).
 
+    ``init``: "line" (the default) - every window starts from the triangulated forehead of its own frames, all angles 0, as
+    above - or "pose_fit": every window starts from ``pose_fit_start`` of its model, a pose fit of each of its frames; a
+    window none of whose frames has a triangulated point keeps the forehead start, and every info says which start its window
+    had (``init``).  The warm starts, the stages of the robust loss and everything after the solve are the same.  Any other
+    value is a ValueError.
+
     There is no ``n_samples`` here: a stitched video is not one posterior (every window has its own, and draws of neighbouring
     windows are independent); call ``model_samples`` on the windows' models."""
+    _check_init(init)
     if "n_samples" in kw or "sample_seed" in kw:
         raise TypeError("solve_video takes no n_samples: a stitched video is not one posterior (use model_samples per window)")
     if gate is not None and not return_reprojection:
@@ -1130,6 +1282,12 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     x0s = [m.init_x.copy() for m in models]
     for st, x0 in zip(starts, x0s if head is not None else []):
         x0[:, :3] = head[st - f0:st - f0 + window]
+    started = ["line"] * len(models)
+    if init == "pose_fit":
+        for i, m in enumerate(models):
+            fitted = _pose_fit_start(m, {})
+            if fitted is not None:                            # (None: no frame of the window has a triangulated point)
+                x0s[i], started[i] = fitted, "pose_fit"
     solved = solve_models(models, x0s, **kw)
     px = [window_residual_px(m, i) for m, (_r, i) in zip(models, solved)]
     warm_from = _warm_passes(models, x0s, starts, window, solved, px, warm_px, warm_passes, kw)
@@ -1146,6 +1304,9 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     results = _stitch(owner, starts, f0, [res for res, _info in solved], ("positions", "x", "dx", "ddx"))
     results.update(start_frame=f0, seams=[int(n) for n in np.nonzero(np.diff(owner) != 0)[0] + 1])
     infos = [dict(info, mean_abs_residual_px=px[i], warm_started_from=warm_from[i]) for i, (_r, info) in enumerate(solved)]
+    if init == "pose_fit":
+        for info, how in zip(infos, started):
+            info["init"] = how
     if loss != "l1":
         results["robust_failed_windows"] = robust_failed
     if return_cov or return_rate_cov:

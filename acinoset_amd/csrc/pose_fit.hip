@@ -20,11 +20,9 @@
 // lanes by v_readlane (no LDS traffic inside its 25 steps: the LDS form, a read-modify-write per entry, made the kernel twice
 // as long); the inverse for cov_x is 25 right-hand sides, one per lane, on the same registers.
 #include "fte_cov_dev.hpp"
-#include "ldl3.hpp"
+#include "pose_fit_dev.hpp"
 
 namespace acino {
-
-enum { PF_CONVERGED = 0, PF_MAX_ITER = 1, PF_FEW_MARKERS = 2, PF_NUMERIC = 3 };
 
 constexpr int PF_ROWS = 3 * NL;      // 60 rows of J
 constexpr int PF_LD = NP + 1;        // leading dimension of A and of its factor
@@ -215,12 +213,6 @@ __device__ __forceinline__ unsigned pf_active_set(const PoseFitLds& S, int lane)
   return (unsigned)__ballot(fixed);
 }
 
-// the value lane ``l`` holds (``l`` the same in every lane: a constant of an unrolled loop)
-__device__ __forceinline__ double pf_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
 // Cholesky factor of A + lam diag(A) on the free states (identity rows for the pinned ones), row i in the registers of lane
 // i: r[j] = L[i][j] for j < i, dinv = 1 / L[i][i]; the rows are stored to S.L as well, for the products with L^T.  No LDS
 // traffic and no barrier inside the 25 steps: the pivot column passes between lanes by v_readlane.  False on a pivot that is
@@ -317,35 +309,11 @@ __global__ void __launch_bounds__(64) k_pose_fit(PoseFitArgs a) {
     // ---- the markers that enter, their whitening factors
     bool enter = false;
     if (lane < NL) {
-      const double* yp = a.points + (n * NL + lane) * 3;
-      const double y0 = yp[0], y1 = yp[1], y2 = yp[2];
-      double U[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      enter = m_finite(y0) && m_finite(y1) && m_finite(y2);
-      if (a.cov) {
-        const double* s = a.cov + (n * NL + lane) * 9;
-        double c[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-          c[k] = s[k];
-          enter = enter && m_finite(c[k]);
-        }
-        Ldl3 f;
-        enter = enter && ldl3(c[0], c[1], c[2], c[4], c[5], c[8], 1e-12 * (c[0] + c[4] + c[8]), f);
-        if (enter) {
-          const double s0 = sqrt(f.i0), s1 = sqrt(f.i1), s2 = sqrt(f.i2);
-          U[0] = s0;
-          U[1] = -s1 * f.l10;
-          U[2] = s1;
-          U[3] = s2 * (f.l10 * f.l21 - f.l20);
-          U[4] = -s2 * f.l21;
-          U[5] = s2;
-        }
-      } else if (enter) {
-        U[0] = U[2] = U[5] = a.inv_sigma_iso;
-      }
-      S.y[3 * lane] = enter ? y0 : 0.0;
-      S.y[3 * lane + 1] = enter ? y1 : 0.0;
-      S.y[3 * lane + 2] = enter ? y2 : 0.0;
+      double y[3], U[6];
+      enter = pf_whiten(a.points + (n * NL + lane) * 3, a.cov ? a.cov + (n * NL + lane) * 9 : nullptr, a.inv_sigma_iso, y, U);
+      S.y[3 * lane] = enter ? y[0] : 0.0;
+      S.y[3 * lane + 1] = enter ? y[1] : 0.0;
+      S.y[3 * lane + 2] = enter ? y[2] : 0.0;
 #pragma unroll
       for (int k = 0; k < 6; ++k) S.U[lane][k] = U[k];
     }

@@ -428,7 +428,8 @@ int skel_upload(const SkelDev& h, const double* d_cams, int camera_model, SkelDe
   hipLaunchKernelGGL(k_skel_dev_store, dim3(1), dim3(256), 0, s, head, tail, d_dev);
   ACINO_LAUNCH_CHECK();
   const bool pinhole = camera_model == 1;
-  ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + (pinhole ? offsetof(SkelDev, pins) : offsetof(SkelDev, cams)),
+  if (d_cams)                                    // (NULL: an entry that reads the link program alone - acino_skel_pose_fit)
+    ACINO_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(d_dev) + (pinhole ? offsetof(SkelDev, pins) : offsetof(SkelDev, cams)),
                                  d_cams, sizeof(double) * (pinhole ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE) * h.n_cams,
                                  hipMemcpyDeviceToDevice, s));
   ACINO_HIP_CHECK(hipMemsetAsync(d_clip, 0, sizeof(SkelClip) * (size_t)n_clips, s));

@@ -69,7 +69,7 @@ inline K skel_camera_kernel(int camera_model, K fisheye, K pinhole) {
 
 // ---- The only writer of a SkelDev, all on stream s: the host half of h travels by value as the argument of k_skel_dev_store
 //      (no host buffer has to outlive the call), the n_cams records of the camera model are copied device-to-device into cams or
-//      pins (the other array is left as it is: no kernel reads it), the clips' words are cleared.
+//      pins (the other array is left as it is: no kernel reads it; d_cams NULL: neither is written), the clips' words are cleared.
 int skel_upload(const SkelDev& h, const double* d_cams, int camera_model, SkelDev* d_dev, SkelClip* d_clip, int n_clips,
                 hipStream_t s);
 

@@ -702,17 +702,19 @@ def pose_fit(points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01, min_m
 PSI_COLUMNS = [int(np.nonzero(ACTIVE == PSI + k)[0][0]) for k in (0, 1, 3, 4, 5)]     # the psi states among the active ones
 
 
-def fill_unfitted_frames(x, fitted):
+def fill_unfitted_frames(x, fitted, psi_columns=None):
     """The rule of ``pose_fit_init`` for the frames without a fit: x [N,25] with the rows where ``fitted`` is False filled by
     np.interp over the frames that have one (held flat at the ends), the five psi columns unwrapped over the fitted frames
-    first.  ValueError when no frame has a fit."""
+    first.  ValueError when no frame has a fit.  ``psi_columns``: the columns to unwrap for another state layout
+    (``build.pose_fit_start``: x [N, n_active] of a skeleton); default: the cheetah's PSI_COLUMNS."""
+    psi_columns = PSI_COLUMNS if psi_columns is None else psi_columns
     x = np.array(x, dtype=np.float64, copy=True)
     fitted = np.asarray(fitted, dtype=bool)
     if not fitted.any():
         raise ValueError("no frame has a pose fit: no marker was triangulated in the whole sequence")
     idx = np.arange(len(x))
     for p in range(x.shape[1]):
-        col = np.unwrap(x[fitted, p]) if p in PSI_COLUMNS else x[fitted, p]
+        col = np.unwrap(x[fitted, p]) if p in psi_columns else x[fitted, p]
         x[:, p] = np.interp(idx, idx[fitted], col)
     return x
 

@@ -18,6 +18,7 @@
  *                                    same dense detections as acino_triangulate_pairs
  *   acino_cheetah_pose_fit           (no counterpart) per-frame pose with error bars from 3-D marker points and their
  *                                    covariances (the outputs of acino_triangulate_multiview)
+ *   acino_skel_pose_fit              (no counterpart) the same for a skeleton's link program (acino_skel_fte_*)
  *   acino_cheetah_fk                 pose_to_3d                       src/all_optimizations.py:66-190
  *   acino_fte_*                      the Pyomo model + opt.solve()    src/all_optimizations.py:283-556
  *
@@ -959,6 +960,37 @@ int acino_skel_fte_reprojection_weights(const acino_skel_fte_params* p, int n_cl
                                         const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
                                         const double* d_x, const double* d_cov_pos, double gate_w, double* d_uv, double* d_cov_uv,
                                         double* d_res, double* d_mahal2, uint8_t* d_flags, double* d_weight, void* stream);
+
+/* ---- per-frame pose fit of a skeleton from 3-D points with a covariance each (csrc/skel_pose_fit.hip) -------------------
+ * acino_cheetah_pose_fit for a link program.  Per frame n, from d_points[N][n_pose][3] (metres; slot l is pose slot l of the
+ * link program) and d_cov[N][n_pose][3][3], over the P = n_active states x inside the frame's box d_lo[n] <= x <= d_hi[n]:
+ *   F(x) = 1/2 sum_{l enters} (FK_l(x) - y_l)^T W_l (FK_l(x) - y_l) + 1/2 sum_{p >= 3} (x_p - m_p)^2 / prior_sigma^2.
+ * The entry rule of a slot, W_l, m, the ridge (on the angles only, never on x, y, z), the iteration, its stops and the status
+ * codes are those of acino_cheetah_pose_fit; acino_pose_fit_params is reused with min_markers in 1..n_pose.
+ * Start: d_x0[N][P], or with d_x0 NULL every angle 0 and x, y, z the mean over the entering slots, in slot order, of
+ * y_l - rest_l, rest the poses of the zero state; clipped to the box.
+ * Of p ONLY n_pose, n_ops, n_angles and n_active are read (limits as acino_skel_fte_solve; no camera, no frame count, no
+ * solver field); h_ops / h_active as the solve.  The dynamic LDS of a frame is sized from (n_active, n_pose, n_ops): 157 KB
+ * for the largest shape the limits allow (64 states, 65 slots), 42 KB for the shipped human skeleton; a shape beyond
+ * 160 KB would be ACINO_ERR_INVALID_ARG.
+ * At the returned x (every floating-point output of a frame is NaN, and d_pinned 0, for status 2 and 3):
+ *   d_x[N][P], d_cost[N], d_nmarkers[N] (slots that entered), d_status[N], d_iters[N] (trials made), d_pinned[N][P]
+ *   d_cov_x[N][P][P]          A_free^-1 without a Marquardt term, rows and columns of pinned states exactly 0, symmetric
+ *                             bit for bit
+ *   d_pos[N][n_pose][3]       FK(x)
+ *   d_cov_pos[N][n_pose][3][3]  G_l cov_x G_l^T for every slot, with or without a point, symmetric bit for bit;
+ *   d_std_pos[N][n_pose]      sqrt((c00 + c11) + c22)
+ * Any output but d_x and d_status may be NULL.  d_ws: acino_skel_pose_fit_workspace_bytes(p) bytes, 256-byte aligned (the
+ * device copy of the link program; 0: p is outside the limits).  Argument validation happens before any device call;
+ * n_frames == 0 is a no-op.  One launch (one 64-lane wave per frame), no synchronisation: d_ws and the device arrays must
+ * stay valid until the stream reaches it. */
+size_t acino_skel_pose_fit_workspace_bytes(const acino_skel_fte_params* p);
+int acino_skel_pose_fit(const acino_pose_fit_params* prm, const acino_skel_fte_params* p, const acino_skel_op* h_ops,
+                        const int32_t* h_active, const double* d_points /* [N][n_pose][3] */,
+                        const double* d_cov /* [N][n_pose][3][3] or NULL */, const double* d_x0 /* [N][P] or NULL */,
+                        const double* d_lo, const double* d_hi /* [N][P] */, int64_t n_frames, double* d_x, double* d_cost,
+                        uint8_t* d_nmarkers, uint8_t* d_status, uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x,
+                        double* d_pos, double* d_cov_pos, double* d_std_pos, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
