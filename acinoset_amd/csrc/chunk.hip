@@ -122,6 +122,16 @@ __device__ __forceinline__ void syrk_mask_n(d4 (&acc)[NQ], bool load) {
 // the stencil pass; tdone (a wave's tiles of F^T T are finished: the strips it read may be overwritten) and fready (a wave's
 // strips of F_k+1 are complete) among the S waves.  No workgroup barrier inside the node loop: the S team's tail (T -> Y,
 // stencil) runs under the D team's G_k+1, the D team's build under the S team's T = G F.
+// The ENDS of a run, where half the CU would stand idle, have their own role map:
+//   first node (before the loop; the strip waves have no spike yet): chain wave 0, helper L wave 1, helper U WAVE 2 - each
+//     helper with the matrix pipe of its own SIMD; wave 5 is helper U from the second node on (TrioSync::sat_out).
+//   last node of a run with a left separator (no factorisation follows): once the right separator is built, wave 0 takes
+//     strip 3 and wave 1 strip 0 with their whole pipelines (spike_node, roles 10 and 9: F from Y, T = G F, F^T T, T -> Y,
+//     stencil, store of their strip of block(R, L)); wave 6 keeps strip 2 alone (role 8), wave 3 computes its tiles of G_k and
+//     stores G_k in wave 4's place, waves 5 and 4 store the right separator's diagonal block.  Matrix instructions of
+//     the spike per SIMD: 190 | 114 | 285 | 171 (waves 0, 4 | 1, 5 | 2, 6 | 3, 7) instead of 0 | 0 | 399 | 361.  The tiles of AL that
+//     change owner (role 6's five, tile {0,0}) are handed over through memory: the old owner waits for its stores and signals
+//     c_end, the new owner loads at device scope behind its poll (hand_over, AlTiles::fetch_handed_over).
 // (k-step 19 - rows 76 .. 79 of F and of T - is skipped everywhere: those rows are exact zeros)
 constexpr int SP_STEPS = 4 * NT - 1;
 __device__ __forceinline__ void spike_gf(const double* G, const double (&bF)[NT][4], d4 (&acc)[NT], int li, int lk) {
@@ -182,6 +192,15 @@ struct AlTiles {
     for (int q = 0; q < NQ; ++q)
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) acc[q][rr] = *at(q, rr, li, lk);
+  }
+  // The tiles of a wave that takes them over from ANOTHER wave of the workgroup for the run's last node (spike_node, roles
+  // 9 and 10): the previous owner has waited for its stores of node k - 1 and signalled (hand_over), and these loads are
+  // issued behind the poll and at device scope - answered by the L2, which holds those stores, whatever the CU's L1 holds.
+  __device__ __forceinline__ void fetch_handed_over(int li, int lk) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) acc[q][rr] = __hip_atomic_load(at(q, rr, li, lk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __device__ __forceinline__ void run(bool load, const double* Yf, const d4 (&T)[NT], int li, int lk) {
     syrk_mask_n<NQ>(acc, load);
@@ -264,6 +283,15 @@ __device__ __forceinline__ void gram_fixed(const double* Xf, double* Xg, int* do
 // The spike of one node on one strip wave (ROLE 4: wave 2, strip 1 | 5: wave 6, strips 2 and 0 | 6: wave 3, strip 3 | 7: wave 7,
 // strip 4), a function per role so that each gets its own register allocation.  Tiles of F^T T: role 4 {1,1} {0,1} {1,2},
 // role 5 {2,2} {0,2} | {0,0}, role 6 {3,3} {0,3} {1,3} {2,3} {3,4}, role 7 {4,4} {0,4} {1,4} {2,4}.
+// The LAST node of a run with a left separator (no factorisation follows: the D team's two SIMDs would stand idle from the
+// build on) deals one strip of each S SIMD to a D wave, with its whole pipeline:
+//   ROLE 8: wave 6, strip 2 alone, tiles {2,2} {0,2}            ROLE 9: wave 1, strip 0, tile {0,0} (role 5's second strip)
+//   ROLE 10: wave 0, strip 3 with role 6's five tiles; wave 3 computes its tiles of G_k and stores G_k at that node
+// per SIMD 152 + 133 (waves 2, 6), 171 (wave 7), 190 (wave 0), 114 (wave 1) of the 760 matrix instructions, against 399 | 361.
+// A moved strip's F is read from Y by a wave that did not write it (it waits for fready of node k - 1), its tiles of AL
+// change owner through memory (AlTiles::fetch_handed_over; c_end below), strip 0 is now written by a wave that role 8 - a
+// reader, tile {0,2} - does not share: role 8 reports its tiles on c_end.  Every strip of block(R, L) is stored by its owner.
+// c_end (used at that node only): 1 + 1 when waves 3 and 6 have handed their tiles over, the third arrival = role 8's tiles.
 struct SpikeArgs {
   const double* Xg;
   double* Y;
@@ -275,16 +303,36 @@ struct SpikeArgs {
                                                      // its right-hand side in HBM; both null at every other node
   int *c_gfdone, *c_fready, *c_bv, *tdone;           // tdone[0 .. 2]: tile batches finished by roles 4, 6, 7
   int *g_open, *g_done;
+  int* c_end;                                        // the last node's hand-overs (above)
   const double* Xf;
   int k, n_s;
   bool hasL, has_next;
   long long* stamps;
 };
+// G_k -> HBM by one wave, lower tiles only (G is symmetric: the back-substitution mirrors them), 30 items per lane
+__device__ __forceinline__ void store_G(const double* Xg, double* Gg, int ln) {
+#pragma unroll 6
+  for (int q = 0; q < LOWER_ITEMS / 64; ++q) {
+    const int idx = ln + 64 * q;
+    int r, cc;
+    lower_item(idx, r, cc);
+    *reinterpret_cast<double2*>(Gg + r * BS + cc) = make_double2(Xg[r * LD + cc], Xg[r * LD + cc + 1]);
+  }
+}
+// A wave gives tiles of AL to another wave of the workgroup: every store it has issued (its tiles of node k - 1) is complete
+// before the signal - the one place where the counter protocol does wait for global memory, once per run.
+__device__ __forceinline__ void hand_over(int* c_end, int ln) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  lds_signal(c_end, ln);
+}
 template <int ROLE>
 __device__ __forceinline__ void spike_node(const SpikeArgs& A, int& tsb, int ln) {
   constexpr bool two = ROLE == 5;
-  constexpr int j0 = ROLE == 4 ? 1 : (ROLE == 5 ? 2 : (ROLE == 6 ? 3 : 4));
-  constexpr int NA = ROLE == 4 ? 3 : (ROLE == 5 ? 2 : (ROLE == 6 ? 5 : 4));
+  constexpr bool moved = ROLE >= 9;                    // a D wave with a strip that another wave held until this node
+  constexpr int j0 = ROLE == 4 ? 1 : (ROLE == 5 || ROLE == 8 ? 2 : (ROLE == 6 || ROLE == 10 ? 3 : (ROLE == 7 ? 4 : 0)));
+  constexpr int NA = ROLE == 4 ? 3 : (ROLE == 5 || ROLE == 8 ? 2 : (ROLE == 6 || ROLE == 10 ? 5 : (ROLE == 7 ? 4 : 1)));
+  // stamps: a role of the last node takes the places of wave 6's (8) and of the factorisation's, which does not run then (9, 10)
+  constexpr int sb = ROLE <= 7 ? 16 + 4 * (ROLE - 4) : (ROLE == 8 ? 20 : (ROLE == 9 ? 40 : 44));
   const int li = ln & 15, lk = ln >> 4;
   double* const Y = A.Y;
   auto stamp = [&](int i) { if (A.stamps && ln == 0) A.stamps[i] = (long long)wall_clock64(); };
@@ -293,18 +341,23 @@ __device__ __forceinline__ void spike_node(const SpikeArgs& A, int& tsb, int ln)
   al.Ag = A.Ag;
   al.j = j0;
   if (ROLE == 4) { al.as[0] = 1; al.as[1] = 0; al.as[2 % NA] = 2; }
-  if (ROLE == 5) { al.as[0] = 2; al.as[1] = 0; }
-  if (ROLE == 6) { al.as[0] = 3; al.as[1] = 0; al.as[2 % NA] = 1; al.as[3 % NA] = 2; al.as[4 % NA] = 4; }
+  if (ROLE == 5 || ROLE == 8) { al.as[0] = 2; al.as[1 % NA] = 0; }
+  if (ROLE == 6 || ROLE == 10) { al.as[0] = 3; al.as[1 % NA] = 0; al.as[2 % NA] = 1; al.as[3 % NA] = 2; al.as[4 % NA] = 4; }
   if (ROLE == 7) { al.as[0] = 4; al.as[1] = 0; al.as[2 % NA] = 1; al.as[3 % NA] = 2; }
+  if (ROLE == 9) al.as[0] = 0;
   al0.Ag = A.Ag;
   al0.j = 0;
   al0.as[0] = 0;
-  if (A.hasL) {
+  if (ROLE == 8) hand_over(A.c_end, ln);               // tile {0, 0} leaves this wave: its store of node k - 1 is complete
+  if (moved) {
+    lds_wait2(A.c_end, 2, A.c_fready, A.n_s * A.k);    // the tiles handed over; every strip of F_k complete (written by others)
+    al.fetch_handed_over(li, lk);
+  } else if (A.hasL) {
     al.fetch(li, lk);
     if (two) al0.fetch(li, lk);
   }
   // G_k: this wave's tiles of the fixed schedule once U_k is complete and Xg free (waves 3 and 7), then wait for the last one
-  if (ROLE >= 6) {
+  if (ROLE == 6 || ROLE == 7) {
     double* const Xg = const_cast<double*>(A.Xg);
     lds_wait(A.g_open, A.k + 1);
     if (ROLE == 6) gram_fixed<2, 13>(A.Xf, Xg, A.g_done, li, lk, ln);
@@ -312,7 +365,7 @@ __device__ __forceinline__ void spike_node(const SpikeArgs& A, int& tsb, int ln)
     else gram_fixed<2, 5, 9, 13, 14>(A.Xf, Xg, A.g_done, li, lk, ln);     // (wave 3 is not alive)
   }
   lds_wait(A.g_done, 15 * (A.k + 1));
-  stamp(16 + 4 * (ROLE - 4));
+  stamp(sb + 0);
   d4 T0[NT], T1[NT];
   {
     double bF[NT][4];
@@ -333,21 +386,28 @@ __device__ __forceinline__ void spike_node(const SpikeArgs& A, int& tsb, int ln)
     spike_gf(A.Xg, bF, T1, li, lk);
   }
   lds_signal(A.c_gfdone, ln);                          // this wave is through with G_k
-  stamp(17 + 4 * (ROLE - 4));
+  stamp(sb + 1);
   if (A.hasL) {
     lds_wait(A.c_fready, A.n_s * A.k);                 // every strip of F_k is complete
     al.run(A.k > 0, Y, T0, li, lk);
     if (two) al0.run(A.k > 0, Y, T1, li, lk);
   }
-  stamp(18 + 4 * (ROLE - 4));
+  stamp(sb + 2);
   // nobody reads this wave's strips of F_k any more: strip 3 is read by its owner only, strip 4 also by role 6 (tile {3,4}),
   // strip 1 by roles 6 and 7, strips 0 and 2 (role 5) by everybody - and role 5 itself reads no strip but its own: nobody waits
-  // for the wave with two strips, which finishes its tiles last
+  // for the wave with two strips, which finishes its tiles last.  At the last node role 10 stands for role 6 (tdone[1] goes on
+  // counting), strip 2 is role 8's and strip 0 role 9's, which also waits for role 8's tile {0,2}: the third arrival on c_end,
+  // behind the two hand-overs (a wait that has long been met).
   if (A.hasL) {
-    if (ROLE != 5) lds_signal(A.tdone + (ROLE == 4 ? 0 : (ROLE == 6 ? 1 : 2)), ln);
-    if (ROLE == 7 || ROLE == 4 || ROLE == 5) lds_wait(A.tdone + 1, A.k + 1);
-    if (ROLE == 4 || ROLE == 5) lds_wait(A.tdone + 2, A.k + 1);
-    if (ROLE == 5) lds_wait(A.tdone + 0, A.k + 1);
+    if (ROLE == 4 || ROLE == 6 || ROLE == 7 || ROLE == 10) lds_signal(A.tdone + (ROLE == 4 ? 0 : (ROLE == 7 ? 2 : 1)), ln);
+    if (ROLE == 8) {
+      lds_wait(A.c_end, 2);
+      lds_signal(A.c_end, ln);
+    }
+    if (ROLE == 7 || ROLE == 4 || ROLE == 5 || ROLE == 8 || ROLE == 9) lds_wait(A.tdone + 1, A.k + 1);
+    if (ROLE == 4 || ROLE == 5 || ROLE == 8 || ROLE == 9) lds_wait(A.tdone + 2, A.k + 1);
+    if (ROLE == 5 || ROLE == 8 || ROLE == 9) lds_wait(A.tdone + 0, A.k + 1);
+    if (ROLE == 9) lds_wait(A.c_end, 3);
   }
   (void)tsb;
   // ---- T_k -> Y (own strips), z_k (column 79 of T) -> HBM, then F_k+1 = -E^T T_k in place, column 79 += the next node's
@@ -402,11 +462,12 @@ __device__ __forceinline__ void spike_node(const SpikeArgs& A, int& tsb, int ln)
     }
   }
   lds_signal(A.c_fready, ln);
-  stamp(19 + 4 * (ROLE - 4));
+  stamp(sb + 3);
   // After the run's last node F is block(R, L) of the right separator, and this wave's strips of it are final: -> HBM by their
   // owner, now (columns >= 75 are not part of the separator's coupling: zero), the separator's right-hand side (column 79) by
   // strip 4's.  (LDS operations of one wave complete in order: the lanes read what other lanes of the wave have just written.)
-  // The wave with two strips is the last one out of the node: its strips are stored by the idle D waves, which wait for it.
+  // (No wave holds two strips at that node when there is a left separator - roles 8, 9, 10 above: every strip has an owner
+  //  that stores it.)
   if (A.bR) {
     if (A.Cg && !two) {
       const int cc = 16 * j0 + li;
@@ -437,7 +498,8 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
   int* const cB = sync + 5;                            // barrier of the four D waves
   int* const tdone = sync + 2;                         // [3]: tile batches of F^T T finished by roles 4, 6, 7 (sync[2 .. 4])
   int* const g_done = sync + 6;                        // tiles of G finished (15 per node)
-  int* const g_open = sync + 10;                       // G_k may start: U_k complete, Xg free (sync[1] is unused)
+  int* const g_open = sync + 10;                       // G_k may start: U_k complete, Xg free
+  int* const c_end = sync + 1;                         // the last node's hand-overs between waves (spike_node)
   int* const c_gfdone = sync + 7;
   int* const c_fready = sync + 8;
   int* const c_bv = sync + 9;
@@ -512,7 +574,12 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       }
     if (tid < BS) Y[tid * LD + (BS - 1)] = bvb[tid];
     __syncthreads();
-    if (role < 3) chol80_trio(Xf, role, lane, numeric_err, sync, tsy);
+    // The strip waves have nothing to do before the first node is factored, and their two SIMDs stand idle: helper U's role
+    // is wave 2's for this one call, so that helper L (wave 1) has the matrix pipe of its SIMD to itself as in the separator
+    // kernels.  Wave 5 takes the role from the next node on (its counters move on as if it had been there); the tiles are the
+    // same instructions on the same operands whichever wave issues them.
+    if (role < 2 || role == 4) chol80_trio(Xf, role == 4 ? 2 : role, lane, numeric_err, sync, tsy, (dbgp && dbg_k < 0) ? lst : nullptr);
+    else if (role == 2) tsy.sat_out(true);
     __syncthreads();
     if (dbgp && tid == 0) lst[61] = (long long)wall_clock64();
   }
@@ -561,6 +628,19 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       }
     }
     double* const cRk = tab_cur ? cL : cR0;
+    // The last node of a run with a left separator: waves 0 and 1 take a strip of the spike each once the right separator is
+    // built (roles 10 and 9 of spike_node), wave 6 keeps strip 2 alone (role 8), wave 3 its tiles of G_k and wave 4's store of G_k.
+    const bool spread = last && hasL;
+    auto spike_args = [&]() {
+      SpikeArgs sa;
+      sa.Xg = Xg; sa.Y = Y; sa.Ag = sp.AL + (size_t)(hasL ? opaque(sL) : 0) * MB; sa.cRk = cRk; sa.bvn = bvb + ((k + 1) & 1) * BS;
+      sa.zk = ch.b + (size_t)node * BS; sa.g_open = g_open; sa.g_done = g_done; sa.Xf = Xf; sa.c_gfdone = c_gfdone; sa.c_fready = c_fready; sa.c_bv = c_bv; sa.tdone = tdone;
+      sa.c_end = c_end;
+      sa.bR = (last && hasR) ? sp.b + (size_t)sR * BS : nullptr;
+      sa.Cg = (last && hasR && hasL) ? sp.Cpl + (size_t)sL * MB : nullptr;
+      sa.k = k; sa.n_s = n_s; sa.hasL = hasL; sa.has_next = has_next; sa.stamps = (dbgp && k == dbg_k) ? lst : nullptr;
+      return sa;
+    };
     if (builder) {
       // ============================== G_k and the next node: the four D waves ==============================
       const int bw = role;                             // 0 chain, 1, 2 helpers, 3 the chain's SIMD mate (wave 4)
@@ -739,56 +819,58 @@ k_chunk_sweep(BcrChain ch, SepView sp, const FteConst* __restrict__ cst, int* nu
       lds_barrier(cB, tb, 4, ln);                      // next node complete in Xf
       if (bt == 0) __hip_atomic_fetch_add(c_bv, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (bw == 0) SW_STAMP(4);
+      // the node built last is the right separator: its diagonal block is final in Xf -> HBM now, while the spike is finished
+      auto store_sep_diag = [&](int part, int parts) {
+        double2* d2 = reinterpret_cast<double2*>(sp.D + (size_t)sR * MB);
+        for (int idx = 64 * part + ln; idx < BS * BS / 2; idx += 64 * parts) {
+          const int e = 2 * idx, r = e / BS, cc = e % BS;
+          d2[idx] = make_double2(Xf[r * LD + cc], Xf[r * LD + cc + 1]);
+        }
+      };
       if (bw < 3) {
         // (no closing barrier of the trio: the four D waves meet at the top of the next iteration, before anyone reads the factor)
         if (!last) {
           chol80_trio<false>(Xf, bw, ln, numeric_err, sync, tsy, (dbgp && k == dbg_k) ? lst : nullptr);
-        } else if (hasR) {
-          // the node built last is the right separator: its diagonal block is final in Xf -> HBM now, by the three waves that
-          // have no factorisation to do, while the strip waves finish the spike
-          double2* d2 = reinterpret_cast<double2*>(sp.D + (size_t)sR * MB);
-          for (int idx = bt; idx < BS * BS / 2; idx += 192) {
-            const int e = 2 * idx, r = e / BS, cc = e % BS;
-            d2[idx] = make_double2(Xf[r * LD + cc], Xf[r * LD + cc + 1]);
-          }
-          if (hasL) {
-            // strips 2 and 0 of block(R, L), the two of wave 6, once every strip wave is through with its stencil pass (the other
-            // strips are stored by their owners, spike_node): 2 x 80 rows x 8 two-double items
-            double* const Cg = sp.Cpl + (size_t)sL * MB;
-            lds_wait(c_fready, n_s * (k + 1));
-#pragma unroll 7
-            for (int idx = bt; idx < 2 * BS * 8; idx += 192) {
-              const int h = idx / (BS * 8), rem = idx % (BS * 8), r = rem >> 3, cc = (h ? 32 : 0) + 2 * (rem & 7);
-              *reinterpret_cast<double2*>(Cg + r * BS + cc) = make_double2(Y[r * LD + cc], Y[r * LD + cc + 1]);
-            }
-          }
+        } else if (!spread) {
+          if (hasR) store_sep_diag(bw, 3);             // by the three waves that have no factorisation to do
+        } else if (bw == 2) {
+          if (hasR) store_sep_diag(0, 2);              // by waves 5 and 4: waves 0 and 1 take a strip each
+        } else {
+          if (dbgp && k == dbg_k && ln == 0) lst[63] = (long long)wall_clock64();    // (tells the stamps' reader the role map)
+          const SpikeArgs sa = spike_args();
+          if (bw == 0) spike_node<10>(sa, tsb, ln);
+          else spike_node<9>(sa, tsb, ln);
         }
         SW_STAMP(8 + wave);
       } else if (bw == 3) {
-        // G_k -> HBM, lower tiles only (G is symmetric: the back-substitution mirrors them): the chain's SIMD mate, 30 items per lane
-        double* Gg = ch.D + node * MB;
-#pragma unroll 6
-        for (int q = 0; q < LOWER_ITEMS / 64; ++q) {
-          const int idx = ln + 64 * q;
-          int r, cc;
-          lower_item(idx, r, cc);
-          *reinterpret_cast<double2*>(Gg + r * BS + cc) = make_double2(Xg[r * LD + cc], Xg[r * LD + cc + 1]);
-        }
+        // G_k -> HBM: the chain's SIMD mate.  (At a last node with the roles spread wave 3, which has no strip there, stores it:
+        // this wave's SIMD mate streams matrix instructions then, and a wave that moves data beside it is 3x slower and slows it.)
+        if (!spread) store_G(Xg, ch.D + node * MB, ln);
+        else if (hasR) store_sep_diag(1, 2);
         SW_STAMP(8 + wave);
       }
     }
     if (strips) {
       // ============================== the spike of node k ==============================
-      SpikeArgs sa;
-      sa.Xg = Xg; sa.Y = Y; sa.Ag = sp.AL + (size_t)(hasL ? opaque(sL) : 0) * MB; sa.cRk = cRk; sa.bvn = bvb + ((k + 1) & 1) * BS;
-      sa.zk = ch.b + (size_t)node * BS; sa.g_open = g_open; sa.g_done = g_done; sa.Xf = Xf; sa.c_gfdone = c_gfdone; sa.c_fready = c_fready; sa.c_bv = c_bv; sa.tdone = tdone;
-      sa.bR = (last && hasR) ? sp.b + (size_t)sR * BS : nullptr;
-      sa.Cg = (last && hasR && hasL) ? sp.Cpl + (size_t)sL * MB : nullptr;
-      sa.k = k; sa.n_s = n_s; sa.hasL = hasL; sa.has_next = has_next; sa.stamps = (dbgp && k == dbg_k) ? lst : nullptr;
+      const SpikeArgs sa = spike_args();
       if (role == 4) spike_node<4>(sa, tsb, ln);
-      else if (role == 5) spike_node<5>(sa, tsb, ln);
-      else if (role == 6) spike_node<6>(sa, tsb, ln);
-      else spike_node<7>(sa, tsb, ln);
+      else if (role == 5) {
+        if (spread) spike_node<8>(sa, tsb, ln);
+        else spike_node<5>(sa, tsb, ln);
+      } else if (role == 6) {
+        if (spread) {                                  // its strip is wave 0's at this node: the tiles of AL handed over, then G_k's
+          hand_over(c_end, ln);
+          lds_wait(g_open, k + 1);
+          gram_fixed<2, 13>(Xf, Xg, g_done, li, lk, ln);
+          lds_wait(g_done, 15 * (k + 1));
+          store_G(Xg, ch.D + node * MB, ln);           // (wave 4's at every other node)
+          if (dbgp && k == dbg_k && ln == 0) lst[24] = (long long)wall_clock64();
+        } else {
+          spike_node<6>(sa, tsb, ln);
+        }
+      } else {
+        spike_node<7>(sa, tsb, ln);
+      }
     }
   }
   __syncthreads();                                     // both teams through

@@ -192,6 +192,16 @@ __device__ __forceinline__ void panel_tiles(double* Lm, int kb, int t0, int li, 
 }
 struct TrioSync {
   int t3 = 0, posts = 0, crit = 0, lpan = 0, udone = 0, ulow = 0;
+  // a wave that sat one call of chol80_trio<MEET> out - another wave took its role for that call - and takes the role from
+  // the next call on: the counters went on without it
+  __device__ __forceinline__ void sat_out(bool meet) {
+    if (meet) t3 += 3;
+    posts += 9;
+    crit += 4;
+    lpan += 4;
+    udone += 1;
+    ulow += 1;
+  }
 };
 // (MEET = false: no closing barrier of the three - the caller's next synchronisation point includes them all)
 template <bool MEET = true>
