@@ -763,10 +763,6 @@ def _check_init(init):
         raise ValueError(f"init must be 'line' or 'pose_fit' (got {init!r})")
 
 
-def _shape(a):
-    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-
-
 def pose_fit(model, points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01, min_markers=1, max_iter=100, ftol=1e-10,
              xtol=1e-10, lam0=1e-3, return_cov=True):
     """Per-frame pose of a ``SkeletonModel`` from 3-D points with a covariance each (include/acinoset_hip.h:
@@ -795,55 +791,24 @@ def pose_fit(model, points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01
       [N, n_pose] in metres.
 
     numpy in, numpy out; CUDA tensors in, CUDA tensors out with no host copy."""
-    if isinstance(points, dict):
-        if cov is not None:
-            raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
-        points, cov = points["points"], points["cov"]
     act = np.asarray(model.active, dtype=np.int32)
     N, Pa, Lp = model.N, len(act), len(model.names)
-    if _shape(points) != (N, Lp, 3):
-        raise ValueError(f"points must be [{N}, {Lp}, 3] (model.N frames, one slot per pose)")
-    if cov is not None and _shape(cov) != (N, Lp, 3, 3):
-        raise ValueError(f"cov must be [{N}, {Lp}, 3, 3]")
-    if x0 is not None and _shape(x0) != (N, Pa):
-        raise ValueError(f"x0 must be [{N}, {Pa}] (the active states)")
-    for name, val in (("prior_sigma", prior_sigma), ("sigma_iso", sigma_iso), ("ftol", ftol), ("xtol", xtol), ("lam0", lam0)):
-        if not (np.isfinite(val) and val > 0):
-            raise ValueError(f"{name} must be finite and > 0")
-    if int(max_iter) != max_iter or not 1 <= max_iter <= 255:
-        raise ValueError("max_iter must be an integer in 1..255")
-    if int(min_markers) != min_markers or not 1 <= min_markers <= Lp:
-        raise ValueError(f"min_markers must be an integer in 1..{Lp}")
-    dev = calib._dev()
-    pts = calib._to_dev(points, dev)
-    cv = None if cov is None else calib._to_dev(cov, dev)
-    xs = None if x0 is None else calib._to_dev(x0, dev)
-    lo, hi = calib._to_dev(model.lo[:, act], dev), calib._to_dev(model.hi[:, act], dev)
-    p = _skel_params(model, Pa)
-    nbytes = lib().acino_skel_pose_fit_workspace_bytes(C.byref(p))
-    if nbytes == 0:
-        raise ValueError("problem outside the kernel limits (n_active <= 64)")
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
-    x, cost, pos = torch.empty((N, Pa), **f64), torch.empty((N,), **f64), torch.empty((N, Lp, 3), **f64)
-    nm, status, iters, pinned = (torch.empty(sh, **u8) for sh in ((N,), (N,), (N,), (N, Pa)))
-    cov_x = torch.empty((N, Pa, Pa), **f64) if return_cov else None
-    cov_pos = torch.empty((N, Lp, 3, 3), **f64) if return_cov else None
-    std_pos = torch.empty((N, Lp), **f64) if return_cov else None
-    prm = _lib.PoseFitParams(int(max_iter), int(min_markers), float(lam0), float(ftol), float(xtol), float(prior_sigma),
-                             float(sigma_iso))
-    act_c = (C.c_int32 * Pa)(*[int(a) for a in act])
-    check(lib().acino_skel_pose_fit(prm, C.byref(p), _ops_array(model.prog), act_c, ptr(pts), ptr(cv), ptr(xs), ptr(lo), ptr(hi), N,
-                                    ptr(x), ptr(cost), ptr(nm), ptr(status), ptr(iters), ptr(pinned), ptr(cov_x), ptr(pos),
-                                    ptr(cov_pos), ptr(std_pos), C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
-    x_full = torch.zeros((N, model.P), **f64)
-    x_full[:, torch.as_tensor(act.astype(np.int64), device=dev)] = x
-    out = dict(x=x, x_full=x_full, positions=pos, cost=cost, n_markers=nm, status=status, iters=iters, pinned=pinned)
-    if return_cov:
-        out.update(cov_x=cov_x, cov_positions=cov_pos, std_positions=std_pos)
-    if isinstance(points, torch.Tensor):               # (the workspace goes back to the allocator of this very stream)
-        return out
-    return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def launch(prm, dev, N, ins, outs):
+        lo, hi = calib._to_dev(model.lo[:, act], dev), calib._to_dev(model.hi[:, act], dev)
+        p = _skel_params(model, Pa)
+        nbytes = lib().acino_skel_pose_fit_workspace_bytes(C.byref(p))
+        if nbytes == 0:
+            raise ValueError("problem outside the kernel limits (n_active <= 64)")
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)      # (it goes back to the allocator of this very stream)
+        act_c = (C.c_int32 * Pa)(*[int(a) for a in act])
+        check(lib().acino_skel_pose_fit(prm, C.byref(p), _ops_array(model.prog), act_c, *ins, ptr(lo), ptr(hi), N, *outs,
+                                        C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
+
+    return fte._pose_fit(launch, points, cov, x0, N, Lp, act, model.P,
+                         (f"points must be [{N}, {Lp}, 3] (model.N frames, one slot per pose)", f"cov must be [{N}, {Lp}, 3, 3]",
+                          f"x0 must be [{N}, {Pa}] (the active states)"),
+                         prior_sigma, sigma_iso, min_markers, max_iter, ftol, xtol, lam0, return_cov)
 
 
 def model_triangulation(model, f_scale=5.0, sigma_px=None, **kw):

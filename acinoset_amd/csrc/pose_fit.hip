@@ -18,7 +18,9 @@
 // took 22.4 k ticks per trial with A on the VALU (325 entries over 64 lanes, summed over the markers two columns share) and
 // 9.5 k with the tiles.  The factorisation keeps row i of L in the registers of lane i and passes the pivot column between
 // lanes by v_readlane (no LDS traffic inside its 25 steps: the LDS form, a read-modify-write per entry, made the kernel twice
-// as long); the inverse for cov_x is 25 right-hand sides, one per lane, on the same registers.
+// as long); the inverse for cov_x is 25 right-hand sides, one per lane, on the same registers.  The frame after its prologue -
+// controller, factor steps, substitutions, epilogue - is pf_fit_frame<25> of pose_fit_dev.hpp, which skel_pose_fit.hip
+// instantiates too; this file is its model CheetahFit: FK frames, Jacobian, the three-tile Gram product, cov_x, the LDS.
 #include "fte_cov_dev.hpp"
 #include "pose_fit_dev.hpp"
 
@@ -40,15 +42,7 @@ static __device__ const double c_pf_hi[NP] = {
     M_PI / 2,     M_PI,         PF_INF,       M_PI / 6,     M_PI / 6,     M_PI / 1.5,  M_PI / 1.5};
 #undef PF_INF
 
-struct PoseFitArgs {
-  const double *points, *cov, *x0;
-  int64_t n_frames;
-  double *x, *cost;
-  uint8_t *nmarkers, *status, *iters, *pinned;
-  double *cov_x, *pos, *cov_pos, *std_pos;
-  int max_iter, min_markers;
-  double lam0, ftol, xtol, kappa, inv_sigma_iso;
-};
+using PoseFitArgs = PoseFitIo;
 
 struct PoseFitLds {
   CovFrame F[2];
@@ -62,9 +56,6 @@ struct PoseFitLds {
   double red[64];
   unsigned colmask[NP];        // the markers that move with state p
 };
-
-// np.clip: a NaN stays a NaN
-__device__ __forceinline__ double pf_clip(double v, int p) { return v != v ? v : fmin(fmax(v, c_pf_lo[p]), c_pf_hi[p]); }
 
 // sin / cos and the head position of ``xv``, then the three columns of the chain
 __device__ __forceinline__ void pf_frame(CovFrame& F, const double* xv, int lane) {
@@ -203,74 +194,6 @@ __device__ __forceinline__ void pf_normal(PoseFitLds& S, unsigned emask, double 
   __syncthreads();
 }
 
-// the active set at S.x, one bit per state: at a bound with the gradient pushing outward (oracle active_set, cov_codes)
-__device__ __forceinline__ unsigned pf_active_set(const PoseFitLds& S, int lane) {
-  bool fixed = false;
-  if (lane < NP) {
-    const double xv = S.x[lane], gv = S.g[lane], gtol = GRAD_ZERO_REL * S.A[lane][lane];
-    fixed = (xv <= c_pf_lo[lane] && gv > gtol) || (xv >= c_pf_hi[lane] && gv < -gtol);
-  }
-  return (unsigned)__ballot(fixed);
-}
-
-// Cholesky factor of A + lam diag(A) on the free states (identity rows for the pinned ones), row i in the registers of lane
-// i: r[j] = L[i][j] for j < i, dinv = 1 / L[i][i]; the rows are stored to S.L as well, for the products with L^T.  No LDS
-// traffic and no barrier inside the 25 steps: the pivot column passes between lanes by v_readlane.  False on a pivot that is
-// not above zero (the same value in every lane).
-__device__ __forceinline__ bool pf_factor(PoseFitLds& S, unsigned fixmask, double lam, int lane, double (&r)[NP],
-                                          double& dinv) {
-  const int i = lane < NP ? lane : NP - 1;        // (the lanes beyond the matrix shadow its last row; nothing reads them)
-  const bool fi = (fixmask >> i) & 1u;
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    double v = S.A[i][j];
-    if (fi || ((fixmask >> j) & 1u))
-      v = i == j ? 1.0 : 0.0;
-    else if (i == j)
-      v += lam * fmax(v, DIAG_FLOOR);
-    r[j] = v;
-  }
-  bool ok = true;
-  dinv = 0.0;
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    const double dk = pf_readlane(r[k], k);
-    ok = ok && dk > 0.0 && m_finite(dk);
-    double ik = __builtin_amdgcn_rsq(dk);         // 1 / sqrt(dk): the hardware estimate and two Newton steps
-#pragma unroll
-    for (int nr = 0; nr < 2; ++nr) ik = fma(0.5 * ik, fma(-dk * ik, ik, 1.0), ik);
-    const double lik = r[k] * ik;                 // L[i][k] in the lanes i > k
-    r[k] = lik;
-    if (lane == k) dinv = ik;
-#pragma unroll
-    for (int j = k + 1; j < NP; ++j) r[j] -= lik * pf_readlane(lik, j);
-  }
-  __syncthreads();                                // (the readers of the previous factor are done)
-  if (lane < NP) {
-#pragma unroll
-    for (int j = 0; j < NP; ++j) S.L[lane][j] = r[j];
-  }
-  __syncthreads();
-  return ok;
-}
-
-// d = (L L^T)^-1 b, lane p holding entry p: forward substitution on the rows in registers, back substitution on the rows
-// of S.L read as columns of L^T, the finished entry passed on by v_readlane
-__device__ __forceinline__ double pf_solve(const PoseFitLds& S, const double (&r)[NP], double dinv, double v, int lane) {
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    const double zk = pf_readlane(v * dinv, k);
-    v = lane == k ? zk : (lane > k ? v - r[k] * zk : v);
-  }
-  const int col = lane < NP ? lane : 0;
-#pragma unroll
-  for (int k = NP - 1; k >= 0; --k) {
-    const double xk = pf_readlane(v * dinv, k);
-    v = lane == k ? xk : (lane < k ? v - S.L[k][col] * xk : v);
-  }
-  return v;
-}
-
 // column ``lane`` of (L L^T)^-1 into z, every lane a right-hand side of its own: the entries of L come by v_readlane
 __device__ __forceinline__ void pf_inverse_column(const double (&r)[NP], double dinv, int lane, double (&z)[NP]) {
 #pragma unroll
@@ -289,10 +212,104 @@ __device__ __forceinline__ void pf_inverse_column(const double (&r)[NP], double 
   }
 }
 
+// the cheetah as a model of pf_fit_frame (pose_fit_dev.hpp): the constant box, FK frames F[cur] (the iterate's) and F[cur ^ 1]
+// (the trial's), A and the factor's rows in PoseFitLds
+struct CheetahFit {
+  static constexpr int RED2 = 32;
+  PoseFitLds& S;
+  const int (&piv)[PF_TASKS];
+  const double kappa;
+  const int lane;
+  const unsigned emask;
+  int cur = 0;
+
+  __device__ __forceinline__ static constexpr int n_states() { return NP; }
+  __device__ __forceinline__ static constexpr int n_slots() { return NL; }
+  __device__ __forceinline__ double* x() const { return S.x; }
+  __device__ __forceinline__ double* xt() const { return S.xt; }
+  __device__ __forceinline__ double* m() const { return S.m; }
+  __device__ __forceinline__ double* g() const { return S.g; }
+  __device__ __forceinline__ double* red() const { return S.red; }
+  __device__ __forceinline__ double* cp() const { return &S.L[0][0]; }      // [60][3]; the factor is not read again
+
+  __device__ __forceinline__ double lo(int p) const { return c_pf_lo[p]; }
+  __device__ __forceinline__ double hi(int p) const { return c_pf_hi[p]; }
+
+  __device__ __forceinline__ double eval(const double* xv, bool trial) {
+    CovFrame& T = S.F[trial ? cur ^ 1 : cur];
+    pf_frame(T, xv, lane);
+    return pf_cost(S, T, xv, kappa, lane);
+  }
+  __device__ __forceinline__ void linearise() {
+    pf_jacobian<false>(S, S.F[cur], emask, piv, lane);
+    pf_normal(S, emask, kappa, lane);
+  }
+  __device__ __forceinline__ void accepted() { cur ^= 1; }
+  __device__ __forceinline__ double diag(int p) const { return S.A[p][p]; }
+  // the active set at S.x, one bit per state: at a bound with the gradient pushing outward (oracle active_set, cov_codes)
+  __device__ __forceinline__ unsigned active_set(int lane) const {
+    bool fixed = false;
+    if (lane < NP) {
+      const double xv = S.x[lane], gv = S.g[lane], gtol = GRAD_ZERO_REL * S.A[lane][lane];
+      fixed = (xv <= c_pf_lo[lane] && gv > gtol) || (xv >= c_pf_hi[lane] && gv < -gtol);
+    }
+    return (unsigned)__ballot(fixed);
+  }
+
+  // pf_factor_rows; the rows are stored to S.L as well, for the products with L^T
+  __device__ __forceinline__ bool factor(unsigned fixmask, double lam, int lane, double (&r)[NP], double& dinv) {
+    const bool ok = pf_factor_rows<NP, PF_LD, false>(&S.A[0][0], fixmask, lam, lane, r, dinv);
+    __syncthreads();                              // (the readers of the previous factor are done)
+    if (lane < NP) {
+#pragma unroll
+      for (int j = 0; j < NP; ++j) S.L[lane][j] = r[j];
+    }
+    __syncthreads();
+    return ok;
+  }
+  // pf_solve, its back substitution on the rows of S.L read as columns of L^T
+  __device__ __forceinline__ double solve(const double (&r)[NP], double dinv, double v, int lane) const {
+    const int col = lane < NP ? lane : 0;
+    return pf_solve<NP, false>(r, dinv, v, lane, NP, [&](int k) { return &S.L[k][col]; });
+  }
+
+  // column c of the inverse by lane c, into row c of S.A (A itself is not read again); then symmetric bit for bit, pinned
+  // rows and columns exactly 0
+  __device__ __forceinline__ bool cov_x(unsigned fixmask, const double (&r)[NP], double dinv, int lane) {
+    bool ok = true;
+    double z[NP];
+    pf_inverse_column(r, dinv, lane, z);
+    if (lane < NP) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        S.A[lane][i] = z[i];
+        ok = ok && m_finite(z[i]);
+      }
+    }
+    ok = __all(ok);
+    __syncthreads();
+    for (int t = lane; t < PF_PAIRS; t += 64) {
+      int p = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+      if (p * (p + 1) / 2 > t) --p;
+      if ((p + 1) * (p + 2) / 2 <= t) ++p;
+      const int q = t - p * (p + 1) / 2;
+      const double v = (((fixmask >> p) | (fixmask >> q)) & 1u) ? 0.0 : 0.5 * (S.A[p][q] + S.A[q][p]);
+      S.A[p][q] = v;
+      S.A[q][p] = v;
+    }
+    return ok;
+  }
+  __device__ __forceinline__ void outputs_at_x(bool) {}                     // (F[cur] is the returned point's)
+  __device__ __forceinline__ double pos(int t) const { return S.F[cur].pos[t / 3][t % 3]; }
+  __device__ __forceinline__ double cov(int p, int q) const { return S.A[p][q]; }
+  __device__ __forceinline__ void jacobian_raw(int lane) { pf_jacobian<true>(S, S.F[cur], emask, piv, lane); }
+  __device__ __forceinline__ double jw(int p, int row) const { return S.Jw[p][row]; }
+  __device__ __forceinline__ bool moves(int p, int l) const { return (S.colmask[p] >> l) & 1u; }
+};
+
 __global__ void __launch_bounds__(64) k_pose_fit(PoseFitArgs a) {
   __shared__ PoseFitLds S;
   const int lane = threadIdx.x;
-  const double NaN = __builtin_nan("");
   if (lane < NP) {
     unsigned mk = 0xFFFFFu;
     if (lane >= 3) {
@@ -306,7 +323,7 @@ __global__ void __launch_bounds__(64) k_pose_fit(PoseFitArgs a) {
   pf_tasks(lane, piv);
   for (int64_t n = blockIdx.x; n < a.n_frames; n += gridDim.x) {
     __syncthreads();                              // the previous frame is done with S (and colmask is complete)
-    // ---- the markers that enter, their whitening factors
+    // ---- the markers that enter, their whitening factors (k_skel_pose_fit holds the twin of this prologue)
     bool enter = false;
     if (lane < NL) {
       double y[3], U[6];
@@ -335,166 +352,13 @@ __global__ void __launch_bounds__(64) k_pose_fit(PoseFitArgs a) {
       } else if (lane == 20 && (emask & 12u) == 12u) {
         v = atan2(S.y[3 * 2 + 1] - S.y[3 * 3 + 1], S.y[3 * 2] - S.y[3 * 3]);
       }
-      v = pf_clip(v, lane);
+      v = pf_clip(v, c_pf_lo[lane], c_pf_hi[lane]);
       S.m[lane] = v;
       S.x[lane] = v;
     }
     __syncthreads();
-
-    int st = PF_MAX_ITER, it = 0, cur = 0;
-    double F = NaN;
-    if (n_enter < a.min_markers) {
-      st = PF_FEW_MARKERS;
-    } else {
-      pf_frame(S.F[0], S.x, lane);
-      F = pf_cost(S, S.F[0], S.x, a.kappa, lane);
-      pf_jacobian<false>(S, S.F[0], emask, piv, lane);
-      pf_normal(S, emask, a.kappa, lane);
-      double lam = a.lam0, nu = 2.0;
-      if (!m_finite(F)) st = PF_NUMERIC;
-#pragma unroll 1
-      while (st == PF_MAX_ITER && it < a.max_iter) {
-        ++it;
-        const unsigned fixmask = pf_active_set(S, lane);
-        double r[NP], dinv;
-        if (!pf_factor(S, fixmask, lam, lane, r, dinv)) {
-          st = PF_NUMERIC;
-          break;
-        }
-        const bool free_p = lane < NP && !((fixmask >> lane) & 1u);
-        const double pg = free_p ? S.g[lane] : 0.0;
-        const double d = pf_solve(S, r, dinv, -pg, lane);
-        double term = 0.0, mv = 0.0;
-        if (lane < NP) {
-          const double xo = S.x[lane], xn = pf_clip(xo + d, lane);
-          S.xt[lane] = xn;
-          term = d * (lam * fmax(S.A[lane][lane], DIAG_FLOOR) * d - pg);
-          mv = fabs(xn - xo);
-        }
-        if (lane < NP) {
-          S.red[lane] = term;
-          S.red[32 + lane] = mv;
-        }
-        __syncthreads();
-        double pred = 0.0, step = 0.0;
-        for (int k = 0; k < NP; ++k) {
-          pred += S.red[k];
-          step = fmax(step, S.red[32 + k]);
-        }
-        pred *= 0.5;
-        __syncthreads();
-        CovFrame& T = S.F[cur ^ 1];
-        pf_frame(T, S.xt, lane);
-        const double Ft = pf_cost(S, T, S.xt, a.kappa, lane);
-        if (Ft < F) {
-          const double dF = F - Ft, gain = pred > 0.0 ? dF / pred : -1.0;
-          cur ^= 1;
-          F = Ft;
-          if (lane < NP) S.x[lane] = S.xt[lane];
-          __syncthreads();
-          pf_jacobian<false>(S, S.F[cur], emask, piv, lane);
-          pf_normal(S, emask, a.kappa, lane);
-          const double t = 2.0 * gain - 1.0;
-          lam *= fmax(1.0 / 3.0, 1.0 - t * t * t);
-          nu = 2.0;
-          if (dF <= a.ftol * fabs(F) || step <= a.xtol) st = PF_CONVERGED;
-        } else {
-          lam *= nu;
-          nu *= 2.0;
-          if (lam > 1e16) break;
-        }
-      }
-    }
-
-    // ---- the outputs at the returned x: the active set, A_free^-1, positions and J cov_x J^T
-    const bool want_cov = a.cov_x || a.cov_pos || a.std_pos;
-    bool live = st == PF_CONVERGED || st == PF_MAX_ITER;
-    unsigned fixmask = 0;
-    if (live) {
-      fixmask = pf_active_set(S, lane);
-      double r[NP], dinv;
-      bool ok = pf_factor(S, fixmask, 0.0, lane, r, dinv) && m_finite(F);
-      if (lane < NP) ok = ok && m_finite(S.x[lane]);
-      ok = __all(ok);
-      if (ok && want_cov) {
-        // column c of the inverse by lane c, into row c of S.A (A itself is not read again); then symmetric bit for bit,
-        // pinned rows and columns exactly 0
-        double z[NP];
-        pf_inverse_column(r, dinv, lane, z);
-        if (lane < NP) {
-#pragma unroll
-          for (int i = 0; i < NP; ++i) {
-            S.A[lane][i] = z[i];
-            ok = ok && m_finite(z[i]);
-          }
-        }
-        ok = __all(ok);
-        __syncthreads();
-        for (int t = lane; t < PF_PAIRS; t += 64) {
-          int p = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-          if (p * (p + 1) / 2 > t) --p;
-          if ((p + 1) * (p + 2) / 2 <= t) ++p;
-          const int q = t - p * (p + 1) / 2;
-          const double v = (((fixmask >> p) | (fixmask >> q)) & 1u) ? 0.0 : 0.5 * (S.A[p][q] + S.A[q][p]);
-          S.A[p][q] = v;
-          S.A[q][p] = v;
-        }
-      }
-      if (!ok) {
-        st = PF_NUMERIC;
-        live = false;
-      }
-      __syncthreads();
-    }
-
-    if (lane == 0) {
-      a.status[n] = (uint8_t)st;
-      if (a.nmarkers) a.nmarkers[n] = (uint8_t)n_enter;
-      if (a.iters) a.iters[n] = (uint8_t)it;
-      if (a.cost) a.cost[n] = live ? F : NaN;
-    }
-    if (lane < NP) {
-      a.x[n * NP + lane] = live ? S.x[lane] : NaN;
-      if (a.pinned) a.pinned[n * NP + lane] = (uint8_t)(live ? (fixmask >> lane) & 1u : 0);
-    }
-    if (a.pos && lane < PF_ROWS) a.pos[n * PF_ROWS + lane] = live ? S.F[cur].pos[lane / 3][lane % 3] : NaN;
-    if (a.cov_x)
-      for (int t = lane; t < NP * NP; t += 64) a.cov_x[n * NP * NP + t] = live ? S.A[t / NP][t % NP] : NaN;
-    if (a.cov_pos || a.std_pos) {
-      double* CP = &S.L[0][0];                     // [60][3]; the factor is not read again
-      if (live) {
-        pf_jacobian<true>(S, S.F[cur], emask, piv, lane);
-        if (lane < PF_ROWS) {
-          const int l = lane / 3;
-          double t[NP];
-#pragma unroll
-          for (int q = 0; q < NP; ++q) t[q] = 0.0;
-          for (int p = 0; p < NP; ++p) {
-            if (!((S.colmask[p] >> l) & 1u)) continue;
-            const double jp = S.Jw[p][lane];
-#pragma unroll
-            for (int q = 0; q < NP; ++q) t[q] += jp * S.A[p][q];
-          }
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < NP; ++q) acc += t[q] * S.Jw[q][3 * l + j];
-            CP[lane * 3 + j] = acc;
-          }
-        }
-        __syncthreads();
-      }
-      if (lane < PF_ROWS) {
-        const int l = lane / 3, i = lane - 3 * l;
-        if (a.cov_pos)
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            a.cov_pos[(n * NL + l) * 9 + i * 3 + j] = live ? 0.5 * (CP[lane * 3 + j] + CP[(3 * l + j) * 3 + i]) : NaN;
-        if (a.std_pos && i == 0)
-          a.std_pos[n * NL + l] = live ? sqrt((CP[(3 * l) * 3] + CP[(3 * l + 1) * 3 + 1]) + CP[(3 * l + 2) * 3 + 2]) : NaN;
-      }
-    }
+    CheetahFit m{S, piv, a.kappa, lane, emask};
+    pf_fit_frame<NP>(m, a, n, lane, n_enter);
   }
 }
 
@@ -511,23 +375,12 @@ int acino_cheetah_pose_fit(const acino_pose_fit_params* prm, const double* d_poi
                            uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x, double* d_pos, double* d_cov_pos,
                            double* d_std_pos, void* stream) {
   ACINO_REQUIRE(prm != nullptr, "prm");
-  ACINO_REQUIRE(n_frames >= 0, "n_frames");
-  ACINO_REQUIRE(prm->max_iter >= 1 && prm->max_iter <= 255, "max_iter must be 1..255 (the iteration count is one byte)");
-  ACINO_REQUIRE(prm->min_markers >= 1 && prm->min_markers <= ACINO_N_MARKERS, "min_markers must be 1..20");
-  ACINO_REQUIRE(prm->lam0 > 0 && prm->lam0 < INFINITY, "lam0 must be > 0");
-  ACINO_REQUIRE(prm->ftol > 0 && prm->ftol < INFINITY, "ftol must be > 0");
-  ACINO_REQUIRE(prm->xtol > 0 && prm->xtol < INFINITY, "xtol must be > 0");
-  ACINO_REQUIRE(prm->prior_sigma > 0 && prm->prior_sigma < INFINITY, "prior_sigma must be > 0");
-  ACINO_REQUIRE(prm->sigma_iso > 0 && prm->sigma_iso < INFINITY, "sigma_iso must be > 0");
+  if (int rc = pf_check_params(prm, n_frames, ACINO_N_MARKERS, "min_markers must be 1..20")) return rc;
   if (n_frames == 0) return ACINO_OK;
   ACINO_REQUIRE(d_points && d_x && d_status, "null buffer (d_points, d_x, d_status)");
   PoseFitArgs a;
-  a.points = d_points, a.cov = d_cov, a.x0 = d_x0, a.n_frames = n_frames, a.x = d_x, a.cost = d_cost;
-  a.nmarkers = d_nmarkers, a.status = d_status, a.iters = d_iters, a.pinned = d_pinned;
-  a.cov_x = d_cov_x, a.pos = d_pos, a.cov_pos = d_cov_pos, a.std_pos = d_std_pos;
-  a.max_iter = prm->max_iter, a.min_markers = prm->min_markers, a.lam0 = prm->lam0, a.ftol = prm->ftol, a.xtol = prm->xtol;
-  a.kappa = 1.0 / (prm->prior_sigma * prm->prior_sigma);
-  a.inv_sigma_iso = 1.0 / prm->sigma_iso;
+  pf_fill_io(a, prm, d_points, d_cov, d_x0, n_frames, d_x, d_cost, d_nmarkers, d_status, d_iters, d_pinned, d_cov_x, d_pos, d_cov_pos,
+             d_std_pos);
   const int grid = grid_for(n_frames, 1);       // one frame per workgroup pass, grid-stride beyond the cap
   hipLaunchKernelGGL(k_pose_fit, dim3(grid), dim3(64), 0, (hipStream_t)stream, a);
   ACINO_LAUNCH_CHECK();

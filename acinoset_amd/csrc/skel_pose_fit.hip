@@ -4,8 +4,9 @@
 // Per frame the minimiser, over the P = n_active states x inside the frame's box lo <= x <= hi, of
 //   F(x) = 1/2 sum_{l enters} (FK_l(x) - y_l)^T W_l (FK_l(x) - y_l) + 1/2 sum_{p >= 3} (x_p - m_p)^2 / prior_sigma^2
 // with FK the link program of SkelDev, W_l = S_l^-1 (or I / sigma_iso^2) and m the start clipped to the box, by the projected
-// Levenberg-Marquardt of pose_fit.hip, decision for decision: the active set, the damped step on the free states, Nielsen's
-// rule, the stops and the status codes are its statements with P for 25.
+// Levenberg-Marquardt that pose_fit.hip runs too: one definition, pf_fit_frame<PT> of pose_fit_dev.hpp (active set,
+// damped step on the free states, Nielsen's rule, the stops, the status codes, the stores and cov_pos), instantiated here with
+// the model SkelFit<PT>: FK and Jacobian of the link program, the Gram product, where the factor is stored, cov_x, the LDS.
 //
 // One 64-lane wave per frame, one wave per workgroup, a grid-stride loop over the frames, no atomics: every barrier is
 // wave-wide and nothing waits on another workgroup.  The kernel is a template on PT = 16, 32, 48, 64 (P rounded up to 16):
@@ -32,14 +33,9 @@
 namespace acino {
 
 struct SkelPoseFitArgs {
+  PoseFitIo io;
   const SkelDev* dev;
-  const double *points, *cov, *x0, *lo, *hi;
-  int64_t n_frames;
-  double *x, *cost;
-  uint8_t *nmarkers, *status, *iters, *pinned;
-  double *cov_x, *pos, *cov_pos, *std_pos;
-  int max_iter, min_markers;
-  double lam0, ftol, xtol, kappa, inv_sigma_iso;
+  const double *lo, *hi;
 };
 
 // offsets into the dynamic LDS, in units of 8 bytes
@@ -90,9 +86,6 @@ __device__ __forceinline__ int spf_here(int lane) {
   asm volatile("" : "+v"(lane));
   return lane;
 }
-
-// np.clip: a NaN stays a NaN
-__device__ __forceinline__ double spf_clip(double v, double lo, double hi) { return v != v ? v : fmin(fmax(v, lo), hi); }
 
 // M off, dM/dphi off, dM/dtheta off, dM/dpsi off of op k at the states xs: the statements of k_skel_assemble
 __device__ __forceinline__ void spf_link_op(const SkelDev& D, int k, const double* xs, double* out) {
@@ -284,77 +277,6 @@ __device__ __forceinline__ void spf_normal(const Spf& S, double kappa, unsigned 
   __syncthreads();
 }
 
-// the active set at S.x, one bit per state: at a bound with the gradient pushing outward
-__device__ __forceinline__ unsigned long long spf_active_set(const Spf& S, int lane) {
-  bool fixed = false;
-  if (lane < S.P) fixed = skel_fixed(S.x[lane], S.g[lane], S.M[lane * S.ldm + lane], S.lo[lane], S.hi[lane]);
-  return __ballot(fixed);
-}
-
-// Cholesky factor of A + lam diag(A) on the free states (identity rows for the pinned ones and for the rows P .. PT-1), row i
-// in the registers of lane i: r[j] = L[i][j] for j < i, dinv = 1 / L[i][i] (pf_factor's steps).  The strict lower triangle
-// goes to S.M above the diagonal, L[k][c] at M[c][k + 1], for the back substitution.  False on a pivot that is not above zero.
-template <int PT>
-__device__ __forceinline__ bool spf_factor(const Spf& S, unsigned long long fixmask, double lam, int lane, double (&r)[PT],
-                                           double& dinv) {
-  lane = spf_here(lane);
-  const int i = lane < PT ? lane : PT - 1;        // (the lanes beyond the matrix shadow its last row; nothing reads them)
-  const unsigned long long fix = fixmask | (S.P >= 64 ? 0ull : ~0ull << S.P);
-  const bool fi = (fix >> i) & 1ull;
-#pragma unroll
-  for (int j = 0; j < PT; ++j) {
-    double v = i == j ? 1.0 : 0.0;
-    if (!fi && !((fix >> j) & 1ull)) {
-      v = S.M[j <= i ? i * (PT + 1) + j : j * (PT + 1) + i];
-      if (i == j) v += lam * fmax(v, DIAG_FLOOR);
-    }
-    r[j] = v;
-  }
-  bool ok = true;
-  dinv = 0.0;
-#pragma unroll
-  for (int k = 0; k < PT; ++k) {
-    const double dk = pf_readlane(r[k], k);
-    ok = ok && dk > 0.0 && m_finite(dk);
-    double ik = __builtin_amdgcn_rsq(dk);         // 1 / sqrt(dk): the hardware estimate and two Newton steps
-#pragma unroll
-    for (int nr = 0; nr < 2; ++nr) ik = fma(0.5 * ik, fma(-dk * ik, ik, 1.0), ik);
-    const double lik = r[k] * ik;                 // L[i][k] in the lanes i > k
-    r[k] = lik;
-    if (lane == k) dinv = ik;
-#pragma unroll
-    for (int j = k + 1; j < PT; ++j) r[j] -= lik * pf_readlane(lik, j);
-  }
-  __syncthreads();                                // (the readers of the previous factor are done)
-  if (lane < S.P) {
-#pragma unroll
-    for (int c = 0; c < PT - 1; ++c)
-      if (c < lane) S.M[c * (PT + 1) + lane + 1] = r[c];
-  }
-  __syncthreads();
-  return ok;
-}
-
-// d = (L L^T)^-1 b, lane p holding entry p: forward substitution on the rows in registers, back substitution on the columns
-// of L^T in S.M, the finished entry passed on by v_readlane
-template <int PT>
-__device__ __forceinline__ double spf_solve(const Spf& S, const double (&r)[PT], double dinv, double v, int lane) {
-  lane = spf_here(lane);
-#pragma unroll
-  for (int k = 0; k < PT; ++k) {
-    const double zk = pf_readlane(v * dinv, k);
-    v = lane == k ? zk : (lane > k ? v - r[k] * zk : v);
-  }
-  const int col = lane < S.P ? lane : 0;
-#pragma unroll
-  for (int k = PT - 1; k >= 0; --k) {
-    const double xk = pf_readlane(v * dinv, k);
-    const double lkc = k < S.P && lane < k ? S.M[col * (PT + 1) + k + 1] : 0.0;      // (rows P .. PT-1 are the identity's)
-    v = lane == k ? xk : (lane < k ? v - lkc * xk : v);
-  }
-  return v;
-}
-
 // X = L^-1 in place of the factor: afterwards lane i holds X[i][c] = r[c] * dinv for c < i and X[i][i] = dinv.  Step k
 // broadcasts the finished row k and every later row takes its multiple; r[k] is read for the last time in step k and takes
 // the new column's entry, so the inverse needs no registers beyond the factor's.
@@ -373,12 +295,106 @@ __device__ __forceinline__ void spf_invert_factor(double (&r)[PT], double dinv, 
   }
 }
 
+// a link program as a model of pf_fit_frame (pose_fit_dev.hpp): the frame's box from the caller, one set of link operators and
+// poses (the trial's: the returned point's are evaluated again for the outputs), A and the factor in S.M
+template <int PT>
+struct SkelFit {
+  static constexpr int RED2 = SK_MAXP;
+  const Spf& S;
+  const SkelDev& D;
+  const double kappa;
+  const int lane;
+  const unsigned long long em0, em1;
+
+  __device__ __forceinline__ int n_states() const { return S.P; }
+  __device__ __forceinline__ int n_slots() const { return S.n_pose; }
+  __device__ __forceinline__ double* x() const { return S.x; }
+  __device__ __forceinline__ double* xt() const { return S.xt; }
+  __device__ __forceinline__ double* m() const { return S.m; }
+  __device__ __forceinline__ double* g() const { return S.g; }
+  __device__ __forceinline__ double* red() const { return S.red; }
+  __device__ __forceinline__ double* cp() const { return S.y; }             // (y, U, u are not read by then)
+
+  __device__ __forceinline__ double lo(int p) const { return S.lo[p]; }
+  __device__ __forceinline__ double hi(int p) const { return S.hi[p]; }
+
+  __device__ __forceinline__ double eval(const double* xv, bool) {
+    spf_frame(S, D, xv, lane);
+    return spf_cost(S, xv, kappa, lane);
+  }
+  __device__ __forceinline__ void linearise() {
+    spf_jacobian<false>(S, lane);
+    spf_normal<PT>(S, kappa, em0, em1, lane);
+  }
+  __device__ __forceinline__ void accepted() {}
+  __device__ __forceinline__ double diag(int p) const { return S.M[p * (PT + 1) + p]; }
+  // the active set at S.x, one bit per state: at a bound with the gradient pushing outward
+  __device__ __forceinline__ unsigned long long active_set(int lane) const {
+    bool fixed = false;
+    if (lane < S.P) fixed = skel_fixed(S.x[lane], S.g[lane], S.M[lane * S.ldm + lane], S.lo[lane], S.hi[lane]);
+    return __ballot(fixed);
+  }
+
+  // pf_factor_rows with identity rows P .. PT-1; the strict lower triangle goes to S.M above the diagonal, L[k][c] at
+  // M[c][k + 1], for the back substitution
+  __device__ __forceinline__ bool factor(unsigned long long fixmask, double lam, int lane, double (&r)[PT], double& dinv) {
+    lane = spf_here(lane);
+    const unsigned long long fix = fixmask | (S.P >= 64 ? 0ull : ~0ull << S.P);
+    const bool ok = pf_factor_rows<PT, PT + 1, true>(S.M, fix, lam, lane, r, dinv);
+    __syncthreads();                              // (the readers of the previous factor are done)
+    if (lane < S.P) {
+#pragma unroll
+      for (int c = 0; c < PT - 1; ++c)
+        if (c < lane) S.M[c * (PT + 1) + lane + 1] = r[c];
+    }
+    __syncthreads();
+    return ok;
+  }
+  // pf_solve, its back substitution on the columns of L^T in S.M
+  __device__ __forceinline__ double solve(const double (&r)[PT], double dinv, double v, int lane) const {
+    lane = spf_here(lane);
+    const int col = lane < S.P ? lane : 0;
+    return pf_solve<PT, true>(r, dinv, v, lane, S.P, [&](int k) { return S.M + col * (PT + 1) + k + 1; });      // (rows P .. PT-1 are the identity's)
+  }
+
+  // cov_x = X^T X with X = L^-1: the rows of X from the registers into S.Jw as columns (W[p][i] = X[i][p], zero above the
+  // diagonal and in the padding rows), the product on the matrix cores into S.M - neither A nor the factor is read again -,
+  // mirrored, so symmetric bit for bit, the rows and columns of pinned states exactly 0
+  __device__ __forceinline__ bool cov_x(unsigned long long fixmask, double (&r)[PT], double dinv, int lane) {
+    const int P = S.P;
+    spf_invert_factor<PT>(r, dinv, lane);
+    lane = spf_here(lane);
+    const int kpad = (P + 3) & ~3;
+    if (lane < kpad) {
+#pragma unroll
+      for (int p = 0; p < PT; ++p)
+        if (p < P) S.Jw[p * S.ldj + lane] = lane >= P || p > lane ? 0.0 : (p == lane ? dinv : r[p] * dinv);
+    }
+    __syncthreads();
+    bool fin = true;
+    spf_gram<PT>(S.Jw, S.ldj, kpad / 4, P, lane, [&](int row, int col, double v) {
+      if (((fixmask >> row) | (fixmask >> col)) & 1ull) v = 0.0;
+      fin = fin && m_finite(v);
+      S.M[row * (PT + 1) + col] = v;
+      S.M[col * (PT + 1) + row] = v;
+    });
+    return __all(fin);
+  }
+  __device__ __forceinline__ void outputs_at_x(bool live) {
+    if (live) spf_frame(S, D, S.x, lane);          // (S.opv and S.pos hold the last trial's, which may have been refused)
+  }
+  __device__ __forceinline__ double pos(int t) const { return S.pos[t]; }
+  __device__ __forceinline__ double cov(int p, int q) const { return S.M[p * (PT + 1) + q]; }
+  __device__ __forceinline__ void jacobian_raw(int lane) { spf_jacobian<true>(S, lane); }
+  __device__ __forceinline__ double jw(int p, int row) const { return S.Jw[p * S.ldj + row]; }
+  __device__ __forceinline__ bool moves(int p, int l) const { return (S.cm[2 * p + (l >> 6)] >> (l & 63)) & 1ull; }
+};
+
 template <int PT>
 __global__ void __launch_bounds__(64) k_skel_pose_fit(SkelPoseFitArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const SkelDev& D = *a.dev;
   const int lane = threadIdx.x;
-  const double NaN = __builtin_nan("");
   const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, R3 = 3 * NPOSE;
   const SpfLayout lay = spf_layout(P, PT, NPOSE, NOPS);
   double* base = reinterpret_cast<double*>(smem_raw);
@@ -393,7 +409,6 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit(SkelPoseFitArgs a) {
   S.axs = reinterpret_cast<int*>(base + lay.axs);
   S.ent = reinterpret_cast<int*>(base + lay.ent);
   S.P = P, S.n_pose = NPOSE, S.n_ops = NOPS, S.ldj = lay.ldj, S.ldm = lay.ldm, S.ks = (R3 + 3) / 4;
-  double* CP = S.y;                                // [3 n_pose][3] of the outputs (y, U, u are not read by then)
 
   // ---- once per workgroup: the op and slot masks of every state, the rest pose
   for (int l = lane; l < NPOSE; l += 64) S.pm[l] = D.pmask[l];
@@ -421,11 +436,12 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit(SkelPoseFitArgs a) {
   spf_frame(S, D, S.x, lane);
   for (int t = lane; t < R3; t += 64) S.rest[t] = S.pos[t];
 
-  for (int64_t n = blockIdx.x; n < a.n_frames; n += gridDim.x) {
+  for (int64_t n = blockIdx.x; n < a.io.n_frames; n += gridDim.x) {
+    const PoseFitIo& io = a.io;
     __syncthreads();                              // the previous frame is done with S (and the tables are complete)
     for (int e = lane; e < P * (4 * S.ks - R3); e += 64)      // the padding rows of Jw (cov_x's product has used them)
       S.Jw[(e / (4 * S.ks - R3)) * S.ldj + R3 + e % (4 * S.ks - R3)] = 0.0;
-    // ---- the slots that enter, their whitening factors
+    // ---- the slots that enter, their whitening factors (k_pose_fit holds the twin of this prologue)
     unsigned long long em0 = 0, em1 = 0;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -433,7 +449,7 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit(SkelPoseFitArgs a) {
       bool enter = false;
       if (l < NPOSE) {
         double y[3], U[6];
-        enter = pf_whiten(a.points + (n * NPOSE + l) * 3, a.cov ? a.cov + (n * NPOSE + l) * 9 : nullptr, a.inv_sigma_iso, y, U);
+        enter = pf_whiten(io.points + (n * NPOSE + l) * 3, io.cov ? io.cov + (n * NPOSE + l) * 9 : nullptr, io.inv_sigma_iso, y, U);
 #pragma unroll
         for (int k = 0; k < 3; ++k) S.y[3 * l + k] = enter ? y[k] : 0.0;
 #pragma unroll
@@ -449,169 +465,23 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit(SkelPoseFitArgs a) {
     if (lane < P) {
       const double lo = a.lo[n * P + lane], hi = a.hi[n * P + lane];
       double v = 0.0;
-      if (a.x0) {
-        v = a.x0[n * P + lane];
+      if (io.x0) {
+        v = io.x0[n * P + lane];
       } else if (lane < 3 && n_enter > 0) {
         double sum = 0.0;
         for (int l = 0; l < NPOSE; ++l)
           if (S.ent[l]) sum += S.y[3 * l + lane] - S.rest[3 * l + lane];
         v = sum / (double)n_enter;
       }
-      v = spf_clip(v, lo, hi);
+      v = pf_clip(v, lo, hi);
       S.lo[lane] = lo;
       S.hi[lane] = hi;
       S.m[lane] = v;
       S.x[lane] = v;
     }
     __syncthreads();
-
-    int st = PF_MAX_ITER, it = 0;
-    double F = NaN;
-    if (n_enter < a.min_markers) {
-      st = PF_FEW_MARKERS;
-    } else {
-      spf_frame(S, D, S.x, lane);
-      F = spf_cost(S, S.x, a.kappa, lane);
-      spf_jacobian<false>(S, lane);
-      spf_normal<PT>(S, a.kappa, em0, em1, lane);
-      double lam = a.lam0, nu = 2.0;
-      if (!m_finite(F)) st = PF_NUMERIC;
-#pragma unroll 1
-      while (st == PF_MAX_ITER && it < a.max_iter) {
-        ++it;
-        const unsigned long long fixmask = spf_active_set(S, lane);
-        double r[PT], dinv;
-        if (!spf_factor<PT>(S, fixmask, lam, lane, r, dinv)) {
-          st = PF_NUMERIC;
-          break;
-        }
-        const bool free_p = lane < P && !((fixmask >> lane) & 1ull);
-        const double pg = free_p ? S.g[lane] : 0.0;
-        const double d = spf_solve<PT>(S, r, dinv, -pg, lane);
-        if (lane < P) {
-          const double xo = S.x[lane], xn = spf_clip(xo + d, S.lo[lane], S.hi[lane]);
-          S.xt[lane] = xn;
-          S.red[lane] = d * (lam * fmax(S.M[lane * (PT + 1) + lane], DIAG_FLOOR) * d - pg);
-          S.red[SK_MAXP + lane] = fabs(xn - xo);
-        }
-        __syncthreads();
-        double pred = 0.0, step = 0.0;
-        for (int k = 0; k < P; ++k) {
-          pred += S.red[k];
-          step = fmax(step, S.red[SK_MAXP + k]);
-        }
-        pred *= 0.5;
-        __syncthreads();
-        spf_frame(S, D, S.xt, lane);
-        const double Ft = spf_cost(S, S.xt, a.kappa, lane);
-        if (Ft < F) {
-          const double dF = F - Ft, gain = pred > 0.0 ? dF / pred : -1.0;
-          F = Ft;
-          if (lane < P) S.x[lane] = S.xt[lane];
-          __syncthreads();
-          spf_jacobian<false>(S, lane);
-          spf_normal<PT>(S, a.kappa, em0, em1, lane);
-          const double t = 2.0 * gain - 1.0;
-          lam *= fmax(1.0 / 3.0, 1.0 - t * t * t);
-          nu = 2.0;
-          if (dF <= a.ftol * fabs(F) || step <= a.xtol) st = PF_CONVERGED;
-        } else {
-          lam *= nu;
-          nu *= 2.0;
-          if (lam > 1e16) break;
-        }
-      }
-    }
-
-    // ---- the outputs at the returned x: the active set, A_free^-1, positions and G cov_x G^T
-    const bool want_cov = a.cov_x || a.cov_pos || a.std_pos;
-    bool live = st == PF_CONVERGED || st == PF_MAX_ITER;
-    unsigned long long fixmask = 0;
-    if (live) {
-      fixmask = spf_active_set(S, lane);
-      double r[PT], dinv;
-      bool ok = spf_factor<PT>(S, fixmask, 0.0, lane, r, dinv) && m_finite(F);
-      if (lane < P) ok = ok && m_finite(S.x[lane]);
-      ok = __all(ok);
-      if (ok && want_cov) {
-        // cov_x = X^T X with X = L^-1: the rows of X from the registers into S.Jw as columns (W[p][i] = X[i][p], zero
-        // above the diagonal and in the padding rows), the product on the matrix cores into S.M - neither A nor the factor
-        // is read again -, mirrored, so symmetric bit for bit, the rows and columns of pinned states exactly 0
-        spf_invert_factor<PT>(r, dinv, lane);
-        const int kpad = (P + 3) & ~3;
-        if (lane < kpad) {
-#pragma unroll
-          for (int p = 0; p < PT; ++p)
-            if (p < P) S.Jw[p * S.ldj + lane] = lane >= P || p > lane ? 0.0 : (p == lane ? dinv : r[p] * dinv);
-        }
-        __syncthreads();
-        bool fin = true;
-        spf_gram<PT>(S.Jw, S.ldj, kpad / 4, P, lane, [&](int row, int col, double v) {
-          if (((fixmask >> row) | (fixmask >> col)) & 1ull) v = 0.0;
-          fin = fin && m_finite(v);
-          S.M[row * (PT + 1) + col] = v;
-          S.M[col * (PT + 1) + row] = v;
-        });
-        ok = __all(fin);
-      }
-      if (!ok) {
-        st = PF_NUMERIC;
-        live = false;
-      }
-      __syncthreads();
-    }
-    if (live) spf_frame(S, D, S.x, lane);          // (S.opv and S.pos hold the last trial's, which may have been refused)
-
-    if (lane == 0) {
-      a.status[n] = (uint8_t)st;
-      if (a.nmarkers) a.nmarkers[n] = (uint8_t)n_enter;
-      if (a.iters) a.iters[n] = (uint8_t)it;
-      if (a.cost) a.cost[n] = live ? F : NaN;
-    }
-    if (lane < P) {
-      a.x[n * P + lane] = live ? S.x[lane] : NaN;
-      if (a.pinned) a.pinned[n * P + lane] = (uint8_t)(live ? (fixmask >> lane) & 1ull : 0);
-    }
-    if (a.pos)
-      for (int t = lane; t < R3; t += 64) a.pos[n * R3 + t] = live ? S.pos[t] : NaN;
-    if (a.cov_x)
-      for (int t = lane; t < P * P; t += 64) a.cov_x[n * P * P + t] = live ? S.M[(t / P) * (PT + 1) + t % P] : NaN;
-    if (a.cov_pos || a.std_pos) {
-      if (live) {
-        spf_jacobian<true>(S, lane);
-        for (int rw = lane; rw < R3; rw += 64) {
-          const int l = rw / 3;
-          double t[PT];
-#pragma unroll
-          for (int q = 0; q < PT; ++q) t[q] = 0.0;
-          for (int p = 0; p < P; ++p) {
-            if (!((S.cm[2 * p + (l >> 6)] >> (l & 63)) & 1ull)) continue;
-            const double jp = S.Jw[p * S.ldj + rw];
-#pragma unroll
-            for (int q = 0; q < PT; ++q)
-              if (q < P) t[q] += jp * S.M[p * (PT + 1) + q];
-          }
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < PT; ++q)
-              if (q < P) acc += t[q] * S.Jw[q * S.ldj + 3 * l + j];
-            CP[rw * 3 + j] = acc;
-          }
-        }
-        __syncthreads();
-      }
-      for (int rw = lane; rw < R3; rw += 64) {
-        const int l = rw / 3, i = rw - 3 * l;
-        if (a.cov_pos)
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            a.cov_pos[(n * NPOSE + l) * 9 + i * 3 + j] = live ? 0.5 * (CP[rw * 3 + j] + CP[(3 * l + j) * 3 + i]) : NaN;
-        if (a.std_pos && i == 0)
-          a.std_pos[n * NPOSE + l] = live ? sqrt((CP[(3 * l) * 3] + CP[(3 * l + 1) * 3 + 1]) + CP[(3 * l + 2) * 3 + 2]) : NaN;
-      }
-    }
+    SkelFit<PT> m{S, D, io.kappa, lane, em0, em1};
+    pf_fit_frame<PT>(m, io, n, lane, n_enter);
   }
 }
 
@@ -652,14 +522,7 @@ int acino_skel_pose_fit(const acino_pose_fit_params* prm, const acino_skel_fte_p
   const acino_skel_fte_params q = spf_params(p);
   int rc = skel_validate(&q);
   if (rc) return rc;
-  ACINO_REQUIRE(n_frames >= 0, "n_frames");
-  ACINO_REQUIRE(prm->max_iter >= 1 && prm->max_iter <= 255, "max_iter must be 1..255 (the iteration count is one byte)");
-  ACINO_REQUIRE(prm->min_markers >= 1 && prm->min_markers <= p->n_pose, "min_markers must be 1..n_pose");
-  ACINO_REQUIRE(prm->lam0 > 0 && prm->lam0 < INFINITY, "lam0 must be > 0");
-  ACINO_REQUIRE(prm->ftol > 0 && prm->ftol < INFINITY, "ftol must be > 0");
-  ACINO_REQUIRE(prm->xtol > 0 && prm->xtol < INFINITY, "xtol must be > 0");
-  ACINO_REQUIRE(prm->prior_sigma > 0 && prm->prior_sigma < INFINITY, "prior_sigma must be > 0");
-  ACINO_REQUIRE(prm->sigma_iso > 0 && prm->sigma_iso < INFINITY, "sigma_iso must be > 0");
+  if ((rc = pf_check_params(prm, n_frames, p->n_pose, "min_markers must be 1..n_pose"))) return rc;
   ACINO_REQUIRE(h_ops && h_active, "null buffer (h_ops, h_active)");
   SkelDev h;
   if ((rc = skel_program(&q, h_ops, h_active, h))) return rc;
@@ -676,13 +539,9 @@ int acino_skel_pose_fit(const acino_pose_fit_params* prm, const acino_skel_fte_p
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(reinterpret_cast<char*>(d_ws) + spf_ws_clip());
   if ((rc = skel_upload(h, nullptr, 0, d_dev, d_clip, 1, s))) return rc;      // (no camera: only the link program is read)
   SkelPoseFitArgs a;
-  a.dev = d_dev;
-  a.points = d_points, a.cov = d_cov, a.x0 = d_x0, a.lo = d_lo, a.hi = d_hi, a.n_frames = n_frames, a.x = d_x, a.cost = d_cost;
-  a.nmarkers = d_nmarkers, a.status = d_status, a.iters = d_iters, a.pinned = d_pinned;
-  a.cov_x = d_cov_x, a.pos = d_pos, a.cov_pos = d_cov_pos, a.std_pos = d_std_pos;
-  a.max_iter = prm->max_iter, a.min_markers = prm->min_markers, a.lam0 = prm->lam0, a.ftol = prm->ftol, a.xtol = prm->xtol;
-  a.kappa = 1.0 / (prm->prior_sigma * prm->prior_sigma);
-  a.inv_sigma_iso = 1.0 / prm->sigma_iso;
+  a.dev = d_dev, a.lo = d_lo, a.hi = d_hi;
+  pf_fill_io(a.io, prm, d_points, d_cov, d_x0, n_frames, d_x, d_cost, d_nmarkers, d_status, d_iters, d_pinned, d_cov_x, d_pos,
+             d_cov_pos, d_std_pos);
   const int grid = grid_for(n_frames, 1);       // one frame per workgroup pass, grid-stride beyond the cap
   return skel_dispatch_pt(h.PT, [&](auto pt) -> int {
     constexpr int T = decltype(pt)::value;

@@ -656,41 +656,61 @@ def pose_fit(points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01, min_m
       J cov_x J^T and std_positions [N,20] in metres.
 
     numpy in, numpy out; CUDA tensors in, CUDA tensors out with no host copy."""
+    return _pose_fit(lambda prm, dev, N, ins, outs: check(lib().acino_cheetah_pose_fit(prm, *ins, N, *outs, stream_ptr())),
+                     points, cov, x0, None, N_MARKERS, ACTIVE, N_STATES,
+                     ("points must be [N, 20, 3]", "cov must be [N, 20, 3, 3]", "x0 must be [N, 25] (the active states)"),
+                     prior_sigma, sigma_iso, min_markers, max_iter, ftol, xtol, lam0, return_cov)
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def _pose_fit(launch, points, cov, x0, N, n_slots, active, n_full, texts, prior_sigma, sigma_iso, min_markers, max_iter, ftol,
+              xtol, lam0, return_cov):
+    """What ``pose_fit`` and ``build.pose_fit`` share: the dict in place of ``points``, the checks of the shapes - points
+    [N, n_slots, 3], cov [N, n_slots, 3, 3], x0 [N, len(active)], with ``texts`` the caller's three messages; N None: the
+    frames of ``points`` - and of the parameters, the staging, the outputs, ``PoseFitParams``, the scatter of x into
+    x_full [N, n_full] at the columns ``active``, the dict, and numpy out for numpy in.  ``launch(prm, dev, N, ins, outs)``
+    makes the library call: ``ins`` the pointers of points, cov, x0 and ``outs`` those of the ten outputs, both in the order
+    of the C entries."""
     if isinstance(points, dict):
         if cov is not None:
             raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
         points, cov = points["points"], points["cov"]
-    shape = tuple(points.shape) if hasattr(points, "shape") else np.shape(points)
-    if len(shape) != 3 or shape[1:] != (N_MARKERS, 3):
-        raise ValueError("points must be [N, 20, 3]")
-    N = shape[0]
-    if cov is not None and (tuple(cov.shape) if hasattr(cov, "shape") else np.shape(cov)) != (N, N_MARKERS, 3, 3):
-        raise ValueError("cov must be [N, 20, 3, 3]")
-    if x0 is not None and (tuple(x0.shape) if hasattr(x0, "shape") else np.shape(x0)) != (N, N_ACTIVE):
-        raise ValueError("x0 must be [N, 25] (the active states)")
+    L, P = n_slots, len(active)
+    shape = _shape(points)
+    if N is None and len(shape) == 3:
+        N = shape[0]
+    if shape != (N, L, 3):
+        raise ValueError(texts[0])
+    if cov is not None and _shape(cov) != (N, L, 3, 3):
+        raise ValueError(texts[1])
+    if x0 is not None and _shape(x0) != (N, P):
+        raise ValueError(texts[2])
     for name, val in (("prior_sigma", prior_sigma), ("sigma_iso", sigma_iso), ("ftol", ftol), ("xtol", xtol), ("lam0", lam0)):
         if not (np.isfinite(val) and val > 0):
             raise ValueError(f"{name} must be finite and > 0")
     if int(max_iter) != max_iter or not 1 <= max_iter <= 255:
         raise ValueError("max_iter must be an integer in 1..255")
-    if int(min_markers) != min_markers or not 1 <= min_markers <= N_MARKERS:
-        raise ValueError("min_markers must be an integer in 1..20")
+    if int(min_markers) != min_markers or not 1 <= min_markers <= L:
+        raise ValueError(f"min_markers must be an integer in 1..{L}")
     dev = calib._dev()
     pts = calib._to_dev(points, dev)
     cv = None if cov is None else calib._to_dev(cov, dev)
     xs = None if x0 is None else calib._to_dev(x0, dev)
     f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
-    x, cost, pos = torch.empty((N, N_ACTIVE), **f64), torch.empty((N,), **f64), torch.empty((N, N_MARKERS, 3), **f64)
-    nm, status, iters, pinned = (torch.empty(sh, **u8) for sh in ((N,), (N,), (N,), (N, N_ACTIVE)))
-    cov_x = torch.empty((N, N_ACTIVE, N_ACTIVE), **f64) if return_cov else None
-    cov_pos = torch.empty((N, N_MARKERS, 3, 3), **f64) if return_cov else None
-    std_pos = torch.empty((N, N_MARKERS), **f64) if return_cov else None
+    x, cost, pos = torch.empty((N, P), **f64), torch.empty((N,), **f64), torch.empty((N, L, 3), **f64)
+    nm, status, iters, pinned = (torch.empty(sh, **u8) for sh in ((N,), (N,), (N,), (N, P)))
+    cov_x = torch.empty((N, P, P), **f64) if return_cov else None
+    cov_pos = torch.empty((N, L, 3, 3), **f64) if return_cov else None
+    std_pos = torch.empty((N, L), **f64) if return_cov else None
     prm = _lib.PoseFitParams(int(max_iter), int(min_markers), float(lam0), float(ftol), float(xtol), float(prior_sigma),
                              float(sigma_iso))
-    check(lib().acino_cheetah_pose_fit(prm, ptr(pts), ptr(cv), ptr(xs), N, ptr(x), ptr(cost), ptr(nm), ptr(status), ptr(iters),
-                                       ptr(pinned), ptr(cov_x), ptr(pos), ptr(cov_pos), ptr(std_pos), stream_ptr()))
-    x_full = torch.zeros((N, N_STATES), **f64)
-    x_full[:, torch.as_tensor(ACTIVE, device=dev)] = x
+    launch(prm, dev, N, [ptr(t) for t in (pts, cv, xs)],
+           [ptr(t) for t in (x, cost, nm, status, iters, pinned, cov_x, pos, cov_pos, std_pos)])
+    x_full = torch.zeros((N, n_full), **f64)
+    x_full[:, torch.as_tensor(np.asarray(active, dtype=np.int64), device=dev)] = x
     out = dict(x=x, x_full=x_full, positions=pos, cost=cost, n_markers=nm, status=status, iters=iters, pinned=pinned)
     if return_cov:
         out.update(cov_x=cov_x, cov_positions=cov_pos, std_positions=std_pos)
