@@ -12,9 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libacinoset_hip.so")
 BUILD_ID_SOURCE = "camera_kernels.hip"      # defines acino_build_id()
-SOURCES = ["camera_kernels.hip", "triangulate_mv.hip", "pose_fit.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_calib.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "ekf_cov.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_calib.hip", "skel_reproj.hip", "skel_pose_fit.hip"]
+SOURCES = ["camera_kernels.hip", "triangulate_mv.hip", "pose_fit.hip", "pose_fit_px.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_calib.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "ekf_cov.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_calib.hip", "skel_reproj.hip", "skel_pose_fit.hip"]
 HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "fte_cov.hpp", "fte_cov_dev.hpp", "fte_calib.hpp", "fte_reproj.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
-           "pinhole.hpp", "ldl3.hpp", "pose_fit_dev.hpp", "ekf_dev.hpp", "sba_dev.hpp", "sba_host.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "skel_assemble.hpp",
+           "pinhole.hpp", "ldl3.hpp", "pose_fit_dev.hpp", "pose_fit_cheetah.hpp", "ekf_dev.hpp", "sba_dev.hpp", "sba_host.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "skel_assemble.hpp",
            os.path.join("..", "..", "include", "acinoset_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DNDEBUG"]      # scripts/isa_diff.py compiles with the same
@@ -123,6 +123,12 @@ class PoseFitParams(C.Structure):
                 ("xtol", C.c_double), ("prior_sigma", C.c_double), ("sigma_iso", C.c_double)]
 
 
+class PoseFitPxParams(C.Structure):
+    _fields_ = [("camera_model", C.c_int32), ("max_iter", C.c_int32), ("min_detections", C.c_int32), ("reserved", C.c_int32),
+                ("lam0", C.c_double), ("ftol", C.c_double), ("xtol", C.c_double), ("prior_sigma", C.c_double),
+                ("thresh", C.c_double), ("f_scale", C.c_double), ("sigma_px", C.c_double)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -153,6 +159,8 @@ SIGNATURES = {
     "acino_triangulate_multiview": (_I, [C.POINTER(TriMvParams), _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "acino_sizeof_pose_fit_params": (_Z, []),
     "acino_cheetah_pose_fit": (_I, [C.POINTER(PoseFitParams), _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "acino_sizeof_pose_fit_px_params": (_Z, []),
+    "acino_cheetah_pose_fit_px": (_I, [C.POINTER(PoseFitPxParams), _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "acino_cheetah_fk": (_I, [_P, _L, _P, _P]),
     "acino_fk_active": (_I, [_P, _L, _P, _P]),
     "acino_sizeof_fte_params": (_Z, []),
@@ -395,6 +403,8 @@ def lib():
         raise RuntimeError("libacinoset_hip.so multi-view triangulation struct layout differs from the Python binding (stale build?)")
     if handle.acino_sizeof_pose_fit_params() != C.sizeof(PoseFitParams):
         raise RuntimeError("libacinoset_hip.so pose-fit struct layout differs from the Python binding (stale build?)")
+    if handle.acino_sizeof_pose_fit_px_params() != C.sizeof(PoseFitPxParams):
+        raise RuntimeError("libacinoset_hip.so pixel pose-fit struct layout differs from the Python binding (stale build?)")
     if handle.acino_sizeof_ekf_params() != C.sizeof(EkfParams):
         raise RuntimeError("libacinoset_hip.so EKF struct layout differs from the Python binding (stale build?)")
     _lib = handle

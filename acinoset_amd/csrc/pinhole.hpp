@@ -88,4 +88,40 @@ __device__ __forceinline__ void project_jac(const Pin& c, double xc, double yc, 
   pinhole_project<true>(c, xc, yc, zc, uv, J);
 }
 
+// calibration-level projection of a camera-frame point and d(uv)/d(Xc).  Fisheye: project_points_fisheye - the r > 1e-8
+// branch and the record's skew, u = fx (xd + alpha yd) + cx -, the algebra of fisheye_cam<true> (sba_dev.hpp) plus the skew.
+__device__ __forceinline__ void mv_project(const Cam& c, double xc, double yc, double zc, double uv[2], double J[2][3]) {
+  const double iz = rcp64(zc);
+  const double a = xc * iz, b = yc * iz;
+  const double r2 = a * a + b * b;
+  const double r = sqrt(r2);
+  const double th = atan(r), th2 = th * th;
+  const double thd = th * (1 + th2 * (c.k1 + th2 * (c.k2 + th2 * (c.k3 + th2 * c.k4))));
+  const bool small = !(r > 1e-8);
+  const double ir = small ? 0.0 : rcp64(r);
+  const double m = small ? 1.0 : thd * ir;
+  const double xd = a * m, yd = b * m;
+  uv[0] = c.fx * (xd + c.alpha * yd) + c.cx;
+  uv[1] = c.fy * yd + c.cy;
+  double dm_da = 0.0, dm_db = 0.0;
+  if (!small) {
+    const double dthd = 1 + th2 * (3 * c.k1 + th2 * (5 * c.k2 + th2 * (7 * c.k3 + th2 * 9 * c.k4)));
+    const double dm_dr = (dthd * rcp64(1 + r2) * r - thd) * (ir * ir);
+    dm_da = dm_dr * a * ir;
+    dm_db = dm_dr * b * ir;
+  }
+  const double dxd_da = m + a * dm_da, dxd_db = a * dm_db, dyd_da = b * dm_da, dyd_db = m + b * dm_db;
+  const double du_da = c.fx * (dxd_da + c.alpha * dyd_da), du_db = c.fx * (dxd_db + c.alpha * dyd_db);
+  const double dv_da = c.fy * dyd_da, dv_db = c.fy * dyd_db;
+  J[0][0] = du_da * iz;
+  J[0][1] = du_db * iz;
+  J[0][2] = -(du_da * a + du_db * b) * iz;
+  J[1][0] = dv_da * iz;
+  J[1][1] = dv_db * iz;
+  J[1][2] = -(dv_da * a + dv_db * b) * iz;
+}
+__device__ __forceinline__ void mv_project(const Pin& c, double xc, double yc, double zc, double uv[2], double J[2][3]) {
+  pinhole_project<true>(c, xc, yc, zc, uv, J);
+}
+
 }  // namespace acino

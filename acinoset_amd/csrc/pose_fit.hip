@@ -20,27 +20,11 @@
 // lanes by v_readlane (no LDS traffic inside its 25 steps: the LDS form, a read-modify-write per entry, made the kernel twice
 // as long); the inverse for cov_x is 25 right-hand sides, one per lane, on the same registers.  The frame after its prologue -
 // controller, factor steps, substitutions, epilogue - is pf_fit_frame<25> of pose_fit_dev.hpp, which skel_pose_fit.hip
-// instantiates too; this file is its model CheetahFit: FK frames, Jacobian, the three-tile Gram product, cov_x, the LDS.
-#include "fte_cov_dev.hpp"
-#include "pose_fit_dev.hpp"
+// instantiates too; this file is its model CheetahFit: the whitened residuals, Jw = U J and the three-tile Gram product on top of
+// CheetahCore (pose_fit_cheetah.hpp: FK frames, marker Jacobian, factor, cov_x), which pose_fit_px.hip's model shares.
+#include "pose_fit_cheetah.hpp"
 
 namespace acino {
-
-constexpr int PF_ROWS = 3 * NL;      // 60 rows of J
-constexpr int PF_LD = NP + 1;        // leading dimension of A and of its factor
-constexpr int PF_PAIRS = NP * (NP + 1) / 2;
-
-// the box of the 25 active states (all_optimizations.py:403-483; acinoset_amd.fte.bounds45()[ACTIVE])
-#define PF_INF __builtin_huge_val()
-static __device__ const double c_pf_lo[NP] = {
-    -PF_INF,      -PF_INF,      -PF_INF,      -M_PI / 6,    -M_PI / 6,    -M_PI / 6,   -M_PI / 6, -M_PI / 6, -M_PI / 6,
-    -M_PI / 6,    -M_PI / 1.5,  -M_PI / 1.5,  -M_PI / 2,    -M_PI,        -M_PI / 2,   -M_PI,     -M_PI / 2, 0.0,
-    -M_PI / 2,    0.0,          -PF_INF,      -M_PI / 6,    -M_PI / 6,    -M_PI / 1.5, -M_PI / 1.5};
-static __device__ const double c_pf_hi[NP] = {
-    PF_INF,       PF_INF,       PF_INF,       M_PI / 6,     M_PI / 6,     M_PI / 6,    M_PI / 6,  M_PI / 6,  M_PI / 6,
-    M_PI / 6,     M_PI / 1.5,   M_PI / 1.5,   M_PI / 2,     0.0,          M_PI / 2,    0.0,       M_PI / 2,  M_PI,
-    M_PI / 2,     M_PI,         PF_INF,       M_PI / 6,     M_PI / 6,     M_PI / 1.5,  M_PI / 1.5};
-#undef PF_INF
 
 using PoseFitArgs = PoseFitIo;
 
@@ -56,23 +40,6 @@ struct PoseFitLds {
   double red[64];
   unsigned colmask[NP];        // the markers that move with state p
 };
-
-// sin / cos and the head position of ``xv``, then the three columns of the chain
-__device__ __forceinline__ void pf_frame(CovFrame& F, const double* xv, int lane) {
-  if (lane < NP) {
-    if (lane < 3) {
-      F.pos[20][lane] = xv[lane];
-    } else {
-      double s, c;
-      sincos(xv[lane], &s, &c);
-      F.sc[lane - 3][0] = s;
-      F.sc[lane - 3][1] = c;
-    }
-  }
-  __syncthreads();
-  if (lane < 3) fk_columns(F, lane);
-  __syncthreads();
-}
 
 // F(xv) of the frame F holds: the whitened residuals into S.u, the sum in a fixed order (the same value in every lane)
 __device__ __forceinline__ double pf_cost(PoseFitLds& S, const CovFrame& F, const double* xv, double kappa, int lane) {
@@ -99,46 +66,6 @@ __device__ __forceinline__ double pf_cost(PoseFitLds& S, const CovFrame& F, cons
   return f;
 }
 
-constexpr int PF_TASKS = (NP * NL + 63) / 64;      // (state, marker) entries of J per lane: entry t = lane + 64 k
-
-// what lane ``lane`` needs for its entries of J, once per launch: the pivot of (p, l) = (t / 20, t % 20) - rate_pivot -, -1
-// where the marker does not hang on the angle, -2 for a column of the head position (the identity)
-__device__ __forceinline__ void pf_tasks(int lane, int (&piv)[PF_TASKS]) {
-#pragma unroll
-  for (int k = 0; k < PF_TASKS; ++k) {
-    const int t = lane + 64 * k, p = t / NL, l = t - p * NL;
-    piv[k] = t >= NP * NL ? -1 : (p < 3 ? -2 : rate_pivot(l, p));
-  }
-}
-
-// Jw = U J (RAW: J, every marker) of the frame F, zero outside the markers of a column
-template <bool RAW>
-__device__ __forceinline__ void pf_jacobian(PoseFitLds& S, const CovFrame& F, unsigned emask, const int (&piv)[PF_TASKS],
-                                            int lane) {
-#pragma unroll
-  for (int k = 0; k < PF_TASKS; ++k) {
-    const int t = lane + 64 * k, p = t / NL, l = t - p * NL;
-    if (t >= NP * NL) break;
-    double w0 = 0.0, w1 = 0.0, w2 = 0.0;
-    if (piv[k] != -1 && (RAW || ((emask >> l) & 1u))) {
-      double j[3] = {p == 0 ? 1.0 : 0.0, p == 1 ? 1.0 : 0.0, p == 2 ? 1.0 : 0.0};
-      if (piv[k] >= 0) rate_cross(F, l, p, piv[k], j);
-      if (RAW) {
-        w0 = j[0], w1 = j[1], w2 = j[2];
-      } else {
-        const double* U = S.U[l];
-        w0 = U[0] * j[0];
-        w1 = U[1] * j[0] + U[2] * j[1];
-        w2 = U[3] * j[0] + U[4] * j[1] + U[5] * j[2];
-      }
-    }
-    S.Jw[p][3 * l] = w0;
-    S.Jw[p][3 * l + 1] = w1;
-    S.Jw[p][3 * l + 2] = w2;
-  }
-  __syncthreads();
-}
-
 // A = Jw^T Jw + diag(kappa) on the fp64 matrix cores - the three lower 16 x 16 tiles of the 25 x 25 padded to 32, 15 k-steps
 // of four rows each, through the wrapper of dense80.hpp: lane (i, k) = (lane & 15, lane >> 4) feeds Jw[i][4 s + k] and
 // Jw[16 + i][4 s + k] and holds result[4 r + k][i] in register r.  A column of zeros (a state no entering marker moves)
@@ -161,24 +88,7 @@ __device__ __forceinline__ void pf_normal(PoseFitLds& S, unsigned emask, double 
     a10 = mfma(hi[s], lo[s], a10);
     a11 = mfma(hi[s], hi[s], a11);
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int m = 4 * r + k;
-    if (m >= i) {                                 // the lower triangle of the diagonal tiles, mirrored
-      const double v = a00[r] + (m == i && m >= 3 ? kappa : 0.0);
-      S.A[m][i] = v;
-      S.A[i][m] = v;
-      if (16 + m < NP) {
-        const double w = a11[r] + (m == i ? kappa : 0.0);
-        S.A[16 + m][16 + i] = w;
-        S.A[16 + i][16 + m] = w;
-      }
-    }
-    if (16 + m < NP) {
-      S.A[16 + m][i] = a10[r];
-      S.A[i][16 + m] = a10[r];
-    }
-  }
+  pf_store_tiles(S, a00, a10, a11, kappa, lane);
   if (lane < NP) {
     unsigned mk = S.colmask[lane] & emask;
     double acc = 0.0;
@@ -194,46 +104,14 @@ __device__ __forceinline__ void pf_normal(PoseFitLds& S, unsigned emask, double 
   __syncthreads();
 }
 
-// column ``lane`` of (L L^T)^-1 into z, every lane a right-hand side of its own: the entries of L come by v_readlane
-__device__ __forceinline__ void pf_inverse_column(const double (&r)[NP], double dinv, int lane, double (&z)[NP]) {
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    double acc = i == lane ? 1.0 : 0.0;
-#pragma unroll
-    for (int k = 0; k < i; ++k) acc -= pf_readlane(r[k], i) * z[k];
-    z[i] = acc * pf_readlane(dinv, i);
-  }
-#pragma unroll
-  for (int i = NP - 1; i >= 0; --i) {
-    double acc = z[i];
-#pragma unroll
-    for (int k = i + 1; k < NP; ++k) acc -= pf_readlane(r[i], k) * z[k];
-    z[i] = acc * pf_readlane(dinv, i);
-  }
-}
-
-// the cheetah as a model of pf_fit_frame (pose_fit_dev.hpp): the constant box, FK frames F[cur] (the iterate's) and F[cur ^ 1]
-// (the trial's), A and the factor's rows in PoseFitLds
-struct CheetahFit {
-  static constexpr int RED2 = 32;
-  PoseFitLds& S;
-  const int (&piv)[PF_TASKS];
+// the cheetah fitted to 3-D points as a model of pf_fit_frame (pose_fit_dev.hpp): CheetahCore (pose_fit_cheetah.hpp) plus the
+// whitened residuals, Jw = U J and the three-tile Gram product
+struct CheetahFit : CheetahCore<PoseFitLds> {
   const double kappa;
-  const int lane;
   const unsigned emask;
-  int cur = 0;
 
-  __device__ __forceinline__ static constexpr int n_states() { return NP; }
-  __device__ __forceinline__ static constexpr int n_slots() { return NL; }
-  __device__ __forceinline__ double* x() const { return S.x; }
-  __device__ __forceinline__ double* xt() const { return S.xt; }
-  __device__ __forceinline__ double* m() const { return S.m; }
-  __device__ __forceinline__ double* g() const { return S.g; }
-  __device__ __forceinline__ double* red() const { return S.red; }
-  __device__ __forceinline__ double* cp() const { return &S.L[0][0]; }      // [60][3]; the factor is not read again
-
-  __device__ __forceinline__ double lo(int p) const { return c_pf_lo[p]; }
-  __device__ __forceinline__ double hi(int p) const { return c_pf_hi[p]; }
+  __device__ __forceinline__ CheetahFit(PoseFitLds& S_, const int (&piv_)[PF_TASKS], double kappa_, int lane_, unsigned emask_)
+      : CheetahCore<PoseFitLds>(S_, piv_, lane_), kappa(kappa_), emask(emask_) {}
 
   __device__ __forceinline__ double eval(const double* xv, bool trial) {
     CovFrame& T = S.F[trial ? cur ^ 1 : cur];
@@ -245,73 +123,14 @@ struct CheetahFit {
     pf_normal(S, emask, kappa, lane);
   }
   __device__ __forceinline__ void accepted() { cur ^= 1; }
-  __device__ __forceinline__ double diag(int p) const { return S.A[p][p]; }
-  // the active set at S.x, one bit per state: at a bound with the gradient pushing outward (oracle active_set, cov_codes)
-  __device__ __forceinline__ unsigned active_set(int lane) const {
-    bool fixed = false;
-    if (lane < NP) {
-      const double xv = S.x[lane], gv = S.g[lane], gtol = GRAD_ZERO_REL * S.A[lane][lane];
-      fixed = (xv <= c_pf_lo[lane] && gv > gtol) || (xv >= c_pf_hi[lane] && gv < -gtol);
-    }
-    return (unsigned)__ballot(fixed);
-  }
-
-  // pf_factor_rows; the rows are stored to S.L as well, for the products with L^T
-  __device__ __forceinline__ bool factor(unsigned fixmask, double lam, int lane, double (&r)[NP], double& dinv) {
-    const bool ok = pf_factor_rows<NP, PF_LD, false>(&S.A[0][0], fixmask, lam, lane, r, dinv);
-    __syncthreads();                              // (the readers of the previous factor are done)
-    if (lane < NP) {
-#pragma unroll
-      for (int j = 0; j < NP; ++j) S.L[lane][j] = r[j];
-    }
-    __syncthreads();
-    return ok;
-  }
-  // pf_solve, its back substitution on the rows of S.L read as columns of L^T
-  __device__ __forceinline__ double solve(const double (&r)[NP], double dinv, double v, int lane) const {
-    const int col = lane < NP ? lane : 0;
-    return pf_solve<NP, false>(r, dinv, v, lane, NP, [&](int k) { return &S.L[k][col]; });
-  }
-
-  // column c of the inverse by lane c, into row c of S.A (A itself is not read again); then symmetric bit for bit, pinned
-  // rows and columns exactly 0
-  __device__ __forceinline__ bool cov_x(unsigned fixmask, const double (&r)[NP], double dinv, int lane) {
-    bool ok = true;
-    double z[NP];
-    pf_inverse_column(r, dinv, lane, z);
-    if (lane < NP) {
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        S.A[lane][i] = z[i];
-        ok = ok && m_finite(z[i]);
-      }
-    }
-    ok = __all(ok);
-    __syncthreads();
-    for (int t = lane; t < PF_PAIRS; t += 64) {
-      int p = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-      if (p * (p + 1) / 2 > t) --p;
-      if ((p + 1) * (p + 2) / 2 <= t) ++p;
-      const int q = t - p * (p + 1) / 2;
-      const double v = (((fixmask >> p) | (fixmask >> q)) & 1u) ? 0.0 : 0.5 * (S.A[p][q] + S.A[q][p]);
-      S.A[p][q] = v;
-      S.A[q][p] = v;
-    }
-    return ok;
-  }
   __device__ __forceinline__ void outputs_at_x(bool) {}                     // (F[cur] is the returned point's)
-  __device__ __forceinline__ double pos(int t) const { return S.F[cur].pos[t / 3][t % 3]; }
-  __device__ __forceinline__ double cov(int p, int q) const { return S.A[p][q]; }
-  __device__ __forceinline__ void jacobian_raw(int lane) { pf_jacobian<true>(S, S.F[cur], emask, piv, lane); }
-  __device__ __forceinline__ double jw(int p, int row) const { return S.Jw[p][row]; }
-  __device__ __forceinline__ bool moves(int p, int l) const { return (S.colmask[p] >> l) & 1u; }
 };
 
 __global__ void __launch_bounds__(64) k_pose_fit(PoseFitArgs a) {
   __shared__ PoseFitLds S;
   const int lane = threadIdx.x;
-  if (lane < NP) {
-    unsigned mk = 0xFFFFFu;
+  if (lane < NP) {                                // (pf_colmask of pose_fit_cheetah.hpp is the twin of these lines: called from
+    unsigned mk = 0xFFFFFu;                       //  here it reorders this kernel's instructions, and the kernel keeps its code)
     if (lane >= 3) {
       mk = 0;
       for (int l = 0; l < NL; ++l)
@@ -357,7 +176,7 @@ __global__ void __launch_bounds__(64) k_pose_fit(PoseFitArgs a) {
       S.x[lane] = v;
     }
     __syncthreads();
-    CheetahFit m{S, piv, a.kappa, lane, emask};
+    CheetahFit m(S, piv, a.kappa, lane, emask);
     pf_fit_frame<NP>(m, a, n, lane, n_enter);
   }
 }

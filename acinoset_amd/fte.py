@@ -670,8 +670,9 @@ def _pose_fit(launch, points, cov, x0, N, n_slots, active, n_full, texts, prior_
               xtol, lam0, return_cov):
     """What ``pose_fit`` and ``build.pose_fit`` share: the dict in place of ``points``, the checks of the shapes - points
     [N, n_slots, 3], cov [N, n_slots, 3, 3], x0 [N, len(active)], with ``texts`` the caller's three messages; N None: the
-    frames of ``points`` - and of the parameters, the staging, the outputs, ``PoseFitParams``, the scatter of x into
-    x_full [N, n_full] at the columns ``active``, the dict, and numpy out for numpy in.  ``launch(prm, dev, N, ins, outs)``
+    frames of ``points`` - and of the parameters (``_fit_checks``), the staging, the outputs (``_fit_outputs``), ``PoseFitParams``,
+    the scatter of x into x_full [N, n_full] at the columns ``active``, the dict, and numpy out for numpy in (``_fit_dict``: the
+    three that ``pose_fit_pixels`` uses too).  ``launch(prm, dev, N, ins, outs)``
     makes the library call: ``ins`` the pointers of points, cov, x0 and ``outs`` those of the ten outputs, both in the order
     of the C entries."""
     if isinstance(points, dict):
@@ -688,35 +689,121 @@ def _pose_fit(launch, points, cov, x0, N, n_slots, active, n_full, texts, prior_
         raise ValueError(texts[1])
     if x0 is not None and _shape(x0) != (N, P):
         raise ValueError(texts[2])
-    for name, val in (("prior_sigma", prior_sigma), ("sigma_iso", sigma_iso), ("ftol", ftol), ("xtol", xtol), ("lam0", lam0)):
-        if not (np.isfinite(val) and val > 0):
-            raise ValueError(f"{name} must be finite and > 0")
-    if int(max_iter) != max_iter or not 1 <= max_iter <= 255:
-        raise ValueError("max_iter must be an integer in 1..255")
-    if int(min_markers) != min_markers or not 1 <= min_markers <= L:
-        raise ValueError(f"min_markers must be an integer in 1..{L}")
+    _fit_checks((("prior_sigma", prior_sigma), ("sigma_iso", sigma_iso), ("ftol", ftol), ("xtol", xtol), ("lam0", lam0)),
+                max_iter, "min_markers", min_markers, L)
     dev = calib._dev()
     pts = calib._to_dev(points, dev)
     cv = None if cov is None else calib._to_dev(cov, dev)
     xs = None if x0 is None else calib._to_dev(x0, dev)
-    f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
-    x, cost, pos = torch.empty((N, P), **f64), torch.empty((N,), **f64), torch.empty((N, L, 3), **f64)
-    nm, status, iters, pinned = (torch.empty(sh, **u8) for sh in ((N,), (N,), (N,), (N, P)))
-    cov_x = torch.empty((N, P, P), **f64) if return_cov else None
-    cov_pos = torch.empty((N, L, 3, 3), **f64) if return_cov else None
-    std_pos = torch.empty((N, L), **f64) if return_cov else None
+    o = _fit_outputs(N, P, L, dev, return_cov)
+    nm = torch.empty((N,), dtype=torch.uint8, device=dev)
     prm = _lib.PoseFitParams(int(max_iter), int(min_markers), float(lam0), float(ftol), float(xtol), float(prior_sigma),
                              float(sigma_iso))
     launch(prm, dev, N, [ptr(t) for t in (pts, cv, xs)],
-           [ptr(t) for t in (x, cost, nm, status, iters, pinned, cov_x, pos, cov_pos, std_pos)])
-    x_full = torch.zeros((N, n_full), **f64)
-    x_full[:, torch.as_tensor(np.asarray(active, dtype=np.int64), device=dev)] = x
-    out = dict(x=x, x_full=x_full, positions=pos, cost=cost, n_markers=nm, status=status, iters=iters, pinned=pinned)
-    if return_cov:
-        out.update(cov_x=cov_x, cov_positions=cov_pos, std_positions=std_pos)
-    if isinstance(points, torch.Tensor):
+           [ptr(t) for t in (o["x"], o["cost"], nm, o["status"], o["iters"], o["pinned"], o["cov_x"], o["positions"],
+                             o["cov_positions"], o["std_positions"])])
+    return _fit_dict(o, "n_markers", nm, active, n_full, isinstance(points, torch.Tensor))
+
+
+def _fit_checks(positive, max_iter, count_name, count, count_max):
+    """The parameter checks of the per-frame fits: ``positive`` (name, value) pairs finite and > 0, max_iter one byte, the
+    least count of measurements an integer in 1..count_max."""
+    for name, val in positive:
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError(f"{name} must be finite and > 0")
+    if int(max_iter) != max_iter or not 1 <= max_iter <= 255:
+        raise ValueError("max_iter must be an integer in 1..255")
+    if int(count) != count or not 1 <= count <= count_max:
+        raise ValueError(f"{count_name} must be an integer in 1..{count_max}")
+
+
+def _fit_outputs(N, P, L, dev, return_cov):
+    """The output tensors every per-frame fit has, under the names of the returned dict (None for the covariances not asked
+    for)."""
+    f64, u8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+    o = dict(x=torch.empty((N, P), **f64), cost=torch.empty((N,), **f64), positions=torch.empty((N, L, 3), **f64))
+    o.update((key, torch.empty(sh, **u8)) for key, sh in (("status", (N,)), ("iters", (N,)), ("pinned", (N, P))))
+    o["cov_x"] = torch.empty((N, P, P), **f64) if return_cov else None
+    o["cov_positions"] = torch.empty((N, L, 3, 3), **f64) if return_cov else None
+    o["std_positions"] = torch.empty((N, L), **f64) if return_cov else None
+    return o
+
+
+def _fit_dict(o, count_key, count, active, n_full, tensors, **more):
+    """The dict of a per-frame fit from its output tensors: x scattered into x_full [N, n_full] at the columns ``active``, the
+    count under its key, ``more`` after the integer outputs, the covariances when they were asked for; numpy unless
+    ``tensors``."""
+    x = o["x"]
+    x_full = torch.zeros((x.shape[0], n_full), dtype=torch.float64, device=x.device)
+    x_full[:, torch.as_tensor(np.asarray(active, dtype=np.int64), device=x.device)] = x
+    out = dict(x=x, x_full=x_full, positions=o["positions"], cost=o["cost"])
+    out[count_key] = count
+    out.update(status=o["status"], iters=o["iters"], pinned=o["pinned"], **more)
+    if o["cov_x"] is not None:
+        out.update(cov_x=o["cov_x"], cov_positions=o["cov_positions"], std_positions=o["std_positions"])
+    if tensors:
         return out
     return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def pose_fit_pixels(det, k_arr, d_arr, r_arr, t_arr, thresh=0.5, camera_model="fisheye", x0=None, f_scale=5.0, sigma_px=5.0,
+                    prior_sigma=np.pi, min_detections=2, max_iter=100, ftol=1e-10, xtol=1e-10, lam0=1e-3, return_cov=True):
+    """Per-frame pose of the cheetah model from the detections themselves (include/acinoset_hip.h:
+    acino_cheetah_pose_fit_px): per frame the minimiser over the 25 active states, inside the box of ``bounds45()[ACTIVE]``, of
+
+        F(x) = 1/sigma_px^2 sum_{(c,l) valid} sum_{k in (u,v)} 1/2 f^2 log1p(r_k^2 / f^2)
+             + 1/2 sum_{p = 3..24} (x_p - m_p)^2 / prior_sigma^2,        r = pi_c(FK_l(x)) - det[n, c, l, :2],  f = f_scale
+
+    - the reprojection error of the skeleton in every camera under the per-coordinate Cauchy loss of
+    ``calib.triangulate_multiview_dense`` - by the projected Levenberg-Marquardt of ``pose_fit``, one launch.  ``det``
+    [N,C,20,3] (x, y, likelihood); a detection is valid when its likelihood is above ``thresh`` and its pixel finite, so a
+    marker one camera sees enters and a clip of one camera has a pose.  The rig and ``camera_model`` ("fisheye" or "pinhole")
+    as in ``calib.triangulate_multiview_dense``.  ``x0`` [N,25] is the start and, clipped to the box, the centre m of the ridge;
+    default: ``pose_fit`` of ``calib.triangulate_multiview_dense`` of the same detections (thresh, f_scale, sigma_px), the
+    frames without a fit filled by ``fill_unfitted_frames`` (ValueError when no frame has one: give ``x0`` to a clip of one
+    camera).  Returns the dict of ``pose_fit`` with n_detections uint16 [N] (the valid detections; status 2: fewer than
+    ``min_detections``) in place of n_markers, plus weight [N,C,20,2]: the IRLS weight 1 / (1 + r^2 / f^2) every coordinate
+    ended with, exactly 0 for an invalid detection.  cov_x = A_free^-1 with A = sum w J^T J / sigma_px^2 + the ridge: the
+    matrix family of ``calib.triangulate_multiview_dense`` and ``sba.covariance``, carried to the states.
+
+    numpy in, numpy out; CUDA tensors in, CUDA tensors out with no host copy when ``x0`` is given (the default start fills its
+    unfitted frames on the host, N x 25 values, as ``pose_fit_init`` does)."""
+    if camera_model not in calib.CAMERAS:
+        raise ValueError(f"camera_model must be one of {calib.CAMERA_MODELS}")
+    shape = _shape(det)
+    if len(shape) != 4 or shape[2:] != (N_MARKERS, 3):
+        raise ValueError("det must be [N, C, 20, 3]")
+    N, Cn = shape[:2]
+    if not 1 <= Cn <= _lib.MAX_CAMS:
+        raise ValueError(f"det holds {Cn} cameras: 1..{_lib.MAX_CAMS} are supported")
+    if len(k_arr) != Cn:
+        raise ValueError("camera count mismatch")
+    if x0 is not None and _shape(x0) != (N, N_ACTIVE):
+        raise ValueError("x0 must be [N, 25] (the active states)")
+    _fit_checks((("prior_sigma", prior_sigma), ("f_scale", f_scale), ("sigma_px", sigma_px), ("ftol", ftol), ("xtol", xtol),
+                 ("lam0", lam0)), max_iter, "min_detections", min_detections, N_MARKERS * Cn)
+    if np.isnan(thresh):
+        raise ValueError("thresh must not be NaN")
+    recs = calib.camera_records(camera_model, k_arr, d_arr, r_arr, t_arr)
+    dev = calib._dev()
+    d = calib._to_dev(det, dev)
+    if x0 is None:
+        tri = calib.triangulate_multiview_dense(d, thresh, k_arr, d_arr, r_arr, t_arr, model=camera_model, f_scale=f_scale,
+                                                sigma_px=sigma_px)
+        fit = pose_fit(tri, return_cov=False)
+        x0 = fill_unfitted_frames(fit["x"].cpu().numpy(), fit["status"].cpu().numpy() < 2)
+    xs = calib._to_dev(x0, dev)
+    cams = torch.as_tensor(recs, device=dev)
+    o = _fit_outputs(N, N_ACTIVE, N_MARKERS, dev, return_cov)
+    nd = torch.empty((N,), dtype=torch.uint16, device=dev)
+    weight = torch.empty((N, Cn, N_MARKERS, 2), dtype=torch.float64, device=dev)
+    prm = _lib.PoseFitPxParams(calib.CAMERAS[camera_model].code, int(max_iter), int(min_detections), 0, float(lam0), float(ftol),
+                               float(xtol), float(prior_sigma), float(thresh), float(f_scale), float(sigma_px))
+    check(lib().acino_cheetah_pose_fit_px(prm, ptr(d), N, Cn, ptr(cams), ptr(xs),
+                                          *(ptr(t) for t in (o["x"], o["cost"], nd, o["status"], o["iters"], o["pinned"], o["cov_x"],
+                                                             o["positions"], o["cov_positions"], o["std_positions"], weight)),
+                                          stream_ptr()))
+    return _fit_dict(o, "n_detections", nd, ACTIVE, N_STATES, isinstance(det, torch.Tensor), weight=weight)
 
 
 PSI_COLUMNS = [int(np.nonzero(ACTIVE == PSI + k)[0][0]) for k in (0, 1, 3, 4, 5)]     # the psi states among the active ones

@@ -19,6 +19,8 @@
  *   acino_cheetah_pose_fit           (no counterpart) per-frame pose with error bars from 3-D marker points and their
  *                                    covariances (the outputs of acino_triangulate_multiview)
  *   acino_skel_pose_fit              (no counterpart) the same for a skeleton's link program (acino_skel_fte_*)
+ *   acino_cheetah_pose_fit_px        (no counterpart) per-frame pose with error bars from the detections themselves: the
+ *                                    reprojection error of the skeleton in every camera, robust weight per coordinate
  *   acino_cheetah_fk                 pose_to_3d                       src/all_optimizations.py:66-190
  *   acino_fte_*                      the Pyomo model + opt.solve()    src/all_optimizations.py:283-556
  *
@@ -194,6 +196,41 @@ int acino_cheetah_pose_fit(const acino_pose_fit_params* prm, const double* d_poi
                            const double* d_x0, int64_t n_frames, double* d_x, double* d_cost, uint8_t* d_nmarkers,
                            uint8_t* d_status, uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x, double* d_pos,
                            double* d_cov_pos, double* d_std_pos, void* stream);
+
+/* ---- per-frame cheetah pose fit from the detections of every camera (csrc/pose_fit_px.hip) -------
+ * Per frame n, from d_det[N][C][20][3] (x, y, likelihood) and d_cams - the layouts of acino_triangulate_multiview,
+ * 1 <= n_cams <= ACINO_MAX_CAMS -, over the 25 active states x inside the box of the FTE:
+ *   F(x) = 1/sigma_px^2 sum_{(c,l) valid} sum_{k in (u,v)} 1/2 f^2 log1p(r_k^2 / f^2)
+ *        + 1/2 sum_{p = 3..24} (x_p - m_p)^2 / prior_sigma^2,      r = pi_c(FK_l(x)) - z_{n,c,l},  f = f_scale,
+ * pi_c the calibration-level projection of acino_triangulate_multiview and its per-coordinate Cauchy loss.  A detection is
+ * valid when its likelihood is above thresh and both pixel values are finite: a marker one camera sees enters, and no
+ * triangulation stands between a detection and the skeleton.  m = the start d_x0[N][25] (required) clipped to the box.
+ * Gradient and matrix carry the IRLS weight w = 1 / (1 + r_k^2 / f^2): g = sum w r J / sigma_px^2 + ridge and
+ * A = sum w J^T J / sigma_px^2 + ridge with J = (J_pi R_c) J_FK; the same A serves the step, the predicted reduction, the
+ * active set and the outputs, so cov_x = A_free^-1 is the matrix family of acino_triangulate_multiview and
+ * acino_sba_covariance carried to the states.  An x that puts a marker with a valid detection at z_c <= 0 in that camera has
+ * F = +inf: as a trial it is refused, as a start it gives status 3.  Iteration, stops, active set, status codes, NaN
+ * conventions and the bit-symmetric covariances are those of acino_cheetah_pose_fit, with "fewer than min_detections valid
+ * detections" for status 2.  One launch (one 64-lane wave per frame), no synchronisation, no workspace.  At the returned x:
+ *   d_x, d_cost, d_status, d_iters, d_pinned, d_cov_x, d_pos, d_cov_pos, d_std_pos   as acino_cheetah_pose_fit
+ *   d_ndet[N]              uint16: the valid detections of the frame (at most 20 C)
+ *   d_weight[N][C][20][2]  the w every coordinate ended with, exactly 0 for an invalid detection, NaN for status 2 and 3
+ * Any output but d_x and d_status may be NULL.  Argument validation happens before any device call; n_frames == 0 is a
+ * no-op. */
+typedef struct acino_pose_fit_px_params {
+  int32_t camera_model;     /* 0 fisheye (24-double records), 1 pinhole (32) */
+  int32_t max_iter;         /* 1..255 */
+  int32_t min_detections;   /* 1..20 n_cams */
+  int32_t reserved;         /* 0 */
+  double lam0, ftol, xtol, prior_sigma;   /* all > 0; prior_sigma [rad] */
+  double thresh;            /* not NaN */
+  double f_scale, sigma_px; /* > 0 [px] */
+} acino_pose_fit_px_params;
+size_t acino_sizeof_pose_fit_px_params(void);
+int acino_cheetah_pose_fit_px(const acino_pose_fit_px_params* prm, const double* d_det, int64_t n_frames, int n_cams,
+                              const double* d_cams, const double* d_x0, double* d_x, double* d_cost, uint16_t* d_ndet,
+                              uint8_t* d_status, uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x, double* d_pos,
+                              double* d_cov_pos, double* d_std_pos, double* d_weight, void* stream);
 
 /* ---- cheetah forward kinematics (a-4) ---------------------------------------------------------
  * d_q[N][45] full state -> d_pos[N][20][3]. */
