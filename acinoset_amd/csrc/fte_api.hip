@@ -369,14 +369,34 @@ k_totals(acino_fte_state* st, const double* cost_part, int n_cost, const double*
         // the noise - with many sweeps they are not, and their ratio (noise over noise, ~1) must not refuse a converged
         // solve.  Nothing measurable at all (the first update already at rounding): rho = 1/2 assumed, as with one sweep.
         double rho = 0.5;
+        const double noise = 0x1p-44 * r_x;
+        const double d1 = n_ref == 2 ? r_d0 : r_f1, d2 = n_ref == 2 ? r_d1 : (n_ref == 3 ? r_d0 : r_f2);
         if (n_ref >= 2) {
-          const double noise = 0x1p-44 * r_x;
-          const double d1 = n_ref == 2 ? r_d0 : r_f1, d2 = n_ref == 2 ? r_d1 : (n_ref == 3 ? r_d0 : r_f2);
           const double rho_first = d1 > noise ? d2 / d1 : 0.5;
           const double rho_last = (r_d1 > noise && r_d0 > noise) ? r_d1 / r_d0 : 0.0;
           rho = fmax(rho_first, rho_last);
         }
         bound = (rho <= 0.5 && r_x > 0.0) ? rho / (1.0 - rho) * r_d1 / r_x : (r_d1 == 0.0 ? 0.0 : 1.0);
+        if (n_ref >= 2 && rho <= 0.5 && r_x > 0.0 && r_d1 > 0.0) {
+          // One ratio of consecutive updates is not the contraction.  Block Jacobi on a chain alternates: the max-norm ratios
+          // |u_k+1| / |u_k| of odd and of even k differ (a two-node chain with couplings a, b: the ratios are a, b, a, ... while
+          // the rate is sqrt(a b)), and the error left after sweep n starts with u_n+1 = r_n u_n - the ratio of the parity of n,
+          // which the first pair of sweeps measures only for odd n.  With two sweeps the bound above was 5 to 7 times below the
+          // true error (10 000 and 999 frames at lam = 1e-6: tests/test_gpu_fte_step_reference.py).  What does contract
+          // uniformly is a PAIR of sweeps, |u_k+2| <= sigma |u_k|:
+          //     |error after sweep n| <= |u_n+1| + |u_n+2| + ... <= sigma / (1 - sigma) (|u_n-1| + |u_n|).
+          // sigma from updates an even number of sweeps apart - (u_3, u_1); n >= 4: (u_n, u_2) for even n, (u_n, u_1) for odd n -
+          // when both are above the noise; otherwise (and with two sweeps, which have no such pair) from the first ratio and
+          // the unmeasured one taken as 1/2, the rate above which a step is refused anyway.
+          const int steps = n_ref == 2 ? 0 : (n_ref == 3 ? 2 : ((n_ref & 1) ? n_ref - 1 : n_ref - 2));
+          const double den = (n_ref >= 4 && !(n_ref & 1)) ? d2 : d1;
+          double sigma = 0.5 * (d1 > noise ? d2 / d1 : 0.5);
+          if (steps > 0 && r_d1 > noise && den > noise) sigma = pow(r_d1 / den, 2.0 / (double)steps);
+          const double pair = sigma <= 0.25 ? sigma / (1.0 - sigma) * (r_d0 + r_d1) / r_x : 1.0;
+          // (two sweeps: u_3 <= u_2 / 2 leads, u_4 = sigma u_2 follows)
+          const double two = (0.5 * r_d1 + sigma * r_d1) / (1.0 - sigma) / r_x;
+          bound = fmax(bound, n_ref == 2 ? two : pair);
+        }
         S.trunc_eps = bound;
       } else {
         S.trunc_eps = sqrt(e2);

@@ -85,6 +85,20 @@ def test_chunk_sweep_first_step_equals_oracle_banded_solve(mods, n, m):
     xt = np.clip(x + delta, prob.lo, prob.hi)
     assert np.abs(got[4] - xt).max() < 1e-9 * max(1.0, float(np.abs(delta).max())), float(np.abs(got[4] - xt).max())
     assert abs(got[0] - prob.evaluate(xt)[0]) < 1e-9 * abs(F)
+    # ... and on the scale of what fp64 LAPACK itself is off by on this system (tests/fte_step_ref.py: the refined solution of
+    # the oracle's system; K and the allowance of one rounding of x as in test_gpu_fte_step_reference.py)
+    import fte_step_ref as ref
+    K_TOL = ref.K_GPU
+    h = H.copy()
+    idx = np.arange(25)
+    h[:, idx, idx] += ref.smooth_diag(prob)
+    r = ref.step_reference(prob, x, g, h, 1e-3)
+    assert np.array_equal(r.fixed, fixed)
+    e_lapack = float(np.abs(r.delta_lapack - r.delta_ref_ld).max())
+    e_gpu = float(np.abs(got[4] - np.clip(x + r.delta_ref, prob.lo, prob.hi)).max())
+    scale = max(e_lapack, 2.0 ** -52 * float(np.abs(r.delta_ref).max()))
+    print(f"n={n} m={m}: e_gpu {e_gpu:.3e} e_lapack {e_lapack:.3e} ratio {e_gpu / scale:.2f}")
+    assert e_gpu <= K_TOL * scale + 2.0 ** -52 * float(np.abs(x).max()), (e_gpu, e_lapack)
 
 
 def test_chunk_sweep_with_clips_and_windows(mods):
