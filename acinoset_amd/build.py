@@ -811,21 +811,33 @@ def pose_fit(model, points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01
                          prior_sigma, sigma_iso, min_markers, max_iter, ftol, xtol, lam0, return_cov)
 
 
+def _model_detections(model):
+    """The model's own per-slot detections as det [N, C, n_pose, 3] (x, y, likelihood): ``model.meas`` with the likelihood 1
+    where ``model.weights`` > 0 and 0 elsewhere, so that a weighted detection is the valid one at threshold 0.5."""
+    w = np.asarray(model.weights, dtype=np.float64)
+    return np.ascontiguousarray(np.concatenate([np.asarray(model.meas, dtype=np.float64), (w > 0).astype(np.float64)[..., None]],
+                                               axis=-1))
+
+
+def _model_sigma_px(model):
+    """1 / max(``model.weights``), the model's r_meas; ValueError when no weight is positive."""
+    w_max = float(np.nanmax(np.asarray(model.weights, dtype=np.float64), initial=0.0))
+    if not w_max > 0:
+        raise ValueError("no positive weight in the model: pass sigma_px (px), the noise scale of a detection")
+    return 1.0 / w_max
+
+
 def model_triangulation(model, f_scale=5.0, sigma_px=None, **kw):
     """``calib.triangulate_multiview_dense`` of the model's own per-slot detections: det = [``model.meas``,
     ``model.weights`` > 0] with threshold 0.5 (a weighted detection is a valid one), the model's cameras and camera model.
     ``sigma_px`` defaults to 1 / max(``model.weights``), the model's r_meas, so that the covariances are those of the noise the
     solve states.  ``kw`` goes to the triangulation (``max_iter``, ``xtol``).  The detections go to the device as a tensor:
     the dict holds CUDA tensors (points [N, n_pose, 3], cov [N, n_pose, 3, 3], ...), what ``pose_fit`` takes."""
-    w = np.asarray(model.weights, dtype=np.float64)
     if sigma_px is None:
-        w_max = float(np.nanmax(w, initial=0.0))
-        if not w_max > 0:
-            raise ValueError("no positive weight in the model: pass sigma_px (px), the noise scale of a detection")
-        sigma_px = 1.0 / w_max
-    det = np.concatenate([np.asarray(model.meas, dtype=np.float64), (w > 0).astype(np.float64)[..., None]], axis=-1)
+        sigma_px = _model_sigma_px(model)
+    det = _model_detections(model)
     dev = calib._dev()
-    return calib.triangulate_multiview_dense(torch.as_tensor(np.ascontiguousarray(det), device=dev), 0.5, model.K, model.D, model.R,
+    return calib.triangulate_multiview_dense(torch.as_tensor(det, device=dev), 0.5, model.K, model.D, model.R,
                                              model.t, model=getattr(model, "camera_model", "fisheye"), f_scale=f_scale,
                                              sigma_px=float(sigma_px), **kw)
 
@@ -856,6 +868,78 @@ def _pose_fit_start(model, fit_kw):
     init_x = np.zeros((model.N, model.P))
     init_x[:, act] = np.clip(xa, model.lo[:, act], model.hi[:, act])
     return init_x
+
+
+def pose_fit_pixels(model, x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=None, prior_sigma=np.pi, min_detections=2,
+                    max_iter=100, ftol=1e-10, xtol=1e-10, lam0=1e-3, return_cov=True):
+    """Per-frame pose of a ``SkeletonModel`` from the detections of every camera (include/acinoset_hip.h:
+    acino_skel_pose_fit_px; ``fte.pose_fit_pixels`` for a skeleton): per frame the minimiser over the ``model.active`` states,
+    inside the frame's box ``model.lo`` / ``model.hi``, of
+
+        F(x) = 1/sigma_px^2 sum_{(c,l) valid} sum_{k in (u,v)} 1/2 f^2 log1p(r_k^2 / f^2)
+             + 1/2 sum_{p >= 3} (x_p - m_p)^2 / prior_sigma^2,        r = pi_c(FK_l(x)) - det[n, c, l, :2],  f = f_scale
+
+    by the projected Levenberg-Marquardt of ``pose_fit``, one launch.  No triangulation stands between a detection and the
+    skeleton: a slot one camera sees enters, a frame without any triangulated slot has a pose, and a wrong detection is
+    down-weighted frame by frame (w = 1 / (1 + r^2 / f^2)).  ``det`` [N, C, n_pose, 3] (x, y, likelihood; N = ``model.N``, slot
+    l is pose slot l) is valid where its likelihood is above ``thresh`` and both pixel values are finite; default: the model's
+    own detections as ``model_triangulation`` takes them, [``model.meas``, ``model.weights`` > 0].  ``sigma_px`` defaults to
+    1 / max(``model.weights``).  The rig and the camera model are the model's.  ``x0`` [N, n_active] is the start and, clipped
+    to the box, the centre m of the ridge on the angles; default: the chain of ``pose_fit_start`` on the model's own
+    detections - ``model_triangulation``, ``pose_fit`` without covariances, ``fte.fill_unfitted_frames`` with the skeleton's
+    psi columns, the clip to the box - and ValueError when no frame has a fit (a clip of one camera: pass ``x0``).
+
+    Returns the dict of ``pose_fit`` with n_detections uint16 [N] (the valid detections; status 2: fewer than
+    ``min_detections``) in place of n_markers, plus weight [N, C, n_pose, 2]: the weight every coordinate ended with, exactly 0
+    for an invalid detection, NaN for status 2 and 3.  cov_x = A_free^-1 with A = sum w J^T J / sigma_px^2 + the ridge.
+
+    numpy in, numpy out; a CUDA tensor as ``det`` or ``x0`` gives CUDA tensors out, with no host copy when ``x0`` is given."""
+    act = np.asarray(model.active, dtype=np.int32)
+    N, Pa, Lp, Cn = model.N, len(act), len(model.names), int(np.shape(model.meas)[1])
+    camera_model = getattr(model, "camera_model", "fisheye")
+    if camera_model not in calib.CAMERAS:
+        raise ValueError(f"the model's camera_model must be one of {calib.CAMERA_MODELS}")
+    if det is not None and fte._shape(det) != (N, Cn, Lp, 3):
+        raise ValueError(f"det must be [{N}, {Cn}, {Lp}, 3] (model.N frames, the model's cameras, one slot per pose)")
+    if not 1 <= Cn <= _lib.MAX_CAMS:
+        raise ValueError(f"the model holds {Cn} cameras: 1..{_lib.MAX_CAMS} are supported")
+    if x0 is not None and fte._shape(x0) != (N, Pa):
+        raise ValueError(f"x0 must be [{N}, {Pa}] (the active states)")
+    if sigma_px is None:
+        sigma_px = _model_sigma_px(model)
+    fte._fit_checks((("prior_sigma", prior_sigma), ("f_scale", f_scale), ("sigma_px", sigma_px), ("ftol", ftol), ("xtol", xtol),
+                     ("lam0", lam0)), max_iter, "min_detections", min_detections, Lp * Cn)
+    if np.isnan(thresh):
+        raise ValueError("thresh must not be NaN")
+    recs = calib.camera_records(camera_model, model.K, model.D, model.R, model.t)
+    tensors = isinstance(det, torch.Tensor) or isinstance(x0, torch.Tensor)
+    dev = calib._dev()
+    p = _skel_params(model, Pa)
+    nbytes = lib().acino_skel_pose_fit_px_workspace_bytes(C.byref(p))
+    if nbytes == 0:
+        raise ValueError("problem outside the kernel limits (n_active <= 64)")
+    d = calib._to_dev(_model_detections(model) if det is None else det, dev)
+    if x0 is None:
+        init_x = _pose_fit_start(model, {})
+        if init_x is None:
+            raise ValueError("no frame has a pose fit to start from (no slot was triangulated in the whole clip): pass x0")
+        x0 = init_x[:, act]
+    xs = calib._to_dev(x0, dev)
+    lo, hi = calib._to_dev(model.lo[:, act], dev), calib._to_dev(model.hi[:, act], dev)
+    cams = torch.as_tensor(recs, device=dev)
+    o = fte._fit_outputs(N, Pa, Lp, dev, return_cov)
+    nd = torch.empty((N,), dtype=torch.uint16, device=dev)
+    weight = torch.empty((N, Cn, Lp, 2), dtype=torch.float64, device=dev)
+    prm = _lib.PoseFitPxParams(calib.CAMERAS[camera_model].code, int(max_iter), int(min_detections), 0, float(lam0), float(ftol),
+                               float(xtol), float(prior_sigma), float(thresh), float(f_scale), float(sigma_px))
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)      # (it goes back to the allocator of this very stream)
+    act_c = (C.c_int32 * Pa)(*[int(a) for a in act])
+    check(lib().acino_skel_pose_fit_px(prm, C.byref(p), _ops_array(model.prog), act_c, ptr(d), N, Cn, ptr(cams), ptr(xs), ptr(lo),
+                                       ptr(hi), *(ptr(t) for t in (o["x"], o["cost"], nd, o["status"], o["iters"], o["pinned"],
+                                                                   o["cov_x"], o["positions"], o["cov_positions"],
+                                                                   o["std_positions"], weight)),
+                                       C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
+    return fte._fit_dict(o, "n_detections", nd, act, model.P, tensors, weight=weight)
 
 
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,

@@ -1,6 +1,8 @@
-// The per-frame pose fit, stated once: pose_fit.hip (the cheetah, 25 states, from 3-D points), pose_fit_px.hip (the cheetah from
-// the detections of every camera) and skel_pose_fit.hip (a link program, PT = 16 .. 64 rows) instantiate pf_fit_frame<N> with
-// their model.  Here: the status codes, the I/O block of both kernels, the admission
+// The per-frame pose fit, stated once.  Four models instantiate pf_fit_frame<N>: CheetahFit (pose_fit.hip: the cheetah, 25
+// states, from 3-D points), CheetahPxFit (pose_fit_px.hip: the cheetah from the detections of every camera), SkelFit<PT>
+// (skel_pose_fit.hip: a link program, PT = 16 .. 64 rows, from 3-D points) and SkelPxFit<PT, PINHOLE> (skel_pose_fit_px.hip: a
+// link program from the detections); the cheetah's two share CheetahCore (pose_fit_cheetah.hpp), the skeleton's two SkelCore
+// (pose_fit_skel.hpp), the two pixel models px_project (pose_fit_px_dev.hpp).  Here: the status codes, the I/O block of both kernels, the admission
 // and whitening of a 3-D point with its covariance, the register-resident Cholesky steps and the two substitutions, the
 // projected Levenberg-Marquardt controller (active set, damped step on the free states, clip, predicted reduction, trial;
 // Nielsen's rule and the ftol / xtol stops on an accepted trial, lam *= nu on a refused one), the epilogue (active set and

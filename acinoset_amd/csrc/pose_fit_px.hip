@@ -32,20 +32,12 @@
 //   outputs    the count of valid detections (uint16: it exceeds a byte) and the weights at the returned x, stored by the
 //              model (outputs_at_x); PoseFitIo's nmarkers is NULL.
 #include "pose_fit_cheetah.hpp"
+#include "pose_fit_px_dev.hpp"
 
 namespace acino {
 
 constexpr int PX_ROWS = 2 * NL;       // 40 rows of one camera: (u, v) of marker l in rows 2 l, 2 l + 1
 constexpr int PX_GROUP = 3;           // cameras projected in one pass: 20 markers each over 60 of the 64 lanes
-
-// what the kernel reads and writes beyond PoseFitIo
-struct PxArgs {
-  const double *det, *cams;
-  int n_cams;
-  double thresh, fs2, ifs2, inv_sigma;
-  uint16_t* ndet;
-  double* weight;
-};
 
 struct PxLds {
   CovFrame F[2];
@@ -62,25 +54,6 @@ struct PxLds {
   unsigned colmask[NP];         // the markers that move with state p
   unsigned vmask[ACINO_MAX_CAMS];   // the markers with a valid detection in camera c
 };
-
-// marker position X in camera cm: pixel, d(uv)/dX = J_pi R_c (JAC), and whether it is in front
-template <bool JAC, class Rec>
-__device__ __forceinline__ bool px_project(const Rec& cm, const double* X, double uv[2], double JR[2][3]) {
-  const double xc = cm.R[0] * X[0] + cm.R[1] * X[1] + cm.R[2] * X[2] + cm.t[0];
-  const double yc = cm.R[3] * X[0] + cm.R[4] * X[1] + cm.R[5] * X[2] + cm.t[1];
-  const double zc = cm.R[6] * X[0] + cm.R[7] * X[1] + cm.R[8] * X[2] + cm.t[2];
-  double J[2][3];
-  mv_project(cm, xc, yc, zc, uv, J);
-  if (JAC) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      JR[k][0] = J[k][0] * cm.R[0] + J[k][1] * cm.R[3] + J[k][2] * cm.R[6];
-      JR[k][1] = J[k][0] * cm.R[1] + J[k][1] * cm.R[4] + J[k][2] * cm.R[7];
-      JR[k][2] = J[k][0] * cm.R[2] + J[k][1] * cm.R[5] + J[k][2] * cm.R[8];
-    }
-  }
-  return zc > 0.0;
-}
 
 template <bool PINHOLE>
 struct CheetahPxFit : CheetahCore<PxLds> {
@@ -285,22 +258,15 @@ int acino_cheetah_pose_fit_px(const acino_pose_fit_px_params* prm, const double*
                               uint8_t* d_status, uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x, double* d_pos,
                               double* d_cov_pos, double* d_std_pos, double* d_weight, void* stream) {
   ACINO_REQUIRE(prm != nullptr, "prm");
-  ACINO_REQUIRE(n_cams >= 1 && n_cams <= ACINO_MAX_CAMS, "n_cams must be 1..16");
-  ACINO_REQUIRE(prm->camera_model == 0 || prm->camera_model == 1, "camera_model must be 0 (fisheye) or 1 (pinhole)");
-  const acino_pose_fit_params fit = {prm->max_iter, prm->min_detections, prm->lam0, prm->ftol, prm->xtol, prm->prior_sigma, 1.0};
-  if (int rc = pf_check_params(&fit, n_frames, ACINO_N_MARKERS * n_cams, "min_detections must be 1..20 n_cams")) return rc;
-  ACINO_REQUIRE(prm->thresh == prm->thresh, "thresh must not be NaN");
-  ACINO_REQUIRE(prm->f_scale > 0 && prm->f_scale < INFINITY, "f_scale must be > 0");
-  ACINO_REQUIRE(prm->sigma_px > 0 && prm->sigma_px < INFINITY, "sigma_px must be > 0");
+  acino_pose_fit_params fit;
+  if (int rc = px_check_params(prm, n_frames, n_cams, ACINO_N_MARKERS, "min_detections must be 1..20 n_cams", fit)) return rc;
   if (n_frames == 0) return ACINO_OK;
   ACINO_REQUIRE(d_det && d_cams && d_x0 && d_x && d_status, "null buffer (d_det, d_cams, d_x0, d_x, d_status)");
   PoseFitIo a;
   pf_fill_io(a, &fit, nullptr, nullptr, d_x0, n_frames, d_x, d_cost, nullptr, d_status, d_iters, d_pinned, d_cov_x, d_pos,
              d_cov_pos, d_std_pos);
   PxArgs b;
-  b.det = d_det, b.cams = d_cams, b.n_cams = n_cams, b.thresh = prm->thresh;
-  b.fs2 = prm->f_scale * prm->f_scale, b.ifs2 = 1.0 / b.fs2, b.inv_sigma = 1.0 / prm->sigma_px;
-  b.ndet = d_ndet, b.weight = d_weight;
+  px_fill_args(b, prm, d_det, d_cams, n_cams, d_ndet, d_weight);
   const int grid = grid_for(n_frames, 1);       // one frame per workgroup pass, grid-stride beyond the cap
   const size_t record = prm->camera_model == 1 ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE;
   const size_t dyn = (size_t)n_cams * (record + ACINO_N_MARKERS * 3) * sizeof(double);    // at most 11 776 bytes: no opt-in needed

@@ -6,7 +6,8 @@
 // with FK the link program of SkelDev, W_l = S_l^-1 (or I / sigma_iso^2) and m the start clipped to the box, by the projected
 // Levenberg-Marquardt that pose_fit.hip runs too: one definition, pf_fit_frame<PT> of pose_fit_dev.hpp (active set,
 // damped step on the free states, Nielsen's rule, the stops, the status codes, the stores and cov_pos), instantiated here with
-// the model SkelFit<PT>: FK and Jacobian of the link program, the Gram product, where the factor is stored, cov_x, the LDS.
+// the model SkelFit<PT>: SkelCore<PT> of pose_fit_skel.hpp (FK and Jacobian of the link program, the Gram product, where the
+// factor is stored, cov_x - what skel_pose_fit_px.hip's model shares) plus the 3-D measurement and the LDS layout of this file.
 //
 // One 64-lane wave per frame, one wave per workgroup, a grid-stride loop over the frames, no atomics: every barrier is
 // wave-wide and nothing waits on another workgroup.  The kernel is a template on PT = 16, 32, 48, 64 (P rounded up to 16):
@@ -27,8 +28,7 @@
 // (with a second register set for the columns of the inverse, PT = 64 spilled to scratch) and the product runs on the matrix
 // cores as A's does.  The shipped human skeleton (P = 36, n_pose = 15) takes 42 KB, the largest
 // shape the limits allow (P = 64, n_pose = 65) 157 KB; a shape beyond 160 KB is refused.
-#include "pose_fit_dev.hpp"
-#include "skel_host.hpp"
+#include "pose_fit_skel.hpp"
 
 namespace acino {
 
@@ -72,80 +72,6 @@ __host__ __device__ inline SpfLayout spf_layout(int P, int PT, int n_pose, int n
   return L;
 }
 
-struct Spf {                       // the carved LDS of one workgroup
-  double *Jw, *M, *y, *U, *u, *rest, *pos, *opv, *x, *xt, *m, *g, *lo, *hi, *red;
-  unsigned long long *pm, *opm, *cm;   // per slot: the ops on its path; per state: the ops that hang on it, the slots it moves [2]
-  int *axs, *ent;                  // per state: its axis (0 phi, 1 theta, 2 psi); per slot: does its point enter
-  int P, n_pose, n_ops, ldj, ldm, ks;
-};
-
-// The lane index again, opaque to the optimiser: what a loop body derives from it (LDS addresses, the selects of an unrolled
-// row) then stays inside the body.  Hoisted out of the frame loop, hundreds of such values outlive every register and are
-// spilled to scratch.
-__device__ __forceinline__ int spf_here(int lane) {
-  asm volatile("" : "+v"(lane));
-  return lane;
-}
-
-// M off, dM/dphi off, dM/dtheta off, dM/dpsi off of op k at the states xs: the statements of k_skel_assemble
-__device__ __forceinline__ void spf_link_op(const SkelDev& D, int k, const double* xs, double* out) {
-  const acino_skel_op& o = D.op[k];
-  const int f = o.flags;
-  double sp = 0, cp = 1, st = 0, ct = 1, sz = 0, cz = 1;
-  if (f & 1) sincos(D.amap[k][0] >= 0 ? xs[D.amap[k][0]] : 0.0, &sp, &cp);
-  if (f & 2) sincos(D.amap[k][1] >= 0 ? xs[D.amap[k][1]] : 0.0, &st, &ct);
-  if (f & 4) sincos(D.amap[k][2] >= 0 ? xs[D.amap[k][2]] : 0.0, &sz, &cz);
-  const double Ry[3][3] = {{ct, 0, -st}, {0, 1, 0}, {st, 0, ct}}, dRy[3][3] = {{-st, 0, -ct}, {0, 0, 0}, {ct, 0, -st}};
-  const double Rx[3][3] = {{1, 0, 0}, {0, cp, sp}, {0, -sp, cp}}, dRx[3][3] = {{0, 0, 0}, {0, -sp, cp}, {0, -cp, -sp}};
-  const double Rz[3][3] = {{cz, sz, 0}, {-sz, cz, 0}, {0, 0, 1}}, dRz[3][3] = {{-sz, cz, 0}, {-cz, -sz, 0}, {0, 0, 0}};
-  auto mul = [](const double (&a)[3][3], const double (&b)[3][3], double (&c)[3][3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) c[i][j] = a[i][0] * b[0][j] + a[i][1] * b[1][j] + a[i][2] * b[2][j];
-  };
-  double RxRy[3][3], M[4][3][3], T1[3][3];
-  mul(Rx, Ry, RxRy);
-  mul(Rz, RxRy, M[0]);
-  mul(dRx, Ry, T1);
-  mul(Rz, T1, M[1]);
-  mul(Rx, dRy, T1);
-  mul(Rz, T1, M[2]);
-  mul(dRz, RxRy, M[3]);
-  const bool untr = (f & 8) != 0;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const bool on = m == 0 || ((f >> (m - 1)) & 1);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      double v = 0.0;
-      if (on)
-        v = untr ? M[m][i][0] * o.off[0] + M[m][i][1] * o.off[1] + M[m][i][2] * o.off[2]
-                 : M[m][0][i] * o.off[0] + M[m][1][i] * o.off[1] + M[m][2][i] * o.off[2];
-      out[m * 3 + i] = v;
-    }
-  }
-}
-
-// the link operators and the poses of ``xv`` into S.opv and S.pos
-__device__ __forceinline__ void spf_frame(const Spf& S, const SkelDev& D, const double* xv, int lane) {
-  lane = spf_here(lane);
-  if (lane < S.n_ops) spf_link_op(D, lane, xv, S.opv + lane * 12);
-  __syncthreads();
-  for (int t = lane; t < 3 * S.n_pose; t += 64) {
-    const int l = t / 3, c = t - 3 * l;
-    double v = xv[c];
-    unsigned long long path = S.pm[l];
-    while (path) {
-      const int k = __ffsll((long long)path) - 1;
-      path &= path - 1;
-      v = v + S.opv[k * 12 + c];
-    }
-    S.pos[t] = v;
-  }
-  __syncthreads();
-}
-
 // F(xv) of the poses S.pos: the whitened residuals into S.u, the sum in a fixed order (the same value in every lane)
 __device__ __forceinline__ double spf_cost(const Spf& S, const double* xv, double kappa, int lane) {
   for (int l = lane; l < S.n_pose; l += 64) {
@@ -166,87 +92,6 @@ __device__ __forceinline__ double spf_cost(const Spf& S, const double* xv, doubl
   for (int k = 0; k < S.n_pose + S.P - 3; ++k) f += S.red[k];
   __syncthreads();
   return f;
-}
-
-// Jw = U G (RAW: G itself, every slot) from S.opv, zero outside the slots a column moves
-template <bool RAW>
-__device__ __forceinline__ void spf_jacobian(const Spf& S, int lane) {
-  lane = spf_here(lane);
-  const int T = S.P * S.n_pose;
-  for (int t = lane; t < T; t += 64) {
-    const int p = t / S.n_pose, l = t - p * S.n_pose;
-    double w0 = 0.0, w1 = 0.0, w2 = 0.0;
-    unsigned long long mk = p < 3 ? 0ull : (S.opm[p] & S.pm[l]);
-    if ((p < 3 || mk) && (RAW || S.ent[l])) {
-      double j0 = p == 0 ? 1.0 : 0.0, j1 = p == 1 ? 1.0 : 0.0, j2 = p == 2 ? 1.0 : 0.0;
-      const double* dv0 = S.opv + (1 + S.axs[p]) * 3;
-      while (mk) {
-        const int k = __ffsll((long long)mk) - 1;
-        mk &= mk - 1;
-        const double* dv = dv0 + k * 12;
-        j0 += dv[0];
-        j1 += dv[1];
-        j2 += dv[2];
-      }
-      if (RAW) {
-        w0 = j0, w1 = j1, w2 = j2;
-      } else {
-        const double* U = S.U + 6 * l;
-        w0 = U[0] * j0;
-        w1 = U[1] * j0 + U[2] * j1;
-        w2 = U[3] * j0 + U[4] * j1 + U[5] * j2;
-      }
-    }
-    double* o = S.Jw + p * S.ldj + 3 * l;
-    o[0] = w0;
-    o[1] = w1;
-    o[2] = w2;
-  }
-  __syncthreads();
-}
-
-// The lower tiles of W^T-style products on the fp64 matrix cores: result[r][c] = sum_j W[r][j] W[c][j] over j < 4 ks for the
-// rows r, c < P of W (leading dimension ld; rows beyond P count as zeros).  Lane (i, k) = (lane & 15, lane >> 4) feeds
-// W[16 a + i][4 s + k] for every tile row a and holds result[16 a + 4 r + k][16 b + i] of tile (a, b) in register r;
-// store(row, col, value) is called for every entry with col <= row < PT (zeros beyond P).
-template <int PT, class Store>
-__device__ __forceinline__ void spf_gram(const double* W, int ld, int ks, int P, int lane, Store&& store) {
-  lane = spf_here(lane);
-  constexpr int NTL = PT / 16;
-  const int i = lane & 15, k = lane >> 4;
-  const double* pr[NTL];
-  bool in[NTL];
-#pragma unroll
-  for (int a = 0; a < NTL; ++a) {
-    in[a] = 16 * a + i < P;
-    pr[a] = W + (in[a] ? 16 * a + i : 0) * ld + k;
-  }
-  d4 acc[NTL * (NTL + 1) / 2];
-#pragma unroll
-  for (int t = 0; t < NTL * (NTL + 1) / 2; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-  for (int s = 0; s < ks; ++s) {
-    double v[NTL];
-#pragma unroll
-    for (int a = 0; a < NTL; ++a) {
-      const double h = pr[a][4 * s];
-      v[a] = in[a] ? h : 0.0;
-    }
-    int t = 0;
-#pragma unroll
-    for (int a = 0; a < NTL; ++a)
-#pragma unroll
-      for (int b = 0; b <= a; ++b) acc[t] = mfma(v[a], v[b], acc[t]), ++t;
-  }
-  int t = 0;
-#pragma unroll
-  for (int a = 0; a < NTL; ++a)
-#pragma unroll
-    for (int b = 0; b <= a; ++b, ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * a + 4 * r + k, col = 16 * b + i;
-        if (a > b || col <= row) store(row, col, acc[t][r]);
-      }
 }
 
 // A = Jw^T Jw + diag(kappa) into the lower triangle of S.M (spf_gram over the 3 n_pose rows of Jw).  A column of zeros (a
@@ -277,46 +122,22 @@ __device__ __forceinline__ void spf_normal(const Spf& S, double kappa, unsigned 
   __syncthreads();
 }
 
-// X = L^-1 in place of the factor: afterwards lane i holds X[i][c] = r[c] * dinv for c < i and X[i][i] = dinv.  Step k
-// broadcasts the finished row k and every later row takes its multiple; r[k] is read for the last time in step k and takes
-// the new column's entry, so the inverse needs no registers beyond the factor's.
+// a link program seen as 3-D points: SkelCore of pose_fit_skel.hpp plus the measurement - the whitened residuals and their
+// sum, Jw = U G and the Gram product over the entering slots
 template <int PT>
-__device__ __forceinline__ void spf_invert_factor(double (&r)[PT], double dinv, int lane) {
-  lane = spf_here(lane);
-#pragma unroll
-  for (int k = 0; k < PT; ++k) {
-    const double lik = r[k], xkk = pf_readlane(dinv, k);
-#pragma unroll
-    for (int c = 0; c < k; ++c) {
-      const double xkc = pf_readlane(r[c] * dinv, k);
-      r[c] = lane > k ? r[c] - lik * xkc : r[c];
-    }
-    r[k] = lane > k ? -lik * xkk : r[k];
-  }
-}
-
-// a link program as a model of pf_fit_frame (pose_fit_dev.hpp): the frame's box from the caller, one set of link operators and
-// poses (the trial's: the returned point's are evaluated again for the outputs), A and the factor in S.M
-template <int PT>
-struct SkelFit {
-  static constexpr int RED2 = SK_MAXP;
-  const Spf& S;
-  const SkelDev& D;
+struct SkelFit : SkelCore<PT> {
+  typedef SkelCore<PT> Core;
+  using Core::D;
+  using Core::lane;
+  using Core::S;
   const double kappa;
-  const int lane;
   const unsigned long long em0, em1;
 
-  __device__ __forceinline__ int n_states() const { return S.P; }
-  __device__ __forceinline__ int n_slots() const { return S.n_pose; }
-  __device__ __forceinline__ double* x() const { return S.x; }
-  __device__ __forceinline__ double* xt() const { return S.xt; }
-  __device__ __forceinline__ double* m() const { return S.m; }
-  __device__ __forceinline__ double* g() const { return S.g; }
-  __device__ __forceinline__ double* red() const { return S.red; }
-  __device__ __forceinline__ double* cp() const { return S.y; }             // (y, U, u are not read by then)
+  __device__ __forceinline__ SkelFit(const Spf& S_, const SkelDev& D_, double kappa_, int lane_, unsigned long long em0_,
+                                     unsigned long long em1_)
+      : Core{S_, D_, lane_}, kappa(kappa_), em0(em0_), em1(em1_) {}
 
-  __device__ __forceinline__ double lo(int p) const { return S.lo[p]; }
-  __device__ __forceinline__ double hi(int p) const { return S.hi[p]; }
+  __device__ __forceinline__ double* cp() const { return S.y; }             // (y, U, u are not read by then)
 
   __device__ __forceinline__ double eval(const double* xv, bool) {
     spf_frame(S, D, xv, lane);
@@ -327,67 +148,9 @@ struct SkelFit {
     spf_normal<PT>(S, kappa, em0, em1, lane);
   }
   __device__ __forceinline__ void accepted() {}
-  __device__ __forceinline__ double diag(int p) const { return S.M[p * (PT + 1) + p]; }
-  // the active set at S.x, one bit per state: at a bound with the gradient pushing outward
-  __device__ __forceinline__ unsigned long long active_set(int lane) const {
-    bool fixed = false;
-    if (lane < S.P) fixed = skel_fixed(S.x[lane], S.g[lane], S.M[lane * S.ldm + lane], S.lo[lane], S.hi[lane]);
-    return __ballot(fixed);
-  }
-
-  // pf_factor_rows with identity rows P .. PT-1; the strict lower triangle goes to S.M above the diagonal, L[k][c] at
-  // M[c][k + 1], for the back substitution
-  __device__ __forceinline__ bool factor(unsigned long long fixmask, double lam, int lane, double (&r)[PT], double& dinv) {
-    lane = spf_here(lane);
-    const unsigned long long fix = fixmask | (S.P >= 64 ? 0ull : ~0ull << S.P);
-    const bool ok = pf_factor_rows<PT, PT + 1, true>(S.M, fix, lam, lane, r, dinv);
-    __syncthreads();                              // (the readers of the previous factor are done)
-    if (lane < S.P) {
-#pragma unroll
-      for (int c = 0; c < PT - 1; ++c)
-        if (c < lane) S.M[c * (PT + 1) + lane + 1] = r[c];
-    }
-    __syncthreads();
-    return ok;
-  }
-  // pf_solve, its back substitution on the columns of L^T in S.M
-  __device__ __forceinline__ double solve(const double (&r)[PT], double dinv, double v, int lane) const {
-    lane = spf_here(lane);
-    const int col = lane < S.P ? lane : 0;
-    return pf_solve<PT, true>(r, dinv, v, lane, S.P, [&](int k) { return S.M + col * (PT + 1) + k + 1; });      // (rows P .. PT-1 are the identity's)
-  }
-
-  // cov_x = X^T X with X = L^-1: the rows of X from the registers into S.Jw as columns (W[p][i] = X[i][p], zero above the
-  // diagonal and in the padding rows), the product on the matrix cores into S.M - neither A nor the factor is read again -,
-  // mirrored, so symmetric bit for bit, the rows and columns of pinned states exactly 0
-  __device__ __forceinline__ bool cov_x(unsigned long long fixmask, double (&r)[PT], double dinv, int lane) {
-    const int P = S.P;
-    spf_invert_factor<PT>(r, dinv, lane);
-    lane = spf_here(lane);
-    const int kpad = (P + 3) & ~3;
-    if (lane < kpad) {
-#pragma unroll
-      for (int p = 0; p < PT; ++p)
-        if (p < P) S.Jw[p * S.ldj + lane] = lane >= P || p > lane ? 0.0 : (p == lane ? dinv : r[p] * dinv);
-    }
-    __syncthreads();
-    bool fin = true;
-    spf_gram<PT>(S.Jw, S.ldj, kpad / 4, P, lane, [&](int row, int col, double v) {
-      if (((fixmask >> row) | (fixmask >> col)) & 1ull) v = 0.0;
-      fin = fin && m_finite(v);
-      S.M[row * (PT + 1) + col] = v;
-      S.M[col * (PT + 1) + row] = v;
-    });
-    return __all(fin);
-  }
   __device__ __forceinline__ void outputs_at_x(bool live) {
     if (live) spf_frame(S, D, S.x, lane);          // (S.opv and S.pos hold the last trial's, which may have been refused)
   }
-  __device__ __forceinline__ double pos(int t) const { return S.pos[t]; }
-  __device__ __forceinline__ double cov(int p, int q) const { return S.M[p * (PT + 1) + q]; }
-  __device__ __forceinline__ void jacobian_raw(int lane) { spf_jacobian<true>(S, lane); }
-  __device__ __forceinline__ double jw(int p, int row) const { return S.Jw[p * S.ldj + row]; }
-  __device__ __forceinline__ bool moves(int p, int l) const { return (S.cm[2 * p + (l >> 6)] >> (l & 63)) & 1ull; }
 };
 
 template <int PT>
@@ -410,7 +173,9 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit(SkelPoseFitArgs a) {
   S.ent = reinterpret_cast<int*>(base + lay.ent);
   S.P = P, S.n_pose = NPOSE, S.n_ops = NOPS, S.ldj = lay.ldj, S.ldm = lay.ldm, S.ks = (R3 + 3) / 4;
 
-  // ---- once per workgroup: the op and slot masks of every state, the rest pose
+  // ---- once per workgroup: the op and slot masks of every state, the rest pose.  The masks are the twin of spf_masks
+  //      (pose_fit_skel.hpp), kept here as text: called as that function the same statements come out in another register
+  //      order and this kernel measured 0.08 to 0.19 ms slower on the 6 240 frames of the shipped video (NOTES_perf.md).
   for (int l = lane; l < NPOSE; l += 64) S.pm[l] = D.pmask[l];
   {
     unsigned long long om = 0;
@@ -484,20 +249,6 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit(SkelPoseFitArgs a) {
     pf_fit_frame<PT>(m, io, n, lane, n_enter);
   }
 }
-
-// the params block of skel_program with the four fields this entry reads, everything else at a value skel_validate accepts
-static acino_skel_fte_params spf_params(const acino_skel_fte_params* p) {
-  acino_skel_fte_params q;
-  memset(&q, 0, sizeof(q));
-  q.n_frames = 1, q.n_cams = 1;
-  q.n_pose = p->n_pose, q.n_ops = p->n_ops, q.n_angles = p->n_angles, q.n_active = p->n_active;
-  q.loss = ACINO_SKEL_LOSS_L1;
-  q.h = 1.0, q.l1_eps = 1e-2, q.lam0 = 1e-3;
-  return q;
-}
-
-constexpr size_t SPF_LDS_MAX = 160 * 1024;
-static size_t spf_ws_clip() { return skel_align256(sizeof(SkelDev)); }
 
 }  // namespace acino
 

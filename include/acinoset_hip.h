@@ -21,6 +21,7 @@
  *   acino_skel_pose_fit              (no counterpart) the same for a skeleton's link program (acino_skel_fte_*)
  *   acino_cheetah_pose_fit_px        (no counterpart) per-frame pose with error bars from the detections themselves: the
  *                                    reprojection error of the skeleton in every camera, robust weight per coordinate
+ *   acino_skel_pose_fit_px           (no counterpart) the same for a skeleton's link program
  *   acino_cheetah_fk                 pose_to_3d                       src/all_optimizations.py:66-190
  *   acino_fte_*                      the Pyomo model + opt.solve()    src/all_optimizations.py:283-556
  *
@@ -1028,6 +1029,31 @@ int acino_skel_pose_fit(const acino_pose_fit_params* prm, const acino_skel_fte_p
                         const double* d_lo, const double* d_hi /* [N][P] */, int64_t n_frames, double* d_x, double* d_cost,
                         uint8_t* d_nmarkers, uint8_t* d_status, uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x,
                         double* d_pos, double* d_cov_pos, double* d_std_pos, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ---- per-frame pose of a skeleton from the detections of every camera (csrc/skel_pose_fit_px.hip) ------------------
+ * acino_cheetah_pose_fit_px for a link program: per frame the minimiser, over the P = n_active states inside the frame's
+ * box d_lo[n] <= x <= d_hi[n], of
+ *   F(x) = 1/sigma_px^2 sum_{(c,l) valid} sum_{k in (u,v)} 1/2 f^2 log1p(r_k^2 / f^2) + 1/2 sum_{p >= 3} (x_p - m_p)^2 / prior_sigma^2
+ * with r = pi_c(FK_l(x)) - d_det[n][c][l][0..1], FK the link program, pi_c the calibration-level projection of
+ * acino_triangulate_multiview, f = f_scale, m the start clipped to the box; a detection (x, y, likelihood) is valid when its
+ * likelihood is above thresh and both pixel values are finite.  The controller, the status codes and the outputs are
+ * acino_skel_pose_fit's, the parameter block, d_cams (n_cams records of the stated camera model), d_ndet and d_weight
+ * acino_cheetah_pose_fit_px's with n_pose slots in place of the 20 markers: min_detections in 1..n_pose n_cams,
+ *   d_det[N][C][n_pose][3], d_ndet[N] uint16, d_weight[N][C][n_pose][2] (exactly 0 for an invalid detection, NaN for status
+ *   2 and 3).
+ * d_x0 [N][P] is required: there is no triangulated point to derive a start from.  ``reserved`` of the block: 0; bit 0 set
+ * makes the kernel sum the gradient state by state even where it could take it from the matrix product (same minimiser,
+ * other rounding; a measurement switch).  Any output but d_x and d_status may be NULL.  d_ws:
+ * acino_skel_pose_fit_px_workspace_bytes(p) bytes, 256-byte aligned (0: p is outside the limits).  A shape whose LDS exceeds
+ * 160 KB is refused.  Argument validation happens before any device call; n_frames == 0 is a no-op.  One launch (one 64-lane
+ * wave per frame), no synchronisation. */
+size_t acino_skel_pose_fit_px_workspace_bytes(const acino_skel_fte_params* p);
+int acino_skel_pose_fit_px(const acino_pose_fit_px_params* prm, const acino_skel_fte_params* p, const acino_skel_op* h_ops,
+                           const int32_t* h_active, const double* d_det /* [N][C][n_pose][3] */, int64_t n_frames, int n_cams,
+                           const double* d_cams, const double* d_x0 /* [N][P] */, const double* d_lo,
+                           const double* d_hi /* [N][P] */, double* d_x, double* d_cost, uint16_t* d_ndet, uint8_t* d_status,
+                           uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x, double* d_pos, double* d_cov_pos,
+                           double* d_std_pos, double* d_weight, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
