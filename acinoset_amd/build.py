@@ -763,6 +763,27 @@ def _check_init(init):
         raise ValueError(f"init must be 'line' or 'pose_fit' (got {init!r})")
 
 
+def _skel_workspace(model, act, workspace_bytes):
+    """The params block of a per-frame fit and the bytes ``workspace_bytes`` asks for it; ValueError when it refuses the shape."""
+    p = _skel_params(model, len(act))
+    nbytes = workspace_bytes(C.byref(p))
+    if nbytes == 0:
+        raise ValueError("problem outside the kernel limits (n_active <= 64)")
+    return p, nbytes
+
+
+def _skel_fit_call(model, act, dev, sized, call):
+    """The skeleton's side of a per-frame fit's library call: the boxes at the columns ``act`` on the device, ``sized`` (the pair
+    of ``_skel_workspace``), the workspace aligned to 256 bytes, the active states as int32.  ``call(skel, box, ws)`` returns the
+    status: ``skel`` = (params, ops, active), ``box`` = (lo, hi), ``ws`` = (workspace, its bytes, stream)."""
+    p, nbytes = sized
+    lo, hi = calib._to_dev(model.lo[:, act], dev), calib._to_dev(model.hi[:, act], dev)
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)      # (it goes back to the allocator of this very stream)
+    act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
+    check(call((C.byref(p), _ops_array(model.prog), act_c), (ptr(lo), ptr(hi)),
+               (C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr())))
+
+
 def pose_fit(model, points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01, min_markers=1, max_iter=100, ftol=1e-10,
              xtol=1e-10, lam0=1e-3, return_cov=True):
     """Per-frame pose of a ``SkeletonModel`` from 3-D points with a covariance each (include/acinoset_hip.h:
@@ -795,15 +816,8 @@ def pose_fit(model, points, cov=None, x0=None, prior_sigma=np.pi, sigma_iso=0.01
     N, Pa, Lp = model.N, len(act), len(model.names)
 
     def launch(prm, dev, N, ins, outs):
-        lo, hi = calib._to_dev(model.lo[:, act], dev), calib._to_dev(model.hi[:, act], dev)
-        p = _skel_params(model, Pa)
-        nbytes = lib().acino_skel_pose_fit_workspace_bytes(C.byref(p))
-        if nbytes == 0:
-            raise ValueError("problem outside the kernel limits (n_active <= 64)")
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)      # (it goes back to the allocator of this very stream)
-        act_c = (C.c_int32 * Pa)(*[int(a) for a in act])
-        check(lib().acino_skel_pose_fit(prm, C.byref(p), _ops_array(model.prog), act_c, *ins, ptr(lo), ptr(hi), N, *outs,
-                                        C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
+        _skel_fit_call(model, act, dev, _skel_workspace(model, act, lib().acino_skel_pose_fit_workspace_bytes),
+                       lambda skel, box, ws: lib().acino_skel_pose_fit(prm, *skel, *ins, *box, N, *outs, *ws))
 
     return fte._pose_fit(launch, points, cov, x0, N, Lp, act, model.P,
                          (f"points must be [{N}, {Lp}, 3] (model.N frames, one slot per pose)", f"cov must be [{N}, {Lp}, 3, 3]",
@@ -896,50 +910,32 @@ def pose_fit_pixels(model, x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=
     numpy in, numpy out; a CUDA tensor as ``det`` or ``x0`` gives CUDA tensors out, with no host copy when ``x0`` is given."""
     act = np.asarray(model.active, dtype=np.int32)
     N, Pa, Lp, Cn = model.N, len(act), len(model.names), int(np.shape(model.meas)[1])
-    camera_model = getattr(model, "camera_model", "fisheye")
-    if camera_model not in calib.CAMERAS:
-        raise ValueError(f"the model's camera_model must be one of {calib.CAMERA_MODELS}")
-    if det is not None and fte._shape(det) != (N, Cn, Lp, 3):
-        raise ValueError(f"det must be [{N}, {Cn}, {Lp}, 3] (model.N frames, the model's cameras, one slot per pose)")
-    if not 1 <= Cn <= _lib.MAX_CAMS:
-        raise ValueError(f"the model holds {Cn} cameras: 1..{_lib.MAX_CAMS} are supported")
-    if x0 is not None and fte._shape(x0) != (N, Pa):
-        raise ValueError(f"x0 must be [{N}, {Pa}] (the active states)")
-    if sigma_px is None:
-        sigma_px = _model_sigma_px(model)
-    fte._fit_checks((("prior_sigma", prior_sigma), ("f_scale", f_scale), ("sigma_px", sigma_px), ("ftol", ftol), ("xtol", xtol),
-                     ("lam0", lam0)), max_iter, "min_detections", min_detections, Lp * Cn)
-    if np.isnan(thresh):
-        raise ValueError("thresh must not be NaN")
-    recs = calib.camera_records(camera_model, model.K, model.D, model.R, model.t)
-    tensors = isinstance(det, torch.Tensor) or isinstance(x0, torch.Tensor)
-    dev = calib._dev()
-    p = _skel_params(model, Pa)
-    nbytes = lib().acino_skel_pose_fit_px_workspace_bytes(C.byref(p))
-    if nbytes == 0:
-        raise ValueError("problem outside the kernel limits (n_active <= 64)")
-    d = calib._to_dev(_model_detections(model) if det is None else det, dev)
-    if x0 is None:
+
+    def start(d):
         init_x = _pose_fit_start(model, {})
         if init_x is None:
             raise ValueError("no frame has a pose fit to start from (no slot was triangulated in the whole clip): pass x0")
-        x0 = init_x[:, act]
-    xs = calib._to_dev(x0, dev)
-    lo, hi = calib._to_dev(model.lo[:, act], dev), calib._to_dev(model.hi[:, act], dev)
-    cams = torch.as_tensor(recs, device=dev)
-    o = fte._fit_outputs(N, Pa, Lp, dev, return_cov)
-    nd = torch.empty((N,), dtype=torch.uint16, device=dev)
-    weight = torch.empty((N, Cn, Lp, 2), dtype=torch.float64, device=dev)
-    prm = _lib.PoseFitPxParams(calib.CAMERAS[camera_model].code, int(max_iter), int(min_detections), 0, float(lam0), float(ftol),
-                               float(xtol), float(prior_sigma), float(thresh), float(f_scale), float(sigma_px))
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)      # (it goes back to the allocator of this very stream)
-    act_c = (C.c_int32 * Pa)(*[int(a) for a in act])
-    check(lib().acino_skel_pose_fit_px(prm, C.byref(p), _ops_array(model.prog), act_c, ptr(d), N, Cn, ptr(cams), ptr(xs), ptr(lo),
-                                       ptr(hi), *(ptr(t) for t in (o["x"], o["cost"], nd, o["status"], o["iters"], o["pinned"],
-                                                                   o["cov_x"], o["positions"], o["cov_positions"],
-                                                                   o["std_positions"], weight)),
-                                       C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
-    return fte._fit_dict(o, "n_detections", nd, act, model.P, tensors, weight=weight)
+        return init_x[:, act]
+
+    sized = []
+
+    def ready(dev):                                          # (the workspace's refusal comes before anything is staged)
+        sized.append(_skel_workspace(model, act, lib().acino_skel_pose_fit_px_workspace_bytes))
+
+    def launch(prm, dev, N, Cn, ins, outs):
+        _skel_fit_call(model, act, dev, sized[0],
+                       lambda skel, box, ws: lib().acino_skel_pose_fit_px(prm, *skel, ins[0], N, Cn, *ins[1:], *box, *outs, *ws))
+
+    texts = dict(camera_model=f"the model's camera_model must be one of {calib.CAMERA_MODELS}",
+                 det=f"det must be [{N}, {Cn}, {Lp}, 3] (model.N frames, the model's cameras, one slot per pose)",
+                 cams="the model holds {} cameras: 1..{} are supported", x0=f"x0 must be [{N}, {Pa}] (the active states)")
+    return fte._pose_fit_px(launch, (lambda: _model_detections(model)) if det is None else det, x0, start, shape=(N, Cn, Lp),
+                            active=act, n_full=model.P, camera_model=getattr(model, "camera_model", "fisheye"),
+                            rig=(model.K, model.D, model.R, model.t), texts=texts, ready=ready,
+                            tensors=isinstance(det, torch.Tensor) or isinstance(x0, torch.Tensor), thresh=thresh, f_scale=f_scale,
+                            sigma_px=(lambda: _model_sigma_px(model)) if sigma_px is None else sigma_px, prior_sigma=prior_sigma,
+                            min_detections=min_detections, max_iter=max_iter, ftol=ftol, xtol=xtol, lam0=lam0,
+                            return_cov=return_cov)
 
 
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,

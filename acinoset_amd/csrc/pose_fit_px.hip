@@ -8,7 +8,7 @@
 // IRLS weight w = 1 / (1 + r_k^2 / f^2), J = (J_pi R_c) J_FK; the same A serves step, predicted reduction, active set and
 // outputs, so the frame after its prologue is pf_fit_frame<25> of pose_fit_dev.hpp as pose_fit.hip runs it, and this file is its
 // third model, CheetahPxFit: CheetahCore of pose_fit_cheetah.hpp (FK frames, raw marker Jacobian, register-resident factor,
-// cov_x) plus the measurement.
+// cov_x) plus the measurement, whose arithmetic is pose_fit_px_dev.hpp's, shared with skel_pose_fit_px.hip.
 //
 // One 64-lane wave per frame, one launch, a grid-stride loop over the frames.  Static LDS 34 016 bytes: two FK frames, the raw
 // J_FK as 25 columns of 60, one camera's weighted rows Jc as 26 columns of 40 (the rows of the Cholesky factor lie over them:
@@ -84,20 +84,9 @@ struct CheetahPxFit : CheetahCore<PxLds> {
     for (int t = lane; t < pairs; t += 64) {
       const int c = t / NL, l = t - c * NL;
       if (!((S.vmask[c] >> l) & 1u)) continue;
-      double uv[2];
-      behind = !px_project<false>(cams[c], T.pos[l], uv, nullptr) || behind;
-      const double* d = &det[(c * NL + l) * 3];
-      const double r0 = uv[0] - d[0], r1 = uv[1] - d[1];
-      part += 0.5 * b.fs2 * (log1p(r0 * r0 * b.ifs2) + log1p(r1 * r1 * b.ifs2));
+      part += px_pair_cost(b, cams[c], T.pos[l], det, t, behind);
     }
-    part *= b.inv_sigma * b.inv_sigma;
-    if (lane >= 3 && lane < NP) {
-      const double e = xv[lane] - S.m[lane];
-      part += 0.5 * kappa * e * e;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
-    return __any(behind) ? __builtin_huge_val() : part;
+    return px_cost_finish(part, xv, S.m, kappa, NP, lane, b, behind);
   }
 
   // J_FK, then A and g at S.x camera by camera
@@ -115,20 +104,7 @@ struct CheetahPxFit : CheetahCore<PxLds> {
       if (cg < PX_GROUP) {
         const int c = c0 + cg;
         double jr[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, u[2] = {0.0, 0.0};
-        if (c < b.n_cams && ((S.vmask[c] >> lg) & 1u)) {
-          double uv[2], JR[2][3];
-          px_project<true>(cams[c], F.pos[lg], uv, JR);
-          const double* d = &det[(c * NL + lg) * 3];
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            const double r = uv[k] - d[k];
-            const double sw = sqrt(rcp64(1.0 + r * r * b.ifs2)) * b.inv_sigma;
-            jr[3 * k] = sw * JR[k][0];
-            jr[3 * k + 1] = sw * JR[k][1];
-            jr[3 * k + 2] = sw * JR[k][2];
-            u[k] = sw * r;
-          }
-        }
+        if (c < b.n_cams && ((S.vmask[c] >> lg) & 1u)) px_pair_rows(b, cams[c], F.pos[lg], det, NL, c, lg, jr, u);
 #pragma unroll
         for (int k = 0; k < 6; ++k) S.jr[cg][lg][k] = jr[k];
         S.ur[cg][2 * lg] = u[0];
@@ -182,25 +158,8 @@ struct CheetahPxFit : CheetahCore<PxLds> {
 
   // the count of valid detections and, at the returned x (F[cur]), the weight every coordinate ended with
   __device__ __forceinline__ void outputs_at_x(bool live) {
-    if (lane == 0 && b.ndet) b.ndet[n] = (uint16_t)n_det;
-    if (!b.weight) return;
-    const CovFrame& F = S.F[cur];
-    const int pairs = NL * b.n_cams;
-    double* out = b.weight + n * pairs * 2;
-    for (int t = lane; t < pairs; t += 64) {
-      const int c = t / NL, l = t - c * NL;
-      double w0 = live ? 0.0 : __builtin_nan(""), w1 = w0;
-      if (live && ((S.vmask[c] >> l) & 1u)) {
-        double uv[2];
-        px_project<false>(cams[c], F.pos[l], uv, nullptr);
-        const double* d = &det[(c * NL + l) * 3];
-        const double r0 = uv[0] - d[0], r1 = uv[1] - d[1];
-        w0 = rcp64(1.0 + r0 * r0 * b.ifs2);
-        w1 = rcp64(1.0 + r1 * r1 * b.ifs2);
-      }
-      out[2 * t] = w0;
-      out[2 * t + 1] = w1;
-    }
+    px_store_outputs(b, cams, det, NL, n, n_det, live, lane, [&](int c, int l) { return (S.vmask[c] >> l) & 1u; },
+                     [&](int l) { return S.F[cur].pos[l]; });
   }
 };
 
@@ -227,7 +186,7 @@ __global__ void __launch_bounds__(64) k_pose_fit_px(PoseFitIo a, PxArgs b) {
       bool valid = false;
       if (lane < NL) {
         const double* d = &det[(c * NL + lane) * 3];
-        valid = d[2] > b.thresh && m_finite(d[0]) && m_finite(d[1]);
+        valid = px_valid(d, b.thresh);
       }
       const unsigned vm = (unsigned)(__ballot(valid) & 0xFFFFFull);
       if (lane == 0) S.vmask[c] = vm;

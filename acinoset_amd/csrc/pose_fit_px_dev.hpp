@@ -1,6 +1,8 @@
 // What the two pose fits from the detections share (pose_fit_px.hip: the cheetah; skel_pose_fit_px.hip: a link program): what
-// their kernels read and write beyond PoseFitIo, the projection of a model point into a camera of the rig, and the checks of
-// the C entries on the pixel parameters.
+// their kernels read and write beyond PoseFitIo, the projection of a model point into a camera of the rig, the pixel
+// measurement (px_valid, px_pair_cost, px_cost_finish, px_pair_rows, px_store_outputs: a model keeps where a position lives,
+// its mask packing, camera grouping and Gram product) and the checks of the C entries on the pixel parameters.  The pieces
+// keep the statement order the kernels had (the detection's address after the projection; profiles/pose_fit_shared/).
 #pragma once
 #include "pinhole.hpp"
 #include "pose_fit_dev.hpp"
@@ -33,6 +35,79 @@ __device__ __forceinline__ bool px_project(const Rec& cm, const double* X, doubl
     }
   }
   return zc > 0.0;
+}
+
+// a detection (x, y, likelihood) counts: likelihood above thresh, both pixel values finite
+__device__ __forceinline__ bool px_valid(const double* d, double thresh) {
+  return d[2] > thresh && m_finite(d[0]) && m_finite(d[1]);
+}
+
+// the two log terms of one valid pair: X in camera cm against detection e = c L + l of det; ``behind`` is set when z_c <= 0
+template <class Rec>
+__device__ __forceinline__ double px_pair_cost(const PxArgs& b, const Rec& cm, const double* X, const double* det, int e,
+                                               bool& behind) {
+  double uv[2];
+  behind = !px_project<false>(cm, X, uv, nullptr) || behind;
+  const double* d = det + e * 3;
+  const double r0 = uv[0] - d[0], r1 = uv[1] - d[1];
+  return 0.5 * b.fs2 * (log1p(r0 * r0 * b.ifs2) + log1p(r1 * r1 * b.ifs2));
+}
+
+// F from a lane's sum of pair terms: times 1 / sigma_px^2, the ridge of xv about m by lanes 3 .. P-1, the 64 partial sums by a
+// butterfly whose additions pair the same operands in every lane (the same bits in every lane); +inf when a pair was behind
+__device__ __forceinline__ double px_cost_finish(double part, const double* xv, const double* m, double kappa, int P, int lane,
+                                                 const PxArgs& b, bool behind) {
+  part *= b.inv_sigma * b.inv_sigma;
+  if (lane >= 3 && lane < P) {
+    const double e = xv[lane] - m[lane];
+    part += 0.5 * kappa * e * e;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
+  return __any(behind) ? __builtin_huge_val() : part;
+}
+
+// the weighted rows of one valid pair, w = 1 / (1 + r^2 / f^2) per coordinate: jr = sqrt(w) / sigma_px * (J_pi R_c), u = ... * r
+template <class Rec>
+__device__ __forceinline__ void px_pair_rows(const PxArgs& b, const Rec& cm, const double* X, const double* det, int L, int c,
+                                             int l, double jr[6], double u[2]) {
+  double uv[2], JR[2][3];
+  px_project<true>(cm, X, uv, JR);
+  const double* d = det + (c * L + l) * 3;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const double r = uv[k] - d[k];
+    const double sw = sqrt(rcp64(1.0 + r * r * b.ifs2)) * b.inv_sigma;
+    jr[3 * k] = sw * JR[k][0];
+    jr[3 * k + 1] = sw * JR[k][1];
+    jr[3 * k + 2] = sw * JR[k][2];
+    u[k] = sw * r;
+  }
+}
+
+// frame n's count of valid detections and, over the L n_cams pairs, the weight every coordinate ended with at the positions
+// pos(l) of the returned x - NaN when not live, exactly 0 for an invalid detection; valid(c, l) reads the model's mask
+template <class Rec, class Valid, class Pos>
+__device__ __forceinline__ void px_store_outputs(const PxArgs& b, const Rec* cams, const double* det, int L, int64_t n, int n_det,
+                                                 bool live, int lane, Valid&& valid, Pos&& pos) {
+  if (lane == 0 && b.ndet) b.ndet[n] = (uint16_t)n_det;
+  if (!b.weight) return;
+  const int pairs = L * b.n_cams;
+  double* out = b.weight + n * pairs * 2;
+  for (int t = lane; t < pairs; t += 64) {
+    const int c = t / L, l = t - c * L;
+    double w0 = live ? 0.0 : __builtin_nan(""), w1 = w0;
+    if (live && valid(c, l)) {
+      double uv[2];
+      px_project<false>(cams[c], pos(l), uv, nullptr);
+      const double* d = det + (c * L + l) * 3;
+      const double r0 = uv[0] - d[0], r1 = uv[1] - d[1];
+      w0 = rcp64(1.0 + r0 * r0 * b.ifs2);
+      w1 = rcp64(1.0 + r1 * r1 * b.ifs2);
+    }
+    out[2 * t] = w0;
+    out[2 * t + 1] = w1;
+  }
 }
 
 // the checks of both pixel entries on the parameter block (prm is not NULL) and the camera count; ``fit`` receives the block of

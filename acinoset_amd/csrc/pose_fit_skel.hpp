@@ -1,11 +1,13 @@
 // What the skeleton's per-frame pose fits share as models of pf_fit_frame<PT> (pose_fit_dev.hpp): skel_pose_fit.hip (SkelFit,
 // from 3-D points) and skel_pose_fit_px.hip (SkelPxFit, from the detections of every camera).  Here: the carved LDS of a link
-// program (Spf), the lane made opaque (spf_here), the link operators and the poses of a state vector (spf_frame), the pose
+// program (Spf), its layout around a model's own regions and its carving (spf_layout, spf_carve), the lane made opaque
+// (spf_here), the link operators and the poses of a state vector (spf_frame), the pose
 // Jacobian taken from them (spf_jacobian), the op and slot masks of every state (spf_masks), the Gram product on the fp64 matrix
 // cores (spf_gram, spf_gram_passes), the inverse of the register-resident factor (spf_invert_factor) and SkelCore<PT> - the members of a
 // model that do not depend on the measurement: the LDS arrays, the frame's box, the active set, factor and solve, cov_x with its
 // symmetric store, the positions and the raw Jacobian of the outputs.  Moved here from skel_pose_fit.hip as they stood (same
 // text, same inlining: k_skel_pose_fit keeps its code, instruction for instruction).  A model adds eval, linearise, accepted, outputs_at_x and cp.
+// At the end: the host path of both C entries - spf_workspace_bytes, spf_program, spf_upload, spf_launch.
 //
 // Both kernels: one 64-lane wave per frame, PT = 16, 32, 48, 64 (P rounded up to 16), ONE PT x (PT + 1) array S.M that holds A in
 // its lower triangle and the factor's strict lower triangle transposed above it, Jw as P columns of ldj (odd) doubles.
@@ -21,6 +23,56 @@ struct Spf {                       // the carved LDS of one workgroup
   int *axs, *ent;                  // per state: its axis (0 phi, 1 theta, 2 psi); per slot: does its point enter (3-D measurement)
   int P, n_pose, n_ops, ldj, ldm, ks;
 };
+
+// offsets into the dynamic LDS, in units of 8 bytes: the regions both fits have; a model's own lie between M and pos (``middle``)
+struct SpfLayout {
+  int P, n_pose, n_ops;
+  int ldj, ldm;                    // leading dimensions of Jw and of M (odd: columns on unlike banks)
+  int Jw, M, pos, opv, vec, red, pm, opm, cm, axs;
+};
+struct SpfTake {                   // the next region of n doubles, in 16-byte steps
+  int o = 0;
+  __host__ __device__ int operator()(int n) { return (o += (n + 1) & ~1) - ((n + 1) & ~1); }
+};
+template <class Middle>
+__host__ __device__ inline SpfLayout spf_layout(int P, int PT, int n_pose, int n_ops, SpfTake& take, Middle&& middle) {
+  SpfLayout L;
+  L.P = P, L.n_pose = n_pose, L.n_ops = n_ops;
+  L.ldj = 4 * (((3 * n_pose > P ? 3 * n_pose : P) + 3) / 4) + 1;      // (P: the rows of L^-1 take Jw's place for cov_x)
+  L.ldm = PT + 1;                  // (a compile-time constant of the kernel: its offsets are immediates)
+  L.Jw = take(P * L.ldj);
+  L.M = take(PT * L.ldm);          // (PT rows: the tiles are stored whole, the rows beyond P are zeros)
+  middle(take);
+  L.pos = take(3 * n_pose);
+  L.opv = take(12 * (n_ops > 0 ? n_ops : 1));
+  L.vec = take(6 * SK_MAXP);       // x, xt, m, g, lo, hi
+  L.red = take(3 * SK_MAXP);
+  L.pm = take(n_pose);
+  L.opm = take(SK_MAXP);
+  L.cm = take(2 * SK_MAXP);
+  L.axs = take(SK_MAXP / 2);
+  return L;
+}
+
+// the members of Spf every model has; ``middle(S)`` sets the model's own between M and pos (y, U, u, rest, ent: NULL unless it
+// does).  The pointers are formed in the order of the regions: in another, k_skel_pose_fit gets other scalar address arithmetic
+template <class Middle>
+__device__ __forceinline__ Spf spf_carve(double* base, const SpfLayout& lay, Middle&& middle) {
+  Spf S;
+  S.y = S.U = S.u = S.rest = nullptr, S.ent = nullptr;
+  S.Jw = base + lay.Jw, S.M = base + lay.M;
+  middle(S);
+  S.pos = base + lay.pos, S.opv = base + lay.opv;
+  S.x = base + lay.vec, S.xt = S.x + SK_MAXP, S.m = S.xt + SK_MAXP, S.g = S.m + SK_MAXP;
+  S.lo = S.g + SK_MAXP, S.hi = S.lo + SK_MAXP;
+  S.red = base + lay.red;
+  S.pm = reinterpret_cast<unsigned long long*>(base + lay.pm);
+  S.opm = reinterpret_cast<unsigned long long*>(base + lay.opm);
+  S.cm = reinterpret_cast<unsigned long long*>(base + lay.cm);
+  S.axs = reinterpret_cast<int*>(base + lay.axs);
+  S.P = lay.P, S.n_pose = lay.n_pose, S.n_ops = lay.n_ops, S.ldj = lay.ldj, S.ldm = lay.ldm, S.ks = (3 * lay.n_pose + 3) / 4;
+  return S;
+}
 
 // The lane index again, opaque to the optimiser: what a loop body derives from it (LDS addresses, the selects of an unrolled
 // row) then stays inside the body.  Hoisted out of the frame loop, hundreds of such values outlive every register and are
@@ -319,5 +371,46 @@ inline acino_skel_fte_params spf_params(const acino_skel_fte_params* p) {
 
 constexpr size_t SPF_LDS_MAX = 160 * 1024;
 inline size_t spf_ws_clip() { return skel_align256(sizeof(SkelDev)); }
+
+// ---- the host path of both entries, in the order of their checks: spf_program, the entry's 160 KB check of its own layout, its
+//      n_frames == 0 return and null-buffer check, spf_upload, spf_launch.  spf_workspace_bytes: both exported *_workspace_bytes
+inline size_t spf_workspace_bytes(const acino_skel_fte_params* p) {
+  if (!p) return 0;
+  const acino_skel_fte_params q = spf_params(p);
+  if (skel_validate(&q)) return 0;
+  return spf_ws_clip() + skel_align256(sizeof(SkelClip));
+}
+
+// the params block checked, then the entry's own parameters (check_fit()), then the link program into h
+template <class CheckFit>
+inline int spf_program(const acino_skel_fte_params* p, const acino_skel_op* h_ops, const int32_t* h_active, SkelDev& h,
+                       CheckFit&& check_fit) {
+  ACINO_REQUIRE(p != nullptr, "params");
+  const acino_skel_fte_params q = spf_params(p);
+  if (int rc = skel_validate(&q)) return rc;
+  if (int rc = check_fit()) return rc;
+  ACINO_REQUIRE(h_ops && h_active, "null buffer (h_ops, h_active)");
+  return skel_program(&q, h_ops, h_active, h);
+}
+
+// the workspace checked (``query`` names the entry's function), the link program uploaded into it: d_dev (no camera is read)
+inline int spf_upload(const SkelDev& h, const acino_skel_fte_params* p, void* d_ws, size_t ws_bytes, const char* query,
+                      hipStream_t s, const SkelDev*& d_dev) {
+  if (int rc = skel_check_workspace(d_ws, ws_bytes, spf_workspace_bytes(p), query, ACINO_ERR_WORKSPACE)) return rc;
+  SkelDev* dev = reinterpret_cast<SkelDev*>(d_ws);
+  d_dev = dev;
+  return skel_upload(h, nullptr, 0, dev, reinterpret_cast<SkelClip*>(reinterpret_cast<char*>(d_ws) + spf_ws_clip()), 1, s);
+}
+
+// one frame per workgroup pass, grid-stride beyond the cap; the 160 KB opt-in once per device and kernel (``attr``: its static)
+template <class K, class Args>
+inline int spf_launch(K kernel, PerDeviceOnce& attr, int64_t n_frames, size_t lds, hipStream_t s, const Args& a) {
+  if (attr.first())
+    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)SPF_LDS_MAX));
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n_frames, 1)), dim3(64), lds, s, a);
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
 
 }  // namespace acino

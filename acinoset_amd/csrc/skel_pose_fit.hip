@@ -21,7 +21,8 @@
 // l's path that hang on state p (skel_pose_jac_col's sum, from per-state op masks built once per workgroup instead of a scan of
 // the program per entry); it is evaluated only where that set is not empty, and g is summed over those slots in slot order.
 //
-// Dynamic LDS, sized from (P, n_pose, n_ops) by spf_layout: Jw as P columns of 4 ceil(3 n_pose / 4) + 1, ONE PT x (PT + 1)
+// Dynamic LDS, sized from (P, n_pose, n_ops) by spf3_layout (spf_layout of pose_fit_skel.hpp around y, U, u, rest; that header
+// also carves Spf and holds the entry's host path): Jw as P columns of 4 ceil(3 n_pose / 4) + 1, ONE PT x (PT + 1)
 // array that holds A in its lower triangle and the factor's strict lower triangle transposed above it (the factor's diagonal
 // stays in registers), one set of link operators and poses (the trial's; the returned point's are evaluated again for the
 // outputs), the points and whitening factors.  cov_x = X^T X with X = L^-1: the factor is inverted in its own registers
@@ -38,37 +39,22 @@ struct SkelPoseFitArgs {
   const double *lo, *hi;
 };
 
-// offsets into the dynamic LDS, in units of 8 bytes
-struct SpfLayout {
-  int ldj, ldm;                    // leading dimensions of Jw and of M (odd: columns on unlike banks)
-  int Jw, M, y, U, u, rest, pos, opv, vec, red, pm, opm, cm, axs, ent, total;
+// offsets into the dynamic LDS, in units of 8 bytes: SpfLayout with the 3-D measurement's regions
+struct Spf3Layout {
+  SpfLayout s;
+  int y, U, u, rest, ent, total;
 };
-__host__ __device__ inline SpfLayout spf_layout(int P, int PT, int n_pose, int n_ops) {
-  SpfLayout L;
-  L.ldj = 4 * (((3 * n_pose > P ? 3 * n_pose : P) + 3) / 4) + 1;      // (P: the rows of L^-1 take Jw's place for cov_x)
-  L.ldm = PT + 1;                  // (a compile-time constant of the kernel: its offsets are immediates)
-  int o = 0;
-  auto take = [&](int n) {
-    const int at = o;
-    o += (n + 1) & ~1;             // (16-byte steps)
-    return at;
-  };
-  L.Jw = take(P * L.ldj);
-  L.M = take(PT * L.ldm);          // (PT rows: the tiles are stored whole, the rows beyond P are zeros)
-  L.y = take(3 * n_pose);          // y | U | u are consecutive: the outputs' [3 n_pose][3] products take their place
-  L.U = take(6 * n_pose);
-  L.u = take(3 * n_pose);
-  L.rest = take(3 * n_pose);
-  L.pos = take(3 * n_pose);
-  L.opv = take(12 * (n_ops > 0 ? n_ops : 1));
-  L.vec = take(6 * SK_MAXP);       // x, xt, m, g, lo, hi
-  L.red = take(3 * SK_MAXP);
-  L.pm = take(n_pose);
-  L.opm = take(SK_MAXP);
-  L.cm = take(2 * SK_MAXP);
-  L.axs = take(SK_MAXP / 2);
+__host__ __device__ inline Spf3Layout spf3_layout(int P, int PT, int n_pose, int n_ops) {
+  Spf3Layout L;
+  SpfTake take;
+  L.s = spf_layout(P, PT, n_pose, n_ops, take, [&](SpfTake& t) {
+    L.y = t(3 * n_pose);           // y | U | u are consecutive: the outputs' [3 n_pose][3] products take their place
+    L.U = t(6 * n_pose);
+    L.u = t(3 * n_pose);
+    L.rest = t(3 * n_pose);
+  });
   L.ent = take((n_pose + 1) / 2);
-  L.total = o;
+  L.total = take.o;
   return L;
 }
 
@@ -159,19 +145,12 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit(SkelPoseFitArgs a) {
   const SkelDev& D = *a.dev;
   const int lane = threadIdx.x;
   const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, R3 = 3 * NPOSE;
-  const SpfLayout lay = spf_layout(P, PT, NPOSE, NOPS);
+  const Spf3Layout lay = spf3_layout(P, PT, NPOSE, NOPS);
   double* base = reinterpret_cast<double*>(smem_raw);
-  Spf S;
-  S.Jw = base + lay.Jw, S.M = base + lay.M, S.y = base + lay.y, S.U = base + lay.U, S.u = base + lay.u;
-  S.rest = base + lay.rest, S.pos = base + lay.pos, S.opv = base + lay.opv;
-  S.x = base + lay.vec, S.xt = S.x + SK_MAXP, S.m = S.xt + SK_MAXP, S.g = S.m + SK_MAXP, S.lo = S.g + SK_MAXP, S.hi = S.lo + SK_MAXP;
-  S.red = base + lay.red;
-  S.pm = reinterpret_cast<unsigned long long*>(base + lay.pm);
-  S.opm = reinterpret_cast<unsigned long long*>(base + lay.opm);
-  S.cm = reinterpret_cast<unsigned long long*>(base + lay.cm);
-  S.axs = reinterpret_cast<int*>(base + lay.axs);
+  Spf S = spf_carve(base, lay.s, [&](Spf& S) {
+    S.y = base + lay.y, S.U = base + lay.U, S.u = base + lay.u, S.rest = base + lay.rest;
+  });
   S.ent = reinterpret_cast<int*>(base + lay.ent);
-  S.P = P, S.n_pose = NPOSE, S.n_ops = NOPS, S.ldj = lay.ldj, S.ldm = lay.ldm, S.ks = (R3 + 3) / 4;
 
   // ---- once per workgroup: the op and slot masks of every state, the rest pose.  The masks are the twin of spf_masks
   //      (pose_fit_skel.hpp), kept here as text: called as that function the same statements come out in another register
@@ -256,12 +235,7 @@ using namespace acino;
 
 extern "C" {
 
-size_t acino_skel_pose_fit_workspace_bytes(const acino_skel_fte_params* p) {
-  if (!p) return 0;
-  const acino_skel_fte_params q = spf_params(p);
-  if (skel_validate(&q)) return 0;
-  return spf_ws_clip() + skel_align256(sizeof(SkelClip));
-}
+size_t acino_skel_pose_fit_workspace_bytes(const acino_skel_fte_params* p) { return spf_workspace_bytes(p); }
 
 int acino_skel_pose_fit(const acino_pose_fit_params* prm, const acino_skel_fte_params* p, const acino_skel_op* h_ops,
                         const int32_t* h_active, const double* d_points, const double* d_cov, const double* d_x0,
@@ -269,40 +243,22 @@ int acino_skel_pose_fit(const acino_pose_fit_params* prm, const acino_skel_fte_p
                         uint8_t* d_nmarkers, uint8_t* d_status, uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x,
                         double* d_pos, double* d_cov_pos, double* d_std_pos, void* d_ws, size_t ws_bytes, void* stream) {
   ACINO_REQUIRE(prm != nullptr, "prm");
-  ACINO_REQUIRE(p != nullptr, "params");
-  const acino_skel_fte_params q = spf_params(p);
-  int rc = skel_validate(&q);
-  if (rc) return rc;
-  if ((rc = pf_check_params(prm, n_frames, p->n_pose, "min_markers must be 1..n_pose"))) return rc;
-  ACINO_REQUIRE(h_ops && h_active, "null buffer (h_ops, h_active)");
   SkelDev h;
-  if ((rc = skel_program(&q, h_ops, h_active, h))) return rc;
-  const SpfLayout lay = spf_layout(h.n_act, h.PT, h.n_pose, h.n_ops);
-  const size_t lds = sizeof(double) * (size_t)lay.total;
+  auto check_fit = [&] { return pf_check_params(prm, n_frames, p->n_pose, "min_markers must be 1..n_pose"); };
+  if (int rc = spf_program(p, h_ops, h_active, h, check_fit)) return rc;
+  const size_t lds = sizeof(double) * (size_t)spf3_layout(h.n_act, h.PT, h.n_pose, h.n_ops).total;
   ACINO_REQUIRE(lds <= SPF_LDS_MAX, "n_active x n_pose does not fit the pose fit's 160 KB of LDS");
   if (n_frames == 0) return ACINO_OK;
   ACINO_REQUIRE(d_points && d_lo && d_hi && d_x && d_status && d_ws, "null buffer (d_points, d_lo, d_hi, d_x, d_status, d_ws)");
-  if ((rc = skel_check_workspace(d_ws, ws_bytes, acino_skel_pose_fit_workspace_bytes(p), "acino_skel_pose_fit_workspace_bytes",
-                                 ACINO_ERR_WORKSPACE)))
-    return rc;
   hipStream_t s = (hipStream_t)stream;
-  SkelDev* d_dev = reinterpret_cast<SkelDev*>(d_ws);
-  SkelClip* d_clip = reinterpret_cast<SkelClip*>(reinterpret_cast<char*>(d_ws) + spf_ws_clip());
-  if ((rc = skel_upload(h, nullptr, 0, d_dev, d_clip, 1, s))) return rc;      // (no camera: only the link program is read)
   SkelPoseFitArgs a;
-  a.dev = d_dev, a.lo = d_lo, a.hi = d_hi;
+  if (int rc = spf_upload(h, p, d_ws, ws_bytes, "acino_skel_pose_fit_workspace_bytes", s, a.dev)) return rc;
+  a.lo = d_lo, a.hi = d_hi;
   pf_fill_io(a.io, prm, d_points, d_cov, d_x0, n_frames, d_x, d_cost, d_nmarkers, d_status, d_iters, d_pinned, d_cov_x, d_pos,
              d_cov_pos, d_std_pos);
-  const int grid = grid_for(n_frames, 1);       // one frame per workgroup pass, grid-stride beyond the cap
   return skel_dispatch_pt(h.PT, [&](auto pt) -> int {
-    constexpr int T = decltype(pt)::value;
-    static PerDeviceOnce attr;
-    if (attr.first())
-      ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_pose_fit<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)SPF_LDS_MAX));
-    hipLaunchKernelGGL(k_skel_pose_fit<T>, dim3(grid), dim3(64), lds, s, a);
-    ACINO_LAUNCH_CHECK();
-    return ACINO_OK;
+    static PerDeviceOnce attr;                  // (per PT: one per instantiation of this body)
+    return spf_launch(k_skel_pose_fit<decltype(pt)::value>, attr, n_frames, lds, s, a);
   });
 }
 

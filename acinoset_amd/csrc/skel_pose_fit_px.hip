@@ -8,8 +8,8 @@
 // finite, F = +inf when a valid detection's slot has z_c <= 0, m the start clipped to the box.  Gradient and matrix carry the
 // IRLS weight w = 1 / (1 + r_k^2 / f^2), J = (J_pi R_c) G_l; the same A serves step, predicted reduction, active set and
 // outputs.  The model is SkelPxFit<PT, PINHOLE>: SkelCore<PT> of pose_fit_skel.hpp (link operators, poses, raw Jacobian, Gram
-// product, factor, solve, cov_x: what skel_pose_fit.hip's SkelFit runs) plus the pixel measurement, with px_project of
-// pose_fit_px_dev.hpp (what pose_fit_px.hip's CheetahPxFit runs).
+// product, factor, solve, cov_x: what skel_pose_fit.hip's SkelFit runs) plus the pixel measurement of pose_fit_px_dev.hpp
+// (what pose_fit_px.hip's CheetahPxFit runs); the layout's head and tail, the carving and the host path are pose_fit_skel.hpp's.
 //
 // One 64-lane wave per frame, one launch, a grid-stride loop over the frames, no atomics, nothing waits on another workgroup.
 //   eval       FK, then the n_cams n_pose (camera, slot) pairs over the lanes, pair t = lane + 64 k: project, add the two log
@@ -46,42 +46,28 @@ struct SkelPxArgs {
   int loop_g;                      // g by the per-state loop even where P < PT
 };
 
-// offsets into the dynamic LDS, in units of 8 bytes
+// offsets into the dynamic LDS, in units of 8 bytes: SpfLayout with the pixel measurement's regions
 struct SpxLayout {
-  int ldj, ldm, ldc, group;        // leading dimensions of G, M and Jc (odd); cameras projected in one pass
-  int Jw, M, Jc, cams, det, vm, jr, ur, cp, pos, opv, vec, red, pm, opm, cm, axs, total;
+  SpfLayout s;
+  int ldc, group;                  // leading dimension of Jc (odd); cameras projected in one pass
+  int Jc, cams, det, vm, jr, ur, cp, total;
 };
 __host__ __device__ inline SpxLayout spx_layout(int P, int PT, int n_pose, int n_ops, int n_cams, bool pinhole) {
   SpxLayout L;
-  L.ldj = 4 * (((3 * n_pose > P ? 3 * n_pose : P) + 3) / 4) + 1;      // (P: the rows of L^-1 take G's place for cov_x)
-  L.ldm = PT + 1;
-  L.ldc = 4 * ((2 * n_pose + 3) / 4) + 1;
-  L.group = n_pose >= 64 ? 1 : 64 / n_pose;
-  if (L.group > n_cams) L.group = n_cams;
-  int o = 0;
-  auto take = [&](int n) {
-    const int at = o;
-    o += (n + 1) & ~1;             // (16-byte steps)
-    return at;
-  };
-  L.Jw = take(P * L.ldj);
-  L.M = take(PT * L.ldm);
-  L.Jc = take((P + 1) * L.ldc);    // (column P: the weighted residuals)
-  L.cams = take(n_cams * (pinhole ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE));
-  L.det = take(n_cams * n_pose * 3);
-  L.vm = take(2 * n_cams);
-  L.jr = take(L.group * n_pose * 6);
-  L.ur = take(L.group * 2 * n_pose);
-  L.cp = take(9 * n_pose);
-  L.pos = take(3 * n_pose);
-  L.opv = take(12 * (n_ops > 0 ? n_ops : 1));
-  L.vec = take(6 * SK_MAXP);       // x, xt, m, g, lo, hi
-  L.red = take(3 * SK_MAXP);
-  L.pm = take(n_pose);
-  L.opm = take(SK_MAXP);
-  L.cm = take(2 * SK_MAXP);
-  L.axs = take(SK_MAXP / 2);
-  L.total = o;
+  SpfTake take;
+  L.s = spf_layout(P, PT, n_pose, n_ops, take, [&](SpfTake& t) {
+    L.ldc = 4 * ((2 * n_pose + 3) / 4) + 1;
+    L.group = n_pose >= 64 ? 1 : 64 / n_pose;
+    if (L.group > n_cams) L.group = n_cams;
+    L.Jc = t((P + 1) * L.ldc);     // (column P: the weighted residuals)
+    L.cams = t(n_cams * (pinhole ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE));
+    L.det = t(n_cams * n_pose * 3);
+    L.vm = t(2 * n_cams);
+    L.jr = t(L.group * n_pose * 6);
+    L.ur = t(L.group * 2 * n_pose);
+    L.cp = t(9 * n_pose);
+  });
+  L.total = take.o;
   return L;
 }
 
@@ -121,20 +107,9 @@ struct SkelPxFit : SkelCore<PT> {
     for (int t = lane; t < pairs; t += 64) {
       const int c = t / L, l = t - c * L;
       if (!valid(c, l)) continue;
-      double uv[2];
-      behind = !px_project<false>(cams[c], S.pos + 3 * l, uv, nullptr) || behind;
-      const double* d = X.det + (c * L + l) * 3;
-      const double r0 = uv[0] - d[0], r1 = uv[1] - d[1];
-      part += 0.5 * b.fs2 * (log1p(r0 * r0 * b.ifs2) + log1p(r1 * r1 * b.ifs2));
+      part += px_pair_cost(b, cams[c], S.pos + 3 * l, X.det, t, behind);
     }
-    part *= b.inv_sigma * b.inv_sigma;
-    if (lane >= 3 && lane < S.P) {
-      const double e = xv[lane] - S.m[lane];
-      part += 0.5 * kappa * e * e;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
-    return __any(behind) ? __builtin_huge_val() : part;
+    return px_cost_finish(part, xv, S.m, kappa, S.P, lane, b, behind);
   }
 
   // G, then A and g at S.x camera by camera (S.opv and S.pos are S.x's: the last eval was the accepted trial's or the start's)
@@ -154,6 +129,9 @@ struct SkelPxFit : SkelCore<PT> {
           for (int t = here; t < X.group * L; t += 64) {
             const int cc = t / L, l = t - cc * L, cg = c0 + cc;
             double jr[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, u[2] = {0.0, 0.0};
+            // The twin of px_pair_rows (pose_fit_px_dev.hpp), kept here as text, as the weight loop of outputs_at_x is the twin
+            // of px_store_outputs: called as those functions the statements reach this kernel in another order, two
+            // instantiations took other AGPR counts and <48, false> measured 0.2 to 0.8 % slower (NOTES_perf.md).
             if (cg < C && valid(cg, l)) {
               double uv[2], JR[2][3];
               px_project<true>(cams[cg], S.pos + 3 * l, uv, JR);
@@ -257,16 +235,7 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit_px(SkelPxArgs a) {
   const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, C = b.n_cams;
   const SpxLayout lay = spx_layout(P, PT, NPOSE, NOPS, C, PINHOLE);
   double* base = reinterpret_cast<double*>(smem_raw);
-  Spf S;
-  S.Jw = base + lay.Jw, S.M = base + lay.M, S.pos = base + lay.pos, S.opv = base + lay.opv;
-  S.y = S.U = S.u = S.rest = nullptr, S.ent = nullptr;      // (the 3-D measurement's)
-  S.x = base + lay.vec, S.xt = S.x + SK_MAXP, S.m = S.xt + SK_MAXP, S.g = S.m + SK_MAXP, S.lo = S.g + SK_MAXP, S.hi = S.lo + SK_MAXP;
-  S.red = base + lay.red;
-  S.pm = reinterpret_cast<unsigned long long*>(base + lay.pm);
-  S.opm = reinterpret_cast<unsigned long long*>(base + lay.opm);
-  S.cm = reinterpret_cast<unsigned long long*>(base + lay.cm);
-  S.axs = reinterpret_cast<int*>(base + lay.axs);
-  S.P = P, S.n_pose = NPOSE, S.n_ops = NOPS, S.ldj = lay.ldj, S.ldm = lay.ldm, S.ks = (3 * NPOSE + 3) / 4;
+  const Spf S = spf_carve(base, lay.s, [](Spf&) {});
   Spx X;
   X.Jc = base + lay.Jc, X.det = base + lay.det, X.jr = base + lay.jr, X.ur = base + lay.ur, X.cp = base + lay.cp;
   X.vm = reinterpret_cast<unsigned long long*>(base + lay.vm);
@@ -295,7 +264,7 @@ __global__ void __launch_bounds__(64) k_skel_pose_fit_px(SkelPxArgs a) {
         bool ok = false;
         if (l < NPOSE) {
           const double* d = X.det + (c * NPOSE + l) * 3;
-          ok = d[2] > b.thresh && m_finite(d[0]) && m_finite(d[1]);
+          ok = px_valid(d, b.thresh);
         }
         const unsigned long long vm = __ballot(ok);
         if (lane == 0) X.vm[2 * c + h] = vm;
@@ -322,12 +291,7 @@ using namespace acino;
 
 extern "C" {
 
-size_t acino_skel_pose_fit_px_workspace_bytes(const acino_skel_fte_params* p) {
-  if (!p) return 0;
-  const acino_skel_fte_params q = spf_params(p);
-  if (skel_validate(&q)) return 0;
-  return spf_ws_clip() + skel_align256(sizeof(SkelClip));
-}
+size_t acino_skel_pose_fit_px_workspace_bytes(const acino_skel_fte_params* p) { return spf_workspace_bytes(p); }
 
 int acino_skel_pose_fit_px(const acino_pose_fit_px_params* prm, const acino_skel_fte_params* p, const acino_skel_op* h_ops,
                            const int32_t* h_active, const double* d_det, int64_t n_frames, int n_cams, const double* d_cams,
@@ -335,47 +299,30 @@ int acino_skel_pose_fit_px(const acino_pose_fit_px_params* prm, const acino_skel
                            uint16_t* d_ndet, uint8_t* d_status, uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x, double* d_pos,
                            double* d_cov_pos, double* d_std_pos, double* d_weight, void* d_ws, size_t ws_bytes, void* stream) {
   ACINO_REQUIRE(prm != nullptr, "prm");
-  ACINO_REQUIRE(p != nullptr, "params");
-  const acino_skel_fte_params q = spf_params(p);
-  int rc = skel_validate(&q);
-  if (rc) return rc;
   acino_pose_fit_params fit;
-  if ((rc = px_check_params(prm, n_frames, n_cams, p->n_pose, "min_detections must be 1..n_pose n_cams", fit))) return rc;
-  ACINO_REQUIRE(h_ops && h_active, "null buffer (h_ops, h_active)");
   SkelDev h;
-  if ((rc = skel_program(&q, h_ops, h_active, h))) return rc;
+  auto check_fit = [&] {
+    return px_check_params(prm, n_frames, n_cams, p->n_pose, "min_detections must be 1..n_pose n_cams", fit);
+  };
+  if (int rc = spf_program(p, h_ops, h_active, h, check_fit)) return rc;
   const bool pinhole = prm->camera_model == 1;
-  const SpxLayout lay = spx_layout(h.n_act, h.PT, h.n_pose, h.n_ops, n_cams, pinhole);
-  const size_t lds = sizeof(double) * (size_t)lay.total;
+  const size_t lds = sizeof(double) * (size_t)spx_layout(h.n_act, h.PT, h.n_pose, h.n_ops, n_cams, pinhole).total;
   ACINO_REQUIRE(lds <= SPF_LDS_MAX, "n_active x n_pose x n_cams does not fit the pixel pose fit's 160 KB of LDS");
   if (n_frames == 0) return ACINO_OK;
   ACINO_REQUIRE(d_det && d_cams && d_x0 && d_lo && d_hi && d_x && d_status && d_ws,
                 "null buffer (d_det, d_cams, d_x0, d_lo, d_hi, d_x, d_status, d_ws)");
-  if ((rc = skel_check_workspace(d_ws, ws_bytes, acino_skel_pose_fit_px_workspace_bytes(p),
-                                 "acino_skel_pose_fit_px_workspace_bytes", ACINO_ERR_WORKSPACE)))
-    return rc;
   hipStream_t s = (hipStream_t)stream;
-  SkelDev* d_dev = reinterpret_cast<SkelDev*>(d_ws);
-  SkelClip* d_clip = reinterpret_cast<SkelClip*>(reinterpret_cast<char*>(d_ws) + spf_ws_clip());
-  if ((rc = skel_upload(h, nullptr, 0, d_dev, d_clip, 1, s))) return rc;      // (the cameras come as records: only the link program)
   SkelPxArgs a;
-  a.dev = d_dev, a.lo = d_lo, a.hi = d_hi, a.loop_g = prm->reserved & 1;
+  if (int rc = spf_upload(h, p, d_ws, ws_bytes, "acino_skel_pose_fit_px_workspace_bytes", s, a.dev)) return rc;
+  a.lo = d_lo, a.hi = d_hi, a.loop_g = prm->reserved & 1;
   pf_fill_io(a.io, &fit, nullptr, nullptr, d_x0, n_frames, d_x, d_cost, nullptr, d_status, d_iters, d_pinned, d_cov_x, d_pos,
              d_cov_pos, d_std_pos);
   px_fill_args(a.px, prm, d_det, d_cams, n_cams, d_ndet, d_weight);
-  const int grid = grid_for(n_frames, 1);       // one frame per workgroup pass, grid-stride beyond the cap
   return skel_dispatch_pt(h.PT, [&](auto pt) -> int {
     constexpr int T = decltype(pt)::value;
-    auto launch = [&](auto kernel, PerDeviceOnce& attr) -> int {
-      if (attr.first())
-        ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)SPF_LDS_MAX));
-      hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, a);
-      ACINO_LAUNCH_CHECK();
-      return ACINO_OK;
-    };
     static PerDeviceOnce attr_pinhole, attr_fisheye;      // (per PT: one pair per instantiation of this body)
-    return pinhole ? launch(k_skel_pose_fit_px<T, true>, attr_pinhole) : launch(k_skel_pose_fit_px<T, false>, attr_fisheye);
+    return pinhole ? spf_launch(k_skel_pose_fit_px<T, true>, attr_pinhole, n_frames, lds, s, a)
+                   : spf_launch(k_skel_pose_fit_px<T, false>, attr_fisheye, n_frames, lds, s, a);
   });
 }
 

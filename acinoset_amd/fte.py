@@ -768,42 +768,71 @@ def pose_fit_pixels(det, k_arr, d_arr, r_arr, t_arr, thresh=0.5, camera_model="f
 
     numpy in, numpy out; CUDA tensors in, CUDA tensors out with no host copy when ``x0`` is given (the default start fills its
     unfitted frames on the host, N x 25 values, as ``pose_fit_init`` does)."""
-    if camera_model not in calib.CAMERAS:
-        raise ValueError(f"camera_model must be one of {calib.CAMERA_MODELS}")
-    shape = _shape(det)
-    if len(shape) != 4 or shape[2:] != (N_MARKERS, 3):
-        raise ValueError("det must be [N, C, 20, 3]")
-    N, Cn = shape[:2]
-    if not 1 <= Cn <= _lib.MAX_CAMS:
-        raise ValueError(f"det holds {Cn} cameras: 1..{_lib.MAX_CAMS} are supported")
-    if len(k_arr) != Cn:
-        raise ValueError("camera count mismatch")
-    if x0 is not None and _shape(x0) != (N, N_ACTIVE):
-        raise ValueError("x0 must be [N, 25] (the active states)")
-    _fit_checks((("prior_sigma", prior_sigma), ("f_scale", f_scale), ("sigma_px", sigma_px), ("ftol", ftol), ("xtol", xtol),
-                 ("lam0", lam0)), max_iter, "min_detections", min_detections, N_MARKERS * Cn)
-    if np.isnan(thresh):
-        raise ValueError("thresh must not be NaN")
-    recs = calib.camera_records(camera_model, k_arr, d_arr, r_arr, t_arr)
-    dev = calib._dev()
-    d = calib._to_dev(det, dev)
-    if x0 is None:
+    def start(d):
         tri = calib.triangulate_multiview_dense(d, thresh, k_arr, d_arr, r_arr, t_arr, model=camera_model, f_scale=f_scale,
                                                 sigma_px=sigma_px)
         fit = pose_fit(tri, return_cov=False)
-        x0 = fill_unfitted_frames(fit["x"].cpu().numpy(), fit["status"].cpu().numpy() < 2)
-    xs = calib._to_dev(x0, dev)
+        return fill_unfitted_frames(fit["x"].cpu().numpy(), fit["status"].cpu().numpy() < 2)
+
+    def launch(prm, dev, N, Cn, ins, outs):
+        check(lib().acino_cheetah_pose_fit_px(prm, ins[0], N, Cn, *ins[1:], *outs, stream_ptr()))
+
+    texts = dict(camera_model=f"camera_model must be one of {calib.CAMERA_MODELS}", det="det must be [N, C, 20, 3]",
+                 cams="det holds {} cameras: 1..{} are supported", rig="camera count mismatch",
+                 x0="x0 must be [N, 25] (the active states)")
+    return _pose_fit_px(launch, det, x0, start, shape=(None, None, N_MARKERS), active=ACTIVE, n_full=N_STATES,
+                        camera_model=camera_model, rig=(k_arr, d_arr, r_arr, t_arr), texts=texts,
+                        tensors=isinstance(det, torch.Tensor), thresh=thresh, f_scale=f_scale, sigma_px=sigma_px,
+                        prior_sigma=prior_sigma, min_detections=min_detections, max_iter=max_iter, ftol=ftol, xtol=xtol, lam0=lam0,
+                        return_cov=return_cov)
+
+
+def _pose_fit_px(launch, det, x0, start, *, shape, active, n_full, camera_model, rig, texts, tensors, thresh, f_scale, sigma_px,
+                 prior_sigma, min_detections, max_iter, ftol, xtol, lam0, return_cov, ready=None):
+    """What ``pose_fit_pixels`` and ``build.pose_fit_pixels`` share, the analogue of ``_pose_fit``: the checks, in this order -
+    camera model; det [N, Cn, L, 3] with ``shape`` = (N, Cn, L), N and Cn None: those of ``det``; camera count; that of ``rig`` =
+    (K, D, R, t) where ``texts`` has "rig"; x0 [N, len(active)]; ``_fit_checks``; ``thresh`` - with the caller's messages
+    ``texts``, the camera records, ``ready(dev)`` (a refusal of the caller's once the device is known), the staging, the outputs,
+    ``PoseFitPxParams``, the dict (numpy unless ``tensors``).  ``det`` / ``sigma_px`` may be callables, the caller's defaults,
+    called after the shape checks; ``start(d)`` gives the default x0.  ``launch(prm, dev, N, Cn, ins, outs)`` makes the library
+    call: ``ins`` the pointers of det, records, x0, ``outs`` those of the eleven outputs, in the order of the C entries."""
+    if camera_model not in calib.CAMERAS:
+        raise ValueError(texts["camera_model"])
+    (N, Cn, L), P = shape, len(active)
+    if not callable(det):
+        got = _shape(det)
+        if N is None and len(got) == 4:
+            N, Cn = got[:2]
+        if got != (N, Cn, L, 3):
+            raise ValueError(texts["det"])
+    if not 1 <= Cn <= _lib.MAX_CAMS:
+        raise ValueError(texts["cams"].format(Cn, _lib.MAX_CAMS))
+    if "rig" in texts and len(rig[0]) != Cn:
+        raise ValueError(texts["rig"])
+    if x0 is not None and _shape(x0) != (N, P):
+        raise ValueError(texts["x0"])
+    if callable(sigma_px):
+        sigma_px = sigma_px()
+    _fit_checks((("prior_sigma", prior_sigma), ("f_scale", f_scale), ("sigma_px", sigma_px), ("ftol", ftol), ("xtol", xtol),
+                 ("lam0", lam0)), max_iter, "min_detections", min_detections, L * Cn)
+    if np.isnan(thresh):
+        raise ValueError("thresh must not be NaN")
+    recs = calib.camera_records(camera_model, *rig)
+    dev = calib._dev()
+    if ready is not None:
+        ready(dev)
+    d = calib._to_dev(det() if callable(det) else det, dev)
+    xs = calib._to_dev(start(d) if x0 is None else x0, dev)
     cams = torch.as_tensor(recs, device=dev)
-    o = _fit_outputs(N, N_ACTIVE, N_MARKERS, dev, return_cov)
+    o = _fit_outputs(N, P, L, dev, return_cov)
     nd = torch.empty((N,), dtype=torch.uint16, device=dev)
-    weight = torch.empty((N, Cn, N_MARKERS, 2), dtype=torch.float64, device=dev)
+    weight = torch.empty((N, Cn, L, 2), dtype=torch.float64, device=dev)
     prm = _lib.PoseFitPxParams(calib.CAMERAS[camera_model].code, int(max_iter), int(min_detections), 0, float(lam0), float(ftol),
                                float(xtol), float(prior_sigma), float(thresh), float(f_scale), float(sigma_px))
-    check(lib().acino_cheetah_pose_fit_px(prm, ptr(d), N, Cn, ptr(cams), ptr(xs),
-                                          *(ptr(t) for t in (o["x"], o["cost"], nd, o["status"], o["iters"], o["pinned"], o["cov_x"],
-                                                             o["positions"], o["cov_positions"], o["std_positions"], weight)),
-                                          stream_ptr()))
-    return _fit_dict(o, "n_detections", nd, ACTIVE, N_STATES, isinstance(det, torch.Tensor), weight=weight)
+    launch(prm, dev, N, Cn, [ptr(t) for t in (d, cams, xs)],
+           [ptr(t) for t in (o["x"], o["cost"], nd, o["status"], o["iters"], o["pinned"], o["cov_x"], o["positions"],
+                             o["cov_positions"], o["std_positions"], weight)])
+    return _fit_dict(o, "n_detections", nd, active, n_full, tensors, weight=weight)
 
 
 PSI_COLUMNS = [int(np.nonzero(ACTIVE == PSI + k)[0][0]) for k in (0, 1, 3, 4, 5)]     # the psi states among the active ones
