@@ -139,7 +139,7 @@ def _scene_distortion(camera_model, k_arr, d_arr, r_arr, t_arr):
 
 def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_frames=N_FRAMES, start_frame=START_FRAME,
                 h=H_STEP, pairing="reference", lik_thresh=LIK_THRESH, r_meas=R_MEAS, model_weight=MODEL_WEIGHT, initial_line=True,
-                camera_model=None, project_func=None, loss="l1"):
+                camera_model=None, project_func=None, loss="l1", link_scales=None):
     """build.py:28-304.  ``project_dir`` is the reference's: ``data/4_cam_scene_static_sba.json`` and ``data/*.h5`` are read
     from it (:97-109); alternatively pass ``scene = (k_arr, d_arr, r_arr, t_arr)`` and ``dlc_tables`` = one
     ``(bodyparts, values[frames, K, 3])`` per camera.  ``camera_model`` "fisheye" (the default) or "pinhole", or
@@ -147,7 +147,9 @@ def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_f
     ``camera_model`` and every triangulation here uses it.  ``loss``: the measurement loss the model states, kept as
     ``model.loss`` and read by every call on the model - "l1" (the reference's, :299) or "redescending" (its
     ``redescending_loss`` with a, b, c = 3, 10, 20 on the residuals scaled by 1 / ``r_meas``, commented out at :307; see
-    ``solve_models``).  Returns ``(model, pose_to_3d)`` as the reference does."""
+    ``solve_models``).  ``link_scales`` = (groups, scales): ``scale_links`` is applied to the compiled program (the result of
+    ``fit_link_scales`` for another subject than the one the skeleton file was measured on); None changes nothing.
+    Returns ``(model, pose_to_3d)`` as the reference does."""
     _loss_kind(loss)
     cam_model = calib.camera_model_of(camera_model, project_func)
     prog = skeleton.compile_skeleton(skel_dict)
@@ -202,9 +204,11 @@ def build_model(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, n_f
                           K=k_arr, D=d_arr, R=r_arr, t=t_arr, h=float(h), lo=lo, hi=hi, init_x=init_x,
                           start_frame=int(start_frame), model_weight=float(model_weight), pairing=pair, camera_model=cam_model,
                           loss=loss, x=None, info=None)
+    if link_scales is not None:
+        model = scale_links(model, link_scales[1], link_scales[0])
 
     def pose_to_3d(*states):
-        return np.asarray(skeleton.skeleton_fk(prog, np.asarray(states, dtype=np.float64)[None, :]))[0]
+        return np.asarray(skeleton.skeleton_fk(model.prog, np.asarray(states, dtype=np.float64)[None, :]))[0]
     return model, pose_to_3d
 
 
@@ -884,6 +888,208 @@ def _pose_fit_start(model, fit_kw):
     return init_x
 
 
+MAX_LINK_GROUPS = 16        # LSC_MAXK of csrc/skel_link_scale.hip
+
+
+def link_groups(prog, groups="links"):
+    """The group of every op of a link program as int32 [n_ops], -1 for an op whose offset stays fixed, and their number K.
+    ``groups``: "links" - one group per op with a non-zero offset, in program order (ValueError above 16: pass explicit
+    groups); "global" - one scale for every such op; or a sequence of n_ops ints in -1 .. K-1."""
+    ops = prog["ops"]
+    moving = [bool(np.any(np.asarray(op[5], dtype=np.float64) != 0.0)) for op in ops]
+    if isinstance(groups, str):
+        if groups == "links":
+            grp = np.full(len(ops), -1, dtype=np.int32)
+            grp[moving] = np.arange(sum(moving))
+            if sum(moving) > MAX_LINK_GROUPS:
+                raise ValueError(f"the skeleton has {sum(moving)} links with an offset; one scale per link is limited to "
+                                 f"{MAX_LINK_GROUPS}: pass explicit groups")
+        elif groups == "global":
+            grp = np.where(moving, 0, -1).astype(np.int32)
+        else:
+            raise ValueError("groups must be 'links', 'global' or one group index per op")
+    else:
+        grp = np.asarray(groups)
+        if grp.shape != (len(ops),) or not np.issubdtype(grp.dtype, np.integer):
+            raise ValueError(f"groups must hold one int per op of the link program ({len(ops)}), -1 for a fixed op")
+        grp = grp.astype(np.int32)
+    K = int(grp.max()) + 1 if grp.size else 0
+    if grp.size and grp.min() < -1 or not 1 <= K <= MAX_LINK_GROUPS:
+        raise ValueError(f"group indices must be -1 .. K-1 with K in 1..{MAX_LINK_GROUPS}")
+    return grp, K
+
+
+def scale_links(model, scales, groups="links"):
+    """A copy of ``model`` whose link program carries ``scales[group(k)] * off_k`` (``groups`` as ``link_groups``; an op of
+    group -1 keeps its offset).  The copy records ``link_groups`` and ``link_scales``; ``model`` is left as it is.  Scales are
+    applied to the program, not to ``skel["positions"]``: a skeleton that defines a part twice has no positions that give
+    every op its scaled offset."""
+    grp, K = link_groups(model.prog, groups)
+    s = np.asarray(scales, dtype=np.float64)
+    if s.shape != (K,) or not (np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError(f"scales must be {K} finite positive numbers, one per group")
+    ops = [op[:5] + (np.asarray(op[5], dtype=np.float64) * (s[g] if g >= 0 else 1.0),) for op, g in zip(model.prog["ops"], grp)]
+    return SkeletonModel(**{**model.__dict__, "prog": dict(model.prog, ops=ops), "link_groups": grp.copy(), "link_scales": s.copy()})
+
+
+def _pose_fit_centre(model, points, cov, x0, sigma_iso):
+    """m [N, n_active] of a ``pose_fit`` call: ``x0`` clipped to the box, or the kernel's own default start - what a call
+    whose single trial is refused returns; 0 in the frames without a point."""
+    act = np.asarray(model.active, dtype=np.int64)
+    if x0 is not None:
+        return np.clip(np.asarray(x0, dtype=np.float64), model.lo[:, act], model.hi[:, act])
+    start = pose_fit(model, points, cov, sigma_iso=sigma_iso, lam0=1e300, max_iter=1, return_cov=False)["x"]
+    return np.nan_to_num(calib._host(start), nan=0.0)
+
+
+def link_scale_system(model, points, cov, fit, groups="links", prior_sigma=np.pi, sigma_iso=0.01, m=None, return_sens=True):
+    """The Gauss-Newton system of the log-scales of ``model``'s links at the poses of ``fit`` = ``pose_fit(model, points, cov,
+    prior_sigma=..., sigma_iso=...)``, every frame's pose eliminated (include/acinoset_hip.h: acino_skel_link_scale; one launch
+    and a summing one).  ``model`` carries the current offsets (``scale_links``); ``groups`` as ``link_groups``; ``m``
+    [N, n_active] is the ridge centre of the fit - its ``x0`` clipped to the box; None: the fit's default start.  Returns a dict
+    of numpy arrays: S [K, K], r [K], cost and n_used (sums over the used frames, in frame order); S_frames [N, K, K],
+    r_frames [N, K], cost_frames [N], used [N] bool, status [N] (the fit's, 3 where a frame's matrix has no factor) and, with
+    ``return_sens``, sens [N, n_active, K] = d x / d theta (NaN for an unused frame)."""
+    if isinstance(points, dict):
+        if cov is not None:
+            raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
+        points, cov = points["points"], points["cov"]
+    grp, K = link_groups(model.prog, groups)
+    act = np.asarray(model.active, dtype=np.int32)
+    N, Pa, Lp = model.N, len(act), len(model.names)
+    if fte._shape(points) != (N, Lp, 3):
+        raise ValueError(f"points must be [{N}, {Lp}, 3] (model.N frames, one slot per pose)")
+    if cov is not None and fte._shape(cov) != (N, Lp, 3, 3):
+        raise ValueError(f"cov must be [{N}, {Lp}, 3, 3]")
+    for key, shape in (("x", (N, Pa)), ("pinned", (N, Pa)), ("status", (N,))):
+        if fte._shape(fit[key]) != shape:
+            raise ValueError(f"fit['{key}'] must be {list(shape)}: the result of pose_fit on this model")
+    if m is not None and fte._shape(m) != (N, Pa):
+        raise ValueError(f"m must be [{N}, {Pa}] (the active states)")
+    for name, val in (("prior_sigma", prior_sigma), ("sigma_iso", sigma_iso)):
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError(f"{name} must be finite and > 0")
+    sized = _skel_workspace(model, act, lib().acino_skel_link_scale_workspace_bytes)
+    dev = calib._dev()
+    if m is None:
+        m = _pose_fit_centre(model, points, cov, None, sigma_iso)
+    pts, cv = calib._to_dev(points, dev), None if cov is None else calib._to_dev(cov, dev)
+    x, mc = calib._to_dev(fit["x"], dev), calib._to_dev(m, dev)
+    u8 = lambda a: torch.as_tensor(a, device=dev).to(torch.uint8).contiguous()      # noqa: E731
+    pinned, status = u8(fit["pinned"]), u8(fit["status"])
+    f64, b8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+    S, r, F = torch.empty((N, K, K), **f64), torch.empty((N, K), **f64), torch.empty((N,), **f64)
+    used, fst = torch.empty((N,), **b8), torch.empty((N,), **b8)
+    sens = torch.empty((N, Pa, K), **f64) if return_sens else None
+    total = torch.zeros((K * K + K + 2,), **f64)
+    p, nbytes = sized
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    act_c, grp_c = (C.c_int32 * len(act))(*[int(a) for a in act]), (C.c_int32 * max(len(grp), 1))(*[int(g) for g in grp])
+    check(lib().acino_skel_link_scale(C.byref(p), _ops_array(model.prog), act_c, grp_c, K, float(prior_sigma), float(sigma_iso),
+                                      ptr(pts), ptr(cv), ptr(x), ptr(mc), ptr(pinned), ptr(status), N, ptr(S), ptr(r), ptr(F),
+                                      ptr(used), ptr(fst), ptr(sens), ptr(total), C.c_void_p((ws.data_ptr() + 255) // 256 * 256),
+                                      nbytes, stream_ptr()))
+    tot = total.cpu().numpy()
+    out = dict(S=tot[:K * K].reshape(K, K), r=tot[K * K:K * K + K], cost=float(tot[K * K + K]), n_used=int(tot[K * K + K + 1]),
+               S_frames=S.cpu().numpy(), r_frames=r.cpu().numpy(), cost_frames=F.cpu().numpy(), used=used.cpu().numpy().astype(bool),
+               status=fst.cpu().numpy(), groups=grp, sens=None)
+    if return_sens:
+        out["sens"] = sens.cpu().numpy()
+    return out
+
+
+def link_scale_step(S, r, theta, lam, prior_prec=0.0):
+    """One damped step on the observed groups: d = -(S_oo + lam I + prior_prec I)^-1 (r_o + prior_prec theta_o), 0 for a group
+    whose diagonal entry of S is 0 (no frame observes it).  Returns d [K] and observed [K]."""
+    obs = np.diag(S) > 0
+    d = np.zeros(len(r))
+    if obs.any():
+        Soo = S[np.ix_(obs, obs)] + (lam + prior_prec) * np.eye(int(obs.sum()))
+        d[obs] = -np.linalg.solve(Soo, r[obs] + prior_prec * theta[obs])
+    return d, obs
+
+
+def fit_link_scales(model, points=None, cov=None, groups="links", x0=None, scale_prior_sigma=None, max_outer=30, tol=1e-6,
+                    prior_sigma=1.0, max_iter=255, **fit_kw):
+    """The link lengths of ``model``'s skeleton from the 3-D points of a clip, with an error bar each: one scale s_g = exp(theta_g)
+    per group of links (``groups`` as ``link_groups``), the minimiser over all poses and theta of the summed ``pose_fit``
+    objective (plus theta^2 / (2 ``scale_prior_sigma``^2) per group when given).  ``points`` / ``cov`` as ``pose_fit`` takes
+    them; None: ``model_triangulation(model)``.  The points are metric - the cameras are calibrated - so scales are observable.
+
+    Outer Gauss-Newton on theta: ``pose_fit`` at the current scales (``prior_sigma``, ``max_iter``, ``fit_kw``), then
+    ``link_scale_system`` and the step -(S + lam I + prior)^-1 (r + prior); a step is accepted when the cost summed over the
+    frames both points use falls, otherwise lam is raised and the step tried again; stop on max |dtheta| < ``tol``.  The ridge
+    centre m of every pose fit is the first start (``x0`` clipped to the box, or the default start at the scales 1), so that
+    the objective does not move; every pose fit starts there.  A group with a zero diagonal entry of S - no frame has a point
+    below it - stays at 1 with ``observed`` False and ``std`` inf; the others are solved without it.
+
+    Returns a dict: scales [K]; cov_log_scales [K, K] = S_obs^-1 at the end point (zero rows and columns for unobserved
+    groups); std_scales = s sqrt(diag) (inf where unobserved); observed [K]; groups [n_ops]; model - the scaled copy, ready for
+    ``solve_models`` / ``pose_fit*``; fit - the pose fit at the end point; system - ``link_scale_system`` there; history - one
+    dict per outer step (cost, max_dtheta, lam, n_used, accepted); status "ok", "max_outer" or "no_frames"."""
+    grp, K = link_groups(model.prog, groups)
+    if scale_prior_sigma is not None and not (np.isfinite(scale_prior_sigma) and scale_prior_sigma > 0):
+        raise ValueError("scale_prior_sigma must be finite and > 0")
+    if int(max_outer) != max_outer or max_outer < 1 or not (np.isfinite(tol) and tol > 0):
+        raise ValueError("max_outer must be an integer >= 1 and tol > 0")
+    if points is None:
+        points = model_triangulation(model)
+    if isinstance(points, dict):
+        if cov is not None:
+            raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
+        points, cov = points["points"], points["cov"]
+    sigma_iso = fit_kw.get("sigma_iso", 0.01)
+    prec = 0.0 if scale_prior_sigma is None else 1.0 / float(scale_prior_sigma) ** 2
+    m = _pose_fit_centre(model, points, cov, x0, sigma_iso)
+
+    def evaluate(theta):
+        mdl = scale_links(model, np.exp(theta), grp)
+        fit = pose_fit(mdl, points, cov, x0=m, prior_sigma=prior_sigma, max_iter=max_iter, return_cov=False, **fit_kw)
+        fit = {k: calib._host(v) if k in ("x", "x_full", "positions", "cost") else np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+               for k, v in fit.items()}
+        return mdl, fit, link_scale_system(mdl, points, cov, fit, grp, prior_sigma=prior_sigma, sigma_iso=sigma_iso, m=m)
+
+    def cost_on(sys_, theta, frames):
+        return float(np.add.reduce(sys_["cost_frames"][frames])) + 0.5 * prec * float(theta @ theta)
+
+    theta = np.zeros(K)
+    cur = evaluate(theta)
+    lam, history, status = 0.0, [], "max_outer"
+    if cur[2]["n_used"] == 0:
+        status = "no_frames"
+    for _ in range(int(max_outer) if status != "no_frames" else 0):
+        sys_ = cur[2]
+        top = float(np.diag(sys_["S"]).max())
+        accepted = False
+        while True:
+            d, _obs = link_scale_step(sys_["S"], sys_["r"], theta, lam, prec)
+            step = float(np.abs(d).max())
+            if step < tol:
+                break
+            trial = evaluate(theta + d)
+            both = sys_["used"] & trial[2]["used"]
+            if both.any() and cost_on(trial[2], theta + d, both) < cost_on(sys_, theta, both):
+                theta, cur, accepted = theta + d, trial, True
+                lam = lam / 10.0 if lam > 1e-12 * top else 0.0
+                break
+            lam = max(10.0 * lam, 1e-3 * top)
+        history.append(dict(cost=cost_on(cur[2], theta, cur[2]["used"]), max_dtheta=step, lam=lam, n_used=cur[2]["n_used"],
+                            accepted=accepted))
+        if not accepted:
+            status = "ok"
+            break
+    mdl, fit, sys_ = cur
+    obs = np.diag(sys_["S"]) > 0
+    cov_t = np.zeros((K, K))
+    if obs.any():
+        cov_t[np.ix_(obs, obs)] = np.linalg.inv(sys_["S"][np.ix_(obs, obs)] + prec * np.eye(int(obs.sum())))
+    scales = np.exp(theta)
+    with np.errstate(invalid="ignore"):
+        std = np.where(obs, scales * np.sqrt(np.diag(cov_t)), np.inf)
+    return dict(scales=scales, cov_log_scales=cov_t, std_scales=std, observed=obs, groups=grp, model=mdl, fit=fit, system=sys_,
+                history=history, status=status)
+
+
 def pose_fit_pixels(model, x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=None, prior_sigma=np.pi, min_detections=2,
                     max_iter=100, ftol=1e-10, xtol=1e-10, lam0=1e-3, return_cov=True):
     """Per-frame pose of a ``SkeletonModel`` from the detections of every camera (include/acinoset_hip.h:
@@ -1225,7 +1431,7 @@ def _video_forehead(dlc_tables, idx, f0, f1, scene, lik_thresh, cam_model):
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
                 overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, pin_unobserved=False,
-                return_rate_cov=False, cov_cams=None, loss="l1", init="line", **kw):
+                return_rate_cov=False, cov_cams=None, loss="l1", init="line", link_scales=None, **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -1293,6 +1499,8 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     had (``init``).  The warm starts, the stages of the robust loss and everything after the solve are the same.  Any other
     value is a ValueError.
 
+    ``link_scales`` = (groups, scales): every window's model is built with them (``build_model``; None changes nothing).
+
     There is no ``n_samples`` here: a stitched video is not one posterior (every window has its own, and draws of neighbouring
     windows are independent); call ``model_samples`` on the windows' models."""
     _check_init(init)
@@ -1307,6 +1515,8 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
     cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
     build_kw["camera_model"] = cam_model
+    if link_scales is not None:
+        build_kw["link_scales"] = link_scales
     l1_eps = kw.get("l1_eps", 1e-2)
     if scene is None:
         scene = _load_scene(project_dir)

@@ -1055,6 +1055,34 @@ int acino_skel_pose_fit_px(const acino_pose_fit_px_params* prm, const acino_skel
                            uint8_t* d_iters, uint8_t* d_pinned, double* d_cov_x, double* d_pos, double* d_cov_pos,
                            double* d_std_pos, double* d_weight, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- link lengths of a skeleton from the pose fits of a clip (csrc/skel_link_scale.hip) -------------------------------
+ * One log-scale theta_g per group of links, off_k -> exp(theta_g(k)) off_k; h_group[n_ops] names the group of every op
+ * (0 .. n_groups-1, or -1 for an op whose offset stays fixed), n_groups = K in 1..16.  h_ops carries the CURRENT, already
+ * scaled, offsets: the derivative of a pose with respect to theta_g at that point is the sum of M_k off_k over the ops of
+ * group g on its path.  Per frame n with d_status[n] < 2, at the pose d_x[n] (the output of acino_skel_pose_fit on the same
+ * d_points / d_cov / prior_sigma / sigma_iso, d_m its ridge centre - read for p >= 3 only -, d_pinned its active set), the
+ * joint Gauss-Newton system of (pose, theta) with the pose eliminated on the free states F (lam = 0):
+ *   A = Jw^T Jw + kappa, B = Jw^T Js, C = Js^T Js, g = Jw^T u + kappa (x - m), c = Js^T u    (u: the whitened residuals)
+ *   d_S[N][K][K]   C - B_F^T A_FF^-1 B_F, symmetric bit for bit      d_r[N][K]   c - B_F^T A_FF^-1 g_F
+ *   d_F[N]         the pose fit's objective at d_x[n]                d_used[N]   1 where the frame entered
+ *   d_frame_status[N]  d_status[n], or 3 where A_FF has no Cholesky factor
+ *   d_sens[N][P][K]    -A_FF^-1 B_F, the pose's sensitivity to the log-scales; rows of pinned states exactly 0
+ * A frame with d_status[n] >= 2 or without a factor gets zeros in d_S, d_r and d_F, NaN in d_sens and d_used[n] = 0.  A
+ * group that no entering slot of the frame hangs on has exact zeros in its row and column of d_S and in d_r.
+ * d_total[K K + K + 2]: S, r, F and the number of used frames summed over the frames in frame order by a second launch, one
+ * entry per lane, no atomics: the same bits on every call.  d_sens and d_total may be NULL, as d_cov (sigma_iso is read then).
+ * d_ws: acino_skel_link_scale_workspace_bytes(p) bytes, 256-byte aligned (0: p is outside the limits).  Of p the fields that
+ * acino_skel_pose_fit reads.  n_groups outside 1..16, a group outside -1..K-1, a NULL required buffer and a shape whose LDS
+ * exceeds 160 KB are ACINO_ERR_INVALID_ARG before any device call; n_frames == 0 is a no-op.  No synchronisation. */
+size_t acino_skel_link_scale_workspace_bytes(const acino_skel_fte_params* p);
+int acino_skel_link_scale(const acino_skel_fte_params* p, const acino_skel_op* h_ops, const int32_t* h_active,
+                          const int32_t* h_group /* [n_ops] */, int n_groups, double prior_sigma, double sigma_iso,
+                          const double* d_points /* [N][n_pose][3] */, const double* d_cov /* [N][n_pose][3][3] or NULL */,
+                          const double* d_x, const double* d_m /* [N][P] */, const uint8_t* d_pinned /* [N][P] */,
+                          const uint8_t* d_status /* [N] */, int64_t n_frames, double* d_S, double* d_r, double* d_F,
+                          uint8_t* d_used, uint8_t* d_frame_status, double* d_sens, double* d_total, void* d_ws,
+                          size_t ws_bytes, void* stream);
+
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
  * 75 = 3 x 25 [pose | velocity | acceleration], pose parameters in the order of qb_list (:734-746).  d_det is
