@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, calib, fte, io, skeleton
-from ._lib import SkelFteInfo, SkelFteParams, SkelOp, check, lib, ptr, stream_ptr
+from ._lib import MAX_CAMS, PoseFitPxParams, SkelFteInfo, SkelFteParams, SkelOp, check, lib, ptr, stream_ptr
 
 MODEL_WEIGHT = 0.002        # build.py:186-191
 R_MEAS = 3.0                # :142
@@ -1028,10 +1028,7 @@ def fit_link_scales(model, points=None, cov=None, groups="links", x0=None, scale
     ``solve_models`` / ``pose_fit*``; fit - the pose fit at the end point; system - ``link_scale_system`` there; history - one
     dict per outer step (cost, max_dtheta, lam, n_used, accepted); status "ok", "max_outer" or "no_frames"."""
     grp, K = link_groups(model.prog, groups)
-    if scale_prior_sigma is not None and not (np.isfinite(scale_prior_sigma) and scale_prior_sigma > 0):
-        raise ValueError("scale_prior_sigma must be finite and > 0")
-    if int(max_outer) != max_outer or max_outer < 1 or not (np.isfinite(tol) and tol > 0):
-        raise ValueError("max_outer must be an integer >= 1 and tol > 0")
+    _check_outer(scale_prior_sigma, max_outer, tol)
     if points is None:
         points = model_triangulation(model)
     if isinstance(points, dict):
@@ -1039,15 +1036,35 @@ def fit_link_scales(model, points=None, cov=None, groups="links", x0=None, scale
             raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
         points, cov = points["points"], points["cov"]
     sigma_iso = fit_kw.get("sigma_iso", 0.01)
-    prec = 0.0 if scale_prior_sigma is None else 1.0 / float(scale_prior_sigma) ** 2
     m = _pose_fit_centre(model, points, cov, x0, sigma_iso)
 
     def evaluate(theta):
         mdl = scale_links(model, np.exp(theta), grp)
-        fit = pose_fit(mdl, points, cov, x0=m, prior_sigma=prior_sigma, max_iter=max_iter, return_cov=False, **fit_kw)
-        fit = {k: calib._host(v) if k in ("x", "x_full", "positions", "cost") else np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
-               for k, v in fit.items()}
+        fit = _host_fit(pose_fit(mdl, points, cov, x0=m, prior_sigma=prior_sigma, max_iter=max_iter, return_cov=False, **fit_kw))
         return mdl, fit, link_scale_system(mdl, points, cov, fit, grp, prior_sigma=prior_sigma, sigma_iso=sigma_iso, m=m)
+
+    return _fit_link_scales(evaluate, grp, K, scale_prior_sigma, max_outer, tol)
+
+
+def _host_fit(fit):
+    """The dict of a per-frame fit on the host: the floating-point outputs through ``calib._host``, the rest as numpy."""
+    return {k: calib._host(v) if k in ("x", "x_full", "positions", "cost") else np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+            for k, v in fit.items()}
+
+
+def _check_outer(scale_prior_sigma, max_outer, tol):
+    if scale_prior_sigma is not None and not (np.isfinite(scale_prior_sigma) and scale_prior_sigma > 0):
+        raise ValueError("scale_prior_sigma must be finite and > 0")
+    if int(max_outer) != max_outer or max_outer < 1 or not (np.isfinite(tol) and tol > 0):
+        raise ValueError("max_outer must be an integer >= 1 and tol > 0")
+
+
+def _fit_link_scales(evaluate, grp, K, scale_prior_sigma, max_outer, tol):
+    """The outer loop of ``fit_link_scales`` and ``fit_link_scales_pixels``: ``evaluate(theta)`` returns (scaled model, pose fit,
+    system) at the log-scales theta - the system the dict of ``link_scale_system``.  The damped step on the observed groups,
+    the acceptance on the frames both points use, the lam rule, the stop on max |dtheta| < ``tol``, ``observed``,
+    ``cov_log_scales``, the history and the returned dict."""
+    prec = 0.0 if scale_prior_sigma is None else 1.0 / float(scale_prior_sigma) ** 2
 
     def cost_on(sys_, theta, frames):
         return float(np.add.reduce(sys_["cost_frames"][frames])) + 0.5 * prec * float(theta @ theta)
@@ -1088,6 +1105,117 @@ def fit_link_scales(model, points=None, cov=None, groups="links", x0=None, scale
         std = np.where(obs, scales * np.sqrt(np.diag(cov_t)), np.inf)
     return dict(scales=scales, cov_log_scales=cov_t, std_scales=std, observed=obs, groups=grp, model=mdl, fit=fit, system=sys_,
                 history=history, status=status)
+
+
+def _pixel_start(model, x0):
+    """The start of ``pose_fit_pixels`` on ``model`` clipped to the box, [N, n_active]: ``x0``, or the chain of its default."""
+    act = np.asarray(model.active, dtype=np.int64)
+    if x0 is None:
+        init_x = _pose_fit_start(model, {})
+        if init_x is None:
+            raise ValueError("no frame has a pose fit to start from (no slot was triangulated in the whole clip): pass x0")
+        x0 = init_x[:, act]
+    return np.clip(np.asarray(calib._host(x0), dtype=np.float64), model.lo[:, act], model.hi[:, act])
+
+
+def link_scale_system_pixels(model, fit, groups="links", det=None, thresh=0.5, f_scale=5.0, sigma_px=None, prior_sigma=np.pi,
+                             m=None, return_sens=True):
+    """``link_scale_system`` for the objective of ``pose_fit_pixels``: the Gauss-Newton system of the log-scales of ``model``'s
+    links at the poses of ``fit`` = ``pose_fit_pixels(model, det=..., thresh=..., f_scale=..., sigma_px=..., prior_sigma=...)``,
+    every frame's pose eliminated (include/acinoset_hip.h: acino_skel_link_scale_px; one launch and a summing one).  No
+    triangulation stands between a detection and a length: a link whose far end one camera sees at a time is constrained in
+    every such frame.  The residuals carry the IRLS weights w = 1 / (1 + r^2 / f^2) at the fit's x: r is the exact gradient of
+    the summed Cauchy cost in theta at the minimising poses, S its Gauss-Newton curvature.  ``model`` carries the current offsets
+    (``scale_links``); ``groups`` as ``link_groups``; ``det``, ``thresh``, ``f_scale``, ``sigma_px`` and their defaults as
+    ``pose_fit_pixels``; ``m`` [N, n_active] is the ridge centre of the fit - its ``x0`` clipped to the box; None: the chain of
+    the fit's default start.  Works on a rig of any size; on one camera a global scale is a null direction (S = 0 for
+    ``groups="global"``).  Returns the dict of ``link_scale_system``."""
+    grp, K = link_groups(model.prog, groups)
+    act = np.asarray(model.active, dtype=np.int32)
+    N, Pa, Lp, Cn = model.N, len(act), len(model.names), int(np.shape(model.meas)[1])
+    camera_model = getattr(model, "camera_model", "fisheye")
+    if camera_model not in calib.CAMERAS:
+        raise ValueError(f"the model's camera_model must be one of {calib.CAMERA_MODELS}")
+    if det is not None and fte._shape(det) != (N, Cn, Lp, 3):
+        raise ValueError(f"det must be [{N}, {Cn}, {Lp}, 3] (model.N frames, the model's cameras, one slot per pose)")
+    if not 1 <= Cn <= MAX_CAMS:
+        raise ValueError(f"the model holds {Cn} cameras: 1..{MAX_CAMS} are supported")
+    for key, shape in (("x", (N, Pa)), ("pinned", (N, Pa)), ("status", (N,))):
+        if fte._shape(fit[key]) != shape:
+            raise ValueError(f"fit['{key}'] must be {list(shape)}: the result of pose_fit_pixels on this model")
+    if m is not None and fte._shape(m) != (N, Pa):
+        raise ValueError(f"m must be [{N}, {Pa}] (the active states)")
+    if sigma_px is None:
+        sigma_px = _model_sigma_px(model)
+    for name, val in (("prior_sigma", prior_sigma), ("f_scale", f_scale), ("sigma_px", sigma_px)):
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError(f"{name} must be finite and > 0")
+    if np.isnan(thresh):
+        raise ValueError("thresh must not be NaN")
+    recs = calib.camera_records(camera_model, model.K, model.D, model.R, model.t)
+    sized = _skel_workspace(model, act, lib().acino_skel_link_scale_px_workspace_bytes)
+    dev = calib._dev()
+    if m is None:
+        m = _pixel_start(model, None)
+    d = calib._to_dev(_model_detections(model) if det is None else det, dev)
+    cams = torch.as_tensor(recs, device=dev)
+    x, mc = calib._to_dev(fit["x"], dev), calib._to_dev(m, dev)
+    u8 = lambda a: torch.as_tensor(a, device=dev).to(torch.uint8).contiguous()      # noqa: E731
+    pinned, status = u8(fit["pinned"]), u8(fit["status"])
+    f64, b8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
+    S, r, F = torch.empty((N, K, K), **f64), torch.empty((N, K), **f64), torch.empty((N,), **f64)
+    used, fst = torch.empty((N,), **b8), torch.empty((N,), **b8)
+    sens = torch.empty((N, Pa, K), **f64) if return_sens else None
+    total = torch.zeros((K * K + K + 2,), **f64)
+    p, nbytes = sized
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    act_c, grp_c = (C.c_int32 * len(act))(*[int(a) for a in act]), (C.c_int32 * max(len(grp), 1))(*[int(g) for g in grp])
+    prm = PoseFitPxParams(calib.CAMERAS[camera_model].code, 1, 1, 0, 1e-3, 1e-10, 1e-10, float(prior_sigma), float(thresh),
+                          float(f_scale), float(sigma_px))
+    check(lib().acino_skel_link_scale_px(C.byref(prm), C.byref(p), _ops_array(model.prog), act_c, grp_c, K, ptr(d), N, Cn, ptr(cams),
+                                         ptr(x), ptr(mc), ptr(pinned), ptr(status), ptr(S), ptr(r), ptr(F), ptr(used), ptr(fst),
+                                         ptr(sens), ptr(total), C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
+    tot = total.cpu().numpy()
+    out = dict(S=tot[:K * K].reshape(K, K), r=tot[K * K:K * K + K], cost=float(tot[K * K + K]), n_used=int(tot[K * K + K + 1]),
+               S_frames=S.cpu().numpy(), r_frames=r.cpu().numpy(), cost_frames=F.cpu().numpy(), used=used.cpu().numpy().astype(bool),
+               status=fst.cpu().numpy(), groups=grp, sens=None)
+    if return_sens:
+        out["sens"] = sens.cpu().numpy()
+    return out
+
+
+def fit_link_scales_pixels(model, groups="links", x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=None,
+                           scale_prior_sigma=None, max_outer=30, tol=1e-6, prior_sigma=1.0, max_iter=255, **fit_kw):
+    """``fit_link_scales`` on the detections themselves: the link lengths of ``model``'s skeleton as the minimiser, over all poses
+    and one log-scale per group of links (``groups`` as ``link_groups``), of the summed ``pose_fit_pixels`` objective (plus
+    theta^2 / (2 ``scale_prior_sigma``^2) per group when given), with an error bar each.  ``det``, ``thresh``, ``f_scale``,
+    ``sigma_px`` and their defaults as ``pose_fit_pixels``; ``fit_kw`` goes to it (``min_detections``, ``ftol``, ...).
+
+    The outer loop is that of ``fit_link_scales``: ``pose_fit_pixels`` at the current scales (``prior_sigma``, ``max_iter``), then
+    ``link_scale_system_pixels`` and the damped step.  ``x0`` [N, n_active] is the first start; None: the chain of
+    ``pose_fit_pixels`` at the scales 1.  The ridge centre of every pose fit is that first start clipped to the box, and every
+    pose fit starts there, so that the objective does not move.
+
+    One camera cannot tell a larger animal further away from a smaller one nearer: on a model of one camera this raises
+    ValueError unless ``scale_prior_sigma`` is given.  Returns the dict of ``fit_link_scales``."""
+    grp, K = link_groups(model.prog, groups)
+    _check_outer(scale_prior_sigma, max_outer, tol)
+    if int(np.shape(model.meas)[1]) == 1 and scale_prior_sigma is None:
+        raise ValueError("one camera does not determine the size of the skeleton (a larger animal further away gives the same "
+                         "pixels): pass scale_prior_sigma")
+    if sigma_px is None:
+        sigma_px = _model_sigma_px(model)
+    if det is None:
+        det = _model_detections(model)
+    m = _pixel_start(model, x0)
+    px = dict(det=det, thresh=thresh, f_scale=f_scale, sigma_px=sigma_px, prior_sigma=prior_sigma)
+
+    def evaluate(theta):
+        mdl = scale_links(model, np.exp(theta), grp)
+        fit = _host_fit(pose_fit_pixels(mdl, x0=m, max_iter=max_iter, return_cov=False, **px, **fit_kw))
+        return mdl, fit, link_scale_system_pixels(mdl, fit, grp, m=m, **px)
+
+    return _fit_link_scales(evaluate, grp, K, scale_prior_sigma, max_outer, tol)
 
 
 def pose_fit_pixels(model, x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=None, prior_sigma=np.pi, min_detections=2,

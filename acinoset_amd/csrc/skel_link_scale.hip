@@ -18,11 +18,9 @@
 // slot hangs on - gives exact zeros throughout.  The factor stays in registers (row i in lane i); Y and v come from its
 // forward substitution, four columns at a time; Y^T Y and Y^T v are summed over the states in state order, one entry per lane.
 // k_link_scale_total then adds the frames up in frame order, one entry per lane: no atomics, the same bits on every call.
-#include "pose_fit_skel.hpp"
+#include "link_scale_dev.hpp"
 
 namespace acino {
-
-constexpr int LSC_MAXK = 16;
 
 struct LinkScaleArgs {
   const SkelDev* dev;
@@ -123,18 +121,6 @@ __device__ __forceinline__ void lsc_scale_jacobian(const Spf& S, const unsigned 
     o[2] = w2;
   }
   __syncthreads();
-}
-
-// v <- L^-1 v for NC right-hand sides at once, lane p holding entry p of each: the forward half of pf_solve
-template <int N, int NC>
-__device__ __forceinline__ void lsc_forward(const double (&r)[N], double dinv, double (&v)[NC], int lane) {
-#pragma unroll
-  for (int k = 0; k < N; ++k)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const double zk = pf_readlane(v[c] * dinv, k);
-      v[c] = lane == k ? zk : (lane > k ? v[c] - r[k] * zk : v[c]);
-    }
 }
 
 template <int PT>
@@ -319,6 +305,13 @@ __global__ void __launch_bounds__(320) k_link_scale_total(const double* __restri
   total[t] = sum;
 }
 
+int lsc_launch_total(const double* d_S, const double* d_r, const double* d_F, const uint8_t* d_used, int64_t n_frames, int K,
+                     double* d_total, hipStream_t s) {
+  hipLaunchKernelGGL(k_link_scale_total, dim3(1), dim3(320), 0, s, d_S, d_r, d_F, d_used, n_frames, K, d_total);
+  ACINO_LAUNCH_CHECK();
+  return ACINO_OK;
+}
+
 }  // namespace acino
 
 using namespace acino;
@@ -361,10 +354,7 @@ int acino_skel_link_scale(const acino_skel_fte_params* p, const acino_skel_op* h
         return spf_launch(k_skel_link_scale<decltype(pt)::value>, attr, n_frames, lds, s, a);
       }))
     return rc;
-  if (d_total) {
-    hipLaunchKernelGGL(k_link_scale_total, dim3(1), dim3(320), 0, s, d_S, d_r, d_F, d_used, n_frames, n_groups, d_total);
-    ACINO_LAUNCH_CHECK();
-  }
+  if (d_total) return lsc_launch_total(d_S, d_r, d_F, d_used, n_frames, n_groups, d_total, s);
   return ACINO_OK;
 }
 

@@ -1083,6 +1083,32 @@ int acino_skel_link_scale(const acino_skel_fte_params* p, const acino_skel_op* h
                           uint8_t* d_used, uint8_t* d_frame_status, double* d_sens, double* d_total, void* d_ws,
                           size_t ws_bytes, void* stream);
 
+/* ---- link lengths of a skeleton from the pixel pose fits of a clip (csrc/skel_link_scale_px.hip) -----------------------
+ * acino_skel_link_scale for the objective of acino_skel_pose_fit_px: the groups, h_ops (the CURRENT offsets), the outputs,
+ * d_total, the group rules and their messages are acino_skel_link_scale's; the measurement - prm, d_det [N][C][n_pose][3],
+ * n_cams, d_cams - is acino_skel_pose_fit_px's.  Per frame n with d_status[n] < 2, at the pose d_x[n] (the output of
+ * acino_skel_pose_fit_px on the same d_det / d_cams / prm, d_m its ridge centre - its start clipped to the box, read for
+ * p >= 3 only -, d_pinned its active set) and with the IRLS weights w = 1 / (1 + r^2 / f^2) at d_x[n]:
+ *   Jc  = sqrt(w) / sigma_px (J_pi R_c) G_l,   Jsc = sqrt(w) / sigma_px (J_pi R_c) d_gl    (d_gl: d pose_l / d theta_g)
+ *   A = sum_c Jc^T Jc + kappa, B = sum_c Jc^T Jsc, C = sum_c Jsc^T Jsc, g = sum_c Jc^T u + kappa (x - m), c = sum_c Jsc^T u
+ *   d_S = C - B_F^T A_FF^-1 B_F (symmetric bit for bit),  d_r = c - B_F^T A_FF^-1 g_F,  d_sens = -A_FF^-1 B_F
+ *   d_F[N]  the pixel pose fit's objective at d_x[n] (the Cauchy cost and the ridge)
+ * g and c carry w r, the exact gradient of the Cauchy cost: d_r is the derivative of min_x F_n in theta to first order; d_S
+ * is the IRLS Gauss-Newton curvature.  A group that no valid detection of the frame hangs on has exact zeros in its row and
+ * column of d_S and in d_r.  Of prm: thresh, f_scale, sigma_px, prior_sigma and camera_model are read; the block is checked
+ * as acino_skel_pose_fit_px checks it (max_iter, min_detections, lam0, ftol, xtol must be valid and are not read).
+ * d_ws: acino_skel_link_scale_px_workspace_bytes(p) bytes, 256-byte aligned (0: p is outside the limits).  A shape whose LDS
+ * exceeds 160 KB is refused, like every other invalid argument, before any device call; n_frames == 0 is a no-op.  Two
+ * launches (one 64-lane wave per frame; the sums), no atomics, no synchronisation. */
+size_t acino_skel_link_scale_px_workspace_bytes(const acino_skel_fte_params* p);
+int acino_skel_link_scale_px(const acino_pose_fit_px_params* prm, const acino_skel_fte_params* p, const acino_skel_op* h_ops,
+                             const int32_t* h_active, const int32_t* h_group /* [n_ops] */, int n_groups,
+                             const double* d_det /* [N][C][n_pose][3] */, int64_t n_frames, int n_cams, const double* d_cams,
+                             const double* d_x, const double* d_m /* [N][P] */, const uint8_t* d_pinned /* [N][P] */,
+                             const uint8_t* d_status /* [N] */, double* d_S, double* d_r, double* d_F, uint8_t* d_used,
+                             uint8_t* d_frame_status, double* d_sens, double* d_total, void* d_ws, size_t ws_bytes,
+                             void* stream);
+
 /* ---- extended Kalman filter + RTS smoother (src/all_optimizations.py:569-865) ---------
  * One call filters and smooths n_seq independent sequences of n_frames frames (same rig).  States are the reference's
  * 75 = 3 x 25 [pose | velocity | acceleration], pose parameters in the order of qb_list (:734-746).  d_det is
