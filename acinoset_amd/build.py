@@ -635,6 +635,143 @@ def _attach_calibration(out, models, xs, cov_cams, l1_eps, pin_unobserved, with_
             res["std_pos_total"] = np.sqrt(res["std_pos"] ** 2 + res["std_pos_calib"] ** 2)
 
 
+LINK_KEYS = ("sens_links", "dpos_links", "cov_x_links", "cov_pos_links", "std_pos_links")
+
+
+def link_cov_matrix(cov, K):
+    """A covariance of the K link log-scales as ``(sigma, unknown)``: a checked float64 numpy [K, K] matrix and a bool [K] mask of
+    the groups whose length nothing bounds (None, None for None).  ``cov``: a [K, K] array or tensor - a wrong shape, a
+    non-finite entry or an asymmetric matrix is a ValueError, ``unknown`` is all False - or the dict ``fit_link_scales`` /
+    ``fit_link_scales_pixels`` return: its ``cov_log_scales`` is used, and every group with ``observed`` False gets zero rows and
+    columns and is flagged ``unknown`` (the fit left it at scale 1 with an infinite bar).  Host arithmetic, no launch."""
+    if cov is None:
+        return None, None
+    unknown = np.zeros(int(K), dtype=bool)
+    if isinstance(cov, dict):
+        if "cov_log_scales" not in cov or "observed" not in cov:
+            raise ValueError('cov_links given as a dict must hold "cov_log_scales" and "observed" (the dict of fit_link_scales)')
+        obs = np.asarray(cov["observed"], dtype=bool)
+        if obs.shape != (int(K),):
+            raise ValueError(f"cov_links: observed must be [{int(K)}] (one flag per group), got {tuple(obs.shape)}")
+        unknown = ~obs
+        cov = cov["cov_log_scales"]
+    a = cov.detach().cpu().numpy() if isinstance(cov, torch.Tensor) else np.asarray(cov)
+    a = np.array(a, dtype=np.float64)
+    if a.shape != (int(K), int(K)):
+        raise ValueError(f"cov_links must be [{int(K)}, {int(K)}] (one log-scale per group of links), got {tuple(a.shape)}")
+    a[unknown, :] = 0.0
+    a[:, unknown] = 0.0
+    if not np.isfinite(a).all():
+        raise ValueError("cov_links has a non-finite entry")
+    if not np.allclose(a, a.T, rtol=1e-12, atol=1e-12 * max(float(np.abs(a).max()), 1e-300)):
+        raise ValueError("cov_links is not symmetric")
+    return np.ascontiguousarray(a), unknown
+
+
+def _refuse_robust_links(models):
+    for m in models:
+        if model_loss(m) != "l1":
+            raise ValueError(f"the link sensitivity (cov_links) is defined for the l1 loss only; the model's loss is {model_loss(m)!r}")
+
+
+def _link_inputs(model, groups, cov_links):
+    """(grp [n_ops], K, sigma, unknown) of a link-sensitivity call, checked on the host.  ``groups`` None: those the dict of a
+    length fit carries, else "links"."""
+    if groups is None:
+        groups = cov_links["groups"] if isinstance(cov_links, dict) and "groups" in cov_links else "links"
+    grp, K = link_groups(model.prog, groups)
+    return (grp, K) + link_cov_matrix(cov_links, K)
+
+
+def model_link_sensitivity(models, xs, groups="links", cov_links=None, l1_eps=1e-2, pin_unobserved=False):
+    """The link lengths' share of the skeleton solve's error bars at the iterates ``xs`` (one [N, P] array per model, the layout of
+    ``results["x"]``): acino_skel_fte_link_sensitivity, all models in ONE batched call.  theta_g is the log-scale of group g of
+    the link program's ops (``groups`` as ``link_groups``: "links", "global" or one index per op), theta = 0 the offsets the
+    models carry - e.g. the scaled copy a length fit returns.  With A the matrix of ``model_covariance`` (Fisher blocks with w^2,
+    smoothness prior, bound pins; ``pin_unobserved`` as there), ``sens_links`` [N, P, K] = S = -A^-1 G is the shift of the minimiser
+    of the expected (Fisher) quadratic model per unit log-scale (weights w^2: neither the residuals nor ``l1_eps`` enter G; not a
+    derivative of the L1 / LM end point), and ``dpos_links`` [N, n_pose, 3, K] = T_l = G_l S_n + D_l is what a pose does: it moves
+    through the states AND directly, D_l[:, g] the sum of the rotated link vectors of group g on the slot's path.
+    ``cov_links``: whatever ``link_cov_matrix`` takes - a [K, K] covariance of the log-scales, or the dict of ``fit_link_scales`` /
+    ``fit_link_scales_pixels``, whose unobserved groups are flagged unknown; a malformed one is a ValueError before any launch.
+    Returns one dict per model: ``sens_links``, ``cov_x_links`` [N, P, P] = S_n Sigma S_n^T - both in the full-state layout, zero
+    rows (and columns) outside ``model.active`` and, exactly, at pinned variables -, ``dpos_links``, ``cov_pos_links``
+    [N, n_pose, 3, 3] = T_l Sigma T_l^T, ``std_pos_links`` [N, n_pose] = sqrt(trace) in metres - the three covariance keys None
+    without ``cov_links`` -, ``groups`` [n_ops] and ``status`` (0, or 5: singular clip, NaN arrays; for ONE model a RuntimeError, as
+    ``model_covariance``).  A pose slot below an unknown group has ``std_pos_links`` = +inf and NaN ``cov_pos_links``; its column of
+    ``sens_links`` is reported all the same.  With ``pin_unobserved`` every dict carries ``unobserved`` and a pose slot that depends
+    on such a state has ``std_pos_links`` = +inf and NaN ``cov_pos_links``.
+
+    The total is ``cov + cov_links`` (``std_pos_total = sqrt(std_pos^2 + std_pos_links^2)``) ONLY for a length covariance that came
+    from other data than the clips being solved, or for an honest prior; lengths fitted to the same clip have errors correlated
+    with the trajectory's and the sum is not valid.  The term is perfectly correlated across frames: smoothing does not average
+    it out."""
+    return _links(models, xs, groups, cov_links, l1_eps, pin_unobserved)
+
+
+def _links(models, xs, groups, cov_links, l1_eps, pin_unobserved, raise_numeric=True):
+    """model_link_sensitivity.  ``raise_numeric=False``: a singular single clip is reported in its ``status`` like a clip of a
+    batch (solve_video's one-window case)."""
+    if len(models) == 0:
+        raise ValueError("no models")
+    _refuse_robust_links(models)
+    grp, K, sigma, unknown = _link_inputs(models[0], groups, cov_links)
+    pin = bool(pin_unobserved)
+    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_link_workspace_bytes(C.byref(p), B, int(pin)), l1_eps=l1_eps)
+    m0, act, dev = models[0], io_["act"], io_["dev"]
+    B, N, P = len(models), m0.N, m0.P
+    Pa, Lp = len(act), len(m0.names)
+    empty = lambda *shape: torch.empty((B, N) + shape, dtype=torch.float64, device=dev)   # noqa: E731
+    sig_d = None if sigma is None else torch.as_tensor(sigma, dtype=torch.float64, device=dev).contiguous()
+    unk_d = None if sigma is None or not unknown.any() else torch.as_tensor(unknown.astype(np.uint8), device=dev).contiguous()
+    sens, dpos = empty(Pa, K), empty(Lp, 3, K)
+    cov_x, cov_pos, std_pos = (None, None, None) if sigma is None else (empty(Pa, Pa), empty(Lp, 3, 3), empty(Lp))
+    status = (C.c_int32 * B)()
+    mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev) if pin else None
+    grp_c = (C.c_int32 * max(len(grp), 1))(*[int(g) for g in grp])
+    rc = lib().acino_skel_fte_link_sensitivity(*io_["head"], grp_c, K, ptr(sig_d), ptr(unk_d), ptr(sens), ptr(dpos), ptr(cov_x),
+                                               ptr(cov_pos), ptr(std_pos), status, *io_["tail"], int(pin), ptr(mask))
+    if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
+        check(rc)
+    sh, dh = sens.cpu().numpy(), dpos.cpu().numpy()
+    out = []
+    for i in range(B):
+        full = np.zeros((N, P, K))
+        full[:, act] = sh[i]
+        out.append(dict(sens_links=full, dpos_links=dh[i], cov_x_links=None, cov_pos_links=None, std_pos_links=None, groups=grp.copy(),
+                        status=int(status[i])))
+    if sigma is not None:
+        ch, ph, th = cov_x.cpu().numpy(), cov_pos.cpu().numpy(), std_pos.cpu().numpy()
+        for i, o in enumerate(out):
+            full = np.zeros((N, P, P))
+            full[:, act[:, None], act[None, :]] = ch[i]
+            o.update(cov_x_links=full, cov_pos_links=ph[i], std_pos_links=th[i])
+    if pin:
+        for o, un in zip(out, _unobserved_lists(mask, act)):
+            o["unobserved"] = un
+    return out
+
+
+def _check_links(models, cov_links, groups):
+    """What a solve entry checks of ``cov_links`` / ``link_groups`` before it solves; True when either keyword is in use."""
+    if cov_links is None and groups is None:
+        return False
+    if len(models):
+        _refuse_robust_links(models)
+        _link_inputs(models[0], groups, cov_links)
+    return True
+
+
+def _total_std(res):
+    """std_pos_total of a ``results`` that holds ``std_pos``: the shares that are there (``std_pos_links``, ``std_pos_calib``), in
+    quadrature."""
+    var = res["std_pos"] ** 2
+    for key in ("std_pos_links", "std_pos_calib"):
+        if res.get(key) is not None:
+            var = var + res[key] ** 2
+    return np.sqrt(var)
+
+
 REPROJ_KEYS = ("uv", "cov_uv", "std_uv", "res", "mahal2", "flags", "weight")
 
 
@@ -1274,7 +1411,7 @@ def pose_fit_pixels(model, x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=
 
 def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
                  return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
-                 return_rate_cov=False, cov_cams=None, l1_start=True, init="line"):
+                 return_rate_cov=False, cov_cams=None, l1_start=True, init="line", cov_links=None, link_groups=None):
     """The GPU solve of SEVERAL ``SkeletonModel`` s of the same skeleton, cameras and length in one call
     (acino_skel_fte_solve_batch: one workgroup per clip in the banded factorisation, a Levenberg-Marquardt controller per clip
     on the device).  ``x0``: None or one [N, P] array per model.  Returns ``[(results, info), ...]`` in the order of ``models``.
@@ -1298,6 +1435,16 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     ``model_calibration_sensitivity`` at the returned ``x`` join every ``results`` (one more batched call), and with
     ``return_cov`` also ``std_pos_total`` = sqrt(std_pos^2 + std_pos_calib^2) - valid only for a calibration that came from other
     data than these clips.  Without ``cov_cams`` the keys are what they were.
+    ``cov_links`` (whatever ``link_cov_matrix`` takes: a [K, K] covariance of the links' log-scales, or the dict of a length fit; a
+    malformed one is a ValueError before the solve) and ``link_groups`` (``groups`` of ``model_link_sensitivity``; None: those of
+    the dict, else "links"): ``sens_links``, ``dpos_links``, ``cov_x_links``, ``cov_pos_links`` and ``std_pos_links`` of
+    ``model_link_sensitivity`` at the returned ``x`` join every ``results`` (one more batched call), and with ``return_cov``
+    ``std_pos_total`` = sqrt(std_pos^2 + std_pos_links^2 [+ std_pos_calib^2 when ``cov_cams`` is given too]) - valid only for
+    lengths that came from other data than these clips, or an honest prior.  ``link_groups`` without ``cov_links`` gives
+    ``sens_links`` and ``dpos_links`` alone (the three covariance keys None): there is no Sigma of the links, and ``std_pos_total``
+    stays what it is without them - absent, or with ``cov_cams`` the two-term calibration total.  Refused for models of the
+    redescending loss.
+    Without the two keywords the keys are what they were.
 
     Models whose ``loss`` is "redescending" (``build_model(loss=...)``; one batch, one loss) are solved under the redescending
     measurement loss - a wrong detection above the likelihood threshold stops pulling once it is far enough off (beyond c = 20
@@ -1319,6 +1466,7 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     if len(models) and cov_cams is not None:
         _refuse_robust_calibration(models)
         calib.cov_cams_matrix(cov_cams, int(models[0].meas.shape[1]))      # (a malformed matrix fails before the solve, not after)
+    with_links = _check_links(models, cov_links, link_groups)
     lm = dict(max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol, l1_eps=l1_eps, lam_max=lam_max)
     if len(models) and l1_start and all(model_loss(m) != "l1" for m in models):
         first = _lm_solve([_with_loss(m, "l1") for m in models], x0, **lm)
@@ -1339,6 +1487,11 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
                                         cov_pos=[r["cov_pos"] for r, _i in out] if return_cov else None, l1_eps=l1_eps), REPROJ_KEYS)
     if cov_cams is not None:
         _attach_calibration(out, models, xs_out, cov_cams, l1_eps, pin_unobserved, with_total=bool(return_cov))
+    if with_links:
+        _attach(out, _links(models, xs_out, link_groups, cov_links, l1_eps, pin_unobserved), LINK_KEYS + ("unobserved",))
+        if return_cov and cov_links is not None:
+            for res, _info in out:
+                res["std_pos_total"] = _total_std(res)
     return out
 
 
@@ -1365,7 +1518,7 @@ def _lm_solve(models, x0, **lm):
 
 def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10, gtol=1e-8, l1_eps=1e-2, lam_max=1e16,
                 return_cov=False, n_samples=0, sample_seed=0, return_reprojection=False, pin_unobserved=False,
-                return_rate_cov=False, cov_cams=None, l1_start=True, init="line"):
+                return_rate_cov=False, cov_cams=None, l1_start=True, init="line", cov_links=None, link_groups=None):
     """The GPU solve of a ``SkeletonModel`` (acino_skel_fte_solve).  Returns (results, info): ``results`` has the layout of
     ``convert_to_dict`` (positions [N, n_pose, 3], x / dx / ddx [N, P]); states outside ``model.active`` keep their initial
     values - which must be 0, as in the reference's initialisation (:215-222).  A numeric failure raises (one clip: the
@@ -1375,12 +1528,14 @@ def solve_model(model, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-10,
     ``pin_unobserved``: as ``solve_models`` (only together with ``return_cov`` or ``n_samples``; ``results["unobserved"]``).
     ``return_rate_cov``: the bars of ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``) join ``results``.
     ``cov_cams``: the calibration's share (``model_calibration_sensitivity``; ``std_pos_total`` with ``return_cov``), as
-    ``solve_models``.  A model whose ``loss`` is "redescending" is solved in two stages, L1 first (``l1_start``, ``info["l1"]``), as
-    ``solve_models`` describes.  ``init``: "line" or "pose_fit", as ``solve_models``."""
+    ``solve_models``.  ``cov_links`` / ``link_groups``: the link lengths' share (``model_link_sensitivity``; it joins
+    ``std_pos_total``), as ``solve_models``.  A model whose ``loss`` is "redescending" is solved in two stages, L1 first
+    (``l1_start``, ``info["l1"]``), as ``solve_models`` describes.  ``init``: "line" or "pose_fit", as ``solve_models``."""
     return solve_models([model], None if x0 is None else [x0], max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol,
                         l1_eps=l1_eps, lam_max=lam_max, return_cov=return_cov, n_samples=n_samples, sample_seed=sample_seed,
                         return_reprojection=return_reprojection, pin_unobserved=pin_unobserved,
-                        return_rate_cov=return_rate_cov, cov_cams=cov_cams, l1_start=l1_start, init=init)[0]
+                        return_rate_cov=return_rate_cov, cov_cams=cov_cams, l1_start=l1_start, init=init, cov_links=cov_links,
+                        link_groups=link_groups)[0]
 
 
 def solve_model_parallel(model, x0=None, window=N_FRAMES, outer_max=40, xtol_outer=1e-7, first_max_iter=30, later_max_iter=30,
@@ -1559,7 +1714,7 @@ def _video_forehead(dlc_tables, idx, f0, f1, scene, lik_thresh, cam_model):
 
 def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, first_frame=None, last_frame=None, window=N_FRAMES,
                 overlap=20, warm_px=15.0, warm_passes=3, return_cov=False, return_reprojection=False, gate=None, pin_unobserved=False,
-                return_rate_cov=False, cov_cams=None, loss="l1", init="line", link_scales=None, **kw):
+                return_rate_cov=False, cov_cams=None, loss="l1", init="line", link_scales=None, cov_links=None, link_groups=None, **kw):
     """A whole video as the reference would have to do it - windows of ``window`` frames (build.py:131-133: N = 100), here
     ALL of them in one batched GPU solve: consecutive windows overlap by ``overlap`` frames and every frame is taken from
     the window in which it lies deepest.  An extension (the reference solves one window per run): the initial point of a
@@ -1614,6 +1769,12 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     ``positions``, and with ``return_cov`` ``std_pos_total`` = sqrt(std_pos^2 + std_pos_calib^2).  A singular window gives NaN
     for its frames, as with ``return_cov``.  It is NOT passed on to the windows' solves.
 
+    ``cov_links`` / ``link_groups`` (as ``solve_models``; checked before the solve, refused with ``loss="redescending"``): ONE batched
+    ``model_link_sensitivity`` call over all windows at their final iterates; ``results`` gains ``sens_links`` [frames, P, K],
+    ``dpos_links`` [frames, n_pose, 3, K], ``cov_x_links``, ``cov_pos_links`` and ``std_pos_links`` (None without ``cov_links``), every
+    frame from the window that supplied its ``positions``, and with ``return_cov`` ``std_pos_total`` = sqrt(std_pos^2 +
+    std_pos_links^2 [+ std_pos_calib^2]).  A singular window gives NaN for its frames.  Not passed on to the windows' solves.
+
     ``loss="redescending"``: the windows are built, solved, retried and warm-started exactly as above under L1 - which window
     is kept and ``mean_abs_residual_px`` are the L1 stage's - then ONE batched robust call (``solve_models`` on the same windows
     with ``loss="redescending"``, ``l1_start=False``) runs from the windows' L1 end states before the stitching, and everything
@@ -1639,6 +1800,8 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     _loss_kind(loss)
     if loss != "l1" and cov_cams is not None:
         raise ValueError(f"the calibration sensitivity (cov_cams) is defined for the l1 loss only; loss is {loss!r}")
+    if loss != "l1" and (cov_links is not None or link_groups is not None):
+        raise ValueError(f"the link sensitivity (cov_links) is defined for the l1 loss only; loss is {loss!r}")
     kw.pop("l1_start", None)                                  # (the stages are this function's own)
     build_kw = {k: kw.pop(k) for k in ("h", "pairing", "lik_thresh", "r_meas", "model_weight") if k in kw}
     cam_model = calib.camera_model_of(kw.pop("camera_model", None), kw.pop("project_func", None))
@@ -1662,6 +1825,7 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
     head = _video_forehead(dlc_tables, idx, f0, f1, scene, build_kw.get("lik_thresh", LIK_THRESH), cam_model)
     models = [build_model(skel_dict, project_dir, scene=scene, dlc_tables=dlc_tables, n_frames=window, start_frame=st,
                           initial_line=head is None, **build_kw)[0] for st in starts]
+    with_links = _check_links(models, cov_links, link_groups)   # (a malformed matrix fails before the solve, not after)
     x0s = [m.init_x.copy() for m in models]
     for st, x0 in zip(starts, x0s if head is not None else []):
         x0[:, :3] = head[st - f0:st - f0 + window]
@@ -1708,6 +1872,12 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
         results.update(_stitch(owner, starts, f0, cals, CALIB_KEYS, fill=np.nan))
         if return_cov:
             results["std_pos_total"] = np.sqrt(results["std_pos"] ** 2 + results["std_pos_calib"] ** 2)
+    if with_links:
+        lks = _links(models, xs_final, link_groups, cov_links, l1_eps, pin_unobserved, raise_numeric=False)
+        given = tuple(k for k in LINK_KEYS if lks[0][k] is not None)
+        results.update({k: None for k in LINK_KEYS}, **_stitch(owner, starts, f0, lks, given, fill=np.nan))
+        if return_cov and cov_links is not None:
+            results["std_pos_total"] = _total_std(results)
     if return_reprojection:                                   # one clip of all the frames, every frame's detections its owner's
         lo_t, hi_t = bounds_table(skel_dict, total)
         seen = _stitch(owner, starts, f0, [m.__dict__ for m in models], ("meas", "weights"))
@@ -1747,7 +1917,8 @@ def solve_optimisation(model, exe_path=None, project_dir=None, poses=None, **sol
     ``return_reprojection=True`` the image-space report of ``model_reprojection``, ``return_rate_cov=True`` the error bars of
     ``dx``, ``ddx`` and the pose velocities (``model_covariance(rates=True)``), ``pin_unobserved=True`` pins the unobserved
     states in those (``results["unobserved"]``), ``cov_cams=Sigma`` adds the calibration's share of the bars
-    (``model_calibration_sensitivity``); the saved pickle keeps the reference's four entries.  A model built with
+    (``model_calibration_sensitivity``), ``cov_links=Sigma`` (with ``link_groups``) the link lengths' share
+    (``model_link_sensitivity``); the saved pickle keeps the reference's four entries.  A model built with
     ``loss="redescending"`` is solved in two stages (``solve_models``: ``l1_start``, ``info["l1"]``)."""
     results, info = solve_model(model, **solver_kw)
     model.x, model.info = results, info

@@ -376,6 +376,13 @@ static int skel_fwdsub_launch(int B, long long S, const SkelDev* d_dev, const Sk
   return ACINO_OK;
 }
 
+int skel_launch_fwdsub(int PT, int n_clips, long long n_cols, const SkelDev* d_dev, const SkelClip* d_clip, const double* d_band,
+                       const unsigned char* d_fxm, const double* d_b, double* d_y, hipStream_t s) {
+  return skel_dispatch_pt(PT, [&](auto pt) {
+    return skel_fwdsub_launch<decltype(pt)::value>(n_clips, n_cols, d_dev, d_clip, d_band, d_fxm, d_b, d_y, s);
+  });
+}
+
 }  // namespace acino
 
 using namespace acino;
@@ -446,10 +453,7 @@ int acino_skel_fte_calibration_sensitivity(const acino_skel_fte_params* p, int n
                      lds_rhs, s, d_dev, d_x, d_meas, d_w, D(lay.opv), d_fxm, d_b);
   ACINO_LAUNCH_CHECK();
   if ((rc = skel_launch_factor(PT, B, d_dev, d_clip, D(lay.band), D(lay.diag0), s))) return rc;
-  rc = skel_dispatch_pt(PT, [&](auto pt) {
-    return skel_fwdsub_launch<decltype(pt)::value>(B, W, d_dev, d_clip, D(lay.band), d_fxm, d_b, d_y, s);
-  });
-  if (rc) return rc;
+  if ((rc = skel_launch_fwdsub(PT, B, W, d_dev, d_clip, D(lay.band), d_fxm, d_b, d_y, s))) return rc;
   if ((rc = skel_launch_back_columns(PT, B, W, d_dev, d_clip, D(lay.band), d_fxm, d_y, d_b, s))) return rc;
   hipLaunchKernelGGL(k_skel_calib_combine, dim3((unsigned)NT), dim3(256), lds_comb, s, d_dev, d_clip, d_b, d_cov_cams, D(lay.opv),
                      d_unobs, d_sens, d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal);

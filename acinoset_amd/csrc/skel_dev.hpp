@@ -1,6 +1,6 @@
 // What the generic-skeleton kernels share - skel_fte.hip (the solve), skel_cov.hip (covariance and observability at an iterate),
-// skel_sample.hip (joint samples), skel_calib.hip (the sensitivity to the extrinsics) and skel_reproj.hip (the image-space
-// report): the device-resident problem description, the controller state of a clip, the bound-active rule, the link program's forward kinematics, the parameter checks and the
+// skel_sample.hip (joint samples), skel_calib.hip (the sensitivity to the extrinsics), skel_links.hip (the sensitivity to the
+// link lengths) and skel_reproj.hip (the image-space report): the device-resident problem description, the controller state of a clip, the bound-active rule, the link program's forward kinematics, the parameter checks and the
 // host-side compilation of the link program into SkelDev.  The host layer on top of it (entry checks, upload, dispatch,
 // read-back) is skel_host.hpp.
 #pragma once
@@ -86,7 +86,8 @@ __device__ __forceinline__ void skel_pose_row(const SkelDev& D, const double* __
 }
 
 // column p of the pose Jacobian G_l (3 x n_act) of slot l: [I | d(M off)/d(angle) of the ops on the slot's path], from the link
-// operators opv[n_ops][4][3] the assembly leaves (k_skel_cov_pose, k_skel_calib_rhs, k_skel_calib_combine)
+// operators opv[n_ops][4][3] the assembly leaves (k_skel_cov_pose, k_skel_calib_rhs, k_skel_calib_combine, k_skel_links_rhs,
+// k_skel_links_combine)
 __device__ __forceinline__ void skel_pose_jac_col(const SkelDev& D, const double* __restrict__ opv, int l, int p, double (&gc)[3]) {
   gc[0] = p == 0 ? 1.0 : 0.0;
   gc[1] = p == 1 ? 1.0 : 0.0;

@@ -1,7 +1,7 @@
 // What the uses of the skeleton FTE's Fisher matrix share (skel_cov.hip: the selected inverse; skel_sample.hip: joint
-// posterior samples; skel_calib.hip: the sensitivity to the extrinsics): the 16 x 16 tile product, the banded block Cholesky
-// A = L L^T as a device function template, the shape of the triangular solves on it, the workspace layout and the launches
-// that build the band at an iterate.
+// posterior samples; skel_calib.hip: the sensitivity to the extrinsics; skel_links.hip: the sensitivity to the link lengths):
+// the 16 x 16 tile product, the banded block Cholesky A = L L^T as a device function template, the shape of the triangular
+// solves on it, the workspace layout and the launches that build the band at an iterate.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -139,7 +139,8 @@ __device__ __forceinline__ void skel_band_factor(int N, double* __restrict__ ban
 }
 
 // ---- the triangular solves on the factor, 64 right-hand-side columns per workgroup: k_skel_sample_back (skel_sample.hip,
-//      L^-T) and k_skel_fwdsub (skel_calib.hip, L^-1) share the shape of a workgroup and the LDS layout of the blocks
+//      L^-T) and k_skel_fwdsub (skel_calib.hip, L^-1) share the shape of a workgroup and the LDS layout of the blocks;
+//      skel_links.hip launches both through their host launchers below
 constexpr int SKS_W = 4, SKS_T = 64 * SKS_W, SKS_PANEL = 16 * SKS_W;
 
 template <int PT>
@@ -177,6 +178,10 @@ int skel_cov_read_status(const SkelClip* d_clip, int n_clips, hipStream_t s, int
 // k_skel_factor<PT> on stream s (skel_sample.hip), one workgroup per clip: band <- the factor, a failed pivot -> status 5.
 int skel_launch_factor(int PT, int n_clips, const SkelDev* d_dev, SkelClip* d_clip, double* d_band, const double* d_diag0,
                        hipStream_t s);
+// k_skel_fwdsub<PT> on stream s (skel_calib.hip): d_y[b][c] = L_b^-1 d_b[b][c] for the n_cols columns [n_clips][n_cols][N][n_act]
+// (pinned and padding rows of d_b masked to 0 on the way in; a clip whose status is not 0 is left as it is).
+int skel_launch_fwdsub(int PT, int n_clips, long long n_cols, const SkelDev* d_dev, const SkelClip* d_clip, const double* d_band,
+                       const unsigned char* d_fxm, const double* d_b, double* d_y, hipStream_t s);
 // k_skel_sample_back<PT> without the "+ x" on stream s: d_out[b][c] = L_b^-T d_y[b][c] for the n_cols columns
 // [n_clips][n_cols][N][n_act] (the layout of the sampler's z, pinned rows masked to 0; NaN for a clip whose status is not 0).
 int skel_launch_back_columns(int PT, int n_clips, long long n_cols, const SkelDev* d_dev, const SkelClip* d_clip,

@@ -1,0 +1,371 @@
+// Sensitivity of a generic-skeleton FTE trajectory to the link lengths (gfx950, fp64): S = -A^-1 G, the poses' total derivative
+// T_l = G_l S_n + D_l and the "consider" covariances S Sigma S^T, T_l Sigma T_l^T they give for a covariance Sigma of the links'
+// log-scales (acinoset_hip.h: acino_skel_fte_link_sensitivity).  theta_g is the log-scale of group g of the link program's ops
+// (build.link_groups; K <= SKL_MAXK = 16 groups, -1: an op whose offset stays fixed), theta = 0 the model's current offsets:
+//   pos_l(x, theta) = root + sum_{k on l's path} exp(theta_g(k)) M_k(x) off_k
+//   D_l[:, g] = d pos_l / d theta_g = sum_{k in pmask[l], g(k) = g} opv[k][0]      (the rotated link vectors, in program order)
+//   G_n[p, g] = sum_c sum_l G_l[:, p] . (w^2 J_pi^T J_pi) D_l[:, g]               (Fisher weights w^2, the statement A makes)
+// A, the bound pins, pin_unobserved and the status rules are those of skel_cov.hip and skel_calib.hip; the smoothness prior does
+// not depend on theta.  A pose moves through the states AND directly: leaving D_l out of T_l is the obvious mistake.
+//   k_skel_assemble<.., double>, k_skel_cov_build   skel_cov.hip's (skel_cov_launch_build): band, pin mask, opv of every frame
+//   k_skel_links_rhs<PINHOLE>  one workgroup per frame of every clip, as k_skel_calib_rhs: poses from opv (program order), G_l
+//                           (skel_pose_jac_col) and D_l into LDS, per slot Mw_l = sum_c w^2 (ju ju^T + jv jv^T) in camera order
+//                           with the assembly's dropped rows (w = 0, non-finite measurement, |z_cam| < 1e-9), V_l,g = Mw_l D_l[:, g]
+//                           in the place of D_l, then -G_n[p, g] = -sum_l G_l[:, p] . V_l,g in slot order, no atomics, as column g
+//                           of the right-hand side [B][K][N][n_act]; rows of pinned variables 0.
+//                           Known slack, left because the kernel is 0.17 ms of a 9 ms call (78 clips of 100 frames): the Mw_l
+//                           stage is one thread per pose slot, so at most 65 of the 256 threads work in it (a thread per
+//                           (camera, slot) with a sum in camera order would fill more), and skel_link_direct scans all n_ops
+//                           for every (l, i, g) where per-group op lists would not.
+//                           LDS: (n_ops 12 + n_pose 3 + n_pose 3 n_act + n_pose 3 K + n_pose 9) doubles, at most 134 KB.
+//   k_skel_factor<PT>, k_skel_fwdsub<PT>, k_skel_sample_back<PT, false>   the solves of skel_calib.hip, through their host launchers
+//                           (skel_launch_factor, skel_launch_fwdsub, skel_launch_back_columns); K <= 16 columns are one ragged
+//                           panel with one wave busy.
+//   k_skel_links_combine    one workgroup per frame: S_n [n_act][K] out, T = S_n Sigma (Sigma is only PSD - a held group has zero
+//                           rows - and is multiplied, never factored), cov_x_links = T S_n^T on one triangle and mirrored; then per
+//                           pose slot (one wave each) G_l and D_l, T_l = G_l S_n + D_l [3][K] out, T_l Sigma, T_l Sigma T_l^T on its
+//                           upper triangle, mirrored, and sqrt(trace).  With pin_unobserved a slot that depends on an unobserved
+//                           state gets +inf / NaN (k_skel_cov_pose's rule); so does a slot whose path holds an op of a group the
+//                           caller marks `unknown`.  A singular clip: NaN in every output.
+//                           The products are K <= 16 wide (3 x K per slot, n_act x K per frame): fractions of one 16 x 16 x 4 MFMA
+//                           tile, so they are plain fp64 FMAs from LDS; the rows of S_n and T are padded to an odd length (K | 1)
+//                           so that lanes walking down a column fall on different banks.
+//                           LDS: (2 n_act (K | 1) + n_act (n_act + 1) + K^2 + n_ops 12 + 4 (3 n_act + 6 K + 9)) doubles, 67 KB at
+//                           the limits.
+// No workgroup waits for another; vector stores only; the result of a clip is the same bits whatever else shares the call (every
+// kernel's arithmetic on a clip reads that clip's data alone).
+#include <cstddef>
+#include <cstdint>
+
+#include "skel_factor.hpp"
+
+namespace acino {
+
+constexpr int SKL_MAXK = 16;       // groups of links: MAX_LINK_GROUPS of build.py, LSC_MAXK of skel_link_scale.hip
+
+struct SkelLinkGroups {            // by value to both kernels
+  unsigned long long gm[SKL_MAXK]; // per group: its ops
+  int32_t K, pad;
+};
+
+constexpr size_t skel_links_rhs_doubles(size_t n_ops, size_t n_pose, size_t P, size_t K) {
+  return n_ops * 12 + n_pose * 3 + n_pose * 3 * P + n_pose * 3 * K + n_pose * 9;
+}
+constexpr size_t skel_links_combine_doubles(size_t n_ops, size_t P, size_t K) {
+  return 2 * P * (K | 1) + P * (P + 1) + K * K + n_ops * 12 + 4 * (3 * P + 6 * K + 9);
+}
+static_assert(sizeof(double) * skel_links_rhs_doubles(ACINO_SKEL_MAX_OPS, ACINO_SKEL_MAX_OPS + 1, SK_MAXP, SKL_MAXK) <= 160 * 1024 &&
+                  sizeof(double) * skel_links_combine_doubles(ACINO_SKEL_MAX_OPS, SK_MAXP, SKL_MAXK) <= 160 * 1024,
+              "LDS of k_skel_links_rhs / k_skel_links_combine at the limits");
+
+// D_l[i, g]: coordinate i of the sum of the rotated link vectors of group g's ops on slot l's path, in program order
+__device__ __forceinline__ double skel_link_direct(const SkelDev& D, const SkelLinkGroups& grp, const double* __restrict__ opv, int l,
+                                                   int i, int g) {
+  const unsigned long long ops = D.pmask[l] & grp.gm[g];
+  double acc = 0.0;
+  for (int k = 0; k < D.n_ops; ++k)
+    if ((ops >> k) & 1ull) acc += opv[k * 12 + i];
+  return acc;
+}
+
+template <bool PINHOLE>
+__global__ void __launch_bounds__(256)
+k_skel_links_rhs(const SkelDev* __restrict__ dev, const SkelLinkGroups grp, const double* __restrict__ x, const double* __restrict__ meas,
+                 const double* __restrict__ wgt, const double* __restrict__ opv_all, const unsigned char* __restrict__ fxm,
+                 double* __restrict__ rhs) {
+  extern __shared__ __attribute__((aligned(16))) double skl_smem[];
+  const SkelDev& D = *dev;
+  const int tid = threadIdx.x, n = blockIdx.x;
+  const int P = D.n_act, PT = D.PT, C = D.n_cams, NPOSE = D.n_pose, NOPS = D.n_ops, N = D.n_frames, K = grp.K;
+  double* opv = skl_smem;                                    // [n_ops][4][3]
+  double* pos = opv + NOPS * 12;                             // [n_pose][3]
+  double* G = pos + NPOSE * 3;                               // [(l * 3 + i) * P + p]
+  double* V = G + (size_t)NPOSE * 3 * P;                     // [(l * 3 + i) * K + g]: D_l, then Mw_l D_l
+  double* Mw = V + (size_t)NPOSE * 3 * K;                    // [l * 9 + i * 3 + j]
+  for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
+  __syncthreads();
+  if (tid < 3) {                                             // poses, coordinate by coordinate, in program order
+    const double root = x[(size_t)n * P + tid];
+    for (int s = 0; s < NPOSE; ++s) pos[s * 3 + tid] = root;
+    for (int k = 0; k < NOPS; ++k) pos[D.op[k].child * 3 + tid] = pos[D.op[k].parent * 3 + tid] + opv[(k * 4) * 3 + tid];
+  }
+  for (int e = tid; e < NPOSE * P; e += 256) {
+    const int l = e / P, p = e - l * P;
+    double gc[3];
+    skel_pose_jac_col(D, opv, l, p, gc);
+    G[(l * 3) * P + p] = gc[0];
+    G[(l * 3 + 1) * P + p] = gc[1];
+    G[(l * 3 + 2) * P + p] = gc[2];
+  }
+  for (int e = tid; e < NPOSE * 3 * K; e += 256) {
+    const int li = e / K, g = e - li * K;
+    V[e] = skel_link_direct(D, grp, opv, li / 3, li % 3, g);
+  }
+  __syncthreads();
+  for (int l = tid; l < NPOSE; l += 256) {                   // Mw_l: the cameras in their order
+    const double px = pos[l * 3], py = pos[l * 3 + 1], pz = pos[l * 3 + 2];
+    double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int c = 0; c < C; ++c) {
+      const size_t e = ((size_t)n * C + c) * NPOSE + l;
+      const double um = meas[2 * e], vm = meas[2 * e + 1];
+      double w = wgt[e];
+      if (!(m_finite(um) && m_finite(vm))) w = 0.0;
+      const auto& cam = cam_rec<PINHOLE>(D, c);
+      const double* Rc = cam.R;
+      const double* tc = cam.t;
+      const double xc = Rc[0] * px + Rc[1] * py + Rc[2] * pz + tc[0];
+      const double yc = Rc[3] * px + Rc[4] * py + Rc[5] * pz + tc[1];
+      const double zc = Rc[6] * px + Rc[7] * py + Rc[8] * pz + tc[2];
+      if (fabs(zc) < 1e-9) w = 0.0;
+      if (w == 0.0) continue;
+      double uv[2], jc[2][3];                                              // (the pixel itself is not used here)
+      project_jac(cam, xc, yc, zc, uv, jc);
+      double ju[3], jv[3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        ju[j] = jc[0][0] * Rc[j] + jc[0][1] * Rc[3 + j] + jc[0][2] * Rc[6 + j];
+        jv[j] = jc[1][0] * Rc[j] + jc[1][1] * Rc[3 + j] + jc[1][2] * Rc[6 + j];
+      }
+      const double w2 = w * w;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) m[i * 3 + j] += w2 * (ju[i] * ju[j] + jv[i] * jv[j]);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Mw[l * 9 + k] = m[k];
+  }
+  __syncthreads();
+  for (int e = tid; e < NPOSE * K; e += 256) {               // V_l,g = Mw_l D_l[:, g], in place: a thread owns its (l, g)
+    const int l = e / K, g = e - l * K;
+    const double d0 = V[(l * 3) * K + g], d1 = V[(l * 3 + 1) * K + g], d2 = V[(l * 3 + 2) * K + g];
+    const double* M = Mw + l * 9;
+    V[(l * 3) * K + g] = M[0] * d0 + M[1] * d1 + M[2] * d2;
+    V[(l * 3 + 1) * K + g] = M[3] * d0 + M[4] * d1 + M[5] * d2;
+    V[(l * 3 + 2) * K + g] = M[6] * d0 + M[7] * d1 + M[8] * d2;
+  }
+  __syncthreads();
+  const int b = n / N, nl = n - b * N;
+  for (int task = tid; task < K * P; task += 256) {
+    const int g = task / P, p = task - g * P;
+    double acc = 0.0;
+    if (!fxm[(size_t)n * PT + p]) {
+      for (int l = 0; l < NPOSE; ++l) {
+        acc += G[(l * 3) * P + p] * V[(l * 3) * K + g];
+        acc += G[(l * 3 + 1) * P + p] * V[(l * 3 + 1) * K + g];
+        acc += G[(l * 3 + 2) * P + p] * V[(l * 3 + 2) * K + g];
+      }
+      acc = -acc;
+    }
+    rhs[(((size_t)b * K + g) * N + nl) * P + p] = acc;
+  }
+}
+
+// sol: [n_clips][K][N][n_act] (the columns of -A^-1 G); sigma: [K][K] or NULL; unknown: [K] or NULL; unobs: NULL, or the clips'
+// masks [n_clips][P]
+__global__ void __launch_bounds__(256)
+k_skel_links_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip, const SkelLinkGroups grp,
+                     const double* __restrict__ sol, const double* __restrict__ sigma, const unsigned char* __restrict__ unknown,
+                     const double* __restrict__ opv_all, const unsigned char* __restrict__ unobs, double* __restrict__ sens,
+                     double* __restrict__ dpos, double* __restrict__ cov_x, double* __restrict__ cov_pos, double* __restrict__ std_pos) {
+  extern __shared__ __attribute__((aligned(16))) double skl_smem[];
+  const SkelDev& D = *dev;
+  const int n = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, N = D.n_frames, K = grp.K, LDK = K | 1, LDC = P + 1;
+  const int b = n / N, nl = n - b * N;
+  if (clip[b].status != 0) {
+    const double nan = __builtin_nan("");
+    for (int e = tid; e < P * K; e += 256)
+      if (sens) sens[(size_t)n * P * K + e] = nan;
+    for (int e = tid; e < NPOSE * 3 * K; e += 256)
+      if (dpos) dpos[(size_t)n * NPOSE * 3 * K + e] = nan;
+    for (int e = tid; e < P * P; e += 256)
+      if (cov_x) cov_x[(size_t)n * P * P + e] = nan;
+    for (int e = tid; e < NPOSE * 9; e += 256)
+      if (cov_pos) cov_pos[(size_t)n * NPOSE * 9 + e] = nan;
+    for (int e = tid; e < NPOSE; e += 256)
+      if (std_pos) std_pos[(size_t)n * NPOSE + e] = nan;
+    return;
+  }
+  double* Sm = skl_smem;                                     // S_n [P][LDK]
+  double* Tm = Sm + (size_t)P * LDK;                         // S_n Sigma [P][LDK]
+  double* Cx = Tm + (size_t)P * LDK;                         // cov_x_links [P][P + 1]
+  double* Sg = Cx + (size_t)P * LDC;                         // Sigma [K][K]
+  double* opv = Sg + K * K;                                  // [n_ops][4][3]
+  double* Gw = opv + NOPS * 12 + wave * (3 * P + 6 * K + 9); // this wave's G_l [3][P], T_l [3][K], T_l Sigma [3][K], out [9]
+  double* Tl = Gw + 3 * P;
+  double* Ts = Tl + 3 * K;
+  double* out9 = Ts + 3 * K;
+  for (int e = tid; e < P * K; e += 256) {
+    const int col = e / P, p = e - col * P;
+    Sm[p * LDK + col] = sol[(((size_t)b * K + col) * N + nl) * P + p];
+  }
+  if (sigma)
+    for (int e = tid; e < K * K; e += 256) Sg[e] = sigma[e];
+  __syncthreads();
+  if (sens)
+    for (int e = tid; e < P * K; e += 256) sens[(size_t)n * P * K + e] = Sm[(e / K) * LDK + e % K];
+  if (sigma && cov_x) {
+    for (int e = tid; e < P * K; e += 256) {
+      const int p = e / K, j = e - p * K;
+      double acc = 0.0;
+      for (int i = 0; i < K; ++i) acc += Sm[p * LDK + i] * Sg[i * K + j];
+      Tm[p * LDK + j] = acc;
+    }
+    __syncthreads();
+    for (int e = tid; e < P * P; e += 256) {
+      const int p = e / P, q = e - p * P;
+      if (p <= q) {
+        double acc = 0.0;
+        for (int j = 0; j < K; ++j) acc += Tm[p * LDK + j] * Sm[q * LDK + j];
+        Cx[p * LDC + q] = acc;
+        Cx[q * LDC + p] = acc;
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < P * P; e += 256) cov_x[(size_t)n * P * P + e] = Cx[(e / P) * LDC + e % P];
+  }
+  if (!dpos && !cov_pos && !std_pos) return;
+  const bool want_cov = sigma && (cov_pos || std_pos);
+  for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
+  __syncthreads();
+  for (int l0 = 0; l0 < NPOSE; l0 += 4) {                   // a wave is one pose slot; no workgroup barrier inside
+    const int l = l0 + wave;
+    if (l >= NPOSE) break;
+    bool dep = false;
+    if (lane < P) {
+      double gc[3];
+      skel_pose_jac_col(D, opv, l, lane, gc);
+      Gw[lane] = gc[0];
+      Gw[P + lane] = gc[1];
+      Gw[2 * P + lane] = gc[2];
+      if (unobs) dep = unobs[(size_t)b * P + lane] && (gc[0] != 0.0 || gc[1] != 0.0 || gc[2] != 0.0);
+    }
+    if (unknown && lane < K) dep = dep || (unknown[lane] && (D.pmask[l] & grp.gm[lane]) != 0ull);
+    const bool undet = __any(dep ? 1 : 0) != 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 3 * K) {                                      // T_l = G_l S_n + D_l: the states' share in state order, then the direct term
+      const int i = lane / K, g = lane - i * K;
+      double acc = 0.0;
+      for (int p = 0; p < P; ++p) acc += Gw[i * P + p] * Sm[p * LDK + g];
+      acc += skel_link_direct(D, grp, opv, l, i, g);
+      Tl[lane] = acc;
+      if (dpos) dpos[((size_t)n * NPOSE + l) * 3 * K + lane] = acc;
+    }
+    if (!want_cov) {
+      __builtin_amdgcn_wave_barrier();
+      continue;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 3 * K) {
+      const int i = lane / K, j = lane - i * K;
+      double acc = 0.0;
+      for (int g = 0; g < K; ++g) acc += Tl[i * K + g] * Sg[g * K + j];
+      Ts[lane] = acc;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 6) {                                          // the upper triangle, mirrored
+      const int i = lane < 3 ? 0 : (lane < 5 ? 1 : 2), j = lane < 3 ? lane : (lane < 5 ? lane - 2 : 2);
+      double s = 0.0;
+      for (int g = 0; g < K; ++g) s += Ts[i * K + g] * Tl[j * K + g];
+      out9[3 * i + j] = s;
+      out9[3 * j + i] = s;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 9 && cov_pos) cov_pos[((size_t)n * NPOSE + l) * 9 + lane] = undet ? __builtin_nan("") : out9[lane];
+    if (lane == 0 && std_pos)
+      std_pos[(size_t)n * NPOSE + l] = undet ? __builtin_inf() : sqrt(fmax(out9[0] + out9[4] + out9[8], 0.0));
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+}  // namespace acino
+
+using namespace acino;
+
+static size_t skl_column_bytes(const acino_skel_fte_params* p, int n_clips) {
+  return skel_align256(sizeof(double) * (size_t)n_clips * SKL_MAXK * p->n_frames * p->n_active);
+}
+
+extern "C" {
+
+size_t acino_skel_fte_link_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved) {
+  const size_t cov = acino_skel_fte_covariance_pinned_workspace_bytes(p, n_clips, pin_unobserved);
+  if (cov == 0) return 0;
+  return cov + 2 * skl_column_bytes(p, n_clips);
+}
+
+int acino_skel_fte_link_sensitivity(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                    const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                    const double* d_lo, const double* d_hi, const double* d_x, const int32_t* h_group, int n_groups,
+                                    const double* d_cov_links, const uint8_t* d_unknown, double* d_sens, double* d_dpos,
+                                    double* d_cov_x, double* d_cov_pos, double* d_std_pos, int32_t* h_status, void* d_ws,
+                                    size_t ws_bytes, void* stream, int pin_unobserved, uint8_t* d_unobserved) {
+  int rc = skel_check_batch(p, n_clips, true, camera_model, h_ops && h_active && d_meas && d_w && d_cams && d_lo && d_hi && d_x && d_ws);
+  if (rc) return rc;
+  // (the cross term G carries the Fisher weights w^2 of the L1 model; its counterpart under the redescending loss is not built)
+  ACINO_REQUIRE(p->loss == ACINO_SKEL_LOSS_L1, "the link sensitivity is defined for the L1 loss only (loss = redescending)");
+  ACINO_REQUIRE(pin_unobserved == 0 || pin_unobserved == 1, "pin_unobserved: 0 or 1");
+  ACINO_REQUIRE(d_sens || d_dpos || d_cov_x || d_cov_pos || d_std_pos,
+                "at least one of d_sens, d_dpos, d_cov_x, d_cov_pos, d_std_pos");
+  ACINO_REQUIRE(d_cov_links || !(d_cov_x || d_cov_pos || d_std_pos), "a cov / std output needs d_cov_links");
+  ACINO_REQUIRE(n_groups >= 1 && n_groups <= SKL_MAXK, "n_groups must be 1..16");
+  ACINO_REQUIRE(h_group != nullptr || p->n_ops == 0, "null buffer (h_group)");
+  SkelLinkGroups grp;
+  memset(&grp, 0, sizeof(grp));
+  grp.K = n_groups;
+  for (int k = 0; k < p->n_ops; ++k) {
+    ACINO_REQUIRE(h_group[k] >= -1 && h_group[k] < n_groups, "h_group: every op's group must be -1 (fixed) or 0..n_groups-1");
+    if (h_group[k] >= 0) grp.gm[h_group[k]] |= 1ull << k;
+  }
+  const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16, K = n_groups;
+  const size_t NT = (size_t)N * B;                           // frames of all clips
+  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
+  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
+  const size_t col_bytes = skl_column_bytes(p, B);
+  if ((rc = skel_check_workspace(d_ws, ws_bytes, lay.total + 2 * col_bytes, "acino_skel_fte_link_workspace_bytes", ACINO_ERR_WORKSPACE)))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
+                                  d_unobserved)))
+    return rc;
+  char* base = (char*)d_ws;
+  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
+  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
+  unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
+  const unsigned char* d_unobs = pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr;
+  double* d_b = D(lay.total);                                // -G, then S: [B][K][N][P]
+  double* d_y = D(lay.total + col_bytes);                    // L^-1 (-G)
+  const size_t lds_rhs = sizeof(double) * skel_links_rhs_doubles(p->n_ops, p->n_pose, P, K);
+  const size_t lds_comb = sizeof(double) * skel_links_combine_doubles(p->n_ops, P, K);
+  static PerDeviceOnce attr;
+  if (attr.first()) {
+    for (int model = 0; model < 2; ++model)
+      ACINO_HIP_CHECK(hipFuncSetAttribute(
+          reinterpret_cast<const void*>(skel_camera_kernel(model, k_skel_links_rhs<false>, k_skel_links_rhs<true>)),
+          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_links_combine), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024));
+  }
+  hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_links_rhs<false>, k_skel_links_rhs<true>), dim3((unsigned)NT), dim3(256),
+                     lds_rhs, s, d_dev, grp, d_x, d_meas, d_w, D(lay.opv), d_fxm, d_b);
+  ACINO_LAUNCH_CHECK();
+  if ((rc = skel_launch_factor(PT, B, d_dev, d_clip, D(lay.band), D(lay.diag0), s))) return rc;
+  if ((rc = skel_launch_fwdsub(PT, B, K, d_dev, d_clip, D(lay.band), d_fxm, d_b, d_y, s))) return rc;
+  if ((rc = skel_launch_back_columns(PT, B, K, d_dev, d_clip, D(lay.band), d_fxm, d_y, d_b, s))) return rc;
+  hipLaunchKernelGGL(k_skel_links_combine, dim3((unsigned)NT), dim3(256), lds_comb, s, d_dev, d_clip, grp, d_b, d_cov_links, d_unknown,
+                     D(lay.opv), d_unobs, d_sens, d_dpos, d_cov_x, d_cov_pos, d_std_pos);
+  ACINO_LAUNCH_CHECK();
+  return skel_cov_read_status(d_clip, B, s, h_status);
+}
+
+}  // extern "C"

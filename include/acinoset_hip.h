@@ -950,6 +950,51 @@ int acino_skel_fte_calibration_sensitivity(const acino_skel_fte_params* p, int n
                                            void* stream, int pin_unobserved,
                                            uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
 
+/* ---- generic-skeleton FTE error bars that include the link lengths: sensitivity to the links' log-scales ---------------------
+ * acino_skel_fte_link_sensitivity: what the calibration entry above does for the extrinsics, for the body's dimensions.  Every
+ * op k of the link program belongs to a group h_group[k] in -1 .. n_groups-1 (-1: its offset stays fixed; the convention of
+ * acino_skel_link_scale, n_groups in 1..16) and theta_g is the log-scale of group g, theta = 0 the offsets of h_ops as given:
+ *   pos_l(x, theta) = root + sum over the ops k on l's path of exp(theta_g(k)) M_k(x) off_k
+ *   D_l[:, g] = d pos_l / d theta_g = the sum of M_k(x) off_k over the ops of group g on l's path         (the direct term)
+ *   G_n[p, g] = sum over c, l of G_l[:, p] . (w^2 J_pi^T J_pi) D_l[:, g]                                   (the cross term)
+ * with G_l, J_pi, the kept rows (w = 0, a non-finite measurement and |z_cam| < 1e-9 are dropped) and the Fisher weight w^2 of
+ * the calibration entry: neither the residuals nor l1_eps enter, and the smoothness prior does not depend on theta.
+ *   S = -A^-1 G, [n_clips][N][n_active][K]; A, the bound pins, pin_unobserved, the status rules, the limits, both camera models
+ *   and the leading arguments are exactly those of acino_skel_fte_covariance_pinned; rows of pinned variables are EXACTLY 0.
+ *   T_l = G_l S_n + D_l (3 x K): a pose moves through the states AND directly.
+ * With Sigma = d_cov_links[K][K], a covariance of the log-scales (e.g. cov_log_scales of a length fit; only PSD - a held group
+ * has zero rows - so it is multiplied and never factored):
+ *   d_sens    [n_clips][N][n_active][K]          S
+ *   d_dpos    [n_clips][N][n_pose][3][K]         T_l
+ *   d_cov_x   [n_clips][N][n_active][n_active]   S_n Sigma S_n^T, symmetric to the bit
+ *   d_cov_pos [n_clips][N][n_pose][3][3]         T_l Sigma T_l^T, symmetric to the bit
+ *   d_std_pos [n_clips][N][n_pose]               sqrt(trace(cov_pos)), metres
+ * Any output may be NULL, but not all of them; d_cov_x, d_cov_pos or d_std_pos without d_cov_links is ACINO_ERR_INVALID_ARG.
+ * d_unknown[K] (uint8, may be NULL) marks groups whose length the caller cannot bound: a slot whose path holds an op of such a
+ * group gets std_pos = +inf and NaN cov_pos; the group's column of S and T_l is reported all the same.  With pin_unobserved = 1 a
+ * slot whose G_l has a nonzero entry in the column of an unobserved state gets std_pos = +inf and NaN cov_pos (the rule of
+ * d_std_pos of the covariance); its T_l is the derivative with the unobserved states held.  A singular clip gets status 5 and NaN
+ * in every output; in a batch with h_status the other clips stand.  The result of one clip is the same bits whatever else shares
+ * the call.
+ * The total covariance of a trajectory is cov + cov_links ONLY for a Sigma obtained from OTHER data than the clip being solved, or
+ * an honest prior; lengths fitted to the same clip have errors correlated with the trajectory's.  The term is perfectly correlated
+ * across frames: smoothing does not average it out.
+ * Every argument is checked before any device call: n_groups in 1..16, every h_group[k] in -1..n_groups-1, the loss L1
+ * (p->loss != ACINO_SKEL_LOSS_L1 is ACINO_ERR_INVALID_ARG, as above).  Launches on `stream`: the Fisher assembly and build of the
+ * covariance, k_skel_links_rhs (-G as K columns), k_skel_factor, one forward (k_skel_fwdsub) and one backward substitution per
+ * clip (K <= 16 columns: one panel), k_skel_links_combine; one synchronisation.
+ * Workspace: the pinned covariance workspace plus two column buffers [n_clips][16][N][n_active], 256-byte aligned
+ * (ACINO_ERR_WORKSPACE otherwise); the query returns 0 outside the limits. */
+size_t acino_skel_fte_link_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved);
+int acino_skel_fte_link_sensitivity(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                    const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                    const double* d_lo, const double* d_hi, const double* d_x,
+                                    const int32_t* h_group /* [n_ops] */, int n_groups,
+                                    const double* d_cov_links /* [K][K] or NULL */, const uint8_t* d_unknown /* [K] or NULL */,
+                                    double* d_sens, double* d_dpos, double* d_cov_x, double* d_cov_pos, double* d_std_pos,
+                                    int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes, void* stream,
+                                    int pin_unobserved, uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
+
 /* ---- a generic-skeleton FTE iterate in image space: predicted pixels, their covariance, residuals, gating ----------------
  * Evaluated at the iterate d_x[n_clips][N][n_active] (normally the solution of acino_skel_fte_solve*).  Per entry
  * (b, n, c, l) = (clip, frame, camera, pose slot), the layout of d_meas[n_clips][N][C][n_pose][2] / d_w[n_clips][N][C][n_pose]:
