@@ -337,11 +337,26 @@ def _skel_inputs(models, xs, workspace_bytes=None, raw=False, start=False, **par
     return dict(xs=xs, act=act, dev=dev, cam_model=cam_model, x=x, head=head, tail=tail, keep=keep)
 
 
-def _attach(out, extras, keys):
+def _attach(out, extras, keys, total=False):
     """Every ``results`` of ``out`` (the (results, info) pairs of a solve) takes ``keys`` from its clip's dict in ``extras``; a
-    key the extras do not carry (``unobserved`` without ``pin_unobserved``) is left out."""
+    key the extras do not carry (``unobserved`` without ``pin_unobserved``) is left out.  ``total``: the extras are a share of the
+    error bars (the cameras', the links') and ``std_pos_total`` is set beside the ``std_pos`` that is already there."""
     for (res, _info), ex in zip(out, extras):
         res.update({k: ex[k] for k in keys if k in ex})
+        if total:
+            res["std_pos_total"] = _total_std(res)
+
+
+def _full_state(block, act, P, cols=False):
+    """A device block over the active states, [N, n_active, ...], in the full-state layout [N, P, ...], zero outside ``act``;
+    ``cols``: a square block [N, n_active, n_active], rows and columns."""
+    if cols:
+        full = np.zeros((block.shape[0], P, P))
+        full[:, act[:, None], act[None, :]] = block
+    else:
+        full = np.zeros(block.shape[:1] + (P,) + block.shape[2:])
+        full[:, act] = block
+    return full
 
 
 def _unobserved_lists(mask, act):
@@ -397,13 +412,11 @@ def _covariance(models, xs, l1_eps, want, raise_numeric=True, pin_unobserved=Fal
         if key not in want:                                   # the bars alone: only the diagonals leave the device
             dg = arr.diagonal(dim1=-2, dim2=-1).contiguous().cpu().numpy()
             for i in range(B):
-                out[i][std_key] = np.zeros((N, P))
-                out[i][std_key][:, act] = np.sqrt(np.maximum(dg[i], 0.0))
+                out[i][std_key] = _full_state(np.sqrt(np.maximum(dg[i], 0.0)), act, P)
             continue
         ch = arr.cpu().numpy()
         for i in range(B):
-            full = np.zeros((N, P, P))
-            full[:, act[:, None], act[None, :]] = ch[i]
+            full = _full_state(ch[i], act, P, cols=True)
             if key in want:
                 out[i][key] = full
             if std_key is not None and std_key in want:
@@ -577,11 +590,47 @@ def model_calibration_sensitivity(models, xs, cov_cams=None, l1_eps=1e-2, pin_un
     return _calibration(models, xs, cov_cams, l1_eps, pin_unobserved)
 
 
-def _refuse_robust_calibration(models):
+def _refuse_robust(models, what):
+    """``what``: "calibration sensitivity (cov_cams)" or "link sensitivity (cov_links)"."""
     for m in models:
         if model_loss(m) != "l1":
-            raise ValueError(f"the calibration sensitivity (cov_cams) is defined for the l1 loss only; the model's loss is "
-                             f"{model_loss(m)!r}")
+            raise ValueError(f"the {what} is defined for the l1 loss only; the model's loss is {model_loss(m)!r}")
+
+
+def _sensitivity(models, xs, entry, cols, keys, sigma, l1_eps, pin_unobserved, raise_numeric, groups=(), unknown=None):
+    """The one driver of ``_calibration`` and ``_links``: S = -A^-1 G with ``cols`` columns and the covariances ``sigma`` (a checked
+    [cols, cols] matrix, or None) gives.  ``entry``: acino_skel_fte_<entry>_sensitivity with its ..._workspace_bytes; ``keys``: the
+    names of S, cov_x, cov_pos, std_pos in the dicts returned - or, with the link entry's ``groups`` = (h_group, K) and ``unknown``
+    ([K] uint8 or None), of S, T_l, cov_x, cov_pos, std_pos."""
+    pin = bool(pin_unobserved)
+    query = getattr(lib(), f"acino_skel_fte_{entry}_workspace_bytes")
+    io_ = _skel_inputs(models, xs, lambda p, B: query(C.byref(p), B, int(pin)), l1_eps=l1_eps)
+    m0, act, dev = models[0], io_["act"], io_["dev"]
+    B, N, P = len(models), m0.N, m0.P
+    Pa, Lp = len(act), len(m0.names)
+    empty = lambda *shape: torch.empty((B, N) + shape, dtype=torch.float64, device=dev)   # noqa: E731
+    sig_d = None if sigma is None else torch.as_tensor(sigma, dtype=torch.float64, device=dev).contiguous()
+    unk_d = None if unknown is None else torch.as_tensor(unknown, device=dev).contiguous()
+    arrays = [empty(Pa, cols)] + ([empty(Lp, 3, cols)] if groups else [])
+    arrays += [None, None, None] if sigma is None else [empty(Pa, Pa), empty(Lp, 3, 3), empty(Lp)]
+    status = (C.c_int32 * B)()
+    mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev) if pin else None
+    rc = getattr(lib(), f"acino_skel_fte_{entry}_sensitivity")(*io_["head"], *groups, ptr(sig_d), *((ptr(unk_d),) if groups else ()),
+                                                                *[ptr(a) for a in arrays], status, *io_["tail"], int(pin), ptr(mask))
+    if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
+        check(rc)
+    host = [None if a is None else a.cpu().numpy() for a in arrays]
+    out = []
+    for i in range(B):
+        o = dict(zip(keys, (None if h is None else h[i] for h in host)), status=int(status[i]))
+        o[keys[0]] = _full_state(o[keys[0]], act, P)
+        if sigma is not None:
+            o[keys[-3]] = _full_state(o[keys[-3]], act, P, cols=True)
+        out.append(o)
+    if pin:
+        for o, un in zip(out, _unobserved_lists(mask, act)):
+            o["unobserved"] = un
+    return out
 
 
 def _calibration(models, xs, cov_cams, l1_eps, pin_unobserved, raise_numeric=True):
@@ -589,50 +638,10 @@ def _calibration(models, xs, cov_cams, l1_eps, pin_unobserved, raise_numeric=Tru
     of a batch (solve_video's one-window case)."""
     if len(models) == 0:
         raise ValueError("no models")
-    _refuse_robust_calibration(models)
+    _refuse_robust(models, "calibration sensitivity (cov_cams)")
     Cn = int(models[0].meas.shape[1])
-    sigma = calib.cov_cams_matrix(cov_cams, Cn)
-    pin = bool(pin_unobserved)
-    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_calibration_workspace_bytes(C.byref(p), B, int(pin)), l1_eps=l1_eps)
-    m0, act, dev = models[0], io_["act"], io_["dev"]
-    B, N, P = len(models), m0.N, m0.P
-    Pa, Lp, W = len(act), len(m0.names), 6 * Cn
-    empty = lambda *shape: torch.empty((B, N) + shape, dtype=torch.float64, device=dev)   # noqa: E731
-    sig_d = None if sigma is None else torch.as_tensor(sigma, dtype=torch.float64, device=dev).contiguous()
-    sens = empty(Pa, W)
-    cov_x, cov_pos, std_pos = (None, None, None) if sigma is None else (empty(Pa, Pa), empty(Lp, 3, 3), empty(Lp))
-    status = (C.c_int32 * B)()
-    mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev) if pin else None
-    rc = lib().acino_skel_fte_calibration_sensitivity(*io_["head"], ptr(sig_d), ptr(sens), ptr(cov_x), ptr(cov_pos), ptr(std_pos), status,
-                                                      *io_["tail"], int(pin), ptr(mask))
-    if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
-        check(rc)
-    sh = sens.cpu().numpy()
-    out = []
-    for i in range(B):
-        full = np.zeros((N, P, W))
-        full[:, act] = sh[i]
-        out.append(dict(sens_cams=full, cov_x_calib=None, cov_pos_calib=None, std_pos_calib=None, status=int(status[i])))
-    if sigma is not None:
-        ch, ph, th = cov_x.cpu().numpy(), cov_pos.cpu().numpy(), std_pos.cpu().numpy()
-        for i, o in enumerate(out):
-            full = np.zeros((N, P, P))
-            full[:, act[:, None], act[None, :]] = ch[i]
-            o.update(cov_x_calib=full, cov_pos_calib=ph[i], std_pos_calib=th[i])
-    if pin:
-        for o, un in zip(out, _unobserved_lists(mask, act)):
-            o["unobserved"] = un
-    return out
-
-
-def _attach_calibration(out, models, xs, cov_cams, l1_eps, pin_unobserved, with_total):
-    """The four CALIB_KEYS of ``model_calibration_sensitivity`` into every ``results`` of ``out``, and ``std_pos_total`` beside a
-    ``std_pos`` that is already there (``with_total``)."""
-    _attach(out, model_calibration_sensitivity(models, xs, cov_cams, l1_eps=l1_eps, pin_unobserved=pin_unobserved),
-            CALIB_KEYS + ("unobserved",))
-    if with_total:
-        for res, _info in out:
-            res["std_pos_total"] = np.sqrt(res["std_pos"] ** 2 + res["std_pos_calib"] ** 2)
+    return _sensitivity(models, xs, "calibration", 6 * Cn, CALIB_KEYS, calib.cov_cams_matrix(cov_cams, Cn), l1_eps, pin_unobserved,
+                        raise_numeric)
 
 
 LINK_KEYS = ("sens_links", "dpos_links", "cov_x_links", "cov_pos_links", "std_pos_links")
@@ -666,12 +675,6 @@ def link_cov_matrix(cov, K):
     if not np.allclose(a, a.T, rtol=1e-12, atol=1e-12 * max(float(np.abs(a).max()), 1e-300)):
         raise ValueError("cov_links is not symmetric")
     return np.ascontiguousarray(a), unknown
-
-
-def _refuse_robust_links(models):
-    for m in models:
-        if model_loss(m) != "l1":
-            raise ValueError(f"the link sensitivity (cov_links) is defined for the l1 loss only; the model's loss is {model_loss(m)!r}")
 
 
 def _link_inputs(model, groups, cov_links):
@@ -714,41 +717,13 @@ def _links(models, xs, groups, cov_links, l1_eps, pin_unobserved, raise_numeric=
     batch (solve_video's one-window case)."""
     if len(models) == 0:
         raise ValueError("no models")
-    _refuse_robust_links(models)
+    _refuse_robust(models, "link sensitivity (cov_links)")
     grp, K, sigma, unknown = _link_inputs(models[0], groups, cov_links)
-    pin = bool(pin_unobserved)
-    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_link_workspace_bytes(C.byref(p), B, int(pin)), l1_eps=l1_eps)
-    m0, act, dev = models[0], io_["act"], io_["dev"]
-    B, N, P = len(models), m0.N, m0.P
-    Pa, Lp = len(act), len(m0.names)
-    empty = lambda *shape: torch.empty((B, N) + shape, dtype=torch.float64, device=dev)   # noqa: E731
-    sig_d = None if sigma is None else torch.as_tensor(sigma, dtype=torch.float64, device=dev).contiguous()
-    unk_d = None if sigma is None or not unknown.any() else torch.as_tensor(unknown.astype(np.uint8), device=dev).contiguous()
-    sens, dpos = empty(Pa, K), empty(Lp, 3, K)
-    cov_x, cov_pos, std_pos = (None, None, None) if sigma is None else (empty(Pa, Pa), empty(Lp, 3, 3), empty(Lp))
-    status = (C.c_int32 * B)()
-    mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev) if pin else None
     grp_c = (C.c_int32 * max(len(grp), 1))(*[int(g) for g in grp])
-    rc = lib().acino_skel_fte_link_sensitivity(*io_["head"], grp_c, K, ptr(sig_d), ptr(unk_d), ptr(sens), ptr(dpos), ptr(cov_x),
-                                               ptr(cov_pos), ptr(std_pos), status, *io_["tail"], int(pin), ptr(mask))
-    if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
-        check(rc)
-    sh, dh = sens.cpu().numpy(), dpos.cpu().numpy()
-    out = []
-    for i in range(B):
-        full = np.zeros((N, P, K))
-        full[:, act] = sh[i]
-        out.append(dict(sens_links=full, dpos_links=dh[i], cov_x_links=None, cov_pos_links=None, std_pos_links=None, groups=grp.copy(),
-                        status=int(status[i])))
-    if sigma is not None:
-        ch, ph, th = cov_x.cpu().numpy(), cov_pos.cpu().numpy(), std_pos.cpu().numpy()
-        for i, o in enumerate(out):
-            full = np.zeros((N, P, P))
-            full[:, act[:, None], act[None, :]] = ch[i]
-            o.update(cov_x_links=full, cov_pos_links=ph[i], std_pos_links=th[i])
-    if pin:
-        for o, un in zip(out, _unobserved_lists(mask, act)):
-            o["unobserved"] = un
+    out = _sensitivity(models, xs, "link", K, LINK_KEYS, sigma, l1_eps, pin_unobserved, raise_numeric, groups=(grp_c, K),
+                       unknown=None if sigma is None or not unknown.any() else unknown.astype(np.uint8))
+    for o in out:
+        o["groups"] = grp.copy()
     return out
 
 
@@ -757,7 +732,7 @@ def _check_links(models, cov_links, groups):
     if cov_links is None and groups is None:
         return False
     if len(models):
-        _refuse_robust_links(models)
+        _refuse_robust(models, "link sensitivity (cov_links)")
         _link_inputs(models[0], groups, cov_links)
     return True
 
@@ -1464,7 +1439,7 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
     if init == "pose_fit":
         x0 = [pose_fit_start(m) if x0 is None or x0[i] is None else x0[i] for i, m in enumerate(models)]
     if len(models) and cov_cams is not None:
-        _refuse_robust_calibration(models)
+        _refuse_robust(models, "calibration sensitivity (cov_cams)")
         calib.cov_cams_matrix(cov_cams, int(models[0].meas.shape[1]))      # (a malformed matrix fails before the solve, not after)
     with_links = _check_links(models, cov_links, link_groups)
     lm = dict(max_iter=max_iter, lam0=lam0, ftol=ftol, xtol=xtol, gtol=gtol, l1_eps=l1_eps, lam_max=lam_max)
@@ -1486,12 +1461,11 @@ def solve_models(models, x0=None, max_iter=200, lam0=1e-3, ftol=1e-10, xtol=1e-1
         _attach(out, model_reprojection(models, xs_out, cov=bool(return_cov),
                                         cov_pos=[r["cov_pos"] for r, _i in out] if return_cov else None, l1_eps=l1_eps), REPROJ_KEYS)
     if cov_cams is not None:
-        _attach_calibration(out, models, xs_out, cov_cams, l1_eps, pin_unobserved, with_total=bool(return_cov))
+        _attach(out, model_calibration_sensitivity(models, xs_out, cov_cams, l1_eps=l1_eps, pin_unobserved=pin_unobserved),
+                CALIB_KEYS + ("unobserved",), total=bool(return_cov))
     if with_links:
-        _attach(out, _links(models, xs_out, link_groups, cov_links, l1_eps, pin_unobserved), LINK_KEYS + ("unobserved",))
-        if return_cov and cov_links is not None:
-            for res, _info in out:
-                res["std_pos_total"] = _total_std(res)
+        _attach(out, _links(models, xs_out, link_groups, cov_links, l1_eps, pin_unobserved), LINK_KEYS + ("unobserved",),
+                total=bool(return_cov) and cov_links is not None)
     return out
 
 
@@ -1867,17 +1841,15 @@ def solve_video(skel_dict, project_dir=None, *, scene=None, dlc_tables=None, fir
             results["window_std_pos"] = [cv["std_pos"] for cv in covs]
         if pin_unobserved:
             results["cov_unobserved"] = [cv["unobserved"] for cv in covs]
+    def attach_share(rows, keys, total):                      # (the keys a share leaves None - no Sigma - stay None)
+        given = tuple(k for k in keys if rows[0][k] is not None)
+        stitched = dict({k: None for k in keys}, **_stitch(owner, starts, f0, rows, given, fill=np.nan))
+        _attach([(results, None)], [stitched], keys, total=bool(return_cov) and total)
     if cov_cams is not None:
-        cals = _calibration(models, xs_final, cov_cams, l1_eps, pin_unobserved, raise_numeric=False)
-        results.update(_stitch(owner, starts, f0, cals, CALIB_KEYS, fill=np.nan))
-        if return_cov:
-            results["std_pos_total"] = np.sqrt(results["std_pos"] ** 2 + results["std_pos_calib"] ** 2)
+        attach_share(_calibration(models, xs_final, cov_cams, l1_eps, pin_unobserved, raise_numeric=False), CALIB_KEYS, True)
     if with_links:
-        lks = _links(models, xs_final, link_groups, cov_links, l1_eps, pin_unobserved, raise_numeric=False)
-        given = tuple(k for k in LINK_KEYS if lks[0][k] is not None)
-        results.update({k: None for k in LINK_KEYS}, **_stitch(owner, starts, f0, lks, given, fill=np.nan))
-        if return_cov and cov_links is not None:
-            results["std_pos_total"] = _total_std(results)
+        attach_share(_links(models, xs_final, link_groups, cov_links, l1_eps, pin_unobserved, raise_numeric=False), LINK_KEYS,
+                     cov_links is not None)
     if return_reprojection:                                   # one clip of all the frames, every frame's detections its owner's
         lo_t, hi_t = bounds_table(skel_dict, total)
         seen = _stitch(owner, starts, f0, [m.__dict__ for m in models], ("meas", "weights"))

@@ -36,21 +36,31 @@
 //                           (k_skel_cov_pose's rule).  A singular clip: NaN in every output.
 //                           LDS: (2 n_act 6C + n_act (n_act + 1) + n_ops 12 + 4 (6 n_act + 9)) doubles: 147 KB at n_act = 64
 //                           with 16 cameras, so S_n and T both fit and Sigma is read from memory untiled.
+// What the two kernels of this file share with those of skel_links.hip is in skel_sens_dev.hpp (the frame prologue and the tail
+// of a right-hand-side kernel; the NaN fill, the states' share, a slot's G_l and the 3 x 3 tail of a combine), the host pipeline
+// behind the entry's own checks in skel_factor.hpp (skel_sens_run).  The kept row of a (camera, slot) is written out in both
+// right-hand-side kernels: moved into a shared function the compiler pairs its multiplies and adds into other FMAs, and
+// the last bits of S change.
 // n_cams <= ACINO_MAX_CAMS = 16 (96 columns).  No workgroup waits for another; vector stores only; the result of a clip is the
 // same bits whatever else shares the call (every kernel's arithmetic on a clip reads that clip's data alone).
 #include <cstddef>
 #include <cstdint>
 
-#include "skel_factor.hpp"
+#include "skel_sens_dev.hpp"
 
 namespace acino {
 
-static size_t skel_calib_rhs_lds(int n_ops, int n_pose, int n_cams, int P) {
-  return sizeof(double) * ((size_t)n_ops * 12 + (size_t)n_pose * 3 + (size_t)n_pose * 3 * P + (size_t)n_cams * n_pose * 18);
+constexpr size_t skel_calib_rhs_doubles(size_t n_ops, size_t n_pose, size_t n_cams, size_t P) {
+  return n_ops * 12 + n_pose * 3 + n_pose * 3 * P + n_cams * n_pose * 18;
 }
-static size_t skel_calib_combine_lds(int n_ops, int W, int P) {
-  return sizeof(double) * ((size_t)2 * P * W + (size_t)P * (P + 1) + (size_t)n_ops * 12 + 4 * (6 * (size_t)P + 9));
+constexpr size_t skel_calib_combine_doubles(size_t n_ops, size_t W, size_t P) {
+  return 2 * P * W + P * (P + 1) + n_ops * 12 + 4 * (6 * P + 9);
 }
+// (the rhs kernel at the limits: n_cams n_pose <= SK_MAXROWS / 2 rows of (u, v), whatever the two factors are)
+static_assert(sizeof(double) * (skel_calib_rhs_doubles(ACINO_SKEL_MAX_OPS, ACINO_SKEL_MAX_OPS + 1, 0, SK_MAXP) + (SK_MAXROWS / 2) * 18) <=
+                      160 * 1024 &&
+                  sizeof(double) * skel_calib_combine_doubles(ACINO_SKEL_MAX_OPS, 6 * ACINO_MAX_CAMS, SK_MAXP) <= 160 * 1024,
+              "LDS of k_skel_calib_rhs / k_skel_calib_combine at the limits");
 
 template <bool PINHOLE>
 __global__ void __launch_bounds__(256)
@@ -60,26 +70,12 @@ k_skel_calib_rhs(const SkelDev* __restrict__ dev, const double* __restrict__ x, 
   extern __shared__ __attribute__((aligned(16))) double skc_smem[];
   const SkelDev& D = *dev;
   const int tid = threadIdx.x, n = blockIdx.x;
-  const int P = D.n_act, PT = D.PT, C = D.n_cams, NPOSE = D.n_pose, NOPS = D.n_ops, N = D.n_frames, W = 6 * C;
+  const int P = D.n_act, C = D.n_cams, NPOSE = D.n_pose, NOPS = D.n_ops;
   double* opv = skc_smem;                                    // [n_ops][4][3]
   double* pos = opv + NOPS * 12;                             // [n_pose][3]
   double* G = pos + NPOSE * 3;                               // [(l * 3 + i) * P + p]
   double* Mb = G + (size_t)NPOSE * 3 * P;                    // [(c * n_pose + l) * 18 + i * 6 + j]
-  for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
-  __syncthreads();
-  if (tid < 3) {                                             // poses, coordinate by coordinate, in program order
-    const double root = x[(size_t)n * P + tid];
-    for (int s = 0; s < NPOSE; ++s) pos[s * 3 + tid] = root;
-    for (int k = 0; k < NOPS; ++k) pos[D.op[k].child * 3 + tid] = pos[D.op[k].parent * 3 + tid] + opv[(k * 4) * 3 + tid];
-  }
-  for (int e = tid; e < NPOSE * P; e += 256) {
-    const int l = e / P, p = e - l * P;
-    double gc[3];
-    skel_pose_jac_col(D, opv, l, p, gc);
-    G[(l * 3) * P + p] = gc[0];
-    G[(l * 3 + 1) * P + p] = gc[1];
-    G[(l * 3 + 2) * P + p] = gc[2];
-  }
+  skel_sens_frame(D, n, x, opv_all, opv, pos, G);
   __syncthreads();
   for (int task = tid; task < C * NPOSE; task += 256) {
     const int c = task / NPOSE, l = task - c * NPOSE;
@@ -121,22 +117,10 @@ k_skel_calib_rhs(const SkelDev* __restrict__ dev, const double* __restrict__ x, 
       for (int j = 0; j < 6; ++j) M[i * 6 + j] = w2 * (ju[i] * cu[j] + jv[i] * cv[j]);
   }
   __syncthreads();
-  const int b = n / N, nl = n - b * N;
-  for (int task = tid; task < W * P; task += 256) {
-    const int col = task / P, p = task - col * P;
-    const int c = col / 6, j = col - 6 * c;
-    double acc = 0.0;
-    if (!fxm[(size_t)n * PT + p]) {
-      const double* M = Mb + (size_t)c * NPOSE * 18 + j;
-      for (int l = 0; l < NPOSE; ++l) {
-        acc += G[(l * 3) * P + p] * M[l * 18];
-        acc += G[(l * 3 + 1) * P + p] * M[l * 18 + 6];
-        acc += G[(l * 3 + 2) * P + p] * M[l * 18 + 12];
-      }
-      acc = -acc;
-    }
-    rhs[(((size_t)b * W + col) * N + nl) * P + p] = acc;
-  }
+  skel_sens_rhs_out(D, n, 6 * C, G, fxm, rhs, [&](int col, int l, int i) {
+    const int c = col / 6;
+    return Mb[((size_t)c * NPOSE + l) * 18 + i * 6 + (col - 6 * c)];
+  });
 }
 
 // y = L^-1 b on the factor of k_skel_factor<PT>: see the head of the file.  b_all, y_all: [n_clips][S][N][n_act]
@@ -185,9 +169,7 @@ k_skel_fwdsub(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip
       if (s0 + c < S && p < P && !fxm[(size_t)n * PT + p]) v = b_all[row0 + c * srow + (size_t)n * P + p];
       stage[Sh::st(c, p)] = v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    sk_wave_handover();
     d4 r[NTP];
 #pragma unroll
     for (int kb = 0; kb < NTP; ++kb)
@@ -236,9 +218,7 @@ k_skel_fwdsub(const SkelDev* __restrict__ dev, const SkelClip* __restrict__ clip
     for (int kb = 0; kb < NTP; ++kb)
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) stage[Sh::st(li, kb * 16 + lk + 4 * rr)] = dn[kb][rr];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    sk_wave_handover();
     for (int e = lane; e < 16 * PT; e += 64) {
       const int c = e / PT, p = e % PT;
       if (s0 + c < S && p < P) y_all[row0 + c * srow + (size_t)n * P + p] = stage[Sh::st(c, p)];
@@ -262,20 +242,9 @@ k_skel_calib_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict
   extern __shared__ __attribute__((aligned(16))) double skc_smem[];
   const SkelDev& D = *dev;
   const int n = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, N = D.n_frames, W = 6 * D.n_cams, LDC = P + 1;
-  const int b = n / N, nl = n - b * N;
-  if (clip[b].status != 0) {
-    const double nan = __builtin_nan("");
-    for (int e = tid; e < P * W; e += 256)
-      if (sens) sens[(size_t)n * P * W + e] = nan;
-    for (int e = tid; e < P * P; e += 256)
-      if (cov_x) cov_x[(size_t)n * P * P + e] = nan;
-    for (int e = tid; e < NPOSE * 9; e += 256)
-      if (cov_pos) cov_pos[(size_t)n * NPOSE * 9 + e] = nan;
-    for (int e = tid; e < NPOSE; e += 256)
-      if (std_pos) std_pos[(size_t)n * NPOSE + e] = nan;
-    return;
-  }
+  const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, W = 6 * D.n_cams, LDC = P + 1;
+  const int b = n / D.n_frames;
+  if (clip[b].status != 0) return skel_sens_nan(D, n, W, sens, nullptr, cov_x, cov_pos, std_pos);
   double* Sm = skc_smem;                                     // S_n [P][W]
   double* Tm = Sm + (size_t)P * W;                           // S_n Sigma [P][W]
   double* Cx = Tm + (size_t)P * W;                           // cov_x_cal [P][P + 1]
@@ -283,52 +252,16 @@ k_skel_calib_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict
   double* Gw = opv + NOPS * 12 + wave * (6 * P + 9);         // this wave's G_l [3][P], G_l cov_x_cal [3][P], out [9]
   double* Tw = Gw + 3 * P;
   double* out9 = Tw + 3 * P;
-  for (int e = tid; e < P * W; e += 256) {
-    const int col = e / P, p = e - col * P;
-    Sm[p * W + col] = sol[(((size_t)b * W + col) * N + nl) * P + p];
-  }
-  __syncthreads();
-  if (sens)
-    for (int e = tid; e < P * W; e += 256) sens[(size_t)n * P * W + e] = Sm[e];
-  if (!sigma) return;
-  for (int e = tid; e < P * W; e += 256) {
-    const int p = e / W, j = e - p * W;
-    double acc = 0.0;
-    for (int i = 0; i < W; ++i) acc += Sm[p * W + i] * sigma[(size_t)i * W + j];
-    Tm[e] = acc;
-  }
-  __syncthreads();
-  for (int e = tid; e < P * P; e += 256) {
-    const int p = e / P, q = e - p * P;
-    if (p <= q) {
-      double acc = 0.0;
-      for (int j = 0; j < W; ++j) acc += Tm[p * W + j] * Sm[q * W + j];
-      Cx[p * LDC + q] = acc;
-      Cx[q * LDC + p] = acc;
-    }
-  }
-  __syncthreads();
-  if (cov_x)
-    for (int e = tid; e < P * P; e += 256) cov_x[(size_t)n * P * P + e] = Cx[(e / P) * LDC + e % P];
-  if (!cov_pos && !std_pos) return;
+  skel_sens_states(D, n, W, W, sol, sigma, sigma != nullptr, Sm, Tm, Cx, sens, cov_x);
+  if (!sigma || (!cov_pos && !std_pos)) return;
   for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
   __syncthreads();
   for (int l0 = 0; l0 < NPOSE; l0 += 4) {                   // a wave is one pose slot; no workgroup barrier inside
     const int l = l0 + wave;
     if (l >= NPOSE) break;
-    bool dep = false;
-    if (lane < P) {
-      double gc[3];
-      skel_pose_jac_col(D, opv, l, lane, gc);
-      Gw[lane] = gc[0];
-      Gw[P + lane] = gc[1];
-      Gw[2 * P + lane] = gc[2];
-      if (unobs) dep = unobs[(size_t)b * P + lane] && (gc[0] != 0.0 || gc[1] != 0.0 || gc[2] != 0.0);
-    }
+    const bool dep = skel_sens_pose_jac(D, opv, l, lane, unobs ? unobs + (size_t)b * P : nullptr, Gw);
     const bool undet = __any(dep ? 1 : 0) != 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    sk_wave_handover();
     if (lane < P) {
       double t0 = 0.0, t1 = 0.0, t2 = 0.0;
       for (int q = 0; q < P; ++q) {
@@ -341,23 +274,8 @@ k_skel_calib_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict
       Tw[P + lane] = t1;
       Tw[2 * P + lane] = t2;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 6) {                                          // the upper triangle, mirrored
-      const int i = lane < 3 ? 0 : (lane < 5 ? 1 : 2), j = lane < 3 ? lane : (lane < 5 ? lane - 2 : 2);
-      double s = 0.0;
-      for (int q = 0; q < P; ++q) s += Tw[i * P + q] * Gw[j * P + q];
-      out9[3 * i + j] = s;
-      out9[3 * j + i] = s;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 9 && cov_pos) cov_pos[((size_t)n * NPOSE + l) * 9 + lane] = undet ? __builtin_nan("") : out9[lane];
-    if (lane == 0 && std_pos)
-      std_pos[(size_t)n * NPOSE + l] = undet ? __builtin_inf() : sqrt(fmax(out9[0] + out9[4] + out9[8], 0.0));
-    __builtin_amdgcn_wave_barrier();
+    skel_sens_pos_out(lane, P, Tw, Gw, out9, undet, cov_pos ? cov_pos + ((size_t)n * NPOSE + l) * 9 : nullptr,
+                      std_pos ? std_pos + (size_t)n * NPOSE + l : nullptr);
   }
 }
 
@@ -387,16 +305,12 @@ int skel_launch_fwdsub(int PT, int n_clips, long long n_cols, const SkelDev* d_d
 
 using namespace acino;
 
-static size_t skc_column_bytes(const acino_skel_fte_params* p, int n_clips) {
-  return skel_align256(sizeof(double) * (size_t)n_clips * 6 * p->n_cams * p->n_frames * p->n_active);
-}
-
 extern "C" {
 
 size_t acino_skel_fte_calibration_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved) {
   const size_t cov = acino_skel_fte_covariance_pinned_workspace_bytes(p, n_clips, pin_unobserved);
   if (cov == 0 || p->n_cams < 1 || p->n_cams > ACINO_MAX_CAMS) return 0;
-  return cov + 2 * skc_column_bytes(p, n_clips);
+  return skel_sens_workspace_bytes(p, n_clips, pin_unobserved, 6 * p->n_cams);
 }
 
 int acino_skel_fte_calibration_sensitivity(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
@@ -414,51 +328,22 @@ int acino_skel_fte_calibration_sensitivity(const acino_skel_fte_params* p, int n
                 "at least one of d_sens, d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal");
   ACINO_REQUIRE(d_cov_cams || !(d_cov_x_cal || d_cov_pos_cal || d_std_pos_cal), "a cov / std output needs d_cov_cams");
   ACINO_REQUIRE(p->n_cams <= ACINO_MAX_CAMS, "n_cams <= 16 (96 columns)");
-  const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16, W = 6 * p->n_cams;
-  const size_t NT = (size_t)N * B;                           // frames of all clips
-  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
-  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
-  const size_t col_bytes = skc_column_bytes(p, B);
-  if ((rc = skel_check_workspace(d_ws, ws_bytes, lay.total + 2 * col_bytes, "acino_skel_fte_calibration_workspace_bytes",
-                                 ACINO_ERR_WORKSPACE)))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
-                                  d_unobserved)))
-    return rc;
-  char* base = (char*)d_ws;
-  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
-  SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
-  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
-  unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
-  const unsigned char* d_unobs = pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr;
-  double* d_b = D(lay.total);                                // -G, then S: [B][W][N][P]
-  double* d_y = D(lay.total + col_bytes);                    // L^-1 (-G)
-  const size_t lds_rhs = skel_calib_rhs_lds(p->n_ops, p->n_pose, p->n_cams, P), lds_comb = skel_calib_combine_lds(p->n_ops, W, P);
-  static_assert(sizeof(double) * ((size_t)ACINO_SKEL_MAX_OPS * 12 + (ACINO_SKEL_MAX_OPS + 1) * 3 * (1 + SK_MAXP) + (SK_MAXROWS / 2) * 18) <=
-                        160 * 1024 &&
-                    sizeof(double) * ((size_t)2 * SK_MAXP * 6 * ACINO_MAX_CAMS + SK_MAXP * (SK_MAXP + 1) + ACINO_SKEL_MAX_OPS * 12 +
-                                      4 * (6 * SK_MAXP + 9)) <= 160 * 1024,
-                "LDS of k_skel_calib_rhs / k_skel_calib_combine at the limits");
+  const int P = p->n_active, W = 6 * p->n_cams;
   static PerDeviceOnce attr;
-  if (attr.first()) {
-    for (int model = 0; model < 2; ++model)
-      ACINO_HIP_CHECK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(skel_camera_kernel(model, k_skel_calib_rhs<false>, k_skel_calib_rhs<true>)),
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_calib_combine), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-  }
-  hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_calib_rhs<false>, k_skel_calib_rhs<true>), dim3((unsigned)NT), dim3(256),
-                     lds_rhs, s, d_dev, d_x, d_meas, d_w, D(lay.opv), d_fxm, d_b);
-  ACINO_LAUNCH_CHECK();
-  if ((rc = skel_launch_factor(PT, B, d_dev, d_clip, D(lay.band), D(lay.diag0), s))) return rc;
-  if ((rc = skel_launch_fwdsub(PT, B, W, d_dev, d_clip, D(lay.band), d_fxm, d_b, d_y, s))) return rc;
-  if ((rc = skel_launch_back_columns(PT, B, W, d_dev, d_clip, D(lay.band), d_fxm, d_y, d_b, s))) return rc;
-  hipLaunchKernelGGL(k_skel_calib_combine, dim3((unsigned)NT), dim3(256), lds_comb, s, d_dev, d_clip, d_b, d_cov_cams, D(lay.opv),
-                     d_unobs, d_sens, d_cov_x_cal, d_cov_pos_cal, d_std_pos_cal);
-  ACINO_LAUNCH_CHECK();
-  return skel_cov_read_status(d_clip, B, s, h_status);
+  const void* const kernels[3] = {(const void*)k_skel_calib_rhs<false>, (const void*)k_skel_calib_rhs<true>, (const void*)k_skel_calib_combine};
+  return skel_sens_run(
+      p, n_clips, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, W, W, "acino_skel_fte_calibration_workspace_bytes",
+      h_status, d_ws, ws_bytes, stream, pin_unobserved, d_unobserved, attr, kernels,
+      [&](const SkelSens& a) {
+        hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_calib_rhs<false>, k_skel_calib_rhs<true>), dim3((unsigned)a.NT), dim3(256),
+                           sizeof(double) * skel_calib_rhs_doubles(p->n_ops, p->n_pose, p->n_cams, P), a.s, a.d_dev, d_x, d_meas, d_w,
+                           a.d_opv, a.d_fxm, a.d_cols);
+      },
+      [&](const SkelSens& a) {
+        hipLaunchKernelGGL(k_skel_calib_combine, dim3((unsigned)a.NT), dim3(256), sizeof(double) * skel_calib_combine_doubles(p->n_ops, W, P),
+                           a.s, a.d_dev, a.d_clip, a.d_cols, d_cov_cams, a.d_opv, a.d_unobs, d_sens, d_cov_x_cal, d_cov_pos_cal,
+                           d_std_pos_cal);
+      });
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // What the uses of the skeleton FTE's Fisher matrix share (skel_cov.hip: the selected inverse; skel_sample.hip: joint
 // posterior samples; skel_calib.hip: the sensitivity to the extrinsics; skel_links.hip: the sensitivity to the link lengths):
-// the 16 x 16 tile product, the banded block Cholesky A = L L^T as a device function template, the shape of the triangular
-// solves on it, the workspace layout and the launches that build the band at an iterate.
+// the 16 x 16 tile product, the wave-level LDS hand-over, the banded block Cholesky A = L L^T as a device function template,
+// the shape of the triangular solves on it, the workspace layout, the launches that build the band at an iterate and the one
+// host pipeline of the two sensitivities (skel_sens_run; their device blocks are in skel_sens_dev.hpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -31,6 +32,13 @@ __device__ __forceinline__ d4 sk_tile_mac(d4 acc, int k0, int k1, int lk, FA a_a
     for (int s = 0; s < 4; ++s) acc = mfma(av[s], bv[s], acc);
   }
   return acc;
+}
+
+// What a wave's lanes have written to LDS is what its other lanes read next: no workgroup barrier, the wave alone
+__device__ __forceinline__ void sk_wave_handover() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 constexpr int SKC_T = 512, SKC_W = SKC_T / 64;    // threads / waves of the one workgroup that factors a clip
@@ -186,6 +194,64 @@ int skel_launch_fwdsub(int PT, int n_clips, long long n_cols, const SkelDev* d_d
 // [n_clips][n_cols][N][n_act] (the layout of the sampler's z, pinned rows masked to 0; NaN for a clip whose status is not 0).
 int skel_launch_back_columns(int PT, int n_clips, long long n_cols, const SkelDev* d_dev, const SkelClip* d_clip,
                              const double* d_band, const unsigned char* d_fxm, const double* d_y, double* d_out, hipStream_t s);
+// ---- host: the sensitivities S = -A^-1 G (skel_calib.hip, skel_links.hip): the covariance's workspace, then two column buffers
+//      [n_clips][n_cols][N][n_act], the right-hand side (S in the end) and L^-1 of it
+inline size_t skel_sens_column_bytes(const acino_skel_fte_params* p, int n_clips, int n_cols) {
+  return skel_align256(sizeof(double) * (size_t)n_clips * n_cols * p->n_frames * p->n_active);
+}
+// what a ..._workspace_bytes query of theirs answers (0: outside the covariance's limits)
+inline size_t skel_sens_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved, int n_cols) {
+  const size_t cov = acino_skel_fte_covariance_pinned_workspace_bytes(p, n_clips, pin_unobserved);
+  return cov == 0 ? 0 : cov + 2 * skel_sens_column_bytes(p, n_clips, n_cols);
+}
+struct SkelSens {                  // what the pipeline hands to an entry's two launches
+  size_t NT;                       // frames of all clips: the grid of both
+  hipStream_t s;
+  const SkelDev* d_dev;
+  const SkelClip* d_clip;
+  const double* d_opv;
+  const unsigned char *d_fxm, *d_unobs;      // d_unobs: the clips' masks when the unobserved states are pinned, else NULL
+  double* d_cols;                  // the right-hand side -G out of rhs, S into combine
+};
+// An entry behind its own argument checks: the workspace check (query: the entry's ..._workspace_bytes; ws_cols: the columns
+// its buffers are sized for), skel_cov_launch_build, rhs(SkelSens) -> factor -> L^-1 -> L^-T on n_cols columns -> combine(SkelSens),
+// skel_cov_read_status.  rhs and combine each launch one kernel on stream s; kernels: the entry's three (both right-hand
+// sides, the combine), which get the 160 KB dynamic-LDS attribute once per device (once: a static of the entry).
+template <class Rhs, class Combine>
+inline int skel_sens_run(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                         const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams, const double* d_lo,
+                         const double* d_hi, const double* d_x, int n_cols, int ws_cols, const char* query, int32_t* h_status,
+                         void* d_ws, size_t ws_bytes, void* stream, int pin_unobserved, uint8_t* d_unobserved, PerDeviceOnce& once,
+                         const void* const (&kernels)[3], Rhs rhs, Combine combine) {
+  const int B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16;
+  const size_t NT = (size_t)p->n_frames * B;
+  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
+  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
+  const size_t col_bytes = skel_sens_column_bytes(p, B, ws_cols);
+  int rc = skel_check_workspace(d_ws, ws_bytes, lay.total + 2 * col_bytes, query, ACINO_ERR_WORKSPACE);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
+                                  d_unobserved)))
+    return rc;
+  char* base = (char*)d_ws;
+  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  const SkelDev* d_dev = reinterpret_cast<const SkelDev*>(base + lay.dev);
+  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
+  const unsigned char* d_fxm = reinterpret_cast<const unsigned char*>(base + lay.fxm);
+  double *d_b = D(lay.total), *d_y = D(lay.total + col_bytes);      // -G, then S; L^-1 (-G)
+  const SkelSens a = {NT, s, d_dev, d_clip, D(lay.opv), d_fxm, pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr, d_b};
+  if (once.first())
+    for (const void* k : kernels) ACINO_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  rhs(a);
+  ACINO_LAUNCH_CHECK();
+  if ((rc = skel_launch_factor(PT, B, d_dev, d_clip, D(lay.band), D(lay.diag0), s))) return rc;
+  if ((rc = skel_launch_fwdsub(PT, B, n_cols, d_dev, d_clip, D(lay.band), d_fxm, d_b, d_y, s))) return rc;
+  if ((rc = skel_launch_back_columns(PT, B, n_cols, d_dev, d_clip, D(lay.band), d_fxm, d_y, d_b, s))) return rc;
+  combine(a);
+  ACINO_LAUNCH_CHECK();
+  return skel_cov_read_status(d_clip, B, s, h_status);
+}
 // dynamic LDS of k_skel_cov_rates (skel_cov_rates.hip): three blocks [P][P + 1]
 inline size_t skel_cov_rates_lds(int P) { return sizeof(double) * (size_t)3 * P * (P + 1); }
 // k_skel_cov_rates on stream s, one workgroup per frame, after k_skel_selinv has left the blocks of the inverse in d_band:

@@ -1,7 +1,8 @@
 // The host layer of the generic-skeleton entries (skel_fte.hip, skel_cov.hip, skel_sample.hip, skel_calib.hip, skel_links.hip,
 // skel_reproj.hip): the argument checks, the workspace layout builder, the one writer of a SkelDev, the PT and camera-model
 // dispatch and the status read-back.
-// No device code.  skel_upload and skel_read_status are defined in skel_cov.hip, beside k_skel_dev_store.
+// No device code.  skel_upload and skel_read_status are defined in skel_cov.hip, beside k_skel_dev_store.  What comes behind the
+// checks of the two sensitivity entries (skel_calib.hip, skel_links.hip) is one function, skel_factor.hpp's skel_sens_run.
 #pragma once
 #include <cstdint>
 #include <type_traits>

@@ -32,12 +32,14 @@
 //                           so that lanes walking down a column fall on different banks.
 //                           LDS: (2 n_act (K | 1) + n_act (n_act + 1) + K^2 + n_ops 12 + 4 (3 n_act + 6 K + 9)) doubles, 67 KB at
 //                           the limits.
+// The blocks both kernels share with skel_calib.hip's are in skel_sens_dev.hpp, the host pipeline behind the entry's own checks is
+// skel_factor.hpp's skel_sens_run; the kept row of a (camera, slot) stays written out here, as there (skel_calib.hip says why).
 // No workgroup waits for another; vector stores only; the result of a clip is the same bits whatever else shares the call (every
 // kernel's arithmetic on a clip reads that clip's data alone).
 #include <cstddef>
 #include <cstdint>
 
-#include "skel_factor.hpp"
+#include "skel_sens_dev.hpp"
 
 namespace acino {
 
@@ -76,27 +78,13 @@ k_skel_links_rhs(const SkelDev* __restrict__ dev, const SkelLinkGroups grp, cons
   extern __shared__ __attribute__((aligned(16))) double skl_smem[];
   const SkelDev& D = *dev;
   const int tid = threadIdx.x, n = blockIdx.x;
-  const int P = D.n_act, PT = D.PT, C = D.n_cams, NPOSE = D.n_pose, NOPS = D.n_ops, N = D.n_frames, K = grp.K;
+  const int P = D.n_act, C = D.n_cams, NPOSE = D.n_pose, NOPS = D.n_ops, K = grp.K;
   double* opv = skl_smem;                                    // [n_ops][4][3]
   double* pos = opv + NOPS * 12;                             // [n_pose][3]
   double* G = pos + NPOSE * 3;                               // [(l * 3 + i) * P + p]
   double* V = G + (size_t)NPOSE * 3 * P;                     // [(l * 3 + i) * K + g]: D_l, then Mw_l D_l
   double* Mw = V + (size_t)NPOSE * 3 * K;                    // [l * 9 + i * 3 + j]
-  for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
-  __syncthreads();
-  if (tid < 3) {                                             // poses, coordinate by coordinate, in program order
-    const double root = x[(size_t)n * P + tid];
-    for (int s = 0; s < NPOSE; ++s) pos[s * 3 + tid] = root;
-    for (int k = 0; k < NOPS; ++k) pos[D.op[k].child * 3 + tid] = pos[D.op[k].parent * 3 + tid] + opv[(k * 4) * 3 + tid];
-  }
-  for (int e = tid; e < NPOSE * P; e += 256) {
-    const int l = e / P, p = e - l * P;
-    double gc[3];
-    skel_pose_jac_col(D, opv, l, p, gc);
-    G[(l * 3) * P + p] = gc[0];
-    G[(l * 3 + 1) * P + p] = gc[1];
-    G[(l * 3 + 2) * P + p] = gc[2];
-  }
+  skel_sens_frame(D, n, x, opv_all, opv, pos, G);
   for (int e = tid; e < NPOSE * 3 * K; e += 256) {
     const int li = e / K, g = e - li * K;
     V[e] = skel_link_direct(D, grp, opv, li / 3, li % 3, g);
@@ -145,20 +133,7 @@ k_skel_links_rhs(const SkelDev* __restrict__ dev, const SkelLinkGroups grp, cons
     V[(l * 3 + 2) * K + g] = M[6] * d0 + M[7] * d1 + M[8] * d2;
   }
   __syncthreads();
-  const int b = n / N, nl = n - b * N;
-  for (int task = tid; task < K * P; task += 256) {
-    const int g = task / P, p = task - g * P;
-    double acc = 0.0;
-    if (!fxm[(size_t)n * PT + p]) {
-      for (int l = 0; l < NPOSE; ++l) {
-        acc += G[(l * 3) * P + p] * V[(l * 3) * K + g];
-        acc += G[(l * 3 + 1) * P + p] * V[(l * 3 + 1) * K + g];
-        acc += G[(l * 3 + 2) * P + p] * V[(l * 3 + 2) * K + g];
-      }
-      acc = -acc;
-    }
-    rhs[(((size_t)b * K + g) * N + nl) * P + p] = acc;
-  }
+  skel_sens_rhs_out(D, n, K, G, fxm, rhs, [&](int g, int l, int i) { return V[(l * 3 + i) * K + g]; });
 }
 
 // sol: [n_clips][K][N][n_act] (the columns of -A^-1 G); sigma: [K][K] or NULL; unknown: [K] or NULL; unobs: NULL, or the clips'
@@ -171,22 +146,9 @@ k_skel_links_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict
   extern __shared__ __attribute__((aligned(16))) double skl_smem[];
   const SkelDev& D = *dev;
   const int n = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, N = D.n_frames, K = grp.K, LDK = K | 1, LDC = P + 1;
-  const int b = n / N, nl = n - b * N;
-  if (clip[b].status != 0) {
-    const double nan = __builtin_nan("");
-    for (int e = tid; e < P * K; e += 256)
-      if (sens) sens[(size_t)n * P * K + e] = nan;
-    for (int e = tid; e < NPOSE * 3 * K; e += 256)
-      if (dpos) dpos[(size_t)n * NPOSE * 3 * K + e] = nan;
-    for (int e = tid; e < P * P; e += 256)
-      if (cov_x) cov_x[(size_t)n * P * P + e] = nan;
-    for (int e = tid; e < NPOSE * 9; e += 256)
-      if (cov_pos) cov_pos[(size_t)n * NPOSE * 9 + e] = nan;
-    for (int e = tid; e < NPOSE; e += 256)
-      if (std_pos) std_pos[(size_t)n * NPOSE + e] = nan;
-    return;
-  }
+  const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, K = grp.K, LDK = K | 1, LDC = P + 1;
+  const int b = n / D.n_frames;
+  if (clip[b].status != 0) return skel_sens_nan(D, n, K, sens, dpos, cov_x, cov_pos, std_pos);
   double* Sm = skl_smem;                                     // S_n [P][LDK]
   double* Tm = Sm + (size_t)P * LDK;                         // S_n Sigma [P][LDK]
   double* Cx = Tm + (size_t)P * LDK;                         // cov_x_links [P][P + 1]
@@ -196,35 +158,9 @@ k_skel_links_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict
   double* Tl = Gw + 3 * P;
   double* Ts = Tl + 3 * K;
   double* out9 = Ts + 3 * K;
-  for (int e = tid; e < P * K; e += 256) {
-    const int col = e / P, p = e - col * P;
-    Sm[p * LDK + col] = sol[(((size_t)b * K + col) * N + nl) * P + p];
-  }
   if (sigma)
     for (int e = tid; e < K * K; e += 256) Sg[e] = sigma[e];
-  __syncthreads();
-  if (sens)
-    for (int e = tid; e < P * K; e += 256) sens[(size_t)n * P * K + e] = Sm[(e / K) * LDK + e % K];
-  if (sigma && cov_x) {
-    for (int e = tid; e < P * K; e += 256) {
-      const int p = e / K, j = e - p * K;
-      double acc = 0.0;
-      for (int i = 0; i < K; ++i) acc += Sm[p * LDK + i] * Sg[i * K + j];
-      Tm[p * LDK + j] = acc;
-    }
-    __syncthreads();
-    for (int e = tid; e < P * P; e += 256) {
-      const int p = e / P, q = e - p * P;
-      if (p <= q) {
-        double acc = 0.0;
-        for (int j = 0; j < K; ++j) acc += Tm[p * LDK + j] * Sm[q * LDK + j];
-        Cx[p * LDC + q] = acc;
-        Cx[q * LDC + p] = acc;
-      }
-    }
-    __syncthreads();
-    for (int e = tid; e < P * P; e += 256) cov_x[(size_t)n * P * P + e] = Cx[(e / P) * LDC + e % P];
-  }
+  skel_sens_states(D, n, K, LDK, sol, Sg, sigma && cov_x, Sm, Tm, Cx, sens, cov_x);
   if (!dpos && !cov_pos && !std_pos) return;
   const bool want_cov = sigma && (cov_pos || std_pos);
   for (int e = tid; e < NOPS * 12; e += 256) opv[e] = opv_all[(size_t)n * NOPS * 12 + e];
@@ -232,20 +168,10 @@ k_skel_links_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict
   for (int l0 = 0; l0 < NPOSE; l0 += 4) {                   // a wave is one pose slot; no workgroup barrier inside
     const int l = l0 + wave;
     if (l >= NPOSE) break;
-    bool dep = false;
-    if (lane < P) {
-      double gc[3];
-      skel_pose_jac_col(D, opv, l, lane, gc);
-      Gw[lane] = gc[0];
-      Gw[P + lane] = gc[1];
-      Gw[2 * P + lane] = gc[2];
-      if (unobs) dep = unobs[(size_t)b * P + lane] && (gc[0] != 0.0 || gc[1] != 0.0 || gc[2] != 0.0);
-    }
+    bool dep = skel_sens_pose_jac(D, opv, l, lane, unobs ? unobs + (size_t)b * P : nullptr, Gw);
     if (unknown && lane < K) dep = dep || (unknown[lane] && (D.pmask[l] & grp.gm[lane]) != 0ull);
     const bool undet = __any(dep ? 1 : 0) != 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    sk_wave_handover();
     if (lane < 3 * K) {                                      // T_l = G_l S_n + D_l: the states' share in state order, then the direct term
       const int i = lane / K, g = lane - i * K;
       double acc = 0.0;
@@ -258,32 +184,15 @@ k_skel_links_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict
       __builtin_amdgcn_wave_barrier();
       continue;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    sk_wave_handover();
     if (lane < 3 * K) {
       const int i = lane / K, j = lane - i * K;
       double acc = 0.0;
       for (int g = 0; g < K; ++g) acc += Tl[i * K + g] * Sg[g * K + j];
       Ts[lane] = acc;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 6) {                                          // the upper triangle, mirrored
-      const int i = lane < 3 ? 0 : (lane < 5 ? 1 : 2), j = lane < 3 ? lane : (lane < 5 ? lane - 2 : 2);
-      double s = 0.0;
-      for (int g = 0; g < K; ++g) s += Ts[i * K + g] * Tl[j * K + g];
-      out9[3 * i + j] = s;
-      out9[3 * j + i] = s;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 9 && cov_pos) cov_pos[((size_t)n * NPOSE + l) * 9 + lane] = undet ? __builtin_nan("") : out9[lane];
-    if (lane == 0 && std_pos)
-      std_pos[(size_t)n * NPOSE + l] = undet ? __builtin_inf() : sqrt(fmax(out9[0] + out9[4] + out9[8], 0.0));
-    __builtin_amdgcn_wave_barrier();
+    skel_sens_pos_out(lane, K, Ts, Tl, out9, undet, cov_pos ? cov_pos + ((size_t)n * NPOSE + l) * 9 : nullptr,
+                      std_pos ? std_pos + (size_t)n * NPOSE + l : nullptr);
   }
 }
 
@@ -291,16 +200,10 @@ k_skel_links_combine(const SkelDev* __restrict__ dev, const SkelClip* __restrict
 
 using namespace acino;
 
-static size_t skl_column_bytes(const acino_skel_fte_params* p, int n_clips) {
-  return skel_align256(sizeof(double) * (size_t)n_clips * SKL_MAXK * p->n_frames * p->n_active);
-}
-
 extern "C" {
 
 size_t acino_skel_fte_link_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved) {
-  const size_t cov = acino_skel_fte_covariance_pinned_workspace_bytes(p, n_clips, pin_unobserved);
-  if (cov == 0) return 0;
-  return cov + 2 * skl_column_bytes(p, n_clips);
+  return skel_sens_workspace_bytes(p, n_clips, pin_unobserved, SKL_MAXK);
 }
 
 int acino_skel_fte_link_sensitivity(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
@@ -326,46 +229,23 @@ int acino_skel_fte_link_sensitivity(const acino_skel_fte_params* p, int n_clips,
     ACINO_REQUIRE(h_group[k] >= -1 && h_group[k] < n_groups, "h_group: every op's group must be -1 (fixed) or 0..n_groups-1");
     if (h_group[k] >= 0) grp.gm[h_group[k]] |= 1ull << k;
   }
-  const int N = p->n_frames, B = n_clips, P = p->n_active, PT = (P + 15) / 16 * 16, K = n_groups;
-  const size_t NT = (size_t)N * B;                           // frames of all clips
-  const bool pin = pin_unobserved == 1, observe = pin || d_unobserved != nullptr;
-  const SkelCovLayout lay = skel_cov_layout(NT, B, P, PT, p->n_ops, observe);
-  const size_t col_bytes = skl_column_bytes(p, B);
-  if ((rc = skel_check_workspace(d_ws, ws_bytes, lay.total + 2 * col_bytes, "acino_skel_fte_link_workspace_bytes", ACINO_ERR_WORKSPACE)))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = skel_cov_launch_build(p, B, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, d_ws, lay, s, observe, pin,
-                                  d_unobserved)))
-    return rc;
-  char* base = (char*)d_ws;
-  auto D = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
-  SkelDev* d_dev = reinterpret_cast<SkelDev*>(base + lay.dev);
-  SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
-  unsigned char* d_fxm = reinterpret_cast<unsigned char*>(base + lay.fxm);
-  const unsigned char* d_unobs = pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr;
-  double* d_b = D(lay.total);                                // -G, then S: [B][K][N][P]
-  double* d_y = D(lay.total + col_bytes);                    // L^-1 (-G)
-  const size_t lds_rhs = sizeof(double) * skel_links_rhs_doubles(p->n_ops, p->n_pose, P, K);
-  const size_t lds_comb = sizeof(double) * skel_links_combine_doubles(p->n_ops, P, K);
+  const int P = p->n_active, K = n_groups;
   static PerDeviceOnce attr;
-  if (attr.first()) {
-    for (int model = 0; model < 2; ++model)
-      ACINO_HIP_CHECK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(skel_camera_kernel(model, k_skel_links_rhs<false>, k_skel_links_rhs<true>)),
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ACINO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_skel_links_combine), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-  }
-  hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_links_rhs<false>, k_skel_links_rhs<true>), dim3((unsigned)NT), dim3(256),
-                     lds_rhs, s, d_dev, grp, d_x, d_meas, d_w, D(lay.opv), d_fxm, d_b);
-  ACINO_LAUNCH_CHECK();
-  if ((rc = skel_launch_factor(PT, B, d_dev, d_clip, D(lay.band), D(lay.diag0), s))) return rc;
-  if ((rc = skel_launch_fwdsub(PT, B, K, d_dev, d_clip, D(lay.band), d_fxm, d_b, d_y, s))) return rc;
-  if ((rc = skel_launch_back_columns(PT, B, K, d_dev, d_clip, D(lay.band), d_fxm, d_y, d_b, s))) return rc;
-  hipLaunchKernelGGL(k_skel_links_combine, dim3((unsigned)NT), dim3(256), lds_comb, s, d_dev, d_clip, grp, d_b, d_cov_links, d_unknown,
-                     D(lay.opv), d_unobs, d_sens, d_dpos, d_cov_x, d_cov_pos, d_std_pos);
-  ACINO_LAUNCH_CHECK();
-  return skel_cov_read_status(d_clip, B, s, h_status);
+  const void* const kernels[3] = {(const void*)k_skel_links_rhs<false>, (const void*)k_skel_links_rhs<true>, (const void*)k_skel_links_combine};
+  // (the column buffers are sized for SKL_MAXK groups whatever K is: the query does not know K)
+  return skel_sens_run(
+      p, n_clips, camera_model, h_ops, h_active, d_meas, d_w, d_cams, d_lo, d_hi, d_x, K, SKL_MAXK, "acino_skel_fte_link_workspace_bytes",
+      h_status, d_ws, ws_bytes, stream, pin_unobserved, d_unobserved, attr, kernels,
+      [&](const SkelSens& a) {
+        hipLaunchKernelGGL(skel_camera_kernel(camera_model, k_skel_links_rhs<false>, k_skel_links_rhs<true>), dim3((unsigned)a.NT), dim3(256),
+                           sizeof(double) * skel_links_rhs_doubles(p->n_ops, p->n_pose, P, K), a.s, a.d_dev, grp, d_x, d_meas, d_w, a.d_opv,
+                           a.d_fxm, a.d_cols);
+      },
+      [&](const SkelSens& a) {
+        hipLaunchKernelGGL(k_skel_links_combine, dim3((unsigned)a.NT), dim3(256), sizeof(double) * skel_links_combine_doubles(p->n_ops, P, K),
+                           a.s, a.d_dev, a.d_clip, grp, a.d_cols, d_cov_links, d_unknown, a.d_opv, a.d_unobs, d_sens, d_dpos, d_cov_x,
+                           d_cov_pos, d_std_pos);
+      });
 }
 
 }  // extern "C"

@@ -104,9 +104,7 @@ k_skel_sample_back(const SkelDev* __restrict__ dev, const SkelClip* __restrict__
       if (s0 + c < S && p < P && !fxm[(size_t)n * PT + p]) v = z_all[row0 + c * srow + (size_t)n * P + p];
       stage[Sh::st(c, p)] = v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    sk_wave_handover();
     d4 r[NTP];
 #pragma unroll
     for (int kb = 0; kb < NTP; ++kb)
@@ -155,9 +153,7 @@ k_skel_sample_back(const SkelDev* __restrict__ dev, const SkelClip* __restrict__
     for (int kb = 0; kb < NTP; ++kb)
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) stage[Sh::st(li, kb * 16 + lk + 4 * rr)] = dn[kb][rr];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    sk_wave_handover();
     for (int e = lane; e < 16 * PT; e += 64) {
       const int c = e / PT, p = e % PT;
       if (s0 + c < S && p < P) {

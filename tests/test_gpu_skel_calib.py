@@ -302,3 +302,28 @@ def test_solve_entries(gpu_lib, golden_dir):
         assert e <= 1e-10
         for a in 0.01 * np.eye(3):      # and every frame's S is a row of a valid sensitivity (the bar of the worst accepted input)
             assert kref.identity_error(res["sens_cams"][mine][:, prob.ACT], prob.R, a) <= kref.bar(kref.D0_REFUSED) * 0.01
+
+
+def test_null_output_subsets(gpu_lib, golden_dir):
+    """The C entry with outputs left NULL, which the Python layer never does (pt16: 12 frames, PT 16): ``d_sens`` alone without a
+    Sigma - the combine returns after S_n - and ``d_std_pos_cal`` alone with one.  What comes back is the full call's, bit for bit."""
+    import ctypes as C
+
+    import torch
+    from acinoset_amd import build
+    from acinoset_amd._lib import check, lib, ptr
+    c = scases.case(golden_dir, "pt16")
+    model, x, act = c["model"], c["x"], c["prob"].ACT
+    sigma = fref.random_psd(2)
+    full = build.model_calibration_sensitivity([model], [x], sigma)[0]
+    io_ = build._skel_inputs([model], [x], lambda p, B: lib().acino_skel_fte_calibration_workspace_bytes(C.byref(p), B, 0), l1_eps=1e-2)
+    N, L, W = model.N, len(model.names), 6 * c["prob"].C
+    empty = lambda *shape: torch.empty((1, N) + shape, dtype=torch.float64, device=io_["dev"])   # noqa: E731
+    sig_d = torch.as_tensor(sigma, dtype=torch.float64, device=io_["dev"]).contiguous()
+    status, null = (C.c_int32 * 1)(), ptr(None)
+    sens = empty(len(act), W)
+    check(lib().acino_skel_fte_calibration_sensitivity(*io_["head"], null, ptr(sens), null, null, null, status, *io_["tail"], 0, null))
+    assert status[0] == 0 and np.array_equal(sens[0].cpu().numpy(), full["sens_cams"][:, act])
+    std = empty(L)
+    check(lib().acino_skel_fte_calibration_sensitivity(*io_["head"], ptr(sig_d), null, null, null, ptr(std), status, *io_["tail"], 0, null))
+    assert status[0] == 0 and np.array_equal(std[0].cpu().numpy(), full["std_pos_calib"])

@@ -369,3 +369,34 @@ def test_solve_entries(gpu_lib, golden_dir, monkeypatch):
               f"T Sigma T^T {e2:.2e}, cov_x_links against S Sigma S^T {e3:.2e}")
         assert e <= 1e-10 and e2 <= 1e-10 and e3 <= 1e-10
     assert seen == 70
+
+
+def test_null_output_subsets(gpu_lib, golden_dir):
+    """The C entry with outputs left NULL, which the Python layer never does (pt16: 12 frames, PT 16): ``d_dpos`` alone without a
+    Sigma - the combine goes past S_n and cov_x to T_l - and ``d_sens`` with ``d_std_pos`` with one (no cov_x: T and T S_n^T are
+    skipped).  What comes back is the full call's, bit for bit."""
+    import ctypes as C
+
+    import torch
+    from acinoset_amd import build
+    from acinoset_amd._lib import check, lib, ptr
+    c = scases.case(golden_dir, "pt16")
+    model, x, act = c["model"], c["x"], c["prob"].ACT
+    grp, K = build.link_groups(model.prog, "links")
+    sigma = lkref.random_psd(K)
+    full = build.model_link_sensitivity([model], [x], "links", sigma)[0]
+    io_ = build._skel_inputs([model], [x], lambda p, B: lib().acino_skel_fte_link_workspace_bytes(C.byref(p), B, 0), l1_eps=1e-2)
+    N, L = model.N, len(model.names)
+    empty = lambda *shape: torch.empty((1, N) + shape, dtype=torch.float64, device=io_["dev"])   # noqa: E731
+    sig_d = torch.as_tensor(sigma, dtype=torch.float64, device=io_["dev"]).contiguous()
+    grp_c = (C.c_int32 * len(grp))(*[int(g) for g in grp])
+    status, null = (C.c_int32 * 1)(), ptr(None)
+    dpos = empty(L, 3, K)
+    check(lib().acino_skel_fte_link_sensitivity(*io_["head"], grp_c, K, null, null, null, ptr(dpos), null, null, null, status,
+                                                *io_["tail"], 0, null))
+    assert status[0] == 0 and np.array_equal(dpos[0].cpu().numpy(), full["dpos_links"])
+    sens, std = empty(len(act), K), empty(L)
+    check(lib().acino_skel_fte_link_sensitivity(*io_["head"], grp_c, K, ptr(sig_d), null, ptr(sens), null, null, null, ptr(std), status,
+                                                *io_["tail"], 0, null))
+    assert status[0] == 0 and np.array_equal(sens[0].cpu().numpy(), full["sens_links"][:, act])
+    assert np.array_equal(std[0].cpu().numpy(), full["std_pos_links"])
