@@ -888,15 +888,16 @@ def _skel_workspace(model, act, workspace_bytes):
     return p, nbytes
 
 
-def _skel_fit_call(model, act, dev, sized, call):
+def _skel_fit_call(model, act, dev, sized, call, box=True):
     """The skeleton's side of a per-frame fit's library call: the boxes at the columns ``act`` on the device, ``sized`` (the pair
     of ``_skel_workspace``), the workspace aligned to 256 bytes, the active states as int32.  ``call(skel, box, ws)`` returns the
-    status: ``skel`` = (params, ops, active), ``box`` = (lo, hi), ``ws`` = (workspace, its bytes, stream)."""
+    status: ``skel`` = (params, ops, active), ``box`` = (lo, hi) - () with ``box=False``, for an entry that reads no box -,
+    ``ws`` = (workspace, its bytes, stream)."""
     p, nbytes = sized
-    lo, hi = calib._to_dev(model.lo[:, act], dev), calib._to_dev(model.hi[:, act], dev)
+    lo_hi = [calib._to_dev(b[:, act], dev) for b in (model.lo, model.hi)] if box else []
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)      # (it goes back to the allocator of this very stream)
     act_c = (C.c_int32 * len(act))(*[int(a) for a in act])
-    check(call((C.byref(p), _ops_array(model.prog), act_c), (ptr(lo), ptr(hi)),
+    check(call((C.byref(p), _ops_array(model.prog), act_c), tuple(ptr(b) for b in lo_hi),
                (C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr())))
 
 
@@ -1000,7 +1001,7 @@ def _pose_fit_start(model, fit_kw):
     return init_x
 
 
-MAX_LINK_GROUPS = 16        # LSC_MAXK of csrc/skel_link_scale.hip
+MAX_LINK_GROUPS = 16        # LSC_MAXK of csrc/link_scale_dev.hpp
 
 
 def link_groups(prog, groups="links"):
@@ -1062,22 +1063,15 @@ def link_scale_system(model, points, cov, fit, groups="links", prior_sigma=np.pi
     of numpy arrays: S [K, K], r [K], cost and n_used (sums over the used frames, in frame order); S_frames [N, K, K],
     r_frames [N, K], cost_frames [N], used [N] bool, status [N] (the fit's, 3 where a frame's matrix has no factor) and, with
     ``return_sens``, sens [N, n_active, K] = d x / d theta (NaN for an unused frame)."""
-    if isinstance(points, dict):
-        if cov is not None:
-            raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
-        points, cov = points["points"], points["cov"]
+    points, cov = _points_and_cov(points, cov)
     grp, K = link_groups(model.prog, groups)
     act = np.asarray(model.active, dtype=np.int32)
-    N, Pa, Lp = model.N, len(act), len(model.names)
+    N, Lp = model.N, len(model.names)
     if fte._shape(points) != (N, Lp, 3):
         raise ValueError(f"points must be [{N}, {Lp}, 3] (model.N frames, one slot per pose)")
     if cov is not None and fte._shape(cov) != (N, Lp, 3, 3):
         raise ValueError(f"cov must be [{N}, {Lp}, 3, 3]")
-    for key, shape in (("x", (N, Pa)), ("pinned", (N, Pa)), ("status", (N,))):
-        if fte._shape(fit[key]) != shape:
-            raise ValueError(f"fit['{key}'] must be {list(shape)}: the result of pose_fit on this model")
-    if m is not None and fte._shape(m) != (N, Pa):
-        raise ValueError(f"m must be [{N}, {Pa}] (the active states)")
+    _check_fit(fit, m, N, len(act), "pose_fit")
     for name, val in (("prior_sigma", prior_sigma), ("sigma_iso", sigma_iso)):
         if not (np.isfinite(val) and val > 0):
             raise ValueError(f"{name} must be finite and > 0")
@@ -1086,6 +1080,35 @@ def link_scale_system(model, points, cov, fit, groups="links", prior_sigma=np.pi
     if m is None:
         m = _pose_fit_centre(model, points, cov, None, sigma_iso)
     pts, cv = calib._to_dev(points, dev), None if cov is None else calib._to_dev(cov, dev)
+    return _link_scale_call(model, act, grp, K, fit, m, return_sens, dev, sized,
+                            lambda skel, g, f, outs, ws: lib().acino_skel_link_scale(
+                                *skel, *g, float(prior_sigma), float(sigma_iso), ptr(pts), ptr(cv), *f, N, *outs, *ws))
+
+
+def _points_and_cov(points, cov):
+    """``points`` may be the triangulation's dict: its points and its cov then, and ValueError when ``cov`` is given beside it."""
+    if isinstance(points, dict):
+        if cov is not None:
+            raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
+        return points["points"], points["cov"]
+    return points, cov
+
+
+def _check_fit(fit, m, N, Pa, fit_name):
+    """The shapes of ``fit[...]`` (``fit_name``: the pose fit the message names) and of ``m``."""
+    for key, shape in (("x", (N, Pa)), ("pinned", (N, Pa)), ("status", (N,))):
+        if fte._shape(fit[key]) != shape:
+            raise ValueError(f"fit['{key}'] must be {list(shape)}: the result of {fit_name} on this model")
+    if m is not None and fte._shape(m) != (N, Pa):
+        raise ValueError(f"m must be [{N}, {Pa}] (the active states)")
+
+
+def _link_scale_call(model, act, grp, K, fit, m, return_sens, dev, sized, call):
+    """What ``link_scale_system`` and ``link_scale_system_pixels`` do once their checks are through and their measurement is on
+    the device: the fit and ``m`` to the device, the outputs, the library call through ``_skel_fit_call`` - ``call(skel, grp, fit,
+    outs, ws)`` with ``grp`` = (groups, K), ``fit`` = (x, m, pinned, status), ``outs`` = (S, r, F, used, frame_status, sens,
+    total) - and the dict read back."""
+    N, Pa = model.N, len(act)
     x, mc = calib._to_dev(fit["x"], dev), calib._to_dev(m, dev)
     u8 = lambda a: torch.as_tensor(a, device=dev).to(torch.uint8).contiguous()      # noqa: E731
     pinned, status = u8(fit["pinned"]), u8(fit["status"])
@@ -1094,20 +1117,14 @@ def link_scale_system(model, points, cov, fit, groups="links", prior_sigma=np.pi
     used, fst = torch.empty((N,), **b8), torch.empty((N,), **b8)
     sens = torch.empty((N, Pa, K), **f64) if return_sens else None
     total = torch.zeros((K * K + K + 2,), **f64)
-    p, nbytes = sized
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    act_c, grp_c = (C.c_int32 * len(act))(*[int(a) for a in act]), (C.c_int32 * max(len(grp), 1))(*[int(g) for g in grp])
-    check(lib().acino_skel_link_scale(C.byref(p), _ops_array(model.prog), act_c, grp_c, K, float(prior_sigma), float(sigma_iso),
-                                      ptr(pts), ptr(cv), ptr(x), ptr(mc), ptr(pinned), ptr(status), N, ptr(S), ptr(r), ptr(F),
-                                      ptr(used), ptr(fst), ptr(sens), ptr(total), C.c_void_p((ws.data_ptr() + 255) // 256 * 256),
-                                      nbytes, stream_ptr()))
+    grp_c = (C.c_int32 * max(len(grp), 1))(*[int(g) for g in grp])
+    _skel_fit_call(model, act, dev, sized, lambda skel, _box, ws: call(
+        skel, (grp_c, K), (ptr(x), ptr(mc), ptr(pinned), ptr(status)),
+        (ptr(S), ptr(r), ptr(F), ptr(used), ptr(fst), ptr(sens), ptr(total)), ws), box=False)
     tot = total.cpu().numpy()
-    out = dict(S=tot[:K * K].reshape(K, K), r=tot[K * K:K * K + K], cost=float(tot[K * K + K]), n_used=int(tot[K * K + K + 1]),
-               S_frames=S.cpu().numpy(), r_frames=r.cpu().numpy(), cost_frames=F.cpu().numpy(), used=used.cpu().numpy().astype(bool),
-               status=fst.cpu().numpy(), groups=grp, sens=None)
-    if return_sens:
-        out["sens"] = sens.cpu().numpy()
-    return out
+    return dict(S=tot[:K * K].reshape(K, K), r=tot[K * K:K * K + K], cost=float(tot[K * K + K]), n_used=int(tot[K * K + K + 1]),
+                S_frames=S.cpu().numpy(), r_frames=r.cpu().numpy(), cost_frames=F.cpu().numpy(), used=used.cpu().numpy().astype(bool),
+                status=fst.cpu().numpy(), groups=grp, sens=sens.cpu().numpy() if return_sens else None)
 
 
 def link_scale_step(S, r, theta, lam, prior_prec=0.0):
@@ -1143,10 +1160,7 @@ def fit_link_scales(model, points=None, cov=None, groups="links", x0=None, scale
     _check_outer(scale_prior_sigma, max_outer, tol)
     if points is None:
         points = model_triangulation(model)
-    if isinstance(points, dict):
-        if cov is not None:
-            raise ValueError("cov comes with the dict of triangulate_multiview_dense: pass one or the other")
-        points, cov = points["points"], points["cov"]
+    points, cov = _points_and_cov(points, cov)
     sigma_iso = fit_kw.get("sigma_iso", 0.01)
     m = _pose_fit_centre(model, points, cov, x0, sigma_iso)
 
@@ -1223,11 +1237,16 @@ def _pixel_start(model, x0):
     """The start of ``pose_fit_pixels`` on ``model`` clipped to the box, [N, n_active]: ``x0``, or the chain of its default."""
     act = np.asarray(model.active, dtype=np.int64)
     if x0 is None:
-        init_x = _pose_fit_start(model, {})
-        if init_x is None:
-            raise ValueError("no frame has a pose fit to start from (no slot was triangulated in the whole clip): pass x0")
-        x0 = init_x[:, act]
+        x0 = _default_pixel_start(model)
     return np.clip(np.asarray(calib._host(x0), dtype=np.float64), model.lo[:, act], model.hi[:, act])
+
+
+def _default_pixel_start(model):
+    """The default start of ``pose_fit_pixels``, [N, n_active]: the chain of ``pose_fit_start``; ValueError without a fit."""
+    init_x = _pose_fit_start(model, {})
+    if init_x is None:
+        raise ValueError("no frame has a pose fit to start from (no slot was triangulated in the whole clip): pass x0")
+    return init_x[:, np.asarray(model.active, dtype=np.int64)]
 
 
 def link_scale_system_pixels(model, fit, groups="links", det=None, thresh=0.5, f_scale=5.0, sigma_px=None, prior_sigma=np.pi,
@@ -1244,7 +1263,7 @@ def link_scale_system_pixels(model, fit, groups="links", det=None, thresh=0.5, f
     ``groups="global"``).  Returns the dict of ``link_scale_system``."""
     grp, K = link_groups(model.prog, groups)
     act = np.asarray(model.active, dtype=np.int32)
-    N, Pa, Lp, Cn = model.N, len(act), len(model.names), int(np.shape(model.meas)[1])
+    N, Lp, Cn = model.N, len(model.names), int(np.shape(model.meas)[1])
     camera_model = getattr(model, "camera_model", "fisheye")
     if camera_model not in calib.CAMERAS:
         raise ValueError(f"the model's camera_model must be one of {calib.CAMERA_MODELS}")
@@ -1252,11 +1271,7 @@ def link_scale_system_pixels(model, fit, groups="links", det=None, thresh=0.5, f
         raise ValueError(f"det must be [{N}, {Cn}, {Lp}, 3] (model.N frames, the model's cameras, one slot per pose)")
     if not 1 <= Cn <= MAX_CAMS:
         raise ValueError(f"the model holds {Cn} cameras: 1..{MAX_CAMS} are supported")
-    for key, shape in (("x", (N, Pa)), ("pinned", (N, Pa)), ("status", (N,))):
-        if fte._shape(fit[key]) != shape:
-            raise ValueError(f"fit['{key}'] must be {list(shape)}: the result of pose_fit_pixels on this model")
-    if m is not None and fte._shape(m) != (N, Pa):
-        raise ValueError(f"m must be [{N}, {Pa}] (the active states)")
+    _check_fit(fit, m, N, len(act), "pose_fit_pixels")
     if sigma_px is None:
         sigma_px = _model_sigma_px(model)
     for name, val in (("prior_sigma", prior_sigma), ("f_scale", f_scale), ("sigma_px", sigma_px)):
@@ -1269,31 +1284,12 @@ def link_scale_system_pixels(model, fit, groups="links", det=None, thresh=0.5, f
     dev = calib._dev()
     if m is None:
         m = _pixel_start(model, None)
-    d = calib._to_dev(_model_detections(model) if det is None else det, dev)
-    cams = torch.as_tensor(recs, device=dev)
-    x, mc = calib._to_dev(fit["x"], dev), calib._to_dev(m, dev)
-    u8 = lambda a: torch.as_tensor(a, device=dev).to(torch.uint8).contiguous()      # noqa: E731
-    pinned, status = u8(fit["pinned"]), u8(fit["status"])
-    f64, b8 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.uint8, device=dev)
-    S, r, F = torch.empty((N, K, K), **f64), torch.empty((N, K), **f64), torch.empty((N,), **f64)
-    used, fst = torch.empty((N,), **b8), torch.empty((N,), **b8)
-    sens = torch.empty((N, Pa, K), **f64) if return_sens else None
-    total = torch.zeros((K * K + K + 2,), **f64)
-    p, nbytes = sized
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    act_c, grp_c = (C.c_int32 * len(act))(*[int(a) for a in act]), (C.c_int32 * max(len(grp), 1))(*[int(g) for g in grp])
+    d, cams = calib._to_dev(_model_detections(model) if det is None else det, dev), torch.as_tensor(recs, device=dev)
     prm = PoseFitPxParams(calib.CAMERAS[camera_model].code, 1, 1, 0, 1e-3, 1e-10, 1e-10, float(prior_sigma), float(thresh),
                           float(f_scale), float(sigma_px))
-    check(lib().acino_skel_link_scale_px(C.byref(prm), C.byref(p), _ops_array(model.prog), act_c, grp_c, K, ptr(d), N, Cn, ptr(cams),
-                                         ptr(x), ptr(mc), ptr(pinned), ptr(status), ptr(S), ptr(r), ptr(F), ptr(used), ptr(fst),
-                                         ptr(sens), ptr(total), C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
-    tot = total.cpu().numpy()
-    out = dict(S=tot[:K * K].reshape(K, K), r=tot[K * K:K * K + K], cost=float(tot[K * K + K]), n_used=int(tot[K * K + K + 1]),
-               S_frames=S.cpu().numpy(), r_frames=r.cpu().numpy(), cost_frames=F.cpu().numpy(), used=used.cpu().numpy().astype(bool),
-               status=fst.cpu().numpy(), groups=grp, sens=None)
-    if return_sens:
-        out["sens"] = sens.cpu().numpy()
-    return out
+    return _link_scale_call(model, act, grp, K, fit, m, return_sens, dev, sized,
+                            lambda skel, g, f, outs, ws: lib().acino_skel_link_scale_px(
+                                C.byref(prm), *skel, *g, ptr(d), N, Cn, ptr(cams), *f, *outs, *ws))
 
 
 def fit_link_scales_pixels(model, groups="links", x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=None,
@@ -1357,12 +1353,6 @@ def pose_fit_pixels(model, x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=
     act = np.asarray(model.active, dtype=np.int32)
     N, Pa, Lp, Cn = model.N, len(act), len(model.names), int(np.shape(model.meas)[1])
 
-    def start(d):
-        init_x = _pose_fit_start(model, {})
-        if init_x is None:
-            raise ValueError("no frame has a pose fit to start from (no slot was triangulated in the whole clip): pass x0")
-        return init_x[:, act]
-
     sized = []
 
     def ready(dev):                                          # (the workspace's refusal comes before anything is staged)
@@ -1375,7 +1365,8 @@ def pose_fit_pixels(model, x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=
     texts = dict(camera_model=f"the model's camera_model must be one of {calib.CAMERA_MODELS}",
                  det=f"det must be [{N}, {Cn}, {Lp}, 3] (model.N frames, the model's cameras, one slot per pose)",
                  cams="the model holds {} cameras: 1..{} are supported", x0=f"x0 must be [{N}, {Pa}] (the active states)")
-    return fte._pose_fit_px(launch, (lambda: _model_detections(model)) if det is None else det, x0, start, shape=(N, Cn, Lp),
+    return fte._pose_fit_px(launch, (lambda: _model_detections(model)) if det is None else det, x0,
+                            lambda d: _default_pixel_start(model), shape=(N, Cn, Lp),
                             active=act, n_full=model.P, camera_model=getattr(model, "camera_model", "fisheye"),
                             rig=(model.K, model.D, model.R, model.t), texts=texts, ready=ready,
                             tensors=isinstance(det, torch.Tensor) or isinstance(x0, torch.Tensor), thresh=thresh, f_scale=f_scale,

@@ -24,7 +24,8 @@ struct Spf {                       // the carved LDS of one workgroup
   int P, n_pose, n_ops, ldj, ldm, ks;
 };
 
-// offsets into the dynamic LDS, in units of 8 bytes: the regions both fits have; a model's own lie between M and pos (``middle``)
+// offsets into the dynamic LDS, in units of 8 bytes: the regions both fits have; a model's own lie between M and pos (``middle``).
+// ``jw_cols``: the columns of Jw when it holds more than the P of the pose (link_scale_dev.hpp: P + K); 0: P
 struct SpfLayout {
   int P, n_pose, n_ops;
   int ldj, ldm;                    // leading dimensions of Jw and of M (odd: columns on unlike banks)
@@ -35,12 +36,13 @@ struct SpfTake {                   // the next region of n doubles, in 16-byte s
   __host__ __device__ int operator()(int n) { return (o += (n + 1) & ~1) - ((n + 1) & ~1); }
 };
 template <class Middle>
-__host__ __device__ inline SpfLayout spf_layout(int P, int PT, int n_pose, int n_ops, SpfTake& take, Middle&& middle) {
+__host__ __device__ inline SpfLayout spf_layout(int P, int PT, int n_pose, int n_ops, SpfTake& take, Middle&& middle,
+                                                int jw_cols = 0) {
   SpfLayout L;
   L.P = P, L.n_pose = n_pose, L.n_ops = n_ops;
   L.ldj = 4 * (((3 * n_pose > P ? 3 * n_pose : P) + 3) / 4) + 1;      // (P: the rows of L^-1 take Jw's place for cov_x)
   L.ldm = PT + 1;                  // (a compile-time constant of the kernel: its offsets are immediates)
-  L.Jw = take(P * L.ldj);
+  L.Jw = take((jw_cols ? jw_cols : P) * L.ldj);
   L.M = take(PT * L.ldm);          // (PT rows: the tiles are stored whole, the rows beyond P are zeros)
   middle(take);
   L.pos = take(3 * n_pose);

@@ -9,8 +9,10 @@
 //   A = sum_c Jc^T Jc + kappa, B = sum_c Jc^T Jsc, C = sum_c Jsc^T Jsc, g = sum_c Jc^T u + kappa (x - m), c = sum_c Jsc^T u
 //   S_n = C - Y^T Y,  r_n = c - Y^T v,   Y = L^-1 B_F,  v = L^-1 g_F,  A_FF = L L^T  (lam = 0; pinned rows the identity's)
 // g and c carry w r, the exact gradient of the Cauchy cost; S_n is the IRLS Gauss-Newton curvature.  A model on top of
-// pose_fit_skel.hpp and pose_fit_px_dev.hpp, as skel_pose_fit_px.hip is; the elimination, the stores and the summing launch are
-// link_scale_dev.hpp's.  The kernels of skel_pose_fit.hip, skel_pose_fit_px.hip and skel_link_scale.hip are not touched.
+// pose_fit_skel.hpp and pose_fit_px_dev.hpp, as skel_pose_fit_px.hip is.  What the fit shares with its 3-D form is
+// link_scale_dev.hpp's: the arguments, the layout around the measurement's regions, the group masks, the load of x, m and pinned,
+// the scale directions, the Gram store, the elimination, the stores and the host path.  The kernels of skel_pose_fit.hip and
+// skel_pose_fit_px.hip are not touched.
 //
 // One 64-lane wave per frame, PT = 16, 32, 48, 64, both camera models, a grid-stride loop over the frames, no atomics, nothing
 // waits on another workgroup.
@@ -20,8 +22,8 @@
 //              sqrt(w) / sigma_px (J_pi R_c) (2 x 3) and u = sqrt(w) r / sigma_px per (camera, slot); then camera by camera the
 //              2 n_pose rows of [Jc Jsc] for all P + K columns, and the k-steps of ONE Gram product of PT / 16 + 1 tile rows
 //              (spf_gram_passes<PT + 16>) carried across the cameras.  A camera without a valid detection is skipped.  The store
-//              splits the result as the 3-D kernel does: rows below P are A's, rows P .. P + K - 1 hold B below column P and C's
-//              lower triangle beyond, mirrored.  The full 2 n_pose C x (P + K) Jacobian is never in LDS.
+//              is lsc_gram_store: rows below P are A's, rows P .. P + K - 1 hold B below column P and C's lower triangle beyond,
+//              mirrored.  The full 2 n_pose C x (P + K) Jacobian is never in LDS.
 //   g, c       column t = lane, lane + 64 (P + K may exceed 64: P = 51 with K = 16) against u, in (camera, row) order.
 //   tail       the cost by px_pair_cost / px_cost_finish (the value the pose fit reports), lsc_eliminate, lsc_store.
 //
@@ -33,54 +35,28 @@ namespace acino {
 
 struct LinkScalePxArgs {
   PxArgs px;
-  const SkelDev* dev;
-  const double *x, *m;
-  const uint8_t *pinned, *status;
-  int64_t n_frames;
-  LscOut out;
-  double kappa;
-  int K;
-  int8_t grp[ACINO_SKEL_MAX_OPS];  // per op: its group, -1: fixed
+  LscArgs c;
 };
 
-// offsets into the dynamic LDS, in units of 8 bytes: Jw widened by the K raw scale directions, the pixel measurement's regions
-// (as spx_layout; Jc has P + K columns), B (K columns of PT; Y takes its place), C, c and the op mask of every group
+// lsc_layout_around the pixel measurement's regions (as spx_layout; Jc has P + K columns), without ent
 struct LspLayout {
-  SpfLayout s;
+  LscLayout l;
   int ldc, group;
-  int Jc, cams, det, vm, jr, ur, B, C, c, gm, total;
+  int Jc, cams, det, vm, jr, ur;
 };
 __host__ __device__ inline LspLayout lsp_layout(int P, int PT, int n_pose, int n_ops, int n_cams, int K, bool pinhole) {
   LspLayout L;
-  SpfTake take;
-  SpfLayout& s = L.s;
-  s.P = P, s.n_pose = n_pose, s.n_ops = n_ops;
-  s.ldj = 4 * (((3 * n_pose > P ? 3 * n_pose : P) + 3) / 4) + 1;
-  s.ldm = PT + 1;
-  s.Jw = take((P + K) * s.ldj);
-  s.M = take(PT * s.ldm);
   L.ldc = 4 * ((2 * n_pose + 3) / 4) + 1;
   L.group = n_pose >= 64 ? 1 : 64 / n_pose;
   if (L.group > n_cams) L.group = n_cams;
-  L.Jc = take((P + K) * L.ldc);
-  L.cams = take(n_cams * (pinhole ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE));
-  L.det = take(n_cams * n_pose * 3);
-  L.vm = take(2 * n_cams);
-  L.jr = take(L.group * n_pose * 6);
-  L.ur = take(L.group * 2 * n_pose);
-  L.B = take(LSC_MAXK * PT);
-  L.C = take(LSC_MAXK * LSC_MAXK);
-  L.c = take(LSC_MAXK);
-  s.pos = take(3 * n_pose);
-  s.opv = take(12 * (n_ops > 0 ? n_ops : 1));
-  s.vec = take(6 * SK_MAXP);
-  s.red = take(3 * SK_MAXP);
-  s.pm = take(n_pose);
-  s.opm = take(SK_MAXP);
-  s.cm = take(2 * SK_MAXP);
-  s.axs = take(SK_MAXP / 2);
-  L.gm = take(LSC_MAXK);
-  L.total = take.o;
+  L.l = lsc_layout_around(P, PT, n_pose, n_ops, K, false, [&](SpfTake& t) {
+    L.Jc = t((P + K) * L.ldc);
+    L.cams = t(n_cams * (pinhole ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE));
+    L.det = t(n_cams * n_pose * 3);
+    L.vm = t(2 * n_cams);
+    L.jr = t(L.group * n_pose * 6);
+    L.ur = t(L.group * 2 * n_pose);
+  });
   return L;
 }
 
@@ -88,17 +64,17 @@ template <int PT, bool PINHOLE>
 __global__ void __launch_bounds__(64) k_skel_link_scale_px(LinkScalePxArgs a) {
   constexpr int STRIDE = PINHOLE ? ACINO_PINHOLE_STRIDE : ACINO_CAM_STRIDE;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const SkelDev& D = *a.dev;
+  const LscArgs& q = a.c;
+  const SkelDev& D = *q.dev;
   const PxArgs& b = a.px;
   const int lane = threadIdx.x;
-  const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, C = b.n_cams, K = a.K, R2 = 2 * NPOSE;
+  const int P = D.n_act, NPOSE = D.n_pose, NOPS = D.n_ops, C = b.n_cams, K = q.K, R2 = 2 * NPOSE;
   const LspLayout lay = lsp_layout(P, PT, NPOSE, NOPS, C, K, PINHOLE);
   double* base = reinterpret_cast<double*>(smem_raw);
-  const Spf S = spf_carve(base, lay.s, [](Spf&) {});
+  const Spf S = spf_carve(base, lay.l.s, [](Spf&) {});
   double *Jc = base + lay.Jc, *det = base + lay.det, *jr = base + lay.jr, *ur = base + lay.ur;
-  double *Bm = base + lay.B, *Cm = base + lay.C, *cv = base + lay.c;
+  const LscLds W = lsc_carve(base, lay.l);
   unsigned long long* vm = reinterpret_cast<unsigned long long*>(base + lay.vm);
-  unsigned long long* gm = reinterpret_cast<unsigned long long*>(base + lay.gm);
   double* const recs = base + lay.cams;
   const CamRec<PINHOLE>* cams = reinterpret_cast<const CamRec<PINHOLE>*>(recs);
   const int ldc = lay.ldc, ks2 = (R2 + 3) / 4, group = lay.group;
@@ -107,19 +83,14 @@ __global__ void __launch_bounds__(64) k_skel_link_scale_px(LinkScalePxArgs a) {
 
   // ---- once per workgroup: the masks of pose_fit_skel.hpp, the ops of every group, the camera records, Jc's padding rows
   spf_masks(S, D, P, NPOSE, NOPS, lane);
-  if (lane < LSC_MAXK) {
-    unsigned long long om = 0;
-    for (int k = 0; k < NOPS; ++k)
-      if (a.grp[k] == lane) om |= 1ull << k;
-    gm[lane] = om;
-  }
+  lsc_group_masks(W.gm, q.grp, NOPS, lane);
   for (int e = lane; e < C * STRIDE; e += 64) recs[e] = b.cams[e];
   for (int e = lane; e < (P + K) * ldc; e += 64) Jc[e] = 0.0;
   const int frame_doubles = C * NPOSE * 3;
 
-  for (int64_t n = blockIdx.x; n < a.n_frames; n += gridDim.x) {
+  for (int64_t n = blockIdx.x; n < q.n_frames; n += gridDim.x) {
     __syncthreads();                              // the previous frame is done with the LDS (and the tables are complete)
-    const int st_in = a.status[n];
+    const int st_in = q.status[n];
     bool live = st_in < 2;
     double F = 0.0;
     if (live) {
@@ -138,13 +109,7 @@ __global__ void __launch_bounds__(64) k_skel_link_scale_px(LinkScalePxArgs a) {
           if (lane == 0) vm[2 * c + h] = m;
           (h ? any1 : any0) |= m;
         }
-      bool pin = false;
-      if (lane < P) {
-        S.x[lane] = a.x[n * P + lane];
-        S.m[lane] = lane >= 3 ? a.m[n * P + lane] : 0.0;
-        pin = a.pinned[n * P + lane] != 0;
-      }
-      const unsigned long long fixmask = __ballot(pin);
+      const unsigned long long fixmask = lsc_load_frame(S, q, n, lane);
       __syncthreads();
 
       // ---- FK and F at x: SkelPxFit::eval
@@ -158,33 +123,12 @@ __global__ void __launch_bounds__(64) k_skel_link_scale_px(LinkScalePxArgs a) {
           if (!valid(c, l)) continue;
           part += px_pair_cost(b, cams[c], S.pos + 3 * l, det, t, behind);
         }
-        F = px_cost_finish(part, S.x, S.m, a.kappa, P, lane, b, behind);
+        F = px_cost_finish(part, S.x, S.m, q.kappa, P, lane, b, behind);
       }
 
       // ---- the raw directions: G, then d_gl as the columns P .. P + K - 1 of S.Jw
       spf_jacobian<true>(S, lane);
-      {
-        const int here = spf_here(lane);
-        for (int t = here; t < K * NPOSE; t += 64) {
-          const int g = t / NPOSE, l = t - g * NPOSE;
-          double j0 = 0.0, j1 = 0.0, j2 = 0.0;
-          unsigned long long mk = gm[g] & S.pm[l];
-          if (!(((l < 64 ? any0 : any1) >> (l & 63)) & 1ull)) mk = 0;
-          while (mk) {
-            const int k = __ffsll((long long)mk) - 1;
-            mk &= mk - 1;
-            const double* dv = S.opv + k * 12;
-            j0 += dv[0];
-            j1 += dv[1];
-            j2 += dv[2];
-          }
-          double* o = S.Jw + (P + g) * S.ldj + 3 * l;
-          o[0] = j0;
-          o[1] = j1;
-          o[2] = j2;
-        }
-        __syncthreads();
-      }
+      lsc_scale_jacobian<true>(S, W.gm, K, any0, any1, lane);
 
       // ---- A, B, C in one Gram product carried across the cameras; g and c beside it
       {
@@ -243,38 +187,26 @@ __global__ void __launch_bounds__(64) k_skel_link_scale_px(LinkScalePxArgs a) {
                                    more = advance();
                                    return more;
                                  },
-                                 [&](int row, int col, double v) {
-                                   if (row < P) {
-                                     S.M[row * (PT + 1) + col] = v;
-                                   } else if (row < P + K) {
-                                     const int g = row - P;
-                                     if (col < P) {
-                                       Bm[g * PT + col] = v;
-                                     } else {
-                                       Cm[g * LSC_MAXK + col - P] = v;
-                                       Cm[(col - P) * LSC_MAXK + g] = v;
-                                     }
-                                   }
-                                 });
+                                 lsc_gram_store<PT>(S, K, W));
         for (int t = here; t < P + K; t += 64) {
           const double sum = t < 64 ? gs0 : gs1;
           if (t < P)
             S.g[t] = sum;
           else
-            cv[t - P] = sum;
+            W.cv[t - P] = sum;
         }
         __syncthreads();
         if (here >= 3 && here < P) {
-          S.M[here * (PT + 1) + here] += a.kappa;
-          S.g[here] += a.kappa * (S.x[here] - S.m[here]);
+          S.M[here * (PT + 1) + here] += q.kappa;
+          S.g[here] += q.kappa * (S.x[here] - S.m[here]);
         }
         __syncthreads();
       }
 
       // ---- the pose eliminated: S_n, r_n, sens_n
-      live = lsc_eliminate<PT>(S, D, fixmask, F, K, Bm, Cm, cv, a.out.sens ? a.out.sens + n * P * K : nullptr, lane);
+      live = lsc_eliminate<PT>(S, D, fixmask, F, K, W.Bm, W.Cm, W.cv, q.out.sens ? q.out.sens + n * P * K : nullptr, lane);
     }
-    lsc_store(a.out, n, P, K, live, st_in, F, Cm, cv, lane);
+    lsc_store(q.out, n, P, K, live, st_in, F, W.Cm, W.cv, lane);
   }
 }
 
@@ -297,35 +229,27 @@ int acino_skel_link_scale_px(const acino_pose_fit_px_params* prm, const acino_sk
   auto check_fit = [&]() -> int {
     if (int rc = px_check_params(prm, n_frames, n_cams, p->n_pose, "min_detections must be 1..n_pose n_cams", fit)) return rc;
     ACINO_REQUIRE(n_groups >= 1 && n_groups <= LSC_MAXK, "n_groups must be 1..16");
-    ACINO_REQUIRE(h_group != nullptr, "null buffer (h_group)");
-    for (int k = 0; k < p->n_ops; ++k)
-      ACINO_REQUIRE(h_group[k] >= -1 && h_group[k] < n_groups, "h_group: every op's group must be -1 (fixed) or 0..n_groups-1");
-    return ACINO_OK;
+    return lsc_check_groups(p, h_group, n_groups);
   };
   if (int rc = spf_program(p, h_ops, h_active, h, check_fit)) return rc;
   const bool pinhole = prm->camera_model == 1;
-  const size_t lds = sizeof(double) * (size_t)lsp_layout(h.n_act, h.PT, h.n_pose, h.n_ops, n_cams, n_groups, pinhole).total;
+  const size_t lds = sizeof(double) * (size_t)lsp_layout(h.n_act, h.PT, h.n_pose, h.n_ops, n_cams, n_groups, pinhole).l.total;
   ACINO_REQUIRE(lds <= SPF_LDS_MAX, "n_active x n_pose x n_cams does not fit the pixel pose fit's 160 KB of LDS");
   if (n_frames == 0) return ACINO_OK;
   ACINO_REQUIRE(d_det && d_cams && d_x && d_m && d_pinned && d_status && d_S && d_r && d_F && d_used && d_frame_status && d_ws,
                 "null buffer (d_det, d_cams, d_x, d_m, d_pinned, d_status, d_S, d_r, d_F, d_used, d_frame_status, d_ws)");
   hipStream_t s = (hipStream_t)stream;
   LinkScalePxArgs a;
-  if (int rc = spf_upload(h, p, d_ws, ws_bytes, "acino_skel_link_scale_px_workspace_bytes", s, a.dev)) return rc;
+  if (int rc = spf_upload(h, p, d_ws, ws_bytes, "acino_skel_link_scale_px_workspace_bytes", s, a.c.dev)) return rc;
   px_fill_args(a.px, prm, d_det, d_cams, n_cams, nullptr, nullptr);
-  a.x = d_x, a.m = d_m, a.pinned = d_pinned, a.status = d_status, a.n_frames = n_frames;
-  a.out.S = d_S, a.out.r = d_r, a.out.F = d_F, a.out.sens = d_sens, a.out.used = d_used, a.out.frame_status = d_frame_status;
-  a.kappa = 1.0 / (prm->prior_sigma * prm->prior_sigma), a.K = n_groups;
-  for (int k = 0; k < ACINO_SKEL_MAX_OPS; ++k) a.grp[k] = (int8_t)(k < h.n_ops ? h_group[k] : -1);
-  if (int rc = skel_dispatch_pt(h.PT, [&](auto pt) -> int {
-        constexpr int T = decltype(pt)::value;
-        static PerDeviceOnce attr_pinhole, attr_fisheye;      // (per PT: one pair per instantiation of this body)
-        return pinhole ? spf_launch(k_skel_link_scale_px<T, true>, attr_pinhole, n_frames, lds, s, a)
-                       : spf_launch(k_skel_link_scale_px<T, false>, attr_fisheye, n_frames, lds, s, a);
-      }))
-    return rc;
-  if (d_total) return lsc_launch_total(d_S, d_r, d_F, d_used, n_frames, n_groups, d_total, s);
-  return ACINO_OK;
+  lsc_fill_args(a.c, h, h_group, n_groups, prm->prior_sigma, d_x, d_m, d_pinned, d_status, n_frames, d_S, d_r, d_F, d_used,
+                d_frame_status, d_sens);
+  return lsc_finish(h.PT, a.c, d_total, s, [&](auto pt) -> int {
+    constexpr int T = decltype(pt)::value;
+    static PerDeviceOnce attr_pinhole, attr_fisheye;          // (per PT: one pair per instantiation of this body)
+    return pinhole ? spf_launch(k_skel_link_scale_px<T, true>, attr_pinhole, n_frames, lds, s, a)
+                   : spf_launch(k_skel_link_scale_px<T, false>, attr_fisheye, n_frames, lds, s, a);
+  });
 }
 
 }  // extern "C"

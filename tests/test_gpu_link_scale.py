@@ -121,6 +121,65 @@ def test_totals_are_the_in_order_sums(gpu_lib, name):
     assert np.array_equal(got["S"], got["S"].T)
 
 
+def test_sixteen_groups_on_51_states(gpu_lib):
+    """p51 with the op index mod 16 as groups: K = 16, P + K = 67 > 64, so the columns 64 .. 66 of [Jw Js] - c of the groups 13,
+    14 and 15 - are summed by the lanes 0 .. 2 in a second round.  A kernel that sums one column per lane leaves those three
+    entries of c as the LDS held them and r_n of these groups off by the whole of c."""
+    inp = pref.inputs("p51")
+    grp, K = lref.groups_of(inp["skel"], np.arange(len(lref.base_offsets(inp["skel"]))) % 16)
+    scales = np.exp(0.1 * np.cos(1.0 + 2.0 * np.arange(K)))
+    prob = lref.ScaledProblem(inp["skel"], inp["points"], inp["cov"], inp["lo"], inp["hi"], groups=grp, scales=scales, **pref.FIT)
+    assert K == 16 and prob.P + K == 67 and prob.N == 24
+    mdl = build.scale_links(model("p51"), scales, grp)
+    fit = build.pose_fit(mdl, inp["points"], inp["cov"], x0=prob.x0, return_cov=False, **pref.FIT)
+    got = build.link_scale_system(mdl, inp["points"], inp["cov"], fit, grp, prior_sigma=pref.FIT["prior_sigma"], m=prob.x0)
+    r64, r80 = [lref.system(prob, fit["x"], fit["pinned"], fit["status"], dt) for dt in (np.float64, np.longdouble)]
+    used = got["used"]
+    assert np.array_equal(used, r64["used"]) and used.sum() == 23
+    worst = {}
+    for key, mag in (("S_frames", "mag_S"), ("r_frames", "mag_r"), ("sens", "mag_sens")):
+        err = np.abs(got[key][used].astype(np.longdouble) - r80[key][used])
+        bar = np.maximum(np.abs(r64[key][used].astype(np.longdouble) - r80[key][used]), EPS * r80[mag][used])
+        worst[key] = float(np.where(err == 0, 0.0, err / np.where(bar > 0, bar, 1e-300)).astype(np.float64).max())
+    print("p51, 16 groups: error / bar (allowed 256) " + ", ".join(f"{k} {v:.1f}" for k, v in worst.items()) +
+          f"; |r| of the groups 13 .. 15 max {float(np.abs(got['r_frames'][:, 13:]).max()):.2e}")
+    assert np.abs(r80["r_frames"][:, 13:]).max() > 1.0          # (what the three entries carry is far from 0)
+    assert max(worst.values()) <= 256.0, worst
+    rr = np.zeros(K)
+    for n in range(prob.N):
+        rr = rr + got["r_frames"][n]
+    assert np.array_equal(got["r"], rr)
+
+
+def test_without_sens_and_total_the_frames_get_the_same_bits(gpu_lib):
+    """acino_skel_link_scale with d_sens = NULL and d_total = NULL: S, r, F, used and frame_status as the full call writes them."""
+    import ctypes as C
+
+    import torch
+    from acinoset_amd._lib import check, lib, ptr, stream_ptr
+    r, inp = run("pt16", "off"), pref.inputs("pt16")
+    grp, K = groups("pt16")
+    mdl = build.scale_links(model("pt16"), np.exp(0.1 * np.cos(1.0 + 2.0 * np.arange(K))), grp)
+    act = np.asarray(mdl.active, dtype=np.int32)
+    N, dev = r["prob"].N, calib._dev()
+    assert N == 24
+    p = build._skel_params(mdl, len(act))
+    nbytes = lib().acino_skel_link_scale_workspace_bytes(C.byref(p))
+    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)      # noqa: E731
+    u8 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.uint8), device=dev)         # noqa: E731
+    ins = [f64(inp["points"]), f64(inp["cov"]), f64(r["fit"]["x"]), f64(r["prob"].x0), u8(r["fit"]["pinned"]), u8(r["fit"]["status"])]
+    outs = [torch.full(shape, 7, dtype=dt, device=dev) for shape, dt in (((N, K, K), torch.float64), ((N, K), torch.float64),
+                                                                         ((N,), torch.float64), ((N,), torch.uint8), ((N,), torch.uint8))]
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    check(lib().acino_skel_link_scale(C.byref(p), build._ops_array(mdl.prog), (C.c_int32 * len(act))(*[int(a) for a in act]),
+                                      (C.c_int32 * len(grp))(*[int(g) for g in grp]), K, pref.FIT["prior_sigma"], 0.01,
+                                      *[ptr(t) for t in ins], N, *[ptr(t) for t in outs], None, None,
+                                      C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
+    torch.cuda.synchronize()
+    for t, key in zip(outs, ("S_frames", "r_frames", "cost_frames", "used", "status")):
+        assert np.array_equal(t.cpu().numpy().astype(r["got"][key].dtype), r["got"][key]), key
+
+
 @functools.lru_cache(maxsize=None)
 def fitted(drop_slot=None):
     sc, inp = lref.scaled_inputs("pt16"), pref.inputs("pt16")

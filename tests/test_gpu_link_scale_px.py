@@ -120,6 +120,39 @@ def test_totals_are_the_in_order_sums_and_two_calls_give_the_same_bits(gpu_lib, 
     assert got["cost"] == again["cost"]
 
 
+def test_without_sens_and_total_the_frames_get_the_same_bits(gpu_lib):
+    """acino_skel_link_scale_px with d_sens = NULL and d_total = NULL: S, r, F, used and frame_status as the full call writes them."""
+    import ctypes as C
+
+    import torch
+    from acinoset_amd import _lib, calib
+    from acinoset_amd._lib import check, lib, ptr, stream_ptr
+    r = run("pt16-two", "off")
+    mdl, grp, K, fit = r["mdl"], r["grp"], r["K"], r["fit"]
+    act = np.asarray(mdl.active, dtype=np.int32)
+    N, Cn, dev = r["prob"].N, int(np.shape(mdl.meas)[1]), calib._dev()
+    assert N == 24
+    p = build._skel_params(mdl, len(act))
+    nbytes = lib().acino_skel_link_scale_px_workspace_bytes(C.byref(p))
+    camera_model = getattr(mdl, "camera_model", "fisheye")
+    prm = _lib.PoseFitPxParams(calib.CAMERAS[camera_model].code, 1, 1, 0, 1e-3, 1e-10, 1e-10, ppx.OPTS["prior_sigma"], 0.5, 5.0,
+                               build._model_sigma_px(mdl))      # (the defaults of link_scale_system_pixels: what run() passed)
+    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)      # noqa: E731
+    u8 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.uint8), device=dev)         # noqa: E731
+    det, cams = f64(build._model_detections(mdl)), f64(calib.camera_records(camera_model, mdl.K, mdl.D, mdl.R, mdl.t))
+    ins = [f64(fit["x"]), f64(r["prob"].x0), u8(fit["pinned"]), u8(fit["status"])]
+    outs = [torch.full(shape, 7, dtype=dt, device=dev) for shape, dt in (((N, K, K), torch.float64), ((N, K), torch.float64),
+                                                                         ((N,), torch.float64), ((N,), torch.uint8), ((N,), torch.uint8))]
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    check(lib().acino_skel_link_scale_px(C.byref(prm), C.byref(p), build._ops_array(mdl.prog), (C.c_int32 * len(act))(*[int(a) for a in act]),
+                                         (C.c_int32 * len(grp))(*[int(g) for g in grp]), K, ptr(det), N, Cn, ptr(cams),
+                                         *[ptr(t) for t in ins], *[ptr(t) for t in outs], None, None,
+                                         C.c_void_p((ws.data_ptr() + 255) // 256 * 256), nbytes, stream_ptr()))
+    torch.cuda.synchronize()
+    for t, key in zip(outs, ("S_frames", "r_frames", "cost_frames", "used", "status")):
+        assert np.array_equal(t.cpu().numpy().astype(r["got"][key].dtype), r["got"][key]), key
+
+
 def test_mono_identity(gpu_lib):
     """One camera, one scale for every link (test_link_scale_px_host.py): S_n = 0, sens_n[:3, 0] = root - camera centre,
     sens_n[3:, 0] = 0 on the frames with a free root, within the bars of the per-frame outputs."""
