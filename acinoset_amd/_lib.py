@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libacinoset_hip.so")
 BUILD_ID_SOURCE = "camera_kernels.hip"      # defines acino_build_id()
-SOURCES = ["camera_kernels.hip", "triangulate_mv.hip", "pose_fit.hip", "pose_fit_px.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_calib.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "ekf_cov.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_calib.hip", "skel_links.hip", "skel_reproj.hip", "skel_pose_fit.hip", "skel_pose_fit_px.hip", "skel_link_scale.hip", "skel_link_scale_px.hip"]
+SOURCES = ["camera_kernels.hip", "triangulate_mv.hip", "pose_fit.hip", "pose_fit_px.hip", "fte_assemble.hip", "bcr.hip", "seplevel.hip", "chunk.hip", "fte_cov.hip", "fte_calib.hip", "fte_reproj.hip", "fte_api.hip", "sba.hip", "sba_cov.hip", "ekf.hip", "ekf_cov.hip", "skel_fte.hip", "skel_cov.hip", "skel_cov_rates.hip", "skel_sample.hip", "skel_calib.hip", "skel_links.hip", "skel_link_fit.hip", "skel_reproj.hip", "skel_pose_fit.hip", "skel_pose_fit_px.hip", "skel_link_scale.hip", "skel_link_scale_px.hip"]
 HEADERS = ["common.hpp", "fte_kernels.hpp", "bcr.hpp", "bcr_dev.hpp", "seplevel.hpp", "chunk.hpp", "fte_cov.hpp", "fte_cov_dev.hpp", "fte_calib.hpp", "fte_reproj.hpp", "trio80.hpp", "dense80.hpp", "cheetah_fk.hpp",
            "pinhole.hpp", "ldl3.hpp", "pose_fit_dev.hpp", "pose_fit_cheetah.hpp", "pose_fit_px_dev.hpp", "pose_fit_skel.hpp", "link_scale_dev.hpp", "ekf_dev.hpp", "sba_dev.hpp", "sba_host.hpp", "skel_dev.hpp", "skel_host.hpp", "skel_factor.hpp", "skel_sens_dev.hpp", "skel_assemble.hpp",
            os.path.join("..", "..", "include", "acinoset_hip.h")]
@@ -266,6 +266,10 @@ SIGNATURES = {
     "acino_skel_fte_link_sensitivity": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P,
                                              _P, _P, C.POINTER(C.c_int32), _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P,
                                              _Z, _P, _I, _P]),
+    "acino_skel_fte_link_fit_workspace_bytes": (_Z, [C.POINTER(SkelFteParams), _I, _I]),
+    "acino_skel_fte_link_fit_system": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P,
+                                            _P, _P, C.POINTER(C.c_int32), _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P,
+                                            _Z, _P, _I, _P]),
     "acino_skel_fte_reprojection": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P, _P,
                                          _P, _D, _P, _P, _P, _P, _P, _P]),
     "acino_skel_fte_reprojection_weights": (_I, [C.POINTER(SkelFteParams), _I, _I, C.POINTER(SkelOp), C.POINTER(C.c_int32), _P, _P, _P,

@@ -707,7 +707,9 @@ def model_link_sensitivity(models, xs, groups="links", cov_links=None, l1_eps=1e
 
     The total is ``cov + cov_links`` (``std_pos_total = sqrt(std_pos^2 + std_pos_links^2)``) ONLY for a length covariance that came
     from other data than the clips being solved, or for an honest prior; lengths fitted to the same clip have errors correlated
-    with the trajectory's and the sum is not valid.  The term is perfectly correlated across frames: smoothing does not average
+    with the trajectory's and the sum is not valid - except for the dict of ``fit_link_scales_fte`` on these clips: its
+    ``cov_log_scales`` is the Schur complement of the joint posterior over (trajectory, log-scales), and with it the sums ARE that
+    posterior's marginals, the correlation included.  The term is perfectly correlated across frames: smoothing does not average
     it out."""
     return _links(models, xs, groups, cov_links, l1_eps, pin_unobserved)
 
@@ -735,6 +737,55 @@ def _check_links(models, cov_links, groups):
         _refuse_robust(models, "link sensitivity (cov_links)")
         _link_inputs(models[0], groups, cov_links)
     return True
+
+
+def link_fit_system(models, xs, groups="links", l1_eps=1e-2, pin_unobserved=False, return_sens=False):
+    """The reduced system of the links' log-scales with the FTE trajectory eliminated, at the iterates ``xs`` (one [N, P] array per
+    model, the layout of ``results["x"]``): acino_skel_fte_link_fit_system, all models in ONE batched call.  theta, ``groups``, A
+    and G are those of ``model_link_sensitivity``; C = sum w^2 J_theta^T J_theta is the theta-theta block under the same Fisher
+    weights and [[A, G], [G^T, C]] the information of the joint posterior over (trajectory, log-scales).  Returns one dict per
+    model: ``S`` [K, K] = C - G^T A^-1 G, the information of theta with the trajectory eliminated; ``r`` [K] = c - G^T A^-1 g_x,
+    the gradient of min_x F(x, theta) to first order (g_x: the solver's gradient at x, so r is right also where the solve
+    stopped short of a stationary point); ``C``; ``c`` [K] = dF/dtheta at fixed x; ``cost`` = F(x, 0), the solver's own objective;
+    ``status`` (0, or 5: singular clip, NaN arrays; for ONE model a RuntimeError, as ``model_covariance``) and ``groups`` [n_ops].
+    S and C are symmetric to the bit; a group on no weighted slot's path has exact zeros.  Clips that share theta add their S and
+    r.  ``return_sens``: ``sens_links`` [N, P, K] - the bits of ``model_link_sensitivity`` - and ``newton`` [N, P] = -A^-1 g_x, the
+    Fisher-scoring step of the trajectory, both in the full-state layout.  ``pin_unobserved`` as ``model_covariance``; every dict
+    then carries ``unobserved``.  Refused for models of the redescending loss."""
+    return _link_fit_system(models, xs, groups, l1_eps, pin_unobserved, return_sens)
+
+
+def _link_fit_system(models, xs, groups, l1_eps, pin_unobserved, return_sens, raise_numeric=True):
+    """link_fit_system.  ``raise_numeric=False``: a singular single clip is reported in its ``status`` like a clip of a batch."""
+    if len(models) == 0:
+        raise ValueError("no models")
+    _refuse_robust(models, "link fit (link_fit_system)")
+    grp, K, _sigma, _unknown = _link_inputs(models[0], groups, None)
+    grp_c = (C.c_int32 * max(len(grp), 1))(*[int(g) for g in grp])
+    pin = bool(pin_unobserved)
+    io_ = _skel_inputs(models, xs, lambda p, B: lib().acino_skel_fte_link_fit_workspace_bytes(C.byref(p), B, int(pin)), l1_eps=l1_eps)
+    m0, act, dev = models[0], io_["act"], io_["dev"]
+    B, N, P, Pa = len(models), m0.N, m0.P, len(act)
+    empty = lambda *shape: torch.empty((B,) + shape, dtype=torch.float64, device=dev)   # noqa: E731
+    arrays = dict(S=empty(K, K), r=empty(K), C=empty(K, K), c=empty(K), cost=empty())
+    sens, newton = (empty(N, Pa, K), empty(N, Pa)) if return_sens else (None, None)
+    status = (C.c_int32 * B)()
+    mask = torch.zeros((B, Pa), dtype=torch.uint8, device=dev) if pin else None
+    rc = lib().acino_skel_fte_link_fit_system(*io_["head"], grp_c, K, *[ptr(a) for a in arrays.values()], ptr(sens), ptr(newton), status,
+                                              *io_["tail"], int(pin), ptr(mask))
+    if raise_numeric or rc != -6:                  # (ACINO_ERR_NUMERIC: one clip, singular - its status word and NaN arrays are set)
+        check(rc)
+    host = {k: a.cpu().numpy() for k, a in arrays.items()}
+    out = [dict({k: (float(h[i]) if k == "cost" else h[i]) for k, h in host.items()}, status=int(status[i]), groups=grp.copy())
+           for i in range(B)]
+    if return_sens:
+        sh, nh = sens.cpu().numpy(), newton.cpu().numpy()
+        for i, o in enumerate(out):
+            o["sens_links"], o["newton"] = _full_state(sh[i], act, P), _full_state(nh[i], act, P)
+    if pin:
+        for o, un in zip(out, _unobserved_lists(mask, act)):
+            o["unobserved"] = un
+    return out
 
 
 def _total_std(res):
@@ -1324,6 +1375,95 @@ def fit_link_scales_pixels(model, groups="links", x0=None, det=None, thresh=0.5,
         return mdl, fit, link_scale_system_pixels(mdl, fit, grp, m=m, **px)
 
     return _fit_link_scales(evaluate, grp, K, scale_prior_sigma, max_outer, tol)
+
+
+def fit_link_scales_fte(models, groups="links", x0=None, scale_prior_sigma=None, max_outer=30, tol=1e-6, pin_unobserved=False,
+                        **solve_kw):
+    """The link lengths of a skeleton fitted JOINTLY with the FTE trajectory: one scale s_g = exp(theta_g) per group of links
+    (``groups`` as ``link_groups``), the minimiser over theta of sum_b min_x F_b(x, theta) - F_b the objective ``solve_models``
+    minimises on clip b, data term and smoothness prior - plus theta^2 / (2 ``scale_prior_sigma``^2) per group when given.
+    ``models``: one ``SkeletonModel`` or a list of clips of the same skeleton, cameras and length, e.g. the windows of a video: the
+    lengths belong to the animal, so all clips share one theta and their reduced systems add.  ``x0``: None or one [N, P] start
+    per clip (a single array for a single model); ``solve_kw`` goes to ``solve_models`` (``max_iter``, ``ftol``, ``l1_eps``, ...).
+
+    The outer loop is that of ``fit_link_scales``.  Every evaluation at a theta is ``scale_links`` on every model, ONE
+    ``solve_models`` over all clips - started from the iterates of the accepted evaluation moved by ``sens_links`` dtheta and
+    clipped to the box; ``x0`` the first time - and ONE ``link_fit_system`` at the solutions: S = sum_b S_b and r = sum_b r_b over
+    the clips whose solve and system both succeeded.  The Fisher-scoring step ``newton`` is NOT added to the start: at the end
+    point of an L1 solve the gradient does not vanish (the signs of the residuals near zero keep flipping), and -A^-1 g_x
+    amplifies it along the directions two cameras see worst - measured on the 12-frame test windows: steps of 8 to 700 m or rad,
+    a start whose cost is 3e8 against 4e3, and solves that end in a worse local minimum at better scales.  A step is accepted when the cost summed over the clips both
+    points use falls.  A group with a zero diagonal entry of S stays at 1 with ``observed`` False and ``std`` inf.  One camera does
+    not determine the size of the skeleton: a model of one camera raises ValueError unless ``scale_prior_sigma`` is given.
+    ``pin_unobserved`` goes to ``link_fit_system``.  Refused for models of the redescending loss.
+
+    Returns the dict of ``fit_link_scales`` with ``models`` (the scaled copies) and ``results`` (the ``[(results, info), ...]`` of
+    the solve at the end point) in the place of ``model`` and ``fit``; ``system`` carries S, r, ``cost_frames`` (the clips' costs),
+    ``used``, ``n_used`` and ``clips`` (the dicts of ``link_fit_system``); ``joint`` is True.
+
+    ``cov_log_scales`` = S^-1 is the marginal covariance of theta under the joint posterior over (trajectories, log-scales), whose
+    information is [[A, G], [G^T, C]] per clip.  By the block inverse, cov(x) = A^-1 + S_x Sigma S_x^T and
+    cov(pos_l) = G_l A^-1 G_l^T + T_l Sigma T_l^T with S_x = -A^-1 G and T_l = G_l S_x + D_l: the sums ``cov_x + cov_x_links``,
+    ``cov_pos + cov_pos_links`` and ``std_pos_total`` that ``solve_models(result["models"], ..., return_cov=True,
+    cov_links=result)`` returns ARE the marginals of that joint posterior, the correlation between the lengths' errors and the
+    trajectory's included.  This is the valid total for lengths fitted on the same clips."""
+    single = isinstance(models, SkeletonModel)
+    models = [models] if single else list(models)
+    if len(models) == 0:
+        raise ValueError("no models")
+    if x0 is not None:
+        x0 = [x0] if single else list(x0)
+    grp, K = link_groups(models[0].prog, groups)
+    _check_outer(scale_prior_sigma, max_outer, tol)
+    _refuse_robust(models, "link fit (fit_link_scales_fte)")
+    if int(np.shape(models[0].meas)[1]) == 1 and scale_prior_sigma is None:
+        raise ValueError("one camera does not determine the size of the skeleton (a larger animal further away gives the same "
+                         "pixels): pass scale_prior_sigma")
+    prec = 0.0 if scale_prior_sigma is None else 1.0 / float(scale_prior_sigma) ** 2
+    l1_eps = solve_kw.get("l1_eps", 1e-2)
+    seen = []                                                  # the evaluations so far that can still be the accepted one: at most two
+
+    def total(ev, both):
+        return float(np.add.reduce(ev["cost"][both])) + 0.5 * prec * float(ev["theta"] @ ev["theta"])
+
+    def base():
+        """The accepted evaluation by the loop's own rule: the later of two wins when its cost on the clips both use is lower."""
+        if len(seen) == 2:
+            both = seen[0]["used"] & seen[1]["used"]
+            if both.any() and total(seen[1], both) < total(seen[0], both):
+                del seen[0]
+            else:
+                del seen[1]
+        return seen[0]
+
+    def evaluate(theta):
+        mdls = [scale_links(m, np.exp(theta), grp) for m in models]
+        start = x0
+        if seen:
+            b0 = base()
+            start = []
+            for m, xb, sb in zip(mdls, b0["xs"], b0["clips"]):
+                act = np.asarray(m.active, dtype=np.int64)
+                x = xb.copy()
+                if sb["status"] == 0:
+                    x = x + sb["sens_links"] @ (theta - b0["theta"])
+                x[:, act] = np.clip(x[:, act], m.lo[:, act], m.hi[:, act])
+                start.append(x)
+        out = solve_models(mdls, start, **solve_kw)
+        xs = [r["x"] for r, _i in out]
+        clips = _link_fit_system(mdls, xs, grp, l1_eps, pin_unobserved, True, raise_numeric=False)      # (with sens_links)
+        used = np.array([s["status"] == 0 and i["status_name"] != "numeric" for s, (_r, i) in zip(clips, out)], dtype=bool)
+        S, r = np.zeros((K, K)), np.zeros(K)
+        for s, u in zip(clips, used):                          # the clips in their order
+            if u:
+                S, r = S + s["S"], r + s["r"]
+        cost = np.array([s["cost"] for s in clips])
+        seen.append(dict(theta=np.array(theta, copy=True), xs=xs, clips=clips, used=used, cost=cost))
+        return mdls, out, dict(S=S, r=r, cost_frames=cost, used=used, n_used=int(used.sum()), clips=clips)
+
+    fit = _fit_link_scales(evaluate, grp, K, scale_prior_sigma, max_outer, tol)
+    fit["models"], fit["results"], fit["joint"] = fit.pop("model"), fit.pop("fit"), True
+    return fit
 
 
 def pose_fit_pixels(model, x0=None, det=None, thresh=0.5, f_scale=5.0, sigma_px=None, prior_sigma=np.pi, min_detections=2,

@@ -212,6 +212,7 @@ struct SkelSens {                  // what the pipeline hands to an entry's two 
   const double* d_opv;
   const unsigned char *d_fxm, *d_unobs;      // d_unobs: the clips' masks when the unobserved states are pinned, else NULL
   double* d_cols;                  // the right-hand side -G out of rhs, S into combine
+  const double* d_y;               // L^-1 of the right-hand side, for a combine that reduces over it (skel_link_fit.hip)
 };
 // An entry behind its own argument checks: the workspace check (query: the entry's ..._workspace_bytes; ws_cols: the columns
 // its buffers are sized for), skel_cov_launch_build, rhs(SkelSens) -> factor -> L^-1 -> L^-T on n_cols columns -> combine(SkelSens),
@@ -240,7 +241,7 @@ inline int skel_sens_run(const acino_skel_fte_params* p, int n_clips, int camera
   SkelClip* d_clip = reinterpret_cast<SkelClip*>(base + lay.clip);
   const unsigned char* d_fxm = reinterpret_cast<const unsigned char*>(base + lay.fxm);
   double *d_b = D(lay.total), *d_y = D(lay.total + col_bytes);      // -G, then S; L^-1 (-G)
-  const SkelSens a = {NT, s, d_dev, d_clip, D(lay.opv), d_fxm, pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr, d_b};
+  const SkelSens a = {NT, s, d_dev, d_clip, D(lay.opv), d_fxm, pin ? reinterpret_cast<const unsigned char*>(base + lay.unobs) : nullptr, d_b, d_y};
   if (once.first())
     for (const void* k : kernels) ACINO_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   rhs(a);

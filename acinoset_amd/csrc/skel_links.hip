@@ -43,13 +43,6 @@
 
 namespace acino {
 
-constexpr int SKL_MAXK = 16;       // groups of links: MAX_LINK_GROUPS of build.py, LSC_MAXK of skel_link_scale.hip
-
-struct SkelLinkGroups {            // by value to both kernels
-  unsigned long long gm[SKL_MAXK]; // per group: its ops
-  int32_t K, pad;
-};
-
 constexpr size_t skel_links_rhs_doubles(size_t n_ops, size_t n_pose, size_t P, size_t K) {
   return n_ops * 12 + n_pose * 3 + n_pose * 3 * P + n_pose * 3 * K + n_pose * 9;
 }
@@ -59,16 +52,6 @@ constexpr size_t skel_links_combine_doubles(size_t n_ops, size_t P, size_t K) {
 static_assert(sizeof(double) * skel_links_rhs_doubles(ACINO_SKEL_MAX_OPS, ACINO_SKEL_MAX_OPS + 1, SK_MAXP, SKL_MAXK) <= 160 * 1024 &&
                   sizeof(double) * skel_links_combine_doubles(ACINO_SKEL_MAX_OPS, SK_MAXP, SKL_MAXK) <= 160 * 1024,
               "LDS of k_skel_links_rhs / k_skel_links_combine at the limits");
-
-// D_l[i, g]: coordinate i of the sum of the rotated link vectors of group g's ops on slot l's path, in program order
-__device__ __forceinline__ double skel_link_direct(const SkelDev& D, const SkelLinkGroups& grp, const double* __restrict__ opv, int l,
-                                                   int i, int g) {
-  const unsigned long long ops = D.pmask[l] & grp.gm[g];
-  double acc = 0.0;
-  for (int k = 0; k < D.n_ops; ++k)
-    if ((ops >> k) & 1ull) acc += opv[k * 12 + i];
-  return acc;
-}
 
 template <bool PINHOLE>
 __global__ void __launch_bounds__(256)

@@ -53,6 +53,24 @@ __device__ __forceinline__ void skel_sens_rhs_out(const SkelDev& D, int n, int c
   }
 }
 
+// ---- the links' groups (skel_links.hip: the sensitivity to the link lengths; skel_link_fit.hip: the joint fit's system) -------
+constexpr int SKL_MAXK = 16;       // groups of links: MAX_LINK_GROUPS of build.py, LSC_MAXK of skel_link_scale.hip
+
+struct SkelLinkGroups {            // by value to the kernels
+  unsigned long long gm[SKL_MAXK]; // per group: its ops
+  int32_t K, pad;
+};
+
+// D_l[i, g]: coordinate i of the sum of the rotated link vectors of group g's ops on slot l's path, in program order
+__device__ __forceinline__ double skel_link_direct(const SkelDev& D, const SkelLinkGroups& grp, const double* __restrict__ opv, int l,
+                                                   int i, int g) {
+  const unsigned long long ops = D.pmask[l] & grp.gm[g];
+  double acc = 0.0;
+  for (int k = 0; k < D.n_ops; ++k)
+    if ((ops >> k) & 1ull) acc += opv[k * 12 + i];
+  return acc;
+}
+
 // ---- a combine kernel, one workgroup per frame ----------------------------------------------------------------------
 // A singular clip: NaN in every output of frame n that is there (dpos [n_pose][3][cols]: the links' alone)
 __device__ __forceinline__ void skel_sens_nan(const SkelDev& D, int n, int cols, double* __restrict__ sens, double* __restrict__ dpos,

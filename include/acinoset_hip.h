@@ -995,6 +995,39 @@ int acino_skel_fte_link_sensitivity(const acino_skel_fte_params* p, int n_clips,
                                     int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes, void* stream,
                                     int pin_unobserved, uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
 
+/* ---- the link lengths fitted JOINTLY with the generic-skeleton FTE trajectory: the reduced system of the log-scales -----------
+ * acino_skel_fte_link_fit_system: theta, h_group, n_groups, A, G, D_l, the kept rows, the pins, pin_unobserved, the status rules,
+ * the limits and the leading arguments are those of acino_skel_fte_link_sensitivity above.  With e = w (uv - meas),
+ * J_theta = J_pi D_l and F(x, theta) the solver's own objective of a clip (data term plus smoothness), per clip at d_x:
+ *   d_cost   [n_clips]         F(x, 0), the value the solve reports
+ *   d_c      [n_clips][K]      dF/dtheta at fixed x = sum w sign(e) J_theta (the solver's gradient convention gu = w sign(eu))
+ *   d_C      [n_clips][K][K]   sum w^2 J_theta^T J_theta, symmetric to the bit
+ *   d_S      [n_clips][K][K]   C - G^T A^-1 G = C - Y^T Y, Y = L^-1 G (rows of pinned variables 0), symmetric to the bit
+ *   d_r      [n_clips][K]      c - G^T A^-1 g_x, g_x the solver's gradient of F in the active states at x, 0 at pinned rows: the
+ *                              Schur right-hand side of the quadratic model, correct to first order where x is not stationary
+ *   d_sens   [n_clips][N][n_active][K]   (may be NULL) -A^-1 G: the bits of d_sens of acino_skel_fte_link_sensitivity
+ *   d_newton [n_clips][N][n_active]      (may be NULL) -A^-1 g_x, the Fisher-scoring step of the trajectory
+ * [[A, G], [G^T, C]] is the information of the joint posterior over (trajectory, log-scales): S is the information of theta with
+ * the trajectory eliminated, and with Sigma = (sum over the clips that share theta of S)^-1 as d_cov_links the sums
+ * cov + cov_links of the sensitivity entry ARE the marginals of the joint posterior (A^-1 + S_x Sigma S_x^T, S_x = -A^-1 G).
+ * Clips that share theta add their S and r.  A group on no weighted slot's path has exact zeros in its row, column and entries.
+ * The first five outputs are required.  A singular clip gets status 5 and NaN in every output; in a batch with h_status the
+ * other clips stand.  No atomics, every sum in a fixed order: the result of one clip is the same bits whatever else shares the
+ * call, and a second call repeats the first.
+ * Every argument is checked before any device call, with the sensitivity entry's texts (n_groups in 1..16, h_group, the loss
+ * L1).  Launches on `stream`: the Fisher assembly and build of the covariance, k_skel_link_fit_rhs ([-G | -g_x] as K + 1 columns,
+ * the frames' C_n and c_n), k_skel_factor, one forward and one backward substitution per clip, k_skel_link_fit_reduce; one
+ * synchronisation.  Workspace: the pinned covariance workspace, two column buffers [n_clips][17][N][n_active] and the frames'
+ * partials [n_clips N][16][17], 256-byte aligned (ACINO_ERR_WORKSPACE otherwise); the query returns 0 outside the limits. */
+size_t acino_skel_fte_link_fit_workspace_bytes(const acino_skel_fte_params* p, int n_clips, int pin_unobserved);
+int acino_skel_fte_link_fit_system(const acino_skel_fte_params* p, int n_clips, int camera_model, const acino_skel_op* h_ops,
+                                   const int32_t* h_active, const double* d_meas, const double* d_w, const double* d_cams,
+                                   const double* d_lo, const double* d_hi, const double* d_x,
+                                   const int32_t* h_group /* [n_ops] */, int n_groups, double* d_S, double* d_r, double* d_C,
+                                   double* d_c, double* d_cost, double* d_sens /* may be NULL */, double* d_newton /* may be NULL */,
+                                   int32_t* h_status /* [n_clips], may be NULL */, void* d_ws, size_t ws_bytes, void* stream,
+                                   int pin_unobserved, uint8_t* d_unobserved /* [n_clips][n_active], may be NULL */);
+
 /* ---- a generic-skeleton FTE iterate in image space: predicted pixels, their covariance, residuals, gating ----------------
  * Evaluated at the iterate d_x[n_clips][N][n_active] (normally the solution of acino_skel_fte_solve*).  Per entry
  * (b, n, c, l) = (clip, frame, camera, pose slot), the layout of d_meas[n_clips][N][C][n_pose][2] / d_w[n_clips][N][C][n_pose]:
